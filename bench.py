@@ -16,7 +16,8 @@ all-gather that re-assembles the plan batch on every rank.  `value` = converged 
 wall time (max over ranks).  The default line is the TROT (the gait BASELINE.json's metric names); the
 walk of the reference's golden plans is timed right behind it with the same --steps as the `walk` block.
 Behind the W warm-up steps further untimed steps run until three in a row agree to 2 % (--settle, at
-most 50; `warmup_extra` on the line), then EXACTLY K steps are timed.
+most 50; `warmup_extra` on the line), then EXACTLY K steps are timed, on the seeded batches W .. W + K - 1
+(`ms_per_step` = timed region / K).  --dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy.
 
 Extra objects on the JSON line:
   step_ms, step_ms_series, gap_ms_per_step, device_ms_per_step, host_round_trips_per_step ...
@@ -56,6 +57,7 @@ for _k, _v in (("OMP_WAIT_POLICY", "passive"), ("KMP_BLOCKTIME", "0"), ("GOMP_SP
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s
 REF_LOG_PLANS_PER_S = 1.0 / 0.745  # logs/towr_log.out:81-82, unknown CPU -- not this metric's baseline
+DUMP_LIMIT_BYTES = 64 * 10**6      # --dump-outputs: all files together stay below this
 
 
 def parse_args(argv=None):
@@ -128,7 +130,14 @@ def parse_args(argv=None):
     ap.add_argument("--traffic-bytes", type=float, default=None,
                     help="HBM bytes per k_kkt launch from a separate rocprofv3 --pmc pass "
                          "(default: the newest profiles/*_pmc_hbm.json, collected with this same command)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float64): nodes, status, "
+                         "iterations, violation (with --gpus N > 1: nodes / status of the all-gathered batch, iterations / violation of "
+                         "rank 0), and the same for the second leg as <gait>_nodes ...; above %d MB in all, a fixed seeded sample of "
+                         "the plans (row indices in DIR/sample_rows.npy)" % (DUMP_LIMIT_BYTES // 10**6))
     a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.gait is None:
         # the metric's gait on the metric's workload (flat exp_1 goals); the terrain workloads and the 200-knot receding windows keep
         # the walk their goals, schedules (PlannerConfig.knots200) and -m gpu tests are written for
@@ -285,6 +294,28 @@ def golden_parity(Planner, PlannerConfig, device):
     out["note"] = ("P2 (warm start at the reference's plan) meets the 1e-3 m tolerance; from the reference's cold start the "
                    "cost-free NLP returns another feasible plan (P3, centimetres away)")
     return out
+
+
+def dump_outputs(dirname, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every array of `arrays` (name -> numpy array, one row per plan) as DIR/<name>.npy in float64.  If they
+    come to more than `limit` bytes, the same fixed, seeded sample of rows is kept of every array and its indices are written
+    as DIR/sample_rows.npy."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    n = max(a.shape[0] for a in arrays.values())
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(dirname, exist_ok=True)
+    sample_path = os.path.join(dirname, "sample_rows.npy")
+    if total + 128 * len(arrays) > limit:
+        row_bytes = sum(a.itemsize * int(np.prod(a.shape[1:])) for a in arrays.values()) + 8   # (+ the row's index)
+        k = max(1, (limit - 128 * (len(arrays) + 1)) // row_bytes)                              # (128: an .npy header)
+        rows = np.sort(np.random.default_rng(0).choice(n, size=min(k, n), replace=False))
+        arrays = {name: a[rows[rows < a.shape[0]]] for name, a in arrays.items()}
+        arrays["sample_rows"] = rows.astype(np.float64)
+    elif os.path.exists(sample_path):
+        os.remove(sample_path)     # (left by an earlier, larger run: these files are whole)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def percentile(xs, q):
@@ -584,6 +615,9 @@ def main():
         warmup_extra = settle(step, sync, args.settle, args.settle_tol, agree)
     sync()
     state["timed"] = 0
+    # the K timed steps run on batches warmup .. warmup + K - 1 however many steps the adaptive warm-up took: the same inputs run
+    # to run (--dump-outputs compares the last one's plans between builds)
+    state["i"] = args.warmup
     solved_dev.zero_()
     iters_dev.zero_()
     P.totals(reset=True)
@@ -641,6 +675,17 @@ def main():
     sync()
     elapsed = time.perf_counter() - t0
     thr1 = cgroup_throttled()
+    dumped = {}
+    if args.dump_outputs and rank == 0:
+        # what the caller of the timed path holds after its last step (copied to the host now, written after the last timed leg)
+        if lanes:
+            it_last, viol_last = last_lane.iters[:last_lane.n], last_lane.viol[:last_lane.n]
+        elif mpc:
+            it_last, viol_last = torch.cat([Wj.iters for Wj in windows]), torch.cat([Wj.viol for Wj in windows])
+        else:
+            it_last, viol_last = iters, viol
+        dumped = {name: t.cpu().numpy() for name, t in (("nodes", all_nodes), ("status", all_status),
+                                                          ("iterations", it_last), ("violation", viol_last))}
     kkt_s, kkt_n, tot_s, chord_s, chord_n = leg.kkt_s, leg.kkt_n, leg.tot_s, leg.chord_s, leg.chord_n
     if not mpc and not lanes:
         tc, ti = P.totals()
@@ -810,6 +855,7 @@ def main():
         dev_sync()
         extra2 = settle(leg2_step, dev_sync, args.settle, args.settle_tol) if args.settle > 0 else 0
         dev_sync()
+        tstate["i"] = args.warmup      # (the timed steps' batches, as in the first leg)
         Pt.totals(reset=True)
         leg2 = LegTimes()
         thr2 = cgroup_throttled()
@@ -822,6 +868,9 @@ def main():
             leg2.add(Pt, time.perf_counter() - ts, sampled)
         dev_sync()
         tel = time.perf_counter() - tt0
+        if args.dump_outputs:
+            dumped.update({other + "_" + name: t.cpu().numpy() for name, t in (("nodes", nodes_t), ("status", status_t),
+                                                                               ("iterations", iters_t), ("violation", viol_t))})
         tconv, titer = Pt.totals()
         tavg = leg2.kkt_s / max(leg2.kkt_n, 1)
         tag2 = "" if other == "walk" else "trot_"
@@ -862,6 +911,8 @@ def main():
         Pt.close()
     if parity is not None:
         out["parity"] = parity
+    if dumped:
+        dump_outputs(args.dump_outputs, dumped)
     if rank == 0 and world == 1 and args.cpu_sample > 0 and args.workload not in ("mixed", "mpc_random"):
         from oracle.oracle import Oracle, oracle_dict
         O = Oracle(oracle_dict(cfg), height=None if args.workload == "exp1_flat" else terrain[0],
