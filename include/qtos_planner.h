@@ -302,6 +302,56 @@ int qtos_last_timing_detail(QtosPlanner *p, double *out, int n_out);
  * call (default on: bench.py's roofline figure is measured from them).  on = 0 keeps the call's first and last event only -- a
  * caller that does not read kernel times saves the event packets between its kernels; the timing entry points then return -1. */
 int qtos_set_kernel_events(QtosPlanner *p, int on);
+/* Per-solve report (the Ipopt log the reference's ./main prints: iteration table, final measures, evaluation counts).
+ * on != 0: the calls submitted from now on record an iteration history per problem and, behind the call, evaluate the final
+ * measures at the returned iterate (k_report, outside the launch pattern).  A call of one lane (B up to the GPU's compute
+ * units) launches k_report behind its end event, so qtos_last_timing* do not count it; a call cut into lanes launches it
+ * in front of the lanes' join, so its time enters total_seconds there.  k_report rewrites the problems' constraint values
+ * and Jacobian in the workspace with those of the returned iterate: the qtos_debug_read_* readers see that linearisation
+ * after a call with the report on.  The flag is latched per call at submit; returns -5 while a call is open (between
+ * qtos_plan_submit and the end of qtos_plan_wait). */
+int qtos_set_report(QtosPlanner *p, int on);
+
+/* History record of one iteration (qtos_plan_report `rows`, QTOS_HIST_COLS doubles per row, row i = iteration i). */
+#define QTOS_HIST_COLS 10
+enum {
+  QTOS_H_INF_PR = 0,  /* max violation of the working rows (qtos_debug_trace column 0)                     */
+  QTOS_H_THETA,       /* max |c_i - s|, |c_e| (trace column 1)                                           */
+  QTOS_H_MU,          /* barrier parameter after the step (trace column 3)                               */
+  QTOS_H_DNORM,       /* max |dx| of the step's direction, node space (the step applied is alpha_pr times it) */
+  QTOS_H_ALPHA_PR,    /* primal step length (trace column 2; 0 for a discarded chord step)               */
+  QTOS_H_ALPHA_DU,    /* step length of the bound multipliers z (y comes whole from the KKT solve)       */
+  QTOS_H_LS,          /* line-search trials (constraint evaluations) of the step; 0 in row 0             */
+  QTOS_H_KIND,        /* 0 Newton step, 1 chord step, 2 discarded chord step                             */
+  QTOS_H_COMPL,       /* max over inequality rows of |(s - l) z_l|, |(u - s) z_u|                        */
+  QTOS_H_INF_DU       /* max |Je' y + Ji' (z_u - z_l)| over the KKT system's unknowns; in the
+                         last row formed by k_report at the RETURNED iterate (for a stalled or failed problem the restored
+                         best one, with the last iterate's s, z and y) while the row's other columns are the last iterate's */
+};
+
+/* Final report of problem b of the last call made with the report on. */
+typedef struct QtosReport {
+  int status;                  /* 0 converged, 1 out of iterations / stalled / jammed, 2 numerical failure       */
+  int iterations;
+  int n_rows;                  /* history rows: iterations + 1                                                    */
+  int n_con_evals;             /* constraint evaluations: the starting point + every line-search trial            */
+  int n_jac_evals;             /* Jacobian evaluations: the starting point + one per step the solve went on from  */
+  int n_factorizations;        /* KKT solves with a fresh factorisation (Newton steps)                            */
+  int n_chord_solves;          /* KKT solves with the stored factorisation (chord steps, discarded ones included) */
+  int pad;
+  double constraint_violation; /* at the returned iterate                                                         */
+  double dual_infeasibility;
+  double complementarity;
+  double nlp_error;            /* max of the three (objective zero, Ipopt's scaling s_d = 1)                      */
+} QtosReport;
+/* Host pointers.  rows (may be null): up to max_rows history records of QTOS_HIST_COLS doubles.  Returns the number of
+ * history rows (iterations + 1), -1 on bad arguments, -6 if the last call ran without the report or b is outside it. */
+int qtos_plan_report(QtosPlanner *p, int b, QtosReport *out, double *rows, int max_rows);
+/* Host-only: counts the Ipopt header prints that QtosDims lacks, from the host model of the full system (reduce_base = 0,
+ * reduce_swing = 0): counts[0] / [1] structural nonzeros of the equality / inequality constraint Jacobian over the free
+ * variables.  Returns the number written (min(n, 2)) or < 0. */
+int qtos_analyze_counts(const QtosParams *params, long long *counts, int n);
+
 /* The same for the chord-step launches (k_chord, QtosParams.chord_tol) of the last call. */
 int qtos_last_timing_chord(QtosPlanner *p, double *chord_seconds, int *chord_launches);
 /* Running totals over all qtos_plan_batch* calls of the handle since the last reset: problems returned with
@@ -355,6 +405,11 @@ int qtos_debug_initial_guess(QtosPlanner *p, int B, const double *start, const d
 /* per-iteration trace of the last plan call for problem b: rows of (viol, theta, alpha, mu),
  * at most max_iter rows; returns the number of rows */
 int qtos_debug_trace(QtosPlanner *p, int b, double *trace_out);
+/* final primal-dual state of problems 0 .. B-1 of the last plan call, by constraint row (n_cons doubles per problem and
+ * array): slacks s, bound multipliers z_l, z_u (zero on rows that are not inequality rows of the working set) and the
+ * equality multipliers y of the last KKT solve (zero for dropped rows and rows a reduction eliminated).  Any array may be
+ * null. */
+int qtos_debug_duals(QtosPlanner *p, int B, double *s, double *zl, double *zu, double *y);
 /* What this build of the library contains: bit 0 = the kernels that were built, measured and lost (k_kkt3 MODE 0, k_kkt4,
  * the Kronecker assembly: -DQTOS_EXPERIMENTS, scratch/build.sh), bit 1 = per-wave cycle stamps (-DQTOS_STAMPS),
  * bit 2 = a development build with the benchmark's fronts only (-DQTOS_DEV_F128).  The product library returns 0. */

@@ -53,6 +53,20 @@ class QtosDims(C.Structure):
     ]
 
 
+HIST_COLS = 10   # QTOS_HIST_COLS: one record of the iteration history (qtos_plan_report)
+HIST_NAMES = ("inf_pr", "theta", "mu", "dnorm", "alpha_pr", "alpha_du", "ls", "kind", "compl", "inf_du")
+
+
+class QtosReport(C.Structure):
+    _fields_ = [
+        ("status", C.c_int), ("iterations", C.c_int), ("n_rows", C.c_int),
+        ("n_con_evals", C.c_int), ("n_jac_evals", C.c_int), ("n_factorizations", C.c_int), ("n_chord_solves", C.c_int),
+        ("pad", C.c_int),
+        ("constraint_violation", C.c_double), ("dual_infeasibility", C.c_double), ("complementarity", C.c_double),
+        ("nlp_error", C.c_double),
+    ]
+
+
 EXPORTS = [
     "qtos_planner_create", "qtos_planner_destroy", "qtos_planner_dims", "qtos_last_error",
     "qtos_set_heightfields", "qtos_plan_batch", "qtos_plan_batch_device", "qtos_sample_csv",
@@ -63,7 +77,7 @@ EXPORTS = [
     "qtos_plan_submit", "qtos_plan_poll", "qtos_plan_wait", "qtos_set_speculation", "qtos_debug_residual", "qtos_project_nodes",
     "qtos_debug_stream_len", "qtos_debug_read_stream", "qtos_debug_read_rhs", "qtos_build_flags", "qtos_kkt_kernel",
     "qtos_last_timing_detail", "qtos_set_pattern_speculation", "qtos_env", "qtos_analyze_two_ended", "qtos_analyze_order", "qtos_set_kernel_events",
-    "qtos_write_csv",
+    "qtos_write_csv", "qtos_set_report", "qtos_plan_report", "qtos_analyze_counts", "qtos_debug_duals",
 ]
 
 _lib = None
@@ -144,6 +158,12 @@ def load():
     if hasattr(lib, "qtos_shift_warm"):   # (absent from older builds loaded through QTOS_LIB for A/B timing)
         lib.qtos_shift_warm.argtypes = [vp, C.c_int, dp, dp, dp, dp, ip, dp]
         lib.qtos_shift_warm_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(lib, "qtos_set_report"):   # (the per-solve report; older builds loaded through QTOS_LIB lack it)
+        lib.qtos_set_report.argtypes = [vp, C.c_int]
+        lib.qtos_plan_report.argtypes = [vp, C.c_int, C.POINTER(QtosReport), dp, C.c_int]
+        lib.qtos_debug_duals.argtypes = [vp, C.c_int, dp, dp, dp, dp]
+    if hasattr(lib, "qtos_analyze_counts"):
+        lib.qtos_analyze_counts.argtypes = [C.POINTER(QtosParams), C.POINTER(C.c_longlong), C.c_int]
     _lib = lib
     return lib
 
@@ -222,6 +242,19 @@ def analyze(cfg):
     if rc != 0:
         raise ValueError("qtos_analyze failed (%d)" % rc)
     return d, act[:d.n_stages].copy()
+
+
+def analyze_counts(cfg):
+    """Host-only: (nonzeros of the equality, of the inequality constraint Jacobian) of the full system, the counts the
+    Ipopt header prints (qtos_analyze_counts).  None with a library that lacks the entry point."""
+    lib = load()
+    if not hasattr(lib, "qtos_analyze_counts"):
+        return None
+    p = params_from_config(cfg)
+    c = (C.c_longlong * 2)()
+    if lib.qtos_analyze_counts(C.byref(p), c, 2) != 2:
+        raise ValueError("qtos_analyze_counts failed")
+    return int(c[0]), int(c[1])
 
 
 def analyze_order(cfg):
@@ -358,6 +391,32 @@ class Planner:
     def set_kernel_events(self, on):
         """Per-kernel HIP events (what timing() / timing_detail() read) on / off; off = the call's first and last event only."""
         self._chk(self.lib.qtos_set_kernel_events(self.h, int(bool(on))), "set_kernel_events")
+
+    def has_report(self):
+        return hasattr(self.lib, "qtos_set_report")
+
+    def set_report(self, on):
+        """Per-solve report (iteration history + final measures) for the calls submitted from now on; raises while a call is
+        open (the flag is latched per call)."""
+        if not self.has_report():
+            raise RuntimeError("this build of the planner library has no per-solve report (qtos_set_report)")
+        self._chk(self.lib.qtos_set_report(self.h, int(bool(on))), "set_report")
+
+    def report(self, b):
+        """(QtosReport, history rows [n_rows, HIST_COLS]) of problem b of the last call made with the report on."""
+        r = QtosReport()
+        rows = np.zeros((self.cfg.max_iter + 1, HIST_COLS))
+        n = self.lib.qtos_plan_report(self.h, int(b), C.byref(r), _dp(rows), rows.shape[0])
+        if n < 0:
+            raise RuntimeError("plan_report failed (%d): %s" % (n, self.lib.qtos_last_error(self.h).decode()))
+        return r, rows[:n].copy()
+
+    def duals(self, B):
+        """(s, z_l, z_u, y) by constraint row of problems 0 .. B-1 of the last call (qtos_debug_duals)."""
+        m = self.dims.n_cons
+        out = [np.zeros((B, m)) for _ in range(4)]
+        self._chk(self.lib.qtos_debug_duals(self.h, B, *[_dp(a) for a in out]), "qtos_debug_duals")
+        return tuple(out)
 
     def env(self):
         """The environment switches the handle runs with (read once at creation), as a dict of strings."""

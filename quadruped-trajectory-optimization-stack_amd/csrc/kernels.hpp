@@ -165,7 +165,26 @@ struct DevWork {
   double *nodes_out, *viol_out;
   int *status_out, *iters_out;
   unsigned long long *totals;
+  // per-solve report (qtos_set_report), latched per call at submit: null when the call runs without it (every branch on it is
+  // uniform).  hist: (max_iter + 1) records of HIST_COLS doubles per problem; rep: REP_COLS doubles per problem (k_report)
+  double *hist, *rep;
 };
+
+// one record of the iteration history (W.hist), iteration 0 written by k_start, iteration i by the k_step that took step i
+enum HistCol {
+  H_INF_PR = 0,  // max violation of the working rows (= the trace's viol)
+  H_THETA,       // max |c_i - s| and |c_e| (= the trace's theta)
+  H_MU,          // barrier parameter after the step
+  H_DNORM,       // max |dx| of the direction the step went along (node space; the applied step is alpha_pr times it)
+  H_ALPHA_PR,    // primal step length (0 for a discarded chord step)
+  H_ALPHA_DU,    // step length of the bound multipliers z (the planner has no separate step for y: the KKT solve gives y whole)
+  H_LS,          // line-search trials (constraint evaluations of the step)
+  H_KIND,        // 0 Newton step (fresh factorisation), 1 chord step, 2 discarded chord step; iteration 0: 0
+  H_COMPL,       // max over inequality rows of |(s - l) z_l|, |(u - s) z_u|
+  H_INF_DU,      // max over the KKT system's unknowns of |Je' y + Ji' (z_u - z_l)| at the iterate (NaN: not formed, see k_report)
+  HIST_COLS
+};
+enum RepCol { R_VIOL = 0, R_INF_DU, R_COMPL, R_ERR, REP_COLS };
 
 // ---- tiny forward-mode dual (one tangent) for the rotation-dependent Jacobians ---------------
 struct D1 {
@@ -759,6 +778,58 @@ __device__ inline double l1_infeasibility(const DevPlan &P, const double *__rest
   return wg_reduce<0>(t, scratch);
 }
 
+// dual infeasibility of the working system: max over the KKT system's variable unknowns p of |(Je' y + Ji' (z_u - z_l))_p|,
+// with the Jacobian entries of the linearisation in the stream Gs (solver coordinates: B-spline coefficients and the reduced
+// swings' footholds where those reductions are on) and y the multipliers of the last KKT solve by unknown position (sol; null:
+// y = 0).  The lists are those of the chord step's right-hand side (Ji' w) and of k_residual (the equality part of K).
+__device__ inline double dual_infeasibility(const DevPlan &P, const double *__restrict__ Gs, const double *__restrict__ zl,
+                                            const double *__restrict__ zu, const double *__restrict__ sol, double *scratch) {
+  double r = 0.0;
+  for (int p = threadIdx.x; p < P.n_unknowns; p += blockDim.x) {
+    const int t0 = P.rhs_ptr[p], t1 = P.rhs_ptr[p + 1];
+    if (t1 - t0 == 1 && P.rhs_gpos[t0] < 0) continue;   // a multiplier
+    // (a list entry is two dependent memory round trips -- index, then value --: DU entries go in flight together and are
+    //  summed in list order)
+    constexpr int DU = 8;
+    double acc = 0.0;
+    for (int t = t0; t < t1; t += DU) {
+      int gp[DU], rw[DU];
+#pragma unroll
+      for (int u = 0; u < DU; ++u) { const int tt = min(t + u, t1 - 1); gp[u] = P.rhs_gpos[tt]; rw[u] = P.rhs_row[tt]; }
+      double gv[DU], zv[DU];
+#pragma unroll
+      for (int u = 0; u < DU; ++u) { gv[u] = Gs[gp[u]]; zv[u] = zu[rw[u]] - zl[rw[u]]; }
+#pragma unroll
+      for (int u = 0; u < DU; ++u) acc = t + u < t1 ? fma(gv[u], zv[u], acc) : acc;
+    }
+    if (sol) {
+      const int e0 = P.kx_ptr[p], e1 = P.kx_ptr[p + 1];
+      for (int e = e0; e < e1; e += DU) {
+        int cc[DU], kp[DU];
+#pragma unroll
+        for (int u = 0; u < DU; ++u) { const int ee = min(e + u, e1 - 1); cc[u] = P.kx_col[ee]; kp[u] = P.kx_pos[ee]; }
+        int c0[DU], c1[DU];
+        double kv[DU], sv[DU];
+#pragma unroll
+        for (int u = 0; u < DU; ++u) { c0[u] = P.rhs_ptr[cc[u]]; c1[u] = P.rhs_ptr[cc[u] + 1]; kv[u] = Gs[kp[u]]; sv[u] = sol[cc[u]]; }
+        bool mult[DU];
+#pragma unroll
+        for (int u = 0; u < DU; ++u) mult[u] = e + u < e1 && c1[u] - c0[u] == 1 && P.rhs_gpos[c0[u]] < 0;   // (a multiplier's column)
+#pragma unroll
+        for (int u = 0; u < DU; ++u) acc = mult[u] ? fma(kv[u], sv[u], acc) : acc;
+      }
+    }
+    r = acc == acc ? fmax(r, fabs(acc)) : INFINITY;
+  }
+  return wg_reduce<1>(r, scratch);
+}
+
+// max over the inequality rows of |(s - l) z_l|, |(u - s) z_u| (rows whose value is a NaN give inf)
+__device__ __forceinline__ double compl_row(double l, double u, double s, double zl, double zu) {
+  const double a = l > -1e19 ? fabs((s - l) * zl) : 0.0, c = u < 1e19 ? fabs((u - s) * zu) : 0.0;
+  return (a == a && c == c) ? fmax(a, c) : INFINITY;
+}
+
 __device__ inline void record_trace(const DevPlan &P, const DevWork &W, int b, int it, double viol,
                                     double theta, double al, double mu) {
   if (W.trace && it < P.max_iter + 1) {
@@ -924,6 +995,14 @@ __global__ __launch_bounds__(ET) void k_start(DevPlan P, DevWork W, int B) {
     zl[r] = l > -1e19 ? mu / (s[r] - l) : 0.0;
     zu[r] = u < 1e19 ? mu / (u - s[r]) : 0.0;
   }
+  double h_compl = 0.0, h_du = 0.0;   // report on: the history's measures of the starting point (no KKT solve yet: y = 0)
+  if (W.hist) {
+    __syncthreads();
+    double c = 0.0;
+    for (int i = tid; i < P.n_iq; i += blockDim.x) { const int r = P.iq_idx[i]; c = fmax(c, compl_row(P.iq_lo[i], P.iq_hi[i], s[r], zl[r], zu[r])); }
+    h_compl = wg_reduce<1>(c, scratch);
+    h_du = dual_infeasibility(P, W.stream + (size_t)b * P.stream_len, zl, zu, nullptr, scratch);
+  }
   const bool conv = viol <= P.tol && theta <= P.tol;
   const bool bad = !(viol < INFINITY) || !(theta < INFINITY);   // NaN / inf in the inputs
   if (tid == 0) {
@@ -940,6 +1019,11 @@ __global__ __launch_bounds__(ET) void k_start(DevPlan P, DevWork W, int B) {
     W.jam[b] = 0;
     if (!conv && !bad && P.max_iter > 0) atomicAdd(W.n_active, 1);
     record_trace(P, W, b, 0, viol, theta, 0.0, mu);
+    if (W.hist) {
+      double *h = W.hist + (size_t)b * (P.max_iter + 1) * HIST_COLS;
+      for (int c = 0; c < HIST_COLS; ++c) h[c] = 0.0;
+      h[H_INF_PR] = viol; h[H_THETA] = theta; h[H_MU] = mu; h[H_COMPL] = h_compl; h[H_INF_DU] = h_du;
+    }
   }
   if (conv || bad || P.max_iter <= 0) {
     __syncthreads();   // (x of the other threads)
@@ -1429,7 +1513,9 @@ __global__ __launch_bounds__(ET) void k_step(DevPlan P, DevWork W, int B, int sl
   double al = amax, th = 0;
   double rgt[KR], egt[KE];
   bool lin_done = false;   // g and the stream hold the linearisation at the accepted point already
+  int n_trials = 0;
   for (int ls = 0; ls < 6; ++ls) {
+    ++n_trials;
     // the trial point goes to LDS directly (and stays there for the linearisation below if it is accepted): written to
     // memory and staged back it would cost two memory round trips
     for (int v = tid; v < n; v += blockDim.x) evl[v] = x[v] + al * dx[v];
@@ -1525,6 +1611,17 @@ __global__ __launch_bounds__(ET) void k_step(DevPlan P, DevWork W, int B, int sl
     theta = wg_reduce<1>(t, scratch);
   }
   KSTAMP(3);
+  double h_dn = 0.0, h_cp = 0.0;   // report on: max |dx| of the direction and the complementarity of the new iterate
+  if (W.hist) {
+    double d = 0.0, c = 0.0;
+    for (int v = tid; v < n; v += nt) { const double a = fabs(dx[v]); d = a == a ? fmax(d, a) : INFINITY; }
+#pragma unroll
+    for (int k = 0; k < KR; ++k)
+      if (tid + k * nt < P.n_iq) c = fmax(c, compl_row(rl[k], ru[k], rs[k], rzl[k], rzu[k]));
+    for (int i = tid + KR * nt; i < P.n_iq; i += nt) { const int r = P.iq_idx[i]; c = fmax(c, compl_row(P.iq_lo[i], P.iq_hi[i], s[r], zl[r], zu[r])); }
+    h_dn = wg_reduce<1>(d, scratch);
+    h_cp = wg_reduce<1>(c, scratch);
+  }
   const bool conv = viol <= P.tol && theta <= P.tol;
   const bool bad = !(viol < INFINITY) || !(th < INFINITY);
   // stall detection: the iterate with the lowest violation is kept; a problem that has not improved
@@ -1548,6 +1645,11 @@ __global__ __launch_bounds__(ET) void k_step(DevPlan P, DevWork W, int B, int sl
     W.jam[b] = jam;
     if (improved) { W.best_viol[b] = viol; W.best_it[b] = it + 1; }
     record_trace(P, W, b, it + 1, viol, theta, al, mu);
+    if (W.hist) {
+      double *h = W.hist + ((size_t)b * (P.max_iter + 1) + it + 1) * HIST_COLS;
+      h[H_INF_PR] = viol; h[H_THETA] = theta; h[H_MU] = mu; h[H_DNORM] = h_dn; h[H_ALPHA_PR] = al; h[H_ALPHA_DU] = az;
+      h[H_LS] = n_trials; h[H_KIND] = was_chord ? (reject ? 2 : 1) : 0; h[H_COMPL] = h_cp; h[H_INF_DU] = NAN;
+    }
     if (conv || bad || stalled) W.status[b] = conv ? 0 : (bad ? 2 : 1);
     if (conv || bad || stalled || it + 1 >= P.max_iter) {   // (out of iterations: the status k_start gave, 1)
       W.done[b] = 1;
@@ -1627,6 +1729,11 @@ __global__ __launch_bounds__(ET) void k_step(DevPlan P, DevWork W, int B, int sl
     }
   }
   KSTAMP(5);
+  if (W.hist) {   // the dual infeasibility at the new iterate, with its linearisation and this step's y (a finished problem: k_report)
+    __syncthreads();
+    const double du = dual_infeasibility(P, W.stream + (size_t)b * P.stream_len, zl, zu, W.sol + (size_t)b * P.n_stages * PIV, scratch);
+    if (tid == 0) W.hist[((size_t)b * (P.max_iter + 1) + it + 1) * HIST_COLS + H_INF_DU] = du;
+  }
   if (tid == 0) {
     W.chord[b] = next_chord ? 1 : (chord_off ? 2 : 0);
     W.chord_run[b] = next_chord ? (was_chord ? chord_run + 1 : 1) : 0;
@@ -1684,6 +1791,44 @@ __global__ __launch_bounds__(ET) void k_step(DevPlan P, DevWork W, int B, int sl
 #ifdef QTOS_STAMPS
   if (tid == 0 && W.trace && it == 1) for (int i = 0; i < 8; ++i) W.trace[((size_t)b * (P.max_iter + 1) + 70) * 4 + i] = (double)ks[i];
 #endif
+}
+
+// =================================================================================================
+// k_report (qtos_set_report): the final measures of every problem at the iterate the call returned (W.x: the restored best
+// iterate of a stalled or failed problem), launched once behind a call with the report on, outside its launch pattern.
+// Constraints and Jacobian are evaluated afresh; s, z are those of the last iterate, y that of the last KKT solve (none
+// when the problem took no step).  rep: violation, dual infeasibility, complementarity, overall NLP error (their max: the
+// objective is zero and the scaling s_d of Ipopt's error is 1).  The history's last record gets the dual infeasibility when
+// k_step left it unformed (the step that finished the problem builds no linearisation).
+__global__ __launch_bounds__(ET) void k_report(DevPlan P, DevWork W, int B) {
+  const int b = blockIdx.x;
+  if (b >= B) return;
+  __shared__ double scratch[ET];
+  extern __shared__ double evl[];
+  const int n = P.n_vars, m = P.n_cons, tid = threadIdx.x;
+  const double *x = W.x + (size_t)b * n;
+  double *g = W.g + (size_t)b * m, *Gs = W.stream + (size_t)b * P.stream_len;
+  const double *s = W.s + (size_t)b * m, *zl = W.zl + (size_t)b * m, *zu = W.zu + (size_t)b * m;
+  const int map = W.map_id ? W.map_id[b] : 0, iters = W.iters[b];
+  for (int v = tid; v < n; v += blockDim.x) evl[v] = x[v];
+  __syncthreads();
+  eval_all<true>(P, map, nullptr, g, Gs, evl, nullptr, W.held[b]);
+  __syncthreads();
+  double viol, theta;
+  infeasibility(P, g, s, scratch, viol, theta);
+  double c = 0.0;
+  for (int i = tid; i < P.n_iq; i += blockDim.x) { const int r = P.iq_idx[i]; c = fmax(c, compl_row(P.iq_lo[i], P.iq_hi[i], s[r], zl[r], zu[r])); }
+  const double compl_ = wg_reduce<1>(c, scratch);
+  const double du = dual_infeasibility(P, Gs, zl, zu, iters > 0 ? W.sol + (size_t)b * P.n_stages * PIV : nullptr, scratch);
+  if (tid == 0) {
+    double *r = W.rep + (size_t)b * REP_COLS;
+    r[R_VIOL] = viol; r[R_INF_DU] = du; r[R_COMPL] = compl_;
+    r[R_ERR] = (viol == viol && du == du && compl_ == compl_) ? fmax(viol, fmax(du, compl_)) : NAN;
+    if (W.hist && iters <= P.max_iter) {
+      double *h = W.hist + ((size_t)b * (P.max_iter + 1) + iters) * HIST_COLS;
+      if (!(h[H_INF_DU] == h[H_INF_DU])) h[H_INF_DU] = du;
+    }
+  }
 }
 
 // =================================================================================================

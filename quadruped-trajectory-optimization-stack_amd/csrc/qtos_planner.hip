@@ -71,6 +71,9 @@ struct QtosPlanner {
   std::vector<Lane> lanes;
   int lanes_used = 1, lane_chunk = 256;      // lanes of the call in flight; problems per lane above which a call is cut (the GPU's compute units)
   bool call_open = false;
+  // per-solve report (qtos_set_report): the flag, and what the last call latched of it (qtos_plan_report)
+  bool report = false, last_report = false;
+  int last_B = 0;
   unsigned seq = 0;                          // sequence number of the call in flight, stamped into the count words (k_post_counts)
   hipStream_t call_stream = nullptr;
   hipEvent_t ev_in = nullptr;                // the caller's stream at submit time: the other lanes start behind it
@@ -682,6 +685,7 @@ int qtos_planner_create(const QtosParams *params, int max_batch, int device, Qto
   if (M.P.max_iter < 79) { p->err = "diagnostic build (QTOS_STAMPS) parks its stamps in trace rows 16..79: create the planner with max_iter >= 79"; fprintf(stderr, "qtos: %s\n", p->err.c_str()); qtos_planner_destroy(p); return -1; }
 #endif
   TRY(p->alloc(&W.trace, Bm * (size_t)(M.P.max_iter + 1) * 4));
+  TRY(p->alloc(&W.hist, Bm * (size_t)(M.P.max_iter + 1) * HIST_COLS)); TRY(p->alloc(&W.rep, Bm * (size_t)REP_COLS));
   TRY(p->alloc(&W.status, Bm)); TRY(p->alloc(&W.iters, Bm)); TRY(p->alloc(&W.done, Bm));
   TRY(p->alloc(&W.n_active, 4 * 4));   // four counters per lane
   TRY(p->alloc(&W.chord, Bm));
@@ -983,6 +987,7 @@ static DevWork work_slice(const QtosPlanner *p, const DevWork &w, int b0, int *n
   off(s.chord, 1); off(s.chord_run, 1); off(s.jam, 1); off(s.rhs, (size_t)p->S.n_unknowns); off(s.minv, NS * PIV * PIV);
   off(s.sol, NS * PIV); off(s.sol0, NS * PIV); off(s.dx0, ns); off(s.ur, m);
   off(s.nodes_out, n); off(s.viol_out, 1); off(s.status_out, 1); off(s.iters_out, 1);
+  off(s.hist, ((size_t)p->dp.max_iter + 1) * HIST_COLS); off(s.rep, REP_COLS);
   s.n_active = n_active;
   return s;
 }
@@ -1009,6 +1014,10 @@ int qtos_plan_submit(QtosPlanner *p, int B, const double *d_start, const double 
   // (the kernel that finishes a problem writes its result: kernels.hpp export_problem)
   W.nodes_out = d_nodes_out; W.status_out = d_status_out; W.iters_out = d_iters_out; W.viol_out = d_viol_out;
   W.totals = (unsigned long long *)p->d_totals;
+  // the report is latched here for the whole call: without it the kernels see null pointers (no history, no k_report)
+  if (!p->report) { W.hist = nullptr; W.rep = nullptr; }
+  p->last_report = p->report;
+  p->last_B = B;
   const DevPlan &D = p->dp;
 #define SUBCHK(call_) do { hipError_t e_ = (call_); if (e_ != hipSuccess) { p->err = std::string(#call_) + ": " + hipGetErrorString(e_); return fail(e_ == hipErrorOutOfMemory ? -3 : -2); } } while (0)
   // parts: one lane up to the GPU's compute units, then as many lanes as there are (equal parts)
@@ -1117,6 +1126,11 @@ int qtos_plan_poll(QtosPlanner *p, int *done) {
     bool lane_done = false;
     if (int rc = advance_lane(p, c, &lane_done, &device_set)) return fail(rc);
     if (!lane_done) { ++n_open; continue; }
+    if (c.W.rep) {   // report on: the final measures of the lane's problems, behind the lane's last launch and its end event
+      if (!device_set) { if (hipSetDevice(p->device) != hipSuccess) return fail(-2); device_set = true; }
+      hipLaunchKernelGGL(k_report, dim3(c.B), dim3(ET), p->eval_lds, c.st, p->dp, c.W, c.B);
+      if (hipGetLastError() != hipSuccess) return fail(-2);
+    }
     if (j > 0) {   // the caller's stream waits for the part that ran beside it
       if (!device_set) { if (hipSetDevice(p->device) != hipSuccess) return fail(-2); device_set = true; }
       if (hipEventRecord(c.ev_done, c.st) != hipSuccess || hipStreamWaitEvent(p->call_stream, c.ev_done, 0) != hipSuccess) return fail(-2);
@@ -1294,6 +1308,62 @@ int qtos_last_timing_detail(QtosPlanner *p, double *out, int n_out) {
   out[8] = (double)p->n_pattern_calls; out[9] = (double)p->n_pattern_misses;
   if (n_out >= 14) { out[10] = kkt_s; out[11] = kkt_n; out[12] = chord_s; out[13] = chord_n; }
   return 0;
+}
+
+static_assert(HIST_COLS == QTOS_HIST_COLS && H_INF_DU == QTOS_H_INF_DU && H_KIND == QTOS_H_KIND, "history layout: kernels.hpp and the header");
+
+int qtos_set_report(QtosPlanner *p, int on) {
+  if (!p) return -1;
+  if (p->call_open || p->busy.load()) { p->err = "qtos_set_report: a call is open (the flag is latched per call at submit)"; return -5; }
+  p->report = on != 0;
+  return 0;
+}
+
+int qtos_plan_report(QtosPlanner *p, int b, QtosReport *out, double *rows, int max_rows) {
+  if (!p || !out || b < 0 || (rows && max_rows < 0)) return -1;
+  if (!p->last_report || b >= p->last_B) { p->err = "qtos_plan_report: the last call ran without the report, or b is outside it"; return -6; }
+  if (p->call_open) return -5;
+  HIPCHK(p, hipSetDevice(p->device));
+  HIPCHK(p, hipStreamSynchronize(p->last_stream));   // (k_report runs behind the call's end event)
+  const int stride = p->M.P.max_iter + 1;
+  int st = 0, it = 0;
+  double rep[REP_COLS];
+  std::vector<double> h((size_t)stride * HIST_COLS);
+  HIPCHK(p, hipMemcpy(&st, p->wk.status + b, sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(p, hipMemcpy(&it, p->wk.iters + b, sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(p, hipMemcpy(rep, p->wk.rep + (size_t)b * REP_COLS, sizeof(rep), hipMemcpyDeviceToHost));
+  HIPCHK(p, hipMemcpy(h.data(), p->wk.hist + (size_t)b * stride * HIST_COLS, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+  const int n_rows = std::min(it + 1, stride);
+  std::memset(out, 0, sizeof(*out));
+  out->status = st; out->iterations = it; out->n_rows = n_rows;
+  out->n_con_evals = 1; out->n_jac_evals = 1;
+  for (int i = 1; i < n_rows; ++i) {
+    const double *r = h.data() + (size_t)i * HIST_COLS;
+    out->n_con_evals += (int)r[H_LS];
+    if (r[H_KIND] == 0) out->n_factorizations++; else out->n_chord_solves++;
+    if (i + 1 < n_rows) out->n_jac_evals++;   // (the step that finished the solve needs no linearisation)
+  }
+  out->constraint_violation = rep[R_VIOL]; out->dual_infeasibility = rep[R_INF_DU];
+  out->complementarity = rep[R_COMPL]; out->nlp_error = rep[R_ERR];
+  if (rows && max_rows > 0) std::memcpy(rows, h.data(), (size_t)std::min(n_rows, max_rows) * HIST_COLS * sizeof(double));
+  return n_rows;
+}
+
+int qtos_analyze_counts(const QtosParams *params, long long *counts, int n) {
+  if (!params || !counts || n < 0) return -1;
+  QtosParams full = *params;
+  full.reduce_base = 0; full.reduce_swing = 0;
+  HostModel M;
+  if (M.build(full)) { fprintf(stderr, "qtos: %s\n", M.err.c_str()); return -1; }
+  long long nz[2] = {0, 0};
+  for (const Block &blk : M.blocks)
+    for (int r = 0; r < blk.m; ++r) {
+      const int row = blk.row0 + r, k = M.con_lo[row] == M.con_hi[row] ? 0 : 1;
+      for (int a = 0; a < blk.n; ++a) nz[k] += M.is_free(M.block_cols[blk.col_off + a]) ? 1 : 0;
+    }
+  const int k = std::min(n, 2);
+  for (int i = 0; i < k; ++i) counts[i] = nz[i];
+  return k;
 }
 
 int qtos_set_kernel_events(QtosPlanner *p, int on) {
@@ -1764,6 +1834,29 @@ int qtos_debug_factor(QtosPlanner *p, int b, double *panel_out, int *piv_slot_ou
           std::memset(panel_out + ((size_t)k * (F + 1) + 1 + r) * PIV, 0, PIV * sizeof(double));
   }
   if (piv_slot_out) std::memcpy(piv_slot_out, p->S.piv_slot.data(), p->S.piv_slot.size() * sizeof(int));
+  return 0;
+}
+
+int qtos_debug_duals(QtosPlanner *p, int B, double *s, double *zl, double *zu, double *y) {
+  if (!p || B < 1 || B > p->max_batch) return -1;
+  HIPCHK(p, hipSetDevice(p->device));
+  HIPCHK(p, hipStreamSynchronize(p->last_stream));
+  const size_t m = p->M.n_cons, NP = (size_t)p->S.n_stages * PIV;
+  if (s) HIPCHK(p, hipMemcpy(s, p->wk.s, (size_t)B * m * sizeof(double), hipMemcpyDeviceToHost));
+  if (zl) HIPCHK(p, hipMemcpy(zl, p->wk.zl, (size_t)B * m * sizeof(double), hipMemcpyDeviceToHost));
+  if (zu) HIPCHK(p, hipMemcpy(zu, p->wk.zu, (size_t)B * m * sizeof(double), hipMemcpyDeviceToHost));
+  if (y) {
+    std::vector<double> sol((size_t)B * NP);
+    std::vector<int> it(B);
+    HIPCHK(p, hipMemcpy(sol.data(), p->wk.sol, sol.size() * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(p, hipMemcpy(it.data(), p->wk.iters, B * sizeof(int), hipMemcpyDeviceToHost));
+    std::memset(y, 0, (size_t)B * m * sizeof(double));
+    const int n = p->M.n_vars;
+    for (int b = 0; b < B; ++b)
+      if (it[b] > 0)   // (a problem that took no step has no KKT solve of its own)
+        for (int q = 0; q < p->S.n_unknowns; ++q)
+          if (p->S.order[q] >= n) y[(size_t)b * m + (p->S.order[q] - n)] = sol[(size_t)b * NP + q];
+  }
   return 0;
 }
 

@@ -1,7 +1,8 @@
 """Command-line twin of the reference's ``./main``: same argv, same CSV, same exit status.
 
 ``args['scripts']['run']`` of the reference (QTOS/utils.py:17, 'docker exec <id> ./main') can be
-pointed at ``python -m qtos_amd.main --out build/traj.csv`` unchanged otherwise.
+pointed at ``python -m qtos_amd.main --out build/traj.csv`` unchanged otherwise.  ``--log PATH`` (``-``: stdout) writes
+the per-solve report in the layout of the reference's ``logs/towr_log.out`` (report.py).
 """
 import sys
 
@@ -11,14 +12,16 @@ from .planner import LocalPlanner, TOWR_HEIGHTFIELD
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    out, hf = "build/traj.csv", None
-    for opt in ("--out", "--heightfield"):
+    out, hf, log = "build/traj.csv", None, None
+    for opt in ("--out", "--heightfield", "--log"):
         if opt in argv:
             i = argv.index(opt)
             val = argv[i + 1]
             del argv[i:i + 2]
             if opt == "--out":
                 out = val
+            elif opt == "--log":
+                log = val
             else:
                 hf = val
     args = flags.parse_flags(argv)
@@ -28,8 +31,11 @@ def main(argv=None):
         path = hf or TOWR_HEIGHTFIELD
         if os.path.exists(path):
             lp.load_heightfield_file(path, args.get('-resolution'))
-        status = lp.solve(args, out_csv=out)
-        print("status -> %d" % status)  # the line the reference's log carries (logs/towr_log.out:85)
+        # --log PATH: the per-solve report (report.py) goes to PATH; --log -: to stdout, where it ends with the status line
+        # -- the reference's logs/towr_log.out back from `python -m qtos_amd.main ... --log - > logs/towr_log.out`
+        status = lp.solve(args, out_csv=out, log=sys.stdout if log == "-" else log)
+        if log != "-":
+            print("status -> %d" % status)  # the line the reference's log carries (logs/towr_log.out:85)
         return status
     finally:
         lp.close()

@@ -12,7 +12,7 @@ import os
 
 import numpy as np
 
-from . import capi, csvio, flags, heightfield
+from . import capi, csvio, flags, heightfield, report
 from .config import PlannerConfig
 
 TOWR_HEIGHTFIELD = "./data/heightfields/from_pybullet/towr_heightfield.txt"  # QTOS/utils.py:21-22
@@ -116,9 +116,32 @@ class LocalPlanner:
                          r=[a.get('-r') for a in args_list])
         return statuses
 
-    def solve(self, args, out_csv=TRAJ_OUT):
-        """One plan; writes the CSV where the reference's ``docker cp`` would put it."""
-        status = self.solve_batch([args])[0]
+    def solve(self, args, out_csv=TRAJ_OUT, log=None):
+        """One plan; writes the CSV where the reference's ``docker cp`` would put it.
+
+        log: a path or a writable file object -- the per-solve report (report.py: the layout of the reference's
+        logs/towr_log.out) is switched on for this call and written there.  None: the call runs without it."""
+        if log is None:
+            status = self.solve_batch([args])[0]
+        else:
+            P = self.planner(args.get('-duration'))
+            P.set_report(True)
+            P.set_kernel_events(True)   # (the report's timing lines: the call's measured seconds and those of its KKT solves)
+            try:
+                status = self.solve_batch([args])[0]
+                rep, rows = P.report(0)
+                tm = P.timing()
+            finally:
+                P.set_report(False)
+                P.set_kernel_events(False)
+            text = report.format_report(P.dims, capi.analyze_counts(P.cfg), rep, rows, P.cfg.max_iter,
+                                        seconds=(tm.get("total_seconds", 0.0), tm.get("kkt_seconds", 0.0)))
+            if hasattr(log, "write"):
+                log.write(text)
+                log.flush()
+            else:
+                with open(log, "w") as fh:
+                    fh.write(text)
         if out_csv:
             d = os.path.dirname(out_csv)
             if d:
