@@ -212,7 +212,7 @@ int qtos_plan_batch(QtosPlanner *p, int B, const double *start, const double *go
  * defaults are the measured optimum:
  *   QTOS_KKT=2 | 4 | 6       force the factor + solve kernel: k_kkt2 / k_kkt3 MODE 1 / k_kkt5 (default: k_kkt3 MODE 1 for fronts of up
  *                            to 112 slots, k_kkt2 above; see qtos_kkt_kernel below and DESIGN.md section 5).  3 and 5 (k_kkt3 MODE 0,
- *                            k_kkt4) exist in experiment builds only (qtos_build_flags bit 0) and mean "default" elsewhere
+ *                            k_kkt4 of rounds 4 - 5) left the library: a warning on stderr, then the default
  *   QTOS_LANES=n             a call of more problems than the GPU has compute units is cut into up to n (<= 4) contiguous parts,
  *                            each with its own host-driven loop on a stream of the planner; bit-identical plans; default 1
  *                            (measured slower than one lock-step loop at 1024 problems per call)
@@ -410,8 +410,8 @@ int qtos_debug_trace(QtosPlanner *p, int b, double *trace_out);
  * equality multipliers y of the last KKT solve (zero for dropped rows and rows a reduction eliminated).  Any array may be
  * null. */
 int qtos_debug_duals(QtosPlanner *p, int B, double *s, double *zl, double *zu, double *y);
-/* What this build of the library contains: bit 0 = the kernels that were built, measured and lost (k_kkt3 MODE 0, k_kkt4,
- * the Kronecker assembly: -DQTOS_EXPERIMENTS, scratch/build.sh), bit 1 = per-wave cycle stamps (-DQTOS_STAMPS),
+/* What this build of the library contains: bit 0 = the Kronecker assembly of k_kkt2<128> (QTOS_KRON; -DQTOS_EXPERIMENTS,
+ * scratch/build.sh), bit 1 = per-wave cycle stamps (-DQTOS_STAMPS),
  * bit 2 = a development build with the benchmark's fronts only (-DQTOS_DEV_F128).  The product library returns 0. */
 int qtos_build_flags(void);
 /* The factor + solve kernel qtos_planner_create selected for this planner, e.g. "k_kkt2<128>", "k_kkt3<112, 1>",
@@ -422,6 +422,10 @@ int qtos_build_flags(void);
  * pair-mode analysis (fronts 96 .. 144 without continuation records; otherwise the default).  Every choice solves the same
  * KKT systems; plans of different kernels differ by rounding (2e-8 on the walk, up to 5e-6 on the trot). */
 int qtos_kkt_kernel(const QtosPlanner *p, char *buf, int n);
+/* Host-only: the name qtos_kkt_kernel would report for a planner of these parameters created now, under the environment as
+ * it is now (the same choice, no GPU needed); returns the length of the full name, < 0 where qtos_planner_create would fail
+ * in the analysis. */
+int qtos_analyze_kernel(const QtosParams *params, char *buf, int n);
 
 #ifdef __cplusplus
 }

@@ -77,7 +77,7 @@ EXPORTS = [
     "qtos_plan_submit", "qtos_plan_poll", "qtos_plan_wait", "qtos_set_speculation", "qtos_debug_residual", "qtos_project_nodes",
     "qtos_debug_stream_len", "qtos_debug_read_stream", "qtos_debug_read_rhs", "qtos_build_flags", "qtos_kkt_kernel",
     "qtos_last_timing_detail", "qtos_set_pattern_speculation", "qtos_env", "qtos_analyze_two_ended", "qtos_analyze_order", "qtos_set_kernel_events",
-    "qtos_write_csv", "qtos_set_report", "qtos_plan_report", "qtos_analyze_counts", "qtos_debug_duals",
+    "qtos_write_csv", "qtos_set_report", "qtos_plan_report", "qtos_analyze_counts", "qtos_debug_duals", "qtos_analyze_kernel",
 ]
 
 _lib = None
@@ -164,6 +164,8 @@ def load():
         lib.qtos_debug_duals.argtypes = [vp, C.c_int, dp, dp, dp, dp]
     if hasattr(lib, "qtos_analyze_counts"):
         lib.qtos_analyze_counts.argtypes = [C.POINTER(QtosParams), C.POINTER(C.c_longlong), C.c_int]
+    if hasattr(lib, "qtos_analyze_kernel"):
+        lib.qtos_analyze_kernel.argtypes = [C.POINTER(QtosParams), C.c_char_p, C.c_int]
     _lib = lib
     return lib
 
@@ -228,7 +230,7 @@ def params_from_config(cfg):
 
 
 def build_flags():
-    """Bit 0: the library contains the experiment kernels (QTOS_KKT=3 / 5, QTOS_KRON); bit 1: stamps; bit 2: development build."""
+    """Bit 0: the library contains the experiment code (the Kronecker assembly, QTOS_KRON); bit 1: stamps; bit 2: development build."""
     return int(load().qtos_build_flags())
 
 
@@ -255,6 +257,18 @@ def analyze_counts(cfg):
     if lib.qtos_analyze_counts(C.byref(p), c, 2) != 2:
         raise ValueError("qtos_analyze_counts failed")
     return int(c[0]), int(c[1])
+
+
+def analyze_kernel(cfg):
+    """Host-only: the factor + solve kernel a planner created now would select (qtos_analyze_kernel: the name
+    Planner.kkt_kernel would report under the current environment)."""
+    lib = load()
+    p = params_from_config(cfg)
+    buf = C.create_string_buffer(64)
+    n = lib.qtos_analyze_kernel(C.byref(p), buf, 64)
+    if n < 0:
+        raise ValueError("qtos_analyze_kernel failed (%d)" % n)
+    return buf.value.decode()
 
 
 def analyze_order(cfg):

@@ -9,6 +9,7 @@
 // (tests/test_boundary.py compares with Python's "%g" on random values, boundaries and the golden plan); rows are formatted in
 // parallel chunks by a few threads and written with one fwrite.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>

@@ -5,6 +5,7 @@
 // the caller the values the handle actually runs with.  Nothing else in the library calls getenv.  All of these are diagnostics
 // or measured alternatives; the defaults are the measured optimum (include/qtos_planner.h lists what each one does).
 #pragma once
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <string>

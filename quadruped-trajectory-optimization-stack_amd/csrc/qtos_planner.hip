@@ -27,9 +27,12 @@ using namespace qtos;
     }                                                                                         \
   } while (0)
 
-struct QtosPlanner {
-  HostModel M;
-  Symbolic S;
+static constexpr size_t LDS_LIMIT = 160 * 1024 - 256;   // LDS one workgroup of the factor + solve kernels may claim
+enum class Kkt { kkt2, kkt3, kkt5 };                      // the factor + solve kernel (choose_kernel)
+// One host analysis.  Symbolic::build writes into its model (goff, g_doubles, dyn_chunk): a model per variant; moving is safe.
+struct Analysis { HostModel M; Symbolic S; };
+
+struct QtosPlanner : Analysis {   // (the analysis the planner runs: choose_kernel)
   DevPlan dp;
   SamplePlan sp;
   int device = 0, max_batch = 0;
@@ -78,8 +81,7 @@ struct QtosPlanner {
   hipStream_t call_stream = nullptr;
   hipEvent_t ev_in = nullptr;                // the caller's stream at submit time: the other lanes start behind it
   unsigned call_seq = 0;             // sequence number of the last call submitted
-  bool use_kkt3 = false;             // k_kkt3 (kkt3.hpp) instead of k_kkt2: chosen by qtos_planner_create
-  bool use_kkt5 = false;             // k_kkt5 (kkt5.hpp): two stages per set of barriers, Symbolic::pair_mode
+  Kkt kkt = Kkt::kkt2;               // the factor + solve kernel (choose_kernel)
   QtosEnv env;                       // the environment as qtos_planner_create found it (env.hpp; qtos_env reports it)
   int spec_next = 1;                 // blind iterations of the next call: the iterations the last one took
   int spec_cap = 1;                  // limit of the blind iterations (qtos_set_speculation): 1 = off
@@ -193,35 +195,122 @@ static int upload_spline(QtosPlanner *p, const Spline &S, SampleSpline *out) {
   return 0;
 }
 
+// The analysis of an order rule and variant (pair mode, record cap, Kronecker assembly; the default has none): 0, -1 / 1 failed
+static int build_analysis(Analysis &A, const QtosParams &params, const QtosEnv &env, int order_rule, bool pair = false, int cap = 0, bool kron = false) {
+  A = Analysis();
+  A.M.order_rule = order_rule;
+  A.S.env = env; A.S.cell_mode = 2; A.S.pair_mode = pair; A.S.rec_cap_ints = cap; A.S.kron = kron;
+  if (A.M.build(params)) return -1;
+  return A.S.build(A.M) ? 1 : 0;
+}
+static int print_error(const Analysis &A, int rc) { fprintf(stderr, "qtos: %s\n", (rc < 0 ? A.M.err : A.S.err).c_str()); return -1; }
+
 // Which time keys the elimination order uses (model.hpp HostModel::order_rule).  On a reduced base rules 2 and 1 are analysed:
 // the smaller front wins, then the fewer stages, then the order that needs no continuation records, then rule 2.  Rule 0 -- the
 // order of rounds 1 - 5 -- has the smallest front on some short horizons and is NOT in the automatic choice there: its KKT solve
-// loses up to six digits on short trots (model.hpp).  QTOS_ORDER=0 | 1 | 2 forces one.
-static int pick_order_rule(const QtosParams &params, const QtosEnv &env) {
+// loses up to six digits on short trots (model.hpp).  QTOS_ORDER=0 | 1 | 2 forces one.  `won` keeps the winner, the default
+// variant of its rule (`built`), unless the analysis is to talk (QTOS_DEBUG_SYMBOLIC*, QTOS_DUMP_FIRST): the candidates do not.
+static int pick_order_rule(const QtosParams &params, const QtosEnv &env, Analysis &won, bool &built) {
+  built = false;
   if (env.order >= 0) return env.order;
   // (rules 1 and 2 move the B-spline coefficients of the reduced base: without it -- every base row in the system, the
   //  configuration the internals' tests pin -- the order of rounds 1 - 5 stays)
   if (!params.reduce_base) return 0;
+  QtosEnv quiet = env;   // (the candidates do not talk)
+  quiet.debug = 0; quiet.dump_first.clear();
+  Analysis cand;
   int best = 2, best_front = 1 << 30, best_stages = 1 << 30, best_cont = 1 << 30;
   for (int rule : {2, 1}) {
-    HostModel M;
-    Symbolic S;
-    S.env = env;
-    S.env.debug = 0;
-    S.env.dump_first.clear();
-    S.cell_mode = 2;
-    M.order_rule = rule;
-    if (M.build(params) || S.build(M)) continue;
-    if (!M.reduce_base) return 0;   // (the model kept the full base: a short horizon or unequal polynomial durations)
-    int n_cont = 0;
-    for (int k = 0; k < S.n_records; ++k) n_cont += S.srec[S.srec_off[k] + 6];
-    const int cont = n_cont > 0;
+    if (build_analysis(cand, params, quiet, rule)) continue;
+    if (!cand.M.reduce_base) { built = false; return 0; }   // (the model kept the full base: a short horizon or unequal polynomial durations)
+    const Symbolic &S = cand.S;
+    const int cont = S.n_continuation() > 0;
     if (S.front < best_front || (S.front == best_front && (S.n_stages < best_stages || (S.n_stages == best_stages && cont < best_cont)))) {
       best = rule; best_front = S.front; best_stages = S.n_stages; best_cont = cont;
+      std::swap(won, cand);
+      built = true;
     }
   }
   if (env.debug) fprintf(stderr, "qtos: elimination order rule %d (front %d, %d stages)\n", best, best_front, best_stages);
+  built = built && !env.debug && env.dump_first.empty();
   return best;
+}
+
+// What the qtos_analyze* entry points describe: the default variant (kron: Kronecker assembly), whatever a planner would run
+static int analyze_host(const QtosParams &params, const QtosEnv &env, bool kron, Analysis &A) {
+  bool built;
+  const int rule = pick_order_rule(params, env, A, built);
+  const int rc = built && !kron ? 0 : build_analysis(A, params, env, rule, false, 0, kron);
+  return rc ? print_error(A, rc) : 0;
+}
+static size_t kkt_lds_bytes(Kkt k, const Symbolic &S) {
+  switch (k) {
+    case Kkt::kkt5: return kkt5_lds_bytes(S.front, S.n_stages, S.max_srec, S.max_drec, S.n_cells);
+    case Kkt::kkt3: return kkt3_lds_bytes(S.front, S.n_stages, S.max_srec, S.max_drec, S.n_cells);
+    default: return kkt2_lds_bytes(S.front, S.n_stages, S.max_srec, S.max_drec, S.n_cells);
+  }
+}
+// the kernel's name as rocprofv3 lists it (qtos_kkt_kernel, qtos_analyze_kernel)
+static int kkt_kernel_name(Kkt k, const Symbolic &S, char *buf, int n) {
+  const size_t room = buf && n > 0 ? (size_t)n : 0;
+  switch (k) {
+    case Kkt::kkt5: return snprintf(buf, room, "k_kkt5<%d>", S.front);
+    case Kkt::kkt3: return snprintf(buf, room, "k_kkt3<%d, 1>", S.front);
+    default: return snprintf(buf, room, "k_kkt2<%d%s>", S.front, S.n_continuation() > 0 ? ", true" : "");
+  }
+}
+
+// Which factor + solve kernel, and the analysis it runs on; 0, or -1 where the analysis fails.  k_kkt3<F, 1> is the default up
+// to 112 slots (128 once QTOS_KKT is set): k_kkt2's records and arithmetic -- bit-identical plans -- with the assembly on the
+// waves idle in phase AB (-5 % per launch on 112 slots, -6 % on 96, +4 % on 128: profiles/r04_experiments).  k_kkt2 takes the
+// rest, with smaller records (heavy stages spill into continuation records) while they do not fit the LDS next to the panels.
+// QTOS_KKT=6: k_kkt5 on the pair-mode analysis where it applies; 2 forces k_kkt2; 3 and 5 (rounds 4 - 5) left the library.
+static int choose_kernel(const QtosParams &params, const QtosEnv &env, Kkt &kind, Analysis &A) {
+  Analysis def; bool have_def;   // the default variant: the order pick's winner, or built below
+  const int rule = pick_order_rule(params, env, def, have_def);
+  int forced = env.kkt;
+  if (forced == 3 || forced == 5) { fprintf(stderr, "qtos: QTOS_KKT=%d selected an experiment of rounds 4 - 5 that left the library (scratch/experiments/): default kernel\n", forced); forced = 0; }
+  if (forced == 6) {   // (k_kkt5: a front of 96 .. 144 slots, no continuation records, within the LDS)
+    const int rc = build_analysis(A, params, env, rule, true);
+    if (rc < 0) return print_error(A, rc);
+    const Symbolic &S = A.S;
+    const bool ok = rc == 0 && kkt5_kernel(S.front) != nullptr && !(S.pack_src.size() & 1) && S.n_continuation() == 0 && kkt_lds_bytes(Kkt::kkt5, S) <= LDS_LIMIT;
+    if (env.debug) fprintf(stderr, "qtos: k_kkt5 %s (front %d, %s)\n", ok ? "selected" : "not applicable", S.front, S.err.c_str());
+    if (ok) { kind = Kkt::kkt5; return 0; }
+  }
+  const int def_rc = have_def ? 0 : build_analysis(def, params, env, rule);
+  if (def_rc < 0) return print_error(def, def_rc);
+  if (forced != 2) {
+    const Symbolic &S = def.S;
+    const bool ok = def_rc == 0 && S.front <= (forced ? 128 : 112) && !(S.pack_src.size() & 1) && S.n_continuation() == 0 && kkt_lds_bytes(Kkt::kkt3, S) <= LDS_LIMIT;
+    if (env.debug) fprintf(stderr, "qtos: k_kkt3 %s (%s)\n", ok ? "selected" : "not applicable", S.err.c_str());
+    if (ok) { kind = Kkt::kkt3; A = std::move(def); return 0; }
+  }
+  kind = Kkt::kkt2;
+  bool kron = false;   // (experiment builds: Kronecker assembly of the range-of-motion blocks, k_kkt2<128> only)
+#ifdef QTOS_EXPERIMENTS
+  kron = env.kron != 0;
+#endif
+  for (int cap : {0, 4096, 3072, 2048}) {
+    int rc;
+    if (kron) {
+      if ((rc = build_analysis(A, params, env, rule, false, cap, true))) return print_error(A, rc);
+      // the Kronecker assembly needs the benchmark's shape: a 128-slot front, no continuation records, its scratch within the LDS
+      const int n_cont = A.S.n_continuation();
+      const size_t need = kkt_lds_bytes(Kkt::kkt2, A.S) + 16 + sizeof(double) * Symbolic::KRON_SM * (size_t)A.S.max_kblocks;
+      if (A.S.front != 128 || n_cont != 0 || A.S.max_kblocks == 0 || need > LDS_LIMIT) {
+        if (env.debug) fprintf(stderr, "qtos: Kronecker assembly not applicable (front %d, %d continuation records, %zu B of LDS)\n", A.S.front, n_cont, need);
+        kron = false;
+      }
+    }
+    if (!kron) {
+      if (cap == 0) { rc = def_rc; A = std::move(def); }
+      else rc = build_analysis(A, params, env, rule, false, cap);
+      if (rc) return print_error(A, rc);
+    }
+    if (kkt_lds_bytes(Kkt::kkt2, A.S) <= LDS_LIMIT) break;
+  }
+  return 0;
 }
 
 extern "C" {
@@ -314,93 +403,10 @@ int qtos_planner_create(const QtosParams *params, int max_batch, int device, Qto
   QtosPlanner *p = new QtosPlanner();
   p->device = device;
   p->max_batch = max_batch;
-  // model + symbolic analysis; if the stage records and cells of the result do not fit the LDS next to the panels, again with
-  // smaller records (heavy stages then spill into continuation records): both are rebuilt, the analysis writes into the model
-  // Which factor + solve kernel (kkt2.hpp, kkt3.hpp; all give the same plans where they share the arithmetic):
-  //   k_kkt2            the default for fronts above 112 slots
-  //   k_kkt3, MODE 1    the default up to 112 slots: k_kkt2's records and arithmetic -- bit-identical plans -- with the
-  //                     assembly of the records on the waves that have no job in phase AB (-5 % per launch on the trot's
-  //                     112 slots, -6 % on reference_compat's 96; +4 % on 128 slots, where seven idle waves are too few;
-  //                     profiles/r04_experiments)
-  //   k_kkt5            QTOS_KKT=6: two 16-pivot stages per set of barriers (pair-mode analysis)
-  // QTOS_KKT=2 / 4 / 6 force k_kkt2 / k_kkt3 / k_kkt5.  (k_kkt3 MODE 0 -- inequality blocks condensed by matrix instructions --
-  // and k_kkt4 -- the pipelined stage --, QTOS_KKT=3 / 5 of rounds 4 - 5, were correct and slower: scratch/experiments/, last
-  // built from commit 991d29f.)
-  p->use_kkt3 = false;
-  p->use_kkt5 = false;
   p->env = QtosEnv::parse();   // the ONE place a planner reads the environment
   const QtosEnv &env = p->env;
   p->spec_pattern = env.spec_pattern != 0;
-  const int order_rule = pick_order_rule(*params, env);
-  {
-    int forced = env.kkt;
-    if (forced == 3 || forced == 5) { fprintf(stderr, "qtos: QTOS_KKT=%d selected an experiment of rounds 4 - 5 that left the library (scratch/experiments/): default kernel\n", forced); forced = 0; }
-    if (forced == 6) {
-      // k_kkt5: the analysis in pair mode (one record per pair of stages); applicable without continuation records, with a
-      // front of at most 144 slots and everything within the LDS
-      p->M = HostModel();
-      p->S = Symbolic();
-      p->S.env = env;
-      if ((p->M.order_rule = order_rule, p->M.build(*params))) { fprintf(stderr, "qtos: %s\n", p->M.err.c_str()); delete p; return -1; }
-      p->S.cell_mode = 2;
-      p->S.pair_mode = true;
-      bool ok = p->S.build(p->M) == 0 && kkt5_kernel(p->S.front) != nullptr && !(p->S.pack_src.size() & 1);
-      if (ok) {
-        int n_cont = 0;
-        for (int r = 0; r < p->S.n_records; ++r) n_cont += p->S.srec[p->S.srec_off[r] + 6];
-        ok = n_cont == 0 && kkt5_lds_bytes(p->S.front, p->S.n_stages, p->S.max_srec, p->S.max_drec, p->S.n_cells) <= 160 * 1024 - 256;
-      }
-      p->use_kkt5 = ok;
-      if (env.debug) fprintf(stderr, "qtos: k_kkt5 %s (front %d, %s)\n", ok ? "selected" : "not applicable", p->S.front, p->S.err.c_str());
-    }
-    if (forced != 2 && !p->use_kkt5) {
-      p->M = HostModel();
-      p->S = Symbolic();
-      p->S.env = env;
-      if ((p->M.order_rule = order_rule, p->M.build(*params))) { fprintf(stderr, "qtos: %s\n", p->M.err.c_str()); delete p; return -1; }
-      p->S.cell_mode = 2;
-      bool ok = p->S.build(p->M) == 0 && p->S.front <= (forced ? 128 : 112) && !(p->S.pack_src.size() & 1);
-      if (ok) {
-        int n_cont = 0;
-        for (int k = 0; k < p->S.n_stages; ++k) n_cont += p->S.srec[p->S.srec_off[k] + 6];
-        ok = n_cont == 0 && kkt3_lds_bytes(p->S.front, p->S.n_stages, p->S.max_srec, p->S.max_drec, p->S.n_cells) <= 160 * 1024 - 256;
-      }
-      p->use_kkt3 = ok;
-      if (env.debug) fprintf(stderr, "qtos: k_kkt3 %s (%s)\n", ok ? "selected" : "not applicable", p->S.err.c_str());
-    }
-  }
-#ifdef QTOS_EXPERIMENTS
-  bool want_kron = env.kron != 0;   // (experiment: Kronecker assembly of the range-of-motion blocks, k_kkt2<128> only)
-#else
-  bool want_kron = false;
-#endif
-  for (int cap : {0, 4096, 3072, 2048}) {
-    if (p->use_kkt3 || p->use_kkt5) break;
-    p->M = HostModel();
-    p->S = Symbolic();
-    p->S.env = env;
-    if ((p->M.order_rule = order_rule, p->M.build(*params))) { fprintf(stderr, "qtos: %s\n", p->M.err.c_str()); delete p; return -1; }
-    p->S.cell_mode = 2;
-    p->S.rec_cap_ints = cap;
-    p->S.kron = want_kron;
-    if (p->S.build(p->M)) { fprintf(stderr, "qtos: %s\n", p->S.err.c_str()); delete p; return -1; }
-    if (p->S.kron) {
-      // the Kronecker assembly needs the benchmark's shape: a 128-slot front, no continuation records, its scratch within the LDS
-      int n_cont = 0;
-      for (int k = 0; k < p->S.n_stages; ++k) n_cont += p->S.srec[p->S.srec_off[k] + 6];
-      const size_t need = kkt2_lds_bytes(p->S.front, p->S.n_stages, p->S.max_srec, p->S.max_drec, p->S.n_cells) + 16 + sizeof(double) * Symbolic::KRON_SM * (size_t)p->S.max_kblocks;
-      if (p->S.front != 128 || n_cont != 0 || p->S.max_kblocks == 0 || need > 160 * 1024 - 256) {
-        if (env.debug) fprintf(stderr, "qtos: Kronecker assembly not applicable (front %d, %d continuation records, %zu B of LDS)\n", p->S.front, n_cont, need);
-        want_kron = false;
-        p->M = HostModel(); p->S = Symbolic();
-        p->S.env = env;
-        if ((p->M.order_rule = order_rule, p->M.build(*params))) { delete p; return -1; }
-        p->S.cell_mode = 2; p->S.rec_cap_ints = cap;
-        if (p->S.build(p->M)) { delete p; return -1; }
-      }
-    }
-    if (kkt2_lds_bytes(p->S.front, p->S.n_stages, p->S.max_srec, p->S.max_drec, p->S.n_cells) <= 160 * 1024 - 256) break;
-  }
+  if (choose_kernel(*params, env, p->kkt, *p)) { delete p; return -1; }
   const HostModel &M = p->M;
   const Symbolic &S = p->S;
   int ndev = 0;
@@ -501,8 +507,7 @@ int qtos_planner_create(const QtosParams *params, int max_batch, int device, Qto
   D.chord_max = M.P.chord_max > 0 ? M.P.chord_max : 1;
   D.chord_shrink = M.P.chord_shrink > 0 ? M.P.chord_shrink : 1.0 / 3.0;
   D.n_cells = S.n_cells;
-  D.n_cont = 0;
-  for (int k = 0; k < S.n_records; ++k) D.n_cont += S.srec[S.srec_off[k] + 6];
+  D.n_cont = S.n_continuation();
   D.table = nullptr; D.tab_dx = D.tab_dy = nullptr; D.tab_ndx = D.tab_ndy = 0;
   D.off_lin = M.off_lin; D.off_ang = M.off_ang;
   for (int e = 0; e < NEE; ++e) D.off_eem[e] = M.off_eem[e];
@@ -593,38 +598,42 @@ int qtos_planner_create(const QtosParams *params, int max_batch, int device, Qto
   D.panel_stride = (long long)S.n_stages * (S.front + 1) * PIV;
   // LDS budget of k_kkt
   const int F = S.front;
-  p->kkt_lds = p->use_kkt5 ? kkt5_lds_bytes(F, S.n_stages, S.max_srec, S.max_drec, S.n_cells) : p->use_kkt3 ? kkt3_lds_bytes(F, S.n_stages, S.max_srec, S.max_drec, S.n_cells) : kkt2_lds_bytes(F, S.n_stages, S.max_srec, S.max_drec, S.n_cells);
+  p->kkt_lds = kkt_lds_bytes(p->kkt, S);
   D.kron_lds_off = 0;
-  if (env.debug) fprintf(stderr, "qtos: Kronecker assembly %s (kkt3 %d, most blocks in a record %d)\n", S.kron ? "on" : "off", (int)p->use_kkt3, S.max_kblocks);
-  if (S.kron && !p->use_kkt3) {
+  if (env.debug) fprintf(stderr, "qtos: Kronecker assembly %s (kkt3 %d, most blocks in a record %d)\n", S.kron ? "on" : "off", (int)(p->kkt == Kkt::kkt3), S.max_kblocks);
+  if (S.kron) {   // (k_kkt2 only: choose_kernel)
     D.kron_lds_off = (int)((p->kkt_lds + 15) & ~(size_t)15);
     p->kkt_lds = (size_t)D.kron_lds_off + sizeof(double) * Symbolic::KRON_SM * (size_t)S.max_kblocks;
   }
-  if (p->use_kkt5 && F > 128) D.sw_on = 0;   // (nine tile waves of twelve: fewer than three helper waves are left)
+  if (p->kkt == Kkt::kkt5 && F > 128) D.sw_on = 0;   // (nine tile waves of twelve: fewer than three helper waves are left)
   if (D.sw_on) {
     // the helper waves' tables of the backward sweep (solution by position, rounds) behind the sweep's own: within the LDS
     // the forward pass needs anyway, or the kernel's allocation grows up to the limit; beyond that k_step forms ds itself
-    const size_t need = (p->use_kkt5 ? kkt5_sweep_base_bytes(F, S.n_stages) : kkt2_sweep_base_bytes(F, S.n_stages)) + sweep_ds_lds_bytes(S.n_stages, D.sw_steps);
-    if (need > 160 * 1024 - 256 || chord_lds_bytes(S.n_stages, D.sw_steps) > 96 * 1024) D.sw_on = 0;
+    const size_t need = (p->kkt == Kkt::kkt5 ? kkt5_sweep_base_bytes(F, S.n_stages) : kkt2_sweep_base_bytes(F, S.n_stages)) + sweep_ds_lds_bytes(S.n_stages, D.sw_steps);
+    if (need > LDS_LIMIT || chord_lds_bytes(S.n_stages, D.sw_steps) > 96 * 1024) D.sw_on = 0;
     else p->kkt_lds = std::max(p->kkt_lds, need);
   }
-  p->kkt_threads = p->use_kkt5 ? KT5 : KT2;
+  p->kkt_threads = p->kkt == Kkt::kkt5 ? KT5 : KT2;
   const int max_front = 208;
-  if (!p->use_kkt5 && (S.max_drec > 2 * 2 * KT || S.max_srec > 3 * 4 * KT || F > max_front || (S.pack_src.size() & 1))) {
+  if (p->kkt != Kkt::kkt5 && (S.max_drec > 2 * 2 * KT || S.max_srec > 3 * 4 * KT || F > max_front || (S.pack_src.size() & 1))) {
     p->err = "stage record exceeds the prefetch registers";
     fprintf(stderr, "qtos: stage records too long (%d doubles, %d ints) or front %d > %d\n", S.max_drec, S.max_srec, F, max_front);
     qtos_planner_destroy(p);
     return -4;
   }
   if (env.debug) fprintf(stderr, "qtos: front %d, k_kkt LDS %zu B\n", F, p->kkt_lds);
-  if (p->kkt_lds > 160 * 1024 - 256) {
+  if (p->kkt_lds > LDS_LIMIT) {
     p->err = "front too large for LDS";
     fprintf(stderr, "qtos: front %d needs %zu B of LDS\n", F, p->kkt_lds);
     qtos_planner_destroy(p);
     return -4;
   }
   {
-    p->kkt_fn = p->use_kkt5 ? kkt5_kernel(F) : p->use_kkt3 ? kkt3_kernel(F) : kkt2_kernel(F, D.n_cont > 0, S.kron);
+    switch (p->kkt) {
+      case Kkt::kkt5: p->kkt_fn = kkt5_kernel(F); break;
+      case Kkt::kkt3: p->kkt_fn = kkt3_kernel(F); break;
+      case Kkt::kkt2: p->kkt_fn = kkt2_kernel(F, D.n_cont > 0, S.kron); break;
+    }
     p->chord_fn = chord_kernel(F);
     if (!p->kkt_fn) { p->err = "no k_kkt instantiation for this front size"; qtos_planner_destroy(p); return -4; }
     hipError_t e = hipFuncSetAttribute((const void *)p->kkt_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->kkt_lds);
@@ -768,13 +777,11 @@ int qtos_planner_dims(const QtosPlanner *p, QtosDims *d) {
 
 int qtos_analyze(const QtosParams *params, QtosDims *d, int *stage_active, int max_stages) {
   if (!params || !d) return -1;
-  HostModel M;
-  Symbolic S;
-  S.env = QtosEnv::parse();
-  if ((M.order_rule = pick_order_rule(*params, S.env), M.build(*params))) { fprintf(stderr, "qtos: %s\n", M.err.c_str()); return -1; }
-  if (S.env.debug_kron) S.kron = true;
-  if (S.build(M)) { fprintf(stderr, "qtos: %s\n", S.err.c_str()); return -1; }
-  if (S.env.debug_kron) {
+  const QtosEnv env = QtosEnv::parse();
+  Analysis A;
+  if (analyze_host(*params, env, env.debug_kron != 0, A)) return -1;
+  const auto &[M, S] = A;
+  if (env.debug_kron) {
     int nb = 0;
     const double worst = S.check_kron(&nb);
     size_t tot = 0;
@@ -782,7 +789,7 @@ int qtos_analyze(const QtosParams *params, QtosDims *d, int *stage_active, int m
     fprintf(stderr, "qtos: Kronecker blocks %d of %zu inequality blocks, most in a record %d, worst relative difference %.2e, max record %d ints / %d doubles\n", nb, tot, S.max_kblocks, worst, S.max_srec, S.max_drec);
   }
   fill_dims(M, S, d);
-  if (S.env.debug) { std::vector<SwTask> t; std::vector<int> c, c2; (void)build_sweep_tasks(M, S, t, c, c2); }
+  if (env.debug) { std::vector<SwTask> t; std::vector<int> c, c2; (void)build_sweep_tasks(M, S, t, c, c2); }
   if (stage_active)
     for (int k = 0; k < S.n_stages && k < max_stages; ++k) stage_active[k] = S.stages[k].n_active;
   return 0;
@@ -792,11 +799,9 @@ int qtos_analyze(const QtosParams *params, QtosDims *d, int *stage_active, int m
 // for a multiplier, -1 for a dummy pivot; returns the number of positions (n_stages * pivots) or < 0.
 int qtos_analyze_order(const QtosParams *params, int *order, int max_positions) {
   if (!params || !order) return -1;
-  HostModel M;
-  Symbolic S;
-  S.env = QtosEnv::parse();
-  if ((M.order_rule = pick_order_rule(*params, S.env), M.build(*params))) { fprintf(stderr, "qtos: %s\n", M.err.c_str()); return -1; }
-  if (S.build(M)) { fprintf(stderr, "qtos: %s\n", S.err.c_str()); return -1; }
+  Analysis A;
+  if (analyze_host(*params, QtosEnv::parse(), false, A)) return -1;
+  const Symbolic &S = A.S;
   const int np = S.n_stages * PIV;
   for (int i = 0; i < np && i < max_positions; ++i) order[i] = i < (int)S.order.size() ? S.order[i] : -1;   // (as qtos_debug_structure)
   return np;
@@ -813,11 +818,9 @@ int qtos_analyze_order(const QtosParams *params, int *order, int max_positions) 
 //        tables read from L2), the cells; the fixed part twice   [19] the limit (160 KB - 256 B)
 int qtos_analyze_two_ended(const QtosParams *params, int *out, int n_out) {
   if (!params || !out || n_out < 20) return -1;
-  HostModel M;
-  Symbolic S;
-  S.env = QtosEnv::parse();
-  if ((M.order_rule = pick_order_rule(*params, S.env), M.build(*params))) { fprintf(stderr, "qtos: %s\n", M.err.c_str()); return -1; }
-  if (S.build(M)) { fprintf(stderr, "qtos: %s\n", S.err.c_str()); return -1; }
+  Analysis A;
+  if (analyze_host(*params, QtosEnv::parse(), false, A)) return -1;
+  const auto &[M, S] = A;
   const Symbolic::TwoEnded t = S.analyze_two_ended(M);
   const int F = S.front, Fc = std::max(t.front_left, t.front_right);
   auto panel_b = [](int f, int n_pan) { return (size_t)((f + 1) * PLD * n_pan + f * PLD) * sizeof(double); };
@@ -831,7 +834,7 @@ int qtos_analyze_two_ended(const QtosParams *params, int *out, int n_out) {
   out[13] = (int)total; out[14] = (int)panel_b(F, 3); out[15] = (int)rec_b; out[16] = (int)cells_b;
   out[17] = (int)(2 * (panel_b(Fc, 3) + rec_b + cells_b + fixed_b));
   out[18] = (int)(2 * (panel_b(Fc, 2) + kkt2_dbuf_doubles(F, S.max_drec) * sizeof(double) + cells_b + fixed_b));
-  out[19] = 160 * 1024 - 256;
+  out[19] = (int)LDS_LIMIT;
   return 0;
 }
 
@@ -840,12 +843,9 @@ int qtos_analyze_two_ended(const QtosParams *params, int *out, int n_out) {
 // through the 33 sums of a block and the direct three-term sum, on random matrices and weights (Symbolic::check_kron).
 int qtos_analyze_kron(const QtosParams *params, int *n_blocks, int *n_kron, int *max_in_record, double *worst) {
   if (!params || !n_blocks || !n_kron || !max_in_record || !worst) return -1;
-  HostModel M;
-  Symbolic S;
-  S.env = QtosEnv::parse();
-  if ((M.order_rule = pick_order_rule(*params, S.env), M.build(*params))) { fprintf(stderr, "qtos: %s\n", M.err.c_str()); return -1; }
-  S.kron = true;
-  if (S.build(M)) { fprintf(stderr, "qtos: %s\n", S.err.c_str()); return -1; }
+  Analysis A;
+  if (analyze_host(*params, QtosEnv::parse(), true, A)) return -1;
+  const auto &[M, S] = A;
   *n_blocks = 0;
   for (const Block &b : M.blocks) *n_blocks += b.kind == 1;
   *worst = S.check_kron(n_kron);
@@ -858,11 +858,9 @@ int qtos_analyze_kron(const QtosParams *params, int *n_blocks, int *n_kron, int 
 // the row's entries, and the smallest and largest position (elimination order) of the row's columns.
 int qtos_analyze_sweep(const QtosParams *params, int *n_rounds, int *rows, int *entries, int *pos_min, int *pos_max, int max_places) {
   if (!params || !n_rounds) return -1;
-  HostModel M;
-  Symbolic S;
-  S.env = QtosEnv::parse();
-  if ((M.order_rule = pick_order_rule(*params, S.env), M.build(*params))) { fprintf(stderr, "qtos: %s\n", M.err.c_str()); return -1; }
-  if (S.build(M)) { fprintf(stderr, "qtos: %s\n", S.err.c_str()); return -1; }
+  Analysis A;
+  if (analyze_host(*params, QtosEnv::parse(), false, A)) return -1;
+  const auto &[M, S] = A;
   std::vector<SwTask> tasks;
   std::vector<int> cpos, c16;
   *n_rounds = build_sweep_tasks(M, S, tasks, cpos, c16);
@@ -1784,13 +1782,14 @@ int qtos_build_flags(void) {
 }
 int qtos_kkt_kernel(const QtosPlanner *p, char *buf, int n) {
   if (!p) return -1;
-  char name[64];
-  const int F = p->S.front;
-  if (p->use_kkt5) snprintf(name, sizeof name, "k_kkt5<%d>", F);
-  else if (p->use_kkt3) snprintf(name, sizeof name, "k_kkt3<%d, 1>", F);
-  else snprintf(name, sizeof name, "k_kkt2<%d%s>", F, p->dp.n_cont > 0 ? ", true" : "");
-  if (buf && n > 0) snprintf(buf, (size_t)n, "%s", name);
-  return (int)strlen(name);
+  return kkt_kernel_name(p->kkt, p->S, buf, n);
+}
+// Host-only: the name qtos_kkt_kernel would report for a planner created now (choose_kernel); < 0 where the analysis fails
+int qtos_analyze_kernel(const QtosParams *params, char *buf, int n) {
+  Analysis A;
+  Kkt kind;
+  if (!params || choose_kernel(*params, QtosEnv::parse(), kind, A)) return -1;
+  return kkt_kernel_name(kind, A.S, buf, n);
 }
 /* diagnostic: the stage stream of problem b (qtos_debug_stream_len doubles) */
 int qtos_debug_stream_len(const QtosPlanner *p) { return p ? (int)p->S.pack_src.size() : -1; }

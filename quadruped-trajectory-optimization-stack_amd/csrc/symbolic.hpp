@@ -140,6 +140,11 @@ struct Symbolic {
   // pack_src[i] says where stream element i comes from: (kind << 28) | index, kind 0 G, 1 g_static,
   // 2 -g[row], 3 sig[row], 4 w[row], 5 piv_diag, 6 alignment padding
   std::vector<int> srec, srec_off, pack_src, drec_off, stage_hi;
+  int n_continuation() const {   // continuation records of the whole plan (header word 6 of every record)
+    int n = 0;
+    for (int r = 0; r < n_records; ++r) n += srec[srec_off[r] + 6];
+    return n;
+  }
   // Compact storage of the assembled entries (see compact_cells): cell 0 is a constant zero, cells
   // 1..front hold the assembled right-hand side by slot, the rest are handed out to the structural
   // entries of K for the stages between their assembly and the gathering of their pivot column.

@@ -167,6 +167,36 @@ def test_knots100_structure(hip_lib):
     assert (dk.order_rule, dk.front) == (1, 96)
 
 
+def test_kernel_choice_on_the_host(hip_lib, monkeypatch):
+    """qtos_analyze_kernel makes qtos_planner_create's choice of the factor + solve kernel without a GPU: every choice
+    tests/test_gpu_kernels.py pins on a planner, the fallbacks, and the default on the long horizons."""
+    from qtos_amd import capi
+    from qtos_amd.config import PlannerConfig
+    from test_gpu_kernels import EXPECT
+    for k in ("QTOS_KKT", "QTOS_ORDER", "QTOS_SHORT_STAGES", "QTOS_NO_SHORT_STAGES", "QTOS_KRON"):
+        monkeypatch.delenv(k, raising=False)
+    walk = PlannerConfig.knots100()
+    cfgs = {"walk": walk, "trot": PlannerConfig.knots100(gait="trot"), "mixed": walk}   # (the terrains do not enter the analysis)
+    for (kkt, workload), name in EXPECT.items():
+        if kkt is None:
+            monkeypatch.delenv("QTOS_KKT", raising=False)
+        else:
+            monkeypatch.setenv("QTOS_KKT", kkt)
+        assert capi.analyze_kernel(cfgs[workload]) == name, (kkt, workload)
+    monkeypatch.setenv("QTOS_KKT", "6")     # (`-duration 20`: no k_kkt5 for its pair-mode front)
+    assert capi.analyze_kernel(PlannerConfig.reference_compat(duration=20.0)) == "k_kkt2<144, true>"
+    monkeypatch.setenv("QTOS_KKT", "5")     # (an experiment that left the library: the default)
+    assert capi.analyze_kernel(walk) == EXPECT[(None, "walk")]
+    monkeypatch.setenv("QTOS_KKT", "2")
+    monkeypatch.setenv("QTOS_ORDER", "0")
+    monkeypatch.setenv("QTOS_SHORT_STAGES", "0")
+    assert capi.analyze_kernel(walk) == "k_kkt2<128>"
+    for k in ("QTOS_KKT", "QTOS_ORDER", "QTOS_SHORT_STAGES"):
+        monkeypatch.delenv(k)
+    assert capi.analyze_kernel(PlannerConfig.reference_compat(duration=12.0)) == "k_kkt2<112, true>"
+    assert capi.analyze_kernel(PlannerConfig.reference_compat(duration=20.0)) == "k_kkt2<144, true>"
+
+
 def test_knots200_structure(hip_lib):
     """BASELINE configs[4]: two walk cycles over 10 s keep the elimination front at the 128 slots of the
     100-knot problem (scaling the one-cycle schedule to 10 s would need 208)."""

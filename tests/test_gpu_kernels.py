@@ -11,14 +11,16 @@ pytestmark = pytest.mark.gpu
 
 
 def _planner(cfg, B, kkt):
-    from qtos_amd.capi import Planner
+    from qtos_amd.capi import Planner, analyze_kernel
     old = os.environ.get("QTOS_KKT")
     if kkt is None:
         os.environ.pop("QTOS_KKT", None)
     else:
         os.environ["QTOS_KKT"] = kkt
     try:
-        return Planner(cfg, max_batch=B)
+        P = Planner(cfg, max_batch=B)
+        assert P.kkt_kernel() == analyze_kernel(cfg)     # (the host-only entry point makes the same choice)
+        return P
     finally:
         if old is None:
             os.environ.pop("QTOS_KKT", None)
@@ -123,8 +125,9 @@ def test_environment_is_read_once_at_creation_and_read_back():
     os.environ.update(QTOS_KKT="2", QTOS_LANES="3", QTOS_SPEC_PATTERN="0", QTOS_SHORT_STAGES="0", QTOS_ORDER="0")
     try:
         assert P0.env() == e0 and P0.kkt_kernel() == EXPECT[(None, "walk")]     # the old handle keeps what it was created with
-        from qtos_amd.capi import Planner
+        from qtos_amd.capi import Planner, analyze_kernel
         P1 = Planner(PlannerConfig.knots100(), max_batch=2)
+        assert P1.kkt_kernel() == analyze_kernel(PlannerConfig.knots100())
         e1 = P1.env()
         assert (e1["QTOS_KKT"], e1["QTOS_LANES"], e1["QTOS_SPEC_PATTERN"], e1["QTOS_SHORT_STAGES"], e1["QTOS_ORDER"]) == ("2", "3", "0", "0", "0")
         assert P1.kkt_kernel().startswith("k_kkt2<128") and P1.dims.front == 128     # (the order of rounds 1 - 5 without short stages: the walk's 128 slots; k_kkt2 forced)
