@@ -543,6 +543,13 @@ __device__ inline void eval_force(const DevPlan &P, const ForceInst &I, int map,
 // range-of-motion instances
 __device__ __forceinline__ int eval_loc_offset(int n_vars) { return (n_vars + 1) & ~1; }
 constexpr int DYN_VIN = 39, ROM_VIN = 9;   // pre-evaluated spline inputs per instance
+// v as a value the compiler cannot follow back: an address formed from it is formed where it is used.  (Addresses of thread-
+// indexed loops that the evaluation kernels run more than once -- the staging below, the passes of k_step behind an evaluation
+// -- were otherwise formed once, two VGPRs each, and kept live across eval_all: spilled.)
+__device__ __forceinline__ int fresh(int v) {
+  asm volatile("" : "+v"(v));
+  return v;
+}
 // The barriers inside eval_all order LDS traffic only (the nodes, the pre-evaluated inputs, the local Jacobians); what an evaluation
 // writes to memory (g, the stream) is read behind the caller's __syncthreads().  A barrier that also drains the memory counter would
 // put every section behind the stores of the one before it.
@@ -571,9 +578,9 @@ __device__ inline void eval_all(const DevPlan &P, int map, const double *xg, dou
   double *coef_lds = vin + max(DYN_VIN * P.dyn_chunk, ROM_VIN * P.rom_chunk);   // coefficients of the entry lists (JAC only)
   const double *coef = P.coef_in_lds ? coef_lds : P.lin_coef;
   if (xg)   // (null: the caller has left the nodes in lds[0 .. n_vars) already)
-    for (int v = tid; v < P.n_vars; v += nt) x[v] = xg[v];
+    for (int v = fresh(tid); v < P.n_vars; v += nt) x[v] = xg[v];
   if (JAC && P.coef_in_lds)
-    for (int v = tid; v < P.n_lin_coef; v += nt) coef_lds[v] = P.lin_coef[v];
+    for (int v = fresh(tid); v < P.n_lin_coef; v += nt) coef_lds[v] = P.lin_coef[v];
   EVAL_BARRIER();
   // the dynamics knots go through the LDS scratch in chunks of P.dyn_chunk (one chunk up to 128 knots)
   for (int c0 = 0, ch = 0; c0 < P.n_dyn; c0 += P.dyn_chunk, ++ch) {
@@ -1290,6 +1297,13 @@ __device__ __forceinline__ double quadsum(double t) {
 // a look at the counts) may not have run the kernel a problem was waiting for: that problem sits the launch out -- nothing of
 // its state moves, it reports the slot in n_active[2] -- and takes the step behind a later launch.  Its iteration number is
 // therefore its own (W.iters), not the launch's: the plans do not depend on how the launches were queued.
+// the thread's row indices afresh for a pass behind an evaluation (fresh(): one VGPR each live across eval_all instead of the
+// two of every address formed from them)
+template <int K>
+__device__ __forceinline__ void fresh_rows(const int (&r)[K], int (&o)[K]) {
+#pragma unroll
+  for (int k = 0; k < K; ++k) o[k] = fresh(r[k]);
+}
 __global__ __launch_bounds__(ET) void k_step(DevPlan P, DevWork W, int B, int slot, int kinds) {
   const int b = blockIdx.x;
   if (b >= B) return;
@@ -1362,28 +1376,26 @@ __global__ __launch_bounds__(ET) void k_step(DevPlan P, DevWork W, int B, int sl
     for (int t = 0; t < TP; ++t) Rn[t] = row_of(tid + t * nt);
   }
   // (c) the rows of the working set this thread owns: inequality rows tid + k nt (k < KR) and equality rows tid + k nt
-  //     (k < KE) with their bounds, slacks, multipliers and values live in registers from here to the end of the kernel -- every
-  //     pass below (ratio test, merit function, update, convergence test, barrier weights) read them through the row lists
-  //     again: two memory round trips per pass and ten array passes of traffic per launch.  Rows beyond KR nt / KE nt (longer
-  //     horizons) go through memory as before.
+  //     (k < KE) with their bounds, slacks, multipliers and values sit in registers between the evaluations -- every pass
+  //     below (ratio test, merit function, update, convergence test, barrier weights) read them through the row lists again:
+  //     two memory round trips per pass and ten array passes of traffic per launch.  Rows beyond KR nt / KE nt (longer
+  //     horizons) go through memory as before.  Only the row indices stay live across an evaluation: eval_all needs the
+  //     register file, and what else was live across it went to scratch (316 B per lane, stored at the top, reloaded in the
+  //     update and barrier-weight passes).  The passes behind an evaluation reload the values from the arrays instead, at the
+  //     indices they already hold: one round trip to lines that are in L2, and no scratch stores.
   constexpr int KR = 2, KE = 2;
   int rr[KR], er[KE];
   double rl[KR], ru[KR], rs[KR], rzl[KR], rzu[KR], rg[KR], eg[KE];
+  // bounds of the thread's rows: ic_row(k) is the (clamped) list position of its row k, formed afresh by every pass that reads
+  // them (a position kept from the top would stay live across the evaluations)
+  auto ic_row = [&](int k) __attribute__((always_inline)) { return min(fresh(tid) + k * nt, max(P.n_iq - 1, 0)); };
 #pragma unroll
-  for (int k = 0; k < KR; ++k) {
-    const int ic = min(tid + k * nt, max(P.n_iq - 1, 0));
-    rr[k] = P.n_iq > 0 ? P.iq_idx[ic] : 0; rl[k] = P.iq_lo[ic]; ru[k] = P.iq_hi[ic];   // (an empty list is one unset element)
-  }
+  for (int k = 0; k < KR; ++k) rr[k] = P.n_iq > 0 ? P.iq_idx[min(tid + k * nt, max(P.n_iq - 1, 0))] : 0;   // (an empty list is one unset element)
 #pragma unroll
   for (int k = 0; k < KE; ++k) er[k] = P.n_eqw > 0 ? P.eq_idx[min(tid + k * nt, max(P.n_eqw - 1, 0))] : 0;
   const bool rows_in_regs = P.n_iq <= KR * nt && P.n_eqw <= KE * nt;
   for (int v = tid; v < P.n_sol; v += nt) evl[v] = dx[v];
-  // (behind the staging, whose stores waited for every load above: the row indices are there)
-#pragma unroll
-  for (int k = 0; k < KR; ++k) { rs[k] = s[rr[k]]; rzl[k] = zl[rr[k]]; rzu[k] = zu[rr[k]]; rg[k] = g[rr[k]]; }
-#pragma unroll
-  for (int k = 0; k < KE; ++k) eg[k] = g[er[k]];
-  lds_barrier();   // (LDS only: the loads of the thread's rows stay in flight across it)
+  lds_barrier();
   if (done_flag) return;
   if (missed) {
     if (tid == 0) atomicMax(W.n_active + 2, (1 << 20) - slot);   // (the EARLIEST slot somebody sat out; 0 = nobody)
@@ -1458,19 +1470,35 @@ __global__ __launch_bounds__(ET) void k_step(DevPlan P, DevWork W, int B, int sl
   KSTAMP(0);
   const double tau = fmax(0.99, 1.0 - mu);
   double amax = 1.0, az = 1.0;
-  double rds[KR], rdzl[KR], rdzu[KR];
+  double rds[KR];
+  // the thread's rows: one round trip with ds (with the backward sweep's ds nothing above needs them, and loaded at the top
+  // they stayed live across the passes in between: spilled)
 #pragma unroll
-  for (int k = 0; k < KR; ++k) rds[k] = ds[rr[k]];
+  for (int k = 0; k < KR; ++k) {
+    const int ic = ic_row(k);
+    rl[k] = P.iq_lo[ic]; ru[k] = P.iq_hi[ic];
+    rs[k] = s[rr[k]]; rzl[k] = zl[rr[k]]; rzu[k] = zu[rr[k]]; rg[k] = g[rr[k]]; rds[k] = ds[rr[k]];
+  }
+#pragma unroll
+  for (int k = 0; k < KE; ++k) eg[k] = g[er[k]];
   // ratio tests and the step of the multipliers (one row; the formulas of the passes below are these lambdas, on registers
   // for the thread's own rows and on memory for the rest)
   // (an IEEE division is a chain of a dozen dependent f64 instructions, and the compiler leaves one that sits behind a condition
   //  in a branch of its own: eight divisions of a row ran one after the other, 16 k cycles for the thread's two rows.  Every
   //  quotient is formed unconditionally -- on 1.0 where the row has no such bound -- and selected: the chains interleave)
-  auto ratio_row = [&](bool valid, double l, double u, double sv, double d, double zlv, double zuv, double &a, double &c) __attribute__((always_inline)) {
-    const bool hl = valid && l > -1e19, hu = valid && u < 1e19;
-    const double dl = hl ? sv - l : 1.0, du = hu ? u - sv : 1.0;
+  // (the step of the multipliers is formed twice from the same operands: here for the ratio test, and again in the update pass
+  //  below from s, z, ds reloaded from memory -- nothing of a row stays live across the evaluations in between)
+  auto dz_row = [&](bool valid, double l, double u, double sv, double d, double zlv, double zuv, bool &hl, bool &hu, double &dl, double &du,
+                    double &a_, double &c_) __attribute__((always_inline)) {
+    hl = valid && l > -1e19; hu = valid && u < 1e19;
+    dl = hl ? sv - l : 1.0; du = hu ? u - sv : 1.0;
     const double ml = mu / dl, zql = zlv / dl, mq = mu / du, zqu = zuv / du;
-    const double a_ = ml - zlv - zql * d, c_ = mq - zuv + zqu * d;
+    a_ = ml - zlv - zql * d; c_ = mq - zuv + zqu * d;
+  };
+  auto ratio_row = [&](bool valid, double l, double u, double sv, double d, double zlv, double zuv, double &a, double &c) __attribute__((always_inline)) {
+    bool hl, hu;
+    double dl, du, a_, c_;
+    dz_row(valid, l, u, sv, d, zlv, zuv, hl, hu, dl, du, a_, c_);
     a = hl ? a_ : 0.0;
     c = hu ? c_ : 0.0;
     const double r1 = tau * dl / -d, r2 = tau * du / d, r3 = tau * zlv / -a_, r4 = tau * zuv / -c_;
@@ -1480,7 +1508,10 @@ __global__ __launch_bounds__(ET) void k_step(DevPlan P, DevWork W, int B, int sl
     az = (hu && c_ < 0) ? fmin(az, r4) : az;
   };
 #pragma unroll
-  for (int k = 0; k < KR; ++k) ratio_row(tid + k * nt < P.n_iq, rl[k], ru[k], rs[k], rds[k], rzl[k], rzu[k], rdzl[k], rdzu[k]);
+  for (int k = 0; k < KR; ++k) {
+    double a, c;   // (formed again by the update pass)
+    ratio_row(tid + k * nt < P.n_iq, rl[k], ru[k], rs[k], rds[k], rzl[k], rzu[k], a, c);
+  }
   for (int i = tid + KR * nt; i < P.n_iq; i += nt) {
     const int r = P.iq_idx[i];
     double a, c;
@@ -1490,24 +1521,25 @@ __global__ __launch_bounds__(ET) void k_step(DevPlan P, DevWork W, int B, int sl
   }
   amax = wg_reduce<2>(amax, scratch);
   az = wg_reduce<2>(az, scratch);
-  // l1 infeasibility of (c_E, c_I - (s + alpha ds)) for constraint values gI / gE (registers) and gm (memory), summed in the
-  // order of l1_infeasibility: the thread's equality rows, then its inequality rows
-  auto l1_rows = [&](const double (&gI)[KR], const double (&gE)[KE], const double *__restrict__ gm, double alq) __attribute__((always_inline)) {
+  // l1 infeasibility of (c_E, c_I - (s + alpha ds)) for constraint values gI / gE, slacks sI and their steps dI (registers) and
+  // gm (memory), summed in the order of l1_infeasibility: the thread's equality rows, then its inequality rows
+  auto l1_rows = [&](const double (&gI)[KR], const double (&gE)[KE], const double (&sI)[KR], const double (&dI)[KR], const double *__restrict__ gm,
+                     double alq) __attribute__((always_inline)) {
     double t = 0;
 #pragma unroll
     for (int k = 0; k < KE; ++k)
       if (tid + k * nt < P.n_eqw) t += fabs(gE[k]);
-    for (int i = tid + KE * nt; i < P.n_eqw; i += nt) t += fabs(gm[P.eq_idx[i]]);
+    for (int i = fresh(tid) + KE * nt; i < P.n_eqw; i += nt) t += fabs(gm[P.eq_idx[i]]);
 #pragma unroll
     for (int k = 0; k < KR; ++k)
-      if (tid + k * nt < P.n_iq) t += fabs(gI[k] - (rs[k] + alq * rds[k]));
-    for (int i = tid + KR * nt; i < P.n_iq; i += nt) {
+      if (tid + k * nt < P.n_iq) t += fabs(gI[k] - (sI[k] + alq * dI[k]));
+    for (int i = fresh(tid) + KR * nt; i < P.n_iq; i += nt) {
       const int r = P.iq_idx[i];
       t += fabs(gm[r] - (s[r] + alq * ds[r]));
     }
     return wg_reduce<0>(t, scratch);
   };
-  const double th0 = l1_rows(rg, eg, g, 0.0);
+  const double th0 = l1_rows(rg, eg, rs, rds, g, 0.0);
   KSTAMP(1);
   // backtracking on the l1 infeasibility of (c_E, c_I - s)
   double al = amax, th = 0;
@@ -1526,11 +1558,15 @@ __global__ __launch_bounds__(ET) void k_step(DevPlan P, DevWork W, int B, int sl
     else
       eval_all<false>(P, map, nullptr, gt, nullptr, evl, (W.trace && it == 1 && ls == 0) ? W.trace + ((size_t)b * (P.max_iter + 1) + 76) * 4 : nullptr);
     __syncthreads();
+    double st_[KR], dst[KR];   // (the slacks and their steps again: in registers across the evaluation they cost spills)
+    int rk[KR], ek[KE];
+    fresh_rows(rr, rk);
+    fresh_rows(er, ek);
 #pragma unroll
-    for (int k = 0; k < KR; ++k) rgt[k] = gv[rr[k]];
+    for (int k = 0; k < KR; ++k) { rgt[k] = gv[rk[k]]; st_[k] = s[rk[k]]; dst[k] = ds[rk[k]]; }
 #pragma unroll
-    for (int k = 0; k < KE; ++k) egt[k] = gv[er[k]];
-    th = l1_rows(rgt, egt, gv, al);
+    for (int k = 0; k < KE; ++k) egt[k] = gv[ek[k]];
+    th = l1_rows(rgt, egt, st_, dst, gv, al);
     if (th <= (1.0 - 1e-4 * al) * th0 || th < 1e-9) { lin_done = spec && ls == 0; break; }
     if (ls < 5) al *= 0.5;
   }
@@ -1539,8 +1575,17 @@ __global__ __launch_bounds__(ET) void k_step(DevPlan P, DevWork W, int B, int sl
   // is discarded (the iterate stays, the next iteration factors): a damped chord step can park a slack right on
   // its bound, and the KKT matrix of that point is too badly scaled for the block elimination
   const bool reject = was_chord && al != 1.0;
-  if (reject) { al = 0.0; az = 0.0; th = 0.0; }
-  else {
+  if (reject) {
+    al = 0.0; az = 0.0; th = 0.0;
+    // the thread's rows of g at the iterate, as loaded for th0 (a chord step evaluates no Jacobian: g is untouched)
+    int rk[KR], ek[KE];
+    fresh_rows(rr, rk);
+    fresh_rows(er, ek);
+#pragma unroll
+    for (int k = 0; k < KR; ++k) rg[k] = g[rk[k]];
+#pragma unroll
+    for (int k = 0; k < KE; ++k) eg[k] = g[ek[k]];
+  } else {
     for (int v = tid; v < n; v += blockDim.x) x[v] = evl[v];   // (the trial point of the last evaluation)
 #pragma unroll
     for (int k = 0; k < KR; ++k) rg[k] = rgt[k];
@@ -1564,17 +1609,35 @@ __global__ __launch_bounds__(ET) void k_step(DevPlan P, DevWork W, int B, int sl
     zlv = hl ? fmin(fmax(a, lo_l), hi_l) : a;
     zuv = hu ? fmin(fmax(c, lo_u), hi_u) : c;
   };
+  // the thread's rows once more from memory (bounds, s, z, ds: unchanged since the ratio test), and their multiplier steps formed
+  // again from them
+  int rk[KR];
+  fresh_rows(rr, rk);
+#pragma unroll
+  for (int k = 0; k < KR; ++k) {
+    const int ic = ic_row(k);
+    rl[k] = P.iq_lo[ic]; ru[k] = P.iq_hi[ic];
+    rs[k] = s[rk[k]]; rzl[k] = zl[rk[k]]; rzu[k] = zu[rk[k]]; rds[k] = ds[rk[k]];
+  }
 #pragma unroll
   for (int k = 0; k < KR; ++k) {
     const bool valid = tid + k * nt < P.n_iq;
+    double rdzl, rdzu;
+    {
+      bool hl, hu;
+      double dl, du, a_, c_;
+      dz_row(valid, rl[k], ru[k], rs[k], rds[k], rzl[k], rzu[k], hl, hu, dl, du, a_, c_);
+      rdzl = hl ? a_ : 0.0;
+      rdzu = hu ? c_ : 0.0;
+    }
     double sv = rs[k], zlv = rzl[k], zuv = rzu[k];
-    update_row(rl[k], ru[k], sv, rds[k], zlv, zuv, rdzl[k], rdzu[k]);
+    update_row(rl[k], ru[k], sv, rds[k], zlv, zuv, rdzl, rdzu);
     if (valid) {
       rs[k] = sv; rzl[k] = zlv; rzu[k] = zuv;
-      s[rr[k]] = sv; zl[rr[k]] = zlv; zu[rr[k]] = zuv;
+      s[rk[k]] = sv; zl[rk[k]] = zlv; zu[rk[k]] = zuv;
     }
   }
-  for (int i = tid + KR * nt; i < P.n_iq; i += nt) {
+  for (int i = fresh(tid) + KR * nt; i < P.n_iq; i += nt) {
     const int r = P.iq_idx[i];
     double sv = s[r], zlv = zl[r], zuv = zu[r];
     update_row(P.iq_lo[i], P.iq_hi[i], sv, ds[r], zlv, zuv, dzl[r], dzu[r]);
@@ -1599,11 +1662,11 @@ __global__ __launch_bounds__(ET) void k_step(DevPlan P, DevWork W, int B, int sl
 #pragma unroll
     for (int k = 0; k < KE; ++k)
       if (tid + k * nt < P.n_eqw) eq_row(eg[k]);
-    for (int i = tid + KE * nt; i < P.n_eqw; i += nt) eq_row(g[P.eq_idx[i]]);
+    for (int i = fresh(tid) + KE * nt; i < P.n_eqw; i += nt) eq_row(g[P.eq_idx[i]]);
 #pragma unroll
     for (int k = 0; k < KR; ++k)
       if (tid + k * nt < P.n_iq) iq_row(rg[k], rs[k], rl[k], ru[k]);
-    for (int i = tid + KR * nt; i < P.n_iq; i += nt) {
+    for (int i = fresh(tid) + KR * nt; i < P.n_iq; i += nt) {
       const int r = P.iq_idx[i];
       iq_row(g[r], s[r], P.iq_lo[i], P.iq_hi[i]);
     }
@@ -1618,7 +1681,7 @@ __global__ __launch_bounds__(ET) void k_step(DevPlan P, DevWork W, int B, int sl
 #pragma unroll
     for (int k = 0; k < KR; ++k)
       if (tid + k * nt < P.n_iq) c = fmax(c, compl_row(rl[k], ru[k], rs[k], rzl[k], rzu[k]));
-    for (int i = tid + KR * nt; i < P.n_iq; i += nt) { const int r = P.iq_idx[i]; c = fmax(c, compl_row(P.iq_lo[i], P.iq_hi[i], s[r], zl[r], zu[r])); }
+    for (int i = fresh(tid) + KR * nt; i < P.n_iq; i += nt) { const int r = P.iq_idx[i]; c = fmax(c, compl_row(P.iq_lo[i], P.iq_hi[i], s[r], zl[r], zu[r])); }
     h_dn = wg_reduce<1>(d, scratch);
     h_cp = wg_reduce<1>(c, scratch);
   }
@@ -1683,7 +1746,7 @@ __global__ __launch_bounds__(ET) void k_step(DevPlan P, DevWork W, int B, int sl
     // the footholds are held from this iterate on: the proximal weights of the stance footholds (eval_terr), the one thing
     // of the linearisation that depends on the latch
     double *Gp = W.stream + (size_t)b * P.stream_len;
-    for (int ti = tid; ti < P.n_terr; ti += nt) {
+    for (int ti = fresh(tid); ti < P.n_terr; ti += nt) {
       const TerrDev TI = P.terr[ti];
       if (TI.d0 >= 0) Gp[TI.d0] = P.hold_weight + TI.ex;
       if (TI.d1 >= 0) Gp[TI.d1] = P.hold_weight + TI.ey;
@@ -1694,11 +1757,18 @@ __global__ __launch_bounds__(ET) void k_step(DevPlan P, DevWork W, int B, int sl
   {
     // barrier weights of every inequality row, right-hand sides of the equality rows (barrier_terms, on the rows in registers;
     // their constraint values as the linearisation above has just written them: the same point as the last line-search
-    // evaluation, but the two evaluation passes need not round alike)
+    // evaluation, but the two evaluation passes need not round alike; bounds, s and z as the update above left them)
+    int rk[KR], ek[KE];
+    fresh_rows(rr, rk);
+    fresh_rows(er, ek);
 #pragma unroll
-    for (int k = 0; k < KR; ++k) rg[k] = g[rr[k]];
+    for (int k = 0; k < KR; ++k) {
+      const int ic = ic_row(k);
+      rg[k] = g[rk[k]]; rs[k] = s[rk[k]]; rzl[k] = zl[rk[k]]; rzu[k] = zu[rk[k]];
+      rl[k] = P.iq_lo[ic]; ru[k] = P.iq_hi[ic];
+    }
 #pragma unroll
-    for (int k = 0; k < KE; ++k) eg[k] = g[er[k]];
+    for (int k = 0; k < KE; ++k) eg[k] = g[ek[k]];
     double *__restrict__ sigp = W.sig + (size_t)b * m, *__restrict__ wp = W.w + (size_t)b * m, *__restrict__ strm = W.stream + (size_t)b * P.stream_len;
     auto bar_row = [&](bool valid, int r, int sp, int wpos, double l, double u, double sv, double zlv, double zuv, double gv) __attribute__((always_inline)) {
       const bool hl = l > -1e19, hu = u < 1e19;
@@ -1716,14 +1786,14 @@ __global__ __launch_bounds__(ET) void k_step(DevPlan P, DevWork W, int B, int sl
     };
 #pragma unroll
     for (int k = 0; k < KE; ++k)
-      if (tid + k * nt < P.n_eqw) strm[P.rhs_pos[er[k]]] = -eg[k];
-    for (int i = tid + KE * nt; i < P.n_eqw; i += nt) { const int r = P.eq_idx[i]; strm[P.rhs_pos[r]] = -g[r]; }
+      if (tid + k * nt < P.n_eqw) strm[P.rhs_pos[ek[k]]] = -eg[k];
+    for (int i = fresh(tid) + KE * nt; i < P.n_eqw; i += nt) { const int r = P.eq_idx[i]; strm[P.rhs_pos[r]] = -g[r]; }
     int spos[KR], wpos[KR];   // (the positions first: their loads are in flight during the divisions)
 #pragma unroll
-    for (int k = 0; k < KR; ++k) { spos[k] = P.sig_pos[rr[k]]; wpos[k] = P.w_pos[rr[k]]; }
+    for (int k = 0; k < KR; ++k) { spos[k] = P.sig_pos[rk[k]]; wpos[k] = P.w_pos[rk[k]]; }
 #pragma unroll
-    for (int k = 0; k < KR; ++k) bar_row(tid + k * nt < P.n_iq, rr[k], spos[k], wpos[k], rl[k], ru[k], rs[k], rzl[k], rzu[k], rg[k]);
-    for (int i = tid + KR * nt; i < P.n_iq; i += nt) {
+    for (int k = 0; k < KR; ++k) bar_row(tid + k * nt < P.n_iq, rk[k], spos[k], wpos[k], rl[k], ru[k], rs[k], rzl[k], rzu[k], rg[k]);
+    for (int i = fresh(tid) + KR * nt; i < P.n_iq; i += nt) {
       const int r = P.iq_idx[i];
       bar_row(true, r, P.sig_pos[r], P.w_pos[r], P.iq_lo[i], P.iq_hi[i], s[r], zl[r], zu[r], g[r]);
     }

@@ -1459,7 +1459,14 @@ __global__ __launch_bounds__(256) void k_shift_warm(DevPlan P, SamplePlan S, con
     else {
       const double t = off + P.var_time[v];
       if (t <= S.T + 1e-9) {
-        const SampleSpline &sp = I.set == 0 ? S.lin : (I.set == 1 ? S.ang : (I.set < 6 ? S.eem[I.set - 2] : S.eef[I.set - 6]));
+        // (picked with constant indices: an index into the splines of the kernel arguments copies all of them to scratch)
+        SampleSpline sp = S.lin;
+        if (I.set == 1) sp = S.ang;
+#pragma unroll
+        for (int e = 0; e < NEE; ++e) {
+          if (I.set == 2 + e) sp = S.eem[e];
+          if (I.set == 6 + e) sp = S.eef[e];
+        }
         double o3[3];
         sample_spline(sp, x, fmin(t, S.T), I.is_vel, o3);
         val = o3[I.dim];
