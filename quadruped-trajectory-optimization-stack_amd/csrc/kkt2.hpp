@@ -548,10 +548,8 @@ __device__ __forceinline__ void sweep_backward_early(const DevPlan &P, const dou
         if (lane < PIV && t >= 0) {
           xs[bps[d]] = x;
           xp[t * PIV + lane] = x;        // by position, for the helper waves (ds = Ji dx)
-#ifndef QTOS_EXP_CHAIN
           sol[t * PIV + lane] = x;       // by unknown position, multipliers included (k_residual)
           if (bun[d] >= 0 && bun[d] < n) dx[bun[d]] = x;
-#endif
         }
         // the block of stage t - 1 against the entries just found
         double c[4];
@@ -576,9 +574,6 @@ __device__ __forceinline__ void sweep_backward_early(const DevPlan &P, const dou
         if (lane < PIV) red[((t - 1) & 1) * 256 + wv * PIV + j] = t >= 1 ? pp : 0.0;
       }
       // ring slot d is free: wave 0 has used the stage's w, slots and unknowns above, the row waves its rows a step ago
-#ifdef QTOS_EXP_CHAIN
-      if (wv != 0)
-#endif
       if (EARLY) fetch(t - SWD, wnext, bv[d], bam[d], bw[d], bps[d], bun[d]);
 #ifdef QTOS_STAMPS
       HSTAMP(c3);
@@ -599,6 +594,398 @@ __device__ __forceinline__ void sweep_backward_early(const DevPlan &P, const dou
 }
 
 
+// ---- the stage code of k_kkt2 and k_kkt3 -------------------------------------------------------------------------------
+// The two kernels are the same arithmetic on the same LDS layout and differ in their schedule only: which wave does what in
+// which phase, and how the chain of stages starts.  What they share is written once here; each kernel body is its schedule.
+
+typedef unsigned short us4_t __attribute__((ext_vector_type(4)));
+
+// diagnostic build (QTOS_STAMPS): per wave, cycles spent in each part of a stage, accumulated by lane 0 in the problem's
+// trace rows (fire-and-forget atomics, no LDS: the diagnostic build has the product's LDS layout and fits the variants that
+// fill it; stamps2.py reads the 192 counters as 64-bit integers).  An empty object in the product.
+struct Kkt2Stamps {
+#ifdef QTOS_STAMPS
+  unsigned long long *row, ts;
+  int wv;
+  bool lead;
+  __device__ __forceinline__ void start(const DevPlan &P, const DevWork &W, int b, int tid) {
+    row = (unsigned long long *)(W.trace + ((size_t)b * (P.max_iter + 1) + 16) * 4);
+    wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    lead = (tid & 63) == 0;
+    ts = 0;
+    if (tid < 192) row[tid] = 0ull;
+    __syncthreads();
+    if (lead) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(ts) :: "memory");
+  }
+  __device__ __forceinline__ void mark(int i) {
+    if (lead) {
+      unsigned long long t;
+      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
+      atomicAdd(row + wv * 12 + i, t - ts);
+      ts = t;
+    }
+  }
+  __device__ __forceinline__ void finish() { mark(6); __syncthreads(); }
+#else
+  __device__ __forceinline__ void start(const DevPlan &, const DevWork &, int, int) {}
+  __device__ __forceinline__ void mark(int) {}
+  __device__ __forceinline__ void finish() {}
+#endif
+};
+
+// What both kernels set up before their stage loop: the LDS carve-up (Kkt2Layout), the record buffers, the problem's arrays
+// and this lane's share of the Schur complement.  li, lk: the lane's row and column group in a 16 x 16 tile as the kernel
+// computed them before its stage loop (the factor wave's block is read with these).
+template <int F>
+struct Kkt2Ctx {
+  using CF = Kkt2Cfg<F>;
+  using LY = Kkt2Layout<F>;
+  // record buffers: [dbuf 0][dbuf 1][sbuf 0][sbuf 1] with LDS-DMA (record s lives in buffer s & 1), one of each without
+  static constexpr int NBUF = F <= 128 ? 2 : 1;
+  double *lds;
+  int li, lk;
+  double *Lib, *dvb, *dgb, *UF, *xs, *red, *PB, *Minv;
+  int *psb, *hib;
+  unsigned *pm;
+  // slot -> pivot index of stages k+2 / k+3 as bytes; within a 16-slot group the rows lk, lk+4, lk+8, lk+12 are adjacent:
+  // one 32-bit read gives a lane the four rows of a tile it holds
+  unsigned char *jmb;
+  int dstride, sstride;
+  double *dbuf0;
+  int *sbuf0, *hiall;
+  double *A;                    // cells of the assembled entries
+  const double *stream;
+  double *panel, *dx;
+  double *minv_g;               // inverse of every pivot block, kept for chord steps
+  // U tiles of this wave: update index uw (Kkt2Cfg), tile t = uw + NU i of the lower triangle
+  int uw;
+  bool is_upd;
+  int tRC[CF::MAXT];            // (R << 8) | C, or -1
+  int tile_lane;                // (li, lk): row li, column lk of a 16 x 16 tile of a panel, in bytes
+  unsigned ge4, gt4;            // bit 4g: row lk + 4g of a diagonal tile lies on or below / strictly below column li
+
+  __device__ __forceinline__ Kkt2Ctx(double *lds_, const DevPlan &P, const DevWork &W, int b, int wv, int li_, int lk_)
+      : lds(lds_), li(li_), lk(lk_) {
+    const int NS = P.n_stages;
+    Lib = lds + LY::LIB; dvb = lds + LY::DVB; dgb = lds + LY::DGB; UF = lds + LY::UF; xs = lds + LY::XS;
+    red = lds + LY::RED; PB = lds + LY::PB; Minv = lds + LY::MIV;
+    psb = (int *)(lds + LY::PSB); hib = (int *)(lds + LY::HIB);
+    pm = (unsigned *)(lds + LY::PM);
+    jmb = (unsigned char *)(lds + LY::JM);
+    dstride = (int)kkt2_dbuf_doubles(F, P.max_drec); sstride = (int)kkt2_sbuf_ints(F, P.max_srec);
+    dbuf0 = lds + LY::VAR;
+    sbuf0 = (int *)(dbuf0 + NBUF * dstride);
+    hiall = sbuf0 + NBUF * sstride;
+    A = (double *)(hiall + ((NS + 4) & ~3));
+    stream = W.stream + (size_t)b * P.stream_len;
+    panel = W.panel + (size_t)b * P.panel_stride;
+    dx = W.dx + (size_t)b * P.n_sol;
+    minv_g = W.minv + (size_t)b * NS * (PIV * PIV);
+    uw = (wv & 3) ? wv - 1 - (wv >> 2) : (wv == 4 ? 12 : (wv == 8 ? 13 : (wv == 12 ? 14 : 99)));
+    is_upd = uw < CF::NU;
+#pragma unroll
+    for (int i = 0; i < CF::MAXT; ++i) {
+      int t = uw + CF::NU * i;
+      bool tv = t < CF::NTILE;
+      int R = 0;
+      while (is_upd && tv && ((R + 1) * (R + 2)) >> 1 <= t) ++R;
+      const bool valid = is_upd && tv;
+      tRC[i] = valid ? (R << 8) | (t - ((R * (R + 1)) >> 1)) : -1;
+    }
+    tile_lane = (li * PLD + lk) * 8;
+    asm volatile("" : "+v"(tile_lane));
+    ge4 = 0u; gt4 = 0u;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) { ge4 |= (lk + 4 * g >= li ? 1u : 0u) << (4 * g); gt4 |= (lk + 4 * g > li ? 1u : 0u) << (4 * g); }
+  }
+};
+
+// the header of record s -- ints hb, doubles hdb -- into the LDS rings (ring slot rs = s mod 3; parity slot s & 1) by threads
+// t = 0 .. 15: pivot slots, diagonals, slot map and mask of stage s
+template <int F>
+__device__ __forceinline__ void kkt2_publish_header(const Kkt2Ctx<F> &cx, const int *hb, const double *hdb, int s, int rs, int t) {
+  if (t == 0) { const int hv = hb[3]; cx.hib[rs] = hv; cx.hiall[s] = (hv + 15) & ~15; }
+  if (t < PIV) {
+    const int hv = hb[SHDR + t];
+    cx.dgb[rs * PIV + t] = hdb[t];
+    cx.psb[rs * PIV + t] = hv;
+    cx.jmb[(s & 1) * Kkt2Cfg<F>::FR + (hv & ~15) + (hv & 3) * 4 + ((hv >> 2) & 3)] = (unsigned char)t;
+    atomicOr(&cx.pm[(s & 1) * 8 + (hv >> 5)], 1u << (hv & 31));
+  }
+}
+
+// LDS-DMA of the records of stage s into buffer s & 1 by nw waves (1 KB per instruction, chunk c of a record by the wave with
+// wi = c mod nw: wi 0 takes the chunks with the header).  The caller waits for them (vmcnt) before the phase's barrier.
+template <int F>
+__device__ __forceinline__ void kkt2_dma_records(const Kkt2Ctx<F> &cx, const DevPlan &P, int s, int wi, int nw, int lane) {
+  int d0, d1, s0, s1;
+  sload2(P.drec_off + s, d0, d1);
+  sload2(P.srec_off + s, s0, s1);
+  const int nbd = (d1 - d0) * 8, nbs = (s1 - s0) * 4;
+  const char *gd = (const char *)(cx.stream + d0), *gs = (const char *)(P.srec + s0);
+  typedef __attribute__((address_space(3))) char lds_char;
+  lds_char *ld = (lds_char *)(cx.dbuf0 + (s & 1) * cx.dstride), *ls = (lds_char *)(cx.sbuf0 + (s & 1) * cx.sstride);
+  for (int c = wi; c * 1024 < nbd; c += nw)
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(gd + min(c * 1024 + lane * 16, nbd - 16)), (__attribute__((address_space(3))) void *)(ld + c * 1024), 16, 0, 0);
+  for (int c = wi; c * 1024 < nbs; c += nw)
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(gs + min(c * 1024 + lane * 16, nbs - 16)), (__attribute__((address_space(3))) void *)(ls + c * 1024), 16, 0, 0);
+}
+
+// wave 0 in C(k): LDL^T + L^-1 + (L D L^T)^-1 of the pivot block of the panel Pn, then the pivot rows leave the panel
+// (myps: pivot slot of the lane's row li, ps: the stage's pivot slots in LDS; the inverse also to HBM as block ks)
+template <int F>
+__device__ __forceinline__ void kkt2_factor_block(const Kkt2Ctx<F> &cx, double *Pn, const int myps, const int *ps, double *Lin, double *dvn, int ks) {
+  const int li = cx.li, lk = cx.lk;
+  // split layout (ldlt16s): lane (li, lk) holds row li of the block, columns c = 4 g + lk.  The pivot rows of the panel
+  // carry the block's lower triangle (by pivot index): the entries above the diagonal are read from the mirrored
+  // position, so the block that is factored is exactly symmetric
+  double a[4], wi[4], myinv;
+  double *prow_p = Pn + myps * PLD + lk;
+  int pc[4];
+#pragma unroll
+  for (int g = 0; g < 4; ++g) pc[g] = ps[4 * g + lk];
+#pragma unroll
+  for (int g = 0; g < 4; ++g) a[g] = 4 * g + lk > li ? Pn[pc[g] * PLD + li] : prow_p[4 * g];
+  ldlt16s(a, wi, myinv, li, lk);
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    Lin[li * PLD + 4 * g + lk] = wi[g];
+    prow_p[4 * g] = 0.0;   // the pivot rows leave the panel
+  }
+  if (lk == (li & 3)) dvn[li] = myinv;
+  {
+    double zero = 0.0;
+    asm volatile("" : "+v"(zero));
+    d4_t mi = {zero, zero, zero, zero};
+    double lt[4], ld[4];
+#pragma unroll
+    for (int s4 = 0; s4 < 4; ++s4) { lt[s4] = Lin[(lk + 4 * s4) * PLD + li]; ld[s4] = dvn[lk + 4 * s4]; }
+#pragma unroll
+    for (int s4 = 0; s4 < 4; ++s4) mi = __builtin_amdgcn_mfma_f64_16x16x4f64(lt[s4], lt[s4] * ld[s4], mi, 0, 0, 0);
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      cx.Minv[(lk + 4 * g) * PLD + li] = mi[g];
+      cx.minv_g[(size_t)ks * (PIV * PIV) + (lk + 4 * g) * PIV + li] = mi[g];
+    }
+  }
+}
+
+// AB(k) on tile wave R: V = P (L D L^T)^-1 of row tile R of the panel Pk (the rows of am_word's mask to the factor panel in
+// HBM), the tile's part of the next pivot columns into Xn, and the operands of the Schur update into LDS.  ct_cur: the
+// tile's cells of the next pivot columns; rs1: ring slot of stage k+1.
+template <int F>
+__device__ __forceinline__ void kkt2_ab_tile(const Kkt2Ctx<F> &cx, int k, int R, int li, int lk, const double *Pk, double *Yk, double *Xn,
+                                             bool has_next, int prow_next, const Mask256 &m1, us4_t ct_cur, unsigned am_word, int rs1) {
+  using LY = Kkt2Layout<F>;
+  constexpr int pstride = (F + 1) * PIV;   // per stage: w (16), V (F x 16)
+  const int prow = has_next ? prow_next : 0;
+  // operands in the order they are needed (register budget: 128 per lane with sixteen waves)
+  double pr[4], lm[4];
+#pragma unroll
+  for (int s4 = 0; s4 < 4; ++s4) {
+    pr[s4] = Pk[(16 * R + li) * PLD + lk + 4 * s4];
+    lm[s4] = cx.Minv[li * PLD + lk + 4 * s4];
+  }
+  double zero = 0.0;
+  asm volatile("" : "+v"(zero));   // (a loop-invariant zero pair would be kept across the loop -- and spilled)
+  // V = P (L D L^T)^-1 in accumulator layout: vt[g] = V[16R+li][lk+4g] -- V itself as the A operand of the next product
+  d4_t vt = {zero, zero, zero, zero};
+#pragma unroll
+  for (int s4 = 0; s4 < 4; ++s4) vt = __builtin_amdgcn_mfma_f64_16x16x4f64(lm[s4], pr[s4], vt, 0, 0, 0);
+  // next pivot columns: assembled entries (cell table: 0 = the zero cell), extracted Schur updates, pivot
+  // diagonal, minus V P[piv]^T (= Y D^-1 Y[piv]^T: the raw rows of the next pivots are the B operand)
+  double npp[4], xv[4], av[4];
+  int aidx[4];
+#pragma unroll
+  for (int s4 = 0; s4 < 4; ++s4) {
+    const int r = 16 * R + lk + 4 * s4;
+    npp[s4] = Pk[prow * PLD + lk + 4 * s4];
+    xv[s4] = Xn[r * PLD + li];
+    aidx[s4] = ct_cur[s4];
+    av[s4] = cx.A[aidx[s4]];
+  }
+  const double dgn = cx.dgb[rs1 * PIV + li];
+  d4_t acc;
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    const int r = 16 * R + lk + 4 * g;
+    acc[g] = xv[g] + av[g] + (r == prow ? dgn : 0.0);
+    npp[g] = -npp[g];
+  }
+#pragma unroll
+  for (int s4 = 0; s4 < 4; ++s4) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(vt[s4], npp[s4], acc, 0, 0, 0);   // acc -= V P[piv]^T
+#pragma unroll
+  for (int g = 0; g < 4; ++g) cx.A[aidx[g]] = 0.0;   // retired (the zero cell stays zero)
+  if constexpr (LY::VP) {
+    // operands of the Schur update: -V (accumulator layout -> row-major) and the raw rows, next pivots' rows blanked
+    const bool myrowpiv = has_next && ((grp16(m1, R) >> li) & 1u);
+    double *Pm = cx.lds + LY::PMB;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      Yk[(16 * R + li) * PLD + lk + 4 * g] = myrowpiv ? 0.0 : -vt[g];
+      Pm[(16 * R + li) * PLD + lk + 4 * g] = myrowpiv ? 0.0 : pr[g];
+    }
+  } else
+  // Y = P L^-T of this tile: here for the tiles without a partner wave, else on k_kkt2's service wave R
+  if (R == 0 || R >= Kkt2Cfg<F>::NSV) {
+    const double *Lik = cx.Lib + (k & 1) * PIV * PLD;
+    double la[4];
+#pragma unroll
+    for (int s4 = 0; s4 < 4; ++s4) la[s4] = Lik[li * PLD + lk + 4 * s4];
+    d4_t yt = {zero, zero, zero, zero};
+#pragma unroll
+    for (int s4 = 0; s4 < 4; ++s4)
+      yt = __builtin_amdgcn_mfma_f64_16x16x4f64(la[s4], pr[s4], yt, 0, 0, 0);   // yt[g] = Y[16R+li][lk+4g]
+    const bool myrowpiv = has_next && ((grp16(m1, R) >> li) & 1u);
+#pragma unroll
+    for (int g = 0; g < 4; ++g) Yk[(16 * R + li) * PLD + lk + 4 * g] = myrowpiv ? 0.0 : yt[g];
+  }
+  if (has_next) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) Xn[(16 * R + lk + 4 * g) * PLD + li] = acc[g];
+  }
+  const unsigned am16 = (am_word >> ((R & 1) * 16)) & 0xffffu;
+  if ((am16 >> li) & 1u) {
+    double *pv = cx.panel + (size_t)k * pstride + PIV;
+    *(d4_t *)(pv + (16 * R + li) * PIV + 4 * lk) = vt;
+  }
+}
+
+// AB(k) on the right-hand-side wave: w = (L D L^T)^-1 p_F (to the factor panel if store_w), rhs -= P w, and the right-hand side
+// of the next pivots (assembled in cell rc_cur) into Xn
+template <int F>
+__device__ __forceinline__ void kkt2_ab_rhs(const Kkt2Ctx<F> &cx, int k, int lane, int li, int lk, const double *Pk, double *Xn,
+                                            bool has_next, int prow_next, int rc_cur, bool store_w) {
+  constexpr int FR = Kkt2Cfg<F>::FR, pstride = (F + 1) * PIV;
+  double part = 0.0;
+#pragma unroll
+  for (int s4 = 0; s4 < 4; ++s4) part = fma(cx.Minv[li * PLD + lk + 4 * s4], Pk[F * PLD + lk + 4 * s4], part);
+  part = rowsum4(part);                    // w[li] on every lane
+  if (lane < PIV && store_w) cx.panel[(size_t)k * pstride + lane] = part;
+  if (has_next) {
+    asm volatile("s_nop 4" : "+v"(part));    // DPP hazard distance for the broadcast reads below
+#pragma unroll
+    for (int c = 0; c < FR / 64; ++c) {
+      const int r = c * 64 + lane;
+      const int rr = min(r, F - 1);
+      double pq[PIV];
+#pragma unroll
+      for (int q = 0; q < PIV; ++q) pq[q] = Pk[rr * PLD + q];
+      const double uf = cx.UF[r];
+      double a0 = 0.0;
+      dot16_steps<0>(a0, part, pq);
+      cx.UF[r] = r < F ? uf - a0 : 0.0;
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    if (lane < PIV) {
+      const int c = prow_next;
+      Xn[F * PLD + lane] = cx.A[rc_cur] + cx.UF[c];
+      cx.A[rc_cur] = 0.0;
+      cx.UF[c] = 0.0;
+    }
+  }
+}
+
+// C(k) on an update wave: U -= V P^T on the wave's Schur tiles (if products), then the columns of stage k+2 leave the tiles
+// for the dead panel Pk
+template <int F>
+__device__ __forceinline__ void kkt2_update(const Kkt2Ctx<F> &cx, Kkt2Stamps &st, d4_t (&U)[Kkt2Cfg<F>::MAXT], int k, int NS, int lane,
+                                            int li, int lk, double *Pk, const double *Yk, bool products) {
+  using LY = Kkt2Layout<F>;
+  constexpr int MAXT2 = Kkt2Cfg<F>::MAXT, FR = Kkt2Cfg<F>::FR;
+  const Mask256 m2 = load_mask8(cx.pm + (k & 1) * 8, lane);   // pivot slots of stage k+2
+  const bool extract = k + 2 < NS;
+  const unsigned char *jm2 = cx.jmb + (k & 1) * FR;
+  double *Xnn = Pk;   // the panel of stage k is dead: it receives the columns of stage k+2
+  double dv4[4];
+  if constexpr (!LY::VP) {
+    const double *dik = cx.dvb + (k & 1) * PIV;
+#pragma unroll
+    for (int s4 = 0; s4 < 4; ++s4) dv4[s4] = -dik[lk + 4 * s4];
+  }
+  const double *Bop = LY::VP ? cx.lds + LY::PMB : Yk;
+  int rcs[MAXT2];
+#pragma unroll
+  for (int t = 0; t < MAXT2; ++t) { rcs[t] = cx.tRC[t]; asm volatile("" : "+s"(rcs[t])); }
+  double wa[2][4], pbv[2][4];
+  // operand addresses: a lane part that never changes (tile_lane, bytes) plus a wave-uniform tile offset formed on the
+  // scalar unit
+  auto tile_loads = [&](int rc, double (&w)[4], double (&pq)[4]) __attribute__((always_inline)) {
+    const int R = rc < 0 ? 0 : rc >> 8, C = rc < 0 ? 0 : rc & 255;
+    const int oR = __builtin_amdgcn_readfirstlane(R * (16 * PLD * 8)), oC = __builtin_amdgcn_readfirstlane(C * (16 * PLD * 8));
+    const char *wrow = (const char *)Yk + (cx.tile_lane + oR), *prow2 = (const char *)Bop + (cx.tile_lane + oC);
+#pragma unroll
+    for (int s4 = 0; s4 < 4; ++s4) { w[s4] = *(const double *)(wrow + 32 * s4); pq[s4] = *(const double *)(prow2 + 32 * s4); }
+  };
+  // pivot indices of the columns (li) and of the four rows (lk + 4g) this lane holds in each tile: fetched ahead of
+  // the products (the extraction behind them starts with no LDS round trip of its own: -5.5 % per launch)
+  int jc8[MAXT2], jr32[MAXT2];
+#pragma unroll
+  for (int t = 0; t < MAXT2; ++t) {
+    const int rc = rcs[t] < 0 ? 0 : rcs[t];
+    jc8[t] = jm2[16 * (rc & 255) + (li & 3) * 4 + (li >> 2)];
+    jr32[t] = *(const int *)(jm2 + 16 * (rc >> 8) + 4 * lk);
+  }
+  if (products) {
+    tile_loads(rcs[0], wa[0], pbv[0]);
+#pragma unroll
+    for (int t = 0; t < MAXT2; ++t) {
+      if (t + 1 < MAXT2) tile_loads(rcs[t + 1], wa[(t + 1) & 1], pbv[(t + 1) & 1]);
+#pragma unroll
+      for (int s4 = 0; s4 < 4; ++s4)
+        U[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(LY::VP ? wa[t & 1][s4] : wa[t & 1][s4] * dv4[s4], pbv[t & 1][s4], U[t], 0, 0, 0);
+    }
+  }
+  st.mark(5);
+  if (extract) {
+    int jcs[MAXT2], jrs[MAXT2][4];
+#pragma unroll
+    for (int t = 0; t < MAXT2; ++t) {
+      jcs[t] = jc8[t];
+#pragma unroll
+      for (int g = 0; g < 4; ++g) jrs[t][g] = (jr32[t] >> (8 * g)) & 255;
+    }
+    double *dummy = cx.red + 2 * 16 * PIV + lane;
+    const unsigned ge4 = cx.ge4, gt4 = cx.gt4;
+#pragma unroll
+    for (int t = 0; t < MAXT2; ++t) {
+      const int rc = rcs[t];
+      if (rc < 0) continue;
+      const int R = rc >> 8, C = rc & 255;
+      const unsigned cw2 = grp16(m2, C), rw2 = grp16(m2, R);
+      if ((cw2 | rw2) == 0u) continue;
+      const unsigned cm = ((cw2 >> li) & 1u) ? (R > C ? 0x1111u : ge4) : 0u;
+      const unsigned rmk = (rw2 >> lk) & (R > C ? 0x1111u : gt4);
+      double *xr = Xnn + (16 * R + lk) * PLD + jcs[t], *xc = Xnn + (16 * C + li) * PLD;
+      if (cw2) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) *(((cm >> (4 * g)) & 1u) ? xr + g * 4 * PLD : dummy) = U[t][g];
+      }
+      if (rw2) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) *(((rmk >> (4 * g)) & 1u) ? xc + jrs[t][g] : dummy) = U[t][g];
+      }
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int z = ~__builtin_amdgcn_sbfe((int)(cm | rmk), 4 * g, 1);
+        U[t][g] = __hiloint2double(__double2hiint(U[t][g]) & z, __double2loint(U[t][g]) & z);
+      }
+    }
+  }
+}
+
+// backward substitution (sweep_backward: one barrier per stage, one-stage look-ahead), the sweep tables in LDS where the
+// panels were.  The caller has drained the factor-panel stores (__syncthreads): they are read back here.
+template <int F>
+__device__ __forceinline__ void kkt2_backward(const Kkt2Ctx<F> &cx, const DevPlan &P, const DevWork &W, int b, int tid, int wv, int lane) {
+  const int NS = P.n_stages;
+  int *nxp = (int *)cx.PB;   // (the panels are dead)
+  for (int i = tid; i < NS * 4; i += KT2) nxp[i] = P.nxt_pack[i];
+  for (int i = tid; i < NS * 8; i += KT2) nxp[NS * 4 + i] = (int)P.amask2[i];
+  __syncthreads();
+  const SweepDs sd = {W.stream + (size_t)b * P.stream_len, W.ds + (size_t)b * P.n_cons, W.g + (size_t)b * P.n_cons, W.s + (size_t)b * P.n_cons, W.trace ? W.trace + ((size_t)b * (P.max_iter + 1) + 64) * 4 : nullptr};
+  sweep_backward<F>(P, cx.panel, cx.dx, W.sol + (size_t)b * P.n_stages * PIV, cx.xs, cx.red, nxp, wv, lane, cx.lds + ((Kkt2Layout<F>::PB + NS * 6 + 1) & ~1), sd);
+}
 
 template <int F, bool CONT, bool KRON = false>
 __global__ __launch_bounds__(KT2) void k_kkt2(DevPlan P, DevWork W, int B) {
@@ -607,110 +994,31 @@ __global__ __launch_bounds__(KT2) void k_kkt2(DevPlan P, DevWork W, int B) {
   extern __shared__ double lds[];
   using CF = Kkt2Cfg<F>;
   using LY = Kkt2Layout<F>;
-  constexpr int NT = CF::NT, NU = CF::NU, MAXT2 = CF::MAXT, NSV = CF::NSV, NH = CF::NH, FR = CF::FR, PSZ = LY::PSZ;
+  constexpr int NT = CF::NT, NU = CF::NU, MAXT2 = CF::MAXT, NSV = CF::NSV, FR = CF::FR, PSZ = LY::PSZ;
   const int tid = threadIdx.x, NS = P.n_stages, n = P.n_sol;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, li = lane & 15, lk = lane >> 4;
-  double *Lib = lds + LY::LIB, *dvb = lds + LY::DVB, *dgb = lds + LY::DGB, *UF = lds + LY::UF, *xs = lds + LY::XS;
-  double *red = lds + LY::RED, *PB = lds + LY::PB, *dbuf = lds + LY::VAR;
-  int *psb = (int *)(lds + LY::PSB), *hib = (int *)(lds + LY::HIB), *jm = (int *)(lds + LY::JM);
-  unsigned *pm = (unsigned *)(lds + LY::PM);
-  // slot -> pivot index of stages k+2 / k+3 as bytes; within a 16-slot group the rows lk, lk+4, lk+8, lk+12 are adjacent:
-  // one 32-bit read gives a lane the four rows of a tile it holds
-  unsigned char *jmb = (unsigned char *)jm;
-  double *Minv = lds + LY::MIV;
+  const Kkt2Ctx<F> cx(lds, P, W, b, wv, li, lk);
   double *ksm = (double *)((char *)lds + (KRON ? P.kron_lds_off : 0));   // KRON: the 33 sums of the Kronecker blocks of the record about to be assembled
-  // record buffers: [dbuf 0][dbuf 1][sbuf 0][sbuf 1] with DMA (record s lives in buffer s & 1), one of each without
-  constexpr bool DMA = F <= 128;
-  constexpr int NBUF = DMA ? 2 : 1;
-  const int dstride = (int)kkt2_dbuf_doubles(F, P.max_drec), sstride = (int)kkt2_sbuf_ints(F, P.max_srec);
-  double *const dbuf0 = dbuf;
-  int *const sbuf0 = (int *)(dbuf + NBUF * dstride);
-  int *sbuf = sbuf0;
-  int *hiall = sbuf0 + NBUF * sstride;
-  double *A = (double *)(hiall + ((NS + 4) & ~3));   // cells of the assembled entries
-  const double *stream = W.stream + (size_t)b * P.stream_len;
-  double *panel = W.panel + (size_t)b * P.panel_stride;
-  double *dx = W.dx + (size_t)b * n;
-  const int pstride = (F + 1) * PIV;   // per stage: w (16), V (F x 16)
-
-  // ---- U tiles of this wave: update index uw (Kkt2Cfg), tile t = uw + NU i of the lower triangle ---------
-  const int uw = (wv & 3) ? wv - 1 - (wv >> 2) : (wv == 4 ? 12 : (wv == 8 ? 13 : (wv == 12 ? 14 : 99)));
-  const bool is_upd = uw < NU;
+  constexpr bool DMA = F <= 128;   // records by LDS-DMA into two buffers, else through prefetch registers into one
+  double *dbuf = cx.dbuf0;
+  int *sbuf = cx.sbuf0;
   d4_t U[MAXT2];
-  int tRC[MAXT2];   // (R << 8) | C, or -1
 #pragma unroll
-  for (int i = 0; i < MAXT2; ++i) {
-    U[i] = d4_t{0.0, 0.0, 0.0, 0.0};
-    int t = uw + NU * i;
-    bool tv = t < CF::NTILE;
-    int R = 0;
-    while (is_upd && tv && ((R + 1) * (R + 2)) >> 1 <= t) ++R;
-    const bool valid = is_upd && tv;
-    tRC[i] = valid ? (R << 8) | (t - ((R * (R + 1)) >> 1)) : -1;
-  }
-
-  int tile_lane = (li * PLD + lk) * 8;   // (li, lk): row li, column lk of a 16 x 16 tile of a panel, in bytes
-  asm volatile("" : "+v"(tile_lane));
-  unsigned ge4_keep = 0u, gt4_keep = 0u;
-#pragma unroll
-  for (int g = 0; g < 4; ++g) { ge4_keep |= (lk + 4 * g >= li ? 1u : 0u) << (4 * g); gt4_keep |= (lk + 4 * g > li ? 1u : 0u) << (4 * g); }
-  for (int i = tid; i < P.n_cells; i += KT2) A[i] = 0.0;
-  for (int i = tid; i < 3 * PSZ; i += KT2) PB[i] = 0.0;
-  for (int i = tid; i < FR; i += KT2) { UF[i] = 0.0; xs[i] = 0.0; }
-  for (int v = tid; v < n; v += KT2) dx[v] = 0.0;
+  for (int i = 0; i < MAXT2; ++i) U[i] = d4_t{0.0, 0.0, 0.0, 0.0};
+  for (int i = tid; i < P.n_cells; i += KT2) cx.A[i] = 0.0;
+  for (int i = tid; i < 3 * PSZ; i += KT2) cx.PB[i] = 0.0;
+  for (int i = tid; i < FR; i += KT2) { cx.UF[i] = 0.0; cx.xs[i] = 0.0; }
+  for (int v = tid; v < n; v += KT2) cx.dx[v] = 0.0;
   __syncthreads();
 
   auto header_from_lds = [&](int s) __attribute__((always_inline)) {
-    if (tid < 8) pm[(s & 1) * 8 + tid] = 0u;
-    if (tid < PIV) {
-      const int slot = sbuf[SHDR + tid];
-      psb[(s % 3) * PIV + tid] = slot;
-      jmb[(s & 1) * FR + (slot & ~15) + (slot & 3) * 4 + ((slot >> 2) & 3)] = (unsigned char)tid;
-      dgb[(s % 3) * PIV + tid] = dbuf[tid];
-      atomicOr(&pm[(s & 1) * 8 + (slot >> 5)], 1u << (slot & 31));
-    }
-    if (tid == 0) { hib[s % 3] = sbuf[3]; hiall[s] = (sbuf[3] + 15) & ~15; }
+    if (tid < 8) cx.pm[(s & 1) * 8 + tid] = 0u;
+    kkt2_publish_header(cx, sbuf, dbuf, s, s % 3, tid);
   };
   auto load_records = [&](int s) __attribute__((always_inline)) {
     const int s0 = P.srec_off[s], s1 = P.srec_off[s + 1], d0 = P.drec_off[s], d1 = P.drec_off[s + 1];
     for (int i = tid; i < s1 - s0; i += KT2) sbuf[i] = P.srec[s0 + i];
-    for (int i = tid; i < d1 - d0; i += KT2) dbuf[i] = stream[d0 + i];
-  };
-  // wave 0: LDL^T + L^-1 + (L D L^T)^-1 of the pivot block of the panel Pn, then the pivot rows leave the panel
-  double *minv_g = W.minv + (size_t)b * NS * (PIV * PIV);   // inverse of every pivot block, kept for chord steps
-  auto factor_block = [&](double *Pn, const int myps, const int *ps, double *Lin, double *dvn, int ks) __attribute__((always_inline)) {
-    // split layout (ldlt16s): lane (li, lk) holds row li of the block, columns c = 4 g + lk.  The pivot rows of the panel
-    // carry the block's lower triangle (by pivot index): the entries above the diagonal are read from the mirrored
-    // position, so the block that is factored is exactly symmetric (ps = the stage's pivot slots in LDS)
-    double a[4], wi[4], myinv;
-    double *prow_p = Pn + myps * PLD + lk;
-    int pc[4];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) pc[g] = ps[4 * g + lk];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) a[g] = 4 * g + lk > li ? Pn[pc[g] * PLD + li] : prow_p[4 * g];
-    ldlt16s(a, wi, myinv, li, lk);
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      Lin[li * PLD + 4 * g + lk] = wi[g];
-      prow_p[4 * g] = 0.0;   // the pivot rows leave the panel
-    }
-    if (lk == (li & 3)) dvn[li] = myinv;
-    {
-      double zero = 0.0;
-      asm volatile("" : "+v"(zero));
-      d4_t mi = {zero, zero, zero, zero};
-      double lt[4], ld[4];
-#pragma unroll
-      for (int s4 = 0; s4 < 4; ++s4) { lt[s4] = Lin[(lk + 4 * s4) * PLD + li]; ld[s4] = dvn[lk + 4 * s4]; }
-#pragma unroll
-      for (int s4 = 0; s4 < 4; ++s4) mi = __builtin_amdgcn_mfma_f64_16x16x4f64(lt[s4], lt[s4] * ld[s4], mi, 0, 0, 0);
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        Minv[(lk + 4 * g) * PLD + li] = mi[g];
-        minv_g[(size_t)ks * (PIV * PIV) + (lk + 4 * g) * PIV + li] = mi[g];
-      }
-    }
+    for (int i = tid; i < d1 - d0; i += KT2) dbuf[i] = cx.stream[d0 + i];
   };
   auto assemble_continuations = [&](int t0, int nth) __attribute__((always_inline)) {
     if constexpr (!CONT) return;
@@ -721,17 +1029,17 @@ __global__ __launch_bounds__(KT2) void k_kkt2(DevPlan P, DevWork W, int B) {
       lds_barrier();
       const int *co = P.cont + 4 * (c_first + c);
       const int so = co[0], sl = co[1], dof = co[2], dl = co[3];
-      for (int i = threadIdx.x; i < dl; i += KT2) dbuf[i] = stream[dof + i];
+      for (int i = threadIdx.x; i < dl; i += KT2) dbuf[i] = cx.stream[dof + i];
       for (int i = threadIdx.x; i < sl; i += KT2) sbuf[i] = P.srec[so + i];
       lds_barrier();
-      if (t0 >= 0) assemble_stage(A, F, sbuf, dbuf, t0, nth);
+      if (t0 >= 0) assemble_stage(cx.A, F, sbuf, dbuf, t0, nth);
     }
   };
 
   // ---- prologue: assemble stages 0 and 1, gather and factor the pivot block of stage 0, leave the
   //      records of stage 2 in LDS ----------------------------------------------------------------
   auto point_buffers = [&](int s) __attribute__((always_inline)) {   // the buffer that holds the records of stage s
-    if constexpr (DMA) { dbuf = dbuf0 + (s & 1) * dstride; sbuf = sbuf0 + (s & 1) * sstride; }
+    if constexpr (DMA) { dbuf = cx.dbuf0 + (s & 1) * cx.dstride; sbuf = cx.sbuf0 + (s & 1) * cx.sstride; }
   };
   point_buffers(0);
   load_records(0);
@@ -739,27 +1047,27 @@ __global__ __launch_bounds__(KT2) void k_kkt2(DevPlan P, DevWork W, int B) {
   header_from_lds(0);
   if constexpr (KRON) kron_sums(sbuf, dbuf, ksm, wv, 16, lane);
   __syncthreads();
-  if constexpr (KRON) assemble_stage_kron(A, F, sbuf, dbuf, ksm, tid, KT2); else
-  assemble_stage(A, F, sbuf, dbuf, tid, KT2);
+  if constexpr (KRON) assemble_stage_kron(cx.A, F, sbuf, dbuf, ksm, tid, KT2); else
+  assemble_stage(cx.A, F, sbuf, dbuf, tid, KT2);
   assemble_continuations(tid, KT2);
   __syncthreads();
   {
-    double *P0 = PB;
-    const int *ps0 = psb;
+    double *P0 = cx.PB;
+    const int *ps0 = cx.psb;
     auto cell0 = [&](int r, int j) __attribute__((always_inline)) {
       return r < F ? (int)P.ctab[(((r >> 4) * 64) + (r & 3) * 16 + j) * 4 + ((r & 15) >> 2)] : P.rtab[j];
     };
     for (int i = tid; i < (F + 1) * PIV; i += KT2) {
       const int r = i >> 4, j = i & 15, c = ps0[j];
-      P0[r * PLD + j] = A[cell0(r, j)] + (r == c ? dgb[j] : 0.0);
+      P0[r * PLD + j] = cx.A[cell0(r, j)] + (r == c ? cx.dgb[j] : 0.0);
     }
     __syncthreads();
     for (int i = tid; i < (F + 1) * PIV; i += KT2) {
       const int r = i >> 4, j = i & 15;
-      A[cell0(r, j)] = 0.0;
+      cx.A[cell0(r, j)] = 0.0;
     }
     __syncthreads();
-    if (wv == 0) factor_block(P0, ps0[li], ps0, Lib, dvb, 0);
+    if (wv == 0) kkt2_factor_block(cx, P0, ps0[li], ps0, cx.Lib, cx.dvb, 0);
   }
   for (int s = 1; s < 3 && s < NS; ++s) {
     point_buffers(s);
@@ -769,34 +1077,20 @@ __global__ __launch_bounds__(KT2) void k_kkt2(DevPlan P, DevWork W, int B) {
     if constexpr (KRON) { if (s == 1) kron_sums(sbuf, dbuf, ksm, wv, 16, lane); }
     __syncthreads();
     if (s == 1) {
-      if constexpr (KRON) assemble_stage_kron(A, F, sbuf, dbuf, ksm, tid, KT2); else
-      assemble_stage(A, F, sbuf, dbuf, tid, KT2);
+      if constexpr (KRON) assemble_stage_kron(cx.A, F, sbuf, dbuf, ksm, tid, KT2); else
+      assemble_stage(cx.A, F, sbuf, dbuf, tid, KT2);
       assemble_continuations(tid, KT2);
     }
     __syncthreads();
   }
 
-#ifdef QTOS_STAMPS
-  // diagnostic build: per wave, cycles spent in each part of a stage (accumulated in LDS by lane 0)
-  // (the counters live in the trace rows themselves -- fire-and-forget atomics of lane 0 --: no LDS, so that the diagnostic
-  //  build has the product's LDS layout and fits the variants that fill it)
-  unsigned long long *st2g = (unsigned long long *)(W.trace + ((size_t)b * (P.max_iter + 1) + 16) * 4);
-  unsigned long long ts_ = 0;
-  if (tid < 192) st2g[tid] = 0ull;
-  __syncthreads();
-#define KS2_START() do { if (lane == 0) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(ts_) :: "memory"); } while (0)
-#define KS2(i) do { if (lane == 0) { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); atomicAdd(st2g + wv * 12 + (i), t_ - ts_); ts_ = t_; } } while (0)
-  KS2_START();
-#else
-#define KS2_START() do {} while (0)
-#define KS2(i) do {} while (0)
-#endif
+  Kkt2Stamps st;
+  st.start(P, W, b, tid);
   // per-thread prefetch registers: one 128-bit load of doubles and two of ints cover the longest record
   d2_t pfd;
   i4_t pfs0, pfs1;
   int pf_nd2 = 0, pf_ns4 = 0;
-  int prow_next = NS > 1 ? psb[PIV + li] : 0;   // pivot slot li of stage k+1
-  typedef unsigned short us4_t __attribute__((ext_vector_type(4)));
+  int prow_next = NS > 1 ? cx.psb[PIV + li] : 0;   // pivot slot li of stage k+1
   const us4_t *ctab4 = (const us4_t *)P.ctab;
   us4_t ct_cur = ctab4[((size_t)min(1, NS - 1) * NT + min(wv, NT - 1)) * 64 + lane];
   int rc_cur = P.rtab[min(1, NS - 1) * PIV + li];   // cell of the assembled rhs of pivot li of stage k+1
@@ -806,10 +1100,9 @@ __global__ __launch_bounds__(KT2) void k_kkt2(DevPlan P, DevWork W, int B) {
     asm volatile("" : "+v"(tid), "+v"(lane));
     const int li = lane & 15, lk = lane >> 4;
     const int pb = (k & 1) ? 2 : 0;
-    double *Pk = PB + pb * PSZ, *Yk = PB + PSZ, *Xn = PB + (2 - pb) * PSZ;
-    const double *Lik = Lib + (k & 1) * PIV * PLD, *dik = dvb + (k & 1) * PIV;
+    double *Pk = cx.PB + pb * PSZ, *Yk = cx.PB + PSZ, *Xn = cx.PB + (2 - pb) * PSZ;
     const bool has_next = k + 1 < NS;
-    KS2(7);
+    st.mark(7);
     // ---- install the records of stage k+2 (prefetched during phase C of the previous stage; the records of
     //      stage 2 are in LDS since the prologue).  Wave w holds elements 64 rank(w) ..: the record's header sits
     //      in the registers of wave 12 (rank 0), which publishes it. ------------------------------------
@@ -826,112 +1119,14 @@ __global__ __launch_bounds__(KT2) void k_kkt2(DevPlan P, DevWork W, int B) {
     const us4_t ct_nxt = ctab4[((size_t)min(k + 2, NS - 1) * NT + min(wv, NT - 1)) * 64 + lane];
     const int rc_nxt = P.rtab[min(k + 2, NS - 1) * PIV + li];
     // ---- AB(k) ----------------------------------------------------------------------------------------
-    const Mask256 m1 = load_mask8(pm + ((k + 1) & 1) * 8, lane);   // pivot slots of stage k+1
+    const Mask256 m1 = load_mask8(cx.pm + ((k + 1) & 1) * 8, lane);   // pivot slots of stage k+1
     if (wv < NT) {
-      const int R = wv;
-      const unsigned am_word = P.amask[k * 8 + (R >> 1)];
-      const int prow = has_next ? prow_next : 0;
-      // operands in the order they are needed (register budget: 128 per lane with sixteen waves)
-      double pr[4], lm[4];
-#pragma unroll
-      for (int s4 = 0; s4 < 4; ++s4) {
-        pr[s4] = Pk[(16 * R + li) * PLD + lk + 4 * s4];
-        lm[s4] = Minv[li * PLD + lk + 4 * s4];
-      }
-      double zero = 0.0;
-      asm volatile("" : "+v"(zero));   // (a loop-invariant zero pair would be kept across the loop -- and spilled)
-      // V = P (L D L^T)^-1 in accumulator layout: vt[g] = V[16R+li][lk+4g] -- V itself as the A operand of the next product
-      d4_t vt = {zero, zero, zero, zero};
-#pragma unroll
-      for (int s4 = 0; s4 < 4; ++s4) vt = __builtin_amdgcn_mfma_f64_16x16x4f64(lm[s4], pr[s4], vt, 0, 0, 0);
-      // next pivot columns: assembled entries (cell table: 0 = the zero cell), extracted Schur updates, pivot
-      // diagonal, minus V P[piv]^T (= Y D^-1 Y[piv]^T: the raw rows of the next pivots are the B operand)
-      double npp[4], xv[4], av[4];
-      int aidx[4];
-#pragma unroll
-      for (int s4 = 0; s4 < 4; ++s4) {
-        const int r = 16 * R + lk + 4 * s4;
-        npp[s4] = Pk[prow * PLD + lk + 4 * s4];
-        xv[s4] = Xn[r * PLD + li];
-        aidx[s4] = ct_cur[s4];
-        av[s4] = A[aidx[s4]];
-      }
-      const double dgn = dgb[((k + 1) % 3) * PIV + li];
-      d4_t acc;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int r = 16 * R + lk + 4 * g;
-        acc[g] = xv[g] + av[g] + (r == prow ? dgn : 0.0);
-        npp[g] = -npp[g];
-      }
-#pragma unroll
-      for (int s4 = 0; s4 < 4; ++s4) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(vt[s4], npp[s4], acc, 0, 0, 0);   // acc -= V P[piv]^T
-#pragma unroll
-      for (int g = 0; g < 4; ++g) A[aidx[g]] = 0.0;   // retired (the zero cell stays zero)
-      if constexpr (LY::VP) {
-        // operands of the Schur update: -V (accumulator layout -> row-major) and the raw rows, next pivots' rows blanked
-        const bool myrowpiv = has_next && ((grp16(m1, R) >> li) & 1u);
-        double *Pm = lds + LY::PMB;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          Yk[(16 * R + li) * PLD + lk + 4 * g] = myrowpiv ? 0.0 : -vt[g];
-          Pm[(16 * R + li) * PLD + lk + 4 * g] = myrowpiv ? 0.0 : pr[g];
-        }
-      } else
-      // Y = P L^-T of this tile: here for the tiles without a partner wave, else on service wave R (below)
-      if (R == 0 || R >= NSV) {
-        double la[4];
-#pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4) la[s4] = Lik[li * PLD + lk + 4 * s4];
-        d4_t yt = {zero, zero, zero, zero};
-#pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4)
-          yt = __builtin_amdgcn_mfma_f64_16x16x4f64(la[s4], pr[s4], yt, 0, 0, 0);   // yt[g] = Y[16R+li][lk+4g]
-        const bool myrowpiv = has_next && ((grp16(m1, R) >> li) & 1u);
-#pragma unroll
-        for (int g = 0; g < 4; ++g) Yk[(16 * R + li) * PLD + lk + 4 * g] = myrowpiv ? 0.0 : yt[g];
-      }
-      if (has_next) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) Xn[(16 * R + lk + 4 * g) * PLD + li] = acc[g];
-      }
-      const unsigned am16 = (am_word >> ((R & 1) * 16)) & 0xffffu;
-      if ((am16 >> li) & 1u) {
-        double *pv = panel + (size_t)k * pstride + PIV;
-        *(d4_t *)(pv + (16 * R + li) * PIV + 4 * lk) = vt;
-      }
+      kkt2_ab_tile(cx, k, wv, li, lk, Pk, Yk, Xn, has_next, prow_next, m1, ct_cur, P.amask[k * 8 + (wv >> 1)], (k + 1) % 3);
     } else {
       // ---- service waves ------------------------------------------------------------------------------
       const int sv = wv - NT;
       if (sv == 0) {
-        // right-hand-side row: w = (L D L^T)^-1 p_F; rhs -= P w; right-hand side of the next pivots
-        double part = 0.0;
-#pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4) part = fma(Minv[li * PLD + lk + 4 * s4], Pk[F * PLD + lk + 4 * s4], part);
-        part = rowsum4(part);                    // w[li] on every lane
-        if (lane < PIV) panel[(size_t)k * pstride + lane] = part;
-        if (has_next) {
-          asm volatile("s_nop 4" : "+v"(part));    // DPP hazard distance for the broadcast reads below
-#pragma unroll
-          for (int c = 0; c < FR / 64; ++c) {
-            const int r = c * 64 + lane;
-            const int rr = min(r, F - 1);
-            double pq[PIV];
-#pragma unroll
-            for (int q = 0; q < PIV; ++q) pq[q] = Pk[rr * PLD + q];
-            const double uf = UF[r];
-            double a0 = 0.0;
-            dot16_steps<0>(a0, part, pq);
-            UF[r] = r < F ? uf - a0 : 0.0;
-          }
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          if (lane < PIV) {
-            const int c = prow_next;
-            Xn[F * PLD + lane] = A[rc_cur] + UF[c];
-            A[rc_cur] = 0.0;
-            UF[c] = 0.0;
-          }
-        }
+        kkt2_ab_rhs(cx, k, lane, li, lk, Pk, Xn, has_next, prow_next, rc_cur, true);
       }
       else if (KRON && LY::VP) {
         // the waves that idle in this phase: the 33 sums of the Kronecker blocks of the records of stage k+2 (assembled in C(k))
@@ -940,6 +1135,7 @@ __global__ __launch_bounds__(KT2) void k_kkt2(DevPlan P, DevWork W, int B) {
       else if (!LY::VP && sv < NT) {
         // Y = P L^-T of row tile R = sv for its tile wave
         const int R = sv;
+        const double *Lik = cx.Lib + (k & 1) * PIV * PLD;
         double la[4], pr[4];
 #pragma unroll
         for (int s4 = 0; s4 < 4; ++s4) {
@@ -956,231 +1152,96 @@ __global__ __launch_bounds__(KT2) void k_kkt2(DevPlan P, DevWork W, int B) {
         for (int g = 0; g < 4; ++g) Yk[(16 * R + li) * PLD + lk + 4 * g] = myrowpiv ? 0.0 : yt[g];
       }
     }
-    KS2(0);
+    st.mark(0);
     lds_barrier();
-    KS2(1);
+    st.mark(1);
     // ---- C(k) ---------------------------------------------------------------------------------------
     // prefetch of the records of stage k+3 (installed at the top of the next stage): issued by every wave when
     // its urgent work of the phase is done (48 KB-wide loads at once keep the CU's memory pipe busy for ~800 cycles);
     // a wave skips the loads that lie wholly behind the record's end
-    auto prefetch_records = [&]() __attribute__((always_inline)) {
-      if (!DMA && k + 3 < NS) {
-        const int s = k + 3;
-        int d0, d1, s0, s1;
-        sload2(P.drec_off + s, d0, d1);
-        sload2(P.srec_off + s, s0, s1);
-        pf_nd2 = (d1 - d0) >> 1;
-        pf_ns4 = (s1 - s0) >> 2;
-        const d2_t *dsrc = (const d2_t *)(stream + d0);
-        const i4_t *ssrc = (const i4_t *)(P.srec + s0);
-        const int wbase = __builtin_amdgcn_readfirstlane(pidx);   // first element of this wave
-        if (wbase < pf_nd2) pfd = dsrc[min(pidx, pf_nd2 - 1)];
-        if (wbase < pf_ns4) pfs0 = ssrc[min(pidx, pf_ns4 - 1)];
-        if (wbase + KT2 < pf_ns4) pfs1 = ssrc[min(pidx + KT2, pf_ns4 - 1)];
-      }
-    };
-    prefetch_records();
-    KS2(8);
+    if (!DMA && k + 3 < NS) {
+      const int s = k + 3;
+      int d0, d1, s0, s1;
+      sload2(P.drec_off + s, d0, d1);
+      sload2(P.srec_off + s, s0, s1);
+      pf_nd2 = (d1 - d0) >> 1;
+      pf_ns4 = (s1 - s0) >> 2;
+      const d2_t *dsrc = (const d2_t *)(cx.stream + d0);
+      const i4_t *ssrc = (const i4_t *)(P.srec + s0);
+      const int wbase = __builtin_amdgcn_readfirstlane(pidx);   // first element of this wave
+      if (wbase < pf_nd2) pfd = dsrc[min(pidx, pf_nd2 - 1)];
+      if (wbase < pf_ns4) pfs0 = ssrc[min(pidx, pf_ns4 - 1)];
+      if (wbase + KT2 < pf_ns4) pfs1 = ssrc[min(pidx + KT2, pf_ns4 - 1)];
+    }
+    st.mark(8);
     if (wv == 0) {
       __builtin_amdgcn_s_setprio(3);
-      if (has_next) factor_block(Xn, prow_next, psb + ((k + 1) % 3) * PIV, Lib + ((k + 1) & 1) * PIV * PLD, dvb + ((k + 1) & 1) * PIV, k + 1);
+      if (has_next) kkt2_factor_block(cx, Xn, prow_next, cx.psb + ((k + 1) % 3) * PIV, cx.Lib + ((k + 1) & 1) * PIV * PLD, cx.dvb + ((k + 1) & 1) * PIV, k + 1);
       __builtin_amdgcn_s_setprio(0);
-    } else if (is_upd) {
-      const Mask256 m2 = load_mask8(pm + (k & 1) * 8, lane);   // pivot slots of stage k+2
-      const bool extract = k + 2 < NS;
-      const unsigned char *jm2 = jmb + (k & 1) * FR;
-      double *Xnn = Pk;   // the panel of stage k is dead: it receives the columns of stage k+2
-      double dv4[4];
-      if constexpr (!LY::VP) {
-#pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4) dv4[s4] = -dik[lk + 4 * s4];
-      }
-      const double *Bop = LY::VP ? lds + LY::PMB : Yk;
-      int rcs[MAXT2];
-#pragma unroll
-      for (int t = 0; t < MAXT2; ++t) { rcs[t] = tRC[t]; asm volatile("" : "+s"(rcs[t])); }
-      double wa[2][4], pbv[2][4];
-      // operand addresses: a lane part that never changes (tile_lane, bytes) plus a wave-uniform tile offset formed on the
-      // scalar unit
-      auto tile_loads = [&](int rc, double (&w)[4], double (&pq)[4]) __attribute__((always_inline)) {
-        const int R = rc < 0 ? 0 : rc >> 8, C = rc < 0 ? 0 : rc & 255;
-        const int oR = __builtin_amdgcn_readfirstlane(R * (16 * PLD * 8)), oC = __builtin_amdgcn_readfirstlane(C * (16 * PLD * 8));
-        const char *wrow = (const char *)Yk + (tile_lane + oR), *prow2 = (const char *)Bop + (tile_lane + oC);
-#pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4) { w[s4] = *(const double *)(wrow + 32 * s4); pq[s4] = *(const double *)(prow2 + 32 * s4); }
-      };
-      // pivot indices of the columns (li) and of the four rows (lk + 4g) this lane holds in each tile: fetched ahead of
-      // the products (the extraction behind them starts with no LDS round trip of its own: -5.5 % per launch)
-      int jc8[MAXT2], jr32[MAXT2];
-#pragma unroll
-      for (int t = 0; t < MAXT2; ++t) {
-        const int rc = rcs[t] < 0 ? 0 : rcs[t];
-        jc8[t] = jm2[16 * (rc & 255) + (li & 3) * 4 + (li >> 2)];
-        jr32[t] = *(const int *)(jm2 + 16 * (rc >> 8) + 4 * lk);
-      }
-      tile_loads(rcs[0], wa[0], pbv[0]);
-#pragma unroll
-      for (int t = 0; t < MAXT2; ++t) {
-        if (t + 1 < MAXT2) tile_loads(rcs[t + 1], wa[(t + 1) & 1], pbv[(t + 1) & 1]);
-#pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4)
-          U[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(LY::VP ? wa[t & 1][s4] : wa[t & 1][s4] * dv4[s4], pbv[t & 1][s4], U[t], 0, 0, 0);
-      }
-      KS2(5);
-      if (extract) {
-        int jcs[MAXT2], jrs[MAXT2][4];
-#pragma unroll
-        for (int t = 0; t < MAXT2; ++t) {
-          jcs[t] = jc8[t];
-#pragma unroll
-          for (int g = 0; g < 4; ++g) jrs[t][g] = (jr32[t] >> (8 * g)) & 255;
-        }
-        double *dummy = red + 2 * 16 * PIV + lane;
-        // bit 4g of ge4 / gt4: row lk + 4g of a diagonal tile lies on or below / strictly below column li
-        const unsigned ge4 = ge4_keep, gt4 = gt4_keep;
-#pragma unroll
-        for (int t = 0; t < MAXT2; ++t) {
-          const int rc = rcs[t];
-          if (rc < 0) continue;
-          const int R = rc >> 8, C = rc & 255;
-          const unsigned cw2 = grp16(m2, C), rw2 = grp16(m2, R);
-          if ((cw2 | rw2) == 0u) continue;
-          const unsigned cm = ((cw2 >> li) & 1u) ? (R > C ? 0x1111u : ge4) : 0u;
-          const unsigned rmk = (rw2 >> lk) & (R > C ? 0x1111u : gt4);
-          double *xr = Xnn + (16 * R + lk) * PLD + jcs[t], *xc = Xnn + (16 * C + li) * PLD;
-          if (cw2) {
-#pragma unroll
-            for (int g = 0; g < 4; ++g) *(((cm >> (4 * g)) & 1u) ? xr + g * 4 * PLD : dummy) = U[t][g];
-          }
-          if (rw2) {
-#pragma unroll
-            for (int g = 0; g < 4; ++g) *(((rmk >> (4 * g)) & 1u) ? xc + jrs[t][g] : dummy) = U[t][g];
-          }
-#pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            const int z = ~__builtin_amdgcn_sbfe((int)(cm | rmk), 4 * g, 1);
-            U[t][g] = __hiloint2double(__double2hiint(U[t][g]) & z, __double2loint(U[t][g]) & z);
-          }
-        }
-      }
+    } else if (cx.is_upd) {
+      kkt2_update(cx, st, U, k, NS, lane, li, lk, Pk, Yk, true);
     }
-    KS2(2);
-    // every wave but the factor wave ends the phase with its share of the assembly of stage k+2's records
-    // (the waves without a Schur tile come first and take the low item indices)
-    const int apos = is_upd ? (15 - NU) + uw : uw - NU;   // (wave 12, the header wave, is the last of the free ones)
-#ifndef QTOS_ASM_SKIP
-#define QTOS_ASM_SKIP 3
-#endif
-    // one thread per target, low item indices to the waves that get here first (handing the waves without Schur tiles
-    // more of it was tried -- they share the factor wave's SIMD and are the slowest at it).  The youngest update wave of
-    // every SIMD gets its matrix instructions last and ends the phase: it takes no part in the assembly.
-    constexpr int NASM = 15 - (NU >= 12 ? QTOS_ASM_SKIP : 0);
-#ifndef QTOS_ASM_FREEW
-#define QTOS_ASM_FREEW 1
-#endif
-    // the waves without Schur tiles (they share the factor wave's SIMD, which runs no matrix instructions in this phase)
-    // take FREEW shares each
-    constexpr int FREEW = NU == 12 ? QTOS_ASM_FREEW : 1, NFREE = 15 - NU, NVIRT = NASM + NFREE * (FREEW - 1);
+    st.mark(2);
+    // every wave but the factor wave ends the phase with its share of the assembly of stage k+2's records, one thread per
+    // target, low item indices to the waves that get here first: the waves without Schur tiles (wave 12, the header wave,
+    // is the last of them), then the update waves.  (Handing the waves without Schur tiles more of it was tried -- they
+    // share the factor wave's SIMD and are the slowest at it.)  The youngest update wave of every SIMD gets its matrix
+    // instructions last and ends the phase: with twelve update waves and more those three take no part in the assembly.
+    const int apos = cx.is_upd ? (15 - NU) + cx.uw : cx.uw - NU;
+    constexpr int NASM = 15 - (NU >= 12 ? 3 : 0);
     if (wv >= 1 && k + 2 < NS && apos < NASM) {
-      if constexpr (KRON) {
-        if (apos < NFREE) {
-#pragma unroll
-          for (int f = 0; f < FREEW; ++f) assemble_stage_kron(A, F, sbuf, dbuf, ksm, (apos * FREEW + f) * 64 + lane, NVIRT * 64);
-        } else assemble_stage_kron(A, F, sbuf, dbuf, ksm, (apos + NFREE * (FREEW - 1)) * 64 + lane, NVIRT * 64);
-      } else
-      if (apos < NFREE) {
-#pragma unroll
-        for (int f = 0; f < FREEW; ++f) assemble_stage(A, F, sbuf, dbuf, (apos * FREEW + f) * 64 + lane, NVIRT * 64);
-      } else assemble_stage(A, F, sbuf, dbuf, (apos + NFREE * (FREEW - 1)) * 64 + lane, NVIRT * 64);
+      if constexpr (KRON) assemble_stage_kron(cx.A, F, sbuf, dbuf, ksm, apos * 64 + lane, NASM * 64); else
+      assemble_stage(cx.A, F, sbuf, dbuf, apos * 64 + lane, NASM * 64);
     }
     if constexpr (CONT) {
       if (k + 2 < NS) assemble_continuations(wv >= 1 ? apos * 64 + lane : -1, 15 * 64);
     }
-    // LDS-DMA of the records of stage k+3 into the other buffer, by the three waves without Schur tiles once
-    // their assembly is done (1 KB per instruction, chunk c of a record by wave c mod 3; wave 12 takes the
-    // chunks with the header it publishes below); the loads are waited for before the phase's barrier
+    // LDS-DMA of the records of stage k+3 into the other buffer by the three waves without Schur tiles once their
+    // assembly is done (wave 12 takes the chunks with the header it publishes below)
     if constexpr (DMA) {
       if (!(wv & 3) && wv != 0 && k + 3 < NS) {
-        const int s = k + 3, wi = wv == 12 ? 0 : wv >> 2;
-        int d0, d1, s0, s1;
-        sload2(P.drec_off + s, d0, d1);
-        sload2(P.srec_off + s, s0, s1);
-        const int nbd = (d1 - d0) * 8, nbs = (s1 - s0) * 4;
-        const char *gd = (const char *)(stream + d0), *gs = (const char *)(P.srec + s0);
-        typedef __attribute__((address_space(3))) char lds_char;
-        lds_char *ld = (lds_char *)(dbuf0 + (s & 1) * dstride), *ls = (lds_char *)(sbuf0 + (s & 1) * sstride);
-        for (int c = wi; c * 1024 < nbd; c += 3)
-          __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(gd + min(c * 1024 + lane * 16, nbd - 16)), (__attribute__((address_space(3))) void *)(ld + c * 1024), 16, 0, 0);
-        for (int c = wi; c * 1024 < nbs; c += 3)
-          __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(gs + min(c * 1024 + lane * 16, nbs - 16)), (__attribute__((address_space(3))) void *)(ls + c * 1024), 16, 0, 0);
+        kkt2_dma_records(cx, P, k + 3, wv == 12 ? 0 : wv >> 2, 3, lane);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
     }
     if (wv == 12) {
       // header of stage k+3, published to the LDS rings (their slots have no reader left in this phase:
-      // stage k's pivot slots / diagonals, stage k+1's slot map and mask) from this wave's share of the
-      // prefetched record: lane l holds ints 4l .. 4l+3 (static header 0..7, pivot slots 8..23) and doubles
-      // 2l, 2l+1 (pivot diagonals 0..15)
+      // stage k's pivot slots / diagonals, stage k+1's slot map and mask)
       const int hs = k + 3;
       if (hs < NS) {
-        if (lane < 8) pm[(hs & 1) * 8 + lane] = 0u;
+        if (lane < 8) cx.pm[(hs & 1) * 8 + lane] = 0u;
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if constexpr (DMA) {   // the header sits in the first chunks, which this wave has just waited for
-          const int *hb = sbuf0 + (hs & 1) * sstride;
-          const double *hdb = dbuf0 + (hs & 1) * dstride;
-          if (lane == 0) { const int hv = hb[3]; hib[hs % 3] = hv; hiall[hs] = (hv + 15) & ~15; }
-          if (lane < PIV) {
-            const int hv = hb[SHDR + lane];
-            dgb[(hs % 3) * PIV + lane] = hdb[lane];
-            psb[(hs % 3) * PIV + lane] = hv;
-            jmb[(hs & 1) * FR + (hv & ~15) + (hv & 3) * 4 + ((hv >> 2) & 3)] = (unsigned char)lane;
-            atomicOr(&pm[(hs & 1) * 8 + (hv >> 5)], 1u << (hv & 31));
-          }
+        if constexpr (DMA) {   // from the first chunks of the record, which this wave has just waited for
+          kkt2_publish_header(cx, cx.sbuf0 + (hs & 1) * cx.sstride, cx.dbuf0 + (hs & 1) * cx.dstride, hs, hs % 3, lane);
         } else {
-        if (lane == 0) { hib[hs % 3] = pfs0[3]; hiall[hs] = (pfs0[3] + 15) & ~15; }
-        if (lane < 8) { dgb[(hs % 3) * PIV + 2 * lane] = pfd[0]; dgb[(hs % 3) * PIV + 2 * lane + 1] = pfd[1]; }
+        // from this wave's share of the prefetched record: lane l holds ints 4l .. 4l+3 (static header 0..7, pivot slots
+        // 8..23) and doubles 2l, 2l+1 (pivot diagonals 0..15)
+        if (lane == 0) { cx.hib[hs % 3] = pfs0[3]; cx.hiall[hs] = (pfs0[3] + 15) & ~15; }
+        if (lane < 8) { cx.dgb[(hs % 3) * PIV + 2 * lane] = pfd[0]; cx.dgb[(hs % 3) * PIV + 2 * lane + 1] = pfd[1]; }
         if (lane >= 2 && lane < 6) {
 #pragma unroll
           for (int c = 0; c < 4; ++c) {
             const int jidx = 4 * (lane - 2) + c, hv = pfs0[c];
-            psb[(hs % 3) * PIV + jidx] = hv;
-            jmb[(hs & 1) * FR + (hv & ~15) + (hv & 3) * 4 + ((hv >> 2) & 3)] = (unsigned char)jidx;
-            atomicOr(&pm[(hs & 1) * 8 + (hv >> 5)], 1u << (hv & 31));
+            cx.psb[(hs % 3) * PIV + jidx] = hv;
+            cx.jmb[(hs & 1) * FR + (hv & ~15) + (hv & 3) * 4 + ((hv >> 2) & 3)] = (unsigned char)jidx;
+            atomicOr(&cx.pm[(hs & 1) * 8 + (hv >> 5)], 1u << (hv & 31));
           }
         }
         }
       }
     }
-    KS2(3);
+    st.mark(3);
     lds_barrier();
-    KS2(4);
-    if (k + 2 < NS) prow_next = psb[((k + 2) % 3) * PIV + li];
+    st.mark(4);
+    if (k + 2 < NS) prow_next = cx.psb[((k + 2) % 3) * PIV + li];
     ct_cur = ct_nxt;
     rc_cur = rc_nxt;
   }
-  // ---- backward substitution (sweep_backward below: one barrier per stage, one-stage look-ahead) ---------------
   __syncthreads();  // drains the factor-panel stores: they are read back below
-  KS2(7);
-  {
-    int *nxp = (int *)PB;   // (the panels are dead)
-    for (int i = tid; i < NS * 4; i += KT2) nxp[i] = P.nxt_pack[i];
-    for (int i = tid; i < NS * 8; i += KT2) nxp[NS * 4 + i] = (int)P.amask2[i];
-    __syncthreads();
-    const SweepDs sd = {W.stream + (size_t)b * P.stream_len, W.ds + (size_t)b * P.n_cons, W.g + (size_t)b * P.n_cons, W.s + (size_t)b * P.n_cons, W.trace ? W.trace + ((size_t)b * (P.max_iter + 1) + 64) * 4 : nullptr};
-    sweep_backward<F>(P, panel, dx, W.sol + (size_t)b * P.n_stages * PIV, xs, red, nxp, wv, lane, lds + ((LY::PB + NS * 6 + 1) & ~1), sd);
-  }
-#ifdef QTOS_STAMPS
-  KS2(6);
-  __syncthreads();
-  // (stamps2.py reads the 192 counters as 64-bit integers)
-#endif
+  st.mark(7);
+  kkt2_backward(cx, P, W, b, tid, wv, lane);
+  st.finish();
 }
-#ifdef QTOS_STAMPS
-// (k_kkt3 / k_kkt4 keep their counters in LDS)
-#undef KS2
-#define KS2(i) do { if (lane == 0) { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); st2[wv][i] += t_ - ts_; ts_ = t_; } } while (0)
-#endif
-
 
 
 // =================================================================================================

@@ -246,8 +246,7 @@ static int analyze_host(const QtosParams &params, const QtosEnv &env, bool kron,
 static size_t kkt_lds_bytes(Kkt k, const Symbolic &S) {
   switch (k) {
     case Kkt::kkt5: return kkt5_lds_bytes(S.front, S.n_stages, S.max_srec, S.max_drec, S.n_cells);
-    case Kkt::kkt3: return kkt3_lds_bytes(S.front, S.n_stages, S.max_srec, S.max_drec, S.n_cells);
-    default: return kkt2_lds_bytes(S.front, S.n_stages, S.max_srec, S.max_drec, S.n_cells);
+    default: return kkt2_lds_bytes(S.front, S.n_stages, S.max_srec, S.max_drec, S.n_cells);   // (k_kkt2 and k_kkt3: one layout)
   }
 }
 // the kernel's name as rocprofv3 lists it (qtos_kkt_kernel, qtos_analyze_kernel)
