@@ -110,7 +110,9 @@ typedef struct QtosPlanner QtosPlanner;
 /* Build the planner for one transcription (symbolic KKT analysis + device workspaces for up to
  * max_batch problems on HIP device `device`).  Replaces starting the `towr` container
  * (QTOS/utils.py:686-692 DockerInfo).  Returns 0, or <0: -1 bad parameters, -2 no HIP device /
- * HIP error, -3 out of memory, -4 front too large for LDS. */
+ * HIP error, -3 out of memory, -4 front too large for LDS.  Nothing here checks that the elimination
+ * order the analysis picked is numerically sound for the transcription: where horizons, phase tables or
+ * knot spacings vary, use qtos_planner_create_checked (below). */
 int qtos_planner_create(const QtosParams *params, int max_batch, int device, QtosPlanner **out);
 void qtos_planner_destroy(QtosPlanner *p);
 int qtos_planner_dims(const QtosPlanner *p, QtosDims *dims);
@@ -207,12 +209,13 @@ int qtos_plan_batch(QtosPlanner *p, int B, const double *start, const double *go
  * (qtos_amd.pool.PlannerPool: submit to a free handle, poll the others) -- a batch that waits for its slowest problem
  * then shares the GPU with the next ones.  This is the form bench.py times.
  *
- * Environment.  Read ONCE, by qtos_planner_create (and by the host-only qtos_analyze* calls for themselves), in one place
+ * Environment.  Read ONCE, by qtos_planner_create / qtos_planner_create_checked (and by the host-only qtos_analyze* calls for themselves), in one place
  * (csrc/env.hpp); the planner keeps what it found and qtos_env() hands it back.  Diagnostics and measured alternatives, the
  * defaults are the measured optimum:
  *   QTOS_KKT=2 | 4 | 6       force the factor + solve kernel: k_kkt2 / k_kkt3 MODE 1 / k_kkt5 (default: k_kkt3 MODE 1 for fronts of up
  *                            to 112 slots, k_kkt2 above; see qtos_kkt_kernel below and DESIGN.md section 5).  3 and 5 (k_kkt3 MODE 0,
- *                            k_kkt4 of rounds 4 - 5) left the library: a warning on stderr, then the default
+ *                            k_kkt4 of rounds 4 - 5) select nothing in any build, experiment builds included: a warning on stderr,
+ *                            then the default
  *   QTOS_LANES=n             a call of more problems than the GPU has compute units is cut into up to n (<= 4) contiguous parts,
  *                            each with its own host-driven loop on a stream of the planner; bit-identical plans; default 1
  *                            (measured slower than one lock-step loop at 1024 problems per call)
@@ -426,6 +429,63 @@ int qtos_kkt_kernel(const QtosPlanner *p, char *buf, int n);
  * it is now (the same choice, no GPU needed); returns the length of the full name, < 0 where qtos_planner_create would fail
  * in the analysis. */
 int qtos_analyze_kernel(const QtosParams *params, char *buf, int n);
+
+/* ---- self-test of the elimination order ------------------------------------------------------
+ * The factor + solve kernels eliminate the KKT matrix WITHOUT pivoting, in an order the host analysis picks from time keys
+ * (QtosDims.order_rule).  Whether that order is sound for a transcription shows in one KKT solve with barrier weights over six
+ * decades: its residual, and the size of the factor's entries (1 / eps_dual is the norm; an order that loses digits has entries
+ * tens of times larger).  The interior-point loop absorbs a bad solve -- plans still come back with status 0 --, so the check
+ * has to be made on purpose. */
+typedef struct QtosSelftest {
+  int order_rule, front, n_stages;  /* of the planner that was tested                              */
+  int n_problems;                   /* systems solved (2)                                          */
+  int worst_stage;                  /* stage that holds max_factor                                 */
+  int passed;                       /* residual <= tol_residual && max_factor <= growth_limit      */
+  double residual;                  /* max over the systems of max|b - K x| / max|b|               */
+  double residual_refined;          /* the same behind one step of refinement through k_chord;
+                                       -1 where the planner has no chord kernel                    */
+  double max_factor;                /* largest |entry| of the factor panels' V part                */
+  double growth_limit;              /* 1.05 / eps_dual                                             */
+  double tol_residual;              /* as passed in (<= 0: 1e-6)                                   */
+  double seconds;                   /* wall time of the self-test, host clock                      */
+} QtosSelftest;
+/* Two KKT systems on the planner's own device through the planner's own factor + solve and chord kernels: flat ground (the
+ * handle's heightfields and table of nominal plans are ignored, and stay), the rest start at the origin in nominal stance, the
+ * goal 0.09 m per second of horizon straight ahead (qtos_selftest_problem), towr's straight-line guess + dx0, barrier weights
+ * sig and right-hand sides w of qtos_selftest_inputs(seed, problem 0 / 1).  One solve, its residual (k_residual: K applied
+ * without the factorisation), one step of refinement as qtos_debug_residual(refine = 1), and a reduction over the factor panels
+ * on the device (k_panel_absmax).  Returns 0 with `out` filled -- pass or fail is out->passed, not the return code --, -1 bad
+ * arguments, -2 HIP error, -5 while a call is open.  Uses the workspace of the qtos_debug_* entry points; launch pattern, totals,
+ * report flag and heightfields of the handle stay as they were: a plan call behind it returns the bits it would have returned
+ * without it. */
+int qtos_planner_selftest(QtosPlanner *p, unsigned long long seed, double tol_residual, QtosSelftest *out);
+/* Host-only: the self-test's random inputs for problem b (dx0: n_vars; sig, w: n_cons doubles, sizes from qtos_analyze) -- the
+ * very function the self-test calls.  Counter-based, no state:
+ *   mix(z)     z += 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB;
+ *              z ^ z >> 31                                                   (splitmix64; 64-bit wrap-around arithmetic)
+ *   bits(a, i) mix(mix(mix(mix(seed) ^ b) ^ a) ^ i)                          (qtos_selftest_bits; array a: 0 dx0, 1 sig, 2 w)
+ *   u(a, i)    ((bits(a, i) >> 11) + 0.5) * 2^-53                            in (0, 1)
+ *   n(a, i)    sqrt(-2 log u(a, 2 i)) * cos(2 pi u(a, 2 i + 1))              Box-Muller, one normal per pair; 2 pi = 6.283185307179586
+ *   dx0[i] = 0.01 n(0, i)     sig[r] = pow(10, -3 + 6 u(1, r))     w[r] = n(2, r) * sqrt(sig[r])
+ * in IEEE double with the host's libm.  Returns 0, -1 bad arguments / parameters. */
+int qtos_selftest_inputs(const QtosParams *params, unsigned long long seed, int b, double *dx0, double *sig, double *w);
+unsigned long long qtos_selftest_bits(unsigned long long seed, int problem, int array, unsigned long long index);
+/* Host-only: start (24 doubles) and goal (3) of the self-test's problems (both problems have the same). */
+int qtos_selftest_problem(const QtosParams *params, double *start, double *goal);
+/* qtos_planner_create with the self-test as a gate.  Candidates: with QTOS_ORDER set, that rule alone.  Otherwise the rules in
+ * rules_mask (bit r = rule r; 0 = what the automatic choice considers: rules 2 and 1 on a reduced base, rule 0 where the base
+ * is not reduced -- there rule 0 is the only candidate whatever the mask), sorted by the preference of the automatic choice:
+ * smaller front, fewer stages, no continuation records, then 2 before 1 before 0.  With rules_mask = 0 the first candidate is
+ * the planner qtos_planner_create builds.  Each candidate is built and tested (seed 0, tol_residual as above); the first that
+ * passes is returned, the others are destroyed.  tried[i] (up to max_tried; *n_tried of them written) records every attempt
+ * in order; a candidate whose analysis or creation fails is recorded with passed = 0, front = 0 and skipped.
+ * Returns 0 and the planner; -6 and *out = NULL if no candidate passes (stderr names rule, residual, growth and worst stage
+ * of each attempt); -1 .. -4 as qtos_planner_create when nothing could be built; -2 before any analysis without a device. */
+int qtos_planner_create_checked(const QtosParams *params, int max_batch, int device, int rules_mask, double tol_residual,
+                                QtosPlanner **out, QtosSelftest *tried, int max_tried, int *n_tried);
+/* Host-only: the candidates in the order qtos_planner_create_checked would try them under the environment as it is now (rule,
+ * front and stages of each into the arrays, up to n; any may be NULL); returns the count. */
+int qtos_analyze_candidates(const QtosParams *params, int rules_mask, int *rules, int *fronts, int *stages, int n);
 
 #ifdef __cplusplus
 }

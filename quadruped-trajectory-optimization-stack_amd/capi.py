@@ -67,6 +67,36 @@ class QtosReport(C.Structure):
     ]
 
 
+class QtosSelftest(C.Structure):
+    """One attempt of the create-time KKT self-test (qtos_planner_selftest)."""
+    _fields_ = [
+        ("order_rule", C.c_int), ("front", C.c_int), ("n_stages", C.c_int), ("n_problems", C.c_int),
+        ("worst_stage", C.c_int), ("passed", C.c_int),
+        ("residual", C.c_double), ("residual_refined", C.c_double), ("max_factor", C.c_double),
+        ("growth_limit", C.c_double), ("tol_residual", C.c_double), ("seconds", C.c_double),
+    ]
+
+    def copy(self):
+        return QtosSelftest.from_buffer_copy(self)
+
+    def describe(self):
+        if not self.front:
+            return "rule %d, not built" % self.order_rule
+        return "rule %d, residual %.1e, max |V| %.2e, %s" % (self.order_rule, self.residual, self.max_factor,
+                                                              "passed" if self.passed else "rejected (stage %d)" % self.worst_stage)
+
+
+class SelftestError(RuntimeError):
+    """No elimination order passed the KKT self-test (qtos_planner_create_checked returned -6); `attempts`: the QtosSelftest
+    records in the order they were tried."""
+
+    def __init__(self, attempts):
+        self.attempts = attempts
+        RuntimeError.__init__(self, "no elimination order passed the KKT self-test: " + "; ".join(a.describe() for a in attempts))
+
+
+MAX_TRIED = 3    # order rules 0, 1, 2
+
 EXPORTS = [
     "qtos_planner_create", "qtos_planner_destroy", "qtos_planner_dims", "qtos_last_error",
     "qtos_set_heightfields", "qtos_plan_batch", "qtos_plan_batch_device", "qtos_sample_csv",
@@ -78,6 +108,8 @@ EXPORTS = [
     "qtos_debug_stream_len", "qtos_debug_read_stream", "qtos_debug_read_rhs", "qtos_build_flags", "qtos_kkt_kernel",
     "qtos_last_timing_detail", "qtos_set_pattern_speculation", "qtos_env", "qtos_analyze_two_ended", "qtos_analyze_order", "qtos_set_kernel_events",
     "qtos_write_csv", "qtos_set_report", "qtos_plan_report", "qtos_analyze_counts", "qtos_debug_duals", "qtos_analyze_kernel",
+    "qtos_planner_selftest", "qtos_planner_create_checked", "qtos_analyze_candidates", "qtos_selftest_inputs", "qtos_selftest_bits",
+    "qtos_selftest_problem",
 ]
 
 _lib = None
@@ -166,6 +198,16 @@ def load():
         lib.qtos_analyze_counts.argtypes = [C.POINTER(QtosParams), C.POINTER(C.c_longlong), C.c_int]
     if hasattr(lib, "qtos_analyze_kernel"):
         lib.qtos_analyze_kernel.argtypes = [C.POINTER(QtosParams), C.c_char_p, C.c_int]
+    if hasattr(lib, "qtos_planner_selftest"):   # (the create-time KKT self-test)
+        ull = C.c_ulonglong
+        lib.qtos_planner_selftest.argtypes = [vp, ull, C.c_double, C.POINTER(QtosSelftest)]
+        lib.qtos_planner_create_checked.argtypes = [C.POINTER(QtosParams), C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(vp),
+                                                    C.POINTER(QtosSelftest), C.c_int, ip]
+        lib.qtos_analyze_candidates.argtypes = [C.POINTER(QtosParams), C.c_int, ip, ip, ip, C.c_int]
+        lib.qtos_selftest_inputs.argtypes = [C.POINTER(QtosParams), ull, C.c_int, dp, dp, dp]
+        lib.qtos_selftest_bits.argtypes = [ull, C.c_int, C.c_int, ull]
+        lib.qtos_selftest_bits.restype = ull
+        lib.qtos_selftest_problem.argtypes = [C.POINTER(QtosParams), dp, dp]
     _lib = lib
     return lib
 
@@ -271,6 +313,52 @@ def analyze_kernel(cfg):
     return buf.value.decode()
 
 
+def _selftest_lib():
+    lib = load()
+    if not hasattr(lib, "qtos_planner_selftest"):
+        raise RuntimeError("this build of the planner library has no KKT self-test (qtos_planner_selftest)")
+    return lib
+
+
+def analyze_candidates(cfg, rules_mask=0):
+    """Host-only: the order rules a checked create would try, in trial order: a list of (rule, front, stages)."""
+    lib = _selftest_lib()
+    p = params_from_config(cfg)
+    a = [np.zeros(MAX_TRIED, np.int32) for _ in range(3)]
+    n = lib.qtos_analyze_candidates(C.byref(p), int(rules_mask), _ip(a[0]), _ip(a[1]), _ip(a[2]), MAX_TRIED)
+    if n < 0:
+        raise ValueError("qtos_analyze_candidates failed (%d)" % n)
+    return [(int(a[0][i]), int(a[1][i]), int(a[2][i])) for i in range(min(n, MAX_TRIED))]
+
+
+def selftest_inputs(cfg, seed, b):
+    """Host-only: (dx0 [n_vars], sig [n_cons], w [n_cons]) of problem b of the self-test with this seed -- what
+    Planner.selftest(seed) adds to towr's guess and packs as barrier weights and right-hand side."""
+    lib = _selftest_lib()
+    p = params_from_config(cfg)
+    d, _ = analyze(cfg)
+    dx0, sig, w = np.zeros(d.n_vars), np.zeros(d.n_cons), np.zeros(d.n_cons)
+    rc = lib.qtos_selftest_inputs(C.byref(p), int(seed), int(b), _dp(dx0), _dp(sig), _dp(w))
+    if rc != 0:
+        raise ValueError("qtos_selftest_inputs failed (%d)" % rc)
+    return dx0, sig, w
+
+
+def selftest_bits(seed, problem, array, index):
+    """The generator's 64-bit word (qtos_selftest_bits; array 0 dx0, 1 sig, 2 w)."""
+    return int(_selftest_lib().qtos_selftest_bits(int(seed), int(problem), int(array), int(index)))
+
+
+def selftest_problem(cfg):
+    """Host-only: (start [24], goal [3]) of the self-test's problems."""
+    lib = _selftest_lib()
+    p = params_from_config(cfg)
+    start, goal = np.zeros(START_DOUBLES), np.zeros(3)
+    if lib.qtos_selftest_problem(C.byref(p), _dp(start), _dp(goal)) != 0:
+        raise ValueError("qtos_selftest_problem failed")
+    return start, goal
+
+
 def analyze_order(cfg):
     """Host-only: the elimination order by position (solver variable, n_sol + row for a multiplier, -1 = dummy pivot)."""
     lib = load()
@@ -325,15 +413,30 @@ def analyze_sweep(cfg, max_places=1 << 16):
 class Planner:
     """Owning wrapper of a QtosPlanner handle."""
 
-    def __init__(self, cfg, max_batch=256, device=0):
+    def __init__(self, cfg, max_batch=256, device=0, checked=False, rules_mask=0, tol_residual=0.0):
+        """checked: create through qtos_planner_create_checked -- every candidate order (rules_mask; 0 = those of the automatic
+        choice) is built and must pass the KKT self-test; self.selftests keeps the attempts, SelftestError if none passes."""
         self.lib = load()
         self.cfg = cfg
         self.params = params_from_config(cfg)
         self.h = C.c_void_p()
-        rc = self.lib.qtos_planner_create(C.byref(self.params), max_batch, device, C.byref(self.h))
+        self.selftests = []
+        if checked:
+            _selftest_lib()
+            tried = (QtosSelftest * MAX_TRIED)()
+            n = C.c_int(0)
+            rc = self.lib.qtos_planner_create_checked(C.byref(self.params), max_batch, device, int(rules_mask), float(tol_residual),
+                                                      C.byref(self.h), tried, MAX_TRIED, C.byref(n))
+            self.selftests = [tried[i].copy() for i in range(n.value)]
+            if rc == -6:
+                raise SelftestError(self.selftests)
+            what = "qtos_planner_create_checked"
+        else:
+            rc = self.lib.qtos_planner_create(C.byref(self.params), max_batch, device, C.byref(self.h))
+            what = "qtos_planner_create"
         if rc != 0:
-            raise RuntimeError("qtos_planner_create failed (%d): -2 = no HIP device, -3 = out of "
-                               "memory, -4 = front too large" % rc)
+            raise RuntimeError("%s failed (%d): -2 = no HIP device, -3 = out of "
+                               "memory, -4 = front too large" % (what, rc))
         self.max_batch, self.device = max_batch, device
         self.init_table = None
         self.dims = QtosDims()
@@ -405,6 +508,13 @@ class Planner:
     def set_kernel_events(self, on):
         """Per-kernel HIP events (what timing() / timing_detail() read) on / off; off = the call's first and last event only."""
         self._chk(self.lib.qtos_set_kernel_events(self.h, int(bool(on))), "set_kernel_events")
+
+    def selftest(self, seed=0, tol_residual=0.0):
+        """One run of the KKT self-test on this handle (qtos_planner_selftest): a QtosSelftest; raises while a call is open."""
+        _selftest_lib()
+        t = QtosSelftest()
+        self._chk(self.lib.qtos_planner_selftest(self.h, int(seed), float(tol_residual), C.byref(t)), "planner_selftest")
+        return t
 
     def has_report(self):
         return hasattr(self.lib, "qtos_set_report")

@@ -1,7 +1,7 @@
 // env.hpp -- every environment variable the library reads, parsed in ONE place.
 //
 // The header promises "no global state": the environment is read once per entry point that builds a planner or an analysis
-// (qtos_planner_create, qtos_analyze*), into this struct; the planner keeps its copy for its whole life and qtos_env() hands
+// (qtos_planner_create, qtos_planner_create_checked, qtos_analyze*), into this struct; the planner keeps its copy for its whole life and qtos_env() hands
 // the caller the values the handle actually runs with.  Nothing else in the library calls getenv.  All of these are diagnostics
 // or measured alternatives; the defaults are the measured optimum (include/qtos_planner.h lists what each one does).
 #pragma once

@@ -6,8 +6,11 @@
 #include <cstdlib>
 #include <cstring>
 #include <atomic>
+#include <chrono>
+#include <cmath>
 #include <string>
 #include <map>
+#include <memory>
 #include <vector>
 
 #include "kernels.hpp"
@@ -264,9 +267,12 @@ static int kkt_kernel_name(Kkt k, const Symbolic &S, char *buf, int n) {
 // waves idle in phase AB (-5 % per launch on 112 slots, -6 % on 96, +4 % on 128: profiles/r04_experiments).  k_kkt2 takes the
 // rest, with smaller records (heavy stages spill into continuation records) while they do not fit the LDS next to the panels.
 // QTOS_KKT=6: k_kkt5 on the pair-mode analysis where it applies; 2 forces k_kkt2; 3 and 5 (rounds 4 - 5) left the library.
-static int choose_kernel(const QtosParams &params, const QtosEnv &env, Kkt &kind, Analysis &A) {
-  Analysis def; bool have_def;   // the default variant: the order pick's winner, or built below
-  const int rule = pick_order_rule(params, env, def, have_def);
+// order_rule >= 0: that rule instead of the pick (qtos_planner_create_checked builds its candidates so; the same path as QTOS_ORDER).
+// `pre`: the default variant of that rule where the caller has built it (taken, as the pick's winner is).
+static int choose_kernel(const QtosParams &params, const QtosEnv &env, Kkt &kind, Analysis &A, int order_rule = -1, Analysis *pre = nullptr) {
+  Analysis def; bool have_def = false;   // the default variant: the order pick's winner, or built below
+  const int rule = order_rule >= 0 ? order_rule : pick_order_rule(params, env, def, have_def);
+  if (order_rule >= 0 && pre) { def = std::move(*pre); have_def = true; }
   int forced = env.kkt;
   if (forced == 3 || forced == 5) { fprintf(stderr, "qtos: QTOS_KKT=%d selected an experiment of rounds 4 - 5 that left the library (scratch/experiments/): default kernel\n", forced); forced = 0; }
   if (forced == 6) {   // (k_kkt5: a front of 96 .. 144 slots, no continuation records, within the LDS)
@@ -396,16 +402,18 @@ static int build_sweep_tasks(const HostModel &M, const Symbolic &S, std::vector<
   return ok ? step : 0;
 }
 
-int qtos_planner_create(const QtosParams *params, int max_batch, int device, QtosPlanner **out) {
+// The planner of qtos_planner_create (order_rule < 0: the automatic choice / QTOS_ORDER) and of the candidates of
+// qtos_planner_create_checked (order_rule >= 0), under the environment `env0` as the caller parsed it.
+static int create_planner(const QtosParams *params, int max_batch, int device, const QtosEnv &env0, int order_rule, QtosPlanner **out, Analysis *pre = nullptr) {
   if (!params || !out || max_batch < 1 || max_batch >= (1 << 24)) return -1;   // (the count words of k_post_counts hold 24 bits per count)
   *out = nullptr;
   QtosPlanner *p = new QtosPlanner();
   p->device = device;
   p->max_batch = max_batch;
-  p->env = QtosEnv::parse();   // the ONE place a planner reads the environment
+  p->env = env0;
   const QtosEnv &env = p->env;
   p->spec_pattern = env.spec_pattern != 0;
-  if (choose_kernel(*params, env, p->kkt, *p)) { delete p; return -1; }
+  if (choose_kernel(*params, env, p->kkt, *p, order_rule, pre)) { delete p; return -1; }
   const HostModel &M = p->M;
   const Symbolic &S = p->S;
   int ndev = 0;
@@ -740,6 +748,10 @@ int qtos_planner_create(const QtosParams *params, int max_batch, int device, Qto
 #undef TRY
   *out = p;
   return 0;
+}
+
+int qtos_planner_create(const QtosParams *params, int max_batch, int device, QtosPlanner **out) {
+  return create_planner(params, max_batch, device, QtosEnv::parse(), -1, out);   // (a planner reads the environment here, or in qtos_planner_create_checked)
 }
 
 static void fill_dims(const HostModel &M, const Symbolic &S, QtosDims *d) {
@@ -1874,6 +1886,276 @@ int qtos_debug_trace(QtosPlanner *p, int b, double *trace_out) {
   // the caller's buffer holds max_iter + 1 rows (diagnostic builds park phase stamps past `rows`)
   HIPCHK(p, hipMemcpy(trace_out, p->wk.trace + (size_t)b * stride * 4, (size_t)stride * 4 * sizeof(double), hipMemcpyDeviceToHost));
   return rows;
+}
+
+// ---- create-time self-test of the elimination order (include/qtos_planner.h: qtos_planner_selftest) -----------------------
+// The random inputs: counter-based, formed on the host (the device's log / cos / pow round differently from the host's).
+//   mix(z):      z += 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31
+//   bits(i):     mix(mix(mix(mix(seed) ^ problem) ^ array) ^ i)         array: 0 dx0, 1 sig, 2 w
+//   u(i):        ((bits(i) >> 11) + 0.5) * 2^-53                        in (0, 1)
+//   normal(i):   sqrt(-2 log u(2 i)) * cos(2 pi u(2 i + 1))             Box-Muller, one normal per pair
+static inline unsigned long long st_mix(unsigned long long z) {
+  z += 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+static inline unsigned long long st_key(unsigned long long seed, int problem, int array) {
+  return st_mix(st_mix(st_mix(seed) ^ (unsigned long long)problem) ^ (unsigned long long)array);
+}
+static inline double st_uniform(unsigned long long key, unsigned long long i) { return ((double)(st_mix(key ^ i) >> 11) + 0.5) * 0x1p-53; }
+static inline double st_normal(unsigned long long key, unsigned long long i) {
+  const double two_pi = 6.283185307179586;
+  return std::sqrt(-2.0 * std::log(st_uniform(key, 2 * i))) * std::cos(two_pi * st_uniform(key, 2 * i + 1));
+}
+static void selftest_fill(unsigned long long seed, int b, int n, int m, double *dx0, double *sig, double *w) {
+  const unsigned long long k0 = st_key(seed, b, 0), k1 = st_key(seed, b, 1), k2 = st_key(seed, b, 2);
+  for (int i = 0; i < n; ++i) dx0[i] = 0.01 * st_normal(k0, i);
+  for (int r = 0; r < m; ++r) {
+    sig[r] = std::pow(10.0, -3.0 + 6.0 * st_uniform(k1, r));
+    w[r] = st_normal(k2, r) * std::sqrt(sig[r]);
+  }
+}
+// the two problems' start and goal: at rest at the origin in nominal stance, 0.09 m per second of horizon straight ahead
+static void selftest_problem(const QtosParams &P, double *start, double *goal) {
+  double T = 0.0;
+  for (int k = 0; k < P.n_phases[0]; ++k) T += P.phase_dur[0][k];
+  std::memset(start, 0, QTOS_START_DOUBLES * sizeof(double));
+  start[2] = -P.nominal_stance[0][2];
+  for (int e = 0; e < NEE; ++e) { start[6 + 3 * e] = P.nominal_stance[e][0]; start[7 + 3 * e] = P.nominal_stance[e][1]; }
+  goal[0] = 0.09 * T; goal[1] = 0.0; goal[2] = start[2];
+}
+
+unsigned long long qtos_selftest_bits(unsigned long long seed, int problem, int array, unsigned long long index) {
+  return st_mix(st_key(seed, problem, array) ^ index);
+}
+int qtos_selftest_problem(const QtosParams *params, double *start, double *goal) {
+  if (!params || !start || !goal) return -1;
+  selftest_problem(*params, start, goal);
+  return 0;
+}
+int qtos_selftest_inputs(const QtosParams *params, unsigned long long seed, int b, double *dx0, double *sig, double *w) {
+  if (!params || b < 0 || !dx0 || !sig || !w) return -1;
+  HostModel M;   // (n_vars and n_cons do not depend on the elimination order)
+  if (M.build(*params)) { fprintf(stderr, "qtos: %s\n", M.err.c_str()); return -1; }
+  selftest_fill(seed, b, M.n_vars, M.n_cons, dx0, sig, w);
+  return 0;
+}
+
+// nodes = towr's guess + the perturbation (a plain sum: what numpy forms from the same two arrays)
+__global__ __launch_bounds__(256) void k_selftest_nodes(const double *guess, double *nodes, size_t count) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < count) nodes[i] += guess[i];
+}
+
+// The largest |entry| of the V part of a problem's factor panels (rows 1 .. front of every stage: the rows the stage's mask
+// says are stored -- the others hold whatever an earlier solve left) and the first stage that holds it.  One workgroup per
+// problem, a lane per 16 bytes of a row; the waves' results meet in LDS, thread 0 stores the two numbers.  A NaN counts as inf.
+__global__ __launch_bounds__(256) void k_panel_absmax(DevPlan P, DevWork W, int B, double *out) {
+  const int b = blockIdx.x, tid = threadIdx.x;
+  if (b >= B) return;
+  const int F = P.front, NS = P.n_stages;
+  const double *pan = W.panel + (size_t)b * P.panel_stride;
+  double mx = 0.0;
+  int st = 0;
+  for (int k = 0; k < NS; ++k) {
+    const d2_t *V = (const d2_t *)(pan + ((size_t)k * (F + 1) + 1) * PIV);
+    const unsigned *mask = P.amask + (size_t)k * 8;
+    for (int i = tid; i < F * (PIV / 2); i += blockDim.x) {
+      const int r = i / (PIV / 2);
+      if (!((mask[r >> 5] >> (r & 31)) & 1u)) continue;
+      const d2_t v = V[i];
+      double a = fmax(fabs(v.x), fabs(v.y));
+      if (v.x != v.x || v.y != v.y) a = INFINITY;
+      if (a > mx) { mx = a; st = k; }
+    }
+  }
+  for (int s = 32; s > 0; s >>= 1) {
+    const double om = __shfl_xor(mx, s);
+    const int os = __shfl_xor(st, s);
+    if (om > mx || (om == mx && os < st)) { mx = om; st = os; }
+  }
+  __shared__ double wm[4];
+  __shared__ int ws[4];
+  if ((tid & 63) == 0) { wm[tid >> 6] = mx; ws[tid >> 6] = st; }
+  __syncthreads();
+  if (tid == 0) {
+    for (int j = 1; j < 4; ++j)
+      if (wm[j] > mx || (wm[j] == mx && ws[j] < st)) { mx = wm[j]; st = ws[j]; }
+    out[2 * b] = mx;
+    out[2 * b + 1] = (double)st;
+  }
+}
+static_assert(PIV % 2 == 0, "k_panel_absmax reads a row in pairs");
+
+int qtos_planner_selftest(QtosPlanner *p, unsigned long long seed, double tol_residual, QtosSelftest *out) {
+  if (!p || !out) return -1;
+  if (p->call_open || p->busy.load()) { p->err = "qtos_planner_selftest: a call is open"; return -5; }
+  const auto t_begin = std::chrono::steady_clock::now();
+  std::memset(out, 0, sizeof(*out));
+  const HostModel &M = p->M;
+  const Symbolic &S = p->S;
+  out->order_rule = M.order_rule; out->front = S.front; out->n_stages = S.n_stages;
+  out->growth_limit = 1.05 / M.P.eps_dual;
+  out->tol_residual = tol_residual > 0 ? tol_residual : 1e-6;
+  out->residual_refined = -1.0;
+  HIPCHK(p, hipSetDevice(p->device));
+  HIPCHK(p, hipStreamSynchronize(p->last_stream));   // (the last call's kernels own the workspace until then)
+  const int N_PROBLEMS = 2, Bc = std::min(N_PROBLEMS, p->max_batch);
+  const size_t n = M.n_vars, m = M.n_cons;
+  // flat ground and towr's straight-line guess whatever the handle carries: the copy of the plan the kernels get has no maps, no table
+  DevPlan D = p->dp;
+  D.n_maps = 0; D.height = nullptr; D.table = nullptr; D.tab_dx = D.tab_dy = nullptr; D.tab_ndx = D.tab_ndy = 0;
+  std::vector<double> start((size_t)Bc * QTOS_START_DOUBLES), goal((size_t)Bc * 3), dx0(Bc * n), sig(Bc * m), w(Bc * m);
+  const int N_OUT = 4;   // per problem: residual, refined residual, max |V|, its stage
+  double *d_out = nullptr, h_out[2 * 4];
+  HIPCHK(p, hipMalloc((void **)&d_out, (size_t)Bc * N_OUT * sizeof(double)));
+  hipStream_t st = p->own_stream;
+  hipError_t e = hipSuccess;
+  auto ok = [&](hipError_t r) { if (e == hipSuccess) e = r; return e == hipSuccess; };
+  for (int b0 = 0; b0 < N_PROBLEMS && e == hipSuccess; b0 += Bc) {
+    for (int j = 0; j < Bc; ++j) {
+      selftest_problem(M.P, start.data() + (size_t)j * QTOS_START_DOUBLES, goal.data() + (size_t)j * 3);
+      selftest_fill(seed, b0 + j, (int)n, (int)m, dx0.data() + j * n, sig.data() + j * m, w.data() + j * m);
+    }
+    DevWork W = p->wk;
+    W.start = p->d_start; W.goal = p->d_goal; W.map_id = nullptr; W.warm = nullptr;
+    ok(hipMemcpyAsync(p->d_start, start.data(), start.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    ok(hipMemcpyAsync(p->d_goal, goal.data(), goal.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    ok(hipMemcpyAsync(p->d_warm, dx0.data(), dx0.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    ok(hipMemcpyAsync(W.sig, sig.data(), sig.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    ok(hipMemcpyAsync(W.w, w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    if (e != hipSuccess) break;
+    hipLaunchKernelGGL(k_debug_guess, dim3(Bc), dim3(256), 0, st, D, W, Bc, p->d_nodes);
+    hipLaunchKernelGGL(k_selftest_nodes, dim3((unsigned)((Bc * n + 255) / 256)), dim3(256), 0, st, p->d_nodes, p->d_warm, Bc * n);
+    W.warm = p->d_warm;
+    hipLaunchKernelGGL(k_debug_eval, dim3(Bc), dim3(256), p->eval_lds, st, D, W, Bc);
+    hipLaunchKernelGGL(k_debug_pack, dim3(Bc), dim3(256), 0, st, D, W, Bc);
+    hipLaunchKernelGGL(p->kkt_fn, dim3(Bc), dim3(p->kkt_threads), p->kkt_lds, st, D, W, Bc);
+    hipLaunchKernelGGL(k_panel_absmax, dim3(Bc), dim3(256), 0, st, D, W, Bc, d_out + 2 * Bc);
+    if (D.n_rec) hipLaunchKernelGGL(k_recover_dx, dim3(Bc), dim3(256), 0, st, D, W, Bc);   // (as qtos_debug_newton hands dx out)
+    hipLaunchKernelGGL(k_residual, dim3(Bc), dim3(512), 0, st, D, W, Bc, d_out, p->chord_fn ? 1 : 0);   // r -> W.rhs, x remembered
+    if (p->chord_fn) {   // one step of refinement, as qtos_debug_residual(refine = 1)
+      hipLaunchKernelGGL(k_debug_flag_chord, dim3((Bc + 63) / 64), dim3(64), 0, st, W, Bc);
+      hipLaunchKernelGGL(p->chord_fn, dim3(Bc), dim3(KTC), chord_lds_bytes(S.n_stages, D.sw_on ? D.sw_steps : 0), st, D, W, Bc);
+      hipLaunchKernelGGL(k_debug_unchord, dim3((Bc + 63) / 64), dim3(64), 0, st, W, Bc);
+      hipLaunchKernelGGL(k_refine_add, dim3(Bc), dim3(512), 0, st, D, W, Bc);
+      hipLaunchKernelGGL(k_residual, dim3(Bc), dim3(512), 0, st, D, W, Bc, d_out + Bc, 0);
+    }
+    ok(hipGetLastError());
+    ok(hipMemcpyAsync(h_out, d_out, (size_t)Bc * N_OUT * sizeof(double), hipMemcpyDeviceToHost, st));
+    ok(hipStreamSynchronize(st));
+    if (e != hipSuccess) break;
+    for (int j = 0; j < Bc; ++j) {
+      const double res = h_out[j], res2 = h_out[Bc + j], vmax = h_out[2 * Bc + 2 * j];
+      // (a NaN is the worst result there is)
+      auto worse = [](double a, double c) { return a != a || c <= a ? a : c; };
+      out->residual = worse(out->residual, res);
+      if (p->chord_fn) out->residual_refined = out->n_problems == 0 ? res2 : worse(out->residual_refined, res2);
+      if (out->n_problems == 0 || vmax > out->max_factor) { out->max_factor = vmax; out->worst_stage = (int)h_out[2 * Bc + 2 * j + 1]; }
+      out->n_problems++;
+    }
+  }
+  (void)hipFree(d_out);
+  if (e != hipSuccess) { p->err = std::string("qtos_planner_selftest: ") + hipGetErrorString(e); return -2; }
+  out->passed = out->residual <= out->tol_residual && out->max_factor <= out->growth_limit;
+  out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
+  return 0;
+}
+
+// The order rules qtos_planner_create_checked would try, in the order it would try them (include/qtos_planner.h).  A rule whose
+// analysis fails comes last with front 0.
+struct Candidate {
+  int rule, front, stages, cont;
+  bool ok;
+  std::unique_ptr<Analysis> A;   // the default variant of the rule (create_planner takes it), unless the analysis is to talk
+};
+static std::vector<Candidate> order_candidates(const QtosParams &params, const QtosEnv &env, int rules_mask) {
+  QtosEnv quiet = env;
+  quiet.debug = 0; quiet.dump_first.clear();
+  const bool keep = !env.debug && env.dump_first.empty();
+  bool reduced = true;
+  auto analyse = [&](int rule) {
+    Candidate c = {rule, 0, 0, 0, false, std::make_unique<Analysis>()};
+    c.ok = build_analysis(*c.A, params, quiet, rule) == 0;
+    if (c.ok) { c.front = c.A->S.front; c.stages = c.A->S.n_stages; c.cont = c.A->S.n_continuation() > 0; }
+    reduced = c.A->M.reduce_base != 0;
+    if (!c.ok || !keep) c.A.reset();
+    return c;
+  };
+  std::vector<Candidate> out;
+  if (env.order >= 0) { out.push_back(analyse(env.order)); return out; }
+  // (rules 1 and 2 move the coefficients of a reduced base: without one rule 0 is the choice, as in pick_order_rule)
+  if (!params.reduce_base) { out.push_back(analyse(0)); return out; }
+  const int mask = (rules_mask & 7) ? (rules_mask & 7) : 6;
+  for (int rule : {2, 1, 0}) {
+    if (!((mask >> rule) & 1)) continue;
+    Candidate c = analyse(rule);
+    if (c.ok && !reduced) { out.clear(); out.push_back(analyse(0)); return out; }    // (the model kept the full base)
+    out.push_back(std::move(c));
+  }
+  // pick_order_rule's preference; the stable sort keeps 2 before 1 before 0 among equals
+  std::stable_sort(out.begin(), out.end(), [](const Candidate &a, const Candidate &b) {
+    if (a.ok != b.ok) return a.ok;
+    if (a.front != b.front) return a.front < b.front;
+    if (a.stages != b.stages) return a.stages < b.stages;
+    return a.cont < b.cont;
+  });
+  return out;
+}
+
+int qtos_analyze_candidates(const QtosParams *params, int rules_mask, int *rules, int *fronts, int *stages, int n) {
+  if (!params || n < 0) return -1;
+  const std::vector<Candidate> c = order_candidates(*params, QtosEnv::parse(), rules_mask);
+  for (int i = 0; i < (int)c.size() && i < n; ++i) {
+    if (rules) rules[i] = c[i].rule;
+    if (fronts) fronts[i] = c[i].front;
+    if (stages) stages[i] = c[i].stages;
+  }
+  return (int)c.size();
+}
+
+int qtos_planner_create_checked(const QtosParams *params, int max_batch, int device, int rules_mask, double tol_residual,
+                                QtosPlanner **out, QtosSelftest *tried, int max_tried, int *n_tried) {
+  if (n_tried) *n_tried = 0;
+  if (out) *out = nullptr;
+  if (!params || !out || max_batch < 1 || max_batch >= (1 << 24) || (max_tried > 0 && !tried) || max_tried < 0) return -1;
+  const QtosEnv env = QtosEnv::parse();
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= device) {   // (before any analysis: nothing can be tested)
+    fprintf(stderr, "qtos: no HIP device %d (found %d) -- the planner has no CPU fallback\n", device, ndev);
+    return -2;
+  }
+  std::vector<Candidate> cand = order_candidates(*params, env, rules_mask);
+  std::vector<QtosSelftest> log;
+  int first_rc = 0, n_built = 0;
+  for (Candidate &c : cand) {
+    QtosSelftest t;
+    std::memset(&t, 0, sizeof(t));
+    t.order_rule = c.rule; t.residual_refined = -1.0;
+    QtosPlanner *p = nullptr;
+    int rc = c.ok ? create_planner(params, max_batch, device, env, c.rule, &p, c.A.get()) : -1;
+    c.A.reset();
+    if (rc == 0) {
+      ++n_built;
+      rc = qtos_planner_selftest(p, 0, tol_residual, &t);
+      if (rc) fprintf(stderr, "qtos: %s\n", p->err.c_str());
+    }
+    if (rc && !first_rc) first_rc = rc;
+    if (rc) { t.passed = 0; t.front = 0; }
+    log.push_back(t);
+    if ((int)log.size() <= max_tried) tried[log.size() - 1] = t;
+    if (n_tried) *n_tried = std::min((int)log.size(), max_tried);
+    if (rc == 0 && t.passed) { *out = p; return 0; }
+    if (p) qtos_planner_destroy(p);
+  }
+  if (!n_built) return first_rc ? first_rc : -1;
+  fprintf(stderr, "qtos: no elimination order passed the KKT self-test:");
+  for (const QtosSelftest &t : log)
+    if (t.front) fprintf(stderr, " rule %d (front %d): residual %.2e (limit %.1e), max |V| %.3e (limit %.3e) in stage %d;", t.order_rule, t.front, t.residual, t.tol_residual, t.max_factor, t.growth_limit, t.worst_stage);
+    else fprintf(stderr, " rule %d: not built;", t.order_rule);
+  fprintf(stderr, "\n");
+  return -6;
 }
 
 }  // extern "C"

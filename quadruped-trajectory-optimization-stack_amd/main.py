@@ -2,17 +2,22 @@
 
 ``args['scripts']['run']`` of the reference (QTOS/utils.py:17, 'docker exec <id> ./main') can be
 pointed at ``python -m qtos_amd.main --out build/traj.csv`` unchanged otherwise.  ``--log PATH`` (``-``: stdout) writes
-the per-solve report in the layout of the reference's ``logs/towr_log.out`` (report.py).
+the per-solve report in the layout of the reference's ``logs/towr_log.out`` (report.py).  ``--selftest`` creates the planner
+through the KKT self-test (capi.Planner(checked=True)): a transcription whose elimination orders all fail it is not planned --
+the attempts are printed and the exit status is 2, the reference's "numerical failure" class.
 """
 import sys
 
-from . import flags
+from . import capi, flags
 from .planner import LocalPlanner, TOWR_HEIGHTFIELD
 
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     out, hf, log = "build/traj.csv", None, None
+    checked = "--selftest" in argv
+    if checked:
+        argv.remove("--selftest")
     for opt in ("--out", "--heightfield", "--log"):
         if opt in argv:
             i = argv.index(opt)
@@ -25,7 +30,7 @@ def main(argv=None):
             else:
                 hf = val
     args = flags.parse_flags(argv)
-    lp = LocalPlanner(max_batch=1)
+    lp = LocalPlanner(max_batch=1, checked=checked)
     try:
         import os
         path = hf or TOWR_HEIGHTFIELD
@@ -33,7 +38,13 @@ def main(argv=None):
             lp.load_heightfield_file(path, args.get('-resolution'))
         # --log PATH: the per-solve report (report.py) goes to PATH; --log -: to stdout, where it ends with the status line
         # -- the reference's logs/towr_log.out back from `python -m qtos_amd.main ... --log - > logs/towr_log.out`
-        status = lp.solve(args, out_csv=out, log=sys.stdout if log == "-" else log)
+        try:
+            status = lp.solve(args, out_csv=out, log=sys.stdout if log == "-" else log)
+        except capi.SelftestError as e:
+            for t in e.attempts:
+                print("KKT self-test: " + t.describe())
+            print("status -> 2")
+            return 2
         if log != "-":
             print("status -> %d" % status)  # the line the reference's log carries (logs/towr_log.out:85)
         return status

@@ -20,9 +20,11 @@ TRAJ_OUT = "./data/traj/towr.csv"                                             # 
 
 
 class LocalPlanner:
-    def __init__(self, cfg=None, max_batch=256, device=0):
+    def __init__(self, cfg=None, max_batch=256, device=0, checked=False):
+        """checked: every planner (one per ``-duration``) is created through the KKT self-test (capi.Planner(checked=True)):
+        a horizon whose elimination order loses digits raises capi.SelftestError instead of returning status-0 plans."""
         self.cfg = cfg or PlannerConfig.reference_compat()
-        self.max_batch, self.device = max_batch, device
+        self.max_batch, self.device, self.checked = max_batch, device, checked
         self._planners = {}
         self._terrain = None  # (maps[n][nx][ny], cell, x0, y0)
         self.last = None
@@ -60,7 +62,7 @@ class LocalPlanner:
                 kw["phase_durations"] = [[d * duration / cfg.duration for d in foot] for foot in cfg.phase_durations]
                 kw["duration"] = duration
                 cfg = PlannerConfig(**kw)
-            p = capi.Planner(cfg, self.max_batch, self.device)
+            p = capi.Planner(cfg, self.max_batch, self.device, checked=self.checked)
             p.set_kernel_events(False)   # (nobody reads per-kernel times behind this boundary: the event packets between the kernels cost a batch 1.9 %)
             self._push_terrain(p)
             self._planners[key] = p
@@ -135,7 +137,8 @@ class LocalPlanner:
                 P.set_report(False)
                 P.set_kernel_events(False)
             text = report.format_report(P.dims, capi.analyze_counts(P.cfg), rep, rows, P.cfg.max_iter,
-                                        seconds=(tm.get("total_seconds", 0.0), tm.get("kkt_seconds", 0.0)))
+                                        seconds=(tm.get("total_seconds", 0.0), tm.get("kkt_seconds", 0.0)),
+                                        selftests=P.selftests)
             if hasattr(log, "write"):
                 log.write(text)
                 log.flush()

@@ -36,13 +36,15 @@ class PlannerPool:
     lanes' streams are not ordered among each other).  Inputs are device tensors (float64 / int32, contiguous), complete
     at submit time, that must stay alive and unchanged until their batch has been handed over."""
 
-    def __init__(self, cfg, n_lanes=3, max_batch=256, device=0, heightfields=None, on_done=None, planner_factory=None):
+    def __init__(self, cfg, n_lanes=3, max_batch=256, device=0, heightfields=None, on_done=None, planner_factory=None, checked=False):
         import torch
         from .capi import Planner
         self.torch = torch
         self.dev = torch.device("cuda", device)
         self.on_done = on_done or (lambda lane: None)
-        make = planner_factory or (lambda: Planner(cfg, max_batch=max_batch, device=device))
+        # checked: every lane's planner is created through the KKT self-test (capi.Planner(checked=True): SelftestError if no
+        # elimination order passes); a planner_factory decides for itself
+        make = planner_factory or (lambda: Planner(cfg, max_batch=max_batch, device=device, checked=checked))
         self.lanes = []
         for _ in range(n_lanes):
             P = make()

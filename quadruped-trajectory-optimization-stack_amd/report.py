@@ -118,10 +118,20 @@ def exit_line(status, iterations, max_iter):
     return EXIT_LINES.get(int(status), "EXIT: Unknown status %d." % int(status))
 
 
-def format_report(dims, counts, rep, rows, max_iter, seconds=None):
+def selftest_line(t):
+    """The header's line on the create-time KKT self-test the planner passed (a capi.QtosSelftest)."""
+    return "KKT self-test: rule %d, residual %.1e, max |V| %.2e, %s" % (t.order_rule, t.residual, t.max_factor,
+                                                                        "passed" if t.passed else "rejected")
+
+
+def format_report(dims, counts, rep, rows, max_iter, seconds=None, selftests=None):
     """The whole report of one solve: dims (QtosDims), counts (capi.analyze_counts), rep (capi.QtosReport), rows (its
-    history), seconds (see final_lines).  Ends with ``status -> N``."""
-    lines = ["Per-solve report of the qtos_amd planner (interior point, HIP on gfx950).", ""]
+    history), seconds (see final_lines), selftests (the attempts of a planner that was created checked: the one it runs
+    is the last; None or empty: no line).  Ends with ``status -> N``."""
+    lines = ["Per-solve report of the qtos_amd planner (interior point, HIP on gfx950)."]
+    if selftests:
+        lines.append(selftest_line(selftests[-1]))
+    lines.append("")
     lines += header_lines(dims_dict(dims, counts)) + [""]
     lines += table_lines(rows) + [""]
     lines += final_lines(rep.iterations, rep.constraint_violation, rep.dual_infeasibility, rep.complementarity,
