@@ -265,6 +265,44 @@ int qtos_sample_csv(QtosPlanner *p, int B, const double *nodes, const double *t0
 int qtos_sample_csv_device(QtosPlanner *p, int B, const double *d_nodes, const double *d_t0,
                            double hz, int n_rows, double *d_rows_out, void *stream);
 
+/* Hand-over of a receding-horizon replan: which row of the plan being executed the next plan starts from, and that row's
+ * state.  Replaces Combiner._state and legs_in_contact (QTOS/combiner.py:78-92,245-296: read the CSV, go `lookahead` rows
+ * ahead, move on row by row until every foot stands on a known terrain height, zero_filter the state) for B windows at
+ * once, without a table of rows: one workgroup per window (k_handover) tests the candidate rows k0 .. k0 + n_search,
+ * k0 = round(advance * hz), n_search = round(search * hz), row k at plan time k / hz (clamped to the plan's duration as
+ * qtos_sample_csv clamps it), and evaluates the first that passes; k0 itself where none passes (the reference's fall-back
+ * to the un-shifted row).  The numbers are those of qtos_sample_csv's rows, to the bit. */
+typedef struct QtosHandover {
+  double advance, search, hz;   /* seconds, seconds, rows per second (hz <= 0: 1000) */
+  int rule;                     /* 0 force rule: f_z > 0 for all four feet (columns 27, 30, 33, 36 of the row);
+                                   1 height-set rule (Combiner._state): every foot's z (columns 9, 12, 15, 18), at 6 decimals,
+                                   is one of `heights`: rint(z * 1e6) == rint(h * 1e6) */
+  int n_heights;                /* rule 1: 1 .. 8 */
+  double heights[8];
+  int zero_filter;              /* 1: QTOS/utils.py zero_filter on start_out (|v| < 1e-4 -> 0) */
+  int turn;                     /* 1: turn a window round outside [x_lo, x_hi]: goal_step[b][0] = s |goal_step[b][0]|, s = -1 for
+                                   start_out[b][0] > x_hi, +1 for start_out[b][0] < x_lo, else the sign it has; in place */
+  double x_lo, x_hi;
+} QtosHandover;
+/* nodes B x n_vars (the windows' newest plans); start_out B x 24 = columns 1 .. 24 of the hand-over row (`start` of the next
+ * qtos_plan_batch*); offset_out B = row / hz (the plan time of the hand-over: `offset` of qtos_shift_warm*, the reference's
+ * lookahead / hz added to -t, QTOS/combiner.py:173); row_out B (may be NULL) the row index.  goal_step B x 3 (in / out, may be
+ * NULL): the displacement of a window's goal per plan; then goal_out[b][0:2] = start_out[b][0:2] + goal_step[b][0:2]
+ * (goal_out B x 3, NULL iff goal_step is NULL; goal_out[b][2] is not touched).
+ * Device form: all pointers but `h` in device memory, one kernel queued on `stream`, no handle state is read or written but
+ * the sampling tables -- launch pattern, totals and report flag stay, a plan call behind it returns the bits it would have
+ * returned without it, and it may be queued while a call is open.  Host form: host pointers, through the handle's staging
+ * buffers, synchronous; -5 while a call is open (between qtos_plan_submit and the end of qtos_plan_wait), B <= max_batch.
+ * Both: -1 on bad arguments -- a null planner or required pointer, B < 1, goal_step without goal_out or the reverse, a rule
+ * other than 0 / 1, rule 1 with n_heights outside 1 .. 8, advance < 0, search < 0, k0 beyond the plan's last row, a search of
+ * more than a million rows. */
+int qtos_handover(QtosPlanner *p, int B, const QtosHandover *h, const double *nodes, double *goal_step,
+                  double *start_out, double *goal_out, double *offset_out, int *row_out);
+int qtos_handover_device(QtosPlanner *p, int B, const QtosHandover *h, const double *d_nodes,
+                         double *d_goal_step /* in/out, may be NULL */, double *d_start_out,
+                         double *d_goal_out /* NULL iff d_goal_step is NULL */,
+                         double *d_offset_out, int *d_row_out /* may be NULL */, void *stream);
+
 /* The plan as the text file the reference copies out of its container (`docker cp <id>:.../build/traj.csv ./data/traj/towr.csv`,
  * scripts/main.py:90-92; consumers scripts/run.py:129-137, QTOS/combiner.py:263-274): rows is n_rows x 37 (one plan of
  * qtos_sample_csv), every number printed as the solver's C++ stream prints it (default precision 6 = printf "%g"), comma

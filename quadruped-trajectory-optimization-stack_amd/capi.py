@@ -86,6 +86,36 @@ class QtosSelftest(C.Structure):
                                                               "passed" if self.passed else "rejected (stage %d)" % self.worst_stage)
 
 
+class QtosHandover(C.Structure):
+    """Parameters of a replan's hand-over (qtos_handover*, include/qtos_planner.h)."""
+    _fields_ = [
+        ("advance", C.c_double), ("search", C.c_double), ("hz", C.c_double),
+        ("rule", C.c_int), ("n_heights", C.c_int), ("heights", C.c_double * 8),
+        ("zero_filter", C.c_int), ("turn", C.c_int), ("x_lo", C.c_double), ("x_hi", C.c_double),
+    ]
+
+
+HANDOVER_RULES = {"force": 0, "heights": 1}
+
+
+def handover_params(advance=2.5, search=0.4, hz=1000.0, rule="force", heights=(0.0,), zero_filter=False, x_range=None):
+    """A QtosHandover: rule "force" (all four f_z > 0) or "heights" (every foot's z, at 6 decimals, in `heights`: Combiner._state)."""
+    h = QtosHandover()
+    h.advance, h.search, h.hz = float(advance), float(search), float(hz)
+    h.rule = HANDOVER_RULES[rule] if isinstance(rule, str) else int(rule)
+    hs = [float(v) for v in heights] if h.rule == 1 else []
+    if len(hs) > 8:
+        raise ValueError("at most 8 terrain heights")
+    h.n_heights = len(hs)
+    for i, v in enumerate(hs):
+        h.heights[i] = v
+    h.zero_filter = int(bool(zero_filter))
+    h.turn = int(x_range is not None)
+    if x_range is not None:
+        h.x_lo, h.x_hi = float(x_range[0]), float(x_range[1])
+    return h
+
+
 class SelftestError(RuntimeError):
     """No elimination order passed the KKT self-test (qtos_planner_create_checked returned -6); `attempts`: the QtosSelftest
     records in the order they were tried."""
@@ -109,7 +139,7 @@ EXPORTS = [
     "qtos_last_timing_detail", "qtos_set_pattern_speculation", "qtos_env", "qtos_analyze_two_ended", "qtos_analyze_order", "qtos_set_kernel_events",
     "qtos_write_csv", "qtos_set_report", "qtos_plan_report", "qtos_analyze_counts", "qtos_debug_duals", "qtos_analyze_kernel",
     "qtos_planner_selftest", "qtos_planner_create_checked", "qtos_analyze_candidates", "qtos_selftest_inputs", "qtos_selftest_bits",
-    "qtos_selftest_problem",
+    "qtos_selftest_problem", "qtos_handover", "qtos_handover_device",
 ]
 
 _lib = None
@@ -208,6 +238,9 @@ def load():
         lib.qtos_selftest_bits.argtypes = [ull, C.c_int, C.c_int, ull]
         lib.qtos_selftest_bits.restype = ull
         lib.qtos_selftest_problem.argtypes = [C.POINTER(QtosParams), dp, dp]
+    if hasattr(lib, "qtos_handover"):   # (the hand-over kernel of the receding windows; older builds loaded through QTOS_LIB lack it)
+        lib.qtos_handover.argtypes = [vp, C.c_int, C.POINTER(QtosHandover), dp, dp, dp, dp, dp, ip]
+        lib.qtos_handover_device.argtypes = [vp, C.c_int, C.POINTER(QtosHandover), vp, vp, vp, vp, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -577,6 +610,30 @@ class Planner:
         out = np.empty((B, self.n))
         self._chk(self.lib.qtos_shift_warm(self.h, B, _dp(nodes_prev), _dp(off), _dp(start), _dp(goal), _ip(mid), _dp(out)), "shift_warm")
         return out
+
+    def has_handover(self):
+        return hasattr(self.lib, "qtos_handover")
+
+    def handover(self, nodes, advance=2.5, search=0.4, hz=1000.0, rule="force", heights=(0.0,), zero_filter=False,
+                 goal_step=None, goal=None, x_range=None):
+        """Hand-over of a replan (qtos_handover, host form): the first of the rows round(advance * hz) .. + round(search * hz)
+        of every plan in `nodes` that passes the contact rule.  Returns (start [B, 24], offset [B], row [B]); with goal_step
+        (B x 3; turned round outside x_range if that is given) and goal (B x 3; its z is kept) also their new values:
+        (start, offset, row, goal_step, goal)."""
+        if not self.has_handover():
+            raise RuntimeError("this build of the planner library has no hand-over kernel (qtos_handover)")
+        nodes = np.ascontiguousarray(nodes, np.float64).reshape(-1, self.n)
+        B = nodes.shape[0]
+        h = handover_params(advance, search, hz, rule, heights, zero_filter, x_range)
+        start, offset, row = np.empty((B, START_DOUBLES)), np.empty(B), np.empty(B, np.int32)
+        gs = gl = None
+        if (goal_step is None) != (goal is None):
+            raise ValueError("goal_step and goal go together: give both or neither")
+        if goal_step is not None:
+            gs = np.array(goal_step, np.float64).reshape(B, 3)
+            gl = np.array(goal, np.float64).reshape(B, 3)
+        self._chk(self.lib.qtos_handover(self.h, B, C.byref(h), _dp(nodes), _dp(gs), _dp(start), _dp(gl), _dp(offset), _ip(row)), "handover")
+        return (start, offset, row) if gs is None else (start, offset, row, gs, gl)
 
     # ---- optional: nominal-plan table for the starting point of cold solves ----
     def set_init_table(self, dx=None, dy=None, nodes=None):

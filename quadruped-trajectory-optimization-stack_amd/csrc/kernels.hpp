@@ -1943,6 +1943,16 @@ __device__ inline void sample_spline(const SampleSpline &S, const double *x, dou
   }
 }
 
+// Columns 1 .. 24 of a CSV row (the state a plan starts from, QTOS/combiner.py:263-274) at plan time t: k_sample's rows and
+// the one row k_handover evaluates per window go through these lines, so the two agree to the bit.
+__device__ inline void sample_row_state(const SamplePlan &S, const double *x, double t, double *row) {
+  sample_spline(S.lin, x, t, 0, row + 1);
+  sample_spline(S.ang, x, t, 0, row + 4);
+  for (int e = 0; e < NEE; ++e) sample_spline(S.eem[e], x, t, 0, row + 7 + 3 * e);
+  sample_spline(S.lin, x, t, 1, row + 19);
+  sample_spline(S.ang, x, t, 1, row + 22);
+}
+
 __global__ __launch_bounds__(256) void k_sample(SamplePlan S, const double *nodes, const double *t0, double hz,
                                                 int n_rows, double *rows, int B) {
   const int b = blockIdx.y;
@@ -1953,14 +1963,85 @@ __global__ __launch_bounds__(256) void k_sample(SamplePlan S, const double *node
   if (t > S.T) t = S.T;
   double row[QTOS_CSV_COLS];
   row[0] = t0[b] + k / hz;
-  sample_spline(S.lin, x, t, 0, row + 1);
-  sample_spline(S.ang, x, t, 0, row + 4);
-  for (int e = 0; e < NEE; ++e) sample_spline(S.eem[e], x, t, 0, row + 7 + 3 * e);
-  sample_spline(S.lin, x, t, 1, row + 19);
-  sample_spline(S.ang, x, t, 1, row + 22);
+  sample_row_state(S, x, t, row);
   for (int e = 0; e < NEE; ++e) sample_spline(S.eef[e], x, t, 0, row + 25 + 3 * e);
   double *out = rows + ((size_t)b * n_rows + k) * QTOS_CSV_COLS;
   for (int i = 0; i < QTOS_CSV_COLS; ++i) out[i] = row[i];
+}
+
+// Hand-over of a receding-horizon replan (qtos_handover*; QTOS/combiner.py:78-92, 245-296): one workgroup per window picks
+// the row of the window's newest plan the next plan starts from -- the first of the candidate rows k0 .. k0 + n_search with
+// all four feet in contact, k0 where none passes -- and evaluates that one row: no table of rows is written.  Lanes stride
+// over the candidates and evaluate only what the rule reads (z of the four force splines / of the four foot splines, the
+// very expressions of k_sample: the rule sees the numbers a sampled table would hold); the winning row's columns 1 .. 24
+// come from k_sample's own evaluator.  No scratch: the sampling tables come through a pointer (by value, as k_sample
+// takes them, the ten splines and these arguments do not fit the scalar registers), and the heights are read with constant
+// indices (a loop over an array in the kernel arguments copies it to scratch, see k_shift_warm).
+struct HandoverArgs {   // QtosHandover as the kernel reads it (qtos_planner.hip handover_args)
+  double hz, x_lo, x_hi;
+  double h6[8];         // rint(height * 1e6); NaN (equal to nothing) beyond n_heights
+  int rule, zero_filter, turn;
+  int k0, n_search;     // candidate rows k0 .. k0 + n_search
+};
+
+__device__ inline bool handover_contact(const SamplePlan &S, const HandoverArgs &H, const double *x, double t) {
+  bool all = true;
+#pragma unroll
+  for (int e = 0; e < NEE; ++e) {
+    double o3[3];
+    if (H.rule == 0) {   // (uniform over the workgroup)
+      sample_spline(S.eef[e], x, t, 0, o3);
+      all = all && o3[2] > 0;
+    } else {
+      sample_spline(S.eem[e], x, t, 0, o3);
+      const double z6 = rint(o3[2] * 1e6);
+      all = all && (z6 == H.h6[0] || z6 == H.h6[1] || z6 == H.h6[2] || z6 == H.h6[3] || z6 == H.h6[4] || z6 == H.h6[5] ||
+                    z6 == H.h6[6] || z6 == H.h6[7]);
+    }
+  }
+  return all;
+}
+
+__global__ __launch_bounds__(512) void k_handover(const SamplePlan *Sd, HandoverArgs H, const double *nodes, double *goal_step,
+                                                  double *start_out, double *goal_out, double *offset_out, int *row_out, int B) {
+  const int b = blockIdx.x;
+  if (b >= B) return;
+  __shared__ int first;
+  const SamplePlan &S = *Sd;
+  const double *x = nodes + (size_t)b * S.n_vars;
+  if (threadIdx.x == 0) first = INT_MAX;
+  __syncthreads();
+  for (int k = H.k0 + threadIdx.x; k <= H.k0 + H.n_search; k += blockDim.x) {   // (ascending per lane: its first hit is its smallest)
+    double t = k / H.hz;
+    if (t > S.T) t = S.T;
+    if (handover_contact(S, H, x, t)) { atomicMin(&first, k); break; }
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  const int k = first == INT_MAX ? H.k0 : first;
+  double t = k / H.hz;
+  if (t > S.T) t = S.T;
+  double row[1 + QTOS_START_DOUBLES];
+  sample_row_state(S, x, t, row);
+  double *st = start_out + (size_t)b * QTOS_START_DOUBLES;
+#pragma unroll
+  for (int i = 0; i < QTOS_START_DOUBLES; ++i) {
+    if (H.zero_filter && fabs(row[1 + i]) < 1e-4) row[1 + i] = 0.0;     // QTOS/utils.py zero_filter
+    st[i] = row[1 + i];
+  }
+  offset_out[b] = (double)k / H.hz;
+  if (row_out) row_out[b] = k;
+  if (goal_step) {
+    double *gs = goal_step + (size_t)b * 3;
+    double gx = gs[0];
+    if (H.turn) {   // a window past an end of its heightfield turns round
+      const double sgn = row[1] > H.x_hi ? -1.0 : (row[1] < H.x_lo ? 1.0 : (gx > 0 ? 1.0 : (gx < 0 ? -1.0 : 0.0)));
+      gx = sgn * fabs(gx);
+      gs[0] = gx;
+    }
+    goal_out[(size_t)b * 3 + 0] = row[1] + gx;
+    goal_out[(size_t)b * 3 + 1] = row[2] + gs[1];
+  }
 }
 
 }  // namespace qtos

@@ -38,6 +38,7 @@ struct Analysis { HostModel M; Symbolic S; };
 struct QtosPlanner : Analysis {   // (the analysis the planner runs: choose_kernel)
   DevPlan dp;
   SamplePlan sp;
+  SamplePlan *d_sp = nullptr;  // sp in device memory (k_handover reads the tables through a pointer)
   int device = 0, max_batch = 0;
   std::vector<void *> allocs;  // everything to free
   // workspace
@@ -677,6 +678,8 @@ static int create_planner(const QtosParams *params, int max_batch, int device, c
   SP.n_vars = M.n_vars; SP.T = M.T;
   TRY(upload_spline(p, M.lin, &SP.lin)); TRY(upload_spline(p, M.ang, &SP.ang));
   for (int e = 0; e < NEE; ++e) { TRY(upload_spline(p, M.eem[e], &SP.eem[e])); TRY(upload_spline(p, M.eef[e], &SP.eef[e])); }
+  TRY(p->alloc(&p->d_sp, 1));
+  HIPCHK(p, hipMemcpy(p->d_sp, &SP, sizeof(SP), hipMemcpyHostToDevice));
   // workspaces
   DevWork &W = p->wk;
   std::memset(&W, 0, sizeof(W));
@@ -1520,6 +1523,72 @@ int qtos_shift_warm(QtosPlanner *p, int B, const double *nodes_prev, const doubl
   }
   (void)hipFree(d_off);
   return rc;
+}
+
+// ---- hand-over of a replan (k_handover, kernels.hpp) --------------------------------------------------
+// The argument checks of both forms, and QtosHandover as k_handover reads it.
+static int handover_args(const QtosPlanner *p, int B, const QtosHandover *h, const void *nodes, const void *goal_step, const void *start_out,
+                         const void *goal_out, const void *offset_out, HandoverArgs *H) {
+  if (!p || B < 1 || !h || !nodes || !start_out || !offset_out || (goal_step == nullptr) != (goal_out == nullptr)) return -1;
+  if (h->rule != 0 && h->rule != 1) return -1;
+  if (h->rule == 1 && (h->n_heights < 1 || h->n_heights > 8)) return -1;
+  if (!(h->advance >= 0) || !(h->search >= 0)) return -1;
+  H->hz = h->hz > 0 ? h->hz : 1000.0;
+  const double last = std::round(p->M.T * H->hz), a = std::round(h->advance * H->hz), s = std::round(h->search * H->hz);
+  if (a > last || s > 1e6) return -1;
+  H->k0 = (int)a;
+  H->n_search = (int)s;
+  H->rule = h->rule; H->zero_filter = h->zero_filter != 0; H->turn = h->turn != 0;
+  H->x_lo = h->x_lo; H->x_hi = h->x_hi;
+  for (int j = 0; j < 8; ++j) H->h6[j] = h->rule == 1 && j < h->n_heights ? std::rint(h->heights[j] * 1e6) : NAN;
+  return 0;
+}
+
+static int handover_launch(QtosPlanner *p, int B, const HandoverArgs &H, const double *d_nodes, double *d_goal_step, double *d_start_out,
+                           double *d_goal_out, double *d_offset_out, int *d_row_out, hipStream_t st) {
+  HIPCHK(p, hipSetDevice(p->device));
+  hipLaunchKernelGGL(k_handover, dim3(B), dim3(512), 0, st, p->d_sp, H, d_nodes, d_goal_step, d_start_out, d_goal_out, d_offset_out,
+                     d_row_out, B);
+  HIPCHK(p, hipGetLastError());
+  return 0;
+}
+
+int qtos_handover_device(QtosPlanner *p, int B, const QtosHandover *h, const double *d_nodes, double *d_goal_step, double *d_start_out,
+                         double *d_goal_out, double *d_offset_out, int *d_row_out, void *stream_) {
+  HandoverArgs H;
+  if (handover_args(p, B, h, d_nodes, d_goal_step, d_start_out, d_goal_out, d_offset_out, &H)) return -1;
+  return handover_launch(p, B, H, d_nodes, d_goal_step, d_start_out, d_goal_out, d_offset_out, d_row_out, (hipStream_t)stream_);
+}
+
+int qtos_handover(QtosPlanner *p, int B, const QtosHandover *h, const double *nodes, double *goal_step, double *start_out, double *goal_out,
+                  double *offset_out, int *row_out) {
+  HandoverArgs H;
+  if (handover_args(p, B, h, nodes, goal_step, start_out, goal_out, offset_out, &H) || B > p->max_batch) return -1;
+  if (p->call_open || p->busy.load()) { p->err = "qtos_handover: a call is open (the host form goes through the handle's staging buffers)"; return -5; }
+  HIPCHK(p, hipSetDevice(p->device));
+  const size_t n = p->M.n_vars;
+  hipStream_t st = p->own_stream;
+  // staging: nodes, start and goal in their own buffers; goal step (3 B doubles), offset (B) and row (B ints) in the warm-start
+  // buffer: max_batch x n_vars doubles, and 5 B doubles are used -- a plan has hundreds of variables, checked all the same
+  if (n < 5) { p->err = "qtos_handover: the staging buffer is too small"; return -1; }
+  double *d_gs = p->d_warm, *d_off = p->d_warm + 3 * (size_t)B;
+  int *d_row = (int *)(p->d_warm + 4 * (size_t)B);
+  HIPCHK(p, hipMemcpyAsync(p->d_nodes, nodes, (size_t)B * n * sizeof(double), hipMemcpyHostToDevice, st));
+  if (goal_step) {
+    HIPCHK(p, hipMemcpyAsync(d_gs, goal_step, (size_t)B * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(p, hipMemcpyAsync(p->d_goal, goal_out, (size_t)B * 3 * sizeof(double), hipMemcpyHostToDevice, st));   // (goal_out[b][2] stays the caller's)
+  }
+  int rc = handover_launch(p, B, H, p->d_nodes, goal_step ? d_gs : nullptr, p->d_start, goal_step ? p->d_goal : nullptr, d_off, d_row, st);
+  if (rc) return rc;
+  HIPCHK(p, hipMemcpyAsync(start_out, p->d_start, (size_t)B * QTOS_START_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(p, hipMemcpyAsync(offset_out, d_off, B * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (row_out) HIPCHK(p, hipMemcpyAsync(row_out, d_row, B * sizeof(int), hipMemcpyDeviceToHost, st));
+  if (goal_step) {
+    HIPCHK(p, hipMemcpyAsync(goal_step, d_gs, (size_t)B * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(p, hipMemcpyAsync(goal_out, p->d_goal, (size_t)B * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+  }
+  HIPCHK(p, hipStreamSynchronize(st));
+  return 0;
 }
 
 int qtos_set_init_table(QtosPlanner *p, int ndx, const double *dx, int ndy, const double *dy, const double *nodes) {

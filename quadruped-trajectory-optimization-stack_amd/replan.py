@@ -123,14 +123,47 @@ class ReplanLoop:
         return self.plan
 
 
+def handover_index(rows, k0, n_search, rule, heights=(0.0,)):
+    """The hand-over rule of k_handover (qtos_handover*) stated in numpy, on a sampled row table: the first of the rows
+    k0 .. k0 + n_search (inclusive; as far as the table goes) that passes the contact rule, k0 where none does.
+
+    rule 0   force rule: f_z > 0 for all four feet (columns 27, 30, 33, 36)
+    rule 1   height-set rule (Combiner._state, QTOS/combiner.py:78-92; ``Stitcher.legs_in_contact``): every foot's z
+             (columns 9, 12, 15, 18) at 6 decimals is one of ``heights``: rint(z * 1e6) == rint(h * 1e6)
+
+    rows: (n_rows, 37) -> int, or (B, n_rows, 37) -> int64 array.  The table must be sampled from row 0 at the rate the
+    kernel is given (a table that covers the whole plan holds every row the kernel can pick: later rows repeat the last)."""
+    rows = np.asarray(rows, np.float64)
+    if rows.ndim == 2:
+        return int(handover_index(rows[None], k0, n_search, rule, heights)[0])
+    k0, n_search = int(k0), int(n_search)
+    cand = rows[:, k0:k0 + n_search + 1, :]
+    if rule == 0:
+        ok = (cand[:, :, 27:37:3] > 0).all(axis=2)
+    elif rule == 1:
+        known = np.rint(np.asarray([float(h) for h in heights], np.float64) * 1e6)
+        ok = (np.rint(cand[:, :, 9:19:3] * 1e6)[..., None] == known).any(axis=3).all(axis=2)
+    else:
+        raise ValueError("rule 0 (force) or 1 (height set)")
+    return np.where(ok.any(axis=1), k0 + ok.argmax(axis=1), k0).astype(np.int64)
+
+
 class ShiftedWindows:
     """B independent receding windows on one planner: every ``replan()`` starts every window from the row
     ``advance`` seconds into its newest plan (= the reference's hand-over row: a new plan starts ``lookahead``
     rows ahead of the robot's clock and the next one is asked for ``f_steps`` rows later, i.e. ``f_steps`` rows
     into the newest plan), moved on until all four feet are in contact; goals move with the windows; the
-    previous plan shifted by that time is the warm start.  Everything stays on the device (torch tensors)."""
+    previous plan shifted by that time is the warm start.  Everything stays on the device (torch tensors).
 
-    def __init__(self, planner, start, goal_step, map_id=None, advance=2.5, search=0.4, stream=None, warm="none", x_range=None):
+    handover   "kernel": one launch of k_handover per replan picks every window's row and writes start / offset / goal
+               (qtos_handover_device; the default where the library has it); "rows": the whole row table is sampled
+               (qtos_sample_csv_device) and searched with torch ops -- the same bits, kept for A/B
+    contact    "force" (all four f_z > 0) or "heights" (the reference's rule: every foot's z at 6 decimals in
+               ``height_set``, Combiner._state; "kernel" only).  They differ at stance boundaries, where the force spline
+               is exactly zero (``handover_index``)."""
+
+    def __init__(self, planner, start, goal_step, map_id=None, advance=2.5, search=0.4, stream=None, warm="none", x_range=None,
+                 handover=None, contact="force", height_set=(0.0,)):
         import torch
         self.torch = torch
         self.P = planner
@@ -153,7 +186,23 @@ class ShiftedWindows:
         self.viol = torch.empty((B,), **f64)
         self.advance, self.hz = float(advance), 1000.0
         self.n_search = int(round(search * self.hz))
-        self.rows = torch.empty((B, int(round(advance * self.hz)) + self.n_search + 1, 37), **f64)
+        if handover is None:
+            handover = "kernel" if hasattr(planner.lib, "qtos_handover_device") else "rows"
+        if handover not in ("kernel", "rows") or contact not in ("force", "heights"):
+            raise ValueError("handover is 'kernel' or 'rows', contact 'force' or 'heights'")
+        if contact == "heights" and handover != "kernel":
+            raise ValueError("contact='heights' needs handover='kernel'")
+        if handover == "kernel" and not hasattr(planner.lib, "qtos_handover_device"):
+            raise RuntimeError("this build of the planner library has no hand-over kernel (qtos_handover_device)")
+        self.handover, self.contact = handover, contact
+        k0 = int(round(advance * self.hz))
+        if handover == "rows":
+            self.rows = torch.empty((B, k0 + self.n_search + 1, 37), **f64)
+        else:
+            from . import capi
+            # (the row counts are rounded here, once: the kernel gets times that round to exactly these rows)
+            self._hand = capi.handover_params(k0 / self.hz, self.n_search / self.hz, self.hz, contact, height_set, False, x_range)
+            self.row = torch.zeros((B,), dtype=torch.int32, device=dev)      # hand-over row of the last replan
         self.t0 = torch.zeros((B,), **f64)
         self.offset = torch.zeros((B,), **f64)
         self.stream = stream if stream is not None else torch.cuda.current_stream(dev)
@@ -199,32 +248,44 @@ class ShiftedWindows:
         self._pending = False
         return True
 
+    def _handover_rows(self, sp):
+        """The hand-over through the sampled row table (handover="rows"): what _begin did before k_handover."""
+        import ctypes as C
+        torch, P, B = self.torch, self.P, self.B
+        # hand-over rows: sample the newest plan from `advance` on, take the first row with all feet in contact
+        # (force columns 25.. of a foot are non-zero exactly in stance: the reference tests foot heights against
+        # the terrain's height set, QTOS/combiner.py:78-92 -- the same rows on these maps)
+        n_rows = self.rows.shape[1]
+        self._call(P.lib.qtos_sample_csv_device(P.h, B, self.nodes.data_ptr(), self.t0.data_ptr(), C.c_double(self.hz), n_rows,
+                                                self.rows.data_ptr(), sp), "qtos_sample_csv_device")
+        k0 = n_rows - self.n_search - 1
+        cand = self.rows[:, k0:, :]
+        contact = (cand[:, :, 25:37].reshape(B, -1, 4, 3)[..., 2] > 0).all(dim=2)
+        first = torch.where(contact.any(dim=1), contact.to(torch.int32).argmax(dim=1), torch.zeros((B,), dtype=torch.int64, device=self.dev))
+        idx = k0 + first
+        hand = self.rows[torch.arange(B, device=self.dev), idx]
+        self.start.copy_(hand[:, 1:25])
+        self.offset.copy_(idx.to(torch.float64) / self.hz)
+        if self.x_range is not None:
+            lo, hi = self.x_range
+            x = self.start[:, 0]
+            sgn = torch.where(x > hi, -torch.ones_like(x), torch.where(x < lo, torch.ones_like(x), torch.sign(self.goal_step[:, 0])))
+            self.goal_step[:, 0] = sgn * self.goal_step[:, 0].abs()
+        self.goal[:, 0:2] = self.start[:, 0:2] + self.goal_step[:, 0:2]
+
     def _begin(self):
         import ctypes as C
         torch, P, B = self.torch, self.P, self.B
         sp = C.c_void_p(self.stream.cuda_stream)
         warm_ptr = None
         if self.have_plan:
-            # hand-over rows: sample the newest plan from `advance` on, take the first row with all feet in contact
-            # (force columns 25.. of a foot are non-zero exactly in stance: the reference tests foot heights against
-            # the terrain's height set, QTOS/combiner.py:78-92 -- the same rows on these maps)
-            n_rows = self.rows.shape[1]
-            self._call(P.lib.qtos_sample_csv_device(P.h, B, self.nodes.data_ptr(), self.t0.data_ptr(), C.c_double(self.hz), n_rows,
-                                                    self.rows.data_ptr(), sp), "qtos_sample_csv_device")
-            k0 = n_rows - self.n_search - 1
-            cand = self.rows[:, k0:, :]
-            contact = (cand[:, :, 25:37].reshape(B, -1, 4, 3)[..., 2] > 0).all(dim=2)
-            first = torch.where(contact.any(dim=1), contact.to(torch.int32).argmax(dim=1), torch.zeros((B,), dtype=torch.int64, device=self.dev))
-            idx = k0 + first
-            hand = self.rows[torch.arange(B, device=self.dev), idx]
-            self.start.copy_(hand[:, 1:25])
-            self.offset.copy_(idx.to(torch.float64) / self.hz)
-            if self.x_range is not None:
-                lo, hi = self.x_range
-                x = self.start[:, 0]
-                sgn = torch.where(x > hi, -torch.ones_like(x), torch.where(x < lo, torch.ones_like(x), torch.sign(self.goal_step[:, 0])))
-                self.goal_step[:, 0] = sgn * self.goal_step[:, 0].abs()
-            self.goal[:, 0:2] = self.start[:, 0:2] + self.goal_step[:, 0:2]
+            if self.handover == "kernel":
+                # hand-over: k_handover picks every window's row of its newest plan, evaluates it into start and moves the goal
+                self._call(P.lib.qtos_handover_device(P.h, B, C.byref(self._hand), self.nodes.data_ptr(), self.goal_step.data_ptr(),
+                                                      self.start.data_ptr(), self.goal.data_ptr(), self.offset.data_ptr(),
+                                                      self.row.data_ptr(), sp), "qtos_handover_device")
+            else:
+                self._handover_rows(sp)
             self.nodes, self.prev = self.prev, self.nodes
             if self.warm_mode == "shifted":
                 self._call(P.lib.qtos_shift_warm_device(P.h, B, self.prev.data_ptr(), self.offset.data_ptr(), self.start.data_ptr(),
