@@ -303,6 +303,44 @@ int qtos_handover_device(QtosPlanner *p, int B, const QtosHandover *h, const dou
                          double *d_goal_out /* NULL iff d_goal_step is NULL */,
                          double *d_offset_out, int *d_row_out /* may be NULL */, void *stream);
 
+/* Stitching of receding windows: the rows a window has executed, appended to a ring of CSV rows per window.  Replaces
+ * Combiner.combine and _truncate_csv (QTOS/combiner.py:125-135, 298-312: the old plan up to the hand-over row, then the new
+ * plan, written to the file the controller reads) for B windows at once.  A window executes a chain of plans P0, P1, ...: plan
+ * Pi has the nodes x_i and the time stamp t0_i of its first row, its hand-over row r_i is row_out of qtos_handover*, P(i+1)
+ * starts from the state of that row and t0_(i+1) = t0_i + r_i / hz.  Row k of a plan is row k of qtos_sample_csv, to the bit:
+ * 37 columns, time stamp t0 + k / hz, splines at min(k / hz, T).  The executed trajectory is the concatenation over i of the
+ * rows first_row .. first_row + r_i - 1 of Pi: first_row 0 keeps every row (old[:r] ++ new), first_row 1 is what the reference
+ * writes, whose pd.read_csv eats row 0 of both files (old[1:][:r] ++ new[1:]: the old plan's hand-over row stays and the new
+ * plan starts at its second row).  Both append r_i rows; only the first row differs.
+ * One call appends one plan's segment for every window b (k_stitch, one workgroup per window):
+ *   n = n_rows ? n_rows[b] : s->n_rows, clamped to 0 .. capacity
+ *   traj[b][(cursor[b] + j) mod capacity][0:37] = row first_row + j of plan b with the time stamp t0[b] + (first_row + j) / hz,
+ *                                                 j = 0 .. n - 1; the other cells of the ring are not touched
+ *   cursor[b] += n       (a running total, never reduced modulo capacity: min(cursor, capacity) rows of the ring are valid,
+ *                         the oldest at row cursor mod capacity once cursor >= capacity)
+ *   t0[b] += n / hz      if advance_clock: the clock of the window's next plan. */
+typedef struct QtosStitch {
+  double hz;           /* rows per second (<= 0: 1000) */
+  int first_row;       /* 0 clean, 1 the reference's read_csv behaviour; 0 .. 1000000 */
+  int n_rows;          /* count for every window where d_n_rows is NULL (>= 0) */
+  int advance_clock;   /* 1: t0[b] += n / hz */
+  long long capacity;  /* rows per window in the ring (>= 1) */
+} QtosStitch;
+/* nodes B x n_vars (the plans the segments are taken from: in a loop, the plans qtos_handover* was given); n_rows B (may be
+ * NULL: s->n_rows for every window; in a loop, row_out of qtos_handover*); t0 B (in / out); traj B x capacity x 37 (in / out);
+ * cursor B (in / out).
+ * Device form: all pointers but `s` in device memory, one kernel queued on `stream` (behind qtos_handover_device on the same
+ * stream d_n_rows may be its d_row_out), no handle state is read or written but the sampling tables -- launch pattern, totals
+ * and report flag stay, a plan call behind it returns the bits it would have returned without it, and it may be queued while a
+ * call is open.  Host form: host pointers, synchronous, through device buffers of its own as qtos_sample_csv (not the handle's
+ * staging buffers: no -5); the ring is copied in and the whole ring is copied out, the result is what the device form leaves.
+ * Both: -1 on a null planner or required pointer, B < 1, capacity < 1, first_row outside 0 .. 1000000, n_rows < 0 where
+ * d_n_rows is NULL; -2 on a HIP error; -3 out of memory. */
+int qtos_stitch_device(QtosPlanner *p, int B, const QtosStitch *s, const double *d_nodes, const int *d_n_rows /* may be NULL */,
+                       double *d_t0 /* in/out */, double *d_traj /* B x capacity x 37 */, long long *d_cursor /* in/out */, void *stream);
+int qtos_stitch(QtosPlanner *p, int B, const QtosStitch *s, const double *nodes, const int *n_rows,
+                double *t0, double *traj, long long *cursor);
+
 /* The plan as the text file the reference copies out of its container (`docker cp <id>:.../build/traj.csv ./data/traj/towr.csv`,
  * scripts/main.py:90-92; consumers scripts/run.py:129-137, QTOS/combiner.py:263-274): rows is n_rows x 37 (one plan of
  * qtos_sample_csv), every number printed as the solver's C++ stream prints it (default precision 6 = printf "%g"), comma

@@ -116,6 +116,26 @@ def handover_params(advance=2.5, search=0.4, hz=1000.0, rule="force", heights=(0
     return h
 
 
+class QtosStitch(C.Structure):
+    """Parameters of a stitch call (qtos_stitch*, include/qtos_planner.h)."""
+    _fields_ = [
+        ("hz", C.c_double), ("first_row", C.c_int), ("n_rows", C.c_int), ("advance_clock", C.c_int), ("capacity", C.c_longlong),
+    ]
+
+
+STITCH_MODES = {"clean": 0, "reference": 1}     # first_row of the two modes of stitcher.Stitcher
+
+
+def stitch_params(capacity, first_row=0, n_rows=0, hz=1000.0, advance_clock=True):
+    """A QtosStitch: rows first_row .. first_row + n - 1 of every window's plan go to its ring of `capacity` rows; first_row 0
+    ("clean") or 1 ("reference": pd.read_csv eats row 0, Stitcher(mode="reference"))."""
+    s = QtosStitch()
+    s.hz, s.capacity = float(hz), int(capacity)
+    s.first_row = STITCH_MODES[first_row] if isinstance(first_row, str) else int(first_row)
+    s.n_rows, s.advance_clock = int(n_rows), int(bool(advance_clock))
+    return s
+
+
 class SelftestError(RuntimeError):
     """No elimination order passed the KKT self-test (qtos_planner_create_checked returned -6); `attempts`: the QtosSelftest
     records in the order they were tried."""
@@ -139,7 +159,7 @@ EXPORTS = [
     "qtos_last_timing_detail", "qtos_set_pattern_speculation", "qtos_env", "qtos_analyze_two_ended", "qtos_analyze_order", "qtos_set_kernel_events",
     "qtos_write_csv", "qtos_set_report", "qtos_plan_report", "qtos_analyze_counts", "qtos_debug_duals", "qtos_analyze_kernel",
     "qtos_planner_selftest", "qtos_planner_create_checked", "qtos_analyze_candidates", "qtos_selftest_inputs", "qtos_selftest_bits",
-    "qtos_selftest_problem", "qtos_handover", "qtos_handover_device",
+    "qtos_selftest_problem", "qtos_handover", "qtos_handover_device", "qtos_stitch", "qtos_stitch_device",
 ]
 
 _lib = None
@@ -241,6 +261,10 @@ def load():
     if hasattr(lib, "qtos_handover"):   # (the hand-over kernel of the receding windows; older builds loaded through QTOS_LIB lack it)
         lib.qtos_handover.argtypes = [vp, C.c_int, C.POINTER(QtosHandover), dp, dp, dp, dp, dp, ip]
         lib.qtos_handover_device.argtypes = [vp, C.c_int, C.POINTER(QtosHandover), vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(lib, "qtos_stitch"):     # (the stitch kernel of the receding windows; older builds lack it)
+        llp = C.POINTER(C.c_longlong)
+        lib.qtos_stitch.argtypes = [vp, C.c_int, C.POINTER(QtosStitch), dp, ip, dp, dp, llp]
+        lib.qtos_stitch_device.argtypes = [vp, C.c_int, C.POINTER(QtosStitch), vp, vp, vp, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -634,6 +658,29 @@ class Planner:
             gl = np.array(goal, np.float64).reshape(B, 3)
         self._chk(self.lib.qtos_handover(self.h, B, C.byref(h), _dp(nodes), _dp(gs), _dp(start), _dp(gl), _dp(offset), _ip(row)), "handover")
         return (start, offset, row) if gs is None else (start, offset, row, gs, gl)
+
+    def has_stitch(self):
+        return hasattr(self.lib, "qtos_stitch")
+
+    def stitch(self, nodes, n_rows, t0, traj, cursor, first_row=0, hz=1000.0, advance_clock=True):
+        """Append an executed segment of every plan in `nodes` to its window's ring (qtos_stitch, host form): rows first_row ..
+        first_row + n - 1 with n = n_rows[b] (an array: in a loop, the hand-over rows) or n_rows (an int, for every window),
+        clamped to 0 .. capacity, go to traj[b][(cursor[b] + j) % capacity]; traj is (B, capacity, 37).  Returns new arrays
+        (traj, cursor, t0): cursor + n and, with advance_clock, t0 + n / hz."""
+        if not self.has_stitch():
+            raise RuntimeError("this build of the planner library has no stitch kernel (qtos_stitch)")
+        nodes = np.ascontiguousarray(nodes, np.float64).reshape(-1, self.n)
+        B = nodes.shape[0]
+        traj = np.array(traj, np.float64)
+        if traj.ndim != 3 or traj.shape[0] != B or traj.shape[2] != CSV_COLS:
+            raise ValueError("traj is (B, capacity, %d)" % CSV_COLS)
+        t0 = np.array(np.broadcast_to(np.asarray(t0, np.float64), (B,)))
+        cursor = np.array(np.broadcast_to(np.asarray(cursor, np.int64), (B,)))
+        per = None if np.ndim(n_rows) == 0 else np.ascontiguousarray(n_rows, np.int32).reshape(B)
+        s = stitch_params(traj.shape[1], first_row, 0 if per is not None else n_rows, hz, advance_clock)
+        self._chk(self.lib.qtos_stitch(self.h, B, C.byref(s), _dp(nodes), _ip(per), _dp(t0), _dp(traj),
+                                       cursor.ctypes.data_as(C.POINTER(C.c_longlong))), "stitch")
+        return traj, cursor, t0
 
     # ---- optional: nominal-plan table for the starting point of cold solves ----
     def set_init_table(self, dx=None, dy=None, nodes=None):

@@ -1953,17 +1953,27 @@ __device__ inline void sample_row_state(const SamplePlan &S, const double *x, do
   sample_spline(S.ang, x, t, 1, row + 22);
 }
 
+// Row k of a plan's CSV (QTOS/utils.py:107-148) but its forces: the time stamp t0 + k / hz in column 0 and the state in columns
+// 1 .. 24 at plan time min(k / hz, T).  Returns that plan time: the caller evaluates the four force splines of columns 25 .. 36
+// at it, in a loop of its own over S.eef -- with that loop in here k_sample, which takes the tables by value, loads all of
+// them into scalar registers at its start (93 instead of 35) and is no longer the code it was.  k_sample's table and the rows
+// k_stitch appends go through these lines and the same line for the forces, so the two agree to the bit.
+__device__ inline double sample_row_state_at(const SamplePlan &S, const double *x, double t0, int k, double hz, double *row) {
+  double t = k / hz;
+  if (t > S.T) t = S.T;
+  row[0] = t0 + k / hz;
+  sample_row_state(S, x, t, row);
+  return t;
+}
+
 __global__ __launch_bounds__(256) void k_sample(SamplePlan S, const double *nodes, const double *t0, double hz,
                                                 int n_rows, double *rows, int B) {
   const int b = blockIdx.y;
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B || k >= n_rows) return;
   const double *x = nodes + (size_t)b * S.n_vars;
-  double t = k / hz;
-  if (t > S.T) t = S.T;
   double row[QTOS_CSV_COLS];
-  row[0] = t0[b] + k / hz;
-  sample_row_state(S, x, t, row);
+  const double t = sample_row_state_at(S, x, t0[b], k, hz, row);
   for (int e = 0; e < NEE; ++e) sample_spline(S.eef[e], x, t, 0, row + 25 + 3 * e);
   double *out = rows + ((size_t)b * n_rows + k) * QTOS_CSV_COLS;
   for (int i = 0; i < QTOS_CSV_COLS; ++i) out[i] = row[i];
@@ -2041,6 +2051,68 @@ __global__ __launch_bounds__(512) void k_handover(const SamplePlan *Sd, Handover
     }
     goal_out[(size_t)b * 3 + 0] = row[1] + gx;
     goal_out[(size_t)b * 3 + 1] = row[2] + gs[1];
+  }
+}
+
+// Stitching of receding windows (qtos_stitch*; Combiner.combine, QTOS/combiner.py:125-135, 298-312): one workgroup per window
+// appends rows first_row .. first_row + n - 1 of the window's plan -- the segment that was executed before the next plan took
+// over -- to the window's ring of CSV rows, then moves the window's cursor and clock on.  One workgroup per window, so the
+// cursor and the clock are updated in place: every lane reads them before the barrier, lane 0 writes them at the end.
+// A lane evaluates one row of a tile with k_sample's evaluator (sample_row_state_at) and puts it into LDS; the tile then goes out
+// flat, consecutive lanes on consecutive doubles of the ring (k_sample's row per lane is 37 stores at a stride of 296 bytes;
+// this kernel is bound by its stores).  The LDS image keeps the rows' pitch of 37 doubles = 74 dwords: the 16 lanes of a
+// ds_write_b64 group land on banks 10 l mod 32 and the bank after each, all 32 distinct, and the flat read-back is
+// consecutive.  Element e of a tile goes to double (base * 37 + e) mod (capacity * 37) of the ring, base the ring row of
+// the tile's first row: a tile that straddles the wrap needs nothing else.  No scratch: the tables come through a pointer
+// and the row array is indexed with constants only (see k_handover).
+constexpr int STITCH_TILE = 512;   // rows per tile = lanes per workgroup: 512 x 37 x 8 = 151 552 bytes of LDS, one workgroup per CU
+struct StitchArgs {                // QtosStitch as the kernel reads it (qtos_planner.hip stitch_args)
+  double hz;
+  long long capacity;
+  int first_row, n_rows, advance_clock;
+};
+
+__global__ __launch_bounds__(STITCH_TILE) void k_stitch(const SamplePlan *Sd, StitchArgs A, const double *nodes, const int *n_rows,
+                                                        double *t0, double *traj, long long *cursor, int B) {
+  const int b = blockIdx.x;
+  if (b >= B) return;
+  __shared__ double tile[STITCH_TILE * QTOS_CSV_COLS];
+  const SamplePlan &S = *Sd;
+  const double *x = nodes + (size_t)b * S.n_vars;
+  const long long cur = cursor[b];
+  const double t0b = t0[b];
+  long long n = n_rows ? n_rows[b] : A.n_rows;
+  n = n < 0 ? 0 : (n > A.capacity ? A.capacity : n);
+  __syncthreads();                                       // (every lane holds the cursor and the clock: lane 0 may write them)
+  double *ring = traj + (size_t)b * (size_t)A.capacity * QTOS_CSV_COLS;
+  const long long ring_doubles = A.capacity * QTOS_CSV_COLS;
+  long long pos = cur % A.capacity;                      // ring row of the segment's first row
+  if (pos < 0) pos += A.capacity;
+  for (long long j0 = 0; j0 < n; j0 += STITCH_TILE) {    // (n is uniform over the workgroup: so are the barriers)
+    const int m = n - j0 < STITCH_TILE ? (int)(n - j0) : STITCH_TILE;
+    if ((int)threadIdx.x < m) {
+      const long long k = (long long)A.first_row + j0 + threadIdx.x;
+      double row[QTOS_CSV_COLS];
+      const double t = sample_row_state_at(S, x, t0b, k > INT_MAX ? INT_MAX : (int)k, A.hz, row);
+      for (int e = 0; e < NEE; ++e) sample_spline(S.eef[e], x, t, 0, row + 25 + 3 * e);
+      double *dst = tile + threadIdx.x * QTOS_CSV_COLS;
+#pragma unroll
+      for (int i = 0; i < QTOS_CSV_COLS; ++i) dst[i] = row[i];
+    }
+    __syncthreads();
+    long long base = pos + j0;                           // (pos < capacity and j0 < n <= capacity: one subtraction wraps it)
+    if (base >= A.capacity) base -= A.capacity;
+    base *= QTOS_CSV_COLS;
+    for (int e = threadIdx.x; e < m * QTOS_CSV_COLS; e += STITCH_TILE) {
+      long long o = base + e;                            // (m <= capacity: o < 2 ring_doubles)
+      if (o >= ring_doubles) o -= ring_doubles;
+      ring[o] = tile[e];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    cursor[b] = cur + n;
+    if (A.advance_clock) t0[b] = t0b + (double)n / A.hz;
   }
 }
 

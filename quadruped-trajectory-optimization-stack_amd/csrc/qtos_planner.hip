@@ -1591,6 +1591,64 @@ int qtos_handover(QtosPlanner *p, int B, const QtosHandover *h, const double *no
   return 0;
 }
 
+// ---- stitching of receding windows (k_stitch, kernels.hpp) ----------------------------------------------
+// The argument checks of both forms, and QtosStitch as k_stitch reads it.
+static int stitch_args(const QtosPlanner *p, int B, const QtosStitch *s, const void *nodes, const void *n_rows, const void *t0,
+                       const void *traj, const void *cursor, StitchArgs *A) {
+  if (!p || B < 1 || !s || !nodes || !t0 || !traj || !cursor) return -1;
+  if (s->capacity < 1 || s->first_row < 0 || s->first_row > 1000000 || (!n_rows && s->n_rows < 0)) return -1;
+  A->hz = s->hz > 0 ? s->hz : 1000.0;
+  A->capacity = s->capacity;
+  A->first_row = s->first_row; A->n_rows = s->n_rows; A->advance_clock = s->advance_clock != 0;
+  return 0;
+}
+
+int qtos_stitch_device(QtosPlanner *p, int B, const QtosStitch *s, const double *d_nodes, const int *d_n_rows, double *d_t0,
+                       double *d_traj, long long *d_cursor, void *stream_) {
+  StitchArgs A;
+  if (stitch_args(p, B, s, d_nodes, d_n_rows, d_t0, d_traj, d_cursor, &A)) return -1;
+  HIPCHK(p, hipSetDevice(p->device));
+  hipLaunchKernelGGL(k_stitch, dim3(B), dim3(STITCH_TILE), 0, (hipStream_t)stream_, p->d_sp, A, d_nodes, d_n_rows, d_t0, d_traj,
+                     d_cursor, B);
+  HIPCHK(p, hipGetLastError());
+  return 0;
+}
+
+int qtos_stitch(QtosPlanner *p, int B, const QtosStitch *s, const double *nodes, const int *n_rows, double *t0, double *traj,
+                long long *cursor) {
+  StitchArgs A;
+  if (stitch_args(p, B, s, nodes, n_rows, t0, traj, cursor, &A)) return -1;
+  HIPCHK(p, hipSetDevice(p->device));
+  // buffers of its own, as qtos_sample_csv: the handle's staging buffers are not touched, so it may run while a call is open
+  const size_t n = p->M.n_vars, ring_bytes = (size_t)B * (size_t)s->capacity * QTOS_CSV_COLS * sizeof(double);
+  double *d_nodes = nullptr, *d_t0 = nullptr, *d_traj = nullptr;
+  int *d_n = nullptr;
+  long long *d_cur = nullptr;
+  auto run = [&]() -> int {
+    HIPCHK(p, hipMalloc((void **)&d_nodes, (size_t)B * n * sizeof(double)));
+    HIPCHK(p, hipMalloc((void **)&d_t0, B * sizeof(double)));
+    HIPCHK(p, hipMalloc((void **)&d_cur, B * sizeof(long long)));
+    HIPCHK(p, hipMalloc((void **)&d_traj, ring_bytes));
+    if (n_rows) {
+      HIPCHK(p, hipMalloc((void **)&d_n, B * sizeof(int)));
+      HIPCHK(p, hipMemcpy(d_n, n_rows, B * sizeof(int), hipMemcpyHostToDevice));
+    }
+    HIPCHK(p, hipMemcpy(d_nodes, nodes, (size_t)B * n * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(p, hipMemcpy(d_t0, t0, B * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(p, hipMemcpy(d_cur, cursor, B * sizeof(long long), hipMemcpyHostToDevice));
+    HIPCHK(p, hipMemcpy(d_traj, traj, ring_bytes, hipMemcpyHostToDevice));
+    const int rc = qtos_stitch_device(p, B, s, d_nodes, d_n, d_t0, d_traj, d_cur, nullptr);
+    if (rc) return rc;
+    HIPCHK(p, hipMemcpy(traj, d_traj, ring_bytes, hipMemcpyDeviceToHost));
+    HIPCHK(p, hipMemcpy(t0, d_t0, B * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(p, hipMemcpy(cursor, d_cur, B * sizeof(long long), hipMemcpyDeviceToHost));
+    return 0;
+  };
+  const int rc = run();
+  (void)hipFree(d_nodes); (void)hipFree(d_t0); (void)hipFree(d_cur); (void)hipFree(d_traj); (void)hipFree(d_n);
+  return rc;
+}
+
 int qtos_set_init_table(QtosPlanner *p, int ndx, const double *dx, int ndy, const double *dy, const double *nodes) {
   if (!p) return -1;
   HIPCHK(p, hipSetDevice(p->device));

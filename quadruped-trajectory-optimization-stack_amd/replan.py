@@ -160,10 +160,17 @@ class ShiftedWindows:
                (qtos_sample_csv_device) and searched with torch ops -- the same bits, kept for A/B
     contact    "force" (all four f_z > 0) or "heights" (the reference's rule: every foot's z at 6 decimals in
                ``height_set``, Combiner._state; "kernel" only).  They differ at stance boundaries, where the force spline
-               is exactly zero (``handover_index``)."""
+               is exactly zero (``handover_index``).
+    trajectory None (the default): nothing is kept of the plans but the newest.  An int: every window keeps a ring of that many
+               CSV rows (``self.traj``, B x trajectory x 37, with the running row count ``self.cursor``) and every replan
+               appends the rows the window executed of the plan it hands over from (k_stitch through qtos_stitch_device,
+               ``stitcher.stitch_segments``); ``self.t0`` is then the windows' clock: the time stamp of row 0 of the newest
+               plan.  ``finish()`` appends the rest of the newest plan, ``trajectory_rows(b)`` reads a window's ring.
+    stitch     "clean" (every row: old[:r] ++ new) or "reference" (the reference's files, whose first row pd.read_csv eats:
+               old[1:][:r] ++ new[1:], ``Stitcher(mode="reference")``)"""
 
     def __init__(self, planner, start, goal_step, map_id=None, advance=2.5, search=0.4, stream=None, warm="none", x_range=None,
-                 handover=None, contact="force", height_set=(0.0,)):
+                 handover=None, contact="force", height_set=(0.0,), trajectory=None, stitch="clean"):
         import torch
         self.torch = torch
         self.P = planner
@@ -205,6 +212,18 @@ class ShiftedWindows:
             self.row = torch.zeros((B,), dtype=torch.int32, device=dev)      # hand-over row of the last replan
         self.t0 = torch.zeros((B,), **f64)
         self.offset = torch.zeros((B,), **f64)
+        self.traj = None
+        if trajectory is not None:
+            from . import capi
+            if stitch not in capi.STITCH_MODES:
+                raise ValueError("stitch is 'clean' or 'reference'")
+            if not hasattr(planner.lib, "qtos_stitch_device"):
+                raise RuntimeError("this build of the planner library has no stitch kernel (qtos_stitch_device)")
+            self._stitch = capi.stitch_params(int(trajectory), stitch, 0, self.hz, True)
+            self.traj = torch.zeros((B, int(trajectory), 37), **f64)
+            self.cursor = torch.zeros((B,), dtype=torch.int64, device=dev)
+            if handover == "rows":
+                self.row = torch.zeros((B,), dtype=torch.int32, device=dev)
         self.stream = stream if stream is not None else torch.cuda.current_stream(dev)
         self.have_plan = False
         self.x_range = x_range     # (lo, hi): a window that walks past an end of its heightfield turns round (no resets)
@@ -248,6 +267,33 @@ class ShiftedWindows:
         self._pending = False
         return True
 
+    def finish(self):
+        """The end of the loop (with ``trajectory``): append the rest of the newest plan, its rows first_row .. the last, to
+        every window's ring.  The clock stays: ``t0`` is still the time stamp of that plan's row 0."""
+        import ctypes as C
+        from . import capi
+        if self.traj is None:
+            raise RuntimeError("finish() needs a trajectory ring (trajectory=...)")
+        if getattr(self, "_pending", False) or not self.have_plan:
+            raise RuntimeError("finish() needs a finished replan: poll() it first")
+        n_all = int(round(self.P.dims.duration * self.hz)) + 1
+        first, cap = int(self._stitch.first_row), int(self._stitch.capacity)
+        while first < n_all:        # (a call appends at most `capacity` rows: a plan longer than the ring goes in pieces, its newest rows stay)
+            n = min(n_all - first, cap)
+            s = capi.stitch_params(cap, first, n, self.hz, False)
+            self._call(self.P.lib.qtos_stitch_device(self.P.h, self.B, C.byref(s), self.nodes.data_ptr(), None, self.t0.data_ptr(),
+                                                     self.traj.data_ptr(), self.cursor.data_ptr(), C.c_void_p(self.stream.cuda_stream)),
+                       "qtos_stitch_device")
+            first += n
+
+    def trajectory_rows(self, b):
+        """Window b's newest min(cursor, trajectory) rows in time order, as numpy (the stream is synchronised)."""
+        from .stitcher import ring_rows
+        if self.traj is None:
+            raise RuntimeError("trajectory_rows() needs a trajectory ring (trajectory=...)")
+        self.stream.synchronize()
+        return ring_rows(self.traj[b].cpu().numpy(), int(self.cursor[b].item()))
+
     def _handover_rows(self, sp):
         """The hand-over through the sampled row table (handover="rows"): what _begin did before k_handover."""
         import ctypes as C
@@ -266,6 +312,8 @@ class ShiftedWindows:
         hand = self.rows[torch.arange(B, device=self.dev), idx]
         self.start.copy_(hand[:, 1:25])
         self.offset.copy_(idx.to(torch.float64) / self.hz)
+        if self.traj is not None:
+            self.row.copy_(idx)
         if self.x_range is not None:
             lo, hi = self.x_range
             x = self.start[:, 0]
@@ -286,6 +334,11 @@ class ShiftedWindows:
                                                       self.row.data_ptr(), sp), "qtos_handover_device")
             else:
                 self._handover_rows(sp)
+            if self.traj is not None:
+                # the rows executed of the plan handed over from go to the windows' rings; t0 moves on to the new plan's row 0
+                self._call(P.lib.qtos_stitch_device(P.h, B, C.byref(self._stitch), self.nodes.data_ptr(), self.row.data_ptr(),
+                                                    self.t0.data_ptr(), self.traj.data_ptr(), self.cursor.data_ptr(), sp),
+                           "qtos_stitch_device")
             self.nodes, self.prev = self.prev, self.nodes
             if self.warm_mode == "shifted":
                 self._call(P.lib.qtos_shift_warm_device(P.h, B, self.prev.data_ptr(), self.offset.data_ptr(), self.start.data_ptr(),

@@ -98,3 +98,37 @@ class Stitcher:
         else:
             old, new = old_rows[start:end], new_rows
         return np.concatenate([old, new], axis=0)
+
+
+def stitch_segments(tables, rows, first_row):
+    """The rule of k_stitch (qtos_stitch*) stated in numpy, on sampled row tables: a window executes the plans P0, P1, ...
+    (``tables[i]``: the rows of Pi, sampled from its row 0 with its own time stamp t0_i) and hands over at row ``rows[i]`` of
+    Pi; the executed trajectory is the concatenation of the rows first_row .. first_row + rows[i] - 1 of every Pi.
+    first_row 0 is ``Stitcher(mode="clean")`` (old[:r] ++ new), 1 is ``mode="reference"`` (old[1:][:r] ++ new[1:]): both append
+    rows[i] rows, only the first row differs.  Every table must reach row first_row + rows[i] - 1."""
+    first_row = int(first_row)
+    segs = []
+    for t, r in zip(tables, rows):
+        t, r = np.asarray(t, np.float64), max(int(r), 0)
+        if first_row + r > len(t):
+            raise ValueError("the table ends before row first_row + rows - 1")
+        segs.append(t[first_row:first_row + r])
+    return np.concatenate(segs, axis=0) if segs else np.zeros((0, 37))
+
+
+def ring_append(ring, cursor, seg):
+    """Append the rows of ``seg`` to a ring of ``len(ring)`` rows in place: row j goes to ring[(cursor + j) % capacity]; a
+    segment longer than the ring keeps its first ``capacity`` rows (k_stitch clamps the count).  Returns the new cursor, a
+    running total that is never reduced modulo the capacity."""
+    cap = len(ring)
+    seg = np.asarray(seg)[:cap]
+    ring[(int(cursor) + np.arange(len(seg))) % cap] = seg
+    return int(cursor) + len(seg)
+
+
+def ring_rows(ring, cursor):
+    """The newest min(cursor, capacity) rows of a ring in time order."""
+    cap, cursor = len(ring), int(cursor)
+    if cursor <= cap:
+        return np.array(ring[:cursor])
+    return np.roll(ring, -(cursor % cap), axis=0)
