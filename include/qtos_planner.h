@@ -341,6 +341,66 @@ int qtos_stitch_device(QtosPlanner *p, int B, const QtosStitch *s, const double 
 int qtos_stitch(QtosPlanner *p, int B, const QtosStitch *s, const double *nodes, const int *n_rows,
                 double *t0, double *traj, long long *cursor);
 
+/* Goals of receding windows from their global paths: where the next plan goes.  Replaces Global_Planner.update / spine_step
+ * (QTOS/planner.py:139-161, 195-230) and Combiner.plan_init / spine_step (QTOS/combiner.py:137-212, 223-225) for B windows at
+ * once: a window's A* "spine" -- two cubic splines X_p, Y_p over one set of knots -- is read one horizon ahead of the new plan's
+ * start, the displacement from a base point is clipped to step_size per axis, and the goal height is the terrain under the goal
+ * + z_offset.  One lane per window (k_path_goal); per window b, with p its path and H(x, y) the height rule below:
+ *   lt = clock[b] + offset[b]                          the plan time of the new plan's row 0;  tf = lt + horizon
+ *   sx = X_p(tf), 0.0 unless |sx| > tol;  sy likewise;  gz = H(sx, sy) + z_offset
+ *   clamp_x: sx = robot_goal[p][0] where sx is larger      (Combiner.spine_step; behind gz, as the reference does)
+ *   base 0 (spine, Global_Planner.update): (X_p(lt), Y_p(lt), H(X_p(lt), Y_p(lt)) + z_offset), without the tol rule
+ *   base 1 (state, plan_init and spine_step(com, t)): start[b][0:3]
+ *   goal_out[b] = base + clip((sx, sy, gz) - base, -step_size, +step_size)       per component; a NaN stays a NaN
+ *   bit 0: t_end[p] < lt - t_stop   (t_end the path's last knot; the reference stops with t_stop = 5 + lookahead / hz)
+ *   bit 1: stop_dist > 0 and sqrt(dx dx + dy dy) < stop_dist, (dx, dy) = start[b][0:2] - goal_out[b][0:2]  (scripts/main.py:40-46)
+ *   done[b] |= bits (sticky);  hold_done: goal_out[b] = start[b][0:3] where done[b] is now non-zero -- the window stands still
+ *   instead of following the spline's extrapolation beyond the path's end;  advance_clock: clock[b] = lt.
+ * A spline is evaluated as scipy's CubicSpline evaluates it, to the bit: piece i = the number of knots <= t, less one, kept
+ * within 0 .. n - 1 (times before the first knot use piece 0, times at or beyond the last knot piece n - 1), s = t - x[i],
+ * res = 0, z = 1, four times res = res + c[3 - kp][i] * z, z = z * s -- every operation one rounded IEEE double operation.
+ * H: row = floor((y + origin_y) / cell), col = floor((x + origin_x) / cell); a negative index down to -rows / -cols wraps as
+ * Python's does; anything else (out of range, non-finite) reads the cell [rows - 1][cols / 2].  The numpy statement of all of
+ * this is global_planner.path_goal, which the kernel equals to the bit. */
+typedef struct QtosPathGoal {
+  double horizon;              /* seconds the spine is read ahead of the plan's start (the reference: 5.0)      */
+  double step_size;            /* clip of the goal's displacement per axis (>= 0)                               */
+  double tol;                  /* a spine coordinate within tol of zero is zero (the reference: 1e-5)           */
+  double z_offset;             /* height of the base above the terrain (the reference: 0.24)                    */
+  double cell, origin_x, origin_y;  /* of the height grids (> 0; the reference: 0.1, 1.0, 1.0)                  */
+  double t_stop, stop_dist;    /* the done bits (stop_dist <= 0: no bit 1)                                      */
+  int base;                    /* 0 spine, 1 state                                                              */
+  int clamp_x, advance_clock, hold_done;
+  int n_paths, max_pieces;     /* of the path table (>= 1)                                                      */
+  int n_maps, rows, cols;      /* of the height grids (>= 1 where a grid is given)                              */
+} QtosPathGoal;
+/* The path table (global_planner.path_table): knots n_paths x (max_pieces + 1), the rows of shorter paths padded with their
+ * last knot; coef n_paths x 2 x 4 x max_pieces, X then Y, scipy's layout (coef[p][a][k][i] multiplies (t - x[i])^(3 - k)),
+ * padding zero; n_pieces n_paths (values outside 1 .. max_pieces are read as the nearest of the two); robot_goal n_paths x 3
+ * (may be NULL without clamp_x).  path_id B (may be NULL: window b follows path b, which needs n_paths >= B; ids outside the
+ * table are read as the nearest path); height_yx n_maps x rows x cols (may be NULL: every height is 0) with map_id B (may be
+ * NULL: map 0; ids outside are read as the nearest map); clock B (in / out: written only with advance_clock); offset B (may be
+ * NULL: 0; in a loop, offset_out of qtos_handover*); start B x 24 (in a loop, start_out of qtos_handover*; may be NULL where
+ * nothing reads it: base 0, stop_dist <= 0 and hold_done off); goal_out B x 3; done B (in / out, may be NULL: no done bits are
+ * kept -- hold_done needs it).
+ * Device form: all pointers but `g` in device memory, one kernel queued on `stream`; directly behind qtos_handover_device on the
+ * same stream d_start / d_offset may be its d_start_out / d_offset_out.  No handle state is read or written -- launch pattern,
+ * totals and report flag stay, a plan call behind it returns the bits it would have returned without it, and it may be queued
+ * while a call is open.  Host form: host pointers, synchronous, through device buffers of its own as qtos_stitch (no -5); the
+ * result is what the device form leaves.
+ * Both: -1 on bad arguments, with no kernel launched -- a null planner or required pointer, B < 1, n_paths or max_pieces < 1,
+ * path_id NULL with n_paths < B, a height grid with n_maps, rows or cols < 1, cell <= 0, step_size < 0 (or any of the two not a
+ * number), base outside 0 / 1, clamp_x without robot_goal, hold_done without done, start NULL where it is read; -2 on a HIP
+ * error; -3 out of memory. */
+int qtos_path_goal_device(QtosPlanner *p, int B, const QtosPathGoal *g, const double *d_knots, const double *d_coef,
+                          const int *d_n_pieces, const double *d_robot_goal /* may be NULL */, const int *d_path_id /* may be NULL */,
+                          const double *d_height_yx /* may be NULL */, const int *d_map_id /* may be NULL */, double *d_clock /* in/out */,
+                          const double *d_offset /* may be NULL */, const double *d_start /* may be NULL */, double *d_goal_out,
+                          int *d_done /* in/out, may be NULL */, void *stream);
+int qtos_path_goal(QtosPlanner *p, int B, const QtosPathGoal *g, const double *knots, const double *coef, const int *n_pieces,
+                   const double *robot_goal, const int *path_id, const double *height_yx, const int *map_id, double *clock,
+                   const double *offset, const double *start, double *goal_out, int *done);
+
 /* The plan as the text file the reference copies out of its container (`docker cp <id>:.../build/traj.csv ./data/traj/towr.csv`,
  * scripts/main.py:90-92; consumers scripts/run.py:129-137, QTOS/combiner.py:263-274): rows is n_rows x 37 (one plan of
  * qtos_sample_csv), every number printed as the solver's C++ stream prints it (default precision 6 = printf "%g"), comma

@@ -136,6 +136,40 @@ def stitch_params(capacity, first_row=0, n_rows=0, hz=1000.0, advance_clock=True
     return s
 
 
+class QtosPathGoal(C.Structure):
+    """Parameters of a path-goal call (qtos_path_goal*, include/qtos_planner.h)."""
+    _fields_ = [
+        ("horizon", C.c_double), ("step_size", C.c_double), ("tol", C.c_double), ("z_offset", C.c_double),
+        ("cell", C.c_double), ("origin_x", C.c_double), ("origin_y", C.c_double), ("t_stop", C.c_double), ("stop_dist", C.c_double),
+        ("base", C.c_int), ("clamp_x", C.c_int), ("advance_clock", C.c_int), ("hold_done", C.c_int),
+        ("n_paths", C.c_int), ("max_pieces", C.c_int), ("n_maps", C.c_int), ("rows", C.c_int), ("cols", C.c_int),
+    ]
+
+    def copy(self):
+        return QtosPathGoal.from_buffer_copy(self)
+
+
+PATH_BASES = {"spine": 0, "state": 1}      # base point of the clipped step: Global_Planner.update / plan_init
+
+
+def path_goal_params(horizon=5.0, step_size=1.0, tol=1e-5, z_offset=0.24, cell=0.1, origin=(1.0, 1.0), t_stop=5.0, stop_dist=0.0,
+                     base="spine", clamp_x=False, advance_clock=True, hold_done=False, table=None, map_yx=None):
+    """A QtosPathGoal with the reference's constants as defaults; base "spine" (Global_Planner.update) or "state" (plan_init,
+    spine_step(com, t)).  table (global_planner.path_table) and map_yx (n_maps x rows x cols, or rows x cols) fill the sizes."""
+    g = QtosPathGoal()
+    g.horizon, g.step_size, g.tol, g.z_offset = float(horizon), float(step_size), float(tol), float(z_offset)
+    g.cell, g.origin_x, g.origin_y = float(cell), float(origin[0]), float(origin[1])
+    g.t_stop, g.stop_dist = float(t_stop), float(stop_dist)
+    g.base = PATH_BASES[base] if isinstance(base, str) else int(base)
+    g.clamp_x, g.advance_clock, g.hold_done = int(bool(clamp_x)), int(bool(advance_clock)), int(bool(hold_done))
+    if table is not None:
+        g.n_paths, g.max_pieces = (int(v) for v in np.shape(table["coef"])[0::3])
+    if map_yx is not None:
+        shape = np.shape(map_yx)
+        g.n_maps, g.rows, g.cols = (1,) + tuple(shape) if len(shape) == 2 else tuple(shape)
+    return g
+
+
 class SelftestError(RuntimeError):
     """No elimination order passed the KKT self-test (qtos_planner_create_checked returned -6); `attempts`: the QtosSelftest
     records in the order they were tried."""
@@ -160,6 +194,7 @@ EXPORTS = [
     "qtos_write_csv", "qtos_set_report", "qtos_plan_report", "qtos_analyze_counts", "qtos_debug_duals", "qtos_analyze_kernel",
     "qtos_planner_selftest", "qtos_planner_create_checked", "qtos_analyze_candidates", "qtos_selftest_inputs", "qtos_selftest_bits",
     "qtos_selftest_problem", "qtos_handover", "qtos_handover_device", "qtos_stitch", "qtos_stitch_device",
+    "qtos_path_goal", "qtos_path_goal_device",
 ]
 
 _lib = None
@@ -265,6 +300,9 @@ def load():
         llp = C.POINTER(C.c_longlong)
         lib.qtos_stitch.argtypes = [vp, C.c_int, C.POINTER(QtosStitch), dp, ip, dp, dp, llp]
         lib.qtos_stitch_device.argtypes = [vp, C.c_int, C.POINTER(QtosStitch), vp, vp, vp, vp, vp, vp]
+    if hasattr(lib, "qtos_path_goal"):  # (the path-goal kernel of the receding windows; older builds lack it)
+        lib.qtos_path_goal.argtypes = [vp, C.c_int, C.POINTER(QtosPathGoal), dp, dp, ip, dp, ip, dp, ip, dp, dp, dp, dp, ip]
+        lib.qtos_path_goal_device.argtypes = [vp, C.c_int, C.POINTER(QtosPathGoal)] + [vp] * 13
     _lib = lib
     return lib
 
@@ -681,6 +719,43 @@ class Planner:
         self._chk(self.lib.qtos_stitch(self.h, B, C.byref(s), _dp(nodes), _ip(per), _dp(t0), _dp(traj),
                                        cursor.ctypes.data_as(C.POINTER(C.c_longlong))), "stitch")
         return traj, cursor, t0
+
+    def has_path_goal(self):
+        return hasattr(self.lib, "qtos_path_goal")
+
+    def path_goal(self, table, clock, params, path_id=None, map_yx=None, map_id=None, offset=None, start=None, done=None):
+        """Goals of the windows' next plans from their global paths (qtos_path_goal, host form; the rule:
+        global_planner.path_goal).  table: global_planner.path_table; clock [B]; params: a QtosPathGoal (path_goal_params; the
+        sizes of the table and the grids are filled in here); path_id [B] (None: window b follows path b); map_yx n_maps x rows x
+        cols or rows x cols (None: every height 0) with map_id [B] (None: map 0); offset [B] (None: 0); start [B, 24] (None where
+        nothing reads it); done [B] (None: no done bits are kept).  Returns new arrays (goal [B, 3], done [B] int32 or None,
+        clock [B])."""
+        if not self.has_path_goal():
+            raise RuntimeError("this build of the planner library has no path-goal kernel (qtos_path_goal)")
+        clock = np.array(clock, np.float64).reshape(-1)
+        B = len(clock)
+        g = params.copy()
+        knots = np.ascontiguousarray(table["knots"], np.float64)
+        coef = np.ascontiguousarray(table["coef"], np.float64)
+        npc = np.ascontiguousarray(table["n_pieces"], np.int32)
+        rg = None if table.get("robot_goal") is None else np.ascontiguousarray(table["robot_goal"], np.float64)
+        g.n_paths, g.max_pieces = coef.shape[0], coef.shape[3]
+        if knots.shape != (g.n_paths, g.max_pieces + 1) or coef.shape[1:3] != (2, 4) or npc.shape != (g.n_paths,):
+            raise ValueError("not a path table: knots [n_paths, max_pieces + 1], coef [n_paths, 2, 4, max_pieces], n_pieces [n_paths]")
+        grids = None
+        if map_yx is not None:
+            grids = np.ascontiguousarray(map_yx, np.float64)
+            grids = grids[None] if grids.ndim == 2 else grids
+            g.n_maps, g.rows, g.cols = grids.shape
+        pid = None if path_id is None else np.ascontiguousarray(path_id, np.int32).reshape(B)
+        mid = None if map_id is None else np.ascontiguousarray(map_id, np.int32).reshape(B)
+        off = None if offset is None else np.ascontiguousarray(np.broadcast_to(np.asarray(offset, np.float64), (B,)))
+        st = None if start is None else np.ascontiguousarray(start, np.float64).reshape(B, START_DOUBLES)
+        dn = None if done is None else np.array(done, np.int32).reshape(B)
+        goal = np.empty((B, 3))
+        self._chk(self.lib.qtos_path_goal(self.h, B, C.byref(g), _dp(knots), _dp(coef), _ip(npc), _dp(rg), _ip(pid), _dp(grids), _ip(mid),
+                                          _dp(clock), _dp(off), _dp(st), _dp(goal), _ip(dn)), "path_goal")
+        return goal, dn, clock
 
     # ---- optional: nominal-plan table for the starting point of cold solves ----
     def set_init_table(self, dx=None, dy=None, nodes=None):

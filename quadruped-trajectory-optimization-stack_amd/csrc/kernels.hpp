@@ -2116,4 +2116,116 @@ __global__ __launch_bounds__(STITCH_TILE) void k_stitch(const SamplePlan *Sd, St
   }
 }
 
+// Goals of receding windows from their global paths (qtos_path_goal*; Global_Planner.update / spine_step, QTOS/planner.py:139-161,
+// 195-230; Combiner.plan_init / spine_step, QTOS/combiner.py:137-212): where the next plan goes.  One lane per window: the
+// window's A* "spine" (two cubic splines in scipy's layout, global_planner.path_table) is read one horizon ahead of the new plan's
+// start, the displacement from the base point is clipped to step_size per axis, and the goal height is the terrain under the
+// goal + z_offset.  The statement of the rule is global_planner.path_goal, and this kernel equals it to the bit: every
+// function below switches contraction off in its own body (the library is built with the compiler's default, which fuses
+// a * b + c), so each operation is one rounded IEEE double operation, in scipy's order of summation, which is not Horner's.
+// No LDS, no scratch: the tables come through pointers and are indexed per lane, the arguments hold scalars only (see
+// k_handover), and no handle state is read or written.
+struct PathGoalArgs {   // QtosPathGoal as the kernel reads it (qtos_planner.hip path_goal_args)
+  double horizon, step_size, tol, z_offset, cell, origin_x, origin_y, t_stop, stop_dist;
+  int base, clamp_x, advance_clock, hold_done;
+  int n_paths, max_pieces, n_maps, rows, cols;
+};
+
+// One spine at time t (global_planner.spine_eval): x the path's n + 1 knots, c its coefficients c[k * mp + i] of (t - x[i])^(3 - k).
+// The bisection counts the knots <= t, which is searchsorted(x[:n + 1], t, 'right'); a NaN counts none and gives a NaN.
+__device__ inline double path_spine(const double *x, const double *c, int n, int mp, double t) {
+#pragma clang fp contract(off)
+  int lo = 0, hi = n + 1;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (x[mid] <= t) lo = mid + 1; else hi = mid;
+  }
+  const int i = lo - 1 < 0 ? 0 : (lo - 1 > n - 1 ? n - 1 : lo - 1);
+  const double s = t - x[i];
+  double res = 0.0, z = 1.0;
+#pragma unroll
+  for (int kp = 0; kp < 4; ++kp) {
+    res = res + c[(size_t)(3 - kp) * mp + i] * z;
+    z = z * s;
+  }
+  return res;
+}
+
+// GlobalPlanner.get_map_height (global_planner.map_height): the index test is made in double, so a huge or non-finite
+// coordinate takes the fall-back cell and reads nothing else.  hm null: every height is 0.
+__device__ inline double path_height(const PathGoalArgs &A, const double *hm, double x, double y) {
+#pragma clang fp contract(off)
+  if (!hm) return 0.0;
+  const double fr = floor((y + A.origin_y) / A.cell), fc = floor((x + A.origin_x) / A.cell);
+  int r = A.rows - 1, c = A.cols / 2;
+  if (fr >= -(double)A.rows && fr < (double)A.rows && fc >= -(double)A.cols && fc < (double)A.cols) {
+    r = (int)fr; c = (int)fc;
+    if (r < 0) r += A.rows;        // (Python's wrap of a negative index)
+    if (c < 0) c += A.cols;
+  }
+  return hm[(size_t)r * A.cols + c];
+}
+
+__device__ inline double path_clip(double d, double step) {   // np.clip(d, -step, step), step >= 0: a NaN stays a NaN
+  return d < -step ? -step : (d > step ? step : d);
+}
+
+__global__ __launch_bounds__(64) void k_path_goal(PathGoalArgs A, const double *knots, const double *coef, const int *n_pieces,
+                                                  const double *robot_goal, const int *path_id, const double *height_yx,
+                                                  const int *map_id, double *clock, const double *offset, const double *start,
+                                                  double *goal_out, int *done, int B) {
+#pragma clang fp contract(off)
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  int p = path_id ? path_id[b] : b;
+  p = p < 0 ? 0 : (p > A.n_paths - 1 ? A.n_paths - 1 : p);       // (an id outside the table reads its nearest path, never beyond it)
+  int n = n_pieces[p];
+  n = n < 1 ? 1 : (n > A.max_pieces ? A.max_pieces : n);
+  const double *x = knots + (size_t)p * (A.max_pieces + 1);
+  const double *cx = coef + (size_t)p * 8 * A.max_pieces, *cy = cx + (size_t)4 * A.max_pieces;
+  const double *hm = nullptr;
+  if (height_yx) {
+    int m = map_id ? map_id[b] : 0;
+    m = m < 0 ? 0 : (m > A.n_maps - 1 ? A.n_maps - 1 : m);
+    hm = height_yx + (size_t)m * A.rows * A.cols;
+  }
+  const double *st = start ? start + (size_t)b * QTOS_START_DOUBLES : nullptr;
+  const double lt = clock[b] + (offset ? offset[b] : 0.0);       // plan time of the new plan's row 0
+  const double tf = lt + A.horizon;
+  double sx = path_spine(x, cx, n, A.max_pieces, tf), sy = path_spine(x, cy, n, A.max_pieces, tf);
+  if (!(fabs(sx) > A.tol)) sx = 0.0;
+  if (!(fabs(sy) > A.tol)) sy = 0.0;
+  const double gz = path_height(A, hm, sx, sy) + A.z_offset;
+  if (A.clamp_x) {                                               // Combiner.spine_step: behind the height, as the reference does
+    const double rgx = robot_goal[(size_t)p * 3];
+    if (sx > rgx) sx = rgx;
+  }
+  double bx, by, bz;
+  if (A.base == 0) {                                             // Global_Planner.update: the spine at the plan's start
+    bx = path_spine(x, cx, n, A.max_pieces, lt);
+    by = path_spine(x, cy, n, A.max_pieces, lt);
+    bz = path_height(A, hm, bx, by) + A.z_offset;
+  } else {                                                       // plan_init, spine_step(com, t): the state the plan starts from
+    bx = st[0]; by = st[1]; bz = st[2];
+  }
+  double gx = bx + path_clip(sx - bx, A.step_size), gy = by + path_clip(sy - by, A.step_size);
+  double gzc = bz + path_clip(gz - bz, A.step_size);
+  int bits = 0;
+  if (x[n] < lt - A.t_stop) bits |= 1;                           // the path's end lies t_stop behind the plan's start
+  if (A.stop_dist > 0) {
+    const double dx = st[0] - gx, dy = st[1] - gy;
+    if (sqrt(dx * dx + dy * dy) < A.stop_dist) bits |= 2;
+  }
+  int d = 0;
+  if (done) {
+    d = done[b] | bits;
+    done[b] = d;
+  }
+  if (A.hold_done && d) { gx = st[0]; gy = st[1]; gzc = st[2]; }  // a finished window stands still
+  goal_out[(size_t)b * 3 + 0] = gx;
+  goal_out[(size_t)b * 3 + 1] = gy;
+  goal_out[(size_t)b * 3 + 2] = gzc;
+  if (A.advance_clock) clock[b] = lt;
+}
+
 }  // namespace qtos

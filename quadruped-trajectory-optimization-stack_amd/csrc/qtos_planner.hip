@@ -1649,6 +1649,86 @@ int qtos_stitch(QtosPlanner *p, int B, const QtosStitch *s, const double *nodes,
   return rc;
 }
 
+// ---- goals of receding windows from their global paths (k_path_goal, kernels.hpp) ------------------------
+// The argument checks of both forms, and QtosPathGoal as k_path_goal reads it.
+static int path_goal_args(const QtosPlanner *p, int B, const QtosPathGoal *g, const void *knots, const void *coef, const void *n_pieces,
+                          const void *robot_goal, const void *path_id, const void *height_yx, const void *clock, const void *start,
+                          const void *goal_out, const void *done, PathGoalArgs *A) {
+  if (!p || B < 1 || !g || !knots || !coef || !n_pieces || !clock || !goal_out) return -1;
+  if (g->n_paths < 1 || g->max_pieces < 1 || (!path_id && g->n_paths < B)) return -1;
+  if (height_yx && (g->n_maps < 1 || g->rows < 1 || g->cols < 1)) return -1;
+  if (!(g->cell > 0) || !(g->step_size >= 0)) return -1;
+  if (g->base != 0 && g->base != 1) return -1;
+  if ((g->clamp_x && !robot_goal) || (g->hold_done && !done)) return -1;
+  if (!start && (g->base == 1 || g->stop_dist > 0 || g->hold_done)) return -1;
+  A->horizon = g->horizon; A->step_size = g->step_size; A->tol = g->tol; A->z_offset = g->z_offset;
+  A->cell = g->cell; A->origin_x = g->origin_x; A->origin_y = g->origin_y;
+  A->t_stop = g->t_stop; A->stop_dist = g->stop_dist;
+  A->base = g->base; A->clamp_x = g->clamp_x != 0; A->advance_clock = g->advance_clock != 0; A->hold_done = g->hold_done != 0;
+  A->n_paths = g->n_paths; A->max_pieces = g->max_pieces;
+  A->n_maps = g->n_maps; A->rows = g->rows; A->cols = g->cols;
+  return 0;
+}
+
+int qtos_path_goal_device(QtosPlanner *p, int B, const QtosPathGoal *g, const double *d_knots, const double *d_coef, const int *d_n_pieces,
+                          const double *d_robot_goal, const int *d_path_id, const double *d_height_yx, const int *d_map_id, double *d_clock,
+                          const double *d_offset, const double *d_start, double *d_goal_out, int *d_done, void *stream_) {
+  PathGoalArgs A;
+  if (path_goal_args(p, B, g, d_knots, d_coef, d_n_pieces, d_robot_goal, d_path_id, d_height_yx, d_clock, d_start, d_goal_out, d_done, &A))
+    return -1;
+  HIPCHK(p, hipSetDevice(p->device));
+  hipLaunchKernelGGL(k_path_goal, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream_, A, d_knots, d_coef, d_n_pieces, d_robot_goal,
+                     d_path_id, d_height_yx, d_map_id, d_clock, d_offset, d_start, d_goal_out, d_done, B);
+  HIPCHK(p, hipGetLastError());
+  return 0;
+}
+
+int qtos_path_goal(QtosPlanner *p, int B, const QtosPathGoal *g, const double *knots, const double *coef, const int *n_pieces,
+                   const double *robot_goal, const int *path_id, const double *height_yx, const int *map_id, double *clock,
+                   const double *offset, const double *start, double *goal_out, int *done) {
+  PathGoalArgs A;
+  if (path_goal_args(p, B, g, knots, coef, n_pieces, robot_goal, path_id, height_yx, clock, start, goal_out, done, &A)) return -1;
+  HIPCHK(p, hipSetDevice(p->device));
+  // buffers of its own, as qtos_stitch: the handle's staging buffers are not touched, so it may run while a call is open
+  const size_t np_ = (size_t)g->n_paths, mp = (size_t)g->max_pieces;
+  struct Buf { void **d; const void *h; size_t bytes; };
+  double *d_knots = nullptr, *d_coef = nullptr, *d_rg = nullptr, *d_h = nullptr, *d_clock = nullptr, *d_off = nullptr, *d_start = nullptr,
+         *d_goal = nullptr;
+  int *d_n = nullptr, *d_pid = nullptr, *d_mid = nullptr, *d_done = nullptr;
+  const Buf in[] = {
+      {(void **)&d_knots, knots, np_ * (mp + 1) * sizeof(double)},
+      {(void **)&d_coef, coef, np_ * 8 * mp * sizeof(double)},
+      {(void **)&d_n, n_pieces, np_ * sizeof(int)},
+      {(void **)&d_rg, robot_goal, np_ * 3 * sizeof(double)},
+      {(void **)&d_pid, path_id, B * sizeof(int)},
+      {(void **)&d_h, height_yx, height_yx ? (size_t)g->n_maps * g->rows * g->cols * sizeof(double) : 0},
+      {(void **)&d_mid, height_yx ? map_id : nullptr, B * sizeof(int)},
+      {(void **)&d_clock, clock, B * sizeof(double)},
+      {(void **)&d_off, offset, B * sizeof(double)},
+      {(void **)&d_start, start, (size_t)B * QTOS_START_DOUBLES * sizeof(double)},
+      {(void **)&d_done, done, B * sizeof(int)},
+  };
+  auto run = [&]() -> int {
+    for (const Buf &b : in) {
+      if (!b.h) continue;                                  // (an optional array that was not given stays a null pointer)
+      HIPCHK(p, hipMalloc(b.d, b.bytes));
+      HIPCHK(p, hipMemcpy(*b.d, b.h, b.bytes, hipMemcpyHostToDevice));
+    }
+    HIPCHK(p, hipMalloc((void **)&d_goal, (size_t)B * 3 * sizeof(double)));
+    const int rc = qtos_path_goal_device(p, B, g, d_knots, d_coef, d_n, d_rg, d_pid, d_h, d_mid, d_clock, d_off, d_start, d_goal, d_done,
+                                         nullptr);
+    if (rc) return rc;
+    HIPCHK(p, hipMemcpy(goal_out, d_goal, (size_t)B * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (g->advance_clock) HIPCHK(p, hipMemcpy(clock, d_clock, B * sizeof(double), hipMemcpyDeviceToHost));
+    if (done) HIPCHK(p, hipMemcpy(done, d_done, B * sizeof(int), hipMemcpyDeviceToHost));
+    return 0;
+  };
+  const int rc = run();
+  for (const Buf &b : in) (void)hipFree(*b.d);
+  (void)hipFree(d_goal);
+  return rc;
+}
+
 int qtos_set_init_table(QtosPlanner *p, int ndx, const double *dx, int ndy, const double *dy, const double *nodes) {
   if (!p) return -1;
   HIPCHK(p, hipSetDevice(p->device));

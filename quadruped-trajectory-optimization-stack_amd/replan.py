@@ -167,10 +167,26 @@ class ShiftedWindows:
                ``stitcher.stitch_segments``); ``self.t0`` is then the windows' clock: the time stamp of row 0 of the newest
                plan.  ``finish()`` appends the rest of the newest plan, ``trajectory_rows(b)`` reads a window's ring.
     stitch     "clean" (every row: old[:r] ++ new) or "reference" (the reference's files, whose first row pd.read_csv eats:
-               old[1:][:r] ++ new[1:], ``Stitcher(mode="reference")``)"""
+               old[1:][:r] ++ new[1:], ``Stitcher(mode="reference")``)
+    path       None (the default): every goal moves by ``goal_step`` per plan.  A dict: the goals come from the windows' global
+               paths, as the reference's come from its global planner (k_path_goal through qtos_path_goal_device, the rule:
+               ``global_planner.path_goal``) -- ``table`` (``global_planner.path_table``), ``step_size``, and optionally
+               ``path_id`` (B; default window b follows path b), ``map_yx`` (n_maps x rows x cols height grids, row = y) with
+               its own ``map_id`` (B; default map 0), ``cell`` (0.1), ``origin`` ((1.0, 1.0)), ``horizon`` (the plans'
+               duration), ``tol`` (1e-5), ``z_offset`` (0.24), ``stop_dist`` (0: no bit 1), ``clamp_x`` (False).  The table and
+               the grids are uploaded once, here.  ``goal_step`` may then be None.  The first plan's goal is the step from the
+               start state at clock 0 (plan_init); every later one follows the hand-over on the same stream, with its start and
+               offset.  ``self.clock`` (B, f64: the plan time of row 0 of the newest plan) and ``self.done`` (B, int32: bit 0
+               the path's end lies 5 s + ``advance`` behind the plan's start, bit 1 the goal is within ``stop_dist``) live on
+               the device; ``self.path_params_init`` / ``self.path_params`` are the QtosPathGoal of the first / later calls.
+    path_base  "spine" (Global_Planner.update: the step is taken from the spine at the plan's start) or "state" (from the state
+               the plan starts from), for every plan but the first
+    path_hold  True: a window whose done bits are set stands still (its goal is its start) instead of following the spline's
+               extrapolation beyond the path's end"""
 
     def __init__(self, planner, start, goal_step, map_id=None, advance=2.5, search=0.4, stream=None, warm="none", x_range=None,
-                 handover=None, contact="force", height_set=(0.0,), trajectory=None, stitch="clean"):
+                 handover=None, contact="force", height_set=(0.0,), trajectory=None, stitch="clean", path=None, path_base="spine",
+                 path_hold=True):
         import torch
         self.torch = torch
         self.P = planner
@@ -180,10 +196,16 @@ class ShiftedWindows:
         self.B = B
         f64 = dict(dtype=torch.float64, device=dev)
         self.start = torch.as_tensor(np.asarray(start), **f64).contiguous()
-        self.goal_step = torch.as_tensor(np.asarray(goal_step), **f64).contiguous()     # (B, 3): per-plan displacement
-        self.goal = self.start[:, 0:3] + self.goal_step
-        self.goal[:, 2] = 0.24
-        self.goal = self.goal.contiguous()
+        self.path = path
+        if path is None:
+            self.goal_step = torch.as_tensor(np.asarray(goal_step), **f64).contiguous()     # (B, 3): per-plan displacement
+            self.goal = self.start[:, 0:3] + self.goal_step
+            self.goal[:, 2] = 0.24
+            self.goal = self.goal.contiguous()
+        else:
+            self.goal_step = None
+            self.goal = torch.zeros((B, 3), **f64)       # (written by k_path_goal in front of every plan, the first included)
+            self._init_path(path, path_base, path_hold, float(advance))
         self.map_id = None if map_id is None else torch.as_tensor(np.asarray(map_id), dtype=torch.int32, device=dev).contiguous()
         self.nodes = torch.empty((B, planner.n), **f64)
         self.prev = torch.empty((B, planner.n), **f64)
@@ -239,6 +261,49 @@ class ShiftedWindows:
     def _call(self, rc, what):
         if rc != 0:
             raise RuntimeError("%s failed: %d %s" % (what, rc, self.P.lib.qtos_last_error(self.P.h)))
+
+    def _init_path(self, path, path_base, path_hold, advance):
+        """Upload the path table and the height grids (once) and fix the parameters of the path-goal calls."""
+        from . import capi
+        torch, dev, B = self.torch, self.dev, self.B
+        if not hasattr(self.P.lib, "qtos_path_goal_device"):
+            raise RuntimeError("this build of the planner library has no path-goal kernel (qtos_path_goal_device)")
+        if path_base not in capi.PATH_BASES:
+            raise ValueError("path_base is 'spine' or 'state'")
+        table = path["table"]
+        f64 = dict(dtype=torch.float64, device=dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        up = lambda a, kw: None if a is None else torch.as_tensor(np.ascontiguousarray(a), **kw).contiguous()
+        self._path_knots, self._path_coef = up(table["knots"], f64), up(table["coef"], f64)
+        self._path_n, self._path_rg = up(table["n_pieces"], i32), up(table.get("robot_goal"), f64)
+        self.path_id = up(path.get("path_id"), i32)
+        grids = path.get("map_yx")
+        if grids is not None:
+            grids = np.asarray(grids, np.float64)
+            grids = grids[None] if grids.ndim == 2 else grids
+        self._path_grids = up(grids, f64)
+        self.path_map_id = up(path.get("map_id"), i32) if grids is not None else None
+        for t, n in ((self.path_id, "path_id"), (self.path_map_id, "map_id")):
+            if t is not None and tuple(t.shape) != (B,):
+                raise ValueError("path['%s'] has one entry per window" % n)
+        kw = dict(horizon=path.get("horizon", self.P.dims.duration), step_size=path["step_size"], tol=path.get("tol", 1e-5),
+                  z_offset=path.get("z_offset", 0.24), cell=path.get("cell", 0.1), origin=path.get("origin", (1.0, 1.0)),
+                  t_stop=5.0 + advance,     # (the reference stops once max_t < runtime - 5.0, and a plan starts `advance` ahead of the runtime)
+                  stop_dist=path.get("stop_dist", 0.0), clamp_x=path.get("clamp_x", False), advance_clock=True,
+                  hold_done=path_hold, table=table, map_yx=grids)
+        self.path_params_init = capi.path_goal_params(base="state", **kw)      # plan_init: from the start state, at clock 0
+        self.path_params = capi.path_goal_params(base=path_base, **kw)
+        self.clock = torch.zeros((B,), **f64)
+        self.done = torch.zeros((B,), **i32)
+
+    def _path_goal(self, params, offset, sp):
+        """Queue k_path_goal: the goals of the plans about to be asked for, from self.start (and the hand-over's offset)."""
+        import ctypes as C
+        ptr = lambda t: None if t is None else t.data_ptr()
+        self._call(self.P.lib.qtos_path_goal_device(self.P.h, self.B, C.byref(params), ptr(self._path_knots), ptr(self._path_coef),
+                                                    ptr(self._path_n), ptr(self._path_rg), ptr(self.path_id), ptr(self._path_grids),
+                                                    ptr(self.path_map_id), ptr(self.clock), ptr(offset), ptr(self.start), ptr(self.goal),
+                                                    ptr(self.done), sp), "qtos_path_goal_device")
 
     def replan(self):
         """One replan of every window: begin() + poll() until the call is queued to its end (results: synchronise the stream)."""
@@ -314,6 +379,8 @@ class ShiftedWindows:
         self.offset.copy_(idx.to(torch.float64) / self.hz)
         if self.traj is not None:
             self.row.copy_(idx)
+        if self.path is not None:
+            return                       # (the goals come from k_path_goal)
         if self.x_range is not None:
             lo, hi = self.x_range
             x = self.start[:, 0]
@@ -329,11 +396,16 @@ class ShiftedWindows:
         if self.have_plan:
             if self.handover == "kernel":
                 # hand-over: k_handover picks every window's row of its newest plan, evaluates it into start and moves the goal
-                self._call(P.lib.qtos_handover_device(P.h, B, C.byref(self._hand), self.nodes.data_ptr(), self.goal_step.data_ptr(),
-                                                      self.start.data_ptr(), self.goal.data_ptr(), self.offset.data_ptr(),
-                                                      self.row.data_ptr(), sp), "qtos_handover_device")
+                # (with a path: without goal_step, the goal is k_path_goal's)
+                self._call(P.lib.qtos_handover_device(P.h, B, C.byref(self._hand), self.nodes.data_ptr(),
+                                                      None if self.path is not None else self.goal_step.data_ptr(),
+                                                      self.start.data_ptr(), None if self.path is not None else self.goal.data_ptr(),
+                                                      self.offset.data_ptr(), self.row.data_ptr(), sp), "qtos_handover_device")
             else:
                 self._handover_rows(sp)
+            if self.path is not None:
+                # where the next plan goes: the window's path one horizon ahead of the hand-over, behind it on the same stream
+                self._path_goal(self.path_params, self.offset, sp)
             if self.traj is not None:
                 # the rows executed of the plan handed over from go to the windows' rings; t0 moves on to the new plan's row 0
                 self._call(P.lib.qtos_stitch_device(P.h, B, C.byref(self._stitch), self.nodes.data_ptr(), self.row.data_ptr(),
@@ -359,6 +431,8 @@ class ShiftedWindows:
                     elif mix == "base+feet":
                         self.warm[:, self._force_off:] = guess[:, self._force_off:]
                 warm_ptr = self.warm.data_ptr()
+        elif self.path is not None:
+            self._path_goal(self.path_params_init, None, sp)
         self._call(P.lib.qtos_plan_submit(P.h, B, self.start.data_ptr(), self.goal.data_ptr(),
                                           None if self.map_id is None else self.map_id.data_ptr(), warm_ptr,
                                           self.nodes.data_ptr(), self.status.data_ptr(), self.iters.data_ptr(),
