@@ -401,6 +401,51 @@ int qtos_path_goal(QtosPlanner *p, int B, const QtosPathGoal *g, const double *k
                    const double *robot_goal, const int *path_id, const double *height_yx, const int *map_id, double *clock,
                    const double *offset, const double *start, double *goal_out, int *done);
 
+/* The global paths of receding windows, planned on the device: what qtos_path_goal* reads.  Replaces PATH_Solver (QTOS/planner.py:
+ * 282-457; PATH_Solver.solve :422-457 when maps or goals change) for B windows at once, one wavefront per window (k_path_plan):
+ * A* over the window's boolean map from its start point to its robot goal, then every second cell of the path a point of two
+ * not-a-knot cubics X(t), Y(t) over T = |start - goal| / step_size * 10 seconds.  The numpy statement of all of it is
+ * global_planner.path_plan (path_cells, spine_fit), which the kernel equals to the bit:
+ *   cells: (floor((y + origin_y) / cell), floor((x + origin_x) / cell)); 4 neighbours in the order (0,1), (0,-1), (1,0), (-1,0);
+ *   blocked where bool_map > height_bound; g + 1 per step, f = g + sqrt(drow^2 + dcol^2); the open list is popped in the order
+ *   of (f, (row, col)); a cell is pushed again where g < gscore or it has no entry in the open list (PATH_Solver.astar,
+ *   statement by statement; a start cell outside the grid is expanded once and never indexed)
+ *   points: sub = path[::2]; x = col * cell - origin_x over sub, then the last cell's col * cell without the shift (sic); y from
+ *   the rows; n = len(sub) pieces over the knots i * (T / n), the last one T
+ *   splines: scipy's not-a-knot system by a fixed elimination (n = 1 the line, n = 2 the parabola, n >= 3 the Thomas recurrence)
+ * status[b]: 0 found; 1 no path (the open list ran empty, or a start / goal cell that is not finite or no int32); 2 the path has
+ * more than max_cells cells (n_cells[b] is its length); 3 the open list would exceed max_open entries, or more than
+ * 4 * rows * cols + 4 pops happened; 4 T is not > 0.  A window whose status is not 0 gets the one-piece constant spine at its
+ * start point over the knots (0, 0), and with set_done bit 2 (value 4) of done[b]: k_path_goal with hold_done then keeps it on
+ * its start. */
+typedef struct QtosPathPlan {
+  int rows, cols;              /* of the boolean maps (rows * cols <= 16384)                                     */
+  double cell, origin_x, origin_y;  /* of the maps (cell > 0; the reference: 0.1, 1.0, 1.0)                      */
+  double height_bound;         /* a cell is blocked where its value is larger (the reference: 0.2)               */
+  double step_size;            /* of T (> 0)                                                                     */
+  int max_cells;               /* longest path kept (1 .. min(2 * max_pieces, 16384))                            */
+  int max_open;                /* longest open list (1 .. 4096)                                                  */
+  int max_pieces;              /* of the path table written (>= 1)                                               */
+  int n_maps;                  /* >= 1                                                                           */
+  int set_done;                /* set bit 2 of done where status != 0 (needs done)                               */
+} QtosPathPlan;
+/* bool_maps n_maps x rows x cols doubles; map_id B (may be NULL: map 0; ids outside are read as the nearest map); start
+ * B x QTOS_START_DOUBLES (only [0], [1] are read: the window's x, y); robot_goal B x 3 (only [0], [1] are read; the same array
+ * is the table's robot_goal, window b following path b).  Written: knots B x (max_pieces + 1), coef B x 2 x 4 x max_pieces and
+ * n_pieces B -- the path table of qtos_path_goal*, n_paths = B, padded as there; cells B x max_cells x 2 (row, col; padding 0;
+ * may be NULL); n_cells B; status B; done B (in / out; may be NULL without set_done).
+ * Device form: all pointers but `g` in device memory, one kernel queued on `stream`; no handle state is read or written, and it
+ * may be queued while a call is open.  Host form: host pointers, synchronous, through device buffers of its own (no -5).
+ * Both: -1 on a null planner; -2 on any other bad argument, with no kernel launched and the reason in qtos_last_error -- a null
+ * `g` or required pointer, B < 1, rows or cols < 1, rows * cols > 16384, max_open outside 1 .. 4096, max_pieces < 1, max_cells
+ * outside 1 .. min(2 * max_pieces, 16384), n_maps < 1, cell or step_size not > 0, a height_bound that is not a number, set_done
+ * without done -- and on a HIP error; -3 out of memory. */
+int qtos_path_plan_device(QtosPlanner *p, int B, const QtosPathPlan *g, const double *d_bool_maps, const int *d_map_id /* may be NULL */,
+                          const double *d_start, const double *d_robot_goal, double *d_knots, double *d_coef, int *d_n_pieces,
+                          int *d_cells /* may be NULL */, int *d_n_cells, int *d_status, int *d_done /* in/out, may be NULL */, void *stream);
+int qtos_path_plan(QtosPlanner *p, int B, const QtosPathPlan *g, const double *bool_maps, const int *map_id, const double *start,
+                   const double *robot_goal, double *knots, double *coef, int *n_pieces, int *cells, int *n_cells, int *status, int *done);
+
 /* The plan as the text file the reference copies out of its container (`docker cp <id>:.../build/traj.csv ./data/traj/towr.csv`,
  * scripts/main.py:90-92; consumers scripts/run.py:129-137, QTOS/combiner.py:263-274): rows is n_rows x 37 (one plan of
  * qtos_sample_csv), every number printed as the solver's C++ stream prints it (default precision 6 = printf "%g"), comma

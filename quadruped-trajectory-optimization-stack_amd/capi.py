@@ -170,6 +170,36 @@ def path_goal_params(horizon=5.0, step_size=1.0, tol=1e-5, z_offset=0.24, cell=0
     return g
 
 
+class QtosPathPlan(C.Structure):
+    """Parameters of a path-plan call (qtos_path_plan*, include/qtos_planner.h)."""
+    _fields_ = [
+        ("rows", C.c_int), ("cols", C.c_int), ("cell", C.c_double), ("origin_x", C.c_double), ("origin_y", C.c_double),
+        ("height_bound", C.c_double), ("step_size", C.c_double), ("max_cells", C.c_int), ("max_open", C.c_int), ("max_pieces", C.c_int),
+        ("n_maps", C.c_int), ("set_done", C.c_int),
+    ]
+
+    def copy(self):
+        return QtosPathPlan.from_buffer_copy(self)
+
+
+def path_plan_params(step_size=1.0, cell=0.1, origin=(1.0, 1.0), height_bound=0.2, max_cells=None, max_open=4096, max_pieces=None,
+                     set_done=False, bool_map=None):
+    """A QtosPathPlan with the reference's constants as defaults.  bool_map (n_maps x rows x cols, or rows x cols) fills the
+    sizes; max_cells defaults to 2 * max_pieces, or without max_pieces to 2 * (rows + cols), twice the longest way across an
+    empty grid; max_pieces defaults to what max_cells needs, (max_cells + 1) // 2."""
+    g = QtosPathPlan()
+    g.step_size, g.cell, g.origin_x, g.origin_y = float(step_size), float(cell), float(origin[0]), float(origin[1])
+    g.height_bound, g.max_open, g.set_done = float(height_bound), int(max_open), int(bool(set_done))
+    if bool_map is not None:
+        shape = np.shape(bool_map)
+        g.n_maps, g.rows, g.cols = (1,) + tuple(shape) if len(shape) == 2 else tuple(shape)
+    if max_cells is None:
+        max_cells = min(2 * (g.rows + g.cols), 16384) if max_pieces is None else 2 * int(max_pieces)
+    g.max_cells = int(max_cells)
+    g.max_pieces = (g.max_cells + 1) // 2 if max_pieces is None else int(max_pieces)
+    return g
+
+
 class SelftestError(RuntimeError):
     """No elimination order passed the KKT self-test (qtos_planner_create_checked returned -6); `attempts`: the QtosSelftest
     records in the order they were tried."""
@@ -194,7 +224,7 @@ EXPORTS = [
     "qtos_write_csv", "qtos_set_report", "qtos_plan_report", "qtos_analyze_counts", "qtos_debug_duals", "qtos_analyze_kernel",
     "qtos_planner_selftest", "qtos_planner_create_checked", "qtos_analyze_candidates", "qtos_selftest_inputs", "qtos_selftest_bits",
     "qtos_selftest_problem", "qtos_handover", "qtos_handover_device", "qtos_stitch", "qtos_stitch_device",
-    "qtos_path_goal", "qtos_path_goal_device",
+    "qtos_path_goal", "qtos_path_goal_device", "qtos_path_plan", "qtos_path_plan_device",
 ]
 
 _lib = None
@@ -303,6 +333,9 @@ def load():
     if hasattr(lib, "qtos_path_goal"):  # (the path-goal kernel of the receding windows; older builds lack it)
         lib.qtos_path_goal.argtypes = [vp, C.c_int, C.POINTER(QtosPathGoal), dp, dp, ip, dp, ip, dp, ip, dp, dp, dp, dp, ip]
         lib.qtos_path_goal_device.argtypes = [vp, C.c_int, C.POINTER(QtosPathGoal)] + [vp] * 13
+    if hasattr(lib, "qtos_path_plan"):  # (the path-plan kernel of the receding windows; older builds lack it)
+        lib.qtos_path_plan.argtypes = [vp, C.c_int, C.POINTER(QtosPathPlan), dp, ip, dp, dp, dp, dp, ip, ip, ip, ip, ip]
+        lib.qtos_path_plan_device.argtypes = [vp, C.c_int, C.POINTER(QtosPathPlan)] + [vp] * 12
     _lib = lib
     return lib
 
@@ -756,6 +789,41 @@ class Planner:
         self._chk(self.lib.qtos_path_goal(self.h, B, C.byref(g), _dp(knots), _dp(coef), _ip(npc), _dp(rg), _ip(pid), _dp(grids), _ip(mid),
                                           _dp(clock), _dp(off), _dp(st), _dp(goal), _ip(dn)), "path_goal")
         return goal, dn, clock
+
+    def has_path_plan(self):
+        return hasattr(self.lib, "qtos_path_plan")
+
+    def path_plan(self, bool_map, start, robot_goal, params, map_id=None, done=None, cells=True):
+        """The windows' global paths, planned on the device (qtos_path_plan, host form; the rule: global_planner.path_plan).
+        bool_map n_maps x rows x cols or rows x cols with map_id [B] (None: map 0); start [B, 24] or [B, 2] (x, y); robot_goal
+        [B, 3]; params: a QtosPathPlan (path_plan_params; the maps' sizes are filled in here); done [B] (None: no done bits);
+        cells False: the paths' cells are not kept.  Returns the dict of global_planner.path_plan: the path table (knots, coef,
+        n_pieces, robot_goal) plus cells (or None), n_cells, status, and done where it was given."""
+        if not self.has_path_plan():
+            raise RuntimeError("this build of the planner library has no path-plan kernel (qtos_path_plan)")
+        g = params.copy()
+        maps = np.ascontiguousarray(bool_map, np.float64)
+        maps = maps[None] if maps.ndim == 2 else maps
+        g.n_maps, g.rows, g.cols = maps.shape
+        rg = np.ascontiguousarray(robot_goal, np.float64)
+        B = rg.shape[0]
+        rg = rg.reshape(B, 3)
+        st = np.asarray(start, np.float64).reshape(B, -1)
+        if st.shape[1] != START_DOUBLES:
+            st = np.concatenate([st[:, 0:2], np.zeros((B, START_DOUBLES - 2))], axis=1)
+        st = np.ascontiguousarray(st)
+        mid = None if map_id is None else np.ascontiguousarray(map_id, np.int32).reshape(B)
+        dn = None if done is None else np.array(done, np.int32).reshape(B)
+        mp, mc = max(g.max_pieces, 1), max(g.max_cells, 1)     # (sizes of the arrays only: the library checks the values)
+        knots, coef, npc = np.zeros((B, mp + 1)), np.zeros((B, 2, 4, mp)), np.zeros(B, np.int32)
+        cl = np.zeros((B, mc, 2), np.int32) if cells else None
+        ncl, status = np.zeros(B, np.int32), np.zeros(B, np.int32)
+        self._chk(self.lib.qtos_path_plan(self.h, B, C.byref(g), _dp(maps), _ip(mid), _dp(st), _dp(rg), _dp(knots), _dp(coef), _ip(npc),
+                                          _ip(cl), _ip(ncl), _ip(status), _ip(dn)), "path_plan")
+        out = dict(knots=knots, coef=coef, n_pieces=npc, robot_goal=rg.copy(), cells=cl, n_cells=ncl, status=status)
+        if dn is not None:
+            out["done"] = dn
+        return out
 
     # ---- optional: nominal-plan table for the starting point of cold solves ----
     def set_init_table(self, dx=None, dy=None, nodes=None):

@@ -2228,4 +2228,258 @@ __global__ __launch_bounds__(64) void k_path_goal(PathGoalArgs A, const double *
   if (A.advance_clock) clock[b] = lt;
 }
 
+// The global paths of receding windows (qtos_path_plan*; PATH_Solver, QTOS/planner.py:282-457): what k_path_goal reads, made on
+// the device.  One wavefront per window: A* over the window's boolean map, every second cell of the path a point of two
+// not-a-knot cubics.  The statement of the rule is global_planner.path_plan (path_cells, spine_fit), and this kernel equals it to
+// the bit: the cells because every pop is an exact lexicographic minimum of (f, cell), the numbers because every function
+// below switches contraction off and performs the rule's operations one by one.
+// LDS, laid out for the limits the host checks (rows * cols <= PP_GRID, max_open <= PP_OPEN, max_cells <= PP_GRID), PP_LDS_BYTES
+// (139264) in all:
+//   cw   PP_GRID x u32   per cell: bits 0-16 g (an integer: every step costs 1.0; at most the number of pops, 4 * PP_GRID + 4),
+//                        17-18 the direction it was reached by, 19 closed, 20 blocked
+//   live PP_GRID x u16   per cell: its entries in the open list (<= max_open); after the search the path's cells
+//   of   PP_OPEN x f64   the open list's f, unsorted          oc   PP_OPEN x u16   and cells (row * cols + col)
+// The search is uniform over the wave: every lane follows it, the lanes share the pop (a strided scan and six butterfly
+// steps) and lane 0 stores.  No scratch, plain vector stores only, no handle state.
+constexpr int PP_GRID = 16384, PP_OPEN = 4096;
+constexpr int PP_LDS_BYTES = PP_GRID * 4 + PP_GRID * 2 + PP_OPEN * 8 + PP_OPEN * 2;
+constexpr unsigned PP_G = 0x1ffffu, PP_CLOSED = 1u << 19, PP_BLOCKED = 1u << 20;
+struct PathPlanArgs {   // QtosPathPlan as the kernel reads it (qtos_planner.hip path_plan_args)
+  double cell, origin_x, origin_y, height_bound, step_size;
+  int rows, cols, max_cells, max_open, max_pieces, n_maps, set_done;
+};
+
+// floor((v + o) / cell) as an int32 cell index; false where it is not finite or does not fit
+__device__ inline bool pp_cell_of(double v, double o, double cell, int *out) {
+#pragma clang fp contract(off)
+  const double f = floor((v + o) / cell);
+  if (!(f >= -2147483648.0 && f <= 2147483647.0)) return false;
+  *out = (int)f;
+  return true;
+}
+
+// (f, cell, slot) < (f2, cell2, slot2): f as the bits of a double >= 0, which order as the doubles do; the slot only makes the
+// order total, so that every lane of the butterfly ends on the same entry
+__device__ inline void pp_take_less(unsigned long long &f, int &c, int &k, unsigned long long f2, int c2, int k2) {
+  if (f2 < f || (f2 == f && (c2 < c || (c2 == c && k2 < k)))) { f = f2; c = c2; k = k2; }
+}
+
+// The path's point i of n + 1 on one axis (0: x from the columns, 1: y from the rows): cell * cell_size - origin over every
+// second cell, the last cell WITHOUT the shift (sic, QTOS/planner.py:410,412).  The start cell is not in the LDS list.
+__device__ inline double pp_point(const unsigned short *path, int n_cells, int n, int cols, int sr, int sc, int axis, double cell,
+                                  double origin, int i) {
+#pragma clang fp contract(off)
+  const int j = i < n ? 2 * i : n_cells - 1;
+  int r = sr, c = sc;
+  if (j > 0) { r = path[j] / cols; c = path[j] % cols; }
+  const double v = (double)(axis ? r : c) * cell;
+  return i < n ? v - origin : v;
+}
+
+__device__ inline double pp_knot(double T, int n, int i) {   // numpy's linspace(0, T, n + 1)
+#pragma clang fp contract(off)
+  return i >= n ? T : (double)i * (T / (double)n);
+}
+
+// global_planner.spine_fit for one axis, by one lane: c = the window's 4 x mp coefficient rows, which are also the work space
+// (c' in row 0, g' and then s from row 2 on: s[i] is already c2[i], and the last pass runs downwards so that c3 never
+// overwrites the s[n] that spills into row 3 where n = mp).
+__device__ inline void pp_spine_fit(double *c, int mp, const unsigned short *path, int n_cells, int n, int cols, int sr, int sc, int axis,
+                                    double cell, double origin, double T) {
+#pragma clang fp contract(off)
+  auto Y = [&](int i) { return pp_point(path, n_cells, n, cols, sr, sc, axis, cell, origin, i); };
+  auto H = [&](int i) { return pp_knot(T, n, i + 1) - pp_knot(T, n, i); };
+  auto D = [&](int i) { return (Y(i + 1) - Y(i)) / H(i); };
+  double *s = c + (size_t)2 * mp;
+  if (n == 1) {
+    const double d0 = D(0);
+    s[0] = d0; s[1] = d0;
+  } else if (n == 2) {
+    const double h0 = H(0), h1 = H(1), d0 = D(0), d1 = D(1);
+    const double b0 = 2.0 * d0, b1 = 3.0 * (h0 * d1 + h1 * d0), b2 = 2.0 * d1;
+    const double s1 = ((b1 - h1 * b0) - h0 * b2) / ((2.0 * (h0 + h1) - h1) - h0);
+    s[0] = b0 - s1; s[1] = s1; s[2] = b2 - s1;
+  } else {
+    double hp = H(0), dp = D(0), hi = H(1), di = D(1);            // h, d of rows i - 1 and i
+    double dd = pp_knot(T, n, 2) - pp_knot(T, n, 0);
+    double b = ((hp + 2.0 * dd) * hi * dp + hp * hp * di) / dd;
+    double cp = dd / hi, gp = b / hi;
+    c[0] = cp; s[0] = gp;
+    for (int i = 1; i < n; ++i) {
+      if (i > 1) { hp = hi; dp = di; hi = H(i); di = D(i); }
+      b = 3.0 * (hi * dp + hp * di);
+      const double den = 2.0 * (hp + hi) - hi * cp;
+      cp = hp / den;
+      gp = (b - hi * gp) / den;
+      c[i] = cp; s[i] = gp;
+    }
+    // (hp, dp, hi, di are now those of rows n - 2 and n - 1)
+    dd = pp_knot(T, n, n) - pp_knot(T, n, n - 2);
+    b = (hi * hi * dp + (2.0 * dd + hi) * hp * di) / dd;
+    const double den = hp - dd * cp;
+    double sn = (b - dd * gp) / den;
+    s[n] = sn;
+    for (int i = n - 1; i >= 0; --i) {
+      sn = s[i] - c[i] * sn;
+      s[i] = sn;
+    }
+  }
+  for (int i = n - 1; i >= 0; --i) {
+    const double h = H(i), d = D(i), si = s[i], t = ((si + s[i + 1]) - 2.0 * d) / h;
+    c[i] = t / h;
+    c[(size_t)mp + i] = (d - si) / h - t;
+    c[(size_t)3 * mp + i] = Y(i);                                  // (c2[i] = s[i] stands where it is)
+  }
+}
+
+__global__ __launch_bounds__(64) void k_path_plan(PathPlanArgs A, const double *bool_maps, const int *map_id, const double *start,
+                                                  const double *robot_goal, double *knots, double *coef, int *n_pieces, int *cells,
+                                                  int *n_cells_out, int *status_out, int *done) {
+#pragma clang fp contract(off)
+  __shared__ unsigned cw[PP_GRID];
+  __shared__ unsigned short live[PP_GRID];
+  __shared__ double of[PP_OPEN];
+  __shared__ unsigned short oc[PP_OPEN];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int rows = A.rows, cols = A.cols, N = rows * cols, mp = A.max_pieces;
+  const double x0 = start[(size_t)b * QTOS_START_DOUBLES], y0 = start[(size_t)b * QTOS_START_DOUBLES + 1];
+  const double gx = robot_goal[(size_t)b * 3], gy = robot_goal[(size_t)b * 3 + 1];
+  int m = map_id ? map_id[b] : 0;
+  m = m < 0 ? 0 : (m > A.n_maps - 1 ? A.n_maps - 1 : m);           // (an id outside reads its nearest map, never beyond them)
+  const double *bm = bool_maps + (size_t)m * N;
+  for (int i = lane; i < N; i += 64) {
+    cw[i] = bm[i] > A.height_bound ? PP_BLOCKED : 0u;
+    live[i] = 0;
+  }
+  __syncthreads();
+
+  int sr = 0, sc = 0, gr = 0, gc = 0;
+  int status = 0, n_cells = 0;
+  if (!pp_cell_of(y0, A.origin_y, A.cell, &sr) || !pp_cell_of(x0, A.origin_x, A.cell, &sc) || !pp_cell_of(gy, A.origin_y, A.cell, &gr) ||
+      !pp_cell_of(gx, A.origin_x, A.cell, &gc))
+    status = 1;
+  if (status == 0) {
+    // ---- PathSolver.astar ----
+    int n_open = 0, pops = 0;
+    long long r = sr, c = sc;                                      // (the start may lie anywhere in the int32 range: its neighbours in 64 bits)
+    bool found = false;
+    while (true) {
+      if (pops > 0) {                                              // (the first pop is the start: the list's only entry)
+        if (n_open == 0) { status = 1; break; }
+        unsigned long long bf = ~0ull;
+        int bc = 0x7fffffff, bk = 0x7fffffff;
+        for (int k = lane; k < n_open; k += 64) pp_take_less(bf, bc, bk, (unsigned long long)__double_as_longlong(of[k]), (int)oc[k], k);
+        for (int off = 32; off; off >>= 1) {
+          const unsigned long long f2 = __shfl_xor(bf, off);
+          const int c2 = __shfl_xor(bc, off), k2 = __shfl_xor(bk, off);
+          pp_take_less(bf, bc, bk, f2, c2, k2);
+        }
+        const int k = __builtin_amdgcn_readfirstlane(bk), ci = __builtin_amdgcn_readfirstlane(bc);
+        --n_open;
+        if (lane == 0) {                                           // swap with the last
+          of[k] = of[n_open];
+          oc[k] = oc[n_open];
+          live[ci] = live[ci] - 1;
+        }
+        __syncthreads();
+        r = ci / cols; c = ci % cols;
+      }
+      if (++pops > 4 * N + 4) { status = 3; break; }
+      if (r == gr && c == gc) { found = true; break; }
+      int gcur = 0;
+      if (r >= 0 && r < rows && c >= 0 && c < cols) {
+        const int ci = (int)r * cols + (int)c;
+        gcur = (int)(cw[ci] & PP_G);
+        if (lane == 0) cw[ci] = cw[ci] | PP_CLOSED;
+      }
+      for (int d = 0; d < 4; ++d) {                                // (0, 1), (0, -1), (1, 0), (-1, 0)
+        const long long nr = r + (d == 2 ? 1 : (d == 3 ? -1 : 0)), nc = c + (d == 0 ? 1 : (d == 1 ? -1 : 0));
+        if (nr < 0 || nr >= rows || nc < 0 || nc >= cols) continue;
+        const int ni = (int)nr * cols + (int)nc;
+        const unsigned w = cw[ni];
+        if (w & PP_BLOCKED) continue;
+        const int gn = gcur + 1, gnb = (int)(w & PP_G);
+        if ((w & PP_CLOSED) && gn >= gnb) continue;
+        if (gn < gnb || live[ni] == 0) {
+          if (n_open >= A.max_open) { status = 3; break; }
+          const double dr = (double)((long long)gr - nr), dc = (double)((long long)gc - nc);
+          const double f = (double)gn + sqrt(dr * dr + dc * dc);
+          if (lane == 0) {
+            cw[ni] = (w & PP_CLOSED) | ((unsigned)d << 17) | (unsigned)gn;
+            of[n_open] = f;
+            oc[n_open] = (unsigned short)ni;
+            live[ni] = live[ni] + 1;
+          }
+          ++n_open;
+        }
+      }
+      __syncthreads();
+      if (status) break;
+    }
+    if (found) {
+      // ``while current in came_from``: inside the grid and reached by a step (g > 0); the start never is
+      int len = 0;
+      long long wr = r, wc = c;
+      while (wr >= 0 && wr < rows && wc >= 0 && wc < cols && len <= N) {
+        const unsigned w = cw[(int)wr * cols + (int)wc];
+        if ((w & PP_G) == 0) break;
+        const int d = (int)((w >> 17) & 3u);
+        wr -= (d == 2 ? 1 : (d == 3 ? -1 : 0));
+        wc -= (d == 0 ? 1 : (d == 1 ? -1 : 0));
+        ++len;
+      }
+      n_cells = len + 1;
+      if (n_cells > A.max_cells) status = 2;
+      else if (lane == 0) {                                        // the path's cells behind the start, in `live`
+        wr = r; wc = c;
+        for (int j = len; j >= 1; --j) {
+          const int ci = (int)wr * cols + (int)wc;
+          live[j] = (unsigned short)ci;
+          const int d = (int)((cw[ci] >> 17) & 3u);
+          wr -= (d == 2 ? 1 : (d == 3 ? -1 : 0));
+          wc -= (d == 0 ? 1 : (d == 1 ? -1 : 0));
+        }
+      }
+    }
+  }
+  __syncthreads();
+  if (status != 0 && status != 2) n_cells = 0;
+
+  const double dx = x0 - gx, dy = y0 - gy;
+  const double T = sqrt(dx * dx + dy * dy) / A.step_size * 10.0;
+  if (status == 0 && !(T > 0)) status = 4;
+  const int n = status == 0 ? (n_cells + 1) / 2 : 1;               // sub = path[::2]
+  double *kn = knots + (size_t)b * (mp + 1), *cf = coef + (size_t)b * 8 * mp;
+  if (cells) {
+    int *cl = cells + (size_t)b * A.max_cells * 2;
+    for (int j = lane; j < A.max_cells; j += 64) {
+      int pr = 0, pc = 0;
+      if (status == 0 || status == 4) {
+        if (j == 0) { pr = sr; pc = sc; }
+        else if (j < n_cells) { pr = live[j] / cols; pc = live[j] % cols; }
+      }
+      cl[2 * j] = pr;
+      cl[2 * j + 1] = pc;
+    }
+  }
+  for (int i = lane; i <= mp; i += 64) kn[i] = status == 0 ? pp_knot(T, n, i) : 0.0;
+  if (status == 0) {
+    if (lane < 2)
+      pp_spine_fit(cf + (size_t)lane * 4 * mp, mp, live, n_cells, n, cols, sr, sc, lane, A.cell, lane ? A.origin_y : A.origin_x, T);
+  } else if (lane < 2) {
+    cf[(size_t)lane * 4 * mp + (size_t)3 * mp] = lane ? y0 : x0;   // the constant spine at the start point
+  }
+  __syncthreads();                                                 // (the fit's work space lies in the padding where n < mp)
+  for (int i = lane; i < 8 * mp; i += 64) {
+    const int col = i % mp, row = (i / mp) & 3;
+    if (col >= n || (status != 0 && row != 3)) cf[i] = 0.0;
+  }
+  if (lane == 0) {
+    n_pieces[b] = n;
+    n_cells_out[b] = n_cells;
+    status_out[b] = status;
+    if (done && A.set_done && status != 0) done[b] = done[b] | 4;
+  }
+}
+
 }  // namespace qtos

@@ -1729,6 +1729,87 @@ int qtos_path_goal(QtosPlanner *p, int B, const QtosPathGoal *g, const double *k
   return rc;
 }
 
+// ---- the global paths of receding windows (k_path_plan, kernels.hpp) --------------------------------------
+// The argument checks of both forms, and QtosPathPlan as k_path_plan reads it.  The kernel's LDS is laid out for these limits.
+static int path_plan_args(QtosPlanner *p, int B, const QtosPathPlan *g, const void *bool_maps, const void *start, const void *robot_goal,
+                          const void *knots, const void *coef, const void *n_pieces, const void *n_cells, const void *status,
+                          const void *done, PathPlanArgs *A) {
+  if (!p) return -1;
+  const char *why = nullptr;
+  if (!g || !bool_maps || !start || !robot_goal || !knots || !coef || !n_pieces || !n_cells || !status) why = "a required pointer is null";
+  else if (B < 1) why = "B < 1";
+  else if (g->rows < 1 || g->cols < 1 || (long long)g->rows * g->cols > PP_GRID) why = "rows, cols >= 1 and rows * cols <= 16384";
+  else if (g->max_open < 1 || g->max_open > PP_OPEN) why = "max_open is 1 .. 4096";
+  else if (g->max_pieces < 1) why = "max_pieces >= 1";
+  else if (g->max_cells < 1 || g->max_cells > PP_GRID || (long long)g->max_cells > 2LL * g->max_pieces)
+    why = "max_cells is 1 .. min(2 * max_pieces, 16384)";
+  else if (g->n_maps < 1) why = "n_maps >= 1";
+  else if (!(g->cell > 0) || !(g->step_size > 0)) why = "cell and step_size are > 0";
+  else if (g->height_bound != g->height_bound) why = "height_bound is not a number";
+  else if (g->set_done && !done) why = "set_done needs done";
+  if (why) {
+    p->err = std::string("qtos_path_plan: ") + why;
+    return -2;
+  }
+  A->cell = g->cell; A->origin_x = g->origin_x; A->origin_y = g->origin_y; A->height_bound = g->height_bound; A->step_size = g->step_size;
+  A->rows = g->rows; A->cols = g->cols; A->max_cells = g->max_cells; A->max_open = g->max_open; A->max_pieces = g->max_pieces;
+  A->n_maps = g->n_maps; A->set_done = g->set_done != 0;
+  return 0;
+}
+
+int qtos_path_plan_device(QtosPlanner *p, int B, const QtosPathPlan *g, const double *d_bool_maps, const int *d_map_id, const double *d_start,
+                          const double *d_robot_goal, double *d_knots, double *d_coef, int *d_n_pieces, int *d_cells, int *d_n_cells,
+                          int *d_status, int *d_done, void *stream_) {
+  PathPlanArgs A;
+  if (const int rc = path_plan_args(p, B, g, d_bool_maps, d_start, d_robot_goal, d_knots, d_coef, d_n_pieces, d_n_cells, d_status, d_done, &A))
+    return rc;
+  HIPCHK(p, hipSetDevice(p->device));
+  hipLaunchKernelGGL(k_path_plan, dim3(B), dim3(64), 0, (hipStream_t)stream_, A, d_bool_maps, d_map_id, d_start, d_robot_goal, d_knots, d_coef,
+                     d_n_pieces, d_cells, d_n_cells, d_status, d_done);
+  HIPCHK(p, hipGetLastError());
+  return 0;
+}
+
+int qtos_path_plan(QtosPlanner *p, int B, const QtosPathPlan *g, const double *bool_maps, const int *map_id, const double *start,
+                   const double *robot_goal, double *knots, double *coef, int *n_pieces, int *cells, int *n_cells, int *status, int *done) {
+  PathPlanArgs A;
+  if (const int rc = path_plan_args(p, B, g, bool_maps, start, robot_goal, knots, coef, n_pieces, n_cells, status, done, &A)) return rc;
+  HIPCHK(p, hipSetDevice(p->device));
+  // buffers of its own, as qtos_path_goal: the handle's staging buffers are not touched, so it may run while a call is open
+  const size_t mp = (size_t)g->max_pieces, nb = (size_t)B;
+  struct Buf { void **d; const void *in; void *out; size_t bytes; };
+  double *d_maps = nullptr, *d_start = nullptr, *d_rg = nullptr, *d_knots = nullptr, *d_coef = nullptr;
+  int *d_mid = nullptr, *d_n = nullptr, *d_cells = nullptr, *d_nc = nullptr, *d_st = nullptr, *d_done = nullptr;
+  const Buf bufs[] = {
+      {(void **)&d_maps, bool_maps, nullptr, (size_t)g->n_maps * g->rows * g->cols * sizeof(double)},
+      {(void **)&d_mid, map_id, nullptr, map_id ? nb * sizeof(int) : 0},
+      {(void **)&d_start, start, nullptr, nb * QTOS_START_DOUBLES * sizeof(double)},
+      {(void **)&d_rg, robot_goal, nullptr, nb * 3 * sizeof(double)},
+      {(void **)&d_knots, nullptr, knots, nb * (mp + 1) * sizeof(double)},
+      {(void **)&d_coef, nullptr, coef, nb * 8 * mp * sizeof(double)},
+      {(void **)&d_n, nullptr, n_pieces, nb * sizeof(int)},
+      {(void **)&d_cells, nullptr, cells, cells ? nb * g->max_cells * 2 * sizeof(int) : 0},
+      {(void **)&d_nc, nullptr, n_cells, nb * sizeof(int)},
+      {(void **)&d_st, nullptr, status, nb * sizeof(int)},
+      {(void **)&d_done, done, done, done ? nb * sizeof(int) : 0},
+  };
+  auto run = [&]() -> int {
+    for (const Buf &b : bufs) {
+      if (!b.bytes) continue;                              // (an optional array that was not given stays a null pointer)
+      HIPCHK(p, hipMalloc(b.d, b.bytes));
+      if (b.in) HIPCHK(p, hipMemcpy(*b.d, b.in, b.bytes, hipMemcpyHostToDevice));
+    }
+    const int rc = qtos_path_plan_device(p, B, g, d_maps, d_mid, d_start, d_rg, d_knots, d_coef, d_n, d_cells, d_nc, d_st, d_done, nullptr);
+    if (rc) return rc;
+    for (const Buf &b : bufs)
+      if (b.bytes && b.out) HIPCHK(p, hipMemcpy(b.out, *b.d, b.bytes, hipMemcpyDeviceToHost));
+    return 0;
+  };
+  const int rc = run();
+  for (const Buf &b : bufs) (void)hipFree(*b.d);
+  return rc;
+}
+
 int qtos_set_init_table(QtosPlanner *p, int ndx, const double *dx, int ndy, const double *dy, const double *nodes) {
   if (!p) return -1;
   HIPCHK(p, hipSetDevice(p->device));

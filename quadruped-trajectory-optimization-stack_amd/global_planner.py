@@ -283,3 +283,205 @@ def path_goal(table, path_id, map_yx, map_id, clock, offset, start, params, done
     if hold:
         goal = np.where((done_out != 0)[:, None], st[:, 0:3], goal)
     return goal, done_out.astype(np.int32), (lt if g("advance_clock") else clock.copy())
+
+
+# ---- the global paths of B receding windows: the rule of k_path_plan (qtos_path_plan*) in numpy ---------------------------
+# What PATH_Solver does for one robot -- A* over the boolean map, every second cell a point of two not-a-knot cubics -- on plain
+# arrays, in a fixed order of IEEE double operations: the kernel equals these lines to the bit.  ``path_cells`` is
+# ``PathSolver.astar`` cell for cell, ``spine_fit`` is scipy's ``CubicSpline(t, y).c`` up to the rounding of another
+# elimination order, ``path_plan`` puts them together into the table ``path_goal`` reads.
+
+PATH_NEIGHBOURS = ((0, 1), (0, -1), (1, 0), (-1, 0))      # (d row, d col), the order PathSolver.astar visits them in
+PATH_STATUS = {0: "found", 1: "no path", 2: "more than max_cells cells", 3: "open list or pop cap", 4: "T is not > 0"}
+PATH_MAX_GRID, PATH_MAX_OPEN = 16384, 4096                # what the kernel's LDS is laid out for
+PATH_DONE_BIT = 4                                         # bit 2 of a window's done bits: it has no path
+
+
+def _cell_of(v, o, cell):
+    """floor((v + o) / cell) in double, or None where that is not finite or does not fit an int32."""
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        f = np.floor((np.float64(v) + np.float64(o)) / np.float64(cell))
+    return int(f) if np.isfinite(f) and -2147483648.0 <= f <= 2147483647.0 else None
+
+
+def path_cells(bool_map, start_xy, goal_xy, cell=0.1, ox=1.0, oy=1.0, height_bound=0.2, max_cells=None, max_open=PATH_MAX_OPEN):
+    """``PathSolver.astar`` on arrays.  Returns (cells [max_cells, 2] int32 (row, col), padding 0; n_cells; status).
+    The start and goal cells are (floor((y + oy) / cell), floor((x + ox) / cell)) in double.  Per cell of the grid: g (an
+    integer: every step costs exactly 1.0; 0 where ``gscore.get(nb, 0)`` finds nothing), the direction it was reached by, a
+    closed bit and the number of its entries in the open list, which is an unsorted array of (f, row * cols + col) popped by an
+    exact lexicographic minimum (heapq's order: equal tuples are indistinguishable, and only cells inside the grid are ever
+    pushed).  The start cell is the list's only first entry: it is expanded without being indexed, so it may lie outside the
+    grid.  f = g + sqrt(dr * dr + dc * dc) with dr, dc exact and every other operation one rounded double operation.
+    status 0 found; 1 no path (the open list ran empty, or a start / goal cell that is not finite or no int32); 2 the path has
+    more than max_cells cells (n_cells is then its length, cells stay 0); 3 a push would make the open list longer than
+    max_open, or more than 4 * rows * cols + 4 pops happened."""
+    m = np.asarray(bool_map)
+    rows, cols = m.shape
+    max_cells = rows * cols + 1 if max_cells is None else int(max_cells)
+    cells = np.zeros((max_cells, 2), np.int32)
+    sr, sc = _cell_of(start_xy[1], oy, cell), _cell_of(start_xy[0], ox, cell)
+    gr, gc = _cell_of(goal_xy[1], oy, cell), _cell_of(goal_xy[0], ox, cell)
+    if None in (sr, sc, gr, gc):
+        return cells, 0, 1
+    blocked = m > height_bound
+    g = np.zeros((rows, cols), np.int64)
+    came = np.zeros((rows, cols), np.int64)
+    closed = np.zeros((rows, cols), bool)
+    live = np.zeros((rows, cols), np.int64)
+    of, oc, n_open = np.empty(max_open), np.empty(max_open, np.int64), 0
+    inside = lambda r, c: 0 <= r < rows and 0 <= c < cols
+    cur, pops = (sr, sc), 0
+    while True:
+        if pops > 0:                                       # (the first pop is the start: the list's only entry)
+            if n_open == 0:
+                return cells, 0, 1
+            fmin = of[:n_open].min()
+            cand = np.flatnonzero(of[:n_open] == fmin)
+            k = cand[np.argmin(oc[cand])]
+            cur = (int(oc[k]) // cols, int(oc[k]) % cols)
+            n_open -= 1
+            of[k], oc[k] = of[n_open], oc[n_open]          # swap with the last
+            live[cur] -= 1
+        pops += 1
+        if pops > 4 * rows * cols + 4:
+            return cells, 0, 3
+        if cur == (gr, gc):
+            break
+        gcur = 0
+        if inside(*cur):
+            closed[cur] = True
+            gcur = int(g[cur])
+        for d, (di, dj) in enumerate(PATH_NEIGHBOURS):
+            nb = (cur[0] + di, cur[1] + dj)
+            if not inside(*nb) or blocked[nb]:
+                continue
+            gn = gcur + 1
+            if closed[nb] and gn >= g[nb]:
+                continue
+            if gn < g[nb] or live[nb] == 0:
+                if n_open >= max_open:
+                    return cells, 0, 3
+                came[nb], g[nb] = d, gn
+                dr, dc = np.float64(gr - nb[0]), np.float64(gc - nb[1])
+                of[n_open], oc[n_open] = np.float64(gn) + np.sqrt(dr * dr + dc * dc), nb[0] * cols + nb[1]
+                n_open += 1
+                live[nb] += 1
+    back = []                                              # ``while current in came_from``: inside the grid and reached by a step
+    while inside(*cur) and g[cur] > 0:
+        back.append(cur)
+        di, dj = PATH_NEIGHBOURS[came[cur]]
+        cur = (cur[0] - di, cur[1] - dj)
+    n_cells = len(back) + 1
+    if n_cells > max_cells:
+        return cells, n_cells, 2
+    cells[0] = (sr, sc)
+    if back:
+        cells[1:n_cells] = back[::-1]
+    return cells, n_cells, 0
+
+
+def spine_fit(t, y):
+    """The not-a-knot cubic through the n + 1 points (t[i], y[i]) as c [4, n] in scipy's ``CubicSpline.c`` layout, by a fixed
+    sequence of double operations.  h[i] = t[i + 1] - t[i], d[i] = (y[i + 1] - y[i]) / h[i]; the knot slopes s are
+      n = 1: s = (d[0], d[0]): the line
+      n = 2: scipy's 3 x 3 system [1 1 0; h1 2(h0 + h1) h0; 0 1 1] s = (2 d0, 3 (h0 d1 + h1 d0), 2 d1) with s0 and s2 eliminated:
+             s1 = ((b1 - h1 b0) - h0 b2) / ((2 (h0 + h1) - h1) - h0), s0 = b0 - s1, s2 = b2 - s1: the parabola
+      n >= 3: scipy's tridiagonal system (rows h[i], 2 (h[i - 1] + h[i]), h[i - 1]; the two not-a-knot end rows) by the Thomas
+             recurrence without pivoting: c'[0] = u0 / d0, g'[0] = b0 / d0, den = d[i] - l[i] c'[i - 1], c'[i] = u[i] / den,
+             g'[i] = (b[i] - l[i] g'[i - 1]) / den, then s[n] = g'[n], s[i] = g'[i] - c'[i] s[i + 1]
+    and then scipy's last lines: t = (s[i] + s[i + 1] - 2 d[i]) / h[i], c0 = t / h[i], c1 = (d[i] - s[i]) / h[i] - t, c2 = s[i],
+    c3 = y[i]."""
+    t, y = np.asarray(t, np.float64), np.asarray(y, np.float64)
+    n = len(t) - 1
+    if n < 1 or len(y) != n + 1:
+        raise ValueError("spine_fit needs two points at least, and as many values as knots")
+    two, three = np.float64(2.0), np.float64(3.0)
+    with np.errstate(all="ignore"):
+        h = [t[i + 1] - t[i] for i in range(n)]
+        d = [(y[i + 1] - y[i]) / h[i] for i in range(n)]
+        if n == 1:
+            s = [d[0], d[0]]
+        elif n == 2:
+            b0, b1, b2 = two * d[0], three * (h[0] * d[1] + h[1] * d[0]), two * d[1]
+            s1 = ((b1 - h[1] * b0) - h[0] * b2) / ((two * (h[0] + h[1]) - h[1]) - h[0])
+            s = [b0 - s1, s1, b2 - s1]
+        else:
+            cp, gp = [None] * n, [None] * (n + 1)
+            dd = t[2] - t[0]
+            b = ((h[0] + two * dd) * h[1] * d[0] + h[0] * h[0] * d[1]) / dd
+            cp[0], gp[0] = dd / h[1], b / h[1]
+            for i in range(1, n):
+                b = three * (h[i] * d[i - 1] + h[i - 1] * d[i])
+                den = two * (h[i - 1] + h[i]) - h[i] * cp[i - 1]
+                cp[i], gp[i] = h[i - 1] / den, (b - h[i] * gp[i - 1]) / den
+            dd = t[n] - t[n - 2]
+            b = (h[n - 1] * h[n - 1] * d[n - 2] + (two * dd + h[n - 1]) * h[n - 2] * d[n - 1]) / dd
+            den = h[n - 2] - dd * cp[n - 1]
+            gp[n] = (b - dd * gp[n - 1]) / den
+            s = gp
+            for i in range(n - 1, -1, -1):
+                s[i] = gp[i] - cp[i] * s[i + 1]
+        c = np.zeros((4, n))
+        for i in range(n):
+            tt = ((s[i] + s[i + 1]) - two * d[i]) / h[i]
+            c[0, i], c[1, i], c[2, i], c[3, i] = tt / h[i], (d[i] - s[i]) / h[i] - tt, s[i], y[i]
+    return c
+
+
+PATH_PLAN_FIELDS = ("rows", "cols", "cell", "origin_x", "origin_y", "height_bound", "step_size", "max_cells", "max_open", "max_pieces",
+                    "n_maps", "set_done")
+
+
+def path_plan(maps, map_id, start, goal, params, done=None):
+    """The global paths of B windows as the table ``path_goal`` reads: the rule of k_path_plan.  maps [n_maps, rows, cols] (or
+    [rows, cols]) boolean maps (blocked: > height_bound) with map_id [B] (None: map 0; ids outside are read as the nearest
+    map); start [B, >= 2] the windows' start points (x, y); goal [B, 3] the robots' goals; params: a ``capi.QtosPathPlan`` or a
+    dict of cell, origin_x, origin_y, height_bound, step_size, max_cells, max_open, max_pieces, set_done.  Per window, as
+    ``PathSolver``: ``path_cells``; sub = path[::2], n = len(sub) pieces; xs = col * cell - origin_x over sub, then the last
+    cell's col * cell WITHOUT the shift (sic); ys likewise from the rows; T = sqrt(dx dx + dy dy) / step_size * 10 from the
+    start and goal coordinates; knots i * (T / n), the last one T (numpy's linspace); ``spine_fit`` twice.  A window whose
+    status is not 0, or whose T is not > 0 (status 4), gets the one-piece constant spine at its start point over the knots
+    (0, 0).  Rows are padded as ``path_table`` pads them, to max_pieces.  Returns the dict of ``path_table`` (knots, coef,
+    n_pieces, robot_goal) plus cells [B, max_cells, 2], n_cells [B], status [B] (int32), and done [B] where ``done`` is
+    given: with set_done, bit 2 (value 4) is set in it where the status is not 0."""
+    g = lambda name: _path_param(params, name)
+    m = np.asarray(maps)
+    m = m[None] if m.ndim == 2 else m
+    start = np.asarray(start, np.float64)
+    B = len(start)
+    start = start.reshape(B, -1)
+    rg = np.asarray(goal, np.float64).reshape(B, 3)
+    mid = np.zeros(B, np.int64) if map_id is None else np.clip(np.asarray(map_id, np.int64).reshape(B), 0, len(m) - 1)
+    cell, ox, oy = np.float64(g("cell")), np.float64(g("origin_x")), np.float64(g("origin_y"))
+    step, ten = np.float64(g("step_size")), np.float64(10.0)
+    max_cells, max_open, mp = int(g("max_cells")), int(g("max_open")), int(g("max_pieces"))
+    if m.shape[1] * m.shape[2] > PATH_MAX_GRID or not 1 <= max_open <= PATH_MAX_OPEN or not 1 <= max_cells <= 2 * mp:
+        raise ValueError("rows * cols <= %d, 1 <= max_open <= %d and 1 <= max_cells <= 2 * max_pieces" % (PATH_MAX_GRID, PATH_MAX_OPEN))
+    knots, coef = np.zeros((B, mp + 1)), np.zeros((B, 2, 4, mp))
+    n_pieces = np.ones(B, np.int32)
+    cells, n_cells, status = np.zeros((B, max_cells, 2), np.int32), np.zeros(B, np.int32), np.zeros(B, np.int32)
+    for b in range(B):
+        cells[b], n_cells[b], status[b] = path_cells(m[mid[b]], start[b, 0:2], rg[b, 0:2], cell, ox, oy, g("height_bound"), max_cells,
+                                                     max_open)
+        with np.errstate(all="ignore"):
+            dx, dy = start[b, 0] - rg[b, 0], start[b, 1] - rg[b, 1]
+            T = np.sqrt(dx * dx + dy * dy) / step * ten
+            if status[b] == 0 and not T > 0:
+                status[b] = 4
+            if status[b] != 0:
+                coef[b, 0, 3, 0], coef[b, 1, 3, 0] = start[b, 0], start[b, 1]
+                continue
+            path = cells[b, :n_cells[b]].astype(np.int64)
+            sub = path[::2]
+            n = len(sub)
+            xs = np.append(sub[:, 1] * cell - ox, path[-1, 1] * cell)
+            ys = np.append(sub[:, 0] * cell - oy, path[-1, 0] * cell)
+            t = np.arange(n + 1) * (T / np.float64(n))
+            t[n] = T
+        n_pieces[b] = n
+        knots[b, :n + 1], knots[b, n + 1:] = t, T
+        coef[b, 0, :, :n], coef[b, 1, :, :n] = spine_fit(t, xs), spine_fit(t, ys)
+    out = dict(knots=knots, coef=coef, n_pieces=n_pieces, robot_goal=rg.copy(), cells=cells, n_cells=n_cells, status=status)
+    if done is not None:
+        out["done"] = np.asarray(done, np.int32).reshape(B) | np.where((status != 0) & bool(g("set_done")), PATH_DONE_BIT, 0).astype(np.int32)
+    return out

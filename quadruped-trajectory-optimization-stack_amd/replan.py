@@ -179,6 +179,12 @@ class ShiftedWindows:
                offset.  ``self.clock`` (B, f64: the plan time of row 0 of the newest plan) and ``self.done`` (B, int32: bit 0
                the path's end lies 5 s + ``advance`` behind the plan's start, bit 1 the goal is within ``stop_dist``) live on
                the device; ``self.path_params_init`` / ``self.path_params`` are the QtosPathGoal of the first / later calls.
+               Instead of ``table``, ``plan`` = dict(``bool_map`` n_maps x rows x cols or rows x cols, ``robot_goal`` B x 3, and
+               optionally ``map_id`` (B; default map 0), ``max_cells``, ``max_pieces``, ``max_open`` (4096), ``height_bound``
+               (0.2)) plans the paths on the device (k_path_plan through qtos_path_plan_device, the rule:
+               ``global_planner.path_plan``): window b follows its own path from ``start[b, 0:2]`` to ``robot_goal[b]``.
+               ``self.path_status`` (B, int32; 0 found), ``self.path_cells`` and ``self.path_n_cells`` live on the device, a
+               window without a path has bit 2 of ``self.done`` set, and ``repath()`` plans the paths anew.
     path_base  "spine" (Global_Planner.update: the step is taken from the spine at the plan's start) or "state" (from the state
                the plan starts from), for every plan but the first
     path_hold  True: a window whose done bits are set stands still (its goal is its start) instead of following the spline's
@@ -270,12 +276,19 @@ class ShiftedWindows:
             raise RuntimeError("this build of the planner library has no path-goal kernel (qtos_path_goal_device)")
         if path_base not in capi.PATH_BASES:
             raise ValueError("path_base is 'spine' or 'state'")
-        table = path["table"]
         f64 = dict(dtype=torch.float64, device=dev)
         i32 = dict(dtype=torch.int32, device=dev)
         up = lambda a, kw: None if a is None else torch.as_tensor(np.ascontiguousarray(a), **kw).contiguous()
-        self._path_knots, self._path_coef = up(table["knots"], f64), up(table["coef"], f64)
-        self._path_n, self._path_rg = up(table["n_pieces"], i32), up(table.get("robot_goal"), f64)
+        plan = path.get("plan")
+        self._path_plan_params = None
+        if plan is not None:
+            if path.get("table") is not None or path.get("path_id") is not None:
+                raise ValueError("path['plan'] builds the table on the device, one path per window: give no path['table'] or path['path_id']")
+            table = self._init_path_plan(path, plan)
+        else:
+            table = path["table"]
+            self._path_knots, self._path_coef = up(table["knots"], f64), up(table["coef"], f64)
+            self._path_n, self._path_rg = up(table["n_pieces"], i32), up(table.get("robot_goal"), f64)
         self.path_id = up(path.get("path_id"), i32)
         grids = path.get("map_yx")
         if grids is not None:
@@ -295,6 +308,77 @@ class ShiftedWindows:
         self.path_params = capi.path_goal_params(base=path_base, **kw)
         self.clock = torch.zeros((B,), **f64)
         self.done = torch.zeros((B,), **i32)
+        if plan is not None:
+            import ctypes as C
+            # (on the caller's current stream, as the uploads above: __init__ ends with a wait for it)
+            self._path_plan(C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+
+    def _init_path_plan(self, path, plan):
+        """The buffers and parameters of the device path planner (k_path_plan): the table k_path_goal reads is written on the
+        device, one path per window.  Returns what stands for the table where only its sizes are read."""
+        from . import capi
+        torch, dev, B = self.torch, self.dev, self.B
+        if not hasattr(self.P.lib, "qtos_path_plan_device"):
+            raise RuntimeError("this build of the planner library has no path-plan kernel (qtos_path_plan_device)")
+        f64 = dict(dtype=torch.float64, device=dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        maps = np.asarray(plan["bool_map"], np.float64)
+        maps = maps[None] if maps.ndim == 2 else maps
+        rg = np.asarray(plan["robot_goal"], np.float64)
+        if rg.shape != (B, 3):
+            raise ValueError("path['plan']['robot_goal'] is B x 3")
+        g = capi.path_plan_params(step_size=path["step_size"], cell=path.get("cell", 0.1), origin=path.get("origin", (1.0, 1.0)),
+                                  height_bound=plan.get("height_bound", 0.2), max_cells=plan.get("max_cells"),
+                                  max_open=plan.get("max_open", 4096), max_pieces=plan.get("max_pieces"), set_done=True, bool_map=maps)
+        self._path_plan_params = g
+        mp = int(g.max_pieces)
+        self._plan_maps = torch.as_tensor(np.ascontiguousarray(maps), **f64).contiguous()
+        mid = plan.get("map_id")
+        self._plan_map_id = None if mid is None else torch.as_tensor(np.ascontiguousarray(mid), **i32).contiguous()
+        if self._plan_map_id is not None and tuple(self._plan_map_id.shape) != (B,):
+            raise ValueError("path['plan']['map_id'] has one entry per window")
+        self._path_knots, self._path_coef = torch.zeros((B, mp + 1), **f64), torch.zeros((B, 2, 4, mp), **f64)
+        self._path_n = torch.ones((B,), **i32)
+        self._path_rg = torch.as_tensor(np.ascontiguousarray(rg), **f64).contiguous()
+        self.path_cells = torch.zeros((B, int(g.max_cells), 2), **i32)
+        self.path_n_cells, self.path_status = torch.zeros((B,), **i32), torch.zeros((B,), **i32)
+        return dict(coef=np.broadcast_to(0.0, (B, 2, 4, mp)))
+
+    def _path_plan(self, sp):
+        """Queue k_path_plan: every window's path from self.start[:, 0:2] to its robot goal, into the table k_path_goal reads."""
+        import ctypes as C
+        ptr = lambda t: None if t is None else t.data_ptr()
+        self._call(self.P.lib.qtos_path_plan_device(self.P.h, self.B, C.byref(self._path_plan_params), ptr(self._plan_maps),
+                                                    ptr(self._plan_map_id), ptr(self.start), ptr(self._path_rg), ptr(self._path_knots),
+                                                    ptr(self._path_coef), ptr(self._path_n), ptr(self.path_cells), ptr(self.path_n_cells),
+                                                    ptr(self.path_status), ptr(self.done), sp), "qtos_path_plan_device")
+
+    def repath(self, robot_goal=None, bool_map=None):
+        """Plan every window's path anew from where it stands, self.start[:, 0:2], on the set's stream (PATH_Solver.solve,
+        QTOS/planner.py:422-457): to new robot goals (B x 3) and / or over new boolean maps (the shape given at creation), or
+        the old ones.  The windows' clock starts again at 0 and their done bits are cleared (a window without a path gets bit 2
+        back).  Refused while a replan is pending."""
+        import ctypes as C
+        torch = self.torch
+        if self.path is None or self._path_plan_params is None:
+            raise RuntimeError("repath() needs the device path planner (path=dict(plan=...))")
+        if getattr(self, "_pending", False):
+            raise RuntimeError("repath() while a replan is pending: poll() it first")
+        with torch.cuda.stream(self.stream):
+            if robot_goal is not None:
+                rg = np.ascontiguousarray(robot_goal, np.float64)
+                if rg.shape != (self.B, 3):
+                    raise ValueError("robot_goal is B x 3")
+                self._path_rg.copy_(torch.from_numpy(rg))
+            if bool_map is not None:
+                maps = np.ascontiguousarray(bool_map, np.float64)
+                maps = maps[None] if maps.ndim == 2 else maps
+                if maps.shape != tuple(self._plan_maps.shape):
+                    raise ValueError("bool_map has the shape given at creation, %s" % (tuple(self._plan_maps.shape),))
+                self._plan_maps.copy_(torch.from_numpy(maps))
+            self.clock.zero_()
+            self.done.zero_()
+            self._path_plan(C.c_void_p(self.stream.cuda_stream))
 
     def _path_goal(self, params, offset, sp):
         """Queue k_path_goal: the goals of the plans about to be asked for, from self.start (and the hand-over's offset)."""
