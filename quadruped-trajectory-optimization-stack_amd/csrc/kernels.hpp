@@ -1905,7 +1905,8 @@ __global__ __launch_bounds__(ET) void k_report(DevPlan P, DevWork W, int B) {
 // CSV sampling: row layout of QTOS/utils.py:107-148.  Spline lookup tables are built on the host.
 struct SampleSpline {
   int n_polys;
-  const double *tend;  // cumulative end time of each polynomial
+  const double *tend;  // cumulative end time of each polynomial; behind them, tend[n_polys + k]: what the float64 start
+                       // tend[k] - dur[k] of polynomial k is off its exact start by (sample_spline<true>)
   const double *dur;
   const int *idx;      // (n_polys+1) x 6
 };
@@ -1915,6 +1916,12 @@ struct SamplePlan {
   double T;
 };
 
+// EXACT_START: the local time is taken from the polynomial's exact start (the float64 start and its correction word), so it
+// carries the rounding of t alone and not that of the cumulative table as well.  The first derivative of a force polynomial of
+// a short stance (12 ms on a 1 s horizon) has a slope of 6 / T^2 = 4e4 per second at its nodes, times node values tens of
+// newtons apart: the table's half ulp of t was 2e-10 .. 5e-10 N/s in k_shift_warm's force derivatives (tests/test_gpu_splines.py).
+// The rows of k_sample, k_stitch and k_handover hold values and base velocities only and keep the plain form, bit for bit.
+template <bool EXACT_START = false>
 __device__ inline void sample_spline(const SampleSpline &S, const double *x, double t, int deriv, double out[3]) {
   // first polynomial whose end time >= t - eps (towr spline.cc GetSegmentID)
   int lo = 0, hi = S.n_polys - 1;
@@ -1923,7 +1930,9 @@ __device__ inline void sample_spline(const SampleSpline &S, const double *x, dou
     if (S.tend[mid] >= t - 1e-10) hi = mid; else lo = mid + 1;
   }
   const int k = lo;
-  const double T = S.dur[k], tau = t - (S.tend[k] - T);
+  const double T = S.dur[k];
+  double tau = t - (S.tend[k] - T);
+  if (EXACT_START) tau -= S.tend[S.n_polys + k];
   double w[4];
   const double T2 = T * T, T3 = T2 * T, t2 = tau * tau, t3 = t2 * tau;
   if (deriv == 0) {

@@ -185,9 +185,18 @@ static void (*chord_kernel(int F))(DevPlan, DevWork, int) {
 }
 
 static int upload_spline(QtosPlanner *p, const Spline &S, SampleSpline *out) {
-  std::vector<double> tend(S.n_polys), dur(S.dur);
+  std::vector<double> tend(2 * S.n_polys), dur(S.dur);
   double t = 0;
-  for (int i = 0; i < S.n_polys; ++i) { t += S.dur[i]; tend[i] = t; }
+  double start = 0, start_err = 0;   // the exact start of polynomial i as a sum of two doubles (the additions' rounding errors kept)
+  for (int i = 0; i < S.n_polys; ++i) {
+    t += S.dur[i];
+    tend[i] = t;
+    const double start_f64 = tend[i] - S.dur[i];   // the start as sample_spline forms it
+    tend[S.n_polys + i] = (start - start_f64) + start_err;
+    const double sum = start + S.dur[i], b = sum - start;
+    start_err += (start - (sum - b)) + (S.dur[i] - b);
+    start = sum;
+  }
   std::vector<int> idx;
   for (auto &nd : S.idx)
     for (int i = 0; i < 6; ++i) idx.push_back(nd[i]);
@@ -1482,7 +1491,7 @@ __global__ __launch_bounds__(256) void k_shift_warm(DevPlan P, SamplePlan S, con
           if (I.set == 6 + e) sp = S.eef[e];
         }
         double o3[3];
-        sample_spline(sp, x, fmin(t, S.T), I.is_vel, o3);
+        sample_spline<true>(sp, x, fmin(t, S.T), I.is_vel, o3);
         val = o3[I.dim];
       } else val = straight_line_value(P, I, st, gl, map);
     }

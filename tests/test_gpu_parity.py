@@ -979,7 +979,10 @@ def test_shifted_windows_match_oracle_over_five_replans(preset, order):
 
     Round 6 also fixed the shifted start itself: k_shift_warm read the time KEYS of the elimination order as node times, and
     reduce_swing (round 5) had moved a foothold's key to the end of the swing behind its stance -- the warm start's footholds were
-    the NEXT footholds' positions.  With the node times proper the shifted replans take 4 - 8 iterations (5 - 17 before)."""
+    the NEXT footholds' positions.  With the node times proper the shifted replans take 4 - 8 iterations (5 - 17 before).
+
+    This test hands the oracle the kernel's own warm start, so it cannot see a wrong one: the warm start itself is pinned in
+    tests/test_gpu_splines.py (k_shift_warm against oracle/splines.shift_warm, the identity at offset 0)."""
     import torch
     from oracle.oracle import Oracle, oracle_dict, oracle_options
     from qtos_amd import workloads
