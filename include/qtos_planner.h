@@ -446,6 +446,74 @@ int qtos_path_plan_device(QtosPlanner *p, int B, const QtosPathPlan *g, const do
 int qtos_path_plan(QtosPlanner *p, int B, const QtosPathPlan *g, const double *bool_maps, const int *map_id, const double *start,
                    const double *robot_goal, double *knots, double *coef, int *n_pieces, int *cells, int *n_cells, int *status, int *done);
 
+/* The boolean maps of receding windows from their heightfields, on the device: what qtos_path_plan* reads as bool_maps.  Replaces
+ * PATH_MAP (QTOS/generateHeightField.py:172-404: probe_map queues a (start, goal) patch two cells apart wherever an obstacle is
+ * near, 32 `docker exec ./main` workers solve the patches, worker_f stamps the exit codes into the map) for n_maps maps at once,
+ * in two steps with the batched solve that already exists between them, all on one stream:
+ *   map_yx --qtos_probe_device--> start N x 24, goal N x 3, map_id N --qtos_plan_batch_device--> status N
+ *          --qtos_probe_stamp_device--> bool_maps --qtos_path_plan_device--> ...
+ * The host reads ONE word in between: N = offsets[n_maps], the number of problems, to size the plan call or calls (a handle
+ * solves up to max_batch problems per call).  The numpy statement of both steps is feasibility.probe_table / round2 /
+ * stamp_table, which the kernels equal to the bit.
+ * Probe (k_probe_count, k_probe_scan, k_probe; one wavefront per map).  Per map the patches of probe_map in queue order: row
+ * r = 0 .. rows - 1 outside, j = 0 .. cols / 2 - 2 inside, start cell (r, 2 j), goal cell (r, 2 j + 2); a patch is queued where
+ * neighbors_danger_test answers true for its start or its goal cell: the eight neighbours in the order (1,0), (-1,0), (0,1),
+ * (0,-1), (1,1), (1,-1), (-1,-1), (-1,1) (row, column), false at the first one outside the map, true at the first one inside it
+ * that is > 0 (a NaN is not).  The lists of the maps are concatenated, map 0's first; no atomics decide where a patch goes.
+ * Coordinates, every operation one rounded IEEE double operation, with res = cell * (1 / scale), s = (multi_map_shift - 1) *
+ * origin_shift and round2 = Python's round(v, 2):
+ *   x_start = ((-res * (cols / 2)) - res / 2) + s     for x AND y (sic: both from the number of columns)
+ *   x_goal  = ((-res * (cols / 2)) + res / 2) + s
+ *   y_r: y <- round2(y + res) from x_start, once per row;  X_0 = round2(x_start + res), X_1 = round2(x_goal + 2 res),
+ *   X_(j+1) = round2(X_j + 2 res): patch (r, j) starts at (X_j, y_r) and goes to (X_(j+1), y_r)
+ *   round2(v): p = v * 100, e = fma(v, 100, -p) its exact error, k = rint(p); where |p - k| = 0.5 and e != 0,
+ *   k = floor(p) + (e > 0); k / 100
+ * start[i] = (X_j, y_r, z + z_offset), Euler angles 0, the feet nominal_stance[e] + (X_j, y_r, z) in the order FL FR HL HR,
+ * velocities 0; goal[i] = (X_(j+1), y_r, z_goal + z_offset); z, z_goal the heights of the start and the goal cell; map_id[i] = the
+ * map: map m of the call is heightfield m of the handle (qtos_set_heightfields with the same maps in the solver's orientation).
+ * An all-zero map has no patch (the reference's check_flat_ground short-cut).
+ * Stamp (k_probe_stamp; one wavefront per map, one lane per cell in turn).  A cell holds what the LAST patch in queue order
+ * that writes it leaves: a patch with status 0 writes 0 to its start cell, the cell right of it and its goal cell; any other
+ * status writes 1 to the diamonds |a| + |b| <= 3 scale round the start cell and round the goal cell, clipped to the map; a cell
+ * nothing writes is 0. */
+typedef struct QtosProbe {
+  int rows, cols;              /* of the maps (cols >= 2, rows * cols <= 16384: the limit of qtos_path_plan*)    */
+  int n_maps;                  /* 1 .. 16777216; n_maps * rows * (cols / 2 - 1) fits an int                      */
+  double cell;                 /* of the maps at scale 1 (> 0; the reference: 0.1)                               */
+  int scale;                   /* 1 .. 4: the cell is cell * (1 / scale), the diamond's radius 3 * scale         */
+  int multi_map_shift;         /* >= 1 (the reference: the number of tiles of the map)                           */
+  double origin_shift;         /* the reference: 1.0                                                             */
+  double z_offset;             /* height of the base above the terrain (the reference: 0.24)                     */
+  double nominal_stance[QTOS_NEE][3];  /* FL FR HL HR (the reference: (+-0.21, +-0.19, 0.0))                     */
+} QtosProbe;
+/* map_yx n_maps x rows x cols doubles (heights, row = y index, as the maps of qtos_path_goal*); capacity: the number of problems
+ * the arrays patch, start, goal and map_id have room for (>= 0).  Written: offsets n_maps + 1 ints (exclusive prefix sums of the
+ * maps' patch counts: offsets[0] = 0, offsets[n_maps] = N) and slot n_maps x rows x (cols / 2 - 1) ints (a patch's index i, or
+ * -1), both whole; patch N x 3 ints (map, row, start column), start N x QTOS_START_DOUBLES, goal N x 3 and map_id N for the
+ * patches with i < capacity, and nothing beyond them.  offsets, slot and patch are required (patch with capacity 0 is not
+ * written, but not NULL); start, goal and map_id may each be NULL: that array is not written.  Where offsets[n_maps] > capacity
+ * the caller allocates arrays of offsets[n_maps] problems and calls again: the first capacity problems are already right, and the
+ * second call writes the same bits.
+ * qtos_probe_stamp*: offsets, slot as a probe call left them; patch may be NULL: it is not read (the kernel finds the patches
+ * through slot; the argument keeps the probe's arrays together in a call); status offsets[n_maps] ints (status_out of qtos_plan_batch*: 0 solved);
+ * bool_maps n_maps x rows x cols doubles of 0.0 / 1.0, written whole: bool_maps of qtos_path_plan*.  Only rows, cols, n_maps
+ * and scale of `g` are read by the stamp, and all of `g` is checked.
+ * Device forms: all pointers but `g` in device memory, kernels queued on `stream`; no handle state is read or written, and they
+ * may be queued while a call is open.  Host forms: host pointers, synchronous, through device buffers of their own as
+ * qtos_path_plan (no -5); the result is what the device forms leave; qtos_probe_stamp reads offsets[n_maps] to size status.
+ * All: -1 on a null planner; -2 on any other bad argument, with no kernel launched and the reason in qtos_last_error -- a null
+ * `g` or required pointer, cols < 2, rows < 1, rows * cols > 16384, n_maps outside 1 .. 16777216 or too many for an int of
+ * slots, scale outside 1 .. 4, multi_map_shift < 1, cell not > 0, an origin_shift, z_offset or stance that is not a number,
+ * capacity < 0 -- and on a HIP error; -3 out of memory. */
+int qtos_probe_device(QtosPlanner *p, const QtosProbe *g, const double *d_map_yx, int capacity, int *d_offsets, int *d_slot, int *d_patch,
+                      double *d_start /* may be NULL */, double *d_goal /* may be NULL */, int *d_map_id /* may be NULL */, void *stream);
+int qtos_probe(QtosPlanner *p, const QtosProbe *g, const double *map_yx, int capacity, int *offsets, int *slot, int *patch, double *start,
+               double *goal, int *map_id);
+int qtos_probe_stamp_device(QtosPlanner *p, const QtosProbe *g, const int *d_offsets, const int *d_slot, const int *d_patch /* may be NULL */,
+                            const int *d_status, double *d_bool_maps, void *stream);
+int qtos_probe_stamp(QtosPlanner *p, const QtosProbe *g, const int *offsets, const int *slot, const int *patch, const int *status,
+                     double *bool_maps);
+
 /* The plan as the text file the reference copies out of its container (`docker cp <id>:.../build/traj.csv ./data/traj/towr.csv`,
  * scripts/main.py:90-92; consumers scripts/run.py:129-137, QTOS/combiner.py:263-274): rows is n_rows x 37 (one plan of
  * qtos_sample_csv), every number printed as the solver's C++ stream prints it (default precision 6 = printf "%g"), comma

@@ -200,6 +200,36 @@ def path_plan_params(step_size=1.0, cell=0.1, origin=(1.0, 1.0), height_bound=0.
     return g
 
 
+class QtosProbe(C.Structure):
+    """Parameters of a probe / stamp call (qtos_probe*, qtos_probe_stamp*, include/qtos_planner.h)."""
+    _fields_ = [
+        ("rows", C.c_int), ("cols", C.c_int), ("n_maps", C.c_int), ("cell", C.c_double), ("scale", C.c_int), ("multi_map_shift", C.c_int),
+        ("origin_shift", C.c_double), ("z_offset", C.c_double), ("nominal_stance", (C.c_double * 3) * NEE),
+    ]
+
+    def copy(self):
+        return QtosProbe.from_buffer_copy(self)
+
+
+def probe_params(map_yx=None, multi_map_shift=1, scale=1, origin_shift=1.0, cell=0.1, z_offset=0.24,
+                 nominal_stance=((0.21, 0.19, 0.0), (0.21, -0.19, 0.0), (-0.21, 0.19, 0.0), (-0.21, -0.19, 0.0))):
+    """A QtosProbe with the reference's constants as defaults (feasibility.probe_table's).  map_yx fills the sizes: the maps
+    (n_maps x rows x cols, or rows x cols; an array, a tensor or nested lists) or their shape (a tuple or list of 2 or 3 ints)."""
+    g = QtosProbe()
+    g.cell, g.scale, g.multi_map_shift = float(cell), int(scale), int(multi_map_shift)
+    g.origin_shift, g.z_offset = float(origin_shift), float(z_offset)
+    for e in range(NEE):
+        for k in range(3):
+            g.nominal_stance[e][k] = float(nominal_stance[e][k])
+    if map_yx is not None:
+        is_shape = isinstance(map_yx, (tuple, list)) and len(map_yx) in (2, 3) and all(isinstance(v, (int, np.integer)) for v in map_yx)
+        shape = tuple(int(v) for v in (map_yx if is_shape else np.shape(map_yx)))
+        if len(shape) not in (2, 3):
+            raise ValueError("map_yx is n_maps x rows x cols or rows x cols, or that shape")
+        g.n_maps, g.rows, g.cols = (1,) + shape if len(shape) == 2 else shape
+    return g
+
+
 class SelftestError(RuntimeError):
     """No elimination order passed the KKT self-test (qtos_planner_create_checked returned -6); `attempts`: the QtosSelftest
     records in the order they were tried."""
@@ -225,6 +255,7 @@ EXPORTS = [
     "qtos_planner_selftest", "qtos_planner_create_checked", "qtos_analyze_candidates", "qtos_selftest_inputs", "qtos_selftest_bits",
     "qtos_selftest_problem", "qtos_handover", "qtos_handover_device", "qtos_stitch", "qtos_stitch_device",
     "qtos_path_goal", "qtos_path_goal_device", "qtos_path_plan", "qtos_path_plan_device",
+    "qtos_probe", "qtos_probe_device", "qtos_probe_stamp", "qtos_probe_stamp_device",
 ]
 
 _lib = None
@@ -336,6 +367,11 @@ def load():
     if hasattr(lib, "qtos_path_plan"):  # (the path-plan kernel of the receding windows; older builds lack it)
         lib.qtos_path_plan.argtypes = [vp, C.c_int, C.POINTER(QtosPathPlan), dp, ip, dp, dp, dp, dp, ip, ip, ip, ip, ip]
         lib.qtos_path_plan_device.argtypes = [vp, C.c_int, C.POINTER(QtosPathPlan)] + [vp] * 12
+    if hasattr(lib, "qtos_probe"):      # (the probe and stamp kernels of the windows' boolean maps; older builds lack them)
+        lib.qtos_probe.argtypes = [vp, C.POINTER(QtosProbe), dp, C.c_int, ip, ip, ip, dp, dp, ip]
+        lib.qtos_probe_device.argtypes = [vp, C.POINTER(QtosProbe), vp, C.c_int] + [vp] * 7
+        lib.qtos_probe_stamp.argtypes = [vp, C.POINTER(QtosProbe), ip, ip, ip, ip, dp]
+        lib.qtos_probe_stamp_device.argtypes = [vp, C.POINTER(QtosProbe)] + [vp] * 6
     _lib = lib
     return lib
 
@@ -823,6 +859,55 @@ class Planner:
         out = dict(knots=knots, coef=coef, n_pieces=npc, robot_goal=rg.copy(), cells=cl, n_cells=ncl, status=status)
         if dn is not None:
             out["done"] = dn
+        return out
+
+    def has_probe(self):
+        return hasattr(self.lib, "qtos_probe")
+
+    def probe(self, map_yx, params=None, capacity=None):
+        """The probe patches of the maps as solver problems (qtos_probe, host form; the rule: feasibility.probe_table).  map_yx
+        n_maps x rows x cols or rows x cols; params: a QtosProbe (probe_params; the maps' sizes are filled in here); capacity: room
+        for that many problems (None: a first call with capacity 0 reads their number, a second one fills arrays of that size).
+        Returns the dict of feasibility.probe_table -- offsets, slot, patch, start, goal, map_id, the last four with
+        min(N, capacity) rows."""
+        if not self.has_probe():
+            raise RuntimeError("this build of the planner library has no probe kernels (qtos_probe)")
+        maps = np.ascontiguousarray(map_yx, np.float64)
+        maps = maps[None] if maps.ndim == 2 else maps
+        g = (params or probe_params()).copy()
+        g.n_maps, g.rows, g.cols = maps.shape
+        offsets = np.zeros(g.n_maps + 1, np.int32)
+        slot = np.zeros((g.n_maps, g.rows, max(g.cols // 2 - 1, 0)), np.int32)
+
+        def call(cap):
+            out = dict(patch=np.zeros((cap, 3), np.int32), start=np.zeros((cap, START_DOUBLES)), goal=np.zeros((cap, 3)),
+                       map_id=np.zeros(cap, np.int32))
+            self._chk(self.lib.qtos_probe(self.h, C.byref(g), _dp(maps), cap, _ip(offsets), _ip(slot), _ip(out["patch"]), _dp(out["start"]),
+                                          _dp(out["goal"]), _ip(out["map_id"])), "probe")
+            return out
+        out = call(0 if capacity is None else int(capacity))
+        if capacity is None and offsets[-1] > 0:
+            out = call(int(offsets[-1]))
+        n = min(int(offsets[-1]), len(out["patch"]))
+        return dict(offsets=offsets, slot=slot, **{k: v[:n] for k, v in out.items()})
+
+    def probe_stamp(self, shape, offsets, slot, patch, status, params=None):
+        """Exit statuses -> boolean maps (qtos_probe_stamp, host form; the rule: feasibility.stamp_table).  shape (rows, cols) or
+        (n_maps, rows, cols); offsets, slot, patch as probe() returned them; status [offsets[-1]].  Returns n_maps x rows x cols
+        doubles of 0.0 / 1.0."""
+        if not self.has_probe():
+            raise RuntimeError("this build of the planner library has no probe kernels (qtos_probe_stamp)")
+        offsets = np.ascontiguousarray(offsets, np.int32)
+        g = (params or probe_params()).copy()
+        g.n_maps, (g.rows, g.cols) = len(offsets) - 1, tuple(shape)[-2:]
+        slot = np.ascontiguousarray(slot, np.int32)
+        patch = None if patch is None else np.ascontiguousarray(patch, np.int32).reshape(-1, 3)     # (not read by the library)
+        status = np.ascontiguousarray(status, np.int32).reshape(-1)
+        N = int(offsets[-1])
+        if slot.size != g.n_maps * g.rows * max(g.cols // 2 - 1, 0) or len(status) < N or (patch is not None and len(patch) < N):
+            raise ValueError("slot is n_maps x rows x (cols // 2 - 1); patch (or None) and status hold offsets[-1] entries")
+        out = np.zeros((g.n_maps, g.rows, g.cols))
+        self._chk(self.lib.qtos_probe_stamp(self.h, C.byref(g), _ip(offsets), _ip(slot), _ip(patch), _ip(status), _dp(out)), "probe_stamp")
         return out
 
     # ---- optional: nominal-plan table for the starting point of cold solves ----

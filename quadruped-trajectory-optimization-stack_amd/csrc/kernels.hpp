@@ -2491,4 +2491,183 @@ __global__ __launch_bounds__(64) void k_path_plan(PathPlanArgs A, const double *
   }
 }
 
+// The probe and the stamp of the windows' heightfields (qtos_probe*, qtos_probe_stamp*; PATH_MAP.probe_map and worker_f,
+// QTOS/generateHeightField.py:172-404): what k_path_plan reads as bool_maps, made on the device with the batched solve between
+// the two steps.  The statement of the rule is feasibility.probe_table / round2 / stamp_table, and these kernels equal it to
+// the bit: every function that forms a coordinate switches contraction off and performs the rule's operations one by one (the
+// one explicit fma of probe_round2 is the exact error of a product).  One wavefront per map.  The placement of the patches is
+// decided by counting alone: k_probe_count leaves every map's number of patches in offsets[m + 1], k_probe_scan turns them into
+// prefix sums in place, and k_probe places patch q of map m at offsets[m] + (the candidates in front of q in queue order), a
+// ballot and a prefix count per 64 candidates.  No atomics, no scratch, plain vector stores only, no handle state.
+// LDS (k_probe), dynamic, sized at the launch by probe_lds_bytes: the map's row coordinates, its column coordinates and the
+// twelve stance offsets, rows + cols / 2 + 12 doubles (a 20 x 60 map: 496 B; with rows * cols <= 16384 at most 64 KiB).
+struct ProbeArgs {   // QtosProbe as the kernels read it (qtos_planner.hip probe_args)
+  double cell, origin_shift, z_offset, stance[QTOS_NEE * 3];
+  int rows, cols, n_maps, scale, multi_map_shift, capacity;
+};
+
+inline size_t probe_lds_bytes(int rows, int cols) { return ((size_t)rows + (size_t)(cols / 2) + QTOS_NEE * 3) * sizeof(double); }
+
+// Python's round(v, 2) (feasibility.round2): the product's exact error decides the half-way cases that are no true ties
+__device__ inline double probe_round2(double v) {
+#pragma clang fp contract(off)
+  const double p = v * 100.0;
+  const double e = fma(v, 100.0, -p);
+  double k = rint(p);
+  if (fabs(p - k) == 0.5 && e != 0.0) k = floor(p) + (e > 0.0 ? 1.0 : 0.0);
+  return k / 100.0;
+}
+
+// neighbors_danger_test(m, r, c): the eight neighbours in the reference's order; the first one outside the map answers false,
+// the first one inside it that is > 0 answers true (a NaN is not > 0)
+__device__ inline bool probe_danger(const double *hm, int rows, int cols, int r, int c) {
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const int nr = r + ((k == 0 || k == 4 || k == 5) ? 1 : ((k == 1 || k == 6 || k == 7) ? -1 : 0));
+    const int nc = c + ((k == 2 || k == 4 || k == 7) ? 1 : ((k == 3 || k == 5 || k == 6) ? -1 : 0));
+    if (nr < 0 || nr >= rows || nc < 0 || nc >= cols) return false;
+    if (hm[(size_t)nr * cols + nc] > 0.0) return true;
+  }
+  return false;
+}
+
+// candidate q = row * nj + j of a map (queue order): the patch from column 2 j to column 2 j + 2 of that row
+__device__ inline bool probe_candidate(const double *hm, int rows, int cols, int nj, int q) {
+  const int r = q / nj, c = 2 * (q % nj);
+  return probe_danger(hm, rows, cols, r, c) || probe_danger(hm, rows, cols, r, c + 2);
+}
+
+__global__ __launch_bounds__(64) void k_probe_count(ProbeArgs A, const double *map_yx, int *offsets) {
+  const int m = blockIdx.x, lane = threadIdx.x;
+  const int rows = A.rows, cols = A.cols, nj = cols / 2 - 1, Q = rows * nj;
+  const double *hm = map_yx + (size_t)m * rows * cols;
+  int n = 0;
+  for (int q0 = 0; q0 < Q; q0 += 64) {
+    const int q = q0 + lane;
+    const bool cand = q < Q && probe_candidate(hm, rows, cols, nj, q);
+    n += __popcll(__ballot(cand));
+  }
+  if (lane == 0) {
+    offsets[m + 1] = n;
+    if (m == 0) offsets[0] = 0;
+  }
+}
+
+// offsets[1 .. n_maps]: counts -> inclusive prefix sums, in place, by one workgroup (a lane owns a contiguous run of entries)
+__global__ __launch_bounds__(256) void k_probe_scan(int *offsets, int n_maps) {
+  __shared__ int part[256];
+  const int t = threadIdx.x, per = (n_maps + 255) / 256;
+  const int lo = 1 + t * per, hi = lo + per < n_maps + 1 ? lo + per : n_maps + 1;
+  int s = 0;
+  for (int i = lo; i < hi; ++i) s += offsets[i];
+  part[t] = s;
+  __syncthreads();
+  int run = 0;
+  for (int k = 0; k < t; ++k) run += part[k];
+  for (int i = lo; i < hi; ++i) {
+    run += offsets[i];
+    offsets[i] = run;
+  }
+}
+
+__global__ __launch_bounds__(64) void k_probe(ProbeArgs A, const double *map_yx, const int *offsets, int *slot, int *patch, double *start,
+                                              double *goal, int *map_id) {
+#pragma clang fp contract(off)
+  extern __shared__ double co[];                                     // ys[rows], xs[nj + 1] (xs[j] starts patch j, xs[j + 1] is its goal), stance[12]
+  const int m = blockIdx.x, lane = threadIdx.x;
+  const int rows = A.rows, cols = A.cols, nj = cols / 2 - 1, Q = rows * nj;
+  if (Q < 1) return;                                                 // (uniform: a map of 2 or 3 columns has no candidate and no slot)
+  const double *hm = map_yx + (size_t)m * rows * cols;
+  double *ys = co, *xs = co + rows, *stance = xs + nj + 1;           // (the stance is read per patch: in LDS it holds no scalar registers over the loop)
+  if (lane == 0) {                                                   // PATH_MAP.probe_map's walk, statement by statement
+#pragma unroll
+    for (int k = 0; k < QTOS_NEE * 3; ++k) stance[k] = A.stance[k];
+    const double res = A.cell * (1.0 / (double)A.scale), half = (double)cols / 2.0;
+    const double shift = (double)(A.multi_map_shift - 1) * A.origin_shift;
+    const double x_start = ((-res * half) - res / 2.0) + shift;      // (sic: x and y both start from the number of columns)
+    const double x_goal = ((-res * half) + res / 2.0) + shift;
+    double y = x_start;
+    for (int r = 0; r < rows; ++r) {
+      y = probe_round2(y + res);
+      ys[r] = y;
+    }
+    xs[0] = probe_round2(x_start + res);
+    double xg = x_goal;
+    for (int j = 0; j < nj; ++j) {
+      xg = probe_round2(xg + 2.0 * res);
+      xs[j + 1] = xg;
+    }
+  }
+  __syncthreads();
+  int run = offsets[m];
+  for (int q0 = 0; q0 < Q; q0 += 64) {
+    const int q = q0 + lane;
+    const bool cand = q < Q && probe_candidate(hm, rows, cols, nj, q);
+    const unsigned long long mask = __ballot(cand);
+    const int i = run + __popcll(mask & ((1ull << lane) - 1ull));
+    run += __popcll(mask);
+    if (q < Q) slot[(size_t)m * Q + q] = cand ? i : -1;
+    if (!cand || i >= A.capacity) continue;                          // (nothing is written beyond the capacity)
+    const int r = q / nj, j = q % nj;
+    const double px = xs[j], py = ys[r], z = hm[(size_t)r * cols + 2 * j], zg = hm[(size_t)r * cols + 2 * j + 2];
+    patch[(size_t)i * 3] = m;
+    patch[(size_t)i * 3 + 1] = r;
+    patch[(size_t)i * 3 + 2] = 2 * j;
+    if (map_id) map_id[i] = m;
+    if (start) {
+      double *s = start + (size_t)i * QTOS_START_DOUBLES;
+      s[0] = px; s[1] = py; s[2] = z + A.z_offset;
+      s[3] = 0.0; s[4] = 0.0; s[5] = 0.0;
+#pragma unroll
+      for (int e = 0; e < QTOS_NEE; ++e) {
+        s[6 + 3 * e] = stance[3 * e] + px;
+        s[7 + 3 * e] = stance[3 * e + 1] + py;
+        s[8 + 3 * e] = stance[3 * e + 2] + z;
+      }
+#pragma unroll
+      for (int k = 18; k < QTOS_START_DOUBLES; ++k) s[k] = 0.0;
+    }
+    if (goal) {
+      goal[(size_t)i * 3] = xs[j + 1];
+      goal[(size_t)i * 3 + 1] = py;
+      goal[(size_t)i * 3 + 2] = zg + A.z_offset;
+    }
+  }
+}
+
+// worker_f's stamp (feasibility.stamp_table): one lane per cell in turn.  The cell holds what the LAST patch of its map in queue
+// order that writes it leaves, and that patch is the largest (row, j) among the few whose start or goal lies within the
+// diamond's radius R = 3 scale of the cell (a failure), or on the cell and up to two cells left of it (a success: start, the
+// cell right of it, goal).  The rows are walked downwards from r + R, the patches of a row downwards from the last whose
+// diamonds reach the cell; the first patch met that writes the cell decides.  A slot beyond offsets[n_maps] is no patch.
+__global__ __launch_bounds__(64) void k_probe_stamp(ProbeArgs A, const int *offsets, const int *slot, const int *status, double *bool_maps) {
+  const int m = blockIdx.x, lane = threadIdx.x;
+  const int rows = A.rows, cols = A.cols, nj = cols / 2 - 1, R = 3 * A.scale, N = offsets[A.n_maps];
+  const int *sl = slot + (size_t)m * rows * (nj > 0 ? nj : 0);
+  double *bm = bool_maps + (size_t)m * rows * cols;
+  for (int ci = lane; ci < rows * cols; ci += 64) {
+    const int r = ci / cols, c = ci % cols;
+    double v = 0.0;
+    bool found = false;
+    const int r_hi = r + R < rows - 1 ? r + R : rows - 1, r_lo = r - R > 0 ? r - R : 0;
+    for (int pr = r_hi; pr >= r_lo && !found; --pr) {
+      const int w = R - (pr > r ? pr - r : r - pr);                  // the diamond's reach along this row (>= 0)
+      int j_hi = (c + w) >> 1, j_lo = (c - w - 2 + 1) >> 1;          // start columns 2 j within c - w - 2 .. c + w
+      if (j_hi > nj - 1) j_hi = nj - 1;
+      if (j_lo < 0) j_lo = 0;
+      for (int j = j_hi; j >= j_lo; --j) {
+        const int i = sl[(size_t)pr * nj + j];
+        if (i < 0 || i >= N) continue;
+        const int st = status[i], d = c - 2 * j, ds = d < 0 ? -d : d, dg = d < 2 ? 2 - d : d - 2;   // columns from the start, the goal
+        if (st != 0 ? (ds <= w || dg <= w) : (pr == r && d >= 0 && d <= 2)) {
+          v = st != 0 ? 1.0 : 0.0;
+          found = true;
+          break;
+        }
+      }
+    }
+    bm[ci] = v;
+  }
+}
+
 }  // namespace qtos

@@ -681,6 +681,8 @@ static int create_planner(const QtosParams *params, int max_batch, int device, c
   }
   for (const void *fn : {(const void *)k_start, (const void *)k_step, (const void *)k_debug_eval})
     if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->eval_lds) != hipSuccess) { qtos_planner_destroy(p); return -2; }
+  // (k_probe: the widest map the checks of probe_args admit, one row of 16384 columns, needs a little more than 64 KiB)
+  if (hipFuncSetAttribute((const void *)k_probe, hipFuncAttributeMaxDynamicSharedMemorySize, (int)probe_lds_bytes(1, PP_GRID)) != hipSuccess) { qtos_planner_destroy(p); return -2; }
   // sampling tables
   SamplePlan &SP = p->sp;
   std::memset(&SP, 0, sizeof(SP));
@@ -1816,6 +1818,130 @@ int qtos_path_plan(QtosPlanner *p, int B, const QtosPathPlan *g, const double *b
   };
   const int rc = run();
   for (const Buf &b : bufs) (void)hipFree(*b.d);
+  return rc;
+}
+
+// ---- the probe and the stamp of the windows' heightfields (k_probe*, kernels.hpp) -------------------------
+// The argument checks of all four forms, and QtosProbe as the kernels read it.  k_probe's LDS is sized from these limits, and
+// k_probe_scan's index arithmetic stays within an int for PROBE_MAPS maps.
+static constexpr int PROBE_MAPS = 1 << 24;
+static int probe_args(QtosPlanner *p, const QtosProbe *g, const char *who, bool pointers, int capacity, ProbeArgs *A) {
+  if (!p) return -1;
+  const char *why = nullptr;
+  if (!g || !pointers) why = "a required pointer is null";
+  else if (g->rows < 1 || g->cols < 2 || (long long)g->rows * g->cols > PP_GRID) why = "rows >= 1, cols >= 2 and rows * cols <= 16384";
+  else if (g->n_maps < 1 || g->n_maps > PROBE_MAPS) why = "n_maps is 1 .. 16777216";
+  else if ((long long)g->n_maps * g->rows * (g->cols / 2 - 1) > 2147483647LL) why = "the slots, n_maps * rows * (cols / 2 - 1), fit an int";
+  else if (g->scale < 1 || g->scale > 4) why = "scale is 1 .. 4";
+  else if (g->multi_map_shift < 1) why = "multi_map_shift >= 1";
+  else if (!(g->cell > 0)) why = "cell is > 0";
+  else if (g->origin_shift != g->origin_shift || g->z_offset != g->z_offset) why = "origin_shift or z_offset is not a number";
+  else if (capacity < 0) why = "capacity >= 0";
+  if (!why)
+    for (int e = 0; e < QTOS_NEE; ++e)
+      for (int k = 0; k < 3; ++k)
+        if (g->nominal_stance[e][k] != g->nominal_stance[e][k]) why = "nominal_stance is not a number";
+  if (why) {
+    p->err = std::string(who) + ": " + why;
+    return -2;
+  }
+  A->cell = g->cell; A->origin_shift = g->origin_shift; A->z_offset = g->z_offset;
+  for (int e = 0; e < QTOS_NEE; ++e)
+    for (int k = 0; k < 3; ++k) A->stance[3 * e + k] = g->nominal_stance[e][k];
+  A->rows = g->rows; A->cols = g->cols; A->n_maps = g->n_maps; A->scale = g->scale; A->multi_map_shift = g->multi_map_shift;
+  A->capacity = capacity;
+  return 0;
+}
+
+int qtos_probe_device(QtosPlanner *p, const QtosProbe *g, const double *d_map_yx, int capacity, int *d_offsets, int *d_slot, int *d_patch,
+                      double *d_start, double *d_goal, int *d_map_id, void *stream_) {
+  ProbeArgs A;
+  if (const int rc = probe_args(p, g, "qtos_probe", d_map_yx && d_offsets && d_slot && d_patch, capacity, &A)) return rc;
+  HIPCHK(p, hipSetDevice(p->device));
+  hipStream_t s = (hipStream_t)stream_;
+  hipLaunchKernelGGL(k_probe_count, dim3(A.n_maps), dim3(64), 0, s, A, d_map_yx, d_offsets);
+  hipLaunchKernelGGL(k_probe_scan, dim3(1), dim3(256), 0, s, d_offsets, A.n_maps);
+  hipLaunchKernelGGL(k_probe, dim3(A.n_maps), dim3(64), probe_lds_bytes(A.rows, A.cols), s, A, d_map_yx, d_offsets, d_slot, d_patch, d_start, d_goal, d_map_id);
+  HIPCHK(p, hipGetLastError());
+  return 0;
+}
+
+int qtos_probe_stamp_device(QtosPlanner *p, const QtosProbe *g, const int *d_offsets, const int *d_slot, const int *d_patch,
+                            const int *d_status, double *d_bool_maps, void *stream_) {
+  ProbeArgs A;
+  (void)d_patch;                                           // (not read: the kernel finds the patches through slot)
+  if (const int rc = probe_args(p, g, "qtos_probe_stamp", d_offsets && d_slot && d_status && d_bool_maps, 0, &A)) return rc;
+  HIPCHK(p, hipSetDevice(p->device));
+  hipLaunchKernelGGL(k_probe_stamp, dim3(A.n_maps), dim3(64), 0, (hipStream_t)stream_, A, d_offsets, d_slot, d_status, d_bool_maps);
+  HIPCHK(p, hipGetLastError());
+  return 0;
+}
+
+int qtos_probe(QtosPlanner *p, const QtosProbe *g, const double *map_yx, int capacity, int *offsets, int *slot, int *patch, double *start,
+               double *goal, int *map_id) {
+  ProbeArgs A;
+  if (const int rc = probe_args(p, g, "qtos_probe", map_yx && offsets && slot && patch, capacity, &A)) return rc;
+  HIPCHK(p, hipSetDevice(p->device));
+  // buffers of its own, as qtos_path_plan.  The outputs are copied in first: what the kernels do not write -- problems beyond
+  // N -- comes back as it was.  pad: a word allocated behind the bytes that are copied, so that an empty array is a pointer still
+  const size_t cells = (size_t)g->n_maps * g->rows * g->cols, slots = (size_t)g->n_maps * g->rows * (g->cols / 2 - 1), cap = (size_t)capacity;
+  struct Buf { void **d; const void *in; void *out; size_t bytes, pad; };
+  double *d_map = nullptr, *d_start = nullptr, *d_goal = nullptr;
+  int *d_off = nullptr, *d_slot = nullptr, *d_patch = nullptr, *d_mid = nullptr;
+  const Buf bufs[] = {
+      {(void **)&d_map, map_yx, nullptr, cells * sizeof(double), 0},
+      {(void **)&d_off, nullptr, offsets, ((size_t)g->n_maps + 1) * sizeof(int), 0},
+      {(void **)&d_slot, nullptr, slot, slots * sizeof(int), sizeof(int)},
+      {(void **)&d_patch, patch, patch, cap * 3 * sizeof(int), sizeof(int)},
+      {(void **)&d_start, start, start, start ? cap * QTOS_START_DOUBLES * sizeof(double) : 0, start ? sizeof(double) : 0},
+      {(void **)&d_goal, goal, goal, goal ? cap * 3 * sizeof(double) : 0, goal ? sizeof(double) : 0},
+      {(void **)&d_mid, map_id, map_id, map_id ? cap * sizeof(int) : 0, map_id ? sizeof(int) : 0},
+  };
+  auto run = [&]() -> int {
+    for (const Buf &b : bufs) {
+      if (!b.bytes && !b.pad) continue;                    // (an optional array that was not given stays a null pointer)
+      HIPCHK(p, hipMalloc(b.d, b.bytes + b.pad));
+      if (b.in && b.bytes) HIPCHK(p, hipMemcpy(*b.d, b.in, b.bytes, hipMemcpyHostToDevice));
+    }
+    const int rc = qtos_probe_device(p, g, d_map, capacity, d_off, d_slot, d_patch, d_start, d_goal, d_mid, nullptr);
+    if (rc) return rc;
+    for (const Buf &b : bufs)
+      if (b.bytes && b.out) HIPCHK(p, hipMemcpy(b.out, *b.d, b.bytes, hipMemcpyDeviceToHost));
+    return 0;
+  };
+  const int rc = run();
+  for (const Buf &b : bufs) (void)hipFree(*b.d);
+  return rc;
+}
+
+int qtos_probe_stamp(QtosPlanner *p, const QtosProbe *g, const int *offsets, const int *slot, const int *patch, const int *status,
+                     double *bool_maps) {
+  ProbeArgs A;
+  (void)patch;                                             // (not read: the kernel finds the patches through slot)
+  if (const int rc = probe_args(p, g, "qtos_probe_stamp", offsets && slot && status && bool_maps, 0, &A)) return rc;
+  if (offsets[g->n_maps] < 0) {
+    p->err = "qtos_probe_stamp: offsets[n_maps] < 0";
+    return -2;
+  }
+  HIPCHK(p, hipSetDevice(p->device));
+  const size_t cells = (size_t)g->n_maps * g->rows * g->cols, slots = (size_t)g->n_maps * g->rows * (g->cols / 2 - 1), N = (size_t)offsets[g->n_maps];
+  double *d_bm = nullptr;
+  int *d_off = nullptr, *d_slot = nullptr, *d_status = nullptr;
+  auto run = [&]() -> int {                                // (a word more than slot and status need: an empty array is a pointer still)
+    HIPCHK(p, hipMalloc((void **)&d_off, ((size_t)g->n_maps + 1) * sizeof(int)));
+    HIPCHK(p, hipMalloc((void **)&d_slot, (slots + 1) * sizeof(int)));
+    HIPCHK(p, hipMalloc((void **)&d_status, (N + 1) * sizeof(int)));
+    HIPCHK(p, hipMalloc((void **)&d_bm, cells * sizeof(double)));
+    HIPCHK(p, hipMemcpy(d_off, offsets, ((size_t)g->n_maps + 1) * sizeof(int), hipMemcpyHostToDevice));
+    if (slots) HIPCHK(p, hipMemcpy(d_slot, slot, slots * sizeof(int), hipMemcpyHostToDevice));
+    if (N) HIPCHK(p, hipMemcpy(d_status, status, N * sizeof(int), hipMemcpyHostToDevice));
+    const int rc = qtos_probe_stamp_device(p, g, d_off, d_slot, nullptr, d_status, d_bm, nullptr);
+    if (rc) return rc;
+    HIPCHK(p, hipMemcpy(bool_maps, d_bm, cells * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+  };
+  const int rc = run();
+  (void)hipFree(d_off); (void)hipFree(d_slot); (void)hipFree(d_status); (void)hipFree(d_bm);
   return rc;
 }
 

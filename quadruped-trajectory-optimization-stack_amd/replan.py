@@ -355,22 +355,41 @@ class ShiftedWindows:
 
     def repath(self, robot_goal=None, bool_map=None):
         """Plan every window's path anew from where it stands, self.start[:, 0:2], on the set's stream (PATH_Solver.solve,
-        QTOS/planner.py:422-457): to new robot goals (B x 3) and / or over new boolean maps (the shape given at creation), or
-        the old ones.  The windows' clock starts again at 0 and their done bits are cleared (a window without a path gets bit 2
-        back).  Refused while a replan is pending."""
+        QTOS/planner.py:422-457): to new robot goals (B x 3) and / or over new boolean maps (the shape given at creation; numpy,
+        or a float64 tensor on the set's device, which is copied on the set's stream with no host copy), or the old ones.  A
+        tensor is taken as the work queued on the caller's current stream leaves it (feasibility.feasibility_maps_device's
+        result, say): where that is not the set's stream, the host waits for it once, and the caller may drop the tensor as soon
+        as repath() returns.  The windows' clock starts again at 0 and their done bits are cleared (a window without a path gets
+        bit 2 back).  Refused while a replan is pending."""
         import ctypes as C
         torch = self.torch
         if self.path is None or self._path_plan_params is None:
             raise RuntimeError("repath() needs the device path planner (path=dict(plan=...))")
         if getattr(self, "_pending", False):
             raise RuntimeError("repath() while a replan is pending: poll() it first")
+        made_on = torch.cuda.current_stream(self.dev)        # (where the caller's work stands: a bool_map tensor is made there)
         with torch.cuda.stream(self.stream):
             if robot_goal is not None:
                 rg = np.ascontiguousarray(robot_goal, np.float64)
                 if rg.shape != (self.B, 3):
                     raise ValueError("robot_goal is B x 3")
                 self._path_rg.copy_(torch.from_numpy(rg))
-            if bool_map is not None:
+            if torch.is_tensor(bool_map):
+                # (a tensor on the set's device -- feasibility.feasibility_maps_device's --: copied on the set's stream)
+                maps = bool_map[None] if bool_map.dim() == 2 else bool_map
+                if maps.device != self._plan_maps.device or maps.dtype != self._plan_maps.dtype:
+                    raise ValueError("a bool_map tensor is float64 on the set's device, %s" % (self._plan_maps.device,))
+                if tuple(maps.shape) != tuple(self._plan_maps.shape):
+                    raise ValueError("bool_map has the shape given at creation, %s" % (tuple(self._plan_maps.shape),))
+                if made_on != self.stream:
+                    # the tensor is written by work on the caller's stream and read by the copy on the set's.  A host wait, not
+                    # stream.wait_stream, for the reason __init__ gives: a set's stream that has once waited on the default stream
+                    # no longer ran side by side with the other sets' streams.  record_stream: the allocator keeps the tensor's
+                    # block out of the caller's pool until the copy has run, whatever the caller does with the tensor meanwhile
+                    made_on.synchronize()
+                    maps.record_stream(self.stream)
+                self._plan_maps.copy_(maps)
+            elif bool_map is not None:
                 maps = np.ascontiguousarray(bool_map, np.float64)
                 maps = maps[None] if maps.ndim == 2 else maps
                 if maps.shape != tuple(self._plan_maps.shape):
