@@ -152,6 +152,20 @@ int qtos_analyze_kron(const QtosParams *params, int *n_blocks, int *n_kron, int 
  * 598-605).  n_maps = 0 restores flat ground. */
 int qtos_set_heightfields(QtosPlanner *p, int n_maps, const double *height, int hnx, int hny,
                           double cell, double x0, double y0);
+/* The same from a grid in device memory (d_height: n_maps x hnx x hny doubles, e.g. height_xy of qtos_terrain_env_device):
+ * copied device-to-device into the handle's own buffer by a copy queued on `stream`, no host trip.  The handle's buffer is kept
+ * where the number of doubles stays what it was (no allocation, no device-wide wait: the terrain of a moving scene is set per
+ * step), and replaced otherwise.  Ordering, in both directions, without the caller naming the handle's streams:
+ *   - the copy waits (an event, on the device) for the end of the handle's last call, whichever stream that ran on: its kernels
+ *     may still read the buffer that is kept;
+ *   - every host-pointer entry point (qtos_plan_batch, qtos_probe, qtos_debug_*, ...) runs on the handle's own stream, and that
+ *     stream waits for the copy; qtos_plan_batch_device / qtos_plan_submit on any stream wait for it too.
+ * Only other work of the caller's own that reads d_height's source or the result on a third stream is the caller's to order.
+ * Returns 0; -1 on a null planner, a null d_height with n_maps > 0, hnx or hny < 1, cell not > 0 (the reason in qtos_last_error;
+ * the handle's terrain stays); -5 while a call is open (between qtos_plan_submit and the end of qtos_plan_wait: its kernels read
+ * the terrain); -2 HIP error.  n_maps = 0 restores flat ground (synchronous, as qtos_set_heightfields). */
+int qtos_set_heightfields_device(QtosPlanner *p, int n_maps, const double *d_height, int hnx, int hny,
+                                 double cell, double x0, double y0, void *stream);
 
 /* Optional table of nominal plans for the starting point of cold solves (no reference counterpart: the
  * reference's solver always starts from towr's straight-line guess, and so does this planner
@@ -513,6 +527,56 @@ int qtos_probe_stamp_device(QtosPlanner *p, const QtosProbe *g, const int *d_off
                             const int *d_status, double *d_bool_maps, void *stream);
 int qtos_probe_stamp(QtosPlanner *p, const QtosProbe *g, const int *offsets, const int *slot, const int *patch, const int *status,
                      double *bool_maps);
+
+/* The randomised terrain of n_maps windows, on the device: what qtos_set_heightfields_device, qtos_probe* and qtos_path_goal*
+ * read, made from base grids and one seed per map.  Replaces Height_Map_Generator.__init__ with randomize_env = True
+ * (QTOS/generateHeightField.py:563-567: random_map_shift :648-690, random_height_shift :692-730) and, with n_shift = 1 and
+ * n_height = 0 on the current maps and `draws` carried over, Height_Map_Generator.update() (:584-588).  The reference draws from
+ * python's module-level `random`; map m here owns the stream of random.seed(seed[m]), and the kernel (k_terrain_env, one
+ * workgroup per map) equals the numpy statement of the rule, heightfield.random_env_table, to the bit -- and with it the map the
+ * reference leaves behind random.seed(seed[m]).  Per map, with base = base_yx[base_id[m]] (rows x cols, row = y index):
+ *   stream   MT19937 seeded by init_by_array on the 32-bit words of seed[m], low word first (one word below 2^32, else two), its
+ *            first draws[m] outputs discarded.  random() = ((u >> 5) * 2^26 + (u' >> 6)) / 2^53 from two outputs;
+ *            uniform(a, b) = a + (b - a) * random(), product and sum rounded one by one (no fma); choice among n items: the
+ *            top bit_length(n) bits of an output, redrawn while >= n.
+ *   shifts   n_shift choices of a direction for the solver's copy -- consumed, the reference rebuilds that copy from the map --,
+ *            then n_shift for the map, from (left, right, up, down), or from (up, down) where climb != 0; left / right roll
+ *            the columns by -1 / +1, up / down the rows by -1 / +1, with wrap-around: one net roll.
+ *   heights  n_height passes over the solver's copy (its list of levels alone: only the number of draws matters), then n_height
+ *            over the map.  A pass takes the ascending distinct values != 0 (-0.0 is ground) and per such level h, in order,
+ *            draws d = uniform(-delta, delta) and c = choice(0, 1, 2); the cells that equal h as the map stands at that moment
+ *            get + d (c = 0), - d (c = 1) or nothing.  Levels that meet move as one from then on; one that lands on 0 stays.
+ * Written per map: map_yx[m] rows x cols; height_xy[m] cols x rows (may be NULL), the solver's orientation: height_xy[m][x][y] =
+ * map_yx[m][y][x - 1], row x = 0 zero (heightfield.towr_map); draws[m] (in/out, may be NULL: nothing is discarded, nothing
+ * written) moved on by the outputs consumed; status[m]: 0 ok, 1 more than QTOS_ENV_MAX_LEVELS distinct levels, 2 draws[m]
+ * negative or above QTOS_ENV_MAX_DRAWS on entry, 3 a NaN in the base grid, 4 base_id[m] outside 0 .. n_base - 1 (looked for in
+ * the order 2, 4, 3, 1).  A map with a non-zero status keeps map_yx[m], height_xy[m] and draws[m] as they were. */
+#define QTOS_ENV_MAX_LEVELS 64
+#define QTOS_ENV_MAX_DRAWS (1 << 24)
+#define QTOS_ENV_LDS_BYTES 3568      /* k_terrain_env's LDS: the generator's 624 words, two level lists, a reduction's partials */
+typedef struct QtosTerrainEnv {
+  int n_maps;                  /* 1 .. 16777216                                                                  */
+  int n_base;                  /* base grids (>= 1; without base_id: >= n_maps)                                  */
+  int rows, cols;              /* of every grid (>= 1, rows * cols <= 16777216)                                  */
+  int n_shift;                 /* 0 .. 1048576 (the reference: 10 * mesh_scale; update(): 1)                     */
+  int n_height;                /* 0 .. 1024 (the reference: 10; update(): 0)                                     */
+  int climb;                   /* != 0: directions up / down only (climb_map_check: a climb_1 or climb_2 tile)   */
+  double delta;                /* finite, >= 0 (the reference: 0.005)                                            */
+} QtosTerrainEnv;
+/* Device form: base_yx n_base x rows x cols doubles, base_id n_maps ints (may be NULL: map m reads base m; an entry outside
+ * 0 .. n_base - 1 ends its map with status 4), seed n_maps 64-bit words, draws n_maps ints, map_yx, height_xy, status as above, all in device
+ * memory; one kernel queued on `stream`; no handle state is read or written, and it may be queued while a call is open.  Host
+ * form: host pointers, synchronous, through device buffers of its own (no -5); what the kernel does not write comes back as it
+ * was; a base_id entry outside 0 .. n_base - 1 is an argument error there.
+ * Both: -1 on a null planner; -2 on any other bad argument, with no kernel launched and the reason in qtos_last_error -- a null
+ * `g` or required pointer, n_maps, n_base, rows or cols < 1 or beyond the limits above, n_base < n_maps without base_id,
+ * n_shift or n_height negative or beyond the limits, a delta that is negative, infinite or not a number, an output (draws,
+ * map_yx, height_xy, status) that overlaps any other array of the call -- and on a HIP error; -3 out of memory. */
+int qtos_terrain_env_device(QtosPlanner *p, const QtosTerrainEnv *g, const double *d_base_yx, const int *d_base_id /* may be NULL */,
+                            const unsigned long long *d_seed, int *d_draws /* in/out, may be NULL */, double *d_map_yx,
+                            double *d_height_xy /* may be NULL */, int *d_status, void *stream);
+int qtos_terrain_env(QtosPlanner *p, const QtosTerrainEnv *g, const double *base_yx, const int *base_id, const unsigned long long *seed,
+                     int *draws, double *map_yx, double *height_xy, int *status);
 
 /* The plan as the text file the reference copies out of its container (`docker cp <id>:.../build/traj.csv ./data/traj/towr.csv`,
  * scripts/main.py:90-92; consumers scripts/run.py:129-137, QTOS/combiner.py:263-274): rows is n_rows x 37 (one plan of

@@ -230,6 +230,37 @@ def probe_params(map_yx=None, multi_map_shift=1, scale=1, origin_shift=1.0, cell
     return g
 
 
+class QtosTerrainEnv(C.Structure):
+    """Parameters of a terrain-env call (qtos_terrain_env*, include/qtos_planner.h)."""
+    _fields_ = [
+        ("n_maps", C.c_int), ("n_base", C.c_int), ("rows", C.c_int), ("cols", C.c_int), ("n_shift", C.c_int), ("n_height", C.c_int),
+        ("climb", C.c_int), ("delta", C.c_double),
+    ]
+
+    def copy(self):
+        return QtosTerrainEnv.from_buffer_copy(self)
+
+
+ENV_MAX_LEVELS, ENV_MAX_DRAWS, ENV_LDS_BYTES = 64, 1 << 24, 3568     # QTOS_ENV_* of include/qtos_planner.h
+
+
+def terrain_env_params(base_yx=None, n_maps=None, n_shift=10, n_height=10, climb=False, delta=0.005):
+    """A QtosTerrainEnv with the reference's constants as defaults (n_shift: 10 * mesh_scale there).  base_yx fills the sizes: the
+    base grids (n_base x rows x cols, or rows x cols) or their shape; n_maps: None = one map per base grid."""
+    g = QtosTerrainEnv()
+    g.n_shift, g.n_height, g.climb, g.delta = int(n_shift), int(n_height), int(bool(climb)), float(delta)
+    if base_yx is not None:
+        is_shape = isinstance(base_yx, (tuple, list)) and len(base_yx) in (2, 3) and all(isinstance(v, (int, np.integer)) for v in base_yx)
+        shape = tuple(int(v) for v in (base_yx if is_shape else np.shape(base_yx)))
+        if len(shape) not in (2, 3):
+            raise ValueError("base_yx is n_base x rows x cols or rows x cols, or that shape")
+        g.n_base, g.rows, g.cols = (1,) + shape if len(shape) == 2 else shape
+        g.n_maps = g.n_base
+    if n_maps is not None:
+        g.n_maps = int(n_maps)
+    return g
+
+
 class SelftestError(RuntimeError):
     """No elimination order passed the KKT self-test (qtos_planner_create_checked returned -6); `attempts`: the QtosSelftest
     records in the order they were tried."""
@@ -256,6 +287,7 @@ EXPORTS = [
     "qtos_selftest_problem", "qtos_handover", "qtos_handover_device", "qtos_stitch", "qtos_stitch_device",
     "qtos_path_goal", "qtos_path_goal_device", "qtos_path_plan", "qtos_path_plan_device",
     "qtos_probe", "qtos_probe_device", "qtos_probe_stamp", "qtos_probe_stamp_device",
+    "qtos_terrain_env", "qtos_terrain_env_device", "qtos_set_heightfields_device",
 ]
 
 _lib = None
@@ -372,6 +404,12 @@ def load():
         lib.qtos_probe_device.argtypes = [vp, C.POINTER(QtosProbe), vp, C.c_int] + [vp] * 7
         lib.qtos_probe_stamp.argtypes = [vp, C.POINTER(QtosProbe), ip, ip, ip, ip, dp]
         lib.qtos_probe_stamp_device.argtypes = [vp, C.POINTER(QtosProbe)] + [vp] * 6
+    if hasattr(lib, "qtos_terrain_env"):    # (the terrain-env kernel; older builds loaded through QTOS_LIB lack it)
+        u64p = C.POINTER(C.c_uint64)
+        lib.qtos_terrain_env.argtypes = [vp, C.POINTER(QtosTerrainEnv), dp, ip, u64p, ip, dp, dp, ip]
+        lib.qtos_terrain_env_device.argtypes = [vp, C.POINTER(QtosTerrainEnv)] + [vp] * 8
+    if hasattr(lib, "qtos_set_heightfields_device"):
+        lib.qtos_set_heightfields_device.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, vp]
     _lib = lib
     return lib
 
@@ -909,6 +947,53 @@ class Planner:
         out = np.zeros((g.n_maps, g.rows, g.cols))
         self._chk(self.lib.qtos_probe_stamp(self.h, C.byref(g), _ip(offsets), _ip(slot), _ip(patch), _ip(status), _dp(out)), "probe_stamp")
         return out
+
+    def has_terrain_env(self):
+        return hasattr(self.lib, "qtos_terrain_env")
+
+    def terrain_env(self, base_yx, seed, draws=None, base_id=None, params=None, map_yx=None, height_xy=None):
+        """The randomised terrains of the maps (qtos_terrain_env, host form; the rule: heightfield.random_env_table).  base_yx
+        n_base x rows x cols or rows x cols; seed [n_maps] (0 .. 2**64 - 1); draws [n_maps] outputs already consumed (None: 0);
+        base_id [n_maps] or None (map m reads base m); params: a QtosTerrainEnv (terrain_env_params; the sizes are filled in
+        here); map_yx, height_xy: arrays the call writes into (None: zeros) -- a map with a non-zero status keeps what they
+        hold.  Returns the dict of random_env_table: map_yx, height_xy, draws, status."""
+        if not self.has_terrain_env():
+            raise RuntimeError("this build of the planner library has no terrain-env kernel (qtos_terrain_env)")
+        base = np.ascontiguousarray(base_yx, np.float64)
+        base = base[None] if base.ndim == 2 else base
+        seed = np.ascontiguousarray([int(v) for v in np.ravel(seed)], np.uint64)
+        g = (params or terrain_env_params()).copy()
+        g.n_maps, (g.n_base, g.rows, g.cols) = len(seed), base.shape
+        draws = np.zeros(g.n_maps, np.int32) if draws is None else np.array(draws, np.int32).reshape(g.n_maps)
+        bid = None if base_id is None else np.ascontiguousarray(base_id, np.int32).reshape(g.n_maps)
+        out_m = np.zeros((g.n_maps, g.rows, g.cols)) if map_yx is None else map_yx
+        out_h = np.zeros((g.n_maps, g.cols, g.rows)) if height_xy is None else height_xy
+        for a in (out_m, out_h):
+            if a.dtype != np.float64 or not a.flags.c_contiguous or a.size != g.n_maps * g.rows * g.cols:
+                raise ValueError("map_yx and height_xy are contiguous float64 arrays of n_maps x rows x cols values")
+        status = np.zeros(g.n_maps, np.int32)
+        self._chk(self.lib.qtos_terrain_env(self.h, C.byref(g), _dp(base), _ip(bid), seed.ctypes.data_as(C.POINTER(C.c_uint64)), _ip(draws),
+                                            _dp(out_m), _dp(out_h), _ip(status)), "terrain_env")
+        return dict(map_yx=out_m, height_xy=out_h, draws=draws, status=status)
+
+    def set_heightfields_device(self, height_xy, cell, x0=-1.0, y0=-1.0, stream=None):
+        """set_heightfields from a tensor on the planner's device (n_maps x nx x ny or nx x ny, float64; e.g. height_xy of
+        qtos_terrain_env_device): copied device-to-device on `stream` (a torch stream; None: the current one), no host trip.  A
+        tensor that is not contiguous -- a stack of `heightfield.towr_map` results is not: they are transposes -- is made so
+        on that stream first.  The library orders the copy behind the handle's last call and in front of whatever the handle
+        runs next -- `plan`, `probe`, ... on its own stream, a device-form solve on any stream --, so no synchronisation is
+        needed round this call; RuntimeError (-5) while a call is open."""
+        import torch
+        if not hasattr(self.lib, "qtos_set_heightfields_device"):
+            raise RuntimeError("this build of the planner library has no qtos_set_heightfields_device")
+        t = height_xy[None] if height_xy.dim() == 2 else height_xy
+        if not t.is_cuda or t.device.index != self.device or t.dtype != torch.float64 or t.dim() != 3:
+            raise ValueError("height_xy is a float64 tensor n_maps x nx x ny on the planner's device")
+        stream = torch.cuda.current_stream(t.device) if stream is None else stream
+        with torch.cuda.stream(stream):
+            t = t.contiguous()
+            self._chk(self.lib.qtos_set_heightfields_device(self.h, t.shape[0], t.data_ptr(), t.shape[1], t.shape[2], cell, x0, y0,
+                                                            C.c_void_p(stream.cuda_stream)), "set_heightfields_device")
 
     # ---- optional: nominal-plan table for the starting point of cold solves ----
     def set_init_table(self, dx=None, dy=None, nodes=None):

@@ -2670,4 +2670,266 @@ __global__ __launch_bounds__(64) void k_probe_stamp(ProbeArgs A, const int *offs
   }
 }
 
+// The randomised terrain of the windows (qtos_terrain_env*; Height_Map_Generator.__init__ with randomize_env and update(),
+// QTOS/generateHeightField.py:563-567, 584-588, 648-730): what qtos_set_heightfields_device, k_probe and k_path_goal read, made
+// on the device from base grids and one seed per map.  The statement of the rule is heightfield.random_env_table, and this
+// kernel equals it to the bit.  One workgroup of ENV_T lanes per map.  The stream is python's: MT19937 in LDS, seeded by one
+// lane as random.seed(int) seeds it, regenerated by all lanes (a lane owns word t of each of the three runs [0, 227),
+// [227, 454), [454, 623) whose words depend on the run in front alone, so it needs its own results only; word 623 follows).
+// Every lane reads the same words and draws the same numbers, so the control flow is uniform and the barriers of a
+// regeneration are met by all.  A level is a distinct value != 0 of the grid; the levels come out ascending from repeated
+// min-reductions over the grid, lane j of every wave then keeps level j in a register, and the height passes run on those
+// registers -- the solver copy's passes for their draws alone -- with a wave-wide min per snapshot entry.  The grid is touched
+// again only to be written: each cell finds its level's slot by bisection and takes the slot's value, rolled by the net shift,
+// in both orientations.  No atomics, no scratch, plain vector stores.
+constexpr int ENV_T = 256;
+struct TerrainEnvArgs {   // QtosTerrainEnv as the kernel reads it (qtos_planner.hip terrain_env_args)
+  double delta;
+  int n_maps, n_base, rows, cols, n_shift, n_height, climb;
+};
+struct EnvLds {
+  unsigned mt[624];
+  double level[QTOS_ENV_MAX_LEVELS];   // the base grid's levels, ascending: a cell's slot is the index of its value here
+  double value[QTOS_ENV_MAX_LEVELS];   // what the slots hold behind the map's height passes
+  double red[ENV_T / 64];              // a block-wide reduction's partial minima, and whether a wave found a candidate
+  int found[ENV_T / 64];
+};
+static_assert(sizeof(EnvLds) == QTOS_ENV_LDS_BYTES, "QTOS_ENV_LDS_BYTES (qtos_planner.h) is k_terrain_env's LDS");
+
+__device__ inline unsigned env_mix(unsigned a, unsigned b) {
+  const unsigned y = (a & 0x80000000u) | (b & 0x7fffffffu);
+  return (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
+}
+
+// the next 624 words of the state; called by all lanes of the workgroup
+__device__ inline void env_twist(unsigned *mt, int tid) {
+  unsigned n1 = 0, n2 = 0, n3 = 0;
+  const unsigned last = mt[623];
+  if (tid < 227) {
+    n1 = mt[tid + 397] ^ env_mix(mt[tid], mt[tid + 1]);
+    n2 = n1 ^ env_mix(mt[tid + 227], mt[tid + 228]);
+    if (tid < 169) n3 = n2 ^ env_mix(mt[tid + 454], mt[tid + 455]);
+  }
+  __syncthreads();                     // the old state has been read, by this regeneration and by every wave's draws
+  if (tid < 227) {
+    mt[tid] = n1;
+    mt[tid + 227] = n2;
+    if (tid < 169) mt[tid + 454] = n3;
+  }
+  __syncthreads();
+  if (tid == 0) mt[623] = mt[396] ^ env_mix(last, mt[0]);
+  __syncthreads();
+}
+
+// random.seed(s) for 0 <= s < 2^64 (init_by_array on the seed's 32-bit words, low word first); one lane
+__device__ inline void env_seed(unsigned *mt, unsigned long long s) {
+  const unsigned key[2] = {(unsigned)s, (unsigned)(s >> 32)};
+  const int nk = key[1] ? 2 : 1;
+  unsigned prev = 19650218u;
+  mt[0] = prev;
+  for (int i = 1; i < 624; ++i) {
+    prev = 1812433253u * (prev ^ (prev >> 30)) + (unsigned)i;
+    mt[i] = prev;
+  }
+  int i = 1, j = 0;
+  prev = mt[0];
+  for (int k = 0; k < 624; ++k) {
+    prev = (mt[i] ^ ((prev ^ (prev >> 30)) * 1664525u)) + (j ? key[1] : key[0]) + (unsigned)j;
+    mt[i] = prev;
+    j = j + 1 < nk ? j + 1 : 0;
+    if (++i >= 624) { mt[0] = prev; i = 1; }
+  }
+  for (int k = 0; k < 623; ++k) {
+    prev = (mt[i] ^ ((prev ^ (prev >> 30)) * 1566083941u)) - (unsigned)i;
+    mt[i] = prev;
+    if (++i >= 624) { mt[0] = prev; i = 1; }
+  }
+  mt[0] = 0x80000000u;
+}
+
+struct EnvStream {   // a lane's view of the workgroup's stream: the same in every lane
+  unsigned *mt;
+  int tid, pos, used;
+  __device__ inline unsigned bits32() {
+    if (pos >= 624) {
+      env_twist(mt, tid);
+      pos = 0;
+    }
+    unsigned y = __builtin_amdgcn_readfirstlane(mt[pos]);
+    ++pos; ++used;
+    y ^= y >> 11;
+    y ^= (y << 7) & 0x9d2c5680u;
+    y ^= (y << 15) & 0xefc60000u;
+    return y ^ (y >> 18);
+  }
+  __device__ inline void skip(int n) {                     // whole states are passed over without tempering them
+    while (n > 0) {
+      if (pos >= 624) {
+        env_twist(mt, tid);
+        pos = 0;
+      }
+      const int step = n < 624 - pos ? n : 624 - pos;
+      pos += step;
+      n -= step;
+    }
+  }
+  __device__ inline int below(int n, int k) {              // choice among n items, k = bit_length(n)
+    unsigned r = bits32() >> (32 - k);
+    while (r >= (unsigned)n) r = bits32() >> (32 - k);
+    return (int)r;
+  }
+  __device__ inline double uniform(double a, double w) {   // a + (b - a) * random(), w = b - a: the product and the sum round apart
+#pragma clang fp contract(off)
+    const unsigned hi = bits32() >> 5, lo = bits32() >> 6;
+    const double r = ((double)hi * 67108864.0 + (double)lo) / 9007199254740992.0;
+    const double p = w * r;
+    return a + p;
+  }
+};
+
+__device__ inline double env_wave_min(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double w = __shfl_xor(v, o);
+    v = w < v ? w : v;
+  }
+  return v;
+}
+
+// one pass of random_height over the level values a wave keeps one per lane (v; 0 in the lanes behind the last level)
+__device__ inline void env_level_pass(EnvStream &S, double &v, int lane, double a, double w) {
+#pragma clang fp contract(off)
+  double snap = 0.0, last = 0.0;
+  int n = 0;
+  for (;;) {                                               // the snapshot: entry j, ascending, into lane j
+    const bool cand = v != 0.0 && (n == 0 || v > last);
+    if (!__ballot(cand)) break;
+    last = env_wave_min(cand ? v : __builtin_huge_val());
+    if (lane == n) snap = last;
+    ++n;
+  }
+  for (int j = 0; j < n; ++j) {
+    const double h = __shfl(snap, j);
+    const double d = S.uniform(a, w);
+    const int c = S.below(3, 2);
+    if (v == h) {
+      if (c == 0) v += d;
+      else if (c == 1) v -= d;
+    }
+  }
+}
+
+__global__ __launch_bounds__(ENV_T) void k_terrain_env(TerrainEnvArgs A, const double *base_yx, const int *base_id,
+                                                       const unsigned long long *seed, int *draws, double *map_yx, double *height_xy,
+                                                       int *status) {
+#pragma clang fp contract(off)
+  __shared__ EnvLds L;
+  const int m = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int rows = A.rows, cols = A.cols, cells = rows * cols;
+  const int skip = draws ? draws[m] : 0;
+  if (skip < 0 || skip > QTOS_ENV_MAX_DRAWS) {             // (uniform: every lane read the same word)
+    if (tid == 0) status[m] = 2;
+    return;
+  }
+  const int b = base_id ? base_id[m] : m;
+  if (b < 0 || b >= A.n_base) {                            // (uniform; never outside the base grids, whatever base_id holds)
+    if (tid == 0) status[m] = 4;
+    return;
+  }
+  const double *g = base_yx + (size_t)b * cells;
+
+  // the levels, ascending: a min-reduction over the grid per level; the first one also looks for a NaN
+  int n_levels = 0;
+  double last = 0.0;
+  for (;;) {
+    double best = __builtin_huge_val();
+    bool cand = false, nan = false;
+    for (int ci = tid; ci < cells; ci += ENV_T) {
+      const double v = g[ci];
+      nan = nan || v != v;
+      if (v != 0.0 && (n_levels == 0 || v > last)) {
+        cand = true;
+        best = v < best ? v : best;
+      }
+    }
+    best = env_wave_min(best);
+    const int flags = (__ballot(cand) ? 1 : 0) | (__ballot(nan) ? 2 : 0);
+    __syncthreads();                                       // the partial results of the reduction in front have been read
+    if (lane == 0) {
+      L.red[wave] = best;
+      L.found[wave] = flags;
+    }
+    __syncthreads();
+    int any = 0;
+    best = __builtin_huge_val();
+#pragma unroll
+    for (int k = 0; k < ENV_T / 64; ++k) {
+      any |= L.found[k];
+      best = L.red[k] < best ? L.red[k] : best;
+    }
+    if (any & 2) {                                         // (uniform)
+      if (tid == 0) status[m] = 3;
+      return;
+    }
+    if (!(any & 1)) break;
+    if (n_levels == QTOS_ENV_MAX_LEVELS) {
+      if (tid == 0) status[m] = 1;
+      return;
+    }
+    if (tid == 0) L.level[n_levels] = best;
+    last = best;
+    ++n_levels;
+  }
+  if (tid == 0) env_seed(L.mt, seed[m]);
+  __syncthreads();
+
+  // the draws, the same in every lane: the shifts of the solver's copy (consumed), the map's, then the height passes
+  EnvStream S{L.mt, tid, 624, 0};
+  S.skip(skip);
+  const int n_dir = A.climb ? 2 : 4, k_dir = A.climb ? 2 : 3;
+  for (int i = 0; i < A.n_shift; ++i) (void)S.below(n_dir, k_dir);
+  int dy = 0, dx = 0;
+  for (int i = 0; i < A.n_shift; ++i) {
+    const int d = S.below(n_dir, k_dir) + (A.climb ? 2 : 0);   // left, right, up, down
+    dx += d == 0 ? -1 : (d == 1 ? 1 : 0);
+    dy += d == 2 ? -1 : (d == 3 ? 1 : 0);
+  }
+  const double lo = -A.delta, width = A.delta - lo;
+  const double mine = lane < n_levels ? L.level[lane] : 0.0;
+  double v = mine;
+  for (int i = 0; i < A.n_height; ++i) env_level_pass(S, v, lane, lo, width);
+  v = mine;
+  for (int i = 0; i < A.n_height; ++i) env_level_pass(S, v, lane, lo, width);
+  if (wave == 0 && lane < n_levels) L.value[lane] = v;
+  __syncthreads();
+
+  // the grid, rolled, in both orientations: map_yx[r][c] = moved[r - dy][c - dx] with wrap-around, height_xy[x][y] = map_yx[y][x - 1]
+  const int sy = ((dy % rows) + rows) % rows, sx = ((dx % cols) + cols) % cols;
+  auto moved = [&](int r, int c) -> double {
+    int sr = r - sy, sc = c - sx;
+    sr += sr < 0 ? rows : 0;
+    sc += sc < 0 ? cols : 0;
+    const double h = g[(size_t)sr * cols + sc];
+    if (h == 0.0) return h;                                // (ground keeps its own zero, -0.0 included)
+    int at = 0;
+#pragma unroll
+    for (int step = QTOS_ENV_MAX_LEVELS / 2; step > 0; step >>= 1)
+      if (at + step < n_levels && L.level[at + step] <= h) at += step;
+    return L.value[at];
+  };
+  double *out = map_yx + (size_t)m * cells;
+  for (int ci = tid; ci < cells; ci += ENV_T) out[ci] = moved(ci / cols, ci % cols);
+  if (height_xy) {
+    double *hx = height_xy + (size_t)m * cells;
+    for (int ci = tid; ci < cells; ci += ENV_T) {
+      const int x = ci / rows, y = ci % rows;
+      hx[ci] = x == 0 ? 0.0 : moved(y, x - 1);
+    }
+  }
+  if (tid == 0) {
+    if (draws) draws[m] = skip + S.used;
+    status[m] = 0;
+  }
+}
+
 }  // namespace qtos

@@ -46,6 +46,10 @@ struct QtosPlanner : Analysis {   // (the analysis the planner runs: choose_kern
   double *d_start = nullptr, *d_goal = nullptr, *d_nodes = nullptr, *d_warm = nullptr;
   int *d_map = nullptr;
   double *d_height = nullptr;
+  size_t height_cnt = 0;                                   // doubles of d_height (qtos_set_heightfields_device keeps a buffer of the same size)
+  hipEvent_t ev_height = nullptr;                          // behind the copy of qtos_set_heightfields_device: whoever reads the terrain on another stream waits for it
+  hipStream_t height_stream = nullptr;
+  bool height_pending = false;
   hipStream_t own_stream = nullptr;   // stream of the host-pointer entry points (non-blocking: other handles / streams are not synchronised)
   long long *d_totals = nullptr;      // converged problems, iterations: tallied at the end of every plan call (qtos_plan_totals)
   hipStream_t last_stream = nullptr;
@@ -348,6 +352,7 @@ void qtos_planner_destroy(QtosPlanner *p) {
   if (p->ev_in) (void)hipEventDestroy(p->ev_in);
   for (void *q : {(void *)p->d_table, (void *)p->d_tab_dx, (void *)p->d_tab_dy, (void *)p->d_height})
     if (q) (void)hipFree(q);
+  if (p->ev_height) (void)hipEventDestroy(p->ev_height);
   if (p->own_stream) (void)hipStreamDestroy(p->own_stream);
   if (p->d_totals) (void)hipFree(p->d_totals);
   delete p;
@@ -918,6 +923,8 @@ int qtos_set_heightfields(QtosPlanner *p, int n_maps, const double *height, int 
     (void)hipFree(p->d_height);
     p->d_height = nullptr;
   }
+  p->height_cnt = 0;
+  p->height_pending = false;                               // (hipFree waited for the device: a copy into the old buffer is over)
   p->dp.height = nullptr;
   p->dp.n_maps = 0;
   if (n_maps <= 0 || !height) return 0;
@@ -925,6 +932,47 @@ int qtos_set_heightfields(QtosPlanner *p, int n_maps, const double *height, int 
   const size_t cnt = (size_t)n_maps * hnx * hny;
   HIPCHK(p, hipMalloc((void **)&p->d_height, cnt * sizeof(double)));
   HIPCHK(p, hipMemcpy(p->d_height, height, cnt * sizeof(double), hipMemcpyHostToDevice));
+  p->height_cnt = cnt;
+  p->dp.height = p->d_height;
+  p->dp.n_maps = n_maps; p->dp.hnx = hnx; p->dp.hny = hny;
+  p->dp.hcell = cell; p->dp.hx0 = x0; p->dp.hy0 = y0;
+  return 0;
+}
+
+// The terrain from device memory.  Both directions are ordered here, since the caller cannot name the handle's streams: the copy
+// waits for the end of the handle's last call (which may still read a kept buffer), and the handle's own stream -- every
+// host-pointer entry point runs there -- waits for the copy; a solve submitted on a third stream waits in qtos_plan_batch_device.
+int qtos_set_heightfields_device(QtosPlanner *p, int n_maps, const double *d_height, int hnx, int hny,
+                                 double cell, double x0, double y0, void *stream) {
+  if (!p) return -1;
+  if (p->call_open || p->busy.load()) { p->err = "qtos_set_heightfields_device: a call is open (its kernels read the terrain)"; return -5; }
+  if (n_maps <= 0) return qtos_set_heightfields(p, 0, nullptr, 0, 0, 1.0, 0.0, 0.0);
+  if (!d_height || hnx < 1 || hny < 1 || !(cell > 0)) {
+    p->err = "qtos_set_heightfields_device: d_height is not null, hnx and hny are >= 1, cell is > 0";
+    return -1;
+  }
+  HIPCHK(p, hipSetDevice(p->device));
+  hipStream_t st = (hipStream_t)stream;
+  const size_t cnt = (size_t)n_maps * hnx * hny;
+  if (!p->d_height || p->height_cnt != cnt) {              // (a buffer of the same size is written again: no device-wide wait)
+    if (p->d_height) (void)hipFree(p->d_height);
+    p->d_height = nullptr;
+    p->dp.height = nullptr;
+    p->dp.n_maps = 0;
+    p->height_cnt = 0;
+    p->height_pending = false;
+    HIPCHK(p, hipMalloc((void **)&p->d_height, cnt * sizeof(double)));
+    p->height_cnt = cnt;
+  }
+  if (!p->ev_height) HIPCHK(p, hipEventCreateWithFlags(&p->ev_height, hipEventDisableTiming));
+  // the last call's kernels, and whatever the host forms queued, are through with the buffer before it is written
+  if (p->seq && p->last_stream != st) HIPCHK(p, hipStreamWaitEvent(st, p->lanes[0].ev[1], 0));
+  if (p->height_pending && p->height_stream != st) HIPCHK(p, hipStreamWaitEvent(st, p->ev_height, 0));   // (an earlier copy into the same buffer)
+  HIPCHK(p, hipMemcpyAsync(p->d_height, d_height, cnt * sizeof(double), hipMemcpyDeviceToDevice, st));
+  HIPCHK(p, hipEventRecord(p->ev_height, st));
+  if (st != p->own_stream) HIPCHK(p, hipStreamWaitEvent(p->own_stream, p->ev_height, 0));
+  p->height_stream = st;
+  p->height_pending = true;
   p->dp.height = p->d_height;
   p->dp.n_maps = n_maps; p->dp.hnx = hnx; p->dp.hny = hny;
   p->dp.hcell = cell; p->dp.hx0 = x0; p->dp.hy0 = y0;
@@ -1024,6 +1072,10 @@ int qtos_plan_submit(QtosPlanner *p, int B, const double *d_start, const double 
   auto fail = [&](int rc) { p->call_open = false; for (auto &L : p->lanes) L.open = false; p->busy.store(0); return rc; };
   hipStream_t st = (hipStream_t)stream_;
   if (hipSetDevice(p->device) != hipSuccess) return fail(-2);
+  if (p->height_pending) {                                 // a terrain copied in on another stream (qtos_set_heightfields_device)
+    if (hipEventQuery(p->ev_height) == hipSuccess) p->height_pending = false;
+    else if (st != p->height_stream && st != p->own_stream && hipStreamWaitEvent(st, p->ev_height, 0) != hipSuccess) return fail(-2);
+  }
   p->call_open = true;
   p->call_stream = st;
   // 16 bits of sequence number in the count word (0xffff = the reset pattern of the slots): the number wraps after 65 534 calls
@@ -1942,6 +1994,97 @@ int qtos_probe_stamp(QtosPlanner *p, const QtosProbe *g, const int *offsets, con
   };
   const int rc = run();
   (void)hipFree(d_off); (void)hipFree(d_slot); (void)hipFree(d_status); (void)hipFree(d_bm);
+  return rc;
+}
+
+// ---- the randomised terrain of the windows (k_terrain_env, kernels.hpp) -----------------------------------
+static constexpr int ENV_CELLS = 1 << 24, ENV_SHIFTS = 1 << 20, ENV_PASSES = 1 << 10;
+static int terrain_env_args(QtosPlanner *p, const QtosTerrainEnv *g, const double *base, const int *base_id, const unsigned long long *seed,
+                            const int *draws, const double *map_yx, const double *height_xy, const int *status, TerrainEnvArgs *A) {
+  if (!p) return -1;
+  const char *why = nullptr;
+  if (!g || !base || !seed || !map_yx || !status) why = "a required pointer is null";
+  else if (g->n_maps < 1 || g->n_maps > PROBE_MAPS) why = "n_maps is 1 .. 16777216";
+  else if (g->n_base < 1) why = "n_base >= 1";
+  else if (!base_id && g->n_base < g->n_maps) why = "without base_id map m reads base m: n_base >= n_maps";
+  else if (g->rows < 1 || g->cols < 1 || (long long)g->rows * g->cols > ENV_CELLS) why = "rows >= 1, cols >= 1 and rows * cols <= 16777216";
+  else if (g->n_shift < 0 || g->n_shift > ENV_SHIFTS) why = "n_shift is 0 .. 1048576";
+  else if (g->n_height < 0 || g->n_height > ENV_PASSES) why = "n_height is 0 .. 1024";
+  else if (!(g->delta >= 0) || !(g->delta <= 1.7976931348623157e308)) why = "delta is a finite number >= 0";
+  if (!why) {                                              // the workgroups read and write side by side: no output may lie over another array
+    const size_t n = (size_t)g->n_maps, grid = n * g->rows * g->cols * sizeof(double);
+    struct Span { const char *lo; size_t bytes; bool out; };
+    const Span spans[] = {
+        {(const char *)base, (size_t)g->n_base * g->rows * g->cols * sizeof(double), false}, {(const char *)base_id, n * sizeof(int), false},
+        {(const char *)seed, n * sizeof(unsigned long long), false}, {(const char *)draws, n * sizeof(int), true},
+        {(const char *)map_yx, grid, true}, {(const char *)height_xy, grid, true}, {(const char *)status, n * sizeof(int), true}};
+    for (const Span &a : spans)
+      for (const Span &b : spans)
+        if (&a < &b && (a.out || b.out) && a.lo && b.lo && a.lo < b.lo + b.bytes && b.lo < a.lo + a.bytes)
+          why = "an output (draws, map_yx, height_xy, status) overlaps another array of the call";
+  }
+  if (why) {
+    p->err = std::string("qtos_terrain_env: ") + why;
+    return -2;
+  }
+  A->delta = g->delta;
+  A->n_maps = g->n_maps; A->n_base = g->n_base; A->rows = g->rows; A->cols = g->cols;
+  A->n_shift = g->n_shift; A->n_height = g->n_height; A->climb = g->climb != 0;
+  return 0;
+}
+
+int qtos_terrain_env_device(QtosPlanner *p, const QtosTerrainEnv *g, const double *d_base_yx, const int *d_base_id,
+                            const unsigned long long *d_seed, int *d_draws, double *d_map_yx, double *d_height_xy, int *d_status,
+                            void *stream_) {
+  TerrainEnvArgs A;
+  if (const int rc = terrain_env_args(p, g, d_base_yx, d_base_id, d_seed, d_draws, d_map_yx, d_height_xy, d_status, &A)) return rc;
+  HIPCHK(p, hipSetDevice(p->device));
+  hipLaunchKernelGGL(k_terrain_env, dim3(A.n_maps), dim3(ENV_T), 0, (hipStream_t)stream_, A, d_base_yx, d_base_id, d_seed, d_draws, d_map_yx,
+                     d_height_xy, d_status);
+  HIPCHK(p, hipGetLastError());
+  return 0;
+}
+
+int qtos_terrain_env(QtosPlanner *p, const QtosTerrainEnv *g, const double *base_yx, const int *base_id, const unsigned long long *seed,
+                     int *draws, double *map_yx, double *height_xy, int *status) {
+  TerrainEnvArgs A;
+  if (const int rc = terrain_env_args(p, g, base_yx, base_id, seed, draws, map_yx, height_xy, status, &A)) return rc;
+  if (base_id)
+    for (int m = 0; m < g->n_maps; ++m)
+      if (base_id[m] < 0 || base_id[m] >= g->n_base) {
+        p->err = "qtos_terrain_env: base_id is 0 .. n_base - 1";
+        return -2;
+      }
+  HIPCHK(p, hipSetDevice(p->device));
+  // buffers of its own, as qtos_probe.  The outputs are copied in first: a map with a non-zero status comes back as it was
+  const size_t cells = (size_t)g->rows * g->cols, n = (size_t)g->n_maps;
+  struct Buf { void **d; const void *in; void *out; size_t bytes; };
+  double *d_base = nullptr, *d_map = nullptr, *d_hxy = nullptr;
+  unsigned long long *d_seed = nullptr;
+  int *d_bid = nullptr, *d_draws = nullptr, *d_status = nullptr;
+  const Buf bufs[] = {
+      {(void **)&d_base, base_yx, nullptr, (size_t)g->n_base * cells * sizeof(double)},
+      {(void **)&d_bid, base_id, nullptr, base_id ? n * sizeof(int) : 0},
+      {(void **)&d_seed, seed, nullptr, n * sizeof(unsigned long long)},
+      {(void **)&d_draws, draws, draws, draws ? n * sizeof(int) : 0},
+      {(void **)&d_map, map_yx, map_yx, n * cells * sizeof(double)},
+      {(void **)&d_hxy, height_xy, height_xy, height_xy ? n * cells * sizeof(double) : 0},
+      {(void **)&d_status, status, status, n * sizeof(int)},
+  };
+  auto run = [&]() -> int {
+    for (const Buf &b : bufs) {
+      if (!b.bytes) continue;                              // (an optional array that was not given stays a null pointer)
+      HIPCHK(p, hipMalloc(b.d, b.bytes));
+      HIPCHK(p, hipMemcpy(*b.d, b.in, b.bytes, hipMemcpyHostToDevice));
+    }
+    const int rc = qtos_terrain_env_device(p, g, d_base, d_bid, d_seed, d_draws, d_map, d_hxy, d_status, nullptr);
+    if (rc) return rc;
+    for (const Buf &b : bufs)
+      if (b.bytes && b.out) HIPCHK(p, hipMemcpy(b.out, *b.d, b.bytes, hipMemcpyDeviceToHost));
+    return 0;
+  };
+  const int rc = run();
+  for (const Buf &b : bufs) (void)hipFree(*b.d);
   return rc;
 }
 

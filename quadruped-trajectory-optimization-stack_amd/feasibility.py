@@ -281,3 +281,51 @@ def feasibility_maps_device(planner, maps_yx, multi_map_shift=1, scale=1, stream
         chk(P.lib.qtos_probe_stamp_device(P.h, C.byref(g), ptr(offsets), ptr(slot), ptr(patch), ptr(status), ptr(bool_maps), sp),
             "qtos_probe_stamp_device")
     return bool_maps, offsets, patch[:N], status[:N]
+
+
+def random_env_device(planner, base_yx, seeds, base_id=None, draws=None, n_shift=10, n_height=10, climb=False, delta=0.005, cell=None,
+                      stream=None):
+    """The reference's randomised terrains (``heightfield.random_env``) of n_maps windows without a host loop: k_terrain_env
+    makes map m from base grid ``base_id[m]`` (None: base m) and the stream of ``random.seed(seeds[m])``, in both orientations,
+    and the solver's one becomes the handle's terrain through ``set_heightfields_device`` -- map m of the call is heightfield m
+    of the handle, as ``feasibility_maps_device`` expects.  planner: a ``capi.Planner``; base_yx: n_base x rows x cols or
+    rows x cols, numpy or a tensor on the planner's device; seeds: n_maps ints (0 .. 2**63 - 1 as a tensor, 0 .. 2**64 - 1
+    otherwise); draws: None, or an int32 device tensor [n_maps] of the outputs each stream has consumed, moved on in place
+    (``n_shift=1, n_height=0`` on the current maps is the reference's ``update()``); cell: of the heightfields (None: 2 / rows,
+    the reference's).  Returns (map_yx [n_maps, rows, cols] float64, status [n_maps] int32), device tensors; the heightfields
+    are installed whatever the statuses are, and a map with a non-zero status is flat ground (``heightfield.random_env_table``
+    names the statuses: 1 too many levels, 2 draws, 3 a NaN, 4 base_id)."""
+    import ctypes as C
+
+    import torch
+
+    from . import capi
+    P = planner
+    if not P.has_terrain_env():
+        raise RuntimeError("this build of the planner library has no terrain-env kernel (qtos_terrain_env_device)")
+    dev = torch.device("cuda", P.device)
+    stream = torch.cuda.current_stream(dev) if stream is None else stream
+    sp = C.c_void_p(stream.cuda_stream)
+    f64, i32 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.int32, device=dev)
+    with torch.cuda.stream(stream):
+        base = torch.as_tensor(base_yx, **f64)
+        base = (base[None] if base.dim() == 2 else base).contiguous()
+        if torch.is_tensor(seeds):
+            seed = seeds.to(device=dev, dtype=torch.int64).contiguous()
+        else:
+            seed = torch.as_tensor(np.array([int(v) for v in np.ravel(seeds)], np.uint64).view(np.int64), device=dev)
+        n_maps, (n_base, rows, cols) = seed.numel(), base.shape
+        bid = None if base_id is None else torch.as_tensor(base_id, **i32).contiguous()
+        if draws is not None and (not torch.is_tensor(draws) or draws.dtype != torch.int32 or draws.device != dev or draws.numel() != n_maps
+                                  or not draws.is_contiguous()):
+            raise ValueError("draws is a contiguous int32 tensor [n_maps] on the planner's device (it is moved on in place)")
+        g = capi.terrain_env_params((n_base, rows, cols), n_maps, n_shift, n_height, climb, delta)
+        map_yx, height_xy = torch.zeros((n_maps, rows, cols), **f64), torch.zeros((n_maps, cols, rows), **f64)
+        status = torch.zeros((n_maps,), **i32)
+        rc = P.lib.qtos_terrain_env_device(P.h, C.byref(g), base.data_ptr(), None if bid is None else bid.data_ptr(), seed.data_ptr(),
+                                           None if draws is None else draws.data_ptr(), map_yx.data_ptr(), height_xy.data_ptr(),
+                                           status.data_ptr(), sp)
+        if rc != 0:
+            raise RuntimeError("qtos_terrain_env_device failed (%d): %s" % (rc, P.lib.qtos_last_error(P.h).decode()))
+        P.set_heightfields_device(height_xy, 2.0 / rows if cell is None else cell, stream=stream)
+    return map_yx, status

@@ -124,6 +124,19 @@ def random_terrains(n_maps=8, seed=4, mesh_scale=11, shift=10):
     return np.stack(maps), heightfield.cell_size(base)
 
 
+def random_env_terrains(n_maps=8, seed=4, tiles=("climb_2", "climb_1"), mesh_scale=1):
+    """Randomised terrains as the reference's `randomize_env` makes them (QTOS/generateHeightField.py:563-567): the tiles' map
+    shifted 10 * mesh_scale times and its height levels jittered by 10 passes, map m on the stream of `random.seed(seed + m)`,
+    the directions up / down alone where a climb tile is among them.  The host counterpart of `feasibility.random_env_device`
+    (the same seeds give the same bits).  Returns (map_yx[n_maps][rows][cols], height_xy[n_maps][cols][rows] in the solver's
+    orientation, cell)."""
+    import random
+    base = heightfield.build_map([tile(t) for t in tiles], mesh_scale)
+    climb = any(t in ("climb_1", "climb_2") for t in tiles)
+    maps = [heightfield.random_env(base, random.Random(seed + m), 10 * mesh_scale, 10, climb) for m in range(n_maps)]
+    return np.stack(maps), np.stack([heightfield.towr_map(m) for m in maps]), heightfield.cell_size(base)
+
+
 def mpc_goals(batch, seed=5, terrains=None, mode=1):
     """configs[4]: long-horizon goals (0.45-0.7 m ahead over the 10 s / two-cycle horizon: up the
     randomized ledges) from start stances at x in [0, 0.2] standing on the surface of their map, each
