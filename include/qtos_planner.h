@@ -355,6 +355,59 @@ int qtos_stitch_device(QtosPlanner *p, int B, const QtosStitch *s, const double 
 int qtos_stitch(QtosPlanner *p, int B, const QtosStitch *s, const double *nodes, const int *n_rows,
                 double *t0, double *traj, long long *cursor);
 
+/* Joint commands of the windows' plans: leg inverse kinematics and the motor law, per CSV row.  Replaces what the reference's
+ * consumer does once per 1 kHz tick (scripts/run.py:184-200, QTOS/robot/robot.py control_multi: towr_transform, inverse
+ * kinematics per leg, MotorModel.convert_to_torque_ff) for B windows at once (k_joint_rows; the rule: joints.py).  Joint row k
+ * of a plan has 37 columns: the time stamp of CSV row k (t0 + k / hz, qtos_sample_csv's to the bit), then for the legs FL, FR,
+ * HL, HR and their joints HAA, HFE, KFE the angles q (columns 1 .. 12), the rates qdot (13 .. 24) and the torques (25 .. 36), at
+ * the plan time min(k / hz, T) of CSV row k:
+ *   p_b = R(euler)^T (foot - com) + (0, 0, ee_shift), R = Rz(yaw) Ry(pitch) Rx(roll); v_b its time derivative from the plan's
+ *         CoM velocity, Euler rates and the foot spline's first derivative
+ *   r = p_b - hip, h^2 = r_y^2 + r_z^2 - lateral^2, c3 = (r_x^2 + h^2 - l_u^2 - l_l^2) / (2 l_u l_l)
+ *   q1 = atan2(r_y h + r_z lateral, r_y lateral - r_z h), q3 = knee_sign acos(clip(c3, -1, 1)),
+ *   q2 = atan2(-r_x, h) - atan2(l_l sin q3, l_u + l_l cos q3)
+ *   qdot = J^-1 v_b (closed 3 x 3 solve), tau_ff = -J^T R^T f with f the plan's foot force (0 with flags bit 0)
+ *   tau = clip(kp (q - q_mes) + kd (qdot - qd_mes) + tau_ff, -tau_max, tau_max); without q_mes the PD terms are left out,
+ *         tau_max <= 0: no clip
+ * and a status word: bit e the target of foot e is beyond the leg's reach (c3 > 1: the leg is straight and points at it), bit
+ * 4 + e inside its folded length (c3 < -1), bit 8 + e nearer to the hip axis than the lateral offset (h^2 < 0, h taken as 0).  A
+ * leg with a status bit has qdot = 0.
+ * Two addressing modes.  capacity 0 (table): out is B x n_rows x 37, status B x n_rows, and out[b][j] is joint row first + j,
+ * j = 0 .. n - 1, with first = d_first_row ? d_first_row[b] : first_row and n = d_n_rows ? d_n_rows[b] : n_rows clamped to
+ * 0 .. n_rows; rows behind n are not touched.  With n_rows = 1, d_first_row and the measured state that is the 1 kHz tick of B
+ * robots in one launch.  capacity > 0 (ring): out is B x capacity x 37, status B x capacity, and joint row first + j goes to ring
+ * row (cursor[b] + j) mod capacity, n clamped to 0 .. capacity: qtos_stitch's addressing, but cursor and t0 are only read -- queued
+ * in front of qtos_stitch_device on the same stream with the same nodes, n_rows, t0 and cursor, it fills a joint ring row for
+ * row with the CSV ring. */
+#define QTOS_JOINT_NO_FF 1      /* flags: leave the feed-forward torque out (MotorModel.convert_to_torque) */
+typedef struct QtosJointRows {
+  double hz;                    /* rows per second (<= 0: 1000) */
+  int first_row;                /* first row where d_first_row is NULL; 0 .. 1000000 */
+  int n_rows;                   /* table mode: rows per window in `out`; both modes: the count where d_n_rows is NULL (>= 0) */
+  long long capacity;           /* 0: table mode; > 0: rows per window in the ring */
+  double ee_shift;              /* towr_transform's lift of the feet in the base frame */
+  double hip[4][3];             /* HAA origins in the base frame */
+  double lateral[4];            /* y offset of the foot from the HAA axis in the hip frame */
+  double l_upper, l_lower;      /* link lengths (> 0) */
+  double knee_sign[4];          /* branch of the knee: -1 / +1 */
+  double kp[12], kd[12];        /* per joint (MotorModel.UPDATE_GAIT) */
+  double tau_max;               /* <= 0: no clip */
+  int flags;                    /* QTOS_JOINT_* */
+} QtosJointRows;
+/* nodes B x n_vars, t0 B; first_row B, n_rows B, q_mes and qd_mes B x 12 (both or neither) may be NULL; cursor B, NULL in table
+ * mode; out and status as above.
+ * Device form: all pointers but `s` in device memory, one kernel queued on `stream`, no handle state is read or written but the
+ * sampling tables -- it may be queued while a call is open.  Host form: host pointers, synchronous, through device buffers of
+ * its own as qtos_stitch (no -5); out and status are copied in and out whole.
+ * Both: -1 on a null planner or required pointer, B < 1, capacity < 0, a ring without cursor, a table with n_rows < 1, n_rows < 0,
+ * first_row outside 0 .. 1000000, q_mes without qd_mes or the reverse, a link length <= 0; -2 on a HIP error. */
+int qtos_joint_rows_device(QtosPlanner *p, int B, const QtosJointRows *s, const double *d_nodes, const double *d_t0,
+                           const int *d_first_row /* may be NULL */, const int *d_n_rows /* may be NULL */,
+                           const long long *d_cursor /* NULL in table mode */, const double *d_q_mes /* may be NULL */,
+                           const double *d_qd_mes /* NULL iff d_q_mes is NULL */, double *d_out, int *d_status, void *stream);
+int qtos_joint_rows(QtosPlanner *p, int B, const QtosJointRows *s, const double *nodes, const double *t0, const int *first_row,
+                    const int *n_rows, const long long *cursor, const double *q_mes, const double *qd_mes, double *out, int *status);
+
 /* Goals of receding windows from their global paths: where the next plan goes.  Replaces Global_Planner.update / spine_step
  * (QTOS/planner.py:139-161, 195-230) and Combiner.plan_init / spine_step (QTOS/combiner.py:137-212, 223-225) for B windows at
  * once: a window's A* "spine" -- two cubic splines X_p, Y_p over one set of knots -- is read one horizon ahead of the new plan's

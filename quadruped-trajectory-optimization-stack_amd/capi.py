@@ -261,6 +261,41 @@ def terrain_env_params(base_yx=None, n_maps=None, n_shift=10, n_height=10, climb
     return g
 
 
+class QtosJointRows(C.Structure):
+    """Parameters of a joint-rows call (qtos_joint_rows*, include/qtos_planner.h); joints.joint_rows reads the same fields."""
+    _fields_ = [
+        ("hz", C.c_double), ("first_row", C.c_int), ("n_rows", C.c_int), ("capacity", C.c_longlong), ("ee_shift", C.c_double),
+        ("hip", (C.c_double * 3) * 4), ("lateral", C.c_double * 4), ("l_upper", C.c_double), ("l_lower", C.c_double),
+        ("knee_sign", C.c_double * 4), ("kp", C.c_double * 12), ("kd", C.c_double * 12), ("tau_max", C.c_double), ("flags", C.c_int),
+    ]
+
+    def copy(self):
+        return QtosJointRows.from_buffer_copy(self)
+
+
+JOINT_NO_FF = 1     # QTOS_JOINT_NO_FF of include/qtos_planner.h
+
+
+def joint_params(hz=1000.0, first_row=0, n_rows=0, capacity=0, ee_shift=0.015, kp=20.0, kd=0.08, hip_scale=1.0, knee_scale=1.0,
+                 ankle_scale=1.0, tau_max=8.0, feed_forward=True, robot=None):
+    """A QtosJointRows with the SOLO12 leg (joints.SOLO12), towr_transform's ee_shift and the gains of the reference's
+    data/config/solo12.yml (kp 20, kd 0.08, scales 1, t_max 8) as defaults.  capacity 0: table mode."""
+    from . import joints
+    robot = joints.SOLO12 if robot is None else robot
+    g = QtosJointRows()
+    g.hz, g.first_row, g.n_rows, g.capacity, g.ee_shift = float(hz), int(first_row), int(n_rows), int(capacity), float(ee_shift)
+    for e in range(4):
+        for d in range(3):
+            g.hip[e][d] = float(robot.hip[e][d])
+        g.lateral[e], g.knee_sign[e] = float(robot.lateral[e]), float(robot.knee_sign[e])
+    g.l_upper, g.l_lower = float(robot.l_upper), float(robot.l_lower)
+    for j, (a, b) in enumerate(zip(*joints.motor_gains(kp, kd, hip_scale, knee_scale, ankle_scale))):
+        g.kp[j], g.kd[j] = float(a), float(b)
+    g.tau_max = float(tau_max)
+    g.flags = 0 if feed_forward else JOINT_NO_FF
+    return g
+
+
 class SelftestError(RuntimeError):
     """No elimination order passed the KKT self-test (qtos_planner_create_checked returned -6); `attempts`: the QtosSelftest
     records in the order they were tried."""
@@ -288,6 +323,7 @@ EXPORTS = [
     "qtos_path_goal", "qtos_path_goal_device", "qtos_path_plan", "qtos_path_plan_device",
     "qtos_probe", "qtos_probe_device", "qtos_probe_stamp", "qtos_probe_stamp_device",
     "qtos_terrain_env", "qtos_terrain_env_device", "qtos_set_heightfields_device",
+    "qtos_joint_rows", "qtos_joint_rows_device",
 ]
 
 _lib = None
@@ -408,6 +444,10 @@ def load():
         u64p = C.POINTER(C.c_uint64)
         lib.qtos_terrain_env.argtypes = [vp, C.POINTER(QtosTerrainEnv), dp, ip, u64p, ip, dp, dp, ip]
         lib.qtos_terrain_env_device.argtypes = [vp, C.POINTER(QtosTerrainEnv)] + [vp] * 8
+    if hasattr(lib, "qtos_joint_rows"):     # (the joint-rows kernel; older builds loaded through QTOS_LIB lack it)
+        llp = C.POINTER(C.c_longlong)
+        lib.qtos_joint_rows.argtypes = [vp, C.c_int, C.POINTER(QtosJointRows), dp, dp, ip, ip, llp, dp, dp, dp, ip]
+        lib.qtos_joint_rows_device.argtypes = [vp, C.c_int, C.POINTER(QtosJointRows)] + [vp] * 10
     if hasattr(lib, "qtos_set_heightfields_device"):
         lib.qtos_set_heightfields_device.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, vp]
     _lib = lib
@@ -826,6 +866,43 @@ class Planner:
         self._chk(self.lib.qtos_stitch(self.h, B, C.byref(s), _dp(nodes), _ip(per), _dp(t0), _dp(traj),
                                        cursor.ctypes.data_as(C.POINTER(C.c_longlong))), "stitch")
         return traj, cursor, t0
+
+    def has_joint_rows(self):
+        return hasattr(self.lib, "qtos_joint_rows")
+
+    def joint_rows(self, nodes, t0, params=None, first_row=None, n_rows=None, q_mes=None, qd_mes=None, out=None, status=None,
+                   cursor=None):
+        """Joint rows of every plan in `nodes` (qtos_joint_rows, host form; the rule: joints.joint_rows): 37 columns -- the time
+        stamp of the CSV row, q, qdot and tau of the twelve joints -- and an int32 status per row.  params: a QtosJointRows
+        (joint_params(); the default: the SOLO12 values at 1 kHz, the whole plan).  Table mode (params.capacity 0): returns
+        (rows [B, params.n_rows, 37], status [B, params.n_rows]); row j of window b is joint row first + j, first = first_row[b]
+        (an array) or params.first_row.  n_rows (an array) gives every window its own count.  With params.n_rows = 1, first_row
+        and the measured q_mes, qd_mes (B x 12) that is one tick of B robots.  Ring mode (params.capacity > 0): `out`
+        (B x capacity x 37), `status` (B x capacity) and `cursor` (B) are the rings as they stand; returns new arrays."""
+        if not self.has_joint_rows():
+            raise RuntimeError("this build of the planner library has no joint-rows kernel (qtos_joint_rows)")
+        nodes = np.ascontiguousarray(nodes, np.float64).reshape(-1, self.n)
+        B = nodes.shape[0]
+        t0 = np.ascontiguousarray(np.broadcast_to(np.asarray(t0, np.float64), (B,)))
+        if params is None:
+            params = joint_params(n_rows=int(round(self.dims.duration * 1000.0)) + 1)
+        i32 = lambda a: None if a is None else np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.int32), (B,)))
+        f12 = lambda a: None if a is None else np.ascontiguousarray(a, np.float64).reshape(B, 12)
+        first, per, qm, qdm = i32(first_row), i32(n_rows), f12(q_mes), f12(qd_mes)
+        rows = int(params.capacity) if params.capacity > 0 else int(params.n_rows)
+        cur = None
+        if params.capacity > 0:
+            if out is None or status is None or cursor is None:
+                raise ValueError("ring mode takes the rings as they stand: out, status and cursor")
+            cur = np.ascontiguousarray(np.broadcast_to(np.asarray(cursor, np.int64), (B,)))
+        out = np.zeros((B, max(rows, 0), CSV_COLS)) if out is None else np.array(out, np.float64)
+        status = np.zeros((B, max(rows, 0)), np.int32) if status is None else np.array(status, np.int32)
+        if out.shape != (B, rows, CSV_COLS) or status.shape != (B, rows):
+            raise ValueError("out is (B, %d, %d) and status (B, %d)" % (rows, CSV_COLS, rows))
+        self._chk(self.lib.qtos_joint_rows(self.h, B, C.byref(params), _dp(nodes), _dp(t0), _ip(first), _ip(per),
+                                           None if cur is None else cur.ctypes.data_as(C.POINTER(C.c_longlong)), _dp(qm), _dp(qdm),
+                                           _dp(out), _ip(status)), "joint_rows")
+        return out, status
 
     def has_path_goal(self):
         return hasattr(self.lib, "qtos_path_goal")

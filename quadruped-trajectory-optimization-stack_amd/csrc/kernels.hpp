@@ -2125,6 +2125,168 @@ __global__ __launch_bounds__(STITCH_TILE) void k_stitch(const SamplePlan *Sd, St
   }
 }
 
+// Joint commands of the windows' plans (qtos_joint_rows*; scripts/run.py:184-200, QTOS/robot/robot.py control_multi): per CSV row
+// the feet in the base frame of the planned pose (towr_transform, QTOS/utils.py:412-436), the closed-form inverse kinematics
+// of the SOLO12 leg (HAA about x, HFE and KFE about y; the reference asks PyBullet), the joint rates qdot = J^-1 v_b, the
+// feed-forward torques -J^T R^T f and the motor law (MotorModel.convert_to_torque_ff).  The statement of the rule, with its
+// derivation, is joints.py.  A lane evaluates one row: its time stamp and Cartesian state with k_sample's evaluator
+// (sample_row_state_at and the line for the forces: qtos_sample_csv's numbers to the bit), the four foot splines once more
+// with deriv = 1, then the chain for four legs, written into the row's place in an LDS tile as it is computed; the tile goes
+// out flat, consecutive lanes on consecutive doubles, as k_stitch's (whose pitch of 37 doubles it keeps).  The tile has one
+// row per lane of the workgroup: 512, or one wave where no window has more rows than that (the 1 kHz tick).
+// Two addressing modes: capacity 0, row first_row + j of window b goes to out[b][j] of a B x n_rows x 37 table; capacity > 0, to
+// ring row (cursor[b] + j) mod capacity of a B x capacity x 37 ring -- k_stitch's addressing, but cursor and t0 are only read,
+// so the grid runs over tiles and windows in both modes, and in front of k_stitch on one stream the joint ring is filled row
+// for row with the CSV ring.  The status goes out one int per lane, to the same row of a B x (n_rows | capacity) array.
+// No atomics and no scratch: the tables come through a pointer (see k_handover), the arrays of the arguments are read with
+// constant indices only (joint_leg is a template over the leg), and the math library's sincos, which returns the cosine
+// through a pointer, is not used.
+struct JointArgs {   // QtosJointRows as the kernel reads it (qtos_planner.hip joint_args)
+  double hz, ee_shift, l_upper, l_lower, tau_max;
+  double hip[NEE][3], lateral[NEE], knee_sign[NEE], kp[3 * NEE], kd[3 * NEE];
+  long long capacity;
+  int first_row, n_rows, flags;
+};
+constexpr int JOINT_TILE = 512;   // rows per tile = lanes per workgroup (see STITCH_TILE); JOINT_TICK where a window has one wave of rows
+constexpr int JOINT_TICK = 64;    // at the most: 18 944 bytes of LDS, several workgroups per CU
+
+// MotorModel.convert_to_torque_ff as joints.motor_torque states it: every operation one rounded IEEE operation in numpy's
+// order (the library is built with the compiler's default, which fuses a * b + c: switched off here), np.clip's comparisons.
+__device__ inline double joint_motor(double kp, double kd, double q, double qd, double tff, double tau_max, bool pd, double qm,
+                                     double qdm) {
+#pragma clang fp contract(off)
+  double tau = tff;
+  if (pd) {
+    const double a = kp * (q - qm), b = kd * (qd - qdm);
+    tau = (a + b) + tff;
+  }
+  if (tau_max > 0) tau = tau < -tau_max ? -tau_max : (tau > tau_max ? tau_max : tau);
+  return tau;
+}
+
+// R = Rz(yaw) Ry(pitch) Rx(roll) of a row's Euler angles (row-major) and the angular velocity in the base frame from its Euler
+// rates.  Like joint_leg without contraction: which product of a sum the compiler fuses is its choice per instantiation, and
+// the 64-lane tick then differed from the 512-lane table in the last bit of qdot; one rounded operation each, they agree.
+__device__ inline void joint_pose(const double *row, double R[9], double wb[3]) {
+#pragma clang fp contract(off)
+  const double sa = sin(row[4]), ca = cos(row[4]), sb = sin(row[5]), cb = cos(row[5]), sc = sin(row[6]), cc = cos(row[6]);
+  R[0] = cc * cb; R[1] = cc * sb * sa - sc * ca; R[2] = cc * sb * ca + sc * sa;
+  R[3] = sc * cb; R[4] = sc * sb * sa + cc * ca; R[5] = sc * sb * ca - cc * sa;
+  R[6] = -sb; R[7] = cb * sa; R[8] = cb * ca;
+  wb[0] = row[22] - row[24] * sb; wb[1] = row[23] * ca + row[24] * cb * sa; wb[2] = row[24] * cb * ca - row[23] * sa;
+}
+
+// Leg E of a row: R the rotation of the planned pose (row-major), wb the angular velocity in the base frame, fv the foot's
+// velocity.  Writes q, qdot and tau of the leg's three joints to dst (the row's place in the tile); returns the status bits.
+template <int E>
+__device__ inline int joint_leg(const JointArgs &A, const double *row, const double R[9], const double wb[3], const double fv[3],
+                                const double *q_mes, const double *qd_mes, double *dst) {
+#pragma clang fp contract(off)
+  const double d = A.lateral[E], lu = A.l_upper, ll = A.l_lower;
+  const double *pf = row + 7 + 3 * E, *f = row + 25 + 3 * E;
+  const double dx = pf[0] - row[1], dy = pf[1] - row[2], dz = pf[2] - row[3];
+  const double ux = fv[0] - row[19], uy = fv[1] - row[20], uz = fv[2] - row[21];
+  // r_b = R^T (foot - com); v_b = R^T (foot_vel - com_vel) - wb x r_b; p_b = r_b + (0, 0, ee_shift)
+  const double bx = R[0] * dx + R[3] * dy + R[6] * dz, by = R[1] * dx + R[4] * dy + R[7] * dz, bz = R[2] * dx + R[5] * dy + R[8] * dz;
+  const double vx = R[0] * ux + R[3] * uy + R[6] * uz - (wb[1] * bz - wb[2] * by);
+  const double vy = R[1] * ux + R[4] * uy + R[7] * uz - (wb[2] * bx - wb[0] * bz);
+  const double vz = R[2] * ux + R[5] * uy + R[8] * uz - (wb[0] * by - wb[1] * bx);
+  const double rx = bx - A.hip[E][0], ry = by - A.hip[E][1], rz = bz + A.ee_shift - A.hip[E][2];
+  // inverse kinematics (joints.leg_ik)
+  const double h2 = ry * ry + rz * rz - d * d;
+  const double h = sqrt(fmax(h2, 0.0));
+  const double c3 = (rx * rx + fmax(h2, 0.0) - lu * lu - ll * ll) / (2 * lu * ll);
+  const int status = (c3 > 1 ? 1 : 0) | (c3 < -1 ? 1 << 4 : 0) | (h2 < 0 ? 1 << 8 : 0);
+  const double q1 = atan2(ry * h + rz * d, ry * d - rz * h);
+  const double q3 = A.knee_sign[E] * acos(fmin(fmax(c3, -1.0), 1.0));
+  const double s3 = sin(q3), c3c = cos(q3);
+  const double q2 = atan2(-rx, h) - atan2(ll * s3, lu + ll * c3c);
+  // the chain at q (joints._hip_frame): the foot at (x, d, -hh) in the hip frame
+  const double s1 = sin(q1), c1 = cos(q1), s2 = sin(q2), c2 = cos(q2), s23 = sin(q2 + q3), c23 = cos(q2 + q3);
+  const double x = -lu * s2 - ll * s23, hh = lu * c2 + ll * c23, ls = ll * s23, lc = ll * c23;
+  // joint rates (joints.joint_rates): zero for a leg with a status bit
+  double qd1 = 0, qd2 = 0, qd3 = 0;
+  if (!status) {
+    const double wy = c1 * vy + s1 * vz, wz = c1 * vz - s1 * vy, det = -(lu * ll * s3);
+    qd1 = wy / hh;
+    const double r2 = wz - d * qd1;
+    qd2 = (vx * ls + lc * r2) / det;
+    qd3 = (x * vx - hh * r2) / det;
+  }
+  // feed-forward torques (joints.feed_forward)
+  double t1 = 0, t2 = 0, t3 = 0;
+  if (!(A.flags & 1)) {
+    const double fx = R[0] * f[0] + R[3] * f[1] + R[6] * f[2], fy = R[1] * f[0] + R[4] * f[1] + R[7] * f[2],
+                 fz = R[2] * f[0] + R[5] * f[1] + R[8] * f[2];
+    const double gy = c1 * fy + s1 * fz, gz = c1 * fz - s1 * fy;
+    t1 = -(hh * gy + d * gz); t2 = hh * fx + x * gz; t3 = lc * fx - ls * gz;
+  }
+  const bool pd = q_mes != nullptr;
+  const double m1 = pd ? q_mes[3 * E] : 0, m2 = pd ? q_mes[3 * E + 1] : 0, m3 = pd ? q_mes[3 * E + 2] : 0;
+  const double n1 = pd ? qd_mes[3 * E] : 0, n2 = pd ? qd_mes[3 * E + 1] : 0, n3 = pd ? qd_mes[3 * E + 2] : 0;
+  dst[1 + 3 * E] = q1; dst[2 + 3 * E] = q2; dst[3 + 3 * E] = q3;
+  dst[13 + 3 * E] = qd1; dst[14 + 3 * E] = qd2; dst[15 + 3 * E] = qd3;
+  dst[25 + 3 * E] = joint_motor(A.kp[3 * E], A.kd[3 * E], q1, qd1, t1, A.tau_max, pd, m1, n1);
+  dst[26 + 3 * E] = joint_motor(A.kp[3 * E + 1], A.kd[3 * E + 1], q2, qd2, t2, A.tau_max, pd, m2, n2);
+  dst[27 + 3 * E] = joint_motor(A.kp[3 * E + 2], A.kd[3 * E + 2], q3, qd3, t3, A.tau_max, pd, m3, n3);
+  return status << E;
+}
+
+template <int TILE>
+__global__ __launch_bounds__(TILE) void k_joint_rows(const SamplePlan *Sd, JointArgs A, const double *nodes, const double *t0,
+                                                     const int *first_row, const int *n_rows, const long long *cursor,
+                                                     const double *q_mes, const double *qd_mes, double *out, int *status_out, int B) {
+  __shared__ double joint_tile[TILE * QTOS_CSV_COLS];
+  const int b = blockIdx.y;
+  if (b >= B) return;
+  const SamplePlan &S = *Sd;
+  const long long rows_b = A.capacity > 0 ? A.capacity : (long long)A.n_rows;      // rows of window b's table or ring
+  long long n = n_rows ? n_rows[b] : A.n_rows;
+  n = n < 0 ? 0 : (n > rows_b ? rows_b : n);
+  const long long j0 = (long long)blockIdx.x * blockDim.x;                         // first row of this tile, of the n rows
+  if (j0 >= n) return;                                                             // (uniform over the workgroup)
+  const int m = n - j0 < (long long)blockDim.x ? (int)(n - j0) : (int)blockDim.x;
+  long long pos = 0;                                                               // table or ring row of the segment's first row
+  if (A.capacity > 0) {
+    pos = cursor[b] % A.capacity;
+    if (pos < 0) pos += A.capacity;
+  }
+  long long base = pos + j0;                                                       // (pos < rows_b and j0 < n <= rows_b: one subtraction wraps it)
+  if (base >= rows_b) base -= rows_b;
+  if ((int)threadIdx.x < m) {
+    const double *x = nodes + (size_t)b * S.n_vars;
+    long long first = first_row ? first_row[b] : A.first_row;
+    first = first < 0 ? 0 : first;
+    const long long k = first + j0 + threadIdx.x;
+    double row[QTOS_CSV_COLS];
+    const double t = sample_row_state_at(S, x, t0[b], k > INT_MAX ? INT_MAX : (int)k, A.hz, row);
+    for (int e = 0; e < NEE; ++e) sample_spline(S.eef[e], x, t, 0, row + 25 + 3 * e);
+    double fv[NEE][3];
+    for (int e = 0; e < NEE; ++e) sample_spline(S.eem[e], x, t, 1, fv[e]);
+    double R[9], wb[3];
+    joint_pose(row, R, wb);
+    const double *qm = q_mes ? q_mes + (size_t)b * 3 * NEE : nullptr, *qdm = q_mes ? qd_mes + (size_t)b * 3 * NEE : nullptr;
+    double *dst = joint_tile + threadIdx.x * QTOS_CSV_COLS;
+    dst[0] = row[0];
+    int st = joint_leg<0>(A, row, R, wb, fv[0], qm, qdm, dst);
+    st |= joint_leg<1>(A, row, R, wb, fv[1], qm, qdm, dst);
+    st |= joint_leg<2>(A, row, R, wb, fv[2], qm, qdm, dst);
+    st |= joint_leg<3>(A, row, R, wb, fv[3], qm, qdm, dst);
+    long long o = base + threadIdx.x;
+    if (o >= rows_b) o -= rows_b;
+    status_out[(size_t)b * (size_t)rows_b + o] = st;
+  }
+  __syncthreads();
+  double *dst = out + (size_t)b * (size_t)rows_b * QTOS_CSV_COLS;
+  const long long all = rows_b * QTOS_CSV_COLS;
+  base *= QTOS_CSV_COLS;
+  for (int e = threadIdx.x; e < m * QTOS_CSV_COLS; e += blockDim.x) {
+    long long o = base + e;                                                        // (m <= rows_b: o < 2 all)
+    if (o >= all) o -= all;
+    dst[o] = joint_tile[e];
+  }
+}
+
 // Goals of receding windows from their global paths (qtos_path_goal*; Global_Planner.update / spine_step, QTOS/planner.py:139-161,
 // 195-230; Combiner.plan_init / spine_step, QTOS/combiner.py:137-212): where the next plan goes.  One lane per window: the
 // window's A* "spine" (two cubic splines in scipy's layout, global_planner.path_table) is read one horizon ahead of the new plan's

@@ -1712,6 +1712,86 @@ int qtos_stitch(QtosPlanner *p, int B, const QtosStitch *s, const double *nodes,
   return rc;
 }
 
+// ---- joint commands of the windows' plans (k_joint_rows, kernels.hpp) -----------------------------------
+// The argument checks of both forms, and QtosJointRows as k_joint_rows reads it.
+static int joint_args(const QtosPlanner *p, int B, const QtosJointRows *s, const void *nodes, const void *t0, const void *first_row,
+                      const void *n_rows, const void *cursor, const void *q_mes, const void *qd_mes, const void *out,
+                      const void *status, JointArgs *A) {
+  (void)first_row; (void)n_rows;
+  if (!p || B < 1 || !s || !nodes || !t0 || !out || !status) return -1;
+  if (s->capacity < 0 || (s->capacity > 0 && !cursor) || s->n_rows < 0 || (s->capacity == 0 && s->n_rows < 1)) return -1;
+  if (s->first_row < 0 || s->first_row > 1000000 || (q_mes == nullptr) != (qd_mes == nullptr)) return -1;
+  if (!(s->l_upper > 0) || !(s->l_lower > 0)) return -1;
+  A->hz = s->hz > 0 ? s->hz : 1000.0;
+  A->ee_shift = s->ee_shift; A->l_upper = s->l_upper; A->l_lower = s->l_lower; A->tau_max = s->tau_max;
+  for (int e = 0; e < NEE; ++e) {
+    for (int d = 0; d < 3; ++d) A->hip[e][d] = s->hip[e][d];
+    A->lateral[e] = s->lateral[e]; A->knee_sign[e] = s->knee_sign[e];
+  }
+  for (int j = 0; j < 3 * NEE; ++j) { A->kp[j] = s->kp[j]; A->kd[j] = s->kd[j]; }
+  A->capacity = s->capacity; A->first_row = s->first_row; A->n_rows = s->n_rows; A->flags = s->flags;
+  return 0;
+}
+
+int qtos_joint_rows_device(QtosPlanner *p, int B, const QtosJointRows *s, const double *d_nodes, const double *d_t0,
+                           const int *d_first_row, const int *d_n_rows, const long long *d_cursor, const double *d_q_mes,
+                           const double *d_qd_mes, double *d_out, int *d_status, void *stream_) {
+  JointArgs A;
+  if (joint_args(p, B, s, d_nodes, d_t0, d_first_row, d_n_rows, d_cursor, d_q_mes, d_qd_mes, d_out, d_status, &A)) return -1;
+  // the most rows a window can have: the count where it is known here, else what the table or ring holds
+  long long most = A.capacity > 0 ? (d_n_rows ? A.capacity : std::min<long long>(A.n_rows, A.capacity)) : A.n_rows;
+  if (most < 1) return 0;
+  const int lanes = most > JOINT_TICK ? JOINT_TILE : JOINT_TICK;
+  const long long tiles = (most + lanes - 1) / lanes;
+  if (tiles > 65535 || B > 65535) { p->err = "qtos_joint_rows: too many rows or windows for one launch"; return -1; }
+  HIPCHK(p, hipSetDevice(p->device));
+  if (lanes == JOINT_TILE)
+    hipLaunchKernelGGL(k_joint_rows<JOINT_TILE>, dim3((unsigned)tiles, B), dim3(JOINT_TILE), 0, (hipStream_t)stream_, p->d_sp, A, d_nodes,
+                       d_t0, d_first_row, d_n_rows, d_cursor, d_q_mes, d_qd_mes, d_out, d_status, B);
+  else
+    hipLaunchKernelGGL(k_joint_rows<JOINT_TICK>, dim3((unsigned)tiles, B), dim3(JOINT_TICK), 0, (hipStream_t)stream_, p->d_sp, A, d_nodes,
+                       d_t0, d_first_row, d_n_rows, d_cursor, d_q_mes, d_qd_mes, d_out, d_status, B);
+  HIPCHK(p, hipGetLastError());
+  return 0;
+}
+
+int qtos_joint_rows(QtosPlanner *p, int B, const QtosJointRows *s, const double *nodes, const double *t0, const int *first_row,
+                    const int *n_rows, const long long *cursor, const double *q_mes, const double *qd_mes, double *out, int *status) {
+  JointArgs A;
+  if (joint_args(p, B, s, nodes, t0, first_row, n_rows, cursor, q_mes, qd_mes, out, status, &A)) return -1;
+  HIPCHK(p, hipSetDevice(p->device));
+  // buffers of its own, as qtos_stitch: the handle's staging buffers are not touched, so it may run while a call is open
+  const size_t n = p->M.n_vars, rows = (size_t)B * (size_t)(A.capacity > 0 ? A.capacity : A.n_rows);
+  double *d_nodes = nullptr, *d_t0 = nullptr, *d_out = nullptr, *d_qm = nullptr, *d_qdm = nullptr;
+  int *d_first = nullptr, *d_n = nullptr, *d_st = nullptr;
+  long long *d_cur = nullptr;
+  auto up = [&](void **dst, const void *src, size_t bytes) -> int {
+    HIPCHK(p, hipMalloc(dst, bytes));
+    HIPCHK(p, hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
+    return 0;
+  };
+  auto run = [&]() -> int {
+    int rc;
+    if ((rc = up((void **)&d_nodes, nodes, (size_t)B * n * sizeof(double)))) return rc;
+    if ((rc = up((void **)&d_t0, t0, B * sizeof(double)))) return rc;
+    if ((rc = up((void **)&d_out, out, rows * QTOS_CSV_COLS * sizeof(double)))) return rc;
+    if ((rc = up((void **)&d_st, status, rows * sizeof(int)))) return rc;
+    if (first_row && (rc = up((void **)&d_first, first_row, B * sizeof(int)))) return rc;
+    if (n_rows && (rc = up((void **)&d_n, n_rows, B * sizeof(int)))) return rc;
+    if (cursor && (rc = up((void **)&d_cur, cursor, B * sizeof(long long)))) return rc;
+    if (q_mes && (rc = up((void **)&d_qm, q_mes, (size_t)B * 3 * NEE * sizeof(double)))) return rc;
+    if (qd_mes && (rc = up((void **)&d_qdm, qd_mes, (size_t)B * 3 * NEE * sizeof(double)))) return rc;
+    if ((rc = qtos_joint_rows_device(p, B, s, d_nodes, d_t0, d_first, d_n, d_cur, d_qm, d_qdm, d_out, d_st, nullptr))) return rc;
+    HIPCHK(p, hipMemcpy(out, d_out, rows * QTOS_CSV_COLS * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(p, hipMemcpy(status, d_st, rows * sizeof(int), hipMemcpyDeviceToHost));
+    return 0;
+  };
+  const int rc = run();
+  (void)hipFree(d_nodes); (void)hipFree(d_t0); (void)hipFree(d_out); (void)hipFree(d_st); (void)hipFree(d_first); (void)hipFree(d_n);
+  (void)hipFree(d_cur); (void)hipFree(d_qm); (void)hipFree(d_qdm);
+  return rc;
+}
+
 // ---- goals of receding windows from their global paths (k_path_goal, kernels.hpp) ------------------------
 // The argument checks of both forms, and QtosPathGoal as k_path_goal reads it.
 static int path_goal_args(const QtosPlanner *p, int B, const QtosPathGoal *g, const void *knots, const void *coef, const void *n_pieces,

@@ -188,11 +188,17 @@ class ShiftedWindows:
     path_base  "spine" (Global_Planner.update: the step is taken from the spine at the plan's start) or "state" (from the state
                the plan starts from), for every plan but the first
     path_hold  True: a window whose done bits are set stands still (its goal is its start) instead of following the spline's
-               extrapolation beyond the path's end"""
+               extrapolation beyond the path's end
+    joints     None (the default): nothing is queued.  A dict (needs ``trajectory``): every window also keeps a ring of joint rows
+               (``self.joint_traj``, B x trajectory x 37: time stamp, q, qdot, tau of the twelve joints) and their status words
+               (``self.joint_status``, B x trajectory), filled row for row with ``self.traj`` by k_joint_rows
+               (qtos_joint_rows_device, the rule: ``joints.joint_rows``), queued in front of every stitch and in ``finish()``.  The
+               dict's entries are ``capi.joint_params``' keywords (ee_shift, kp, kd, hip_scale, knee_scale, ankle_scale, tau_max,
+               feed_forward, robot); ``joint_rows(b)`` reads a window's ring."""
 
     def __init__(self, planner, start, goal_step, map_id=None, advance=2.5, search=0.4, stream=None, warm="none", x_range=None,
                  handover=None, contact="force", height_set=(0.0,), trajectory=None, stitch="clean", path=None, path_base="spine",
-                 path_hold=True):
+                 path_hold=True, joints=None):
         import torch
         self.torch = torch
         self.P = planner
@@ -252,6 +258,16 @@ class ShiftedWindows:
             self.cursor = torch.zeros((B,), dtype=torch.int64, device=dev)
             if handover == "rows":
                 self.row = torch.zeros((B,), dtype=torch.int32, device=dev)
+        self.joint_traj = None
+        if joints is not None:
+            from . import capi
+            if self.traj is None:
+                raise ValueError("joints needs a trajectory ring (trajectory=N)")
+            if not hasattr(planner.lib, "qtos_joint_rows_device"):
+                raise RuntimeError("this build of the planner library has no joint-rows kernel (qtos_joint_rows_device)")
+            self._joint = capi.joint_params(hz=self.hz, first_row=int(self._stitch.first_row), capacity=int(trajectory), **dict(joints))
+            self.joint_traj = torch.zeros((B, int(trajectory), 37), **f64)
+            self.joint_status = torch.zeros((B, int(trajectory)), dtype=torch.int32, device=dev)
         self.stream = stream if stream is not None else torch.cuda.current_stream(dev)
         self.have_plan = False
         self.x_range = x_range     # (lo, hi): a window that walks past an end of its heightfield turns round (no resets)
@@ -408,6 +424,24 @@ class ShiftedWindows:
                                                     ptr(self.path_map_id), ptr(self.clock), ptr(offset), ptr(self.start), ptr(self.goal),
                                                     ptr(self.done), sp), "qtos_path_goal_device")
 
+    def _joint_rows(self, params, n_rows, sp):
+        """Queue k_joint_rows in front of a stitch: the joint rows of the segment that stitch appends, to the same ring rows (the
+        kernel reads the cursor and the clock the stitch behind it moves on)."""
+        import ctypes as C
+        self._call(self.P.lib.qtos_joint_rows_device(self.P.h, self.B, C.byref(params), self.nodes.data_ptr(), self.t0.data_ptr(), None,
+                                                     n_rows, self.cursor.data_ptr(), None, None, self.joint_traj.data_ptr(),
+                                                     self.joint_status.data_ptr(), sp), "qtos_joint_rows_device")
+
+    def joint_rows(self, b):
+        """Window b's newest min(cursor, trajectory) joint rows in time order and their status words, as numpy (the stream is
+        synchronised): row for row the joint commands of ``trajectory_rows(b)``."""
+        from .stitcher import ring_rows
+        if self.joint_traj is None:
+            raise RuntimeError("joint_rows() needs the joint ring (joints=...)")
+        self.stream.synchronize()
+        cur = int(self.cursor[b].item())
+        return ring_rows(self.joint_traj[b].cpu().numpy(), cur), ring_rows(self.joint_status[b].cpu().numpy(), cur)
+
     def replan(self):
         """One replan of every window: begin() + poll() until the call is queued to its end (results: synchronise the stream)."""
         self.begin()
@@ -449,6 +483,10 @@ class ShiftedWindows:
         while first < n_all:        # (a call appends at most `capacity` rows: a plan longer than the ring goes in pieces, its newest rows stay)
             n = min(n_all - first, cap)
             s = capi.stitch_params(cap, first, n, self.hz, False)
+            if self.joint_traj is not None:
+                g = self._joint.copy()
+                g.first_row, g.n_rows = first, n
+                self._joint_rows(g, None, C.c_void_p(self.stream.cuda_stream))
             self._call(self.P.lib.qtos_stitch_device(self.P.h, self.B, C.byref(s), self.nodes.data_ptr(), None, self.t0.data_ptr(),
                                                      self.traj.data_ptr(), self.cursor.data_ptr(), C.c_void_p(self.stream.cuda_stream)),
                        "qtos_stitch_device")
@@ -511,6 +549,8 @@ class ShiftedWindows:
                 self._path_goal(self.path_params, self.offset, sp)
             if self.traj is not None:
                 # the rows executed of the plan handed over from go to the windows' rings; t0 moves on to the new plan's row 0
+                if self.joint_traj is not None:
+                    self._joint_rows(self._joint, self.row.data_ptr(), sp)
                 self._call(P.lib.qtos_stitch_device(P.h, B, C.byref(self._stitch), self.nodes.data_ptr(), self.row.data_ptr(),
                                                     self.t0.data_ptr(), self.traj.data_ptr(), self.cursor.data_ptr(), sp),
                            "qtos_stitch_device")
