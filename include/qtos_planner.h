@@ -408,6 +408,65 @@ int qtos_joint_rows_device(QtosPlanner *p, int B, const QtosJointRows *s, const 
 int qtos_joint_rows(QtosPlanner *p, int B, const QtosJointRows *s, const double *nodes, const double *t0, const int *first_row,
                     const int *n_rows, const long long *cursor, const double *q_mes, const double *qd_mes, double *out, int *status);
 
+/* Measured states and tracking errors of the windows: what comes back from the robot, per CSV row.  The counterpart of
+ * qtos_joint_rows: replaces what the reference does with the measured state once per 1 kHz tick (scripts/run.py:244-273,
+ * QTOS/robot/robot.py traj_vec, QTOS/tracking.py Tracking.update / _update, the test global_COM_xyz[0] >= goal[0]) for B windows
+ * at once (k_track, one workgroup per window; the rule: tracking.py).  Track row k of a plan has 26 columns:
+ *   0         the time stamp of CSV row k (t0 + k / hz, qtos_sample_csv's to the bit)
+ *   1 .. 18   the reference's traj_vec of the measured state: CoM, Euler angles (roll, pitch, yaw), the feet FL, FR, HL, HR in the
+ *             world, foot e = com + R (fk_e(q_e) - (0, 0, ee_shift)), fk_e the closed-form chain of the SOLO12 leg (hip + Rx(q1)
+ *             (x, lateral, -h), x = -l_u sin q2 - l_l sin(q2 + q3), h = l_u cos q2 + l_l cos(q2 + q3)): the inverse of
+ *             towr_transform's lift.  ee_shift 0.015: a robot exactly on its commanded angles and planned pose has zero foot
+ *             error; ee_shift 0: the URDF's FOOT link, what the reference's simulator returns
+ *   19 .. 23  |plan - measured| of the CoM and of the four feet, against the plan's own row k (qtos_sample_csv's columns 1 .. 3 and
+ *             7 .. 18), each sqrt((d0 d0 + d1 d1) + d2 d2)
+ *   24, 25    total_com and total_feet after this row
+ * meas row: base position (3), Euler angles (3), q of the twelve joints (18 doubles); with QTOS_TRACK_QUAT position, quaternion
+ * (x, y, z, w), q (19 doubles): the quaternion is divided by its norm, R formed from it, roll = atan2(R21, R22), pitch =
+ * asin(clip(-R20, -1, 1)), yaw = atan2(R10, R00).
+ * Per window b, count[b] = (calls, recorded) and total[b] = (total_com, total_feet) are read and written: row j of the call is
+ * call c = calls + j + 1; it is recorded iff c >= delay and c != delay + 1 (Tracking.update's branches as they stand: with the
+ * reference's delay 500 calls 500, 502, 503, ...), with QTOS_TRACK_CLEAN_DELAY iff c > delay.  A recorded row adds its CoM error
+ * to total_com and its four foot errors, FL first, to total_feet, in row order (float64, Tracking._update's order), and counts
+ * in `recorded`; then calls += n.  Unrecorded rows carry their pose and errors and repeat the standing totals.
+ * Status word of a row: bit 0 recorded, bit 1 measured CoM x >= goal_x[b] (never without goal_x), bit 2 the pitch clip acted
+ * (|R20| >= 1, quaternion mode).
+ * Addressing: qtos_joint_rows' exactly, for `out`, `status` and `meas` alike -- capacity 0: tables of n_rows rows per window,
+ * row first + j at [b][j], n = d_n_rows ? d_n_rows[b] : n_rows clamped to 0 .. n_rows, rows behind n untouched, a window with
+ * n = 0 keeps its count and total; capacity > 0: rings, row first + j at ring row (cursor[b] + j) mod capacity; cursor and t0 are
+ * only read, so it is queued next to qtos_joint_rows_device in front of qtos_stitch_device with the same nodes, t0, n_rows and
+ * cursor.  With n_rows = 1 and d_first_row: the tick of B robots. */
+#define QTOS_TRACK_QUAT 1          /* flags: meas rows carry a quaternion (19 doubles) */
+#define QTOS_TRACK_CLEAN_DELAY 2   /* flags: recorded iff call > delay */
+#define QTOS_TRACK_COLS 26
+typedef struct QtosTrack {
+  double hz;                    /* rows per second (<= 0: 1000) */
+  int first_row;                /* first row where d_first_row is NULL; 0 .. 1000000 */
+  int n_rows;                   /* table mode: rows per window; both modes: the count where d_n_rows is NULL (>= 0) */
+  long long capacity;           /* 0: table mode; > 0: rows per window in the rings */
+  double ee_shift;              /* towr_transform's lift, taken off the chain's foot */
+  double hip[4][3];             /* HAA origins in the base frame */
+  double lateral[4];            /* y offset of the foot from the HAA axis in the hip frame */
+  double l_upper, l_lower;      /* link lengths (> 0) */
+  int delay;                    /* in calls (>= 0); the reference: 500 */
+  int flags;                    /* QTOS_TRACK_* */
+} QtosTrack;
+/* nodes B x n_vars, t0 B; first_row B and n_rows B may be NULL; cursor B, NULL in table mode; meas B x rows x 18 (19 with
+ * QTOS_TRACK_QUAT), rows = n_rows or capacity; goal_x B, may be NULL; count B x 2 and total B x 2 in / out; out B x rows x 26,
+ * status B x rows.
+ * Device form: all pointers but `s` in device memory, one kernel queued on `stream`, no handle state is read or written but the
+ * sampling tables -- it may be queued while a call is open.  Host form: host pointers, synchronous, through device buffers of
+ * its own as qtos_joint_rows (no -5); out and status are copied in and out whole.
+ * Both: -1 on a null planner or required pointer, B < 1, capacity < 0, a ring without cursor, a table with n_rows < 1, n_rows < 0,
+ * first_row outside 0 .. 1000000, delay < 0, a link length <= 0; -2 on a HIP error. */
+int qtos_track_device(QtosPlanner *p, int B, const QtosTrack *s, const double *d_nodes, const double *d_t0,
+                      const int *d_first_row /* may be NULL */, const int *d_n_rows /* may be NULL */,
+                      const long long *d_cursor /* NULL in table mode */, const double *d_meas, const double *d_goal_x /* may be NULL */,
+                      long long *d_count /* in/out */, double *d_total /* in/out */, double *d_out, int *d_status, void *stream);
+int qtos_track(QtosPlanner *p, int B, const QtosTrack *s, const double *nodes, const double *t0, const int *first_row,
+               const int *n_rows, const long long *cursor, const double *meas, const double *goal_x, long long *count, double *total,
+               double *out, int *status);
+
 /* Goals of receding windows from their global paths: where the next plan goes.  Replaces Global_Planner.update / spine_step
  * (QTOS/planner.py:139-161, 195-230) and Combiner.plan_init / spine_step (QTOS/combiner.py:137-212, 223-225) for B windows at
  * once: a window's A* "spine" -- two cubic splines X_p, Y_p over one set of knots -- is read one horizon ahead of the new plan's

@@ -296,6 +296,42 @@ def joint_params(hz=1000.0, first_row=0, n_rows=0, capacity=0, ee_shift=0.015, k
     return g
 
 
+class QtosTrack(C.Structure):
+    """Parameters of a track call (qtos_track*, include/qtos_planner.h); tracking.track_rows reads the same fields."""
+    _fields_ = [
+        ("hz", C.c_double), ("first_row", C.c_int), ("n_rows", C.c_int), ("capacity", C.c_longlong), ("ee_shift", C.c_double),
+        ("hip", (C.c_double * 3) * 4), ("lateral", C.c_double * 4), ("l_upper", C.c_double), ("l_lower", C.c_double),
+        ("delay", C.c_int), ("flags", C.c_int),
+    ]
+
+    def copy(self):
+        return QtosTrack.from_buffer_copy(self)
+
+
+TRACK_QUAT, TRACK_CLEAN_DELAY = 1, 2     # QTOS_TRACK_QUAT, QTOS_TRACK_CLEAN_DELAY of include/qtos_planner.h
+TRACK_COLS = 26                          # QTOS_TRACK_COLS
+
+
+def track_params(hz=1000.0, first_row=0, n_rows=0, capacity=0, ee_shift=0.015, delay=500, rule="reference", quaternion=False, robot=None):
+    """A QtosTrack with the SOLO12 leg (joints.SOLO12), towr_transform's ee_shift and the reference's delay of 500 calls as
+    defaults.  rule: "reference" (Tracking.update's branches as they stand) or "clean" (recorded iff call > delay); quaternion: the
+    measured rows carry (x, y, z, w) instead of Euler angles.  capacity 0: table mode."""
+    from . import joints, tracking
+    if rule not in tracking.RULES:
+        raise ValueError("rule is 'reference' or 'clean'")
+    robot = joints.SOLO12 if robot is None else robot
+    g = QtosTrack()
+    g.hz, g.first_row, g.n_rows, g.capacity, g.ee_shift = float(hz), int(first_row), int(n_rows), int(capacity), float(ee_shift)
+    for e in range(4):
+        for d in range(3):
+            g.hip[e][d] = float(robot.hip[e][d])
+        g.lateral[e] = float(robot.lateral[e])
+    g.l_upper, g.l_lower = float(robot.l_upper), float(robot.l_lower)
+    g.delay = int(delay)
+    g.flags = (TRACK_QUAT if quaternion else 0) | (TRACK_CLEAN_DELAY if rule == "clean" else 0)
+    return g
+
+
 class SelftestError(RuntimeError):
     """No elimination order passed the KKT self-test (qtos_planner_create_checked returned -6); `attempts`: the QtosSelftest
     records in the order they were tried."""
@@ -323,7 +359,7 @@ EXPORTS = [
     "qtos_path_goal", "qtos_path_goal_device", "qtos_path_plan", "qtos_path_plan_device",
     "qtos_probe", "qtos_probe_device", "qtos_probe_stamp", "qtos_probe_stamp_device",
     "qtos_terrain_env", "qtos_terrain_env_device", "qtos_set_heightfields_device",
-    "qtos_joint_rows", "qtos_joint_rows_device",
+    "qtos_joint_rows", "qtos_joint_rows_device", "qtos_track", "qtos_track_device",
 ]
 
 _lib = None
@@ -448,6 +484,10 @@ def load():
         llp = C.POINTER(C.c_longlong)
         lib.qtos_joint_rows.argtypes = [vp, C.c_int, C.POINTER(QtosJointRows), dp, dp, ip, ip, llp, dp, dp, dp, ip]
         lib.qtos_joint_rows_device.argtypes = [vp, C.c_int, C.POINTER(QtosJointRows)] + [vp] * 10
+    if hasattr(lib, "qtos_track"):          # (the track kernel; older builds loaded through QTOS_LIB lack it)
+        llp = C.POINTER(C.c_longlong)
+        lib.qtos_track.argtypes = [vp, C.c_int, C.POINTER(QtosTrack), dp, dp, ip, ip, llp, dp, dp, llp, dp, dp, ip]
+        lib.qtos_track_device.argtypes = [vp, C.c_int, C.POINTER(QtosTrack)] + [vp] * 12
     if hasattr(lib, "qtos_set_heightfields_device"):
         lib.qtos_set_heightfields_device.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, vp]
     _lib = lib
@@ -903,6 +943,49 @@ class Planner:
                                            None if cur is None else cur.ctypes.data_as(C.POINTER(C.c_longlong)), _dp(qm), _dp(qdm),
                                            _dp(out), _ip(status)), "joint_rows")
         return out, status
+
+    def has_track(self):
+        return hasattr(self.lib, "qtos_track")
+
+    def track(self, nodes, t0, meas, params, first_row=None, n_rows=None, cursor=None, goal_x=None, count=None, total=None, out=None,
+              status=None):
+        """Track rows of every plan in `nodes` against the measured states `meas` (qtos_track, host form; the rule:
+        tracking.track_rows): 26 columns -- the time stamp of the CSV row, the measured pose as the reference's traj_vec, the five
+        errors against the plan's own row, total_com and total_feet after the row -- and an int32 status per row (bit 0 recorded,
+        bit 1 reached goal_x, bit 2 gimbal).  params: a QtosTrack (track_params()).  meas is (B, rows, 18), or (B, rows, 19) with
+        params' quaternion flag, rows = params.n_rows (table mode) or params.capacity (ring mode: `out`, `status` and `cursor` are
+        the rings as they stand, meas is a ring with the same addressing).  count (B, 2) int64 = (calls, recorded) and total (B, 2)
+        = (total_com, total_feet) are the accumulators as they stand (None: zeros).  With params.n_rows = 1 and first_row that is
+        one tick of B robots.  Returns new arrays (rows, status, count, total)."""
+        if not self.has_track():
+            raise RuntimeError("this build of the planner library has no track kernel (qtos_track)")
+        nodes = np.ascontiguousarray(nodes, np.float64).reshape(-1, self.n)
+        B = nodes.shape[0]
+        t0 = np.ascontiguousarray(np.broadcast_to(np.asarray(t0, np.float64), (B,)))
+        i32 = lambda a: None if a is None else np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.int32), (B,)))
+        first, per = i32(first_row), i32(n_rows)
+        rows = int(params.capacity) if params.capacity > 0 else int(params.n_rows)
+        mcols = 19 if params.flags & TRACK_QUAT else 18
+        meas = np.ascontiguousarray(meas, np.float64)
+        if meas.shape != (B, max(rows, 0), mcols):
+            raise ValueError("meas is (B, %d, %d)" % (rows, mcols))
+        cur = None
+        if params.capacity > 0:
+            if out is None or status is None or cursor is None:
+                raise ValueError("ring mode takes the rings as they stand: out, status and cursor")
+            cur = np.ascontiguousarray(np.broadcast_to(np.asarray(cursor, np.int64), (B,)))
+        goal = None if goal_x is None else np.ascontiguousarray(np.broadcast_to(np.asarray(goal_x, np.float64), (B,)))
+        count = np.zeros((B, 2), np.int64) if count is None else np.array(count, np.int64).reshape(B, 2)
+        total = np.zeros((B, 2)) if total is None else np.array(total, np.float64).reshape(B, 2)
+        out = np.zeros((B, max(rows, 0), TRACK_COLS)) if out is None else np.array(out, np.float64)
+        status = np.zeros((B, max(rows, 0)), np.int32) if status is None else np.array(status, np.int32)
+        if out.shape != (B, rows, TRACK_COLS) or status.shape != (B, rows):
+            raise ValueError("out is (B, %d, %d) and status (B, %d)" % (rows, TRACK_COLS, rows))
+        llp = C.POINTER(C.c_longlong)
+        self._chk(self.lib.qtos_track(self.h, B, C.byref(params), _dp(nodes), _dp(t0), _ip(first), _ip(per),
+                                      None if cur is None else cur.ctypes.data_as(llp), _dp(meas), _dp(goal), count.ctypes.data_as(llp),
+                                      _dp(total), _dp(out), _ip(status)), "track")
+        return out, status, count, total
 
     def has_path_goal(self):
         return hasattr(self.lib, "qtos_path_goal")

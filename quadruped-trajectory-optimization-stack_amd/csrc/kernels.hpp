@@ -2287,6 +2287,181 @@ __global__ __launch_bounds__(TILE) void k_joint_rows(const SamplePlan *Sd, Joint
   }
 }
 
+// Measured states and tracking errors of the windows (qtos_track*; scripts/run.py:244-273, QTOS/tracking.py Tracking.update /
+// _update, QTOS/robot/robot.py traj_vec): the counterpart of k_joint_rows for what comes back from the robot.  Per CSV row the
+// measured base pose and joint angles become the reference's traj_vec (CoM, Euler angles, the four feet in the world by the
+// leg's closed-form forward kinematics, joints.leg_fk), the five Euclidean errors against the plan's own row and the two
+// running totals.  The statement of the rule is tracking.py.  The totals are sequential sums by definition, so one workgroup
+// owns one window and walks its tiles in order.  Per tile: (A) a lane takes a row -- time stamp and planned positions with
+// k_sample's evaluator (sample_row_state_at: qtos_sample_csv's numbers to the bit), R from the measured pose, four legs through
+// a template over the leg, and the 24 values and five errors into the row's place of an LDS tile; (B) behind a barrier lane 0
+// runs the CoM chain over the tile's rows and the first lane of the second wave the feet chain (lane 0 again where the
+// workgroup is one wave), each from the total it carries in a register from the previous tile, into columns 24 and 25; (C) the
+// tile goes out flat, consecutive lanes on consecutive doubles, the pitch of 26 doubles kept (k_stitch's addressing: table or
+// ring, cursor and t0 only read).  The status is one int per lane.  The owners of the chains write count and total back with
+// plain stores behind the last tile; every lane has read them in front of the first barrier.  No atomics, no scratch (constant
+// indices only, see k_joint_rows), no sincos.
+struct TrackArgs {   // QtosTrack as the kernel reads it (qtos_planner.hip track_args)
+  double hz, ee_shift, l_upper, l_lower;
+  double hip[NEE][3], lateral[NEE];
+  long long capacity;
+  int first_row, n_rows, delay, flags;
+};
+constexpr int TRACK_COLS = 26;
+constexpr int TRACK_TILE = 512;   // rows per tile = lanes per workgroup: 512 x 26 x 8 = 106 496 bytes of LDS, one workgroup per CU
+constexpr int TRACK_TICK = 64;    // one wave where no window has more rows (the tick): 13 312 bytes
+
+// R (row-major) of the measured pose and the Euler columns.  Euler mode (m[3 .. 5] roll, pitch, yaw): R = Rz Ry Rx as
+// joint_pose forms it, the angles copied through.  Quaternion mode (m[3 .. 6] = x, y, z, w): divided by its norm, R directly,
+// roll = atan2(R21, R22), pitch = asin(clip(-R20)), yaw = atan2(R10, R00); returns 4 (GIMBAL) where the clip acts.  Without
+// contraction, as joint_pose: one rounded operation each, in tracking.py's order.
+__device__ inline int track_pose(const double *m, bool quat, double R[9], double *euler) {
+#pragma clang fp contract(off)
+  if (!quat) {
+    const double sa = sin(m[3]), ca = cos(m[3]), sb = sin(m[4]), cb = cos(m[4]), sc = sin(m[5]), cc = cos(m[5]);
+    R[0] = cc * cb; R[1] = cc * sb * sa - sc * ca; R[2] = cc * sb * ca + sc * sa;
+    R[3] = sc * cb; R[4] = sc * sb * sa + cc * ca; R[5] = sc * sb * ca - cc * sa;
+    R[6] = -sb; R[7] = cb * sa; R[8] = cb * ca;
+    euler[0] = m[3]; euler[1] = m[4]; euler[2] = m[5];
+    return 0;
+  }
+  double x = m[3], y = m[4], z = m[5], w = m[6];
+  const double n = sqrt(((x * x + y * y) + z * z) + w * w);
+  x = x / n; y = y / n; z = z / n; w = w / n;
+  R[0] = 1 - 2 * (y * y + z * z); R[1] = 2 * (x * y - z * w); R[2] = 2 * (x * z + y * w);
+  R[3] = 2 * (x * y + z * w); R[4] = 1 - 2 * (x * x + z * z); R[5] = 2 * (y * z - x * w);
+  R[6] = 2 * (x * z - y * w); R[7] = 2 * (y * z + x * w); R[8] = 1 - 2 * (x * x + y * y);
+  euler[0] = atan2(R[7], R[8]);
+  euler[1] = asin(fmin(fmax(-R[6], -1.0), 1.0));
+  euler[2] = atan2(R[3], R[0]);
+  return fabs(R[6]) >= 1 ? 4 : 0;
+}
+
+// |a - b| of two points: sqrt((d0 d0 + d1 d1) + d2 d2), one rounded operation after the other (tracking.errors).
+__device__ inline double track_norm(const double *a, const double *b) {
+#pragma clang fp contract(off)
+  const double d0 = a[0] - b[0], d1 = a[1] - b[1], d2 = a[2] - b[2];
+  return sqrt((d0 * d0 + d1 * d1) + d2 * d2);
+}
+
+// Foot E of a measured row in the world: com + R (leg_fk(E, q) - (0, 0, ee_shift)), q the leg's three measured angles
+// (joints.leg_fk: hip + Rx(q1) (x, d, -h)).  Writes the foot to dst[7 + 3 E ..] and its error against the planned foot to
+// dst[20 + E] (dst: the row's place in the tile).
+template <int E>
+__device__ inline void track_leg(const TrackArgs &A, const double *row, const double *com, const double R[9], const double *q,
+                                 double *dst) {
+#pragma clang fp contract(off)
+  const double d = A.lateral[E], lu = A.l_upper, ll = A.l_lower;
+  const double q1 = q[3 * E], q2 = q[3 * E + 1], q3 = q[3 * E + 2];
+  const double s1 = sin(q1), c1 = cos(q1), s2 = sin(q2), c2 = cos(q2), s23 = sin(q2 + q3), c23 = cos(q2 + q3);
+  const double x = -lu * s2 - ll * s23, h = lu * c2 + ll * c23;
+  const double px = A.hip[E][0] + x, py = A.hip[E][1] + c1 * d + s1 * h, pz = (A.hip[E][2] + s1 * d - c1 * h) - A.ee_shift;
+  double foot[3];
+  foot[0] = com[0] + ((R[0] * px + R[1] * py) + R[2] * pz);
+  foot[1] = com[1] + ((R[3] * px + R[4] * py) + R[5] * pz);
+  foot[2] = com[2] + ((R[6] * px + R[7] * py) + R[8] * pz);
+  dst[7 + 3 * E] = foot[0]; dst[8 + 3 * E] = foot[1]; dst[9 + 3 * E] = foot[2];
+  dst[20 + E] = track_norm(row + 7 + 3 * E, foot);
+}
+
+// Whether the 1-based call c of a window is recorded (tracking.recorded): Tracking.update's branches as they stand, c >= delay
+// and c != delay + 1, or with QTOS_TRACK_CLEAN_DELAY c > delay.
+__device__ inline bool track_recorded(long long c, int delay, bool clean) {
+  return clean ? c > delay : (c >= delay && c != (long long)delay + 1);
+}
+
+template <int TILE>
+__global__ __launch_bounds__(TILE) void k_track(const SamplePlan *Sd, TrackArgs A, const double *nodes, const double *t0,
+                                                const int *first_row, const int *n_rows, const long long *cursor, const double *meas,
+                                                const double *goal_x, long long *count, double *total, double *out, int *status_out,
+                                                int B) {
+  __shared__ double track_tile[TILE * TRACK_COLS];
+  constexpr int FEET_LANE = TILE > 64 ? 64 : 0;                                    // the feet chain's owner: a lane of another wave
+  const int b = blockIdx.x;
+  if (b >= B) return;
+  const SamplePlan &S = *Sd;
+  const long long rows_b = A.capacity > 0 ? A.capacity : (long long)A.n_rows;      // rows of window b's table or ring
+  long long n = n_rows ? n_rows[b] : A.n_rows;
+  n = n < 0 ? 0 : (n > rows_b ? rows_b : n);
+  if (n == 0) return;                                                              // (uniform: a window without rows keeps its accumulators)
+  const bool quat = (A.flags & 1) != 0, clean = (A.flags & 2) != 0;
+  const int mcols = quat ? 19 : 18;
+  const long long calls = count[2 * b];                                            // (every lane, in front of the first barrier)
+  long long rec = count[2 * b + 1];
+  double run = total[2 * b + (threadIdx.x == FEET_LANE && FEET_LANE ? 1 : 0)];     // the chain this lane owns, if it owns one
+  double run_feet = total[2 * b + 1];                                              // (one wave: lane 0 owns both)
+  long long pos = 0;                                                               // table or ring row of the segment's first row
+  if (A.capacity > 0) {
+    pos = cursor[b] % A.capacity;
+    if (pos < 0) pos += A.capacity;
+  }
+  const double *x = nodes + (size_t)b * S.n_vars;
+  long long first = first_row ? first_row[b] : A.first_row;
+  first = first < 0 ? 0 : first;
+  const double t0b = t0[b];
+  const double *meas_b = meas + (size_t)b * (size_t)rows_b * mcols;
+  double *out_b = out + (size_t)b * (size_t)rows_b * TRACK_COLS;
+  const long long all = rows_b * TRACK_COLS;
+  for (long long j0 = 0; j0 < n; j0 += TILE) {                                     // (n is uniform over the workgroup: so are the barriers)
+    const int m = n - j0 < TILE ? (int)(n - j0) : TILE;
+    long long base = pos + j0;                                                     // (pos < rows_b and j0 < n <= rows_b: one subtraction wraps it)
+    if (base >= rows_b) base -= rows_b;
+    if ((int)threadIdx.x < m) {                                                    // (A) a lane takes a row
+      const long long k = first + j0 + threadIdx.x;
+      double row[25];
+      sample_row_state_at(S, x, t0b, k > INT_MAX ? INT_MAX : (int)k, A.hz, row);
+      long long o = base + threadIdx.x;
+      if (o >= rows_b) o -= rows_b;
+      const double *mr = meas_b + (size_t)o * mcols;
+      double *dst = track_tile + threadIdx.x * TRACK_COLS;
+      double R[9];
+      int st = track_pose(mr, quat, R, dst + 4);
+      dst[0] = row[0];
+      dst[1] = mr[0]; dst[2] = mr[1]; dst[3] = mr[2];
+      dst[19] = track_norm(row + 1, mr);
+      const double *q = mr + (quat ? 7 : 6);
+      track_leg<0>(A, row, mr, R, q, dst);
+      track_leg<1>(A, row, mr, R, q, dst);
+      track_leg<2>(A, row, mr, R, q, dst);
+      track_leg<3>(A, row, mr, R, q, dst);
+      if (track_recorded(calls + j0 + threadIdx.x + 1, A.delay, clean)) st |= 1;
+      if (goal_x && mr[0] >= goal_x[b]) st |= 2;
+      status_out[(size_t)b * (size_t)rows_b + o] = st;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {                                                        // (B) the chains, in program order
+      for (int i = 0; i < m; ++i) {
+        double *r = track_tile + i * TRACK_COLS;
+        if (track_recorded(calls + j0 + i + 1, A.delay, clean)) { run += r[19]; ++rec; }
+        r[24] = run;
+      }
+    }
+    if (threadIdx.x == FEET_LANE) {
+      double f = FEET_LANE ? run : run_feet;
+      for (int i = 0; i < m; ++i) {
+        double *r = track_tile + i * TRACK_COLS;
+        if (track_recorded(calls + j0 + i + 1, A.delay, clean)) { f += r[20]; f += r[21]; f += r[22]; f += r[23]; }
+        r[25] = f;
+      }
+      if (FEET_LANE) run = f; else run_feet = f;
+    }
+    __syncthreads();
+    base *= TRACK_COLS;                                                            // (C) the tile goes out flat
+    for (int e = threadIdx.x; e < m * TRACK_COLS; e += TILE) {
+      long long o = base + e;                                                      // (m <= rows_b: o < 2 all)
+      if (o >= all) o -= all;
+      out_b[o] = track_tile[e];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    count[2 * b] = calls + n;
+    count[2 * b + 1] = rec;
+    total[2 * b] = run;
+  }
+  if (threadIdx.x == FEET_LANE) total[2 * b + 1] = FEET_LANE ? run : run_feet;
+}
+
 // Goals of receding windows from their global paths (qtos_path_goal*; Global_Planner.update / spine_step, QTOS/planner.py:139-161,
 // 195-230; Combiner.plan_init / spine_step, QTOS/combiner.py:137-212): where the next plan goes.  One lane per window: the
 // window's A* "spine" (two cubic splines in scipy's layout, global_planner.path_table) is read one horizon ahead of the new plan's

@@ -1792,6 +1792,87 @@ int qtos_joint_rows(QtosPlanner *p, int B, const QtosJointRows *s, const double 
   return rc;
 }
 
+// ---- measured states and tracking errors of the windows (k_track, kernels.hpp) ---------------------------
+// The argument checks of both forms, and QtosTrack as k_track reads it.
+static int track_args(const QtosPlanner *p, int B, const QtosTrack *s, const void *nodes, const void *t0, const void *cursor,
+                      const void *meas, const void *count, const void *total, const void *out, const void *status, TrackArgs *A) {
+  if (!p || B < 1 || !s || !nodes || !t0 || !meas || !count || !total || !out || !status) return -1;
+  if (s->capacity < 0 || (s->capacity > 0 && !cursor) || s->n_rows < 0 || (s->capacity == 0 && s->n_rows < 1)) return -1;
+  if (s->first_row < 0 || s->first_row > 1000000 || s->delay < 0) return -1;
+  if (!(s->l_upper > 0) || !(s->l_lower > 0)) return -1;
+  A->hz = s->hz > 0 ? s->hz : 1000.0;
+  A->ee_shift = s->ee_shift; A->l_upper = s->l_upper; A->l_lower = s->l_lower;
+  for (int e = 0; e < NEE; ++e) {
+    for (int d = 0; d < 3; ++d) A->hip[e][d] = s->hip[e][d];
+    A->lateral[e] = s->lateral[e];
+  }
+  A->capacity = s->capacity; A->first_row = s->first_row; A->n_rows = s->n_rows; A->delay = s->delay; A->flags = s->flags;
+  return 0;
+}
+
+int qtos_track_device(QtosPlanner *p, int B, const QtosTrack *s, const double *d_nodes, const double *d_t0, const int *d_first_row,
+                      const int *d_n_rows, const long long *d_cursor, const double *d_meas, const double *d_goal_x, long long *d_count,
+                      double *d_total, double *d_out, int *d_status, void *stream_) {
+  TrackArgs A;
+  if (track_args(p, B, s, d_nodes, d_t0, d_cursor, d_meas, d_count, d_total, d_out, d_status, &A)) return -1;
+  // the most rows a window can have: the count where it is known here, else what the table or ring holds
+  const long long most = A.capacity > 0 ? (d_n_rows ? A.capacity : std::min<long long>(A.n_rows, A.capacity)) : A.n_rows;
+  if (most < 1) return 0;
+  HIPCHK(p, hipSetDevice(p->device));
+  if (most > TRACK_TICK)
+    hipLaunchKernelGGL(k_track<TRACK_TILE>, dim3(B), dim3(TRACK_TILE), 0, (hipStream_t)stream_, p->d_sp, A, d_nodes, d_t0, d_first_row,
+                       d_n_rows, d_cursor, d_meas, d_goal_x, d_count, d_total, d_out, d_status, B);
+  else
+    hipLaunchKernelGGL(k_track<TRACK_TICK>, dim3(B), dim3(TRACK_TICK), 0, (hipStream_t)stream_, p->d_sp, A, d_nodes, d_t0, d_first_row,
+                       d_n_rows, d_cursor, d_meas, d_goal_x, d_count, d_total, d_out, d_status, B);
+  HIPCHK(p, hipGetLastError());
+  return 0;
+}
+
+int qtos_track(QtosPlanner *p, int B, const QtosTrack *s, const double *nodes, const double *t0, const int *first_row, const int *n_rows,
+               const long long *cursor, const double *meas, const double *goal_x, long long *count, double *total, double *out,
+               int *status) {
+  TrackArgs A;
+  if (track_args(p, B, s, nodes, t0, cursor, meas, count, total, out, status, &A)) return -1;
+  HIPCHK(p, hipSetDevice(p->device));
+  // buffers of its own, as qtos_joint_rows: the handle's staging buffers are not touched, so it may run while a call is open
+  const size_t n = p->M.n_vars, rows = (size_t)B * (size_t)(A.capacity > 0 ? A.capacity : A.n_rows);
+  const size_t mcols = (A.flags & QTOS_TRACK_QUAT) ? 19 : 18;
+  double *d_nodes = nullptr, *d_t0 = nullptr, *d_out = nullptr, *d_meas = nullptr, *d_goal = nullptr, *d_total = nullptr;
+  int *d_first = nullptr, *d_n = nullptr, *d_st = nullptr;
+  long long *d_cur = nullptr, *d_count = nullptr;
+  auto up = [&](void **dst, const void *src, size_t bytes) -> int {
+    HIPCHK(p, hipMalloc(dst, bytes));
+    HIPCHK(p, hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
+    return 0;
+  };
+  auto run = [&]() -> int {
+    int rc;
+    if ((rc = up((void **)&d_nodes, nodes, (size_t)B * n * sizeof(double)))) return rc;
+    if ((rc = up((void **)&d_t0, t0, B * sizeof(double)))) return rc;
+    if ((rc = up((void **)&d_meas, meas, rows * mcols * sizeof(double)))) return rc;
+    if ((rc = up((void **)&d_out, out, rows * TRACK_COLS * sizeof(double)))) return rc;
+    if ((rc = up((void **)&d_st, status, rows * sizeof(int)))) return rc;
+    if ((rc = up((void **)&d_count, count, (size_t)B * 2 * sizeof(long long)))) return rc;
+    if ((rc = up((void **)&d_total, total, (size_t)B * 2 * sizeof(double)))) return rc;
+    if (first_row && (rc = up((void **)&d_first, first_row, B * sizeof(int)))) return rc;
+    if (n_rows && (rc = up((void **)&d_n, n_rows, B * sizeof(int)))) return rc;
+    if (cursor && (rc = up((void **)&d_cur, cursor, B * sizeof(long long)))) return rc;
+    if (goal_x && (rc = up((void **)&d_goal, goal_x, B * sizeof(double)))) return rc;
+    if ((rc = qtos_track_device(p, B, s, d_nodes, d_t0, d_first, d_n, d_cur, d_meas, d_goal, d_count, d_total, d_out, d_st, nullptr)))
+      return rc;
+    HIPCHK(p, hipMemcpy(out, d_out, rows * TRACK_COLS * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(p, hipMemcpy(status, d_st, rows * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(p, hipMemcpy(count, d_count, (size_t)B * 2 * sizeof(long long), hipMemcpyDeviceToHost));
+    HIPCHK(p, hipMemcpy(total, d_total, (size_t)B * 2 * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+  };
+  const int rc = run();
+  (void)hipFree(d_nodes); (void)hipFree(d_t0); (void)hipFree(d_meas); (void)hipFree(d_out); (void)hipFree(d_st); (void)hipFree(d_count);
+  (void)hipFree(d_total); (void)hipFree(d_first); (void)hipFree(d_n); (void)hipFree(d_cur); (void)hipFree(d_goal);
+  return rc;
+}
+
 // ---- goals of receding windows from their global paths (k_path_goal, kernels.hpp) ------------------------
 // The argument checks of both forms, and QtosPathGoal as k_path_goal reads it.
 static int path_goal_args(const QtosPlanner *p, int B, const QtosPathGoal *g, const void *knots, const void *coef, const void *n_pieces,

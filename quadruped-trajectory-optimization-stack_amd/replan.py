@@ -194,11 +194,22 @@ class ShiftedWindows:
                (``self.joint_status``, B x trajectory), filled row for row with ``self.traj`` by k_joint_rows
                (qtos_joint_rows_device, the rule: ``joints.joint_rows``), queued in front of every stitch and in ``finish()``.  The
                dict's entries are ``capi.joint_params``' keywords (ee_shift, kp, kd, hip_scale, knee_scale, ankle_scale, tau_max,
-               feed_forward, robot); ``joint_rows(b)`` reads a window's ring."""
+               feed_forward, robot); ``joint_rows(b)`` reads a window's ring.
+    track      None (the default): nothing is queued and nothing is allocated.  A dict (needs ``trajectory``): every window also
+               keeps a ring of measured states (``self.meas_traj``, B x trajectory x 18, or x 19 with ``quaternion``: the caller's to
+               fill, at ring rows (cursor + j) mod trajectory, for the rows a plan executes before the next takes over), a ring of
+               track rows (``self.track_traj``, B x trajectory x 26: time stamp, measured pose, five errors, two running totals),
+               their status words (``self.track_status``) and the accumulators ``self.track_count`` (B x 2, int64: calls, recorded)
+               and ``self.track_total`` (B x 2: total_com, total_feet), filled by k_track (qtos_track_device, the rule:
+               ``tracking.track_rows``), queued in front of every stitch and in ``finish()``, behind the joint rows where both are
+               on.  The dict's entries are ``capi.track_params``' keywords (ee_shift, delay, rule, quaternion, robot), ``goal_x`` (a
+               number or one per window: status bit 1 of a row whose measured CoM x has reached it) and ``fill`` (a callable
+               taking the windows, called on the set's stream in front of every track call: the last place to write
+               ``meas_traj``, e.g. from the joint ring just filled); ``track_rows(b)`` reads a window's ring."""
 
     def __init__(self, planner, start, goal_step, map_id=None, advance=2.5, search=0.4, stream=None, warm="none", x_range=None,
                  handover=None, contact="force", height_set=(0.0,), trajectory=None, stitch="clean", path=None, path_base="spine",
-                 path_hold=True, joints=None):
+                 path_hold=True, joints=None, track=None):
         import torch
         self.torch = torch
         self.P = planner
@@ -268,6 +279,24 @@ class ShiftedWindows:
             self._joint = capi.joint_params(hz=self.hz, first_row=int(self._stitch.first_row), capacity=int(trajectory), **dict(joints))
             self.joint_traj = torch.zeros((B, int(trajectory), 37), **f64)
             self.joint_status = torch.zeros((B, int(trajectory)), dtype=torch.int32, device=dev)
+        self.track_traj = None
+        if track is not None:
+            from . import capi
+            if self.traj is None:
+                raise ValueError("track needs a trajectory ring (trajectory=N)")
+            if not hasattr(planner.lib, "qtos_track_device"):
+                raise RuntimeError("this build of the planner library has no track kernel (qtos_track_device)")
+            track = dict(track)
+            goal_x, self._track_fill = track.pop("goal_x", None), track.pop("fill", None)
+            self._track = capi.track_params(hz=self.hz, first_row=int(self._stitch.first_row), capacity=int(trajectory), **track)
+            self.meas_traj = torch.zeros((B, int(trajectory), 19 if self._track.flags & capi.TRACK_QUAT else 18), **f64)
+            self.track_traj = torch.zeros((B, int(trajectory), capi.TRACK_COLS), **f64)
+            self.track_status = torch.zeros((B, int(trajectory)), dtype=torch.int32, device=dev)
+            self.track_count = torch.zeros((B, 2), dtype=torch.int64, device=dev)
+            self.track_total = torch.zeros((B, 2), **f64)
+            self.track_goal_x = None
+            if goal_x is not None:
+                self.track_goal_x = torch.as_tensor(np.broadcast_to(np.asarray(goal_x, np.float64), (B,)).copy(), **f64)
         self.stream = stream if stream is not None else torch.cuda.current_stream(dev)
         self.have_plan = False
         self.x_range = x_range     # (lo, hi): a window that walks past an end of its heightfield turns round (no resets)
@@ -442,6 +471,28 @@ class ShiftedWindows:
         cur = int(self.cursor[b].item())
         return ring_rows(self.joint_traj[b].cpu().numpy(), cur), ring_rows(self.joint_status[b].cpu().numpy(), cur)
 
+    def _track_rows(self, params, n_rows, sp):
+        """Queue k_track in front of a stitch (behind the joint rows): the track rows of the segment that stitch appends, from the
+        measured ring's rows of that segment, to the same ring rows."""
+        import ctypes as C
+        if self._track_fill is not None:
+            self._track_fill(self)
+        self._call(self.P.lib.qtos_track_device(self.P.h, self.B, C.byref(params), self.nodes.data_ptr(), self.t0.data_ptr(), None, n_rows,
+                                                self.cursor.data_ptr(), self.meas_traj.data_ptr(),
+                                                None if self.track_goal_x is None else self.track_goal_x.data_ptr(),
+                                                self.track_count.data_ptr(), self.track_total.data_ptr(), self.track_traj.data_ptr(),
+                                                self.track_status.data_ptr(), sp), "qtos_track_device")
+
+    def track_rows(self, b):
+        """Window b's newest min(cursor, trajectory) track rows in time order and their status words, as numpy (the stream is
+        synchronised): row for row the measured poses and errors of ``trajectory_rows(b)``."""
+        from .stitcher import ring_rows
+        if self.track_traj is None:
+            raise RuntimeError("track_rows() needs the track ring (track=...)")
+        self.stream.synchronize()
+        cur = int(self.cursor[b].item())
+        return ring_rows(self.track_traj[b].cpu().numpy(), cur), ring_rows(self.track_status[b].cpu().numpy(), cur)
+
     def replan(self):
         """One replan of every window: begin() + poll() until the call is queued to its end (results: synchronise the stream)."""
         self.begin()
@@ -487,6 +538,11 @@ class ShiftedWindows:
                 g = self._joint.copy()
                 g.first_row, g.n_rows = first, n
                 self._joint_rows(g, None, C.c_void_p(self.stream.cuda_stream))
+            if self.track_traj is not None:
+                g = self._track.copy()
+                g.first_row, g.n_rows = first, n
+                with self.torch.cuda.stream(self.stream):
+                    self._track_rows(g, None, C.c_void_p(self.stream.cuda_stream))
             self._call(self.P.lib.qtos_stitch_device(self.P.h, self.B, C.byref(s), self.nodes.data_ptr(), None, self.t0.data_ptr(),
                                                      self.traj.data_ptr(), self.cursor.data_ptr(), C.c_void_p(self.stream.cuda_stream)),
                        "qtos_stitch_device")
@@ -551,6 +607,8 @@ class ShiftedWindows:
                 # the rows executed of the plan handed over from go to the windows' rings; t0 moves on to the new plan's row 0
                 if self.joint_traj is not None:
                     self._joint_rows(self._joint, self.row.data_ptr(), sp)
+                if self.track_traj is not None:
+                    self._track_rows(self._track, self.row.data_ptr(), sp)
                 self._call(P.lib.qtos_stitch_device(P.h, B, C.byref(self._stitch), self.nodes.data_ptr(), self.row.data_ptr(),
                                                     self.t0.data_ptr(), self.traj.data_ptr(), self.cursor.data_ptr(), sp),
                            "qtos_stitch_device")
