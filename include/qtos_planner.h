@@ -467,6 +467,68 @@ int qtos_track(QtosPlanner *p, int B, const QtosTrack *s, const double *nodes, c
                const int *n_rows, const long long *cursor, const double *meas, const double *goal_x, long long *count, double *total,
                double *out, int *status);
 
+/* Feedback hand-over: the next plan starts from where the robot is.  qtos_handover* starts every new plan from the old plan's
+ * own hand-over row (the reference's Combiner._state; it records robot_state in Global_Planner.update and never uses it); this
+ * call corrects that start vector, in place, by the tracking error of the plan handed over from, for B windows in one launch
+ * (k_start_feedback, one lane per window; the rule: feedback.py).  With every gain 0 it changes nothing, to the bit: steps 6
+ * and 7 are left out, the status word has bits 1 and 2 only.  Per window b, with r = row[b] the hand-over row (qtos_handover's
+ * row_out) and lat = round(latency * hz):
+ *   1  the measured plan row is k = clamp(r - lat, first_row, first_row + r - 1), one of the rows qtos_stitch appends for this
+ *      plan; its measurement is meas[b][k - first_row] (capacity 0: a B x n_rows x cols table) or ring row (cursor[b] + k -
+ *      first_row) mod capacity (qtos_track's addressing), cols 18, or 19 with QTOS_FEEDBACK_QUAT.  r <= 0, or a row the table or
+ *      ring does not hold (k - first_row >= n_rows or capacity): status bit 5, and nothing else of the window is touched
+ *   2  m[0 .. 17], the measured pose: qtos_track's columns 1 .. 18 of that row, to the bit (status bit 2: the pitch clip acted)
+ *   3  p[0 .. 17], the planned pose: qtos_sample_csv's columns 1 .. 18 of plan row k, to the bit
+ *   4  e = m - p, the yaw component through the IEEE remainder with 2 pi, every component clipped to +- max_pos (CoM), +- max_ang
+ *      (Euler), +- max_foot (feet); status bit 1: a clip acted.  err_out[b] = the clipped e
+ *   5  start[0 .. 2] += gain_pos e[0 .. 2], start[3 .. 5] += gain_ang e[3 .. 5], start[6 + 3 f + i] += gain_foot e[6 + 3 f + i]
+ *      (a gain of 0 adds nothing: the bits stay).  The velocities, start[18 .. 23], stay the plan's
+ *   6  QTOS_FEEDBACK_SNAP: every foot's z becomes the terrain height under its corrected x, y, from the handle's heightfield
+ *      map_id[b] in the handle's terrain_mode (the solver's own lookup) -- the first stance fixes the foot where the start vector
+ *      puts it, and the terrain row of its second node demands z = h(x, y); status bit 6 + f: that moved foot f's z by more
+ *      than snap_tol against the corrected z
+ *   7  range-of-motion guard: with R of the corrected Euler angles, d_f = R^T (foot_f - com) - nominal[f]; unless every |d_f[i]|
+ *      <= max_deviation[i] + rom_tol (a NaN fails) the window falls back: its start is not written, status bit 3
+ *   8  status bit 0: corrected (a measurement, a gain that is not 0, no fallback).  QTOS_FEEDBACK_ZERO_FILTER: |v| < 1e-4 -> 0 on
+ *      the 24 doubles of a window that did not fall back (QtosHandover.zero_filter).  With goal_step: goal[b][0 .. 1] =
+ *      start[b][0 .. 1] + goal_step[b][0 .. 1] from the start as it stands then; goal[b][2] is not touched */
+#define QTOS_FEEDBACK_QUAT 1         /* meas rows carry a quaternion (19 doubles), as QTOS_TRACK_QUAT */
+#define QTOS_FEEDBACK_SNAP 2
+#define QTOS_FEEDBACK_ZERO_FILTER 4
+typedef struct QtosFeedback {
+  double hz;                    /* rows per second (<= 0: 1000) */
+  int first_row, n_rows;        /* first row of the segment, 0 .. 1000000; table mode: rows per window (>= 1) */
+  long long capacity;           /* 0: table mode; > 0: rows per window in the ring */
+  double latency;               /* seconds (>= 0): the measurement is that much older than the hand-over row */
+  double ee_shift;              /* the leg chain, as QtosTrack */
+  double hip[4][3];
+  double lateral[4];
+  double l_upper, l_lower;      /* link lengths (> 0) */
+  double gain_pos, gain_ang, gain_foot;   /* each in 0 .. 1 */
+  double max_pos, max_ang, max_foot;      /* clips (> 0) */
+  double nominal[4][3];         /* the range-of-motion box of the planner's model: nominal stance ... */
+  double max_deviation[3];      /* ... and half widths */
+  double rom_tol, snap_tol;
+  int flags;                    /* QTOS_FEEDBACK_* */
+} QtosFeedback;
+/* nodes B x n_vars and t0 B: the plan handed over from and its clock, as qtos_track takes them (in front of qtos_stitch); row B;
+ * cursor B, NULL in table mode; meas B x rows x 18 (19 with QTOS_FEEDBACK_QUAT), rows = n_rows or capacity; map_id B, may be
+ * NULL: map 0; start B x 24 in / out; goal_step B x 3 and goal B x 3, both or neither; err_out B x 18, may be NULL; status B.
+ * Device form: all pointers but `s` in device memory, one kernel queued on `stream`; no handle state is read or written but the
+ * sampling tables, the heightfields and their geometry -- it may be queued while a call is open.  Host form: host pointers,
+ * synchronous, through device buffers of its own as qtos_track (no -5).
+ * Both: -1 on a null planner or required pointer, B < 1, capacity < 0, a ring without cursor, a table with n_rows < 1, first_row
+ * outside 0 .. 1000000, latency < 0, a gain outside 0 .. 1, a clip <= 0, a link length <= 0, goal_step without goal or the
+ * reverse; -2 on a HIP error; -3 out of memory. */
+int qtos_start_feedback_device(QtosPlanner *p, int B, const QtosFeedback *s, const double *d_nodes, const double *d_t0, const int *d_row,
+                               const long long *d_cursor /* NULL in table mode */, const double *d_meas,
+                               const int *d_map_id /* may be NULL: map 0 */, double *d_start /* in/out, B x 24 */,
+                               const double *d_goal_step /* may be NULL */, double *d_goal /* NULL iff d_goal_step is NULL */,
+                               double *d_err_out /* B x 18, may be NULL */, int *d_status, void *stream);
+int qtos_start_feedback(QtosPlanner *p, int B, const QtosFeedback *s, const double *nodes, const double *t0, const int *row,
+                        const long long *cursor, const double *meas, const int *map_id, double *start, const double *goal_step,
+                        double *goal, double *err_out, int *status);
+
 /* Goals of receding windows from their global paths: where the next plan goes.  Replaces Global_Planner.update / spine_step
  * (QTOS/planner.py:139-161, 195-230) and Combiner.plan_init / spine_step (QTOS/combiner.py:137-212, 223-225) for B windows at
  * once: a window's A* "spine" -- two cubic splines X_p, Y_p over one set of knots -- is read one horizon ahead of the new plan's

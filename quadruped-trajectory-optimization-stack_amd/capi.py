@@ -332,6 +332,54 @@ def track_params(hz=1000.0, first_row=0, n_rows=0, capacity=0, ee_shift=0.015, d
     return g
 
 
+class QtosFeedback(C.Structure):
+    """Parameters of a feedback hand-over (qtos_start_feedback*, include/qtos_planner.h); feedback.start_feedback reads the same
+    fields."""
+    _fields_ = [
+        ("hz", C.c_double), ("first_row", C.c_int), ("n_rows", C.c_int), ("capacity", C.c_longlong), ("latency", C.c_double),
+        ("ee_shift", C.c_double), ("hip", (C.c_double * 3) * 4), ("lateral", C.c_double * 4), ("l_upper", C.c_double),
+        ("l_lower", C.c_double), ("gain_pos", C.c_double), ("gain_ang", C.c_double), ("gain_foot", C.c_double),
+        ("max_pos", C.c_double), ("max_ang", C.c_double), ("max_foot", C.c_double), ("nominal", (C.c_double * 3) * 4),
+        ("max_deviation", C.c_double * 3), ("rom_tol", C.c_double), ("snap_tol", C.c_double), ("flags", C.c_int),
+    ]
+
+    def copy(self):
+        return QtosFeedback.from_buffer_copy(self)
+
+
+FEEDBACK_QUAT, FEEDBACK_SNAP, FEEDBACK_ZERO_FILTER = 1, 2, 4     # QTOS_FEEDBACK_* of include/qtos_planner.h
+
+
+def feedback_params(cfg=None, hz=1000.0, first_row=0, n_rows=0, capacity=0, latency=0.0, gain_pos=1.0, gain_ang=1.0, gain_foot=1.0,
+                    max_pos=0.05, max_ang=0.2, max_foot=0.05, snap=True, zero_filter=False, quaternion=False, robot=None, ee_shift=0.015,
+                    nominal=None, max_deviation=None, rom_tol=1e-6, snap_tol=0.02):
+    """A QtosFeedback with the SOLO12 leg (joints.SOLO12), towr_transform's ee_shift, full gains, clips of 0.05 m / 0.2 rad /
+    0.05 m and the snap as defaults.  cfg: the planner's PlannerConfig (None: the defaults'), which gives the range-of-motion
+    box, nominal and max_deviation, unless those are given.  capacity 0: table mode."""
+    from . import joints
+    from .config import PlannerConfig
+    robot = joints.SOLO12 if robot is None else robot
+    cfg = PlannerConfig() if cfg is None else cfg
+    nominal = cfg.nominal_stance if nominal is None else nominal
+    max_deviation = cfg.max_deviation if max_deviation is None else max_deviation
+    g = QtosFeedback()
+    g.hz, g.first_row, g.n_rows, g.capacity, g.latency = float(hz), int(first_row), int(n_rows), int(capacity), float(latency)
+    g.ee_shift = float(ee_shift)
+    for e in range(4):
+        for d in range(3):
+            g.hip[e][d] = float(robot.hip[e][d])
+            g.nominal[e][d] = float(nominal[e][d])
+        g.lateral[e] = float(robot.lateral[e])
+    g.l_upper, g.l_lower = float(robot.l_upper), float(robot.l_lower)
+    g.gain_pos, g.gain_ang, g.gain_foot = float(gain_pos), float(gain_ang), float(gain_foot)
+    g.max_pos, g.max_ang, g.max_foot = float(max_pos), float(max_ang), float(max_foot)
+    for d in range(3):
+        g.max_deviation[d] = float(max_deviation[d])
+    g.rom_tol, g.snap_tol = float(rom_tol), float(snap_tol)
+    g.flags = (FEEDBACK_QUAT if quaternion else 0) | (FEEDBACK_SNAP if snap else 0) | (FEEDBACK_ZERO_FILTER if zero_filter else 0)
+    return g
+
+
 class SelftestError(RuntimeError):
     """No elimination order passed the KKT self-test (qtos_planner_create_checked returned -6); `attempts`: the QtosSelftest
     records in the order they were tried."""
@@ -360,6 +408,7 @@ EXPORTS = [
     "qtos_probe", "qtos_probe_device", "qtos_probe_stamp", "qtos_probe_stamp_device",
     "qtos_terrain_env", "qtos_terrain_env_device", "qtos_set_heightfields_device",
     "qtos_joint_rows", "qtos_joint_rows_device", "qtos_track", "qtos_track_device",
+    "qtos_start_feedback", "qtos_start_feedback_device",
 ]
 
 _lib = None
@@ -488,6 +537,10 @@ def load():
         llp = C.POINTER(C.c_longlong)
         lib.qtos_track.argtypes = [vp, C.c_int, C.POINTER(QtosTrack), dp, dp, ip, ip, llp, dp, dp, llp, dp, dp, ip]
         lib.qtos_track_device.argtypes = [vp, C.c_int, C.POINTER(QtosTrack)] + [vp] * 12
+    if hasattr(lib, "qtos_start_feedback"):          # (the feedback hand-over; older builds loaded through QTOS_LIB lack it)
+        llp = C.POINTER(C.c_longlong)
+        lib.qtos_start_feedback.argtypes = [vp, C.c_int, C.POINTER(QtosFeedback), dp, dp, ip, llp, dp, ip, dp, dp, dp, dp, ip]
+        lib.qtos_start_feedback_device.argtypes = [vp, C.c_int, C.POINTER(QtosFeedback)] + [vp] * 12
     if hasattr(lib, "qtos_set_heightfields_device"):
         lib.qtos_set_heightfields_device.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, vp]
     _lib = lib
@@ -986,6 +1039,47 @@ class Planner:
                                       None if cur is None else cur.ctypes.data_as(llp), _dp(meas), _dp(goal), count.ctypes.data_as(llp),
                                       _dp(total), _dp(out), _ip(status)), "track")
         return out, status, count, total
+
+    def has_start_feedback(self):
+        return hasattr(self.lib, "qtos_start_feedback")
+
+    def start_feedback(self, nodes, t0, row, meas, params, start, cursor=None, map_id=None, goal_step=None, goal=None, err=None,
+                       status=None):
+        """Feedback hand-over (qtos_start_feedback, host form; the rule: feedback.start_feedback): the start vectors `start`
+        (B x 24, qtos_handover's) corrected by the tracking error of the plans `nodes` at their hand-over rows `row`, from the
+        measured rows `meas` -- (B, rows, 18), or (B, rows, 19) with params' quaternion flag, rows = params.n_rows (table mode) or
+        params.capacity (a ring, addressed with `cursor` as track() addresses it).  params: a QtosFeedback (feedback_params()).
+        map_id (B): the handle's heightfield of every window (None: map 0).  goal_step and goal (B x 3) go together: goal[:, 0:2]
+        = start[:, 0:2] + goal_step[:, 0:2] of the corrected start.  err (B x 18) and status (B) are the arrays as they stand
+        (None: zeros): a window without a measurement keeps its entries.  Returns new arrays (start, goal or None, err, status)."""
+        if not self.has_start_feedback():
+            raise RuntimeError("this build of the planner library has no feedback hand-over (qtos_start_feedback)")
+        nodes = np.ascontiguousarray(nodes, np.float64).reshape(-1, self.n)
+        B = nodes.shape[0]
+        t0 = np.ascontiguousarray(np.broadcast_to(np.asarray(t0, np.float64), (B,)))
+        i32 = lambda a: None if a is None else np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.int32), (B,)))
+        row, mid = i32(row), i32(map_id)
+        rows = int(params.capacity) if params.capacity > 0 else int(params.n_rows)
+        mcols = 19 if params.flags & FEEDBACK_QUAT else 18
+        meas = np.ascontiguousarray(meas, np.float64)
+        if meas.shape != (B, max(rows, 0), mcols):
+            raise ValueError("meas is (B, %d, %d)" % (rows, mcols))
+        cur = None
+        if params.capacity > 0:
+            if cursor is None:
+                raise ValueError("ring mode takes the ring's cursor")
+            cur = np.ascontiguousarray(np.broadcast_to(np.asarray(cursor, np.int64), (B,)))
+        if (goal_step is None) != (goal is None):
+            raise ValueError("goal_step and goal go together: give both or neither")
+        gs = None if goal_step is None else np.ascontiguousarray(goal_step, np.float64).reshape(B, 3)
+        gl = None if goal is None else np.array(goal, np.float64).reshape(B, 3)
+        start = np.array(start, np.float64).reshape(B, START_DOUBLES)
+        err = np.zeros((B, 18)) if err is None else np.array(err, np.float64).reshape(B, 18)
+        status = np.zeros(B, np.int32) if status is None else np.array(status, np.int32).reshape(B)
+        self._chk(self.lib.qtos_start_feedback(self.h, B, C.byref(params), _dp(nodes), _dp(t0), _ip(row),
+                                               None if cur is None else cur.ctypes.data_as(C.POINTER(C.c_longlong)), _dp(meas), _ip(mid),
+                                               _dp(start), _dp(gs), _dp(gl), _dp(err), _ip(status)), "start_feedback")
+        return start, gl, err, status
 
     def has_path_goal(self):
         return hasattr(self.lib, "qtos_path_goal")

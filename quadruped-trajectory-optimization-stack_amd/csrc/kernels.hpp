@@ -325,8 +325,10 @@ __device__ inline void vec_prepass(const i4_t *__restrict__ V, const d2_t *__res
 struct Terr {
   double h, hx, hy, hxy;
 };
-// bilinear height, clamped at the border (zero slope outside the map)
-__device__ inline Terr terrain_at(const DevPlan &P, int map, double x, double y) {
+// bilinear height, clamped at the border (zero slope outside the map).  PlanT: DevPlan, or the few fields of it that are read
+// here (FeedbackTerrain: k_start_feedback takes them in its arguments, the whole DevPlan does not fit next to them)
+template <class PlanT>
+__device__ inline Terr terrain_at(const PlanT &P, int map, double x, double y) {
   Terr t = {0, 0, 0, 0};
   if (!P.height || P.n_maps <= 0) return t;
   map = min(max(map, 0), P.n_maps - 1);   // a stale / out-of-range map id must not read outside the maps
@@ -2460,6 +2462,154 @@ __global__ __launch_bounds__(TILE) void k_track(const SamplePlan *Sd, TrackArgs 
     total[2 * b] = run;
   }
   if (threadIdx.x == FEET_LANE) total[2 * b + 1] = FEET_LANE ? run : run_feet;
+}
+
+// Feedback hand-over (qtos_start_feedback*): the start vector k_handover wrote is corrected by the tracking error of the plan
+// handed over from, so that the next plan starts where the robot is.  The statement of the rule is feedback.py.  One lane per
+// window, as k_path_goal: the work of a window is one plan row (k_sample's evaluator), four legs (track_leg, k_track's own
+// lines: the measured pose is k_track's columns 1 .. 18 to the bit) and four terrain look-ups (terrain_at, the solver's), a few
+// hundred operations behind a launch; a wider layout was not measured.  Every function switches contraction off: one rounded
+// operation per operation of the rule, in its order (the bilinear terrain_at keeps the solver's own build).  A window that
+// falls back or has no measurement stores nothing to its start.  No LDS, no atomics, no scratch: the arrays of the arguments
+// and the local vectors are indexed with constants only (templates over the leg, unrolled loops), the tables come through
+// pointers.  No handle state is read or written but the sampling tables, the heightfields and their geometry.
+struct FeedbackTerrain {   // what terrain_at reads of DevPlan
+  const double *height;
+  double hcell, hx0, hy0;
+  int n_maps, hnx, hny, terrain_mode;
+};
+struct FeedbackArgs {   // QtosFeedback as the kernel reads it (qtos_planner.hip feedback_args)
+  TrackArgs K;          // the leg chain, hz, the addressing and bit 0 of the flags (the quaternion), as k_track reads them
+  FeedbackTerrain T;
+  double gain_pos, gain_ang, gain_foot, max_pos, max_ang, max_foot;
+  double nominal[NEE][3], max_deviation[3], rom_tol, snap_tol;
+  int lat;              // round(latency * hz)
+  int snap, zero_filter;
+};
+
+__device__ inline double feedback_clip(double e, double c, int &st) {   // a NaN stays a NaN
+  if (e < -c) { st |= 2; return -c; }
+  if (e > c) { st |= 2; return c; }
+  return e;
+}
+
+// Foot E of the corrected start c (24 doubles): x and y by the gain, z by the gain or, with the snap, the terrain under the
+// corrected x, y (status bit 6 + E where that moves z by more than snap_tol), then the range-of-motion test of the foot against
+// the corrected base: d = R^T (foot - com) - nominal[E], false where a |d_i| is not within max_deviation[i] + rom_tol.
+template <int E>
+__device__ inline bool feedback_foot(const FeedbackArgs &A, int map, const double *s, const double *e, const double R[9], double *c,
+                                     int &st) {
+#pragma clang fp contract(off)
+  constexpr int o = 6 + 3 * E;
+  if (A.gain_foot != 0) {
+    c[o] = s[o] + A.gain_foot * e[o];
+    c[o + 1] = s[o + 1] + A.gain_foot * e[o + 1];
+    c[o + 2] = s[o + 2] + A.gain_foot * e[o + 2];
+  } else {
+    c[o] = s[o]; c[o + 1] = s[o + 1]; c[o + 2] = s[o + 2];
+  }
+  if (A.snap) {
+    const double z = terrain_at(A.T, map, c[o], c[o + 1]).h;
+    if (fabs(z - c[o + 2]) > A.snap_tol) st |= 64 << E;
+    c[o + 2] = z;
+  }
+  const double v0 = c[o] - c[0], v1 = c[o + 1] - c[1], v2 = c[o + 2] - c[2];
+  const double d0 = ((R[0] * v0 + R[3] * v1) + R[6] * v2) - A.nominal[E][0];
+  const double d1 = ((R[1] * v0 + R[4] * v1) + R[7] * v2) - A.nominal[E][1];
+  const double d2 = ((R[2] * v0 + R[5] * v1) + R[8] * v2) - A.nominal[E][2];
+  return fabs(d0) <= A.max_deviation[0] + A.rom_tol && fabs(d1) <= A.max_deviation[1] + A.rom_tol &&
+         fabs(d2) <= A.max_deviation[2] + A.rom_tol;
+}
+
+__global__ __launch_bounds__(64) void k_start_feedback(const SamplePlan *Sd, FeedbackArgs A, const double *nodes, const double *t0,
+                                                       const int *row_in, const long long *cursor, const double *meas,
+                                                       const int *map_id, double *start, const double *goal_step, double *goal,
+                                                       double *err_out, int *status, int B) {
+#pragma clang fp contract(off)
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const SamplePlan &S = *Sd;
+  // The window's places in the outputs, as lane values from the start: with the uniform pointers kept to the end, and with the
+  // plan row evaluated in front of the legs (the sampling tables and the leg data live together), the scalar registers run out
+  // and the kernel gets a scratch frame.
+  double *sb = start + (size_t)b * QTOS_START_DOUBLES, *eo = err_out ? err_out + (size_t)b * 18 : nullptr;
+  double *gb = goal_step ? goal + (size_t)b * 3 : nullptr;
+  const double *gs = goal_step ? goal_step + (size_t)b * 3 : nullptr;
+  int *stb = status + b;
+  const int map = map_id ? map_id[b] : 0;
+  const long long r = row_in[b];
+  const long long rows_b = A.K.capacity > 0 ? A.K.capacity : (long long)A.K.n_rows;   // rows of window b's table or ring
+  long long k = r - A.lat;                                                            // the measured plan row
+  if (k > A.K.first_row + r - 1) k = A.K.first_row + r - 1;
+  if (k < A.K.first_row) k = A.K.first_row;
+  const long long j = k - A.K.first_row;                                              // its place in the segment
+  if (r <= 0 || j >= rows_b) { *stb = 32; return; }                              // no measurement: nothing else is touched
+  long long o = j;
+  if (A.K.capacity > 0) {
+    long long pos = cursor[b] % A.K.capacity;
+    if (pos < 0) pos += A.K.capacity;
+    o = pos + j;                                                                      // (pos, j < capacity: one subtraction wraps it)
+    if (o >= A.K.capacity) o -= A.K.capacity;
+  }
+  const bool quat = (A.K.flags & 1) != 0;
+  const double *mr = meas + ((size_t)b * (size_t)rows_b + (size_t)o) * (quat ? 19 : 18);
+  double row[25] = {0}, dst[TRACK_COLS], R[9];   // (track_leg's error column against `row` is not used here: the row comes behind the legs)
+  int st = track_pose(mr, quat, R, dst + 4);                                          // (bit 2: the pitch clip acted)
+  dst[1] = mr[0]; dst[2] = mr[1]; dst[3] = mr[2];
+  const double *q = mr + (quat ? 7 : 6);
+  track_leg<0>(A.K, row, mr, R, q, dst);
+  track_leg<1>(A.K, row, mr, R, q, dst);
+  track_leg<2>(A.K, row, mr, R, q, dst);
+  track_leg<3>(A.K, row, mr, R, q, dst);
+  sample_row_state_at(S, nodes + (size_t)b * S.n_vars, t0[b], k > INT_MAX ? INT_MAX : (int)k, A.K.hz, row);
+  double e[18];
+#pragma unroll
+  for (int i = 0; i < 18; ++i) e[i] = dst[1 + i] - row[1 + i];
+  e[5] = remainder(e[5], 6.283185307179586);
+#pragma unroll
+  for (int i = 0; i < 18; ++i) e[i] = feedback_clip(e[i], i < 3 ? A.max_pos : (i < 6 ? A.max_ang : A.max_foot), st);
+  if (eo) {
+#pragma unroll
+    for (int i = 0; i < 18; ++i) eo[i] = e[i];
+  }
+  double s[QTOS_START_DOUBLES], c[QTOS_START_DOUBLES];
+#pragma unroll
+  for (int i = 0; i < QTOS_START_DOUBLES; ++i) { s[i] = sb[i]; c[i] = s[i]; }
+  if (A.gain_pos != 0) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) c[i] = s[i] + A.gain_pos * e[i];
+  }
+  if (A.gain_ang != 0) {
+#pragma unroll
+    for (int i = 3; i < 6; ++i) c[i] = s[i] + A.gain_ang * e[i];
+  }
+  double Rc[9], unused[3];
+  track_pose(c, false, Rc, unused);                                                   // R of the corrected Euler angles
+  bool ok = feedback_foot<0>(A, map, s, e, Rc, c, st);
+  ok = feedback_foot<1>(A, map, s, e, Rc, c, st) && ok;
+  ok = feedback_foot<2>(A, map, s, e, Rc, c, st) && ok;
+  ok = feedback_foot<3>(A, map, s, e, Rc, c, st) && ok;
+  // (the fallback's goal comes from two loads of its own: with s[0] here the two branches end in the same load, the compiler
+  // merges them into one load through a choice of two addresses, and s and c stay in scratch for it)
+  double gx = sb[0], gy = sb[1];
+  if (A.gain_pos == 0 && A.gain_ang == 0 && A.gain_foot == 0) {
+    st &= 6;                                                                          // (uniform) nothing to add: the start stays, to the bit
+  } else if (!ok) {
+    st |= 8;                                                                          // fallback: the start stays as it is
+  } else {
+    st |= 1;
+#pragma unroll
+    for (int i = 0; i < QTOS_START_DOUBLES; ++i) {
+      if (A.zero_filter && fabs(c[i]) < 1e-4) c[i] = 0.0;                             // QTOS/utils.py zero_filter
+      if (i < 18 || A.zero_filter) sb[i] = c[i];
+    }
+    gx = c[0]; gy = c[1];
+  }
+  if (gs) {
+    gb[0] = gx + gs[0];
+    gb[1] = gy + gs[1];
+  }
+  *stb = st;
 }
 
 // Goals of receding windows from their global paths (qtos_path_goal*; Global_Planner.update / spine_step, QTOS/planner.py:139-161,

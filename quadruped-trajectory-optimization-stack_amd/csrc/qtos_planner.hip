@@ -1873,6 +1873,96 @@ int qtos_track(QtosPlanner *p, int B, const QtosTrack *s, const double *nodes, c
   return rc;
 }
 
+// ---- feedback hand-over: the next plan starts from the measured state (k_start_feedback, kernels.hpp) ------
+// The argument checks of both forms, and QtosFeedback as k_start_feedback reads it.
+static int feedback_args(const QtosPlanner *p, int B, const QtosFeedback *s, const void *nodes, const void *t0, const void *row,
+                         const void *cursor, const void *meas, const void *start, const void *goal_step, const void *goal,
+                         const void *status, FeedbackArgs *A) {
+  if (!p || B < 1 || !s || !nodes || !t0 || !row || !meas || !start || !status || (goal_step == nullptr) != (goal == nullptr)) return -1;
+  if (s->capacity < 0 || (s->capacity > 0 && !cursor) || (s->capacity == 0 && s->n_rows < 1)) return -1;
+  if (s->first_row < 0 || s->first_row > 1000000 || !(s->latency >= 0)) return -1;
+  if (!(s->l_upper > 0) || !(s->l_lower > 0)) return -1;
+  for (double g : {s->gain_pos, s->gain_ang, s->gain_foot})
+    if (!(g >= 0 && g <= 1)) return -1;
+  if (!(s->max_pos > 0) || !(s->max_ang > 0) || !(s->max_foot > 0)) return -1;
+  TrackArgs &K = A->K;
+  K.hz = s->hz > 0 ? s->hz : 1000.0;
+  K.ee_shift = s->ee_shift; K.l_upper = s->l_upper; K.l_lower = s->l_lower;
+  for (int e = 0; e < NEE; ++e) {
+    for (int d = 0; d < 3; ++d) { K.hip[e][d] = s->hip[e][d]; A->nominal[e][d] = s->nominal[e][d]; }
+    K.lateral[e] = s->lateral[e];
+  }
+  K.capacity = s->capacity; K.first_row = s->first_row; K.n_rows = s->n_rows; K.delay = 0;
+  K.flags = (s->flags & QTOS_FEEDBACK_QUAT) ? 1 : 0;
+  const double lat = std::round(s->latency * K.hz);
+  A->lat = lat > 2e9 ? 2000000000 : (int)lat;
+  A->gain_pos = s->gain_pos; A->gain_ang = s->gain_ang; A->gain_foot = s->gain_foot;
+  A->max_pos = s->max_pos; A->max_ang = s->max_ang; A->max_foot = s->max_foot;
+  for (int d = 0; d < 3; ++d) A->max_deviation[d] = s->max_deviation[d];
+  A->rom_tol = s->rom_tol; A->snap_tol = s->snap_tol;
+  A->snap = (s->flags & QTOS_FEEDBACK_SNAP) != 0; A->zero_filter = (s->flags & QTOS_FEEDBACK_ZERO_FILTER) != 0;
+  const DevPlan &D = p->dp;
+  A->T.height = D.height; A->T.hcell = D.hcell; A->T.hx0 = D.hx0; A->T.hy0 = D.hy0;
+  A->T.n_maps = D.n_maps; A->T.hnx = D.hnx; A->T.hny = D.hny; A->T.terrain_mode = D.terrain_mode;
+  return 0;
+}
+
+int qtos_start_feedback_device(QtosPlanner *p, int B, const QtosFeedback *s, const double *d_nodes, const double *d_t0, const int *d_row,
+                               const long long *d_cursor, const double *d_meas, const int *d_map_id, double *d_start,
+                               const double *d_goal_step, double *d_goal, double *d_err_out, int *d_status, void *stream_) {
+  FeedbackArgs A;
+  if (feedback_args(p, B, s, d_nodes, d_t0, d_row, d_cursor, d_meas, d_start, d_goal_step, d_goal, d_status, &A)) return -1;
+  HIPCHK(p, hipSetDevice(p->device));
+  hipLaunchKernelGGL(k_start_feedback, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream_, p->d_sp, A, d_nodes, d_t0, d_row, d_cursor,
+                     d_meas, d_map_id, d_start, d_goal_step, d_goal, d_err_out, d_status, B);
+  HIPCHK(p, hipGetLastError());
+  return 0;
+}
+
+int qtos_start_feedback(QtosPlanner *p, int B, const QtosFeedback *s, const double *nodes, const double *t0, const int *row,
+                        const long long *cursor, const double *meas, const int *map_id, double *start, const double *goal_step,
+                        double *goal, double *err_out, int *status) {
+  FeedbackArgs A;
+  if (feedback_args(p, B, s, nodes, t0, row, cursor, meas, start, goal_step, goal, status, &A)) return -1;
+  HIPCHK(p, hipSetDevice(p->device));
+  // buffers of its own, as qtos_track: the handle's staging buffers are not touched, so it may run while a call is open
+  const size_t n = p->M.n_vars, rows = (size_t)B * (size_t)(A.K.capacity > 0 ? A.K.capacity : A.K.n_rows);
+  const size_t mcols = A.K.flags ? 19 : 18;
+  double *d_nodes = nullptr, *d_t0 = nullptr, *d_meas = nullptr, *d_start = nullptr, *d_gs = nullptr, *d_goal = nullptr, *d_err = nullptr;
+  int *d_row = nullptr, *d_map = nullptr, *d_st = nullptr;
+  long long *d_cur = nullptr;
+  auto up = [&](void **dst, const void *src, size_t bytes) -> int {
+    HIPCHK(p, hipMalloc(dst, bytes));
+    HIPCHK(p, hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
+    return 0;
+  };
+  auto run = [&]() -> int {
+    int rc;
+    if ((rc = up((void **)&d_nodes, nodes, (size_t)B * n * sizeof(double)))) return rc;
+    if ((rc = up((void **)&d_t0, t0, B * sizeof(double)))) return rc;
+    if ((rc = up((void **)&d_row, row, B * sizeof(int)))) return rc;
+    if ((rc = up((void **)&d_meas, meas, rows * mcols * sizeof(double)))) return rc;
+    if ((rc = up((void **)&d_start, start, (size_t)B * QTOS_START_DOUBLES * sizeof(double)))) return rc;
+    if ((rc = up((void **)&d_st, status, B * sizeof(int)))) return rc;
+    if (cursor && (rc = up((void **)&d_cur, cursor, B * sizeof(long long)))) return rc;
+    if (map_id && (rc = up((void **)&d_map, map_id, B * sizeof(int)))) return rc;
+    if (goal_step && (rc = up((void **)&d_gs, goal_step, (size_t)B * 3 * sizeof(double)))) return rc;
+    if (goal && (rc = up((void **)&d_goal, goal, (size_t)B * 3 * sizeof(double)))) return rc;
+    if (err_out && (rc = up((void **)&d_err, err_out, (size_t)B * 18 * sizeof(double)))) return rc;
+    if ((rc = qtos_start_feedback_device(p, B, s, d_nodes, d_t0, d_row, d_cur, d_meas, d_map, d_start, d_gs, d_goal, d_err, d_st, nullptr)))
+      return rc;
+    HIPCHK(p, hipMemcpy(start, d_start, (size_t)B * QTOS_START_DOUBLES * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(p, hipMemcpy(status, d_st, B * sizeof(int), hipMemcpyDeviceToHost));
+    if (goal) HIPCHK(p, hipMemcpy(goal, d_goal, (size_t)B * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (err_out) HIPCHK(p, hipMemcpy(err_out, d_err, (size_t)B * 18 * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+  };
+  const int rc = run();
+  (void)hipFree(d_nodes); (void)hipFree(d_t0); (void)hipFree(d_row); (void)hipFree(d_meas); (void)hipFree(d_start); (void)hipFree(d_st);
+  (void)hipFree(d_cur); (void)hipFree(d_map); (void)hipFree(d_gs); (void)hipFree(d_goal); (void)hipFree(d_err);
+  return rc;
+}
+
 // ---- goals of receding windows from their global paths (k_path_goal, kernels.hpp) ------------------------
 // The argument checks of both forms, and QtosPathGoal as k_path_goal reads it.
 static int path_goal_args(const QtosPlanner *p, int B, const QtosPathGoal *g, const void *knots, const void *coef, const void *n_pieces,

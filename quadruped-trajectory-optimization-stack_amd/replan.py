@@ -205,11 +205,21 @@ class ShiftedWindows:
                on.  The dict's entries are ``capi.track_params``' keywords (ee_shift, delay, rule, quaternion, robot), ``goal_x`` (a
                number or one per window: status bit 1 of a row whose measured CoM x has reached it) and ``fill`` (a callable
                taking the windows, called on the set's stream in front of every track call: the last place to write
-               ``meas_traj``, e.g. from the joint ring just filled); ``track_rows(b)`` reads a window's ring."""
+               ``meas_traj``, e.g. from the joint ring just filled); ``track_rows(b)`` reads a window's ring.
+    feedback   None (the default): every plan starts from the old plan's own hand-over row, nothing is queued and nothing is
+               allocated.  A dict (needs ``track``, whose measured ring it reads): behind every hand-over the start vectors are
+               corrected by the tracking error at the hand-over row (k_start_feedback through qtos_start_feedback_device, the rule:
+               ``feedback.start_feedback``), in place on ``self.start`` and, without a path, ``self.goal``;
+               ``self.feedback_status`` (B, int32: bit 0 corrected, 1 clipped, 2 gimbal, 3 fell back, 5 no measurement, 6 + f foot
+               f snapped by more than snap_tol) and ``self.feedback_err`` (B x 18: the clipped error) live on the device.  The
+               dict's entries are ``capi.feedback_params``' keywords (gain_pos, gain_ang, gain_foot, max_pos, max_ang, max_foot,
+               latency, snap, zero_filter, rom_tol, snap_tol, nominal, max_deviation, cfg; the leg and the quaternion flag are the
+               track's).  The order of a replan is then hand-over, joint rows, track (whose ``fill`` writes the measurements of the
+               segment), feedback, path goal (so that ``path_base="state"`` sees the corrected start), stitch."""
 
     def __init__(self, planner, start, goal_step, map_id=None, advance=2.5, search=0.4, stream=None, warm="none", x_range=None,
                  handover=None, contact="force", height_set=(0.0,), trajectory=None, stitch="clean", path=None, path_base="spine",
-                 path_hold=True, joints=None, track=None):
+                 path_hold=True, joints=None, track=None, feedback=None):
         import torch
         self.torch = torch
         self.P = planner
@@ -297,6 +307,20 @@ class ShiftedWindows:
             self.track_goal_x = None
             if goal_x is not None:
                 self.track_goal_x = torch.as_tensor(np.broadcast_to(np.asarray(goal_x, np.float64), (B,)).copy(), **f64)
+        self._feedback = None
+        if feedback is not None:
+            from . import capi
+            if self.track_traj is None:
+                raise ValueError("feedback needs the measured ring of track (track=dict(...))")
+            if not hasattr(planner.lib, "qtos_start_feedback_device"):
+                raise RuntimeError("this build of the planner library has no feedback hand-over (qtos_start_feedback_device)")
+            kw = dict(feedback)
+            kw.setdefault("cfg", getattr(planner, "cfg", None))
+            t = self._track
+            self._feedback = capi.feedback_params(hz=self.hz, first_row=int(self._stitch.first_row), capacity=int(trajectory),
+                                                  quaternion=bool(t.flags & capi.TRACK_QUAT), ee_shift=float(t.ee_shift), robot=t, **kw)
+            self.feedback_status = torch.zeros((B,), dtype=torch.int32, device=dev)
+            self.feedback_err = torch.zeros((B, 18), **f64)
         self.stream = stream if stream is not None else torch.cuda.current_stream(dev)
         self.have_plan = False
         self.x_range = x_range     # (lo, hi): a window that walks past an end of its heightfield turns round (no resets)
@@ -483,6 +507,18 @@ class ShiftedWindows:
                                                 self.track_count.data_ptr(), self.track_total.data_ptr(), self.track_traj.data_ptr(),
                                                 self.track_status.data_ptr(), sp), "qtos_track_device")
 
+    def _start_feedback(self, sp):
+        """Queue k_start_feedback behind the track call and in front of the stitch: self.start (and, without a path, self.goal)
+        from the measured ring's row of the hand-over (the kernel reads the cursor and the clock the stitch behind it moves on)."""
+        import ctypes as C
+        moves = self.path is None
+        self._call(self.P.lib.qtos_start_feedback_device(self.P.h, self.B, C.byref(self._feedback), self.nodes.data_ptr(), self.t0.data_ptr(),
+                                                         self.row.data_ptr(), self.cursor.data_ptr(), self.meas_traj.data_ptr(),
+                                                         None if self.map_id is None else self.map_id.data_ptr(), self.start.data_ptr(),
+                                                         self.goal_step.data_ptr() if moves else None,
+                                                         self.goal.data_ptr() if moves else None, self.feedback_err.data_ptr(),
+                                                         self.feedback_status.data_ptr(), sp), "qtos_start_feedback_device")
+
     def track_rows(self, b):
         """Window b's newest min(cursor, trajectory) track rows in time order and their status words, as numpy (the stream is
         synchronised): row for row the measured poses and errors of ``trajectory_rows(b)``."""
@@ -600,7 +636,7 @@ class ShiftedWindows:
                                                       self.offset.data_ptr(), self.row.data_ptr(), sp), "qtos_handover_device")
             else:
                 self._handover_rows(sp)
-            if self.path is not None:
+            if self.path is not None and self._feedback is None:
                 # where the next plan goes: the window's path one horizon ahead of the hand-over, behind it on the same stream
                 self._path_goal(self.path_params, self.offset, sp)
             if self.traj is not None:
@@ -609,6 +645,11 @@ class ShiftedWindows:
                     self._joint_rows(self._joint, self.row.data_ptr(), sp)
                 if self.track_traj is not None:
                     self._track_rows(self._track, self.row.data_ptr(), sp)
+                if self._feedback is not None:
+                    # the start moves to where the robot is; the path goal follows it, so that path_base="state" sees it
+                    self._start_feedback(sp)
+                    if self.path is not None:
+                        self._path_goal(self.path_params, self.offset, sp)
                 self._call(P.lib.qtos_stitch_device(P.h, B, C.byref(self._stitch), self.nodes.data_ptr(), self.row.data_ptr(),
                                                     self.t0.data_ptr(), self.traj.data_ptr(), self.cursor.data_ptr(), sp),
                            "qtos_stitch_device")
