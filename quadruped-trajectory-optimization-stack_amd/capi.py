@@ -570,6 +570,15 @@ def _ip(a):
     return None if a is None else a.ctypes.data_as(C.POINTER(C.c_int))
 
 
+def _llp(a):
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_longlong))
+
+
+def _i32(a, B):
+    """An int or an array of B ints as a contiguous int32 array of B (None stays None)."""
+    return None if a is None else np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.int32), (B,)))
+
+
 def params_from_config(cfg):
     p = QtosParams()
     for e in range(NEE):
@@ -956,8 +965,8 @@ class Planner:
         cursor = np.array(np.broadcast_to(np.asarray(cursor, np.int64), (B,)))
         per = None if np.ndim(n_rows) == 0 else np.ascontiguousarray(n_rows, np.int32).reshape(B)
         s = stitch_params(traj.shape[1], first_row, 0 if per is not None else n_rows, hz, advance_clock)
-        self._chk(self.lib.qtos_stitch(self.h, B, C.byref(s), _dp(nodes), _ip(per), _dp(t0), _dp(traj),
-                                       cursor.ctypes.data_as(C.POINTER(C.c_longlong))), "stitch")
+        self._chk(self.lib.qtos_stitch(self.h, B, C.byref(s), _dp(nodes), _ip(per), _dp(t0), _dp(traj), _llp(cursor)),
+                  "stitch")
         return traj, cursor, t0
 
     def has_joint_rows(self):
@@ -979,9 +988,8 @@ class Planner:
         t0 = np.ascontiguousarray(np.broadcast_to(np.asarray(t0, np.float64), (B,)))
         if params is None:
             params = joint_params(n_rows=int(round(self.dims.duration * 1000.0)) + 1)
-        i32 = lambda a: None if a is None else np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.int32), (B,)))
         f12 = lambda a: None if a is None else np.ascontiguousarray(a, np.float64).reshape(B, 12)
-        first, per, qm, qdm = i32(first_row), i32(n_rows), f12(q_mes), f12(qd_mes)
+        first, per, qm, qdm = _i32(first_row, B), _i32(n_rows, B), f12(q_mes), f12(qd_mes)
         rows = int(params.capacity) if params.capacity > 0 else int(params.n_rows)
         cur = None
         if params.capacity > 0:
@@ -993,8 +1001,7 @@ class Planner:
         if out.shape != (B, rows, CSV_COLS) or status.shape != (B, rows):
             raise ValueError("out is (B, %d, %d) and status (B, %d)" % (rows, CSV_COLS, rows))
         self._chk(self.lib.qtos_joint_rows(self.h, B, C.byref(params), _dp(nodes), _dp(t0), _ip(first), _ip(per),
-                                           None if cur is None else cur.ctypes.data_as(C.POINTER(C.c_longlong)), _dp(qm), _dp(qdm),
-                                           _dp(out), _ip(status)), "joint_rows")
+                                           _llp(cur), _dp(qm), _dp(qdm), _dp(out), _ip(status)), "joint_rows")
         return out, status
 
     def has_track(self):
@@ -1015,8 +1022,7 @@ class Planner:
         nodes = np.ascontiguousarray(nodes, np.float64).reshape(-1, self.n)
         B = nodes.shape[0]
         t0 = np.ascontiguousarray(np.broadcast_to(np.asarray(t0, np.float64), (B,)))
-        i32 = lambda a: None if a is None else np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.int32), (B,)))
-        first, per = i32(first_row), i32(n_rows)
+        first, per = _i32(first_row, B), _i32(n_rows, B)
         rows = int(params.capacity) if params.capacity > 0 else int(params.n_rows)
         mcols = 19 if params.flags & TRACK_QUAT else 18
         meas = np.ascontiguousarray(meas, np.float64)
@@ -1034,10 +1040,8 @@ class Planner:
         status = np.zeros((B, max(rows, 0)), np.int32) if status is None else np.array(status, np.int32)
         if out.shape != (B, rows, TRACK_COLS) or status.shape != (B, rows):
             raise ValueError("out is (B, %d, %d) and status (B, %d)" % (rows, TRACK_COLS, rows))
-        llp = C.POINTER(C.c_longlong)
         self._chk(self.lib.qtos_track(self.h, B, C.byref(params), _dp(nodes), _dp(t0), _ip(first), _ip(per),
-                                      None if cur is None else cur.ctypes.data_as(llp), _dp(meas), _dp(goal), count.ctypes.data_as(llp),
-                                      _dp(total), _dp(out), _ip(status)), "track")
+                                      _llp(cur), _dp(meas), _dp(goal), _llp(count), _dp(total), _dp(out), _ip(status)), "track")
         return out, status, count, total
 
     def has_start_feedback(self):
@@ -1057,8 +1061,7 @@ class Planner:
         nodes = np.ascontiguousarray(nodes, np.float64).reshape(-1, self.n)
         B = nodes.shape[0]
         t0 = np.ascontiguousarray(np.broadcast_to(np.asarray(t0, np.float64), (B,)))
-        i32 = lambda a: None if a is None else np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.int32), (B,)))
-        row, mid = i32(row), i32(map_id)
+        row, mid = _i32(row, B), _i32(map_id, B)
         rows = int(params.capacity) if params.capacity > 0 else int(params.n_rows)
         mcols = 19 if params.flags & FEEDBACK_QUAT else 18
         meas = np.ascontiguousarray(meas, np.float64)
@@ -1077,8 +1080,8 @@ class Planner:
         err = np.zeros((B, 18)) if err is None else np.array(err, np.float64).reshape(B, 18)
         status = np.zeros(B, np.int32) if status is None else np.array(status, np.int32).reshape(B)
         self._chk(self.lib.qtos_start_feedback(self.h, B, C.byref(params), _dp(nodes), _dp(t0), _ip(row),
-                                               None if cur is None else cur.ctypes.data_as(C.POINTER(C.c_longlong)), _dp(meas), _ip(mid),
-                                               _dp(start), _dp(gs), _dp(gl), _dp(err), _ip(status)), "start_feedback")
+                                               _llp(cur), _dp(meas), _ip(mid), _dp(start), _dp(gs), _dp(gl), _dp(err), _ip(status)),
+                  "start_feedback")
         return start, gl, err, status
 
     def has_path_goal(self):

@@ -1,0 +1,1537 @@
+// window_kernels.hpp -- gfx950 device code around the solve: the sampler and the kernels of the receding loop (the "windows").
+// They read plans through SamplePlan; of the solver's kernels (kernels.hpp) they use the terrain look-up (terrain_at) only.
+//
+//   k_sample        : 1 kHz spline sampling into the 37-column CSV row layout
+//   k_handover      : start, goal and clock offset of the next window from the plan that is running
+//   k_stitch        : the rows a window executed, appended to its trajectory ring
+//   k_joint_rows    : joint commands of the windows' plans (leg IK and motor law)
+//   k_track         : measured states and tracking errors of the windows
+//   k_start_feedback: the next plan's start from the measured state
+//   k_path_goal     : goals of the windows from their global paths
+//   k_path_plan     : the global paths (A* and spines)
+//   k_probe*        : the probe and the stamp of the windows' heightfields
+//   k_terrain_env   : the randomised terrains of the windows
+//
+// The argument checks and launches are in window_api.hpp.
+#pragma once
+#include "kernels.hpp"
+
+namespace qtos {
+
+// =================================================================================================
+// CSV sampling: row layout of QTOS/utils.py:107-148.  Spline lookup tables are built on the host.
+struct SampleSpline {
+  int n_polys;
+  const double *tend;  // cumulative end time of each polynomial; behind them, tend[n_polys + k]: what the float64 start
+                       // tend[k] - dur[k] of polynomial k is off its exact start by (sample_spline<true>)
+  const double *dur;
+  const int *idx;      // (n_polys+1) x 6
+};
+struct SamplePlan {
+  SampleSpline lin, ang, eem[NEE], eef[NEE];
+  int n_vars;
+  double T;
+};
+
+// EXACT_START: the local time is taken from the polynomial's exact start (the float64 start and its correction word), so it
+// carries the rounding of t alone and not that of the cumulative table as well.  The first derivative of a force polynomial of
+// a short stance (12 ms on a 1 s horizon) has a slope of 6 / T^2 = 4e4 per second at its nodes, times node values tens of
+// newtons apart: the table's half ulp of t was 2e-10 .. 5e-10 N/s in k_shift_warm's force derivatives (tests/test_gpu_splines.py).
+// The rows of k_sample, k_stitch and k_handover hold values and base velocities only and keep the plain form, bit for bit.
+template <bool EXACT_START = false>
+__device__ inline void sample_spline(const SampleSpline &S, const double *x, double t, int deriv, double out[3]) {
+  // first polynomial whose end time >= t - eps (towr spline.cc GetSegmentID)
+  int lo = 0, hi = S.n_polys - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (S.tend[mid] >= t - 1e-10) hi = mid; else lo = mid + 1;
+  }
+  const int k = lo;
+  const double T = S.dur[k];
+  double tau = t - (S.tend[k] - T);
+  if (EXACT_START) tau -= S.tend[S.n_polys + k];
+  double w[4];
+  const double T2 = T * T, T3 = T2 * T, t2 = tau * tau, t3 = t2 * tau;
+  if (deriv == 0) {
+    w[0] = 1 - 3 * t2 / T2 + 2 * t3 / T3; w[1] = tau - 2 * t2 / T + t3 / T2;
+    w[2] = 3 * t2 / T2 - 2 * t3 / T3; w[3] = -t2 / T + t3 / T2;
+  } else {
+    w[0] = -6 * tau / T2 + 6 * t2 / T3; w[1] = 1 - 4 * tau / T + 3 * t2 / T2;
+    w[2] = 6 * tau / T2 - 6 * t2 / T3; w[3] = -2 * tau / T + 3 * t2 / T2;
+  }
+  for (int d = 0; d < 3; ++d) {
+    double acc = 0;
+    for (int a = 0; a < 4; ++a) {
+      const int v = S.idx[(k + (a >> 1)) * 6 + (a & 1) * 3 + d];
+      if (v >= 0) acc += w[a] * x[v];
+    }
+    out[d] = acc;
+  }
+}
+
+// Columns 1 .. 24 of a CSV row (the state a plan starts from, QTOS/combiner.py:263-274) at plan time t: k_sample's rows and
+// the one row k_handover evaluates per window go through these lines, so the two agree to the bit.
+__device__ inline void sample_row_state(const SamplePlan &S, const double *x, double t, double *row) {
+  sample_spline(S.lin, x, t, 0, row + 1);
+  sample_spline(S.ang, x, t, 0, row + 4);
+  for (int e = 0; e < NEE; ++e) sample_spline(S.eem[e], x, t, 0, row + 7 + 3 * e);
+  sample_spline(S.lin, x, t, 1, row + 19);
+  sample_spline(S.ang, x, t, 1, row + 22);
+}
+
+// Row k of a plan's CSV (QTOS/utils.py:107-148) but its forces: the time stamp t0 + k / hz in column 0 and the state in columns
+// 1 .. 24 at plan time min(k / hz, T).  Returns that plan time: the caller evaluates the four force splines of columns 25 .. 36
+// at it, in a loop of its own over S.eef -- with that loop in here k_sample, which takes the tables by value, loads all of
+// them into scalar registers at its start (93 instead of 35) and is no longer the code it was.  k_sample's table and the rows
+// k_stitch appends go through these lines and the same line for the forces, so the two agree to the bit.
+__device__ inline double sample_row_state_at(const SamplePlan &S, const double *x, double t0, int k, double hz, double *row) {
+  double t = k / hz;
+  if (t > S.T) t = S.T;
+  row[0] = t0 + k / hz;
+  sample_row_state(S, x, t, row);
+  return t;
+}
+
+__global__ __launch_bounds__(256) void k_sample(SamplePlan S, const double *nodes, const double *t0, double hz,
+                                                int n_rows, double *rows, int B) {
+  const int b = blockIdx.y;
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B || k >= n_rows) return;
+  const double *x = nodes + (size_t)b * S.n_vars;
+  double row[QTOS_CSV_COLS];
+  const double t = sample_row_state_at(S, x, t0[b], k, hz, row);
+  for (int e = 0; e < NEE; ++e) sample_spline(S.eef[e], x, t, 0, row + 25 + 3 * e);
+  double *out = rows + ((size_t)b * n_rows + k) * QTOS_CSV_COLS;
+  for (int i = 0; i < QTOS_CSV_COLS; ++i) out[i] = row[i];
+}
+
+// Hand-over of a receding-horizon replan (qtos_handover*; QTOS/combiner.py:78-92, 245-296): one workgroup per window picks
+// the row of the window's newest plan the next plan starts from -- the first of the candidate rows k0 .. k0 + n_search with
+// all four feet in contact, k0 where none passes -- and evaluates that one row: no table of rows is written.  Lanes stride
+// over the candidates and evaluate only what the rule reads (z of the four force splines / of the four foot splines, the
+// very expressions of k_sample: the rule sees the numbers a sampled table would hold); the winning row's columns 1 .. 24
+// come from k_sample's own evaluator.  No scratch: the sampling tables come through a pointer (by value, as k_sample
+// takes them, the ten splines and these arguments do not fit the scalar registers), and the heights are read with constant
+// indices (a loop over an array in the kernel arguments copies it to scratch, see k_shift_warm).
+struct HandoverArgs {   // QtosHandover as the kernel reads it (window_api.hpp handover_args)
+  double hz, x_lo, x_hi;
+  double h6[8];         // rint(height * 1e6); NaN (equal to nothing) beyond n_heights
+  int rule, zero_filter, turn;
+  int k0, n_search;     // candidate rows k0 .. k0 + n_search
+};
+
+__device__ inline bool handover_contact(const SamplePlan &S, const HandoverArgs &H, const double *x, double t) {
+  bool all = true;
+#pragma unroll
+  for (int e = 0; e < NEE; ++e) {
+    double o3[3];
+    if (H.rule == 0) {   // (uniform over the workgroup)
+      sample_spline(S.eef[e], x, t, 0, o3);
+      all = all && o3[2] > 0;
+    } else {
+      sample_spline(S.eem[e], x, t, 0, o3);
+      const double z6 = rint(o3[2] * 1e6);
+      all = all && (z6 == H.h6[0] || z6 == H.h6[1] || z6 == H.h6[2] || z6 == H.h6[3] || z6 == H.h6[4] || z6 == H.h6[5] ||
+                    z6 == H.h6[6] || z6 == H.h6[7]);
+    }
+  }
+  return all;
+}
+
+__global__ __launch_bounds__(512) void k_handover(const SamplePlan *Sd, HandoverArgs H, const double *nodes, double *goal_step,
+                                                  double *start_out, double *goal_out, double *offset_out, int *row_out, int B) {
+  const int b = blockIdx.x;
+  if (b >= B) return;
+  __shared__ int first;
+  const SamplePlan &S = *Sd;
+  const double *x = nodes + (size_t)b * S.n_vars;
+  if (threadIdx.x == 0) first = INT_MAX;
+  __syncthreads();
+  for (int k = H.k0 + threadIdx.x; k <= H.k0 + H.n_search; k += blockDim.x) {   // (ascending per lane: its first hit is its smallest)
+    double t = k / H.hz;
+    if (t > S.T) t = S.T;
+    if (handover_contact(S, H, x, t)) { atomicMin(&first, k); break; }
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  const int k = first == INT_MAX ? H.k0 : first;
+  double t = k / H.hz;
+  if (t > S.T) t = S.T;
+  double row[1 + QTOS_START_DOUBLES];
+  sample_row_state(S, x, t, row);
+  double *st = start_out + (size_t)b * QTOS_START_DOUBLES;
+#pragma unroll
+  for (int i = 0; i < QTOS_START_DOUBLES; ++i) {
+    if (H.zero_filter && fabs(row[1 + i]) < 1e-4) row[1 + i] = 0.0;     // QTOS/utils.py zero_filter
+    st[i] = row[1 + i];
+  }
+  offset_out[b] = (double)k / H.hz;
+  if (row_out) row_out[b] = k;
+  if (goal_step) {
+    double *gs = goal_step + (size_t)b * 3;
+    double gx = gs[0];
+    if (H.turn) {   // a window past an end of its heightfield turns round
+      const double sgn = row[1] > H.x_hi ? -1.0 : (row[1] < H.x_lo ? 1.0 : (gx > 0 ? 1.0 : (gx < 0 ? -1.0 : 0.0)));
+      gx = sgn * fabs(gx);
+      gs[0] = gx;
+    }
+    goal_out[(size_t)b * 3 + 0] = row[1] + gx;
+    goal_out[(size_t)b * 3 + 1] = row[2] + gs[1];
+  }
+}
+
+// Stitching of receding windows (qtos_stitch*; Combiner.combine, QTOS/combiner.py:125-135, 298-312): one workgroup per window
+// appends rows first_row .. first_row + n - 1 of the window's plan -- the segment that was executed before the next plan took
+// over -- to the window's ring of CSV rows, then moves the window's cursor and clock on.  One workgroup per window, so the
+// cursor and the clock are updated in place: every lane reads them before the barrier, lane 0 writes them at the end.
+// A lane evaluates one row of a tile with k_sample's evaluator (sample_row_state_at) and puts it into LDS; the tile then goes out
+// flat, consecutive lanes on consecutive doubles of the ring (k_sample's row per lane is 37 stores at a stride of 296 bytes;
+// this kernel is bound by its stores).  The LDS image keeps the rows' pitch of 37 doubles = 74 dwords: the 16 lanes of a
+// ds_write_b64 group land on banks 10 l mod 32 and the bank after each, all 32 distinct, and the flat read-back is
+// consecutive.  Element e of a tile goes to double (base * 37 + e) mod (capacity * 37) of the ring, base the ring row of
+// the tile's first row: a tile that straddles the wrap needs nothing else.  No scratch: the tables come through a pointer
+// and the row array is indexed with constants only (see k_handover).
+constexpr int STITCH_TILE = 512;   // rows per tile = lanes per workgroup: 512 x 37 x 8 = 151 552 bytes of LDS, one workgroup per CU
+struct StitchArgs {                // QtosStitch as the kernel reads it (window_api.hpp stitch_args)
+  double hz;
+  long long capacity;
+  int first_row, n_rows, advance_clock;
+};
+
+__global__ __launch_bounds__(STITCH_TILE) void k_stitch(const SamplePlan *Sd, StitchArgs A, const double *nodes, const int *n_rows,
+                                                        double *t0, double *traj, long long *cursor, int B) {
+  const int b = blockIdx.x;
+  if (b >= B) return;
+  __shared__ double tile[STITCH_TILE * QTOS_CSV_COLS];
+  const SamplePlan &S = *Sd;
+  const double *x = nodes + (size_t)b * S.n_vars;
+  const long long cur = cursor[b];
+  const double t0b = t0[b];
+  long long n = n_rows ? n_rows[b] : A.n_rows;
+  n = n < 0 ? 0 : (n > A.capacity ? A.capacity : n);
+  __syncthreads();                                       // (every lane holds the cursor and the clock: lane 0 may write them)
+  double *ring = traj + (size_t)b * (size_t)A.capacity * QTOS_CSV_COLS;
+  const long long ring_doubles = A.capacity * QTOS_CSV_COLS;
+  long long pos = cur % A.capacity;                      // ring row of the segment's first row
+  if (pos < 0) pos += A.capacity;
+  for (long long j0 = 0; j0 < n; j0 += STITCH_TILE) {    // (n is uniform over the workgroup: so are the barriers)
+    const int m = n - j0 < STITCH_TILE ? (int)(n - j0) : STITCH_TILE;
+    if ((int)threadIdx.x < m) {
+      const long long k = (long long)A.first_row + j0 + threadIdx.x;
+      double row[QTOS_CSV_COLS];
+      const double t = sample_row_state_at(S, x, t0b, k > INT_MAX ? INT_MAX : (int)k, A.hz, row);
+      for (int e = 0; e < NEE; ++e) sample_spline(S.eef[e], x, t, 0, row + 25 + 3 * e);
+      double *dst = tile + threadIdx.x * QTOS_CSV_COLS;
+#pragma unroll
+      for (int i = 0; i < QTOS_CSV_COLS; ++i) dst[i] = row[i];
+    }
+    __syncthreads();
+    long long base = pos + j0;                           // (pos < capacity and j0 < n <= capacity: one subtraction wraps it)
+    if (base >= A.capacity) base -= A.capacity;
+    base *= QTOS_CSV_COLS;
+    for (int e = threadIdx.x; e < m * QTOS_CSV_COLS; e += STITCH_TILE) {
+      long long o = base + e;                            // (m <= capacity: o < 2 ring_doubles)
+      if (o >= ring_doubles) o -= ring_doubles;
+      ring[o] = tile[e];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    cursor[b] = cur + n;
+    if (A.advance_clock) t0[b] = t0b + (double)n / A.hz;
+  }
+}
+
+// Joint commands of the windows' plans (qtos_joint_rows*; scripts/run.py:184-200, QTOS/robot/robot.py control_multi): per CSV row
+// the feet in the base frame of the planned pose (towr_transform, QTOS/utils.py:412-436), the closed-form inverse kinematics
+// of the SOLO12 leg (HAA about x, HFE and KFE about y; the reference asks PyBullet), the joint rates qdot = J^-1 v_b, the
+// feed-forward torques -J^T R^T f and the motor law (MotorModel.convert_to_torque_ff).  The statement of the rule, with its
+// derivation, is joints.py.  A lane evaluates one row: its time stamp and Cartesian state with k_sample's evaluator
+// (sample_row_state_at and the line for the forces: qtos_sample_csv's numbers to the bit), the four foot splines once more
+// with deriv = 1, then the chain for four legs, written into the row's place in an LDS tile as it is computed; the tile goes
+// out flat, consecutive lanes on consecutive doubles, as k_stitch's (whose pitch of 37 doubles it keeps).  The tile has one
+// row per lane of the workgroup: 512, or one wave where no window has more rows than that (the 1 kHz tick).
+// Two addressing modes: capacity 0, row first_row + j of window b goes to out[b][j] of a B x n_rows x 37 table; capacity > 0, to
+// ring row (cursor[b] + j) mod capacity of a B x capacity x 37 ring -- k_stitch's addressing, but cursor and t0 are only read,
+// so the grid runs over tiles and windows in both modes, and in front of k_stitch on one stream the joint ring is filled row
+// for row with the CSV ring.  The status goes out one int per lane, to the same row of a B x (n_rows | capacity) array.
+// No atomics and no scratch: the tables come through a pointer (see k_handover), the arrays of the arguments are read with
+// constant indices only (joint_leg is a template over the leg), and the math library's sincos, which returns the cosine
+// through a pointer, is not used.
+struct JointArgs {   // QtosJointRows as the kernel reads it (window_api.hpp joint_args)
+  double hz, ee_shift, l_upper, l_lower, tau_max;
+  double hip[NEE][3], lateral[NEE], knee_sign[NEE], kp[3 * NEE], kd[3 * NEE];
+  long long capacity;
+  int first_row, n_rows, flags;
+};
+constexpr int JOINT_TILE = 512;   // rows per tile = lanes per workgroup (see STITCH_TILE); JOINT_TICK where a window has one wave of rows
+constexpr int JOINT_TICK = 64;    // at the most: 18 944 bytes of LDS, several workgroups per CU
+
+// MotorModel.convert_to_torque_ff as joints.motor_torque states it: every operation one rounded IEEE operation in numpy's
+// order (the library is built with the compiler's default, which fuses a * b + c: switched off here), np.clip's comparisons.
+__device__ inline double joint_motor(double kp, double kd, double q, double qd, double tff, double tau_max, bool pd, double qm,
+                                     double qdm) {
+#pragma clang fp contract(off)
+  double tau = tff;
+  if (pd) {
+    const double a = kp * (q - qm), b = kd * (qd - qdm);
+    tau = (a + b) + tff;
+  }
+  if (tau_max > 0) tau = tau < -tau_max ? -tau_max : (tau > tau_max ? tau_max : tau);
+  return tau;
+}
+
+// R = Rz(yaw) Ry(pitch) Rx(roll) of a row's Euler angles (row-major) and the angular velocity in the base frame from its Euler
+// rates.  Like joint_leg without contraction: which product of a sum the compiler fuses is its choice per instantiation, and
+// the 64-lane tick then differed from the 512-lane table in the last bit of qdot; one rounded operation each, they agree.
+__device__ inline void joint_pose(const double *row, double R[9], double wb[3]) {
+#pragma clang fp contract(off)
+  const double sa = sin(row[4]), ca = cos(row[4]), sb = sin(row[5]), cb = cos(row[5]), sc = sin(row[6]), cc = cos(row[6]);
+  R[0] = cc * cb; R[1] = cc * sb * sa - sc * ca; R[2] = cc * sb * ca + sc * sa;
+  R[3] = sc * cb; R[4] = sc * sb * sa + cc * ca; R[5] = sc * sb * ca - cc * sa;
+  R[6] = -sb; R[7] = cb * sa; R[8] = cb * ca;
+  wb[0] = row[22] - row[24] * sb; wb[1] = row[23] * ca + row[24] * cb * sa; wb[2] = row[24] * cb * ca - row[23] * sa;
+}
+
+// Leg E of a row: R the rotation of the planned pose (row-major), wb the angular velocity in the base frame, fv the foot's
+// velocity.  Writes q, qdot and tau of the leg's three joints to dst (the row's place in the tile); returns the status bits.
+template <int E>
+__device__ inline int joint_leg(const JointArgs &A, const double *row, const double R[9], const double wb[3], const double fv[3],
+                                const double *q_mes, const double *qd_mes, double *dst) {
+#pragma clang fp contract(off)
+  const double d = A.lateral[E], lu = A.l_upper, ll = A.l_lower;
+  const double *pf = row + 7 + 3 * E, *f = row + 25 + 3 * E;
+  const double dx = pf[0] - row[1], dy = pf[1] - row[2], dz = pf[2] - row[3];
+  const double ux = fv[0] - row[19], uy = fv[1] - row[20], uz = fv[2] - row[21];
+  // r_b = R^T (foot - com); v_b = R^T (foot_vel - com_vel) - wb x r_b; p_b = r_b + (0, 0, ee_shift)
+  const double bx = R[0] * dx + R[3] * dy + R[6] * dz, by = R[1] * dx + R[4] * dy + R[7] * dz, bz = R[2] * dx + R[5] * dy + R[8] * dz;
+  const double vx = R[0] * ux + R[3] * uy + R[6] * uz - (wb[1] * bz - wb[2] * by);
+  const double vy = R[1] * ux + R[4] * uy + R[7] * uz - (wb[2] * bx - wb[0] * bz);
+  const double vz = R[2] * ux + R[5] * uy + R[8] * uz - (wb[0] * by - wb[1] * bx);
+  const double rx = bx - A.hip[E][0], ry = by - A.hip[E][1], rz = bz + A.ee_shift - A.hip[E][2];
+  // inverse kinematics (joints.leg_ik)
+  const double h2 = ry * ry + rz * rz - d * d;
+  const double h = sqrt(fmax(h2, 0.0));
+  const double c3 = (rx * rx + fmax(h2, 0.0) - lu * lu - ll * ll) / (2 * lu * ll);
+  const int status = (c3 > 1 ? 1 : 0) | (c3 < -1 ? 1 << 4 : 0) | (h2 < 0 ? 1 << 8 : 0);
+  const double q1 = atan2(ry * h + rz * d, ry * d - rz * h);
+  const double q3 = A.knee_sign[E] * acos(fmin(fmax(c3, -1.0), 1.0));
+  const double s3 = sin(q3), c3c = cos(q3);
+  const double q2 = atan2(-rx, h) - atan2(ll * s3, lu + ll * c3c);
+  // the chain at q (joints._hip_frame): the foot at (x, d, -hh) in the hip frame
+  const double s1 = sin(q1), c1 = cos(q1), s2 = sin(q2), c2 = cos(q2), s23 = sin(q2 + q3), c23 = cos(q2 + q3);
+  const double x = -lu * s2 - ll * s23, hh = lu * c2 + ll * c23, ls = ll * s23, lc = ll * c23;
+  // joint rates (joints.joint_rates): zero for a leg with a status bit
+  double qd1 = 0, qd2 = 0, qd3 = 0;
+  if (!status) {
+    const double wy = c1 * vy + s1 * vz, wz = c1 * vz - s1 * vy, det = -(lu * ll * s3);
+    qd1 = wy / hh;
+    const double r2 = wz - d * qd1;
+    qd2 = (vx * ls + lc * r2) / det;
+    qd3 = (x * vx - hh * r2) / det;
+  }
+  // feed-forward torques (joints.feed_forward)
+  double t1 = 0, t2 = 0, t3 = 0;
+  if (!(A.flags & 1)) {
+    const double fx = R[0] * f[0] + R[3] * f[1] + R[6] * f[2], fy = R[1] * f[0] + R[4] * f[1] + R[7] * f[2],
+                 fz = R[2] * f[0] + R[5] * f[1] + R[8] * f[2];
+    const double gy = c1 * fy + s1 * fz, gz = c1 * fz - s1 * fy;
+    t1 = -(hh * gy + d * gz); t2 = hh * fx + x * gz; t3 = lc * fx - ls * gz;
+  }
+  const bool pd = q_mes != nullptr;
+  const double m1 = pd ? q_mes[3 * E] : 0, m2 = pd ? q_mes[3 * E + 1] : 0, m3 = pd ? q_mes[3 * E + 2] : 0;
+  const double n1 = pd ? qd_mes[3 * E] : 0, n2 = pd ? qd_mes[3 * E + 1] : 0, n3 = pd ? qd_mes[3 * E + 2] : 0;
+  dst[1 + 3 * E] = q1; dst[2 + 3 * E] = q2; dst[3 + 3 * E] = q3;
+  dst[13 + 3 * E] = qd1; dst[14 + 3 * E] = qd2; dst[15 + 3 * E] = qd3;
+  dst[25 + 3 * E] = joint_motor(A.kp[3 * E], A.kd[3 * E], q1, qd1, t1, A.tau_max, pd, m1, n1);
+  dst[26 + 3 * E] = joint_motor(A.kp[3 * E + 1], A.kd[3 * E + 1], q2, qd2, t2, A.tau_max, pd, m2, n2);
+  dst[27 + 3 * E] = joint_motor(A.kp[3 * E + 2], A.kd[3 * E + 2], q3, qd3, t3, A.tau_max, pd, m3, n3);
+  return status << E;
+}
+
+template <int TILE>
+__global__ __launch_bounds__(TILE) void k_joint_rows(const SamplePlan *Sd, JointArgs A, const double *nodes, const double *t0,
+                                                     const int *first_row, const int *n_rows, const long long *cursor,
+                                                     const double *q_mes, const double *qd_mes, double *out, int *status_out, int B) {
+  __shared__ double joint_tile[TILE * QTOS_CSV_COLS];
+  const int b = blockIdx.y;
+  if (b >= B) return;
+  const SamplePlan &S = *Sd;
+  const long long rows_b = A.capacity > 0 ? A.capacity : (long long)A.n_rows;      // rows of window b's table or ring
+  long long n = n_rows ? n_rows[b] : A.n_rows;
+  n = n < 0 ? 0 : (n > rows_b ? rows_b : n);
+  const long long j0 = (long long)blockIdx.x * blockDim.x;                         // first row of this tile, of the n rows
+  if (j0 >= n) return;                                                             // (uniform over the workgroup)
+  const int m = n - j0 < (long long)blockDim.x ? (int)(n - j0) : (int)blockDim.x;
+  long long pos = 0;                                                               // table or ring row of the segment's first row
+  if (A.capacity > 0) {
+    pos = cursor[b] % A.capacity;
+    if (pos < 0) pos += A.capacity;
+  }
+  long long base = pos + j0;                                                       // (pos < rows_b and j0 < n <= rows_b: one subtraction wraps it)
+  if (base >= rows_b) base -= rows_b;
+  if ((int)threadIdx.x < m) {
+    const double *x = nodes + (size_t)b * S.n_vars;
+    long long first = first_row ? first_row[b] : A.first_row;
+    first = first < 0 ? 0 : first;
+    const long long k = first + j0 + threadIdx.x;
+    double row[QTOS_CSV_COLS];
+    const double t = sample_row_state_at(S, x, t0[b], k > INT_MAX ? INT_MAX : (int)k, A.hz, row);
+    for (int e = 0; e < NEE; ++e) sample_spline(S.eef[e], x, t, 0, row + 25 + 3 * e);
+    double fv[NEE][3];
+    for (int e = 0; e < NEE; ++e) sample_spline(S.eem[e], x, t, 1, fv[e]);
+    double R[9], wb[3];
+    joint_pose(row, R, wb);
+    const double *qm = q_mes ? q_mes + (size_t)b * 3 * NEE : nullptr, *qdm = q_mes ? qd_mes + (size_t)b * 3 * NEE : nullptr;
+    double *dst = joint_tile + threadIdx.x * QTOS_CSV_COLS;
+    dst[0] = row[0];
+    int st = joint_leg<0>(A, row, R, wb, fv[0], qm, qdm, dst);
+    st |= joint_leg<1>(A, row, R, wb, fv[1], qm, qdm, dst);
+    st |= joint_leg<2>(A, row, R, wb, fv[2], qm, qdm, dst);
+    st |= joint_leg<3>(A, row, R, wb, fv[3], qm, qdm, dst);
+    long long o = base + threadIdx.x;
+    if (o >= rows_b) o -= rows_b;
+    status_out[(size_t)b * (size_t)rows_b + o] = st;
+  }
+  __syncthreads();
+  double *dst = out + (size_t)b * (size_t)rows_b * QTOS_CSV_COLS;
+  const long long all = rows_b * QTOS_CSV_COLS;
+  base *= QTOS_CSV_COLS;
+  for (int e = threadIdx.x; e < m * QTOS_CSV_COLS; e += blockDim.x) {
+    long long o = base + e;                                                        // (m <= rows_b: o < 2 all)
+    if (o >= all) o -= all;
+    dst[o] = joint_tile[e];
+  }
+}
+
+// Measured states and tracking errors of the windows (qtos_track*; scripts/run.py:244-273, QTOS/tracking.py Tracking.update /
+// _update, QTOS/robot/robot.py traj_vec): the counterpart of k_joint_rows for what comes back from the robot.  Per CSV row the
+// measured base pose and joint angles become the reference's traj_vec (CoM, Euler angles, the four feet in the world by the
+// leg's closed-form forward kinematics, joints.leg_fk), the five Euclidean errors against the plan's own row and the two
+// running totals.  The statement of the rule is tracking.py.  The totals are sequential sums by definition, so one workgroup
+// owns one window and walks its tiles in order.  Per tile: (A) a lane takes a row -- time stamp and planned positions with
+// k_sample's evaluator (sample_row_state_at: qtos_sample_csv's numbers to the bit), R from the measured pose, four legs through
+// a template over the leg, and the 24 values and five errors into the row's place of an LDS tile; (B) behind a barrier lane 0
+// runs the CoM chain over the tile's rows and the first lane of the second wave the feet chain (lane 0 again where the
+// workgroup is one wave), each from the total it carries in a register from the previous tile, into columns 24 and 25; (C) the
+// tile goes out flat, consecutive lanes on consecutive doubles, the pitch of 26 doubles kept (k_stitch's addressing: table or
+// ring, cursor and t0 only read).  The status is one int per lane.  The owners of the chains write count and total back with
+// plain stores behind the last tile; every lane has read them in front of the first barrier.  No atomics, no scratch (constant
+// indices only, see k_joint_rows), no sincos.
+struct TrackArgs {   // QtosTrack as the kernel reads it (window_api.hpp track_args)
+  double hz, ee_shift, l_upper, l_lower;
+  double hip[NEE][3], lateral[NEE];
+  long long capacity;
+  int first_row, n_rows, delay, flags;
+};
+constexpr int TRACK_COLS = 26;
+constexpr int TRACK_TILE = 512;   // rows per tile = lanes per workgroup: 512 x 26 x 8 = 106 496 bytes of LDS, one workgroup per CU
+constexpr int TRACK_TICK = 64;    // one wave where no window has more rows (the tick): 13 312 bytes
+
+// R (row-major) of the measured pose and the Euler columns.  Euler mode (m[3 .. 5] roll, pitch, yaw): R = Rz Ry Rx as
+// joint_pose forms it, the angles copied through.  Quaternion mode (m[3 .. 6] = x, y, z, w): divided by its norm, R directly,
+// roll = atan2(R21, R22), pitch = asin(clip(-R20)), yaw = atan2(R10, R00); returns 4 (GIMBAL) where the clip acts.  Without
+// contraction, as joint_pose: one rounded operation each, in tracking.py's order.
+__device__ inline int track_pose(const double *m, bool quat, double R[9], double *euler) {
+#pragma clang fp contract(off)
+  if (!quat) {
+    const double sa = sin(m[3]), ca = cos(m[3]), sb = sin(m[4]), cb = cos(m[4]), sc = sin(m[5]), cc = cos(m[5]);
+    R[0] = cc * cb; R[1] = cc * sb * sa - sc * ca; R[2] = cc * sb * ca + sc * sa;
+    R[3] = sc * cb; R[4] = sc * sb * sa + cc * ca; R[5] = sc * sb * ca - cc * sa;
+    R[6] = -sb; R[7] = cb * sa; R[8] = cb * ca;
+    euler[0] = m[3]; euler[1] = m[4]; euler[2] = m[5];
+    return 0;
+  }
+  double x = m[3], y = m[4], z = m[5], w = m[6];
+  const double n = sqrt(((x * x + y * y) + z * z) + w * w);
+  x = x / n; y = y / n; z = z / n; w = w / n;
+  R[0] = 1 - 2 * (y * y + z * z); R[1] = 2 * (x * y - z * w); R[2] = 2 * (x * z + y * w);
+  R[3] = 2 * (x * y + z * w); R[4] = 1 - 2 * (x * x + z * z); R[5] = 2 * (y * z - x * w);
+  R[6] = 2 * (x * z - y * w); R[7] = 2 * (y * z + x * w); R[8] = 1 - 2 * (x * x + y * y);
+  euler[0] = atan2(R[7], R[8]);
+  euler[1] = asin(fmin(fmax(-R[6], -1.0), 1.0));
+  euler[2] = atan2(R[3], R[0]);
+  return fabs(R[6]) >= 1 ? 4 : 0;
+}
+
+// |a - b| of two points: sqrt((d0 d0 + d1 d1) + d2 d2), one rounded operation after the other (tracking.errors).
+__device__ inline double track_norm(const double *a, const double *b) {
+#pragma clang fp contract(off)
+  const double d0 = a[0] - b[0], d1 = a[1] - b[1], d2 = a[2] - b[2];
+  return sqrt((d0 * d0 + d1 * d1) + d2 * d2);
+}
+
+// Foot E of a measured row in the world: com + R (leg_fk(E, q) - (0, 0, ee_shift)), q the leg's three measured angles
+// (joints.leg_fk: hip + Rx(q1) (x, d, -h)).  Writes the foot to dst[7 + 3 E ..] and its error against the planned foot to
+// dst[20 + E] (dst: the row's place in the tile).
+template <int E>
+__device__ inline void track_leg(const TrackArgs &A, const double *row, const double *com, const double R[9], const double *q,
+                                 double *dst) {
+#pragma clang fp contract(off)
+  const double d = A.lateral[E], lu = A.l_upper, ll = A.l_lower;
+  const double q1 = q[3 * E], q2 = q[3 * E + 1], q3 = q[3 * E + 2];
+  const double s1 = sin(q1), c1 = cos(q1), s2 = sin(q2), c2 = cos(q2), s23 = sin(q2 + q3), c23 = cos(q2 + q3);
+  const double x = -lu * s2 - ll * s23, h = lu * c2 + ll * c23;
+  const double px = A.hip[E][0] + x, py = A.hip[E][1] + c1 * d + s1 * h, pz = (A.hip[E][2] + s1 * d - c1 * h) - A.ee_shift;
+  double foot[3];
+  foot[0] = com[0] + ((R[0] * px + R[1] * py) + R[2] * pz);
+  foot[1] = com[1] + ((R[3] * px + R[4] * py) + R[5] * pz);
+  foot[2] = com[2] + ((R[6] * px + R[7] * py) + R[8] * pz);
+  dst[7 + 3 * E] = foot[0]; dst[8 + 3 * E] = foot[1]; dst[9 + 3 * E] = foot[2];
+  dst[20 + E] = track_norm(row + 7 + 3 * E, foot);
+}
+
+// Whether the 1-based call c of a window is recorded (tracking.recorded): Tracking.update's branches as they stand, c >= delay
+// and c != delay + 1, or with QTOS_TRACK_CLEAN_DELAY c > delay.
+__device__ inline bool track_recorded(long long c, int delay, bool clean) {
+  return clean ? c > delay : (c >= delay && c != (long long)delay + 1);
+}
+
+template <int TILE>
+__global__ __launch_bounds__(TILE) void k_track(const SamplePlan *Sd, TrackArgs A, const double *nodes, const double *t0,
+                                                const int *first_row, const int *n_rows, const long long *cursor, const double *meas,
+                                                const double *goal_x, long long *count, double *total, double *out, int *status_out,
+                                                int B) {
+  __shared__ double track_tile[TILE * TRACK_COLS];
+  constexpr int FEET_LANE = TILE > 64 ? 64 : 0;                                    // the feet chain's owner: a lane of another wave
+  const int b = blockIdx.x;
+  if (b >= B) return;
+  const SamplePlan &S = *Sd;
+  const long long rows_b = A.capacity > 0 ? A.capacity : (long long)A.n_rows;      // rows of window b's table or ring
+  long long n = n_rows ? n_rows[b] : A.n_rows;
+  n = n < 0 ? 0 : (n > rows_b ? rows_b : n);
+  if (n == 0) return;                                                              // (uniform: a window without rows keeps its accumulators)
+  const bool quat = (A.flags & 1) != 0, clean = (A.flags & 2) != 0;
+  const int mcols = quat ? 19 : 18;
+  const long long calls = count[2 * b];                                            // (every lane, in front of the first barrier)
+  long long rec = count[2 * b + 1];
+  double run = total[2 * b + (threadIdx.x == FEET_LANE && FEET_LANE ? 1 : 0)];     // the chain this lane owns, if it owns one
+  double run_feet = total[2 * b + 1];                                              // (one wave: lane 0 owns both)
+  long long pos = 0;                                                               // table or ring row of the segment's first row
+  if (A.capacity > 0) {
+    pos = cursor[b] % A.capacity;
+    if (pos < 0) pos += A.capacity;
+  }
+  const double *x = nodes + (size_t)b * S.n_vars;
+  long long first = first_row ? first_row[b] : A.first_row;
+  first = first < 0 ? 0 : first;
+  const double t0b = t0[b];
+  const double *meas_b = meas + (size_t)b * (size_t)rows_b * mcols;
+  double *out_b = out + (size_t)b * (size_t)rows_b * TRACK_COLS;
+  const long long all = rows_b * TRACK_COLS;
+  for (long long j0 = 0; j0 < n; j0 += TILE) {                                     // (n is uniform over the workgroup: so are the barriers)
+    const int m = n - j0 < TILE ? (int)(n - j0) : TILE;
+    long long base = pos + j0;                                                     // (pos < rows_b and j0 < n <= rows_b: one subtraction wraps it)
+    if (base >= rows_b) base -= rows_b;
+    if ((int)threadIdx.x < m) {                                                    // (A) a lane takes a row
+      const long long k = first + j0 + threadIdx.x;
+      double row[25];
+      sample_row_state_at(S, x, t0b, k > INT_MAX ? INT_MAX : (int)k, A.hz, row);
+      long long o = base + threadIdx.x;
+      if (o >= rows_b) o -= rows_b;
+      const double *mr = meas_b + (size_t)o * mcols;
+      double *dst = track_tile + threadIdx.x * TRACK_COLS;
+      double R[9];
+      int st = track_pose(mr, quat, R, dst + 4);
+      dst[0] = row[0];
+      dst[1] = mr[0]; dst[2] = mr[1]; dst[3] = mr[2];
+      dst[19] = track_norm(row + 1, mr);
+      const double *q = mr + (quat ? 7 : 6);
+      track_leg<0>(A, row, mr, R, q, dst);
+      track_leg<1>(A, row, mr, R, q, dst);
+      track_leg<2>(A, row, mr, R, q, dst);
+      track_leg<3>(A, row, mr, R, q, dst);
+      if (track_recorded(calls + j0 + threadIdx.x + 1, A.delay, clean)) st |= 1;
+      if (goal_x && mr[0] >= goal_x[b]) st |= 2;
+      status_out[(size_t)b * (size_t)rows_b + o] = st;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {                                                        // (B) the chains, in program order
+      for (int i = 0; i < m; ++i) {
+        double *r = track_tile + i * TRACK_COLS;
+        if (track_recorded(calls + j0 + i + 1, A.delay, clean)) { run += r[19]; ++rec; }
+        r[24] = run;
+      }
+    }
+    if (threadIdx.x == FEET_LANE) {
+      double f = FEET_LANE ? run : run_feet;
+      for (int i = 0; i < m; ++i) {
+        double *r = track_tile + i * TRACK_COLS;
+        if (track_recorded(calls + j0 + i + 1, A.delay, clean)) { f += r[20]; f += r[21]; f += r[22]; f += r[23]; }
+        r[25] = f;
+      }
+      if (FEET_LANE) run = f; else run_feet = f;
+    }
+    __syncthreads();
+    base *= TRACK_COLS;                                                            // (C) the tile goes out flat
+    for (int e = threadIdx.x; e < m * TRACK_COLS; e += TILE) {
+      long long o = base + e;                                                      // (m <= rows_b: o < 2 all)
+      if (o >= all) o -= all;
+      out_b[o] = track_tile[e];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    count[2 * b] = calls + n;
+    count[2 * b + 1] = rec;
+    total[2 * b] = run;
+  }
+  if (threadIdx.x == FEET_LANE) total[2 * b + 1] = FEET_LANE ? run : run_feet;
+}
+
+// Feedback hand-over (qtos_start_feedback*): the start vector k_handover wrote is corrected by the tracking error of the plan
+// handed over from, so that the next plan starts where the robot is.  The statement of the rule is feedback.py.  One lane per
+// window, as k_path_goal: the work of a window is one plan row (k_sample's evaluator), four legs (track_leg, k_track's own
+// lines: the measured pose is k_track's columns 1 .. 18 to the bit) and four terrain look-ups (terrain_at, the solver's), a few
+// hundred operations behind a launch; a wider layout was not measured.  Every function switches contraction off: one rounded
+// operation per operation of the rule, in its order (the bilinear terrain_at keeps the solver's own build).  A window that
+// falls back or has no measurement stores nothing to its start.  No LDS, no atomics, no scratch: the arrays of the arguments
+// and the local vectors are indexed with constants only (templates over the leg, unrolled loops), the tables come through
+// pointers.  No handle state is read or written but the sampling tables, the heightfields and their geometry.
+struct FeedbackTerrain {   // what terrain_at reads of DevPlan
+  const double *height;
+  double hcell, hx0, hy0;
+  int n_maps, hnx, hny, terrain_mode;
+};
+struct FeedbackArgs {   // QtosFeedback as the kernel reads it (window_api.hpp feedback_args)
+  TrackArgs K;          // the leg chain, hz, the addressing and bit 0 of the flags (the quaternion), as k_track reads them
+  FeedbackTerrain T;
+  double gain_pos, gain_ang, gain_foot, max_pos, max_ang, max_foot;
+  double nominal[NEE][3], max_deviation[3], rom_tol, snap_tol;
+  int lat;              // round(latency * hz)
+  int snap, zero_filter;
+};
+
+__device__ inline double feedback_clip(double e, double c, int &st) {   // a NaN stays a NaN
+  if (e < -c) { st |= 2; return -c; }
+  if (e > c) { st |= 2; return c; }
+  return e;
+}
+
+// Foot E of the corrected start c (24 doubles): x and y by the gain, z by the gain or, with the snap, the terrain under the
+// corrected x, y (status bit 6 + E where that moves z by more than snap_tol), then the range-of-motion test of the foot against
+// the corrected base: d = R^T (foot - com) - nominal[E], false where a |d_i| is not within max_deviation[i] + rom_tol.
+template <int E>
+__device__ inline bool feedback_foot(const FeedbackArgs &A, int map, const double *s, const double *e, const double R[9], double *c,
+                                     int &st) {
+#pragma clang fp contract(off)
+  constexpr int o = 6 + 3 * E;
+  if (A.gain_foot != 0) {
+    c[o] = s[o] + A.gain_foot * e[o];
+    c[o + 1] = s[o + 1] + A.gain_foot * e[o + 1];
+    c[o + 2] = s[o + 2] + A.gain_foot * e[o + 2];
+  } else {
+    c[o] = s[o]; c[o + 1] = s[o + 1]; c[o + 2] = s[o + 2];
+  }
+  if (A.snap) {
+    const double z = terrain_at(A.T, map, c[o], c[o + 1]).h;
+    if (fabs(z - c[o + 2]) > A.snap_tol) st |= 64 << E;
+    c[o + 2] = z;
+  }
+  const double v0 = c[o] - c[0], v1 = c[o + 1] - c[1], v2 = c[o + 2] - c[2];
+  const double d0 = ((R[0] * v0 + R[3] * v1) + R[6] * v2) - A.nominal[E][0];
+  const double d1 = ((R[1] * v0 + R[4] * v1) + R[7] * v2) - A.nominal[E][1];
+  const double d2 = ((R[2] * v0 + R[5] * v1) + R[8] * v2) - A.nominal[E][2];
+  return fabs(d0) <= A.max_deviation[0] + A.rom_tol && fabs(d1) <= A.max_deviation[1] + A.rom_tol &&
+         fabs(d2) <= A.max_deviation[2] + A.rom_tol;
+}
+
+__global__ __launch_bounds__(64) void k_start_feedback(const SamplePlan *Sd, FeedbackArgs A, const double *nodes, const double *t0,
+                                                       const int *row_in, const long long *cursor, const double *meas,
+                                                       const int *map_id, double *start, const double *goal_step, double *goal,
+                                                       double *err_out, int *status, int B) {
+#pragma clang fp contract(off)
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const SamplePlan &S = *Sd;
+  // The window's places in the outputs, as lane values from the start: with the uniform pointers kept to the end, and with the
+  // plan row evaluated in front of the legs (the sampling tables and the leg data live together), the scalar registers run out
+  // and the kernel gets a scratch frame.
+  double *sb = start + (size_t)b * QTOS_START_DOUBLES, *eo = err_out ? err_out + (size_t)b * 18 : nullptr;
+  double *gb = goal_step ? goal + (size_t)b * 3 : nullptr;
+  const double *gs = goal_step ? goal_step + (size_t)b * 3 : nullptr;
+  int *stb = status + b;
+  const int map = map_id ? map_id[b] : 0;
+  const long long r = row_in[b];
+  const long long rows_b = A.K.capacity > 0 ? A.K.capacity : (long long)A.K.n_rows;   // rows of window b's table or ring
+  long long k = r - A.lat;                                                            // the measured plan row
+  if (k > A.K.first_row + r - 1) k = A.K.first_row + r - 1;
+  if (k < A.K.first_row) k = A.K.first_row;
+  const long long j = k - A.K.first_row;                                              // its place in the segment
+  if (r <= 0 || j >= rows_b) { *stb = 32; return; }                              // no measurement: nothing else is touched
+  long long o = j;
+  if (A.K.capacity > 0) {
+    long long pos = cursor[b] % A.K.capacity;
+    if (pos < 0) pos += A.K.capacity;
+    o = pos + j;                                                                      // (pos, j < capacity: one subtraction wraps it)
+    if (o >= A.K.capacity) o -= A.K.capacity;
+  }
+  const bool quat = (A.K.flags & 1) != 0;
+  const double *mr = meas + ((size_t)b * (size_t)rows_b + (size_t)o) * (quat ? 19 : 18);
+  double row[25] = {0}, dst[TRACK_COLS], R[9];   // (track_leg's error column against `row` is not used here: the row comes behind the legs)
+  int st = track_pose(mr, quat, R, dst + 4);                                          // (bit 2: the pitch clip acted)
+  dst[1] = mr[0]; dst[2] = mr[1]; dst[3] = mr[2];
+  const double *q = mr + (quat ? 7 : 6);
+  track_leg<0>(A.K, row, mr, R, q, dst);
+  track_leg<1>(A.K, row, mr, R, q, dst);
+  track_leg<2>(A.K, row, mr, R, q, dst);
+  track_leg<3>(A.K, row, mr, R, q, dst);
+  sample_row_state_at(S, nodes + (size_t)b * S.n_vars, t0[b], k > INT_MAX ? INT_MAX : (int)k, A.K.hz, row);
+  double e[18];
+#pragma unroll
+  for (int i = 0; i < 18; ++i) e[i] = dst[1 + i] - row[1 + i];
+  e[5] = remainder(e[5], 6.283185307179586);
+#pragma unroll
+  for (int i = 0; i < 18; ++i) e[i] = feedback_clip(e[i], i < 3 ? A.max_pos : (i < 6 ? A.max_ang : A.max_foot), st);
+  if (eo) {
+#pragma unroll
+    for (int i = 0; i < 18; ++i) eo[i] = e[i];
+  }
+  double s[QTOS_START_DOUBLES], c[QTOS_START_DOUBLES];
+#pragma unroll
+  for (int i = 0; i < QTOS_START_DOUBLES; ++i) { s[i] = sb[i]; c[i] = s[i]; }
+  if (A.gain_pos != 0) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) c[i] = s[i] + A.gain_pos * e[i];
+  }
+  if (A.gain_ang != 0) {
+#pragma unroll
+    for (int i = 3; i < 6; ++i) c[i] = s[i] + A.gain_ang * e[i];
+  }
+  double Rc[9], unused[3];
+  track_pose(c, false, Rc, unused);                                                   // R of the corrected Euler angles
+  bool ok = feedback_foot<0>(A, map, s, e, Rc, c, st);
+  ok = feedback_foot<1>(A, map, s, e, Rc, c, st) && ok;
+  ok = feedback_foot<2>(A, map, s, e, Rc, c, st) && ok;
+  ok = feedback_foot<3>(A, map, s, e, Rc, c, st) && ok;
+  // (the fallback's goal comes from two loads of its own: with s[0] here the two branches end in the same load, the compiler
+  // merges them into one load through a choice of two addresses, and s and c stay in scratch for it)
+  double gx = sb[0], gy = sb[1];
+  if (A.gain_pos == 0 && A.gain_ang == 0 && A.gain_foot == 0) {
+    st &= 6;                                                                          // (uniform) nothing to add: the start stays, to the bit
+  } else if (!ok) {
+    st |= 8;                                                                          // fallback: the start stays as it is
+  } else {
+    st |= 1;
+#pragma unroll
+    for (int i = 0; i < QTOS_START_DOUBLES; ++i) {
+      if (A.zero_filter && fabs(c[i]) < 1e-4) c[i] = 0.0;                             // QTOS/utils.py zero_filter
+      if (i < 18 || A.zero_filter) sb[i] = c[i];
+    }
+    gx = c[0]; gy = c[1];
+  }
+  if (gs) {
+    gb[0] = gx + gs[0];
+    gb[1] = gy + gs[1];
+  }
+  *stb = st;
+}
+
+// Goals of receding windows from their global paths (qtos_path_goal*; Global_Planner.update / spine_step, QTOS/planner.py:139-161,
+// 195-230; Combiner.plan_init / spine_step, QTOS/combiner.py:137-212): where the next plan goes.  One lane per window: the
+// window's A* "spine" (two cubic splines in scipy's layout, global_planner.path_table) is read one horizon ahead of the new plan's
+// start, the displacement from the base point is clipped to step_size per axis, and the goal height is the terrain under the
+// goal + z_offset.  The statement of the rule is global_planner.path_goal, and this kernel equals it to the bit: every
+// function below switches contraction off in its own body (the library is built with the compiler's default, which fuses
+// a * b + c), so each operation is one rounded IEEE double operation, in scipy's order of summation, which is not Horner's.
+// No LDS, no scratch: the tables come through pointers and are indexed per lane, the arguments hold scalars only (see
+// k_handover), and no handle state is read or written.
+struct PathGoalArgs {   // QtosPathGoal as the kernel reads it (window_api.hpp path_goal_args)
+  double horizon, step_size, tol, z_offset, cell, origin_x, origin_y, t_stop, stop_dist;
+  int base, clamp_x, advance_clock, hold_done;
+  int n_paths, max_pieces, n_maps, rows, cols;
+};
+
+// One spine at time t (global_planner.spine_eval): x the path's n + 1 knots, c its coefficients c[k * mp + i] of (t - x[i])^(3 - k).
+// The bisection counts the knots <= t, which is searchsorted(x[:n + 1], t, 'right'); a NaN counts none and gives a NaN.
+__device__ inline double path_spine(const double *x, const double *c, int n, int mp, double t) {
+#pragma clang fp contract(off)
+  int lo = 0, hi = n + 1;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (x[mid] <= t) lo = mid + 1; else hi = mid;
+  }
+  const int i = lo - 1 < 0 ? 0 : (lo - 1 > n - 1 ? n - 1 : lo - 1);
+  const double s = t - x[i];
+  double res = 0.0, z = 1.0;
+#pragma unroll
+  for (int kp = 0; kp < 4; ++kp) {
+    res = res + c[(size_t)(3 - kp) * mp + i] * z;
+    z = z * s;
+  }
+  return res;
+}
+
+// GlobalPlanner.get_map_height (global_planner.map_height): the index test is made in double, so a huge or non-finite
+// coordinate takes the fall-back cell and reads nothing else.  hm null: every height is 0.
+__device__ inline double path_height(const PathGoalArgs &A, const double *hm, double x, double y) {
+#pragma clang fp contract(off)
+  if (!hm) return 0.0;
+  const double fr = floor((y + A.origin_y) / A.cell), fc = floor((x + A.origin_x) / A.cell);
+  int r = A.rows - 1, c = A.cols / 2;
+  if (fr >= -(double)A.rows && fr < (double)A.rows && fc >= -(double)A.cols && fc < (double)A.cols) {
+    r = (int)fr; c = (int)fc;
+    if (r < 0) r += A.rows;        // (Python's wrap of a negative index)
+    if (c < 0) c += A.cols;
+  }
+  return hm[(size_t)r * A.cols + c];
+}
+
+__device__ inline double path_clip(double d, double step) {   // np.clip(d, -step, step), step >= 0: a NaN stays a NaN
+  return d < -step ? -step : (d > step ? step : d);
+}
+
+__global__ __launch_bounds__(64) void k_path_goal(PathGoalArgs A, const double *knots, const double *coef, const int *n_pieces,
+                                                  const double *robot_goal, const int *path_id, const double *height_yx,
+                                                  const int *map_id, double *clock, const double *offset, const double *start,
+                                                  double *goal_out, int *done, int B) {
+#pragma clang fp contract(off)
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  int p = path_id ? path_id[b] : b;
+  p = p < 0 ? 0 : (p > A.n_paths - 1 ? A.n_paths - 1 : p);       // (an id outside the table reads its nearest path, never beyond it)
+  int n = n_pieces[p];
+  n = n < 1 ? 1 : (n > A.max_pieces ? A.max_pieces : n);
+  const double *x = knots + (size_t)p * (A.max_pieces + 1);
+  const double *cx = coef + (size_t)p * 8 * A.max_pieces, *cy = cx + (size_t)4 * A.max_pieces;
+  const double *hm = nullptr;
+  if (height_yx) {
+    int m = map_id ? map_id[b] : 0;
+    m = m < 0 ? 0 : (m > A.n_maps - 1 ? A.n_maps - 1 : m);
+    hm = height_yx + (size_t)m * A.rows * A.cols;
+  }
+  const double *st = start ? start + (size_t)b * QTOS_START_DOUBLES : nullptr;
+  const double lt = clock[b] + (offset ? offset[b] : 0.0);       // plan time of the new plan's row 0
+  const double tf = lt + A.horizon;
+  double sx = path_spine(x, cx, n, A.max_pieces, tf), sy = path_spine(x, cy, n, A.max_pieces, tf);
+  if (!(fabs(sx) > A.tol)) sx = 0.0;
+  if (!(fabs(sy) > A.tol)) sy = 0.0;
+  const double gz = path_height(A, hm, sx, sy) + A.z_offset;
+  if (A.clamp_x) {                                               // Combiner.spine_step: behind the height, as the reference does
+    const double rgx = robot_goal[(size_t)p * 3];
+    if (sx > rgx) sx = rgx;
+  }
+  double bx, by, bz;
+  if (A.base == 0) {                                             // Global_Planner.update: the spine at the plan's start
+    bx = path_spine(x, cx, n, A.max_pieces, lt);
+    by = path_spine(x, cy, n, A.max_pieces, lt);
+    bz = path_height(A, hm, bx, by) + A.z_offset;
+  } else {                                                       // plan_init, spine_step(com, t): the state the plan starts from
+    bx = st[0]; by = st[1]; bz = st[2];
+  }
+  double gx = bx + path_clip(sx - bx, A.step_size), gy = by + path_clip(sy - by, A.step_size);
+  double gzc = bz + path_clip(gz - bz, A.step_size);
+  int bits = 0;
+  if (x[n] < lt - A.t_stop) bits |= 1;                           // the path's end lies t_stop behind the plan's start
+  if (A.stop_dist > 0) {
+    const double dx = st[0] - gx, dy = st[1] - gy;
+    if (sqrt(dx * dx + dy * dy) < A.stop_dist) bits |= 2;
+  }
+  int d = 0;
+  if (done) {
+    d = done[b] | bits;
+    done[b] = d;
+  }
+  if (A.hold_done && d) { gx = st[0]; gy = st[1]; gzc = st[2]; }  // a finished window stands still
+  goal_out[(size_t)b * 3 + 0] = gx;
+  goal_out[(size_t)b * 3 + 1] = gy;
+  goal_out[(size_t)b * 3 + 2] = gzc;
+  if (A.advance_clock) clock[b] = lt;
+}
+
+// The global paths of receding windows (qtos_path_plan*; PATH_Solver, QTOS/planner.py:282-457): what k_path_goal reads, made on
+// the device.  One wavefront per window: A* over the window's boolean map, every second cell of the path a point of two
+// not-a-knot cubics.  The statement of the rule is global_planner.path_plan (path_cells, spine_fit), and this kernel equals it to
+// the bit: the cells because every pop is an exact lexicographic minimum of (f, cell), the numbers because every function
+// below switches contraction off and performs the rule's operations one by one.
+// LDS, laid out for the limits the host checks (rows * cols <= PP_GRID, max_open <= PP_OPEN, max_cells <= PP_GRID), PP_LDS_BYTES
+// (139264) in all:
+//   cw   PP_GRID x u32   per cell: bits 0-16 g (an integer: every step costs 1.0; at most the number of pops, 4 * PP_GRID + 4),
+//                        17-18 the direction it was reached by, 19 closed, 20 blocked
+//   live PP_GRID x u16   per cell: its entries in the open list (<= max_open); after the search the path's cells
+//   of   PP_OPEN x f64   the open list's f, unsorted          oc   PP_OPEN x u16   and cells (row * cols + col)
+// The search is uniform over the wave: every lane follows it, the lanes share the pop (a strided scan and six butterfly
+// steps) and lane 0 stores.  No scratch, plain vector stores only, no handle state.
+constexpr int PP_GRID = 16384, PP_OPEN = 4096;
+constexpr int PP_LDS_BYTES = PP_GRID * 4 + PP_GRID * 2 + PP_OPEN * 8 + PP_OPEN * 2;
+constexpr unsigned PP_G = 0x1ffffu, PP_CLOSED = 1u << 19, PP_BLOCKED = 1u << 20;
+struct PathPlanArgs {   // QtosPathPlan as the kernel reads it (window_api.hpp path_plan_args)
+  double cell, origin_x, origin_y, height_bound, step_size;
+  int rows, cols, max_cells, max_open, max_pieces, n_maps, set_done;
+};
+
+// floor((v + o) / cell) as an int32 cell index; false where it is not finite or does not fit
+__device__ inline bool pp_cell_of(double v, double o, double cell, int *out) {
+#pragma clang fp contract(off)
+  const double f = floor((v + o) / cell);
+  if (!(f >= -2147483648.0 && f <= 2147483647.0)) return false;
+  *out = (int)f;
+  return true;
+}
+
+// (f, cell, slot) < (f2, cell2, slot2): f as the bits of a double >= 0, which order as the doubles do; the slot only makes the
+// order total, so that every lane of the butterfly ends on the same entry
+__device__ inline void pp_take_less(unsigned long long &f, int &c, int &k, unsigned long long f2, int c2, int k2) {
+  if (f2 < f || (f2 == f && (c2 < c || (c2 == c && k2 < k)))) { f = f2; c = c2; k = k2; }
+}
+
+// The path's point i of n + 1 on one axis (0: x from the columns, 1: y from the rows): cell * cell_size - origin over every
+// second cell, the last cell WITHOUT the shift (sic, QTOS/planner.py:410,412).  The start cell is not in the LDS list.
+__device__ inline double pp_point(const unsigned short *path, int n_cells, int n, int cols, int sr, int sc, int axis, double cell,
+                                  double origin, int i) {
+#pragma clang fp contract(off)
+  const int j = i < n ? 2 * i : n_cells - 1;
+  int r = sr, c = sc;
+  if (j > 0) { r = path[j] / cols; c = path[j] % cols; }
+  const double v = (double)(axis ? r : c) * cell;
+  return i < n ? v - origin : v;
+}
+
+__device__ inline double pp_knot(double T, int n, int i) {   // numpy's linspace(0, T, n + 1)
+#pragma clang fp contract(off)
+  return i >= n ? T : (double)i * (T / (double)n);
+}
+
+// global_planner.spine_fit for one axis, by one lane: c = the window's 4 x mp coefficient rows, which are also the work space
+// (c' in row 0, g' and then s from row 2 on: s[i] is already c2[i], and the last pass runs downwards so that c3 never
+// overwrites the s[n] that spills into row 3 where n = mp).
+__device__ inline void pp_spine_fit(double *c, int mp, const unsigned short *path, int n_cells, int n, int cols, int sr, int sc, int axis,
+                                    double cell, double origin, double T) {
+#pragma clang fp contract(off)
+  auto Y = [&](int i) { return pp_point(path, n_cells, n, cols, sr, sc, axis, cell, origin, i); };
+  auto H = [&](int i) { return pp_knot(T, n, i + 1) - pp_knot(T, n, i); };
+  auto D = [&](int i) { return (Y(i + 1) - Y(i)) / H(i); };
+  double *s = c + (size_t)2 * mp;
+  if (n == 1) {
+    const double d0 = D(0);
+    s[0] = d0; s[1] = d0;
+  } else if (n == 2) {
+    const double h0 = H(0), h1 = H(1), d0 = D(0), d1 = D(1);
+    const double b0 = 2.0 * d0, b1 = 3.0 * (h0 * d1 + h1 * d0), b2 = 2.0 * d1;
+    const double s1 = ((b1 - h1 * b0) - h0 * b2) / ((2.0 * (h0 + h1) - h1) - h0);
+    s[0] = b0 - s1; s[1] = s1; s[2] = b2 - s1;
+  } else {
+    double hp = H(0), dp = D(0), hi = H(1), di = D(1);            // h, d of rows i - 1 and i
+    double dd = pp_knot(T, n, 2) - pp_knot(T, n, 0);
+    double b = ((hp + 2.0 * dd) * hi * dp + hp * hp * di) / dd;
+    double cp = dd / hi, gp = b / hi;
+    c[0] = cp; s[0] = gp;
+    for (int i = 1; i < n; ++i) {
+      if (i > 1) { hp = hi; dp = di; hi = H(i); di = D(i); }
+      b = 3.0 * (hi * dp + hp * di);
+      const double den = 2.0 * (hp + hi) - hi * cp;
+      cp = hp / den;
+      gp = (b - hi * gp) / den;
+      c[i] = cp; s[i] = gp;
+    }
+    // (hp, dp, hi, di are now those of rows n - 2 and n - 1)
+    dd = pp_knot(T, n, n) - pp_knot(T, n, n - 2);
+    b = (hi * hi * dp + (2.0 * dd + hi) * hp * di) / dd;
+    const double den = hp - dd * cp;
+    double sn = (b - dd * gp) / den;
+    s[n] = sn;
+    for (int i = n - 1; i >= 0; --i) {
+      sn = s[i] - c[i] * sn;
+      s[i] = sn;
+    }
+  }
+  for (int i = n - 1; i >= 0; --i) {
+    const double h = H(i), d = D(i), si = s[i], t = ((si + s[i + 1]) - 2.0 * d) / h;
+    c[i] = t / h;
+    c[(size_t)mp + i] = (d - si) / h - t;
+    c[(size_t)3 * mp + i] = Y(i);                                  // (c2[i] = s[i] stands where it is)
+  }
+}
+
+__global__ __launch_bounds__(64) void k_path_plan(PathPlanArgs A, const double *bool_maps, const int *map_id, const double *start,
+                                                  const double *robot_goal, double *knots, double *coef, int *n_pieces, int *cells,
+                                                  int *n_cells_out, int *status_out, int *done) {
+#pragma clang fp contract(off)
+  __shared__ unsigned cw[PP_GRID];
+  __shared__ unsigned short live[PP_GRID];
+  __shared__ double of[PP_OPEN];
+  __shared__ unsigned short oc[PP_OPEN];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int rows = A.rows, cols = A.cols, N = rows * cols, mp = A.max_pieces;
+  const double x0 = start[(size_t)b * QTOS_START_DOUBLES], y0 = start[(size_t)b * QTOS_START_DOUBLES + 1];
+  const double gx = robot_goal[(size_t)b * 3], gy = robot_goal[(size_t)b * 3 + 1];
+  int m = map_id ? map_id[b] : 0;
+  m = m < 0 ? 0 : (m > A.n_maps - 1 ? A.n_maps - 1 : m);           // (an id outside reads its nearest map, never beyond them)
+  const double *bm = bool_maps + (size_t)m * N;
+  for (int i = lane; i < N; i += 64) {
+    cw[i] = bm[i] > A.height_bound ? PP_BLOCKED : 0u;
+    live[i] = 0;
+  }
+  __syncthreads();
+
+  int sr = 0, sc = 0, gr = 0, gc = 0;
+  int status = 0, n_cells = 0;
+  if (!pp_cell_of(y0, A.origin_y, A.cell, &sr) || !pp_cell_of(x0, A.origin_x, A.cell, &sc) || !pp_cell_of(gy, A.origin_y, A.cell, &gr) ||
+      !pp_cell_of(gx, A.origin_x, A.cell, &gc))
+    status = 1;
+  if (status == 0) {
+    // ---- PathSolver.astar ----
+    int n_open = 0, pops = 0;
+    long long r = sr, c = sc;                                      // (the start may lie anywhere in the int32 range: its neighbours in 64 bits)
+    bool found = false;
+    while (true) {
+      if (pops > 0) {                                              // (the first pop is the start: the list's only entry)
+        if (n_open == 0) { status = 1; break; }
+        unsigned long long bf = ~0ull;
+        int bc = 0x7fffffff, bk = 0x7fffffff;
+        for (int k = lane; k < n_open; k += 64) pp_take_less(bf, bc, bk, (unsigned long long)__double_as_longlong(of[k]), (int)oc[k], k);
+        for (int off = 32; off; off >>= 1) {
+          const unsigned long long f2 = __shfl_xor(bf, off);
+          const int c2 = __shfl_xor(bc, off), k2 = __shfl_xor(bk, off);
+          pp_take_less(bf, bc, bk, f2, c2, k2);
+        }
+        const int k = __builtin_amdgcn_readfirstlane(bk), ci = __builtin_amdgcn_readfirstlane(bc);
+        --n_open;
+        if (lane == 0) {                                           // swap with the last
+          of[k] = of[n_open];
+          oc[k] = oc[n_open];
+          live[ci] = live[ci] - 1;
+        }
+        __syncthreads();
+        r = ci / cols; c = ci % cols;
+      }
+      if (++pops > 4 * N + 4) { status = 3; break; }
+      if (r == gr && c == gc) { found = true; break; }
+      int gcur = 0;
+      if (r >= 0 && r < rows && c >= 0 && c < cols) {
+        const int ci = (int)r * cols + (int)c;
+        gcur = (int)(cw[ci] & PP_G);
+        if (lane == 0) cw[ci] = cw[ci] | PP_CLOSED;
+      }
+      for (int d = 0; d < 4; ++d) {                                // (0, 1), (0, -1), (1, 0), (-1, 0)
+        const long long nr = r + (d == 2 ? 1 : (d == 3 ? -1 : 0)), nc = c + (d == 0 ? 1 : (d == 1 ? -1 : 0));
+        if (nr < 0 || nr >= rows || nc < 0 || nc >= cols) continue;
+        const int ni = (int)nr * cols + (int)nc;
+        const unsigned w = cw[ni];
+        if (w & PP_BLOCKED) continue;
+        const int gn = gcur + 1, gnb = (int)(w & PP_G);
+        if ((w & PP_CLOSED) && gn >= gnb) continue;
+        if (gn < gnb || live[ni] == 0) {
+          if (n_open >= A.max_open) { status = 3; break; }
+          const double dr = (double)((long long)gr - nr), dc = (double)((long long)gc - nc);
+          const double f = (double)gn + sqrt(dr * dr + dc * dc);
+          if (lane == 0) {
+            cw[ni] = (w & PP_CLOSED) | ((unsigned)d << 17) | (unsigned)gn;
+            of[n_open] = f;
+            oc[n_open] = (unsigned short)ni;
+            live[ni] = live[ni] + 1;
+          }
+          ++n_open;
+        }
+      }
+      __syncthreads();
+      if (status) break;
+    }
+    if (found) {
+      // ``while current in came_from``: inside the grid and reached by a step (g > 0); the start never is
+      int len = 0;
+      long long wr = r, wc = c;
+      while (wr >= 0 && wr < rows && wc >= 0 && wc < cols && len <= N) {
+        const unsigned w = cw[(int)wr * cols + (int)wc];
+        if ((w & PP_G) == 0) break;
+        const int d = (int)((w >> 17) & 3u);
+        wr -= (d == 2 ? 1 : (d == 3 ? -1 : 0));
+        wc -= (d == 0 ? 1 : (d == 1 ? -1 : 0));
+        ++len;
+      }
+      n_cells = len + 1;
+      if (n_cells > A.max_cells) status = 2;
+      else if (lane == 0) {                                        // the path's cells behind the start, in `live`
+        wr = r; wc = c;
+        for (int j = len; j >= 1; --j) {
+          const int ci = (int)wr * cols + (int)wc;
+          live[j] = (unsigned short)ci;
+          const int d = (int)((cw[ci] >> 17) & 3u);
+          wr -= (d == 2 ? 1 : (d == 3 ? -1 : 0));
+          wc -= (d == 0 ? 1 : (d == 1 ? -1 : 0));
+        }
+      }
+    }
+  }
+  __syncthreads();
+  if (status != 0 && status != 2) n_cells = 0;
+
+  const double dx = x0 - gx, dy = y0 - gy;
+  const double T = sqrt(dx * dx + dy * dy) / A.step_size * 10.0;
+  if (status == 0 && !(T > 0)) status = 4;
+  const int n = status == 0 ? (n_cells + 1) / 2 : 1;               // sub = path[::2]
+  double *kn = knots + (size_t)b * (mp + 1), *cf = coef + (size_t)b * 8 * mp;
+  if (cells) {
+    int *cl = cells + (size_t)b * A.max_cells * 2;
+    for (int j = lane; j < A.max_cells; j += 64) {
+      int pr = 0, pc = 0;
+      if (status == 0 || status == 4) {
+        if (j == 0) { pr = sr; pc = sc; }
+        else if (j < n_cells) { pr = live[j] / cols; pc = live[j] % cols; }
+      }
+      cl[2 * j] = pr;
+      cl[2 * j + 1] = pc;
+    }
+  }
+  for (int i = lane; i <= mp; i += 64) kn[i] = status == 0 ? pp_knot(T, n, i) : 0.0;
+  if (status == 0) {
+    if (lane < 2)
+      pp_spine_fit(cf + (size_t)lane * 4 * mp, mp, live, n_cells, n, cols, sr, sc, lane, A.cell, lane ? A.origin_y : A.origin_x, T);
+  } else if (lane < 2) {
+    cf[(size_t)lane * 4 * mp + (size_t)3 * mp] = lane ? y0 : x0;   // the constant spine at the start point
+  }
+  __syncthreads();                                                 // (the fit's work space lies in the padding where n < mp)
+  for (int i = lane; i < 8 * mp; i += 64) {
+    const int col = i % mp, row = (i / mp) & 3;
+    if (col >= n || (status != 0 && row != 3)) cf[i] = 0.0;
+  }
+  if (lane == 0) {
+    n_pieces[b] = n;
+    n_cells_out[b] = n_cells;
+    status_out[b] = status;
+    if (done && A.set_done && status != 0) done[b] = done[b] | 4;
+  }
+}
+
+// The probe and the stamp of the windows' heightfields (qtos_probe*, qtos_probe_stamp*; PATH_MAP.probe_map and worker_f,
+// QTOS/generateHeightField.py:172-404): what k_path_plan reads as bool_maps, made on the device with the batched solve between
+// the two steps.  The statement of the rule is feasibility.probe_table / round2 / stamp_table, and these kernels equal it to
+// the bit: every function that forms a coordinate switches contraction off and performs the rule's operations one by one (the
+// one explicit fma of probe_round2 is the exact error of a product).  One wavefront per map.  The placement of the patches is
+// decided by counting alone: k_probe_count leaves every map's number of patches in offsets[m + 1], k_probe_scan turns them into
+// prefix sums in place, and k_probe places patch q of map m at offsets[m] + (the candidates in front of q in queue order), a
+// ballot and a prefix count per 64 candidates.  No atomics, no scratch, plain vector stores only, no handle state.
+// LDS (k_probe), dynamic, sized at the launch by probe_lds_bytes: the map's row coordinates, its column coordinates and the
+// twelve stance offsets, rows + cols / 2 + 12 doubles (a 20 x 60 map: 496 B; with rows * cols <= 16384 at most 64 KiB).
+struct ProbeArgs {   // QtosProbe as the kernels read it (window_api.hpp probe_args)
+  double cell, origin_shift, z_offset, stance[QTOS_NEE * 3];
+  int rows, cols, n_maps, scale, multi_map_shift, capacity;
+};
+
+inline size_t probe_lds_bytes(int rows, int cols) { return ((size_t)rows + (size_t)(cols / 2) + QTOS_NEE * 3) * sizeof(double); }
+
+// Python's round(v, 2) (feasibility.round2): the product's exact error decides the half-way cases that are no true ties
+__device__ inline double probe_round2(double v) {
+#pragma clang fp contract(off)
+  const double p = v * 100.0;
+  const double e = fma(v, 100.0, -p);
+  double k = rint(p);
+  if (fabs(p - k) == 0.5 && e != 0.0) k = floor(p) + (e > 0.0 ? 1.0 : 0.0);
+  return k / 100.0;
+}
+
+// neighbors_danger_test(m, r, c): the eight neighbours in the reference's order; the first one outside the map answers false,
+// the first one inside it that is > 0 answers true (a NaN is not > 0)
+__device__ inline bool probe_danger(const double *hm, int rows, int cols, int r, int c) {
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const int nr = r + ((k == 0 || k == 4 || k == 5) ? 1 : ((k == 1 || k == 6 || k == 7) ? -1 : 0));
+    const int nc = c + ((k == 2 || k == 4 || k == 7) ? 1 : ((k == 3 || k == 5 || k == 6) ? -1 : 0));
+    if (nr < 0 || nr >= rows || nc < 0 || nc >= cols) return false;
+    if (hm[(size_t)nr * cols + nc] > 0.0) return true;
+  }
+  return false;
+}
+
+// candidate q = row * nj + j of a map (queue order): the patch from column 2 j to column 2 j + 2 of that row
+__device__ inline bool probe_candidate(const double *hm, int rows, int cols, int nj, int q) {
+  const int r = q / nj, c = 2 * (q % nj);
+  return probe_danger(hm, rows, cols, r, c) || probe_danger(hm, rows, cols, r, c + 2);
+}
+
+__global__ __launch_bounds__(64) void k_probe_count(ProbeArgs A, const double *map_yx, int *offsets) {
+  const int m = blockIdx.x, lane = threadIdx.x;
+  const int rows = A.rows, cols = A.cols, nj = cols / 2 - 1, Q = rows * nj;
+  const double *hm = map_yx + (size_t)m * rows * cols;
+  int n = 0;
+  for (int q0 = 0; q0 < Q; q0 += 64) {
+    const int q = q0 + lane;
+    const bool cand = q < Q && probe_candidate(hm, rows, cols, nj, q);
+    n += __popcll(__ballot(cand));
+  }
+  if (lane == 0) {
+    offsets[m + 1] = n;
+    if (m == 0) offsets[0] = 0;
+  }
+}
+
+// offsets[1 .. n_maps]: counts -> inclusive prefix sums, in place, by one workgroup (a lane owns a contiguous run of entries)
+__global__ __launch_bounds__(256) void k_probe_scan(int *offsets, int n_maps) {
+  __shared__ int part[256];
+  const int t = threadIdx.x, per = (n_maps + 255) / 256;
+  const int lo = 1 + t * per, hi = lo + per < n_maps + 1 ? lo + per : n_maps + 1;
+  int s = 0;
+  for (int i = lo; i < hi; ++i) s += offsets[i];
+  part[t] = s;
+  __syncthreads();
+  int run = 0;
+  for (int k = 0; k < t; ++k) run += part[k];
+  for (int i = lo; i < hi; ++i) {
+    run += offsets[i];
+    offsets[i] = run;
+  }
+}
+
+__global__ __launch_bounds__(64) void k_probe(ProbeArgs A, const double *map_yx, const int *offsets, int *slot, int *patch, double *start,
+                                              double *goal, int *map_id) {
+#pragma clang fp contract(off)
+  extern __shared__ double co[];                                     // ys[rows], xs[nj + 1] (xs[j] starts patch j, xs[j + 1] is its goal), stance[12]
+  const int m = blockIdx.x, lane = threadIdx.x;
+  const int rows = A.rows, cols = A.cols, nj = cols / 2 - 1, Q = rows * nj;
+  if (Q < 1) return;                                                 // (uniform: a map of 2 or 3 columns has no candidate and no slot)
+  const double *hm = map_yx + (size_t)m * rows * cols;
+  double *ys = co, *xs = co + rows, *stance = xs + nj + 1;           // (the stance is read per patch: in LDS it holds no scalar registers over the loop)
+  if (lane == 0) {                                                   // PATH_MAP.probe_map's walk, statement by statement
+#pragma unroll
+    for (int k = 0; k < QTOS_NEE * 3; ++k) stance[k] = A.stance[k];
+    const double res = A.cell * (1.0 / (double)A.scale), half = (double)cols / 2.0;
+    const double shift = (double)(A.multi_map_shift - 1) * A.origin_shift;
+    const double x_start = ((-res * half) - res / 2.0) + shift;      // (sic: x and y both start from the number of columns)
+    const double x_goal = ((-res * half) + res / 2.0) + shift;
+    double y = x_start;
+    for (int r = 0; r < rows; ++r) {
+      y = probe_round2(y + res);
+      ys[r] = y;
+    }
+    xs[0] = probe_round2(x_start + res);
+    double xg = x_goal;
+    for (int j = 0; j < nj; ++j) {
+      xg = probe_round2(xg + 2.0 * res);
+      xs[j + 1] = xg;
+    }
+  }
+  __syncthreads();
+  int run = offsets[m];
+  for (int q0 = 0; q0 < Q; q0 += 64) {
+    const int q = q0 + lane;
+    const bool cand = q < Q && probe_candidate(hm, rows, cols, nj, q);
+    const unsigned long long mask = __ballot(cand);
+    const int i = run + __popcll(mask & ((1ull << lane) - 1ull));
+    run += __popcll(mask);
+    if (q < Q) slot[(size_t)m * Q + q] = cand ? i : -1;
+    if (!cand || i >= A.capacity) continue;                          // (nothing is written beyond the capacity)
+    const int r = q / nj, j = q % nj;
+    const double px = xs[j], py = ys[r], z = hm[(size_t)r * cols + 2 * j], zg = hm[(size_t)r * cols + 2 * j + 2];
+    patch[(size_t)i * 3] = m;
+    patch[(size_t)i * 3 + 1] = r;
+    patch[(size_t)i * 3 + 2] = 2 * j;
+    if (map_id) map_id[i] = m;
+    if (start) {
+      double *s = start + (size_t)i * QTOS_START_DOUBLES;
+      s[0] = px; s[1] = py; s[2] = z + A.z_offset;
+      s[3] = 0.0; s[4] = 0.0; s[5] = 0.0;
+#pragma unroll
+      for (int e = 0; e < QTOS_NEE; ++e) {
+        s[6 + 3 * e] = stance[3 * e] + px;
+        s[7 + 3 * e] = stance[3 * e + 1] + py;
+        s[8 + 3 * e] = stance[3 * e + 2] + z;
+      }
+#pragma unroll
+      for (int k = 18; k < QTOS_START_DOUBLES; ++k) s[k] = 0.0;
+    }
+    if (goal) {
+      goal[(size_t)i * 3] = xs[j + 1];
+      goal[(size_t)i * 3 + 1] = py;
+      goal[(size_t)i * 3 + 2] = zg + A.z_offset;
+    }
+  }
+}
+
+// worker_f's stamp (feasibility.stamp_table): one lane per cell in turn.  The cell holds what the LAST patch of its map in queue
+// order that writes it leaves, and that patch is the largest (row, j) among the few whose start or goal lies within the
+// diamond's radius R = 3 scale of the cell (a failure), or on the cell and up to two cells left of it (a success: start, the
+// cell right of it, goal).  The rows are walked downwards from r + R, the patches of a row downwards from the last whose
+// diamonds reach the cell; the first patch met that writes the cell decides.  A slot beyond offsets[n_maps] is no patch.
+__global__ __launch_bounds__(64) void k_probe_stamp(ProbeArgs A, const int *offsets, const int *slot, const int *status, double *bool_maps) {
+  const int m = blockIdx.x, lane = threadIdx.x;
+  const int rows = A.rows, cols = A.cols, nj = cols / 2 - 1, R = 3 * A.scale, N = offsets[A.n_maps];
+  const int *sl = slot + (size_t)m * rows * (nj > 0 ? nj : 0);
+  double *bm = bool_maps + (size_t)m * rows * cols;
+  for (int ci = lane; ci < rows * cols; ci += 64) {
+    const int r = ci / cols, c = ci % cols;
+    double v = 0.0;
+    bool found = false;
+    const int r_hi = r + R < rows - 1 ? r + R : rows - 1, r_lo = r - R > 0 ? r - R : 0;
+    for (int pr = r_hi; pr >= r_lo && !found; --pr) {
+      const int w = R - (pr > r ? pr - r : r - pr);                  // the diamond's reach along this row (>= 0)
+      int j_hi = (c + w) >> 1, j_lo = (c - w - 2 + 1) >> 1;          // start columns 2 j within c - w - 2 .. c + w
+      if (j_hi > nj - 1) j_hi = nj - 1;
+      if (j_lo < 0) j_lo = 0;
+      for (int j = j_hi; j >= j_lo; --j) {
+        const int i = sl[(size_t)pr * nj + j];
+        if (i < 0 || i >= N) continue;
+        const int st = status[i], d = c - 2 * j, ds = d < 0 ? -d : d, dg = d < 2 ? 2 - d : d - 2;   // columns from the start, the goal
+        if (st != 0 ? (ds <= w || dg <= w) : (pr == r && d >= 0 && d <= 2)) {
+          v = st != 0 ? 1.0 : 0.0;
+          found = true;
+          break;
+        }
+      }
+    }
+    bm[ci] = v;
+  }
+}
+
+// The randomised terrain of the windows (qtos_terrain_env*; Height_Map_Generator.__init__ with randomize_env and update(),
+// QTOS/generateHeightField.py:563-567, 584-588, 648-730): what qtos_set_heightfields_device, k_probe and k_path_goal read, made
+// on the device from base grids and one seed per map.  The statement of the rule is heightfield.random_env_table, and this
+// kernel equals it to the bit.  One workgroup of ENV_T lanes per map.  The stream is python's: MT19937 in LDS, seeded by one
+// lane as random.seed(int) seeds it, regenerated by all lanes (a lane owns word t of each of the three runs [0, 227),
+// [227, 454), [454, 623) whose words depend on the run in front alone, so it needs its own results only; word 623 follows).
+// Every lane reads the same words and draws the same numbers, so the control flow is uniform and the barriers of a
+// regeneration are met by all.  A level is a distinct value != 0 of the grid; the levels come out ascending from repeated
+// min-reductions over the grid, lane j of every wave then keeps level j in a register, and the height passes run on those
+// registers -- the solver copy's passes for their draws alone -- with a wave-wide min per snapshot entry.  The grid is touched
+// again only to be written: each cell finds its level's slot by bisection and takes the slot's value, rolled by the net shift,
+// in both orientations.  No atomics, no scratch, plain vector stores.
+constexpr int ENV_T = 256;
+struct TerrainEnvArgs {   // QtosTerrainEnv as the kernel reads it (window_api.hpp terrain_env_args)
+  double delta;
+  int n_maps, n_base, rows, cols, n_shift, n_height, climb;
+};
+struct EnvLds {
+  unsigned mt[624];
+  double level[QTOS_ENV_MAX_LEVELS];   // the base grid's levels, ascending: a cell's slot is the index of its value here
+  double value[QTOS_ENV_MAX_LEVELS];   // what the slots hold behind the map's height passes
+  double red[ENV_T / 64];              // a block-wide reduction's partial minima, and whether a wave found a candidate
+  int found[ENV_T / 64];
+};
+static_assert(sizeof(EnvLds) == QTOS_ENV_LDS_BYTES, "QTOS_ENV_LDS_BYTES (qtos_planner.h) is k_terrain_env's LDS");
+
+__device__ inline unsigned env_mix(unsigned a, unsigned b) {
+  const unsigned y = (a & 0x80000000u) | (b & 0x7fffffffu);
+  return (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
+}
+
+// the next 624 words of the state; called by all lanes of the workgroup
+__device__ inline void env_twist(unsigned *mt, int tid) {
+  unsigned n1 = 0, n2 = 0, n3 = 0;
+  const unsigned last = mt[623];
+  if (tid < 227) {
+    n1 = mt[tid + 397] ^ env_mix(mt[tid], mt[tid + 1]);
+    n2 = n1 ^ env_mix(mt[tid + 227], mt[tid + 228]);
+    if (tid < 169) n3 = n2 ^ env_mix(mt[tid + 454], mt[tid + 455]);
+  }
+  __syncthreads();                     // the old state has been read, by this regeneration and by every wave's draws
+  if (tid < 227) {
+    mt[tid] = n1;
+    mt[tid + 227] = n2;
+    if (tid < 169) mt[tid + 454] = n3;
+  }
+  __syncthreads();
+  if (tid == 0) mt[623] = mt[396] ^ env_mix(last, mt[0]);
+  __syncthreads();
+}
+
+// random.seed(s) for 0 <= s < 2^64 (init_by_array on the seed's 32-bit words, low word first); one lane
+__device__ inline void env_seed(unsigned *mt, unsigned long long s) {
+  const unsigned key[2] = {(unsigned)s, (unsigned)(s >> 32)};
+  const int nk = key[1] ? 2 : 1;
+  unsigned prev = 19650218u;
+  mt[0] = prev;
+  for (int i = 1; i < 624; ++i) {
+    prev = 1812433253u * (prev ^ (prev >> 30)) + (unsigned)i;
+    mt[i] = prev;
+  }
+  int i = 1, j = 0;
+  prev = mt[0];
+  for (int k = 0; k < 624; ++k) {
+    prev = (mt[i] ^ ((prev ^ (prev >> 30)) * 1664525u)) + (j ? key[1] : key[0]) + (unsigned)j;
+    mt[i] = prev;
+    j = j + 1 < nk ? j + 1 : 0;
+    if (++i >= 624) { mt[0] = prev; i = 1; }
+  }
+  for (int k = 0; k < 623; ++k) {
+    prev = (mt[i] ^ ((prev ^ (prev >> 30)) * 1566083941u)) - (unsigned)i;
+    mt[i] = prev;
+    if (++i >= 624) { mt[0] = prev; i = 1; }
+  }
+  mt[0] = 0x80000000u;
+}
+
+struct EnvStream {   // a lane's view of the workgroup's stream: the same in every lane
+  unsigned *mt;
+  int tid, pos, used;
+  __device__ inline unsigned bits32() {
+    if (pos >= 624) {
+      env_twist(mt, tid);
+      pos = 0;
+    }
+    unsigned y = __builtin_amdgcn_readfirstlane(mt[pos]);
+    ++pos; ++used;
+    y ^= y >> 11;
+    y ^= (y << 7) & 0x9d2c5680u;
+    y ^= (y << 15) & 0xefc60000u;
+    return y ^ (y >> 18);
+  }
+  __device__ inline void skip(int n) {                     // whole states are passed over without tempering them
+    while (n > 0) {
+      if (pos >= 624) {
+        env_twist(mt, tid);
+        pos = 0;
+      }
+      const int step = n < 624 - pos ? n : 624 - pos;
+      pos += step;
+      n -= step;
+    }
+  }
+  __device__ inline int below(int n, int k) {              // choice among n items, k = bit_length(n)
+    unsigned r = bits32() >> (32 - k);
+    while (r >= (unsigned)n) r = bits32() >> (32 - k);
+    return (int)r;
+  }
+  __device__ inline double uniform(double a, double w) {   // a + (b - a) * random(), w = b - a: the product and the sum round apart
+#pragma clang fp contract(off)
+    const unsigned hi = bits32() >> 5, lo = bits32() >> 6;
+    const double r = ((double)hi * 67108864.0 + (double)lo) / 9007199254740992.0;
+    const double p = w * r;
+    return a + p;
+  }
+};
+
+__device__ inline double env_wave_min(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double w = __shfl_xor(v, o);
+    v = w < v ? w : v;
+  }
+  return v;
+}
+
+// one pass of random_height over the level values a wave keeps one per lane (v; 0 in the lanes behind the last level)
+__device__ inline void env_level_pass(EnvStream &S, double &v, int lane, double a, double w) {
+#pragma clang fp contract(off)
+  double snap = 0.0, last = 0.0;
+  int n = 0;
+  for (;;) {                                               // the snapshot: entry j, ascending, into lane j
+    const bool cand = v != 0.0 && (n == 0 || v > last);
+    if (!__ballot(cand)) break;
+    last = env_wave_min(cand ? v : __builtin_huge_val());
+    if (lane == n) snap = last;
+    ++n;
+  }
+  for (int j = 0; j < n; ++j) {
+    const double h = __shfl(snap, j);
+    const double d = S.uniform(a, w);
+    const int c = S.below(3, 2);
+    if (v == h) {
+      if (c == 0) v += d;
+      else if (c == 1) v -= d;
+    }
+  }
+}
+
+__global__ __launch_bounds__(ENV_T) void k_terrain_env(TerrainEnvArgs A, const double *base_yx, const int *base_id,
+                                                       const unsigned long long *seed, int *draws, double *map_yx, double *height_xy,
+                                                       int *status) {
+#pragma clang fp contract(off)
+  __shared__ EnvLds L;
+  const int m = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int rows = A.rows, cols = A.cols, cells = rows * cols;
+  const int skip = draws ? draws[m] : 0;
+  if (skip < 0 || skip > QTOS_ENV_MAX_DRAWS) {             // (uniform: every lane read the same word)
+    if (tid == 0) status[m] = 2;
+    return;
+  }
+  const int b = base_id ? base_id[m] : m;
+  if (b < 0 || b >= A.n_base) {                            // (uniform; never outside the base grids, whatever base_id holds)
+    if (tid == 0) status[m] = 4;
+    return;
+  }
+  const double *g = base_yx + (size_t)b * cells;
+
+  // the levels, ascending: a min-reduction over the grid per level; the first one also looks for a NaN
+  int n_levels = 0;
+  double last = 0.0;
+  for (;;) {
+    double best = __builtin_huge_val();
+    bool cand = false, nan = false;
+    for (int ci = tid; ci < cells; ci += ENV_T) {
+      const double v = g[ci];
+      nan = nan || v != v;
+      if (v != 0.0 && (n_levels == 0 || v > last)) {
+        cand = true;
+        best = v < best ? v : best;
+      }
+    }
+    best = env_wave_min(best);
+    const int flags = (__ballot(cand) ? 1 : 0) | (__ballot(nan) ? 2 : 0);
+    __syncthreads();                                       // the partial results of the reduction in front have been read
+    if (lane == 0) {
+      L.red[wave] = best;
+      L.found[wave] = flags;
+    }
+    __syncthreads();
+    int any = 0;
+    best = __builtin_huge_val();
+#pragma unroll
+    for (int k = 0; k < ENV_T / 64; ++k) {
+      any |= L.found[k];
+      best = L.red[k] < best ? L.red[k] : best;
+    }
+    if (any & 2) {                                         // (uniform)
+      if (tid == 0) status[m] = 3;
+      return;
+    }
+    if (!(any & 1)) break;
+    if (n_levels == QTOS_ENV_MAX_LEVELS) {
+      if (tid == 0) status[m] = 1;
+      return;
+    }
+    if (tid == 0) L.level[n_levels] = best;
+    last = best;
+    ++n_levels;
+  }
+  if (tid == 0) env_seed(L.mt, seed[m]);
+  __syncthreads();
+
+  // the draws, the same in every lane: the shifts of the solver's copy (consumed), the map's, then the height passes
+  EnvStream S{L.mt, tid, 624, 0};
+  S.skip(skip);
+  const int n_dir = A.climb ? 2 : 4, k_dir = A.climb ? 2 : 3;
+  for (int i = 0; i < A.n_shift; ++i) (void)S.below(n_dir, k_dir);
+  int dy = 0, dx = 0;
+  for (int i = 0; i < A.n_shift; ++i) {
+    const int d = S.below(n_dir, k_dir) + (A.climb ? 2 : 0);   // left, right, up, down
+    dx += d == 0 ? -1 : (d == 1 ? 1 : 0);
+    dy += d == 2 ? -1 : (d == 3 ? 1 : 0);
+  }
+  const double lo = -A.delta, width = A.delta - lo;
+  const double mine = lane < n_levels ? L.level[lane] : 0.0;
+  double v = mine;
+  for (int i = 0; i < A.n_height; ++i) env_level_pass(S, v, lane, lo, width);
+  v = mine;
+  for (int i = 0; i < A.n_height; ++i) env_level_pass(S, v, lane, lo, width);
+  if (wave == 0 && lane < n_levels) L.value[lane] = v;
+  __syncthreads();
+
+  // the grid, rolled, in both orientations: map_yx[r][c] = moved[r - dy][c - dx] with wrap-around, height_xy[x][y] = map_yx[y][x - 1]
+  const int sy = ((dy % rows) + rows) % rows, sx = ((dx % cols) + cols) % cols;
+  auto moved = [&](int r, int c) -> double {
+    int sr = r - sy, sc = c - sx;
+    sr += sr < 0 ? rows : 0;
+    sc += sc < 0 ? cols : 0;
+    const double h = g[(size_t)sr * cols + sc];
+    if (h == 0.0) return h;                                // (ground keeps its own zero, -0.0 included)
+    int at = 0;
+#pragma unroll
+    for (int step = QTOS_ENV_MAX_LEVELS / 2; step > 0; step >>= 1)
+      if (at + step < n_levels && L.level[at + step] <= h) at += step;
+    return L.value[at];
+  };
+  double *out = map_yx + (size_t)m * cells;
+  for (int ci = tid; ci < cells; ci += ENV_T) out[ci] = moved(ci / cols, ci % cols);
+  if (height_xy) {
+    double *hx = height_xy + (size_t)m * cells;
+    for (int ci = tid; ci < cells; ci += ENV_T) {
+      const int x = ci / rows, y = ci % rows;
+      hx[ci] = x == 0 ? 0.0 : moved(y, x - 1);
+    }
+  }
+  if (tid == 0) {
+    if (draws) draws[m] = skip + S.used;
+    status[m] = 0;
+  }
+}
+
+}  // namespace qtos

@@ -155,6 +155,9 @@ def test_host_forms_leave_what_the_device_forms_leave(gpu):
     assert not P.probe_stamp((5, 8), flat["offsets"], flat["slot"], flat["patch"], np.zeros(0, np.int32)).any()
     narrow = P.probe(np.ones((4, 3)))                                           # (no candidate: the slot array is empty)
     assert narrow["offsets"].tolist() == [0, 0] and narrow["slot"].shape == (1, 4, 0)
+    none = np.zeros(0, np.int32)                                                # (the stamp of it: slot and status both empty)
+    assert same(P.probe_stamp((4, 3), narrow["offsets"], narrow["slot"], narrow["patch"], none),
+                feasibility.stamp_table((4, 3), narrow["offsets"], narrow["slot"], narrow["patch"], none, 1))
 
 
 def test_bad_arguments_answer_minus_two_and_launch_nothing(gpu):

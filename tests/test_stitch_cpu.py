@@ -178,7 +178,7 @@ def one_kernel(notes, kernel):
     return notes[names[0]]
 
 
-STITCH_TILE = 512                  # rows per tile = lanes per workgroup (kernels.hpp)
+STITCH_TILE = 512                  # rows per tile = lanes per workgroup (window_kernels.hpp)
 
 
 def test_k_stitch_uses_no_scratch_and_one_tile_of_lds(notes):
