@@ -16,6 +16,8 @@ import numpy as np
 import pytest
 
 import linearisation_cases as lc
+# the dense Newton step (LAPACK, refined in extended precision): it lives with the rest of the interior-point restatement
+from oracle.ipm import direction as _dense_step
 
 pytestmark = pytest.mark.gpu
 
@@ -111,29 +113,6 @@ def test_values_of_the_reduced_system_match_oracle(name):
     err = max(float(np.abs(g[b] - O.constraints(x[b])).max()) for b in range(B))
     lc.record("gpu_reduced_values", name, dict(problems=B, gate_values=lc.GATE_VALUE, values=err))
     assert err < lc.GATE_VALUE
-
-
-def _dense_step(Jo, go, free, E, Ii, sig, w, delta_x, eps_rows):
-    """The Newton step of the full system from the oracle's Jacobian, as test_kkt_solve_matches_dense_reference builds it --
-    eps_rows: the regularisation of every equality row's multiplier --, LAPACK's solution refined with residuals in extended
-    precision.  Returns (step of the free variables, the last refinement's largest correction relative to the step's largest
-    entry: what the dense solve itself may still be off by)."""
-    from scipy.linalg import lu_factor, lu_solve
-    JE, JI = Jo[np.ix_(E, free)], Jo[np.ix_(Ii, free)]
-    nf, nE = len(free), len(E)
-    K = np.zeros((nf + nE, nf + nE))
-    K[:nf, :nf] = delta_x * np.eye(nf) + JI.T @ (sig[Ii][:, None] * JI)
-    K[nf:, :nf] = JE
-    K[:nf, nf:] = JE.T
-    K[nf:, nf:] = -np.diag(eps_rows)
-    rhs = np.concatenate([-JI.T @ w[Ii], -go[E]])
-    lu = lu_factor(K)
-    Kl, bl = K.astype(np.longdouble), rhs.astype(np.longdouble)
-    hp = lu_solve(lu, rhs).astype(np.longdouble)
-    for _ in range(4):
-        corr = lu_solve(lu, (bl - Kl @ hp).astype(np.float64))
-        hp = hp + corr.astype(np.longdouble)
-    return hp[:nf].astype(np.float64), float(np.abs(corr[:nf]).max() / np.abs(hp[:nf]).max())
 
 
 REDUCED = ((True, False), (False, True), (True, True))       # (reduce_base, reduce_swing)
