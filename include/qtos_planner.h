@@ -529,6 +529,56 @@ int qtos_start_feedback(QtosPlanner *p, int B, const QtosFeedback *s, const doub
                         const long long *cursor, const double *meas, const int *map_id, double *start, const double *goal_step,
                         double *goal, double *err_out, int *status);
 
+/* Plan check: what a plan violates BETWEEN its knots.  The solver holds the rows of its NLP at their own times only (dynamics
+ * every dt_dyn, range of motion every dt_rom, terrain at the foot nodes, forces at the force nodes); the rows the robot executes
+ * lie in between.  For B windows at once (k_plan_check, one workgroup per window; the rule: plan_check.py) check row k of a plan,
+ * at the plan time min(k / hz, T) of CSV row k, has 27 columns:
+ *   0         the time stamp of CSV row k (t0 + k / hz, qtos_sample_csv's to the bit)
+ *   1 ..  3   the angular dynamics rows  I_w wd + w x (I_w w) - sum f_e x (r - p_e)   [N m], signed
+ *   4 ..  6   the linear dynamics rows   m a + m g e_z - sum f_e                       [N], signed
+ *   7 .. 18   range of motion, feet FL FR HL HR x 3 axes: max(lo - g, g - hi) of g = R^T (p_e - r) against nominal_stance -+
+ *             max_dev; negative: inside                                                [m]
+ *  19 .. 22   clearance of the feet z - h(x, y) under the handle's terrain_mode and the window's map (no maps: flat ground) [m]
+ *  23 .. 26   force excess of the feet; in a stance polynomial of the foot's motion the largest excess of the NLP's five force
+ *             rows (normal force in [0, f_max], the four rows of the friction pyramid) with the terrain basis at the foot's
+ *             position, in a swing polynomial max |f_i|                                [N]
+ * A row exactly on a phase switch belongs to the earlier polynomial (qtos_sample_csv's rule).  The summary has five records per
+ * window, the families dyn_ang (max |columns 1 .. 3|), dyn_lin (max |4 .. 6|), rom (max(7 .. 18, 0)), terrain (|clearance| of a
+ * foot in stance, max(-clearance, 0) of one in swing) and force (max(23 .. 26, 0)): the largest violation over the window's
+ * rows, the lowest row that attains it and the number of rows with a violation > tol[family].  A non-finite column counts as
+ * +inf.  A window without rows has max -inf, row -1, count 0.  The summary is a function of the table alone (no atomics). */
+#define QTOS_CHECK_ACCUMULATE 1      /* flags: merge with the records in d_summary: max = max(old, new), row replaced only on a
+                                        strictly greater max, count += new; a window without rows leaves its records alone */
+#define QTOS_CHECK_COLS 27
+#define QTOS_CHECK_FAMILIES 5
+typedef struct QtosCheckRecord {
+  double max;
+  long long row, count;
+} QtosCheckRecord;
+typedef struct QtosPlanCheck {
+  double hz;                    /* rows per second (<= 0: 1000) */
+  int first_row;                /* first row where d_first_row is NULL; 0 .. 1000000 */
+  int n_rows;                   /* rows per window in `rows` (>= 1), and the count where d_n_rows is NULL */
+  double tol[5];                /* per family: a row counts where its violation is > tol */
+  int flags;                    /* QTOS_CHECK_* */
+} QtosPlanCheck;
+/* nodes B x n_vars, t0 B; map_id B (NULL: map 0, or flat ground where the handle has no maps), first_row B and n_rows B
+ * (NULL: the struct's; n clamped to 0 .. n_rows, a negative first_row taken as 0, as qtos_joint_rows does) and cursor B
+ * (NULL: the summary's rows count from first_row; given: from cursor[b], the window's clock as qtos_stitch counts it: row =
+ * cursor[b] + j) may be NULL.  rows B x n_rows x 27 and summary B x 5 records: either may be NULL, not both; rows behind a
+ * window's count are not touched.
+ * Device form: all pointers but `c` in device memory, one kernel queued on `stream`; no handle state is read or written but
+ * the sampling tables, the model's constants and the terrain -- it may be queued while a call is open.  Host form: host
+ * pointers, synchronous, through device buffers of its own (no -5); rows and summary are copied in and out whole.
+ * Both: -1 on a null planner or required pointer, B < 1, n_rows < 1, first_row outside 0 .. 1000000, rows and summary both
+ * NULL; -2 on a HIP error; -3 out of memory. */
+int qtos_plan_check_device(QtosPlanner *p, int B, const QtosPlanCheck *c, const double *d_nodes, const double *d_t0,
+                           const int *d_map_id /* may be NULL */, const int *d_first_row /* may be NULL */,
+                           const int *d_n_rows /* may be NULL */, const long long *d_cursor /* may be NULL */,
+                           double *d_rows /* may be NULL */, QtosCheckRecord *d_summary /* may be NULL */, void *stream);
+int qtos_plan_check(QtosPlanner *p, int B, const QtosPlanCheck *c, const double *nodes, const double *t0, const int *map_id,
+                    const int *first_row, const int *n_rows, const long long *cursor, double *rows, QtosCheckRecord *summary);
+
 /* Goals of receding windows from their global paths: where the next plan goes.  Replaces Global_Planner.update / spine_step
  * (QTOS/planner.py:139-161, 195-230) and Combiner.plan_init / spine_step (QTOS/combiner.py:137-212, 223-225) for B windows at
  * once: a window's A* "spine" -- two cubic splines X_p, Y_p over one set of knots -- is read one horizon ahead of the new plan's

@@ -380,6 +380,34 @@ def feedback_params(cfg=None, hz=1000.0, first_row=0, n_rows=0, capacity=0, late
     return g
 
 
+class QtosPlanCheck(C.Structure):
+    """Parameters of a plan check (qtos_plan_check*, include/qtos_planner.h)."""
+    _fields_ = [("hz", C.c_double), ("first_row", C.c_int), ("n_rows", C.c_int), ("tol", C.c_double * 5), ("flags", C.c_int)]
+
+    def copy(self):
+        return QtosPlanCheck.from_buffer_copy(self)
+
+
+class QtosCheckRecord(C.Structure):
+    """One family of one window in a plan check's summary; plan_check.SUMMARY is its numpy dtype."""
+    _fields_ = [("max", C.c_double), ("row", C.c_longlong), ("count", C.c_longlong)]
+
+
+CHECK_ACCUMULATE = 1     # QTOS_CHECK_ACCUMULATE of include/qtos_planner.h
+CHECK_COLS = 27          # QTOS_CHECK_COLS
+CHECK_TOL = (1e-3, 1e-2, 1e-4, 1e-4, 1e-2)   # check_params' default per family: N m, N, m, m, N
+
+
+def check_params(hz=1000.0, first_row=0, n_rows=0, tol=CHECK_TOL, accumulate=False):
+    """A QtosPlanCheck.  tol: one number for the five families (dyn_ang N m, dyn_lin N, rom m, terrain m, force N) or five."""
+    g = QtosPlanCheck()
+    g.hz, g.first_row, g.n_rows = float(hz), int(first_row), int(n_rows)
+    for f, v in enumerate(np.broadcast_to(np.asarray(tol, np.float64), (5,))):
+        g.tol[f] = float(v)
+    g.flags = CHECK_ACCUMULATE if accumulate else 0
+    return g
+
+
 class SelftestError(RuntimeError):
     """No elimination order passed the KKT self-test (qtos_planner_create_checked returned -6); `attempts`: the QtosSelftest
     records in the order they were tried."""
@@ -408,7 +436,7 @@ EXPORTS = [
     "qtos_probe", "qtos_probe_device", "qtos_probe_stamp", "qtos_probe_stamp_device",
     "qtos_terrain_env", "qtos_terrain_env_device", "qtos_set_heightfields_device",
     "qtos_joint_rows", "qtos_joint_rows_device", "qtos_track", "qtos_track_device",
-    "qtos_start_feedback", "qtos_start_feedback_device",
+    "qtos_start_feedback", "qtos_start_feedback_device", "qtos_plan_check", "qtos_plan_check_device",
 ]
 
 _lib = None
@@ -541,6 +569,10 @@ def load():
         llp = C.POINTER(C.c_longlong)
         lib.qtos_start_feedback.argtypes = [vp, C.c_int, C.POINTER(QtosFeedback), dp, dp, ip, llp, dp, ip, dp, dp, dp, dp, ip]
         lib.qtos_start_feedback_device.argtypes = [vp, C.c_int, C.POINTER(QtosFeedback)] + [vp] * 12
+    if hasattr(lib, "qtos_plan_check"):              # (the plan check; older builds loaded through QTOS_LIB lack it)
+        llp = C.POINTER(C.c_longlong)
+        lib.qtos_plan_check.argtypes = [vp, C.c_int, C.POINTER(QtosPlanCheck), dp, dp, ip, ip, ip, llp, dp, vp]
+        lib.qtos_plan_check_device.argtypes = [vp, C.c_int, C.POINTER(QtosPlanCheck)] + [vp] * 9
     if hasattr(lib, "qtos_set_heightfields_device"):
         lib.qtos_set_heightfields_device.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, vp]
     _lib = lib
@@ -1083,6 +1115,54 @@ class Planner:
                                                _llp(cur), _dp(meas), _ip(mid), _dp(start), _dp(gs), _dp(gl), _dp(err), _ip(status)),
                   "start_feedback")
         return start, gl, err, status
+
+    def has_plan_check(self):
+        return hasattr(self.lib, "qtos_plan_check")
+
+    def plan_check(self, nodes, t0, params, map_id=None, first_row=None, n_rows=None, cursor=None, rows=True, summary=None,
+                   stream=None):
+        """What every plan in `nodes` violates between its knots (qtos_plan_check; the rule: plan_check.py).  params: a
+        QtosPlanCheck (check_params()).  Returns (rows, summary): rows [B, params.n_rows, 27] (rows=True; an array: written into a
+        copy of it, rows behind a window's count stay; False / None: no table) and summary [B, 5] records of plan_check.SUMMARY
+        (summary=None with a table: computed as well; an array: with params' accumulate flag merged with it; False: none).
+        first_row, n_rows: an int or B ints; cursor: B ints, the summary's rows count from it.  numpy arrays go through the host
+        form.  torch tensors on the device (nodes, t0 and whichever of the others are given; rows / summary: tensors to write
+        into, summary as B x 5 x 3 float64 words or None) go through the device form on `stream` (a torch stream; None: the
+        current one) and come back as they are, without a synchronisation."""
+        if not self.has_plan_check():
+            raise RuntimeError("this build of the planner library has no plan-check kernel (qtos_plan_check)")
+        from . import plan_check as pc
+        if hasattr(nodes, "data_ptr"):
+            import torch
+            st = torch.cuda.current_stream(nodes.device) if stream is None else stream
+            B = nodes.reshape(-1, self.n).shape[0]
+            ptr = lambda a: None if a is None or a is False or a is True else C.c_void_p(a.data_ptr())
+            self._chk(self.lib.qtos_plan_check_device(self.h, B, C.byref(params), ptr(nodes), ptr(t0), ptr(map_id), ptr(first_row),
+                                                      ptr(n_rows), ptr(cursor), ptr(rows), ptr(summary), C.c_void_p(st.cuda_stream)),
+                      "plan_check_device")
+            return (rows if ptr(rows) else None), (summary if ptr(summary) else None)
+        nodes = np.ascontiguousarray(nodes, np.float64).reshape(-1, self.n)
+        B = nodes.shape[0]
+        t0 = np.ascontiguousarray(np.broadcast_to(np.asarray(t0, np.float64), (B,)))
+        mid, first, per = _i32(map_id, B), _i32(first_row, B), _i32(n_rows, B)
+        cur = None if cursor is None else np.ascontiguousarray(np.broadcast_to(np.asarray(cursor, np.int64), (B,)))
+        if rows is True:
+            rows = np.zeros((B, int(params.n_rows), CHECK_COLS))
+        elif rows is False or rows is None:
+            rows = None
+        else:
+            rows = np.array(rows, np.float64).reshape(B, int(params.n_rows), CHECK_COLS)
+        if summary is False:
+            summary = None
+            if rows is None:
+                raise ValueError("rows and summary cannot both be left out")
+        elif summary is None:
+            summary = pc.empty_summary(B)
+        else:
+            summary = np.array(summary, pc.SUMMARY).reshape(B, 5)
+        self._chk(self.lib.qtos_plan_check(self.h, B, C.byref(params), _dp(nodes), _dp(t0), _ip(mid), _ip(first), _ip(per), _llp(cur),
+                                           _dp(rows), None if summary is None else summary.ctypes.data_as(C.c_void_p)), "plan_check")
+        return rows, summary
 
     def has_path_goal(self):
         return hasattr(self.lib, "qtos_path_goal")

@@ -42,6 +42,7 @@ struct QtosPlanner : Analysis {   // (the analysis the planner runs: choose_kern
   DevPlan dp;
   SamplePlan sp;
   SamplePlan *d_sp = nullptr;  // sp in device memory (k_handover reads the tables through a pointer)
+  const int *d_stance[NEE] = {nullptr, nullptr, nullptr, nullptr};   // per foot and polynomial of its motion spline: 1 stance, 0 swing (k_plan_check)
   int device = 0, max_batch = 0;
   std::vector<void *> allocs;  // everything to free
   // workspace
@@ -744,6 +745,11 @@ static int create_planner(const QtosParams *params, int max_batch, int device, c
   for (int e = 0; e < NEE; ++e) { TRY(upload_spline(p, M.eem[e], &SP.eem[e])); TRY(upload_spline(p, M.eef[e], &SP.eef[e])); }
   TRY(p->alloc(&p->d_sp, 1));
   HIPCHK(p, hipMemcpy(p->d_sp, &SP, sizeof(SP), hipMemcpyHostToDevice));
+  for (int e = 0; e < NEE; ++e) {   // a stance polynomial of a foot's motion: neither of its nodes has a velocity variable
+    std::vector<int> stance(M.eem[e].n_polys);
+    for (int k = 0; k < M.eem[e].n_polys; ++k) stance[k] = M.eem[e].idx[k][3] < 0 && M.eem[e].idx[k + 1][3] < 0;
+    TRY(p->upload(stance, &p->d_stance[e]));
+  }
   // workspaces
   DevWork &W = p->wk;
   std::memset(&W, 0, sizeof(W));

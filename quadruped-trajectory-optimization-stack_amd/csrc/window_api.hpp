@@ -400,6 +400,60 @@ int qtos_start_feedback(QtosPlanner *p, int B, const QtosFeedback *s, const doub
   return rc ? rc : S.download();
 }
 
+// ---- what the windows' plans violate between their knots (k_plan_check, window_kernels.hpp) --------------------
+// The argument checks of both forms, and QtosPlanCheck as k_plan_check reads it, with the model's constants and the terrain.
+static_assert(sizeof(CheckRecord) == sizeof(QtosCheckRecord), "QtosCheckRecord (qtos_planner.h) is k_plan_check's record");
+static int plan_check_args(const QtosPlanner *p, int B, const QtosPlanCheck *c, const void *nodes, const void *t0, const void *rows,
+                           const void *summary, CheckArgs *A) {
+  if (!p || B < 1 || !c || !nodes || !t0 || (!rows && !summary)) return -1;
+  if (c->n_rows < 1 || c->first_row < 0 || c->first_row > 1000000) return -1;
+  const QtosParams &P = p->M.P;
+  A->hz = c->hz > 0 ? c->hz : 1000.0;
+  A->mass = P.mass; A->gravity = P.gravity; A->mu = P.mu; A->f_max = P.f_max;
+  for (int i = 0; i < 9; ++i) A->Ib[i] = P.inertia_b[i];
+  for (int e = 0; e < NEE; ++e) {
+    for (int d = 0; d < 3; ++d) {
+      A->rom_lo[e][d] = P.nominal_stance[e][d] - P.max_dev[d];
+      A->rom_hi[e][d] = P.nominal_stance[e][d] + P.max_dev[d];
+    }
+    A->stance[e] = p->d_stance[e];
+  }
+  for (int f = 0; f < CHECK_FAMILIES; ++f) A->tol[f] = c->tol[f];
+  const DevPlan &D = p->dp;
+  A->T.height = D.height; A->T.hcell = D.hcell; A->T.hx0 = D.hx0; A->T.hy0 = D.hy0;
+  A->T.n_maps = D.n_maps; A->T.hnx = D.hnx; A->T.hny = D.hny; A->T.terrain_mode = D.terrain_mode;
+  A->first_row = c->first_row; A->n_rows = c->n_rows; A->accumulate = (c->flags & QTOS_CHECK_ACCUMULATE) != 0;
+  return 0;
+}
+
+int qtos_plan_check_device(QtosPlanner *p, int B, const QtosPlanCheck *c, const double *d_nodes, const double *d_t0, const int *d_map_id,
+                           const int *d_first_row, const int *d_n_rows, const long long *d_cursor, double *d_rows,
+                           QtosCheckRecord *d_summary, void *stream_) {
+  CheckArgs A;
+  if (plan_check_args(p, B, c, d_nodes, d_t0, d_rows, d_summary, &A)) return -1;
+  HIPCHK(p, hipSetDevice(p->device));
+  hipLaunchKernelGGL(k_plan_check, dim3(B), dim3(CHECK_TILE), 0, (hipStream_t)stream_, p->d_sp, A, d_nodes, d_t0, d_map_id, d_first_row,
+                     d_n_rows, d_cursor, d_rows, (CheckRecord *)d_summary, B);
+  HIPCHK(p, hipGetLastError());
+  return 0;
+}
+
+int qtos_plan_check(QtosPlanner *p, int B, const QtosPlanCheck *c, const double *nodes, const double *t0, const int *map_id,
+                    const int *first_row, const int *n_rows, const long long *cursor, double *rows, QtosCheckRecord *summary) {
+  CheckArgs A;
+  if (plan_check_args(p, B, c, nodes, t0, rows, summary, &A)) return -1;
+  HIPCHK(p, hipSetDevice(p->device));
+  Staging S(p);
+  const double *d_nodes = S.in(nodes, (size_t)B * p->M.n_vars), *d_t0 = S.in(t0, B);
+  const int *d_map = S.in(map_id, B), *d_first = S.in(first_row, B), *d_n = S.in(n_rows, B);
+  const long long *d_cur = S.in(cursor, B);
+  double *d_rows = S.inout(rows, (size_t)B * (size_t)c->n_rows * CHECK_COLS);    // (rows behind a window's count come back as they were)
+  QtosCheckRecord *d_sum = S.inout(summary, (size_t)B * CHECK_FAMILIES);          // (the accumulate flag merges with what is there)
+  if (S.rc) return S.rc;
+  const int rc = qtos_plan_check_device(p, B, c, d_nodes, d_t0, d_map, d_first, d_n, d_cur, d_rows, d_sum, nullptr);
+  return rc ? rc : S.download();
+}
+
 // ---- goals of receding windows from their global paths (k_path_goal, window_kernels.hpp) ------------------------
 // The argument checks of both forms, and QtosPathGoal as k_path_goal reads it.
 static int path_goal_args(const QtosPlanner *p, int B, const QtosPathGoal *g, const void *knots, const void *coef, const void *n_pieces,

@@ -1,5 +1,6 @@
 // window_kernels.hpp -- gfx950 device code around the solve: the sampler and the kernels of the receding loop (the "windows").
-// They read plans through SamplePlan; of the solver's kernels (kernels.hpp) they use the terrain look-up (terrain_at) only.
+// They read plans through SamplePlan; of the solver's kernels (kernels.hpp) they use the terrain look-up (terrain_at) and, in
+// k_plan_check, the pieces of the Newton-Euler and force rows (dyn_angular, rotation, trig_of, terrain_basis, wg_reduce).
 //
 //   k_sample        : 1 kHz spline sampling into the 37-column CSV row layout
 //   k_handover      : start, goal and clock offset of the next window from the plan that is running
@@ -7,6 +8,7 @@
 //   k_joint_rows    : joint commands of the windows' plans (leg IK and motor law)
 //   k_track         : measured states and tracking errors of the windows
 //   k_start_feedback: the next plan's start from the measured state
+//   k_plan_check    : what the windows' plans violate between their knots
 //   k_path_goal     : goals of the windows from their global paths
 //   k_path_plan     : the global paths (A* and spines)
 //   k_probe*        : the probe and the stamp of the windows' heightfields
@@ -725,6 +727,204 @@ __global__ __launch_bounds__(64) void k_start_feedback(const SamplePlan *Sd, Fee
     gb[1] = gy + gs[1];
   }
   *stb = st;
+}
+
+// Plan check (qtos_plan_check*): what a plan violates between its knots.  The solver holds the rows of its NLP at their own
+// times only; this kernel evaluates the same rows -- Newton-Euler, range of motion, terrain, friction and unilateral force --
+// at every sampled row, 27 columns per row, and reduces them to five families per window (max, the lowest row that attains
+// it, the rows over a tolerance).  The statement of the rule is plan_check.py.  One workgroup per window walks its rows tile
+// by tile, as k_track does: (A) a lane takes a row and puts its 27 values into the row's place of an LDS tile, keeping the
+// five family violations in registers; (B) fifteen workgroup reductions (wg_reduce: max, then the lowest lane that attains
+// it, then the count) whose results every lane merges into the running records it carries from tile to tile -- the results
+// are uniform, so the records are scalars; (C) the tile goes out flat, consecutive lanes on consecutive doubles.  No atomics:
+// max and count do not depend on the order and the row is the lowest one, so the summary is a function of the table alone
+// and equals plan_check.summarise of it to the bit.  The arrays of the arguments are read with constant indices only
+// (check_foot is a template over the foot), the tables come through a pointer (see k_handover).
+constexpr int CHECK_COLS = 27, CHECK_TILE = 256, CHECK_FAMILIES = 5;
+struct CheckRecord {   // one family of one window in d_summary
+  double max;
+  long long row, count;
+};
+struct CheckArgs {     // QtosPlanCheck as the kernel reads it, with the model's constants (window_api.hpp plan_check_args)
+  double hz, mass, gravity, Ib[9], mu, f_max;
+  double rom_lo[NEE][3], rom_hi[NEE][3];   // nominal_stance -+ max_dev, as the NLP's bounds are formed
+  double tol[CHECK_FAMILIES];
+  FeedbackTerrain T;
+  const int *stance[NEE];                  // per foot and polynomial of its motion spline: 1 stance, 0 swing
+  int first_row, n_rows, accumulate;
+};
+
+// The polynomial of time t: sample_spline's search, for the stance flag of a foot's motion spline.
+__device__ inline int sample_segment(const SampleSpline &S, double t) {
+  int lo = 0, hi = S.n_polys - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (S.tend[mid] >= t - 1e-10) hi = mid; else lo = mid + 1;
+  }
+  return lo;
+}
+
+// The second derivative of a spline at time t: sample_spline's polynomial and local time with the weights of the second
+// derivative.  A function of its own: sample_spline keeps the code k_sample, k_stitch and k_handover are held to bit for bit.
+__device__ inline void sample_spline_acc(const SampleSpline &S, const double *x, double t, double out[3]) {
+  const int k = sample_segment(S, t);
+  const double T = S.dur[k];
+  const double tau = t - (S.tend[k] - T);
+  const double T2 = T * T, T3 = T2 * T;
+  const double w[4] = {-6 / T2 + 12 * tau / T3, -4 / T + 6 * tau / T2, 6 / T2 - 12 * tau / T3, -2 / T + 6 * tau / T2};
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    double acc = 0;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+      const int v = S.idx[(k + (a >> 1)) * 6 + (a & 1) * 3 + d];
+      if (v >= 0) acc += w[a] * x[v];
+    }
+    out[d] = acc;
+  }
+}
+
+__device__ inline double check_finite_or_inf(double v) { return isfinite(v) ? v : INFINITY; }
+
+// Foot E of a check row: takes its force and lever arm off the dynamics rows ga, gl, writes the range-of-motion excess, the
+// clearance and the force excess to dst (the row's place in the tile) and raises the three families' violations.
+template <int E>
+__device__ inline void check_foot(const SamplePlan &S, const CheckArgs &A, const double *x, double t, int map, const double r[3],
+                                  const double R[9], double ga[3], double gl[3], double *dst, double &v_rom, double &v_terr,
+                                  double &v_force) {
+  double pe[3], f[3];
+  sample_spline(S.eem[E], x, t, 0, pe);
+  sample_spline(S.eef[E], x, t, 0, f);
+  const bool stance = A.stance[E][sample_segment(S.eem[E], t)] != 0;
+  const double d[3] = {r[0] - pe[0], r[1] - pe[1], r[2] - pe[2]};
+  ga[0] -= f[1] * d[2] - f[2] * d[1];
+  ga[1] -= f[2] * d[0] - f[0] * d[2];
+  ga[2] -= f[0] * d[1] - f[1] * d[0];
+  gl[0] -= f[0]; gl[1] -= f[1]; gl[2] -= f[2];
+  // range of motion: g = R^T (p - r) against its box
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const double g = -(R[i] * d[0] + R[3 + i] * d[1] + R[6 + i] * d[2]);
+    const double ex = fmax(A.rom_lo[E][i] - g, g - A.rom_hi[E][i]);
+    dst[7 + 3 * E + i] = ex;
+    v_rom = fmax(v_rom, isfinite(ex) ? fmax(ex, 0.0) : INFINITY);
+  }
+  // terrain under the foot (a foot at a non-finite place has no terrain: the look-up would clamp it to a cell)
+  Terr tr = terrain_at(A.T, map, pe[0], pe[1]);
+  if (!(isfinite(pe[0]) && isfinite(pe[1]))) { tr.h = NAN; tr.hx = NAN; tr.hy = NAN; }
+  const double c = pe[2] - tr.h;
+  dst[19 + E] = c;
+  v_terr = fmax(v_terr, isfinite(c) ? (stance ? fabs(c) : fmax(-c, 0.0)) : INFINITY);
+  // force: the five rows of the NLP in a stance, max |f_i| in a swing
+  double ex;
+  if (stance) {
+    double b[3][3], bx[3], by[3];
+#pragma unroll
+    for (int w = 0; w < 3; ++w) terrain_basis(tr, w, b[w], bx, by);
+    // (the rows as eval_force forms them: the combined vector first, then its product with f)
+    double g[5];
+    g[0] = f[0] * b[0][0] + f[1] * b[0][1] + f[2] * b[0][2];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const double s = (q & 1) ? A.mu : -A.mu;
+      g[1 + q] = f[0] * (s * b[0][0] + b[1 + (q >> 1)][0]) + f[1] * (s * b[0][1] + b[1 + (q >> 1)][1]) +
+                 f[2] * (s * b[0][2] + b[1 + (q >> 1)][2]);
+    }
+    ex = fmax(fmax(fmax(-g[0], g[0] - A.f_max), fmax(g[1], -g[2])), fmax(g[3], -g[4]));
+    if (!(isfinite(g[0]) && isfinite(g[1]) && isfinite(g[2]) && isfinite(g[3]) && isfinite(g[4]))) ex = NAN;
+  } else {
+    ex = fmax(fmax(fabs(f[0]), fabs(f[1])), fabs(f[2]));
+    if (f[0] != f[0] || f[1] != f[1] || f[2] != f[2]) ex = NAN;
+  }
+  dst[23 + E] = ex;
+  v_force = fmax(v_force, isfinite(ex) ? fmax(ex, 0.0) : INFINITY);
+}
+
+__global__ __launch_bounds__(CHECK_TILE) void k_plan_check(const SamplePlan *Sd, CheckArgs A, const double *nodes, const double *t0,
+                                                           const int *map_id, const int *first_row, const int *n_rows,
+                                                           const long long *cursor, double *rows_out, CheckRecord *summary, int B) {
+  __shared__ double check_tile[CHECK_TILE * CHECK_COLS];
+  __shared__ double check_red[CHECK_TILE];
+  const int b = blockIdx.x;
+  if (b >= B) return;
+  const SamplePlan &S = *Sd;
+  long long n = n_rows ? n_rows[b] : A.n_rows;
+  n = n < 0 ? 0 : (n > A.n_rows ? A.n_rows : n);
+  long long first = first_row ? first_row[b] : A.first_row;
+  first = first < 0 ? 0 : first;
+  const long long row0 = cursor ? cursor[b] : first;                               // what the summary counts its rows from
+  const int map = map_id ? map_id[b] : 0;
+  const double *x = nodes + (size_t)b * S.n_vars;
+  const double t0b = t0[b];
+  double *out_b = rows_out ? rows_out + (size_t)b * (size_t)A.n_rows * CHECK_COLS : nullptr;
+  double run_max[CHECK_FAMILIES];
+  long long run_row[CHECK_FAMILIES], run_cnt[CHECK_FAMILIES];
+#pragma unroll
+  for (int f = 0; f < CHECK_FAMILIES; ++f) { run_max[f] = -INFINITY; run_row[f] = -1; run_cnt[f] = 0; }
+  for (long long j0 = 0; j0 < n; j0 += CHECK_TILE) {                               // (n is uniform over the workgroup: so are the barriers)
+    const int m = n - j0 < CHECK_TILE ? (int)(n - j0) : CHECK_TILE;
+    double v[CHECK_FAMILIES];
+#pragma unroll
+    for (int f = 0; f < CHECK_FAMILIES; ++f) v[f] = -INFINITY;                     // a lane without a row: below every violation
+    if ((int)threadIdx.x < m) {                                                    // (A) a lane takes a row
+      const long long kk = first + j0 + threadIdx.x;
+      const int k = kk > INT_MAX ? INT_MAX : (int)kk;
+      double t = k / A.hz;
+      if (t > S.T) t = S.T;
+      double *dst = check_tile + threadIdx.x * CHECK_COLS;
+      dst[0] = t0b + k / A.hz;                                                     // sample_row_state_at's time stamp
+      double r[3], a[3], th[3], thd[3], thdd[3], ga[3], gl[3], R[9];
+      sample_spline(S.lin, x, t, 0, r);
+      sample_spline_acc(S.lin, x, t, a);
+      sample_spline(S.ang, x, t, 0, th);
+      sample_spline(S.ang, x, t, 1, thd);
+      sample_spline_acc(S.ang, x, t, thdd);
+      const Trig tg = trig_of(th);
+      dyn_angular<double>(A.Ib, th, thd, thdd, tg, ga);
+      rotation<double>(th, tg, R);
+      gl[0] = A.mass * a[0]; gl[1] = A.mass * a[1]; gl[2] = A.mass * a[2] + A.mass * A.gravity;
+      double v_rom = 0, v_terr = 0, v_force = 0;
+      check_foot<0>(S, A, x, t, map, r, R, ga, gl, dst, v_rom, v_terr, v_force);
+      check_foot<1>(S, A, x, t, map, r, R, ga, gl, dst, v_rom, v_terr, v_force);
+      check_foot<2>(S, A, x, t, map, r, R, ga, gl, dst, v_rom, v_terr, v_force);
+      check_foot<3>(S, A, x, t, map, r, R, ga, gl, dst, v_rom, v_terr, v_force);
+      dst[1] = ga[0]; dst[2] = ga[1]; dst[3] = ga[2];
+      dst[4] = gl[0]; dst[5] = gl[1]; dst[6] = gl[2];
+      v[0] = fmax(fmax(check_finite_or_inf(fabs(ga[0])), check_finite_or_inf(fabs(ga[1]))), check_finite_or_inf(fabs(ga[2])));
+      v[1] = fmax(fmax(check_finite_or_inf(fabs(gl[0])), check_finite_or_inf(fabs(gl[1]))), check_finite_or_inf(fabs(gl[2])));
+      v[2] = v_rom; v[3] = v_terr; v[4] = v_force;
+    }
+    if (summary) {                                                                 // (B) the tile's families into the running records
+#pragma unroll
+      for (int f = 0; f < CHECK_FAMILIES; ++f) {
+        const double mx = wg_reduce<1, CHECK_TILE>(v[f], check_red);               // (m >= 1: a violation, >= 0, is among them)
+        const double at = wg_reduce<2, CHECK_TILE>(v[f] == mx ? (double)threadIdx.x : (double)CHECK_TILE, check_red);
+        const double over = wg_reduce<0, CHECK_TILE>(v[f] > A.tol[f] ? 1.0 : 0.0, check_red);
+        if (mx > run_max[f]) { run_max[f] = mx; run_row[f] = row0 + j0 + (long long)at; }
+        run_cnt[f] += (long long)over;
+      }
+    }
+    __syncthreads();
+    if (out_b) {                                                                   // (C) the tile goes out flat
+      double *o = out_b + (size_t)j0 * CHECK_COLS;
+      for (int e = threadIdx.x; e < m * CHECK_COLS; e += CHECK_TILE) o[e] = check_tile[e];
+    }
+    __syncthreads();
+  }
+  if (summary && threadIdx.x == 0) {
+    if (A.accumulate && n == 0) return;                                            // nothing to merge
+#pragma unroll
+    for (int f = 0; f < CHECK_FAMILIES; ++f) {
+      CheckRecord rec = {run_max[f], run_row[f], run_cnt[f]};
+      CheckRecord *dst = summary + (size_t)b * CHECK_FAMILIES + f;
+      if (A.accumulate) {
+        const CheckRecord old = *dst;
+        if (!(rec.max > old.max)) { rec.max = old.max; rec.row = old.row; }
+        rec.count += old.count;
+      }
+      *dst = rec;
+    }
+  }
 }
 
 // Goals of receding windows from their global paths (qtos_path_goal*; Global_Planner.update / spine_step, QTOS/planner.py:139-161,

@@ -4,7 +4,9 @@
 pointed at ``python -m qtos_amd.main --out build/traj.csv`` unchanged otherwise.  ``--log PATH`` (``-``: stdout) writes
 the per-solve report in the layout of the reference's ``logs/towr_log.out`` (report.py).  ``--selftest`` creates the planner
 through the KKT self-test (capi.Planner(checked=True)): a transcription whose elimination orders all fail it is not planned --
-the attempts are printed and the exit status is 2, the reference's "numerical failure" class.
+the attempts are printed and the exit status is 2, the reference's "numerical failure" class.  ``--check`` prints, behind the
+solve, what the plan violates between its knots: one line per family of the plan check (plan_check.py); the exit status is
+unchanged.
 """
 import sys
 
@@ -18,6 +20,9 @@ def main(argv=None):
     checked = "--selftest" in argv
     if checked:
         argv.remove("--selftest")
+    check = "--check" in argv
+    if check:
+        argv.remove("--check")
     for opt in ("--out", "--heightfield", "--log"):
         if opt in argv:
             i = argv.index(opt)
@@ -39,7 +44,7 @@ def main(argv=None):
         # --log PATH: the per-solve report (report.py) goes to PATH; --log -: to stdout, where it ends with the status line
         # -- the reference's logs/towr_log.out back from `python -m qtos_amd.main ... --log - > logs/towr_log.out`
         try:
-            status = lp.solve(args, out_csv=out, log=sys.stdout if log == "-" else log)
+            status = lp.solve(args, out_csv=out, log=sys.stdout if log == "-" else log, check=check)
         except capi.SelftestError as e:
             for t in e.attempts:
                 print("KKT self-test: " + t.describe())

@@ -9,6 +9,7 @@ the process exit status the reference checks (0 = solved, scripts/main.py:93-103
 calls, QTOS/generateHeightField.py:344-386).
 """
 import os
+import sys
 
 import numpy as np
 
@@ -118,8 +119,12 @@ class LocalPlanner:
                          r=[a.get('-r') for a in args_list])
         return statuses
 
-    def solve(self, args, out_csv=TRAJ_OUT, log=None):
+    def solve(self, args, out_csv=TRAJ_OUT, log=None, check=False):
         """One plan; writes the CSV where the reference's ``docker cp`` would put it.
+
+        check: True or a writable file object -- behind the solve one line per family of the plan check (qtos_plan_check: the
+        largest violation of the CSV's rows, its time, the rows over capi.CHECK_TOL) is written there (True: stdout) and the
+        records are kept in ``self.last["check"]``.  The return value is unchanged.
 
         log: a path or a writable file object -- the per-solve report (report.py: the layout of the reference's
         logs/towr_log.out) is switched on for this call and written there.  None: the call runs without it."""
@@ -145,6 +150,18 @@ class LocalPlanner:
             else:
                 with open(log, "w") as fh:
                     fh.write(text)
+        if check:
+            # what the plan violates between its knots, over the rows of the CSV (plan_check.py); the status stays the solver's
+            from . import plan_check
+            P = self.planner(args.get('-duration'))
+            n_rows = len(self.last["rows"][0])
+            params = capi.check_params(hz=self.cfg.hz, n_rows=n_rows)
+            _, summary = P.plan_check(self.last["nodes"][:1], self.last["t0"][:1], params, rows=False)
+            self.last["check"] = summary[0]
+            text = "\n".join(plan_check.report_lines(summary[0], self.last["t0"][0], self.cfg.hz, list(params.tol))) + "\n"
+            out = check if hasattr(check, "write") else sys.stdout
+            out.write(text)
+            out.flush()
         if out_csv:
             d = os.path.dirname(out_csv)
             if d:

@@ -215,11 +215,17 @@ class ShiftedWindows:
                dict's entries are ``capi.feedback_params``' keywords (gain_pos, gain_ang, gain_foot, max_pos, max_ang, max_foot,
                latency, snap, zero_filter, rom_tol, snap_tol, nominal, max_deviation, cfg; the leg and the quaternion flag are the
                track's).  The order of a replan is then hand-over, joint rows, track (whose ``fill`` writes the measurements of the
-               segment), feedback, path goal (so that ``path_base="state"`` sees the corrected start), stitch."""
+               segment), feedback, path goal (so that ``path_base="state"`` sees the corrected start), stitch.
+    check      None (the default): nothing is queued and nothing is allocated.  A ``capi.check_params(...)`` (needs
+               ``trajectory``; its tol is read, its rate and rows are the stitch's): k_plan_check (qtos_plan_check_device, the
+               rule: ``plan_check.check_rows`` / ``summarise`` / ``accumulate``) is queued in front of every stitch and in
+               ``finish()``, over exactly the rows that stitch appends and with its cursor, and merges what they violate into
+               ``self.check_summary`` (B x 5 records as B x 5 x 3 words); ``check_worst()`` reads them.  It writes nothing else:
+               plans and trajectory rows are the same bits with and without it."""
 
     def __init__(self, planner, start, goal_step, map_id=None, advance=2.5, search=0.4, stream=None, warm="none", x_range=None,
                  handover=None, contact="force", height_set=(0.0,), trajectory=None, stitch="clean", path=None, path_base="spine",
-                 path_hold=True, joints=None, track=None, feedback=None):
+                 path_hold=True, joints=None, track=None, feedback=None, check=None):
         import torch
         self.torch = torch
         self.P = planner
@@ -321,6 +327,18 @@ class ShiftedWindows:
                                                   quaternion=bool(t.flags & capi.TRACK_QUAT), ee_shift=float(t.ee_shift), robot=t, **kw)
             self.feedback_status = torch.zeros((B,), dtype=torch.int32, device=dev)
             self.feedback_err = torch.zeros((B, 18), **f64)
+        self._check = None
+        if check is not None:
+            from . import capi, plan_check
+            if self.traj is None:
+                raise ValueError("check needs a trajectory ring (trajectory=N)")
+            if not hasattr(planner.lib, "qtos_plan_check_device"):
+                raise RuntimeError("this build of the planner library has no plan-check kernel (qtos_plan_check_device)")
+            # the stitch's rows: its first row, its clamp of the count (the ring's capacity), its clock
+            self._check = check.copy()
+            self._check.hz, self._check.first_row, self._check.n_rows = self.hz, int(self._stitch.first_row), int(trajectory)
+            self._check.flags |= capi.CHECK_ACCUMULATE
+            self.check_summary = torch.from_numpy(plan_check.empty_summary(B).view(np.float64).reshape(B, 5, 3).copy()).to(dev)
         self.stream = stream if stream is not None else torch.cuda.current_stream(dev)
         self.have_plan = False
         self.x_range = x_range     # (lo, hi): a window that walks past an end of its heightfield turns round (no resets)
@@ -519,6 +537,25 @@ class ShiftedWindows:
                                                          self.goal.data_ptr() if moves else None, self.feedback_err.data_ptr(),
                                                          self.feedback_status.data_ptr(), sp), "qtos_start_feedback_device")
 
+    def _plan_check(self, params, n_rows, sp):
+        """Queue k_plan_check in front of a stitch: the rows that stitch appends, merged into the windows' records (the kernel
+        reads the cursor and the clock the stitch behind it moves on; no table is written)."""
+        import ctypes as C
+        self._call(self.P.lib.qtos_plan_check_device(self.P.h, self.B, C.byref(params), self.nodes.data_ptr(), self.t0.data_ptr(),
+                                                     None if self.map_id is None else self.map_id.data_ptr(), None, n_rows,
+                                                     self.cursor.data_ptr(), None, self.check_summary.data_ptr(), sp),
+                   "qtos_plan_check_device")
+
+    def check_worst(self):
+        """What the windows' executed rows violated so far, [B, 5] records of plan_check.SUMMARY (the families dyn_ang, dyn_lin,
+        rom, terrain, force: the largest violation, the trajectory row -- the window's clock, as ``cursor`` counts it -- that
+        attains it, the rows over the tolerance), as numpy (the stream is synchronised)."""
+        from . import plan_check
+        if self._check is None:
+            raise RuntimeError("check_worst() needs the plan check (check=capi.check_params(...))")
+        self.stream.synchronize()
+        return self.check_summary.cpu().numpy().view(plan_check.SUMMARY).reshape(self.B, 5)
+
     def track_rows(self, b):
         """Window b's newest min(cursor, trajectory) track rows in time order and their status words, as numpy (the stream is
         synchronised): row for row the measured poses and errors of ``trajectory_rows(b)``."""
@@ -579,6 +616,10 @@ class ShiftedWindows:
                 g.first_row, g.n_rows = first, n
                 with self.torch.cuda.stream(self.stream):
                     self._track_rows(g, None, C.c_void_p(self.stream.cuda_stream))
+            if self._check is not None:
+                g = self._check.copy()
+                g.first_row, g.n_rows = first, n
+                self._plan_check(g, None, C.c_void_p(self.stream.cuda_stream))
             self._call(self.P.lib.qtos_stitch_device(self.P.h, self.B, C.byref(s), self.nodes.data_ptr(), None, self.t0.data_ptr(),
                                                      self.traj.data_ptr(), self.cursor.data_ptr(), C.c_void_p(self.stream.cuda_stream)),
                        "qtos_stitch_device")
@@ -650,6 +691,8 @@ class ShiftedWindows:
                     self._start_feedback(sp)
                     if self.path is not None:
                         self._path_goal(self.path_params, self.offset, sp)
+                if self._check is not None:
+                    self._plan_check(self._check, self.row.data_ptr(), sp)
                 self._call(P.lib.qtos_stitch_device(P.h, B, C.byref(self._stitch), self.nodes.data_ptr(), self.row.data_ptr(),
                                                     self.t0.data_ptr(), self.traj.data_ptr(), self.cursor.data_ptr(), sp),
                            "qtos_stitch_device")
