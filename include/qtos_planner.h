@@ -579,6 +579,81 @@ int qtos_plan_check_device(QtosPlanner *p, int B, const QtosPlanCheck *c, const 
 int qtos_plan_check(QtosPlanner *p, int B, const QtosPlanCheck *c, const double *nodes, const double *t0, const int *map_id,
                     const int *first_row, const int *n_rows, const long long *cursor, double *rows, QtosCheckRecord *summary);
 
+/* Rollout: the windows' robots as simulated rigid bodies.  Replaces what scripts/run.py asks its simulator for once per tick (step
+ * the robot, read traj_vec back) for B windows at once, for a user without PyBullet: the planner's own model -- ONE rigid body
+ * with mass, inertia_b and gravity, the plan's forces at the plan's feet -- integrated forward under a plan, with a PD wrench
+ * towards the plan and an optional push (k_rollout, one workgroup per window; the rule: rollout.py).  It has no contacts, no
+ * legs' inertia and no friction limits on the applied forces.  Per row k of a window, at the plan time min(k / hz, T), with c
+ * qtos_sample_csv's row: r_p = c[1:4], v_p = c[19:22], q_p the quaternion (x, y, z, w) of Rz Ry Rx of c[4:7], w_p = M(th) thd
+ * the world angular velocity, F = ff_scale sum f_e, tau_p = ff_scale sum (p_e - r_p) x f_e about the PLANNED CoM.
+ * State of a window, 13 doubles in d_state: r[3], v[3] (world), q[4] body to world (x, y, z, w), w_b[3] (body frame).  One tick
+ * takes `substeps` steps of h = 1 / (hz substeps) with the row's quantities held; every step, from the state at its start:
+ *   e = r - r_p;  F_fb = clip(-(kp_lin e) - kd_lin (v - v_p), +-f_fb_max) per component (a limit of 0: no clip)
+ *   a = ((F + F_fb) + F_push) / m_s - g e_z, m_s = mass mass_scale[b];  R = R(q);  q_e = q_p (x) conj(q), negated if its w < 0
+ *   tau_fb = clip(kp_ang 2 vec(q_e) + kd_ang (w_p - R w_b), +-t_fb_max);  tau = ((tau_p - e x F) + tau_fb) + tau_push
+ *   v += h a, then r += h v;  w_b += h Ib_s^-1 (R^T tau - w_b x Ib_s w_b), Ib_s = mass_scale[b] inertia_b, Ib_s^-1 =
+ *   inertia_b_inv / mass_scale[b];  q = (q + (h / 2) q (x) (w_b, 0)) / |.| with the new w_b
+ * one rounded operation after the other in rollout.py's order: only +, -, x, / and sqrt.  The push, push[b] = (F_push, tau_push)
+ * in the world, acts on the ticks c with push_from <= c < push_from + push_ticks, c = count[b] + j the window's running tick
+ * count (count[b] += n behind the call).
+ * Row k holds the state at the START of tick k; behind a call over n rows the carried state is the state at row first + n.  With
+ * QTOS_ROLLOUT_INIT the state is first set from row `first` of the plan (r_p, v_p, q_p, R^T w_p); without it the carried state
+ * is used: the body does not jump when the plan under it changes.  The flag holds for every window of the call that has rows;
+ * a window whose carried word has QTOS_ROLLOUT_PENDING set is set on its plan likewise, by the first call that gives it rows,
+ * which clears the bit (a window with n = 0 keeps it): for windows that get their first rows in different calls.
+ * Outputs per row, in qtos_track's addressing (table, or ring with capacity / cursor):
+ *   meas    the row qtos_track / qtos_start_feedback read: position, Euler angles (roll = atan2(R21, R22), pitch = asin(clip(-R20)),
+ *           yaw = atan2(R10, R00) of R(q)), or with QTOS_ROLLOUT_QUAT position and q; the twelve joint angles are columns 1 .. 12
+ *           of the same row of d_joint (qtos_joint_rows' rows, same addressing).  With d_joint NULL those columns are not touched
+ *   rows    20 columns: 0 the time stamp (qtos_sample_csv's, to the bit), 1 .. 3 r, 4 .. 6 the Euler angles, 7 .. 9 v, 10 .. 12 R w_b,
+ *           13 .. 16 q, 17 |e|, 18 2 |vec(q_e)| (about the angle between body and plan), 19 |F_fb| of the tick's first step
+ *   status  bit 0 fallen: |e| > dev_max or column 18 > tilt_max (a limit of 0: never); bit 1 a non-finite state; both are kept in
+ *           the window's carried word d_word[b]: the row that sets one and every later row carry it, take no step and repeat
+ *           the frozen state (column 19 is 0, bits 3 and 4 are clear).  Bit 2 gimbal (the clip of the Euler extraction acts),
+ *           bit 3 a feedback component was clipped in this tick, bit 4 the push acts in this tick */
+#define QTOS_ROLLOUT_INIT 1        /* flags: the state is set from the plan's row `first` */
+#define QTOS_ROLLOUT_QUAT 2        /* flags: meas rows carry the quaternion (19 doubles), as QTOS_TRACK_QUAT */
+#define QTOS_ROLLOUT_PENDING 32    /* d_word[b], never a row's status: window b is set on its plan by its first call with rows */
+#define QTOS_ROLLOUT_COLS 20
+#define QTOS_ROLLOUT_STATE 13
+typedef struct QtosRollout {
+  double hz;                    /* rows per second (> 0) */
+  int substeps;                 /* steps per tick, 1 .. 1000 */
+  int first_row;                /* first row where d_first_row is NULL; 0 .. 1000000 */
+  int n_rows;                   /* table mode: rows per window; both modes: the count where d_n_rows is NULL (>= 0) */
+  long long capacity;           /* 0: table mode; > 0: rows per window in the rings */
+  int flags;                    /* QTOS_ROLLOUT_* */
+  double mass, gravity;         /* the body (mass > 0) */
+  double inertia_b[9];          /* row-major, body frame */
+  double inertia_b_inv[9];      /* its inverse, formed once on the host in float64 */
+  double ff_scale;              /* the plan's forces are applied times this (1: as planned, 0: free fall) */
+  double kp_lin[3], kd_lin[3];  /* N / m, N s / m, world axes */
+  double kp_ang[3], kd_ang[3];  /* N m / rad, N m s / rad, world axes */
+  double f_fb_max, t_fb_max;    /* clip of every feedback component (0: none) */
+  double dev_max, tilt_max;     /* fallen beyond these (m, rad; 0: never) */
+  long long push_from, push_ticks;   /* the ticks the push acts on (>= 0) */
+} QtosRollout;
+/* nodes B x n_vars, t0 B; first_row B and n_rows B may be NULL (n clamped to 0 .. n_rows or capacity, a window with n = 0 keeps its
+ * state, count and word); cursor B, NULL in table mode; joint B x rows x 37, mass_scale B (NULL: 1) and push B x 6 may be NULL;
+ * state B x 13, count B and word B in / out; meas B x rows x 18 (19 with QTOS_ROLLOUT_QUAT), rows B x rows x 20 (may be NULL),
+ * status B x rows; rows = n_rows or capacity.
+ * Device form: all pointers but `s` in device memory, one kernel queued on `stream`, no handle state is read or written but the
+ * sampling tables -- it may be queued while a call is open, in front of qtos_track_device with the same nodes, t0, n_rows and
+ * cursor.  Host form: host pointers, synchronous, through device buffers of its own as qtos_track (no -5); the in / out arrays
+ * and the outputs are copied in and out whole.
+ * Both: -1 on a null planner, and with the reason in qtos_last_error on a null required pointer, B < 1, capacity < 0, a ring
+ * without cursor, a table with n_rows < 1, n_rows < 0, first_row outside 0 .. 1000000, substeps outside 1 .. 1000, hz or mass not
+ * > 0, a singular inertia_b, a negative push_from or push_ticks; -2 on a HIP error; -3 out of memory. */
+int qtos_rollout_device(QtosPlanner *p, int B, const QtosRollout *s, const double *d_nodes, const double *d_t0,
+                        const int *d_first_row /* may be NULL */, const int *d_n_rows /* may be NULL */,
+                        const long long *d_cursor /* NULL in table mode */, const double *d_joint /* may be NULL */,
+                        const double *d_mass_scale /* may be NULL = 1 */, const double *d_push /* may be NULL */,
+                        double *d_state /* in/out */, long long *d_count /* in/out */, int *d_word /* in/out */, double *d_meas,
+                        double *d_rows /* may be NULL */, int *d_status, void *stream);
+int qtos_rollout(QtosPlanner *p, int B, const QtosRollout *s, const double *nodes, const double *t0, const int *first_row,
+                 const int *n_rows, const long long *cursor, const double *joint, const double *mass_scale, const double *push,
+                 double *state, long long *count, int *word, double *meas, double *rows, int *status);
+
 /* Goals of receding windows from their global paths: where the next plan goes.  Replaces Global_Planner.update / spine_step
  * (QTOS/planner.py:139-161, 195-230) and Combiner.plan_init / spine_step (QTOS/combiner.py:137-212, 223-225) for B windows at
  * once: a window's A* "spine" -- two cubic splines X_p, Y_p over one set of knots -- is read one horizon ahead of the new plan's

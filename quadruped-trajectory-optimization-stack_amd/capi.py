@@ -408,6 +408,47 @@ def check_params(hz=1000.0, first_row=0, n_rows=0, tol=CHECK_TOL, accumulate=Fal
     return g
 
 
+class QtosRollout(C.Structure):
+    """Parameters of a rollout (qtos_rollout*, include/qtos_planner.h); rollout.rollout_rows reads the same fields."""
+    _fields_ = [
+        ("hz", C.c_double), ("substeps", C.c_int), ("first_row", C.c_int), ("n_rows", C.c_int), ("capacity", C.c_longlong),
+        ("flags", C.c_int), ("mass", C.c_double), ("gravity", C.c_double), ("inertia_b", C.c_double * 9),
+        ("inertia_b_inv", C.c_double * 9), ("ff_scale", C.c_double), ("kp_lin", C.c_double * 3), ("kd_lin", C.c_double * 3),
+        ("kp_ang", C.c_double * 3), ("kd_ang", C.c_double * 3), ("f_fb_max", C.c_double), ("t_fb_max", C.c_double),
+        ("dev_max", C.c_double), ("tilt_max", C.c_double), ("push_from", C.c_longlong), ("push_ticks", C.c_longlong),
+    ]
+
+    def copy(self):
+        return QtosRollout.from_buffer_copy(self)
+
+
+ROLLOUT_INIT, ROLLOUT_QUAT = 1, 2        # QTOS_ROLLOUT_INIT, QTOS_ROLLOUT_QUAT of include/qtos_planner.h
+ROLLOUT_PENDING = 32                     # QTOS_ROLLOUT_PENDING: in a window's carried word, spent by its first call with rows
+ROLLOUT_COLS, ROLLOUT_STATE = 20, 13     # QTOS_ROLLOUT_COLS, QTOS_ROLLOUT_STATE
+
+
+def rollout_params(cfg=None, hz=1000.0, substeps=1, first_row=0, n_rows=0, capacity=0, init=False, quaternion=False, mass=None,
+                   gravity=None, inertia_b=None, ff_scale=1.0, kp_lin=0.0, kd_lin=0.0, kp_ang=0.0, kd_ang=0.0, f_fb_max=0.0,
+                   t_fb_max=0.0, dev_max=0.0, tilt_max=0.0, push_from=0, push_ticks=0):
+    """A QtosRollout.  cfg: the planner's PlannerConfig (None: the defaults'), which gives mass, gravity and inertia_b unless
+    those are given; the inertia is inverted here, in float64 (a singular one raises ValueError).  The gains are one number
+    for the three world axes or three; the defaults are an open loop without limits.  capacity 0: table mode."""
+    from . import rollout
+    r = rollout.RolloutParams(cfg, mass, gravity, inertia_b, substeps, ff_scale, kp_lin, kd_lin, kp_ang, kd_ang, f_fb_max, t_fb_max,
+                              dev_max, tilt_max, push_from, push_ticks, quaternion)
+    g = QtosRollout()
+    g.hz, g.substeps, g.first_row, g.n_rows, g.capacity = float(hz), r.substeps, int(first_row), int(n_rows), int(capacity)
+    g.flags = (ROLLOUT_INIT if init else 0) | r.flags
+    g.mass, g.gravity, g.ff_scale = r.mass, r.gravity, r.ff_scale
+    for i in range(9):
+        g.inertia_b[i], g.inertia_b_inv[i] = float(r.inertia_b[i]), float(r.inertia_b_inv[i])
+    for i in range(3):
+        g.kp_lin[i], g.kd_lin[i], g.kp_ang[i], g.kd_ang[i] = float(r.kp_lin[i]), float(r.kd_lin[i]), float(r.kp_ang[i]), float(r.kd_ang[i])
+    g.f_fb_max, g.t_fb_max, g.dev_max, g.tilt_max = r.f_fb_max, r.t_fb_max, r.dev_max, r.tilt_max
+    g.push_from, g.push_ticks = r.push_from, r.push_ticks
+    return g
+
+
 class SelftestError(RuntimeError):
     """No elimination order passed the KKT self-test (qtos_planner_create_checked returned -6); `attempts`: the QtosSelftest
     records in the order they were tried."""
@@ -437,6 +478,7 @@ EXPORTS = [
     "qtos_terrain_env", "qtos_terrain_env_device", "qtos_set_heightfields_device",
     "qtos_joint_rows", "qtos_joint_rows_device", "qtos_track", "qtos_track_device",
     "qtos_start_feedback", "qtos_start_feedback_device", "qtos_plan_check", "qtos_plan_check_device",
+    "qtos_rollout", "qtos_rollout_device",
 ]
 
 _lib = None
@@ -573,6 +615,10 @@ def load():
         llp = C.POINTER(C.c_longlong)
         lib.qtos_plan_check.argtypes = [vp, C.c_int, C.POINTER(QtosPlanCheck), dp, dp, ip, ip, ip, llp, dp, vp]
         lib.qtos_plan_check_device.argtypes = [vp, C.c_int, C.POINTER(QtosPlanCheck)] + [vp] * 9
+    if hasattr(lib, "qtos_rollout"):                 # (the rollout kernel; older builds loaded through QTOS_LIB lack it)
+        llp = C.POINTER(C.c_longlong)
+        lib.qtos_rollout.argtypes = [vp, C.c_int, C.POINTER(QtosRollout), dp, dp, ip, ip, llp, dp, dp, dp, dp, llp, ip, dp, dp, ip]
+        lib.qtos_rollout_device.argtypes = [vp, C.c_int, C.POINTER(QtosRollout)] + [vp] * 15
     if hasattr(lib, "qtos_set_heightfields_device"):
         lib.qtos_set_heightfields_device.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, vp]
     _lib = lib
@@ -1075,6 +1121,56 @@ class Planner:
         self._chk(self.lib.qtos_track(self.h, B, C.byref(params), _dp(nodes), _dp(t0), _ip(first), _ip(per),
                                       _llp(cur), _dp(meas), _dp(goal), _llp(count), _dp(total), _dp(out), _ip(status)), "track")
         return out, status, count, total
+
+    def has_rollout(self):
+        return hasattr(self.lib, "qtos_rollout")
+
+    def rollout(self, nodes, t0, params, first_row=None, n_rows=None, cursor=None, joint=None, mass_scale=None, push=None, state=None,
+                count=None, word=None, meas=None, rows=True, status=None):
+        """Roll the windows' bodies out over rows of the plans in `nodes` (qtos_rollout, host form; the rule:
+        rollout.rollout_rows).  params: a QtosRollout (rollout_params()).  state (B, 13), count (B) int64 and word (B) int32
+        are what the windows carry (None: zeros -- give params the init flag then, or a word of ROLLOUT_PENDING, which sets
+        each window on its plan at its own first call with rows).  joint: (B, rows, 37) joint rows whose
+        columns 1 .. 12 become the measured joint angles (None: those columns of `meas` stay as they are); mass_scale: a number
+        or B; push: (B, 6).  rows = params.n_rows (table mode) or params.capacity (ring mode: `meas`, `rows`, `status` and
+        `cursor` are the rings as they stand, joint a ring with the same addressing).  meas: (B, rows, 18), or 19 with params'
+        quaternion flag (None: zeros); rows: True, an array (B, rows, 20) or False / None for no table.  Returns new arrays
+        (meas, rows or None, status, state, count, word)."""
+        if not self.has_rollout():
+            raise RuntimeError("this build of the planner library has no rollout kernel (qtos_rollout)")
+        nodes = np.ascontiguousarray(nodes, np.float64).reshape(-1, self.n)
+        B = nodes.shape[0]
+        t0 = np.ascontiguousarray(np.broadcast_to(np.asarray(t0, np.float64), (B,)))
+        first, per = _i32(first_row, B), _i32(n_rows, B)
+        nr = max(int(params.capacity) if params.capacity > 0 else int(params.n_rows), 0)
+        mcols = 19 if params.flags & ROLLOUT_QUAT else 18
+        cur = None
+        if params.capacity > 0:
+            if cursor is None:
+                raise ValueError("ring mode takes the ring's cursor")
+            cur = np.ascontiguousarray(np.broadcast_to(np.asarray(cursor, np.int64), (B,)))
+        joint = None if joint is None else np.ascontiguousarray(joint, np.float64)
+        if joint is not None and joint.shape != (B, nr, CSV_COLS):
+            raise ValueError("joint is (B, %d, %d)" % (nr, CSV_COLS))
+        ms = None if mass_scale is None else np.ascontiguousarray(np.broadcast_to(np.asarray(mass_scale, np.float64), (B,)))
+        push = None if push is None else np.ascontiguousarray(push, np.float64).reshape(B, 6)
+        state = np.zeros((B, ROLLOUT_STATE)) if state is None else np.array(state, np.float64).reshape(B, ROLLOUT_STATE)
+        count = np.zeros(B, np.int64) if count is None else np.array(np.broadcast_to(np.asarray(count, np.int64), (B,)))
+        word = np.zeros(B, np.int32) if word is None else np.array(np.broadcast_to(np.asarray(word, np.int32), (B,)))
+        meas = np.zeros((B, nr, mcols)) if meas is None else np.array(meas, np.float64)
+        if rows is True:
+            rows = np.zeros((B, nr, ROLLOUT_COLS))
+        elif rows is False or rows is None:
+            rows = None
+        else:
+            rows = np.array(rows, np.float64)
+        status = np.zeros((B, nr), np.int32) if status is None else np.array(status, np.int32)
+        if meas.shape != (B, nr, mcols) or status.shape != (B, nr) or (rows is not None and rows.shape != (B, nr, ROLLOUT_COLS)):
+            raise ValueError("meas is (B, %d, %d), rows (B, %d, %d) and status (B, %d)" % (nr, mcols, nr, ROLLOUT_COLS, nr))
+        self._chk(self.lib.qtos_rollout(self.h, B, C.byref(params), _dp(nodes), _dp(t0), _ip(first), _ip(per), _llp(cur), _dp(joint),
+                                        _dp(ms), _dp(push), _dp(state), _llp(count), _ip(word), _dp(meas), _dp(rows), _ip(status)),
+                  "rollout")
+        return meas, rows, status, state, count, word
 
     def has_start_feedback(self):
         return hasattr(self.lib, "qtos_start_feedback")

@@ -454,6 +454,92 @@ int qtos_plan_check(QtosPlanner *p, int B, const QtosPlanCheck *c, const double 
   return rc ? rc : S.download();
 }
 
+// ---- the windows' robots as simulated rigid bodies (k_rollout, window_kernels.hpp) -----------------------------
+// The argument checks of both forms, and QtosRollout as k_rollout reads it.  Every -1 but the null planner's leaves its reason in
+// the handle's err.
+static int rollout_args(QtosPlanner *p, int B, const QtosRollout *s, const void *nodes, const void *t0, const void *cursor,
+                        const void *state, const void *count, const void *word, const void *meas, const void *status, RolloutArgs *A) {
+  if (!p) return -1;
+  const char *why = nullptr;
+  if (B < 1) why = "B < 1";
+  else if (!s || !nodes || !t0 || !state || !count || !word || !meas || !status) why = "a required pointer is null";
+  else if (s->capacity < 0 || (s->capacity > 0 && !cursor)) why = "capacity >= 0, and a ring needs its cursor";
+  else if (s->n_rows < 0 || (s->capacity == 0 && s->n_rows < 1)) why = "n_rows >= 0, and a table has n_rows >= 1";
+  else if (s->first_row < 0 || s->first_row > 1000000) why = "first_row is 0 .. 1000000";
+  else if (s->substeps < 1 || s->substeps > 1000) why = "substeps is 1 .. 1000";
+  else if (!(s->hz > 0) || !(s->hz <= 1e9)) why = "hz is > 0";
+  else if (!(s->mass > 0) || !(s->mass <= 1.7976931348623157e308)) why = "mass is > 0";
+  else if (s->push_from < 0 || s->push_ticks < 0) why = "push_from and push_ticks are >= 0";
+  if (!why) {
+    const double *a = s->inertia_b;
+    const double det = a[0] * (a[4] * a[8] - a[5] * a[7]) - a[1] * (a[3] * a[8] - a[5] * a[6]) + a[2] * (a[3] * a[7] - a[4] * a[6]);
+    double big = 0;
+    bool finite = std::isfinite(det);
+    for (int i = 0; i < 9; ++i) {
+      big = std::max(big, std::fabs(a[i]));
+      finite = finite && std::isfinite(a[i]) && std::isfinite(s->inertia_b_inv[i]);
+    }
+    if (!finite || !(std::fabs(det) > 1e-12 * big * big * big)) why = "inertia_b is singular (or it or inertia_b_inv is not finite)";
+  }
+  if (why) {
+    p->err = std::string("qtos_rollout: ") + why;
+    return -1;
+  }
+  A->hz = s->hz; A->h = 1.0 / (s->hz * (double)s->substeps);
+  A->mass = s->mass; A->gravity = s->gravity; A->ff_scale = s->ff_scale;
+  A->f_fb_max = s->f_fb_max; A->t_fb_max = s->t_fb_max; A->dev_max = s->dev_max; A->tilt_max = s->tilt_max;
+  for (int i = 0; i < 9; ++i) { A->Ib[i] = s->inertia_b[i]; A->Ii[i] = s->inertia_b_inv[i]; }
+  for (int i = 0; i < 3; ++i) {
+    A->kp_lin[i] = s->kp_lin[i]; A->kd_lin[i] = s->kd_lin[i]; A->kp_ang[i] = s->kp_ang[i]; A->kd_ang[i] = s->kd_ang[i];
+  }
+  A->capacity = s->capacity; A->push_from = s->push_from; A->push_ticks = s->push_ticks;
+  A->first_row = s->first_row; A->n_rows = s->n_rows; A->substeps = s->substeps; A->flags = s->flags;
+  return 0;
+}
+
+int qtos_rollout_device(QtosPlanner *p, int B, const QtosRollout *s, const double *d_nodes, const double *d_t0, const int *d_first_row,
+                        const int *d_n_rows, const long long *d_cursor, const double *d_joint, const double *d_mass_scale,
+                        const double *d_push, double *d_state, long long *d_count, int *d_word, double *d_meas, double *d_rows,
+                        int *d_status, void *stream_) {
+  RolloutArgs A;
+  if (rollout_args(p, B, s, d_nodes, d_t0, d_cursor, d_state, d_count, d_word, d_meas, d_status, &A)) return -1;
+  const long long most = most_rows((int)std::min<long long>(A.capacity, INT_MAX), A.n_rows, d_n_rows);
+  if (most < 1) return 0;
+  HIPCHK(p, hipSetDevice(p->device));
+  if (most > ROLLOUT_TICK)
+    hipLaunchKernelGGL(k_rollout<ROLLOUT_TILE>, dim3(B), dim3(ROLLOUT_TILE), 0, (hipStream_t)stream_, p->d_sp, A, d_nodes, d_t0, d_first_row,
+                       d_n_rows, d_cursor, d_joint, d_mass_scale, d_push, d_state, d_count, d_word, d_meas, d_rows, d_status, B);
+  else
+    hipLaunchKernelGGL(k_rollout<ROLLOUT_TICK>, dim3(B), dim3(ROLLOUT_TICK), 0, (hipStream_t)stream_, p->d_sp, A, d_nodes, d_t0, d_first_row,
+                       d_n_rows, d_cursor, d_joint, d_mass_scale, d_push, d_state, d_count, d_word, d_meas, d_rows, d_status, B);
+  HIPCHK(p, hipGetLastError());
+  return 0;
+}
+
+int qtos_rollout(QtosPlanner *p, int B, const QtosRollout *s, const double *nodes, const double *t0, const int *first_row,
+                 const int *n_rows, const long long *cursor, const double *joint, const double *mass_scale, const double *push,
+                 double *state, long long *count, int *word, double *meas, double *rows_out, int *status) {
+  RolloutArgs A;
+  if (rollout_args(p, B, s, nodes, t0, cursor, state, count, word, meas, status, &A)) return -1;
+  HIPCHK(p, hipSetDevice(p->device));
+  const size_t rows = (size_t)B * (size_t)(A.capacity > 0 ? A.capacity : A.n_rows);
+  const size_t mcols = (A.flags & QTOS_ROLLOUT_QUAT) ? 19 : 18;
+  Staging S(p);
+  const double *d_nodes = S.in(nodes, (size_t)B * p->M.n_vars), *d_t0 = S.in(t0, B);
+  const int *d_first = S.in(first_row, B), *d_n = S.in(n_rows, B);
+  const long long *d_cur = S.in(cursor, B);
+  const double *d_joint = S.in(joint, rows * QTOS_CSV_COLS), *d_ms = S.in(mass_scale, B), *d_push = S.in(push, (size_t)B * 6);
+  double *d_state = S.inout(state, (size_t)B * 13);
+  long long *d_count = S.inout(count, B);
+  int *d_word = S.inout(word, B);
+  double *d_meas = S.inout(meas, rows * mcols), *d_rows = S.inout(rows_out, rows * ROLLOUT_COLS);
+  int *d_st = S.inout(status, rows);
+  if (S.rc) return S.rc;
+  const int rc = qtos_rollout_device(p, B, s, d_nodes, d_t0, d_first, d_n, d_cur, d_joint, d_ms, d_push, d_state, d_count, d_word, d_meas,
+                                     d_rows, d_st, nullptr);
+  return rc ? rc : S.download();
+}
+
 // ---- goals of receding windows from their global paths (k_path_goal, window_kernels.hpp) ------------------------
 // The argument checks of both forms, and QtosPathGoal as k_path_goal reads it.
 static int path_goal_args(const QtosPlanner *p, int B, const QtosPathGoal *g, const void *knots, const void *coef, const void *n_pieces,

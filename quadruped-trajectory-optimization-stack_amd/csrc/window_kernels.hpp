@@ -9,6 +9,7 @@
 //   k_track         : measured states and tracking errors of the windows
 //   k_start_feedback: the next plan's start from the measured state
 //   k_plan_check    : what the windows' plans violate between their knots
+//   k_rollout       : the windows' robots as simulated rigid bodies (the measured states k_track reads)
 //   k_path_goal     : goals of the windows from their global paths
 //   k_path_plan     : the global paths (A* and spines)
 //   k_probe*        : the probe and the stamp of the windows' heightfields
@@ -924,6 +925,301 @@ __global__ __launch_bounds__(CHECK_TILE) void k_plan_check(const SamplePlan *Sd,
       }
       *dst = rec;
     }
+  }
+}
+
+// Rollout (qtos_rollout*): the windows' robots as simulated rigid bodies -- what scripts/run.py asks PyBullet for once per tick.
+// The planner's own model, one rigid body under the plan's foot forces, a PD wrench towards the plan and an optional push, is
+// integrated forward row by row; the states become the measured ring k_track and k_start_feedback read.  The statement of the
+// rule is rollout.py, and every function below switches contraction off: one rounded operation per operation of the rule, in
+// its order.  The state is a sequential chain by definition, so one workgroup owns one window and walks its tiles in order.
+// Per tile: (A) a lane takes a row -- the plan row with k_sample's evaluator, then r_p, v_p, q_p, w_p, F, tau_p and the time
+// stamp into the row's place of an LDS tile: all trigonometry of the plan is here, in parallel; (B) behind a barrier lane 0
+// runs the chain over the tile's rows from the state it carries in registers: per row the state at the tick's start, |e|, the
+// tilt, |F_fb| and the status bits go into the row's place, then the tick's substeps are taken (translation first, the rotation
+// reads its e) -- only +, -, x, / and sqrt; (C) behind a barrier a lane turns its row's state into the 20 output columns (R from
+// the quaternion, the Euler extraction of track_pose, R w_b) in the row's own place, and behind one more barrier the tile goes
+// out flat, consecutive lanes on consecutive doubles: `rows` with its pitch of 20, `meas` with its 18 or 19 columns, the joint
+// columns copied from the joint ring's row or left alone (k_stitch's addressing: table or ring, cursor and t0 only read).
+// Carried state, count and word are read in front of the first barrier and written once by lane 0 behind the last tile; a
+// window without rows keeps them (QTOS_ROLLOUT_PENDING in its word with them, until a call gives it rows).  The two chains are NOT split over two lanes or pipelined over tiles: the freeze (a fallen
+// body stops both) couples them row by row, and the one-lane form was not measured against a split one.  No atomics, no
+// scratch (the state and the body's constants are scalars and structs read with constant indices), no sincos.
+struct RolloutArgs {   // QtosRollout as the kernel reads it (window_api.hpp rollout_args)
+  double hz, h, mass, gravity, ff_scale, f_fb_max, t_fb_max, dev_max, tilt_max;
+  double Ib[9], Ii[9], kp_lin[3], kd_lin[3], kp_ang[3], kd_ang[3];
+  long long capacity, push_from, push_ticks;
+  int first_row, n_rows, substeps, flags;
+};
+constexpr int ROLLOUT_COLS = 20;
+constexpr int ROLLOUT_PITCH = 37;   // doubles per row of the tile: 20 inputs / outputs, 13 of the state, |e|, tilt, |F_fb|, status
+constexpr int ROLLOUT_TILE = 256;   // rows per tile = lanes per workgroup: 256 x 37 x 8 = 75 776 bytes of LDS
+constexpr int ROLLOUT_TICK = 64;    // one wave where no window has more rows (the tick): 18 944 bytes
+struct RolloutState { double r0, r1, r2, v0, v1, v2, qx, qy, qz, qw, w0, w1, w2; };
+struct RolloutBody { double m_s, I[9], J[9], F0, F1, F2, T0, T1, T2; };   // mass, inertia and its inverse scaled; the push
+
+// A plan row c (37 columns) into the tile's 20 input columns (rollout.plan_inputs).
+__device__ inline void rollout_inputs(const double *c, double ff, double *d) {
+#pragma clang fp contract(off)
+  d[0] = c[0]; d[1] = c[1]; d[2] = c[2]; d[3] = c[3]; d[4] = c[19]; d[5] = c[20]; d[6] = c[21];
+  const double hr = c[4] * 0.5, hp = c[5] * 0.5, hy = c[6] * 0.5;
+  const double sr = sin(hr), cr = cos(hr), sp = sin(hp), cp = cos(hp), sy = sin(hy), cy = cos(hy);
+  d[7] = sr * cp * cy - cr * sp * sy; d[8] = cr * sp * cy + sr * cp * sy;
+  d[9] = cr * cp * sy - sr * sp * cy; d[10] = cr * cp * cy + sr * sp * sy;
+  const double sb = sin(c[5]), cb = cos(c[5]), sc = sin(c[6]), cc = cos(c[6]);
+  d[11] = cb * cc * c[22] - sc * c[23]; d[12] = cb * sc * c[22] + cc * c[23]; d[13] = c[24] - sb * c[22];
+  double F0 = 0, F1 = 0, F2 = 0, T0 = 0, T1 = 0, T2 = 0;
+#pragma unroll
+  for (int e = 0; e < NEE; ++e) {
+    const double f0 = c[25 + 3 * e], f1 = c[26 + 3 * e], f2 = c[27 + 3 * e];
+    const double d0 = c[7 + 3 * e] - c[1], d1 = c[8 + 3 * e] - c[2], d2 = c[9 + 3 * e] - c[3];
+    const double x0 = d1 * f2 - d2 * f1, x1 = d2 * f0 - d0 * f2, x2 = d0 * f1 - d1 * f0;
+    if (e == 0) { F0 = f0; F1 = f1; F2 = f2; T0 = x0; T1 = x1; T2 = x2; }
+    else { F0 = F0 + f0; F1 = F1 + f1; F2 = F2 + f2; T0 = T0 + x0; T1 = T1 + x1; T2 = T2 + x2; }
+  }
+  d[14] = ff * F0; d[15] = ff * F1; d[16] = ff * F2; d[17] = ff * T0; d[18] = ff * T1; d[19] = ff * T2;
+}
+
+// sqrt((a a + b b) + c c)
+__device__ inline double rollout_norm(double a, double b, double c) {
+#pragma clang fp contract(off)
+  return sqrt((a * a + b * b) + c * c);
+}
+
+// q_e = q_p (x) conj(q), negated if its w < 0 (rollout.attitude_error); p: the row's place in the tile.
+__device__ inline void rollout_attitude(const double *p, const RolloutState &s, double &ex, double &ey, double &ez, double &ew) {
+#pragma clang fp contract(off)
+  const double px = p[7], py = p[8], pz = p[9], pw = p[10];
+  const double x = -s.qx, y = -s.qy, z = -s.qz, w = s.qw;
+  ex = ((pw * x + px * w) + py * z) - pz * y;
+  ey = ((pw * y - px * z) + py * w) + pz * x;
+  ez = ((pw * z + px * y) - py * x) + pz * w;
+  ew = ((pw * w - px * x) - py * y) - pz * z;
+  if (ew < 0) { ex = -ex; ey = -ey; ez = -ez; ew = -ew; }
+}
+
+__device__ inline double rollout_clip(double v, double lim, bool &acted) {   // a NaN stays a NaN
+  if (lim > 0) {
+    if (v < -lim) { acted = true; return -lim; }
+    if (v > lim) { acted = true; return lim; }
+  }
+  return v;
+}
+
+// One step of length A.h under the row p (rollout.step, its lines 1 .. 11); returns |F_fb|.
+__device__ inline double rollout_step(const RolloutArgs &A, const RolloutBody &M, const double *p, bool push, RolloutState &s,
+                                      bool &clipped) {
+#pragma clang fp contract(off)
+  const double h = A.h;
+  const double e0 = s.r0 - p[1], e1 = s.r1 - p[2], e2 = s.r2 - p[3];
+  const double b0 = rollout_clip(-(A.kp_lin[0] * e0) - A.kd_lin[0] * (s.v0 - p[4]), A.f_fb_max, clipped);
+  const double b1 = rollout_clip(-(A.kp_lin[1] * e1) - A.kd_lin[1] * (s.v1 - p[5]), A.f_fb_max, clipped);
+  const double b2 = rollout_clip(-(A.kp_lin[2] * e2) - A.kd_lin[2] * (s.v2 - p[6]), A.f_fb_max, clipped);
+  const double F0 = p[14], F1 = p[15], F2 = p[16];
+  const double P0 = push ? M.F0 : 0.0, P1 = push ? M.F1 : 0.0, P2 = push ? M.F2 : 0.0;
+  const double Q0 = push ? M.T0 : 0.0, Q1 = push ? M.T1 : 0.0, Q2 = push ? M.T2 : 0.0;
+  const double a0 = ((F0 + b0) + P0) / M.m_s, a1 = ((F1 + b1) + P1) / M.m_s, a2 = ((F2 + b2) + P2) / M.m_s - A.gravity;
+  const double x = s.qx, y = s.qy, z = s.qz, w = s.qw;
+  const double R0 = 1 - 2 * (y * y + z * z), R1 = 2 * (x * y - z * w), R2 = 2 * (x * z + y * w);
+  const double R3 = 2 * (x * y + z * w), R4 = 1 - 2 * (x * x + z * z), R5 = 2 * (y * z - x * w);
+  const double R6 = 2 * (x * z - y * w), R7 = 2 * (y * z + x * w), R8 = 1 - 2 * (x * x + y * y);
+  double qx, qy, qz, qw;
+  rollout_attitude(p, s, qx, qy, qz, qw);
+  const double g0 = 2 * qx, g1 = 2 * qy, g2 = 2 * qz;
+  const double u0 = (R0 * s.w0 + R1 * s.w1) + R2 * s.w2, u1 = (R3 * s.w0 + R4 * s.w1) + R5 * s.w2,
+               u2 = (R6 * s.w0 + R7 * s.w1) + R8 * s.w2;
+  const double c0 = rollout_clip(A.kp_ang[0] * g0 + A.kd_ang[0] * (p[11] - u0), A.t_fb_max, clipped);
+  const double c1 = rollout_clip(A.kp_ang[1] * g1 + A.kd_ang[1] * (p[12] - u1), A.t_fb_max, clipped);
+  const double c2 = rollout_clip(A.kp_ang[2] * g2 + A.kd_ang[2] * (p[13] - u2), A.t_fb_max, clipped);
+  const double x0 = e1 * F2 - e2 * F1, x1 = e2 * F0 - e0 * F2, x2 = e0 * F1 - e1 * F0;
+  const double t0 = ((p[17] - x0) + c0) + Q0, t1 = ((p[18] - x1) + c1) + Q1, t2 = ((p[19] - x2) + c2) + Q2;
+  s.v0 = s.v0 + h * a0; s.r0 = s.r0 + h * s.v0;
+  s.v1 = s.v1 + h * a1; s.r1 = s.r1 + h * s.v1;
+  s.v2 = s.v2 + h * a2; s.r2 = s.r2 + h * s.v2;
+  const double tb0 = (R0 * t0 + R3 * t1) + R6 * t2, tb1 = (R1 * t0 + R4 * t1) + R7 * t2, tb2 = (R2 * t0 + R5 * t1) + R8 * t2;
+  const double i0 = (M.I[0] * s.w0 + M.I[1] * s.w1) + M.I[2] * s.w2, i1 = (M.I[3] * s.w0 + M.I[4] * s.w1) + M.I[5] * s.w2,
+               i2 = (M.I[6] * s.w0 + M.I[7] * s.w1) + M.I[8] * s.w2;
+  const double n0 = tb0 - (s.w1 * i2 - s.w2 * i1), n1 = tb1 - (s.w2 * i0 - s.w0 * i2), n2 = tb2 - (s.w0 * i1 - s.w1 * i0);
+  const double w0 = s.w0 + h * ((M.J[0] * n0 + M.J[1] * n1) + M.J[2] * n2);
+  const double w1 = s.w1 + h * ((M.J[3] * n0 + M.J[4] * n1) + M.J[5] * n2);
+  const double w2 = s.w2 + h * ((M.J[6] * n0 + M.J[7] * n1) + M.J[8] * n2);
+  const double hh = h * 0.5;
+  const double d0 = (w * w0 + y * w2) - z * w1, d1 = (w * w1 - x * w2) + z * w0, d2 = (w * w2 + x * w1) - y * w0,
+               d3 = (-(x * w0) - y * w1) - z * w2;
+  const double m0 = x + hh * d0, m1 = y + hh * d1, m2 = z + hh * d2, m3 = w + hh * d3;
+  const double nn = sqrt(((m0 * m0 + m1 * m1) + m2 * m2) + m3 * m3);
+  s.qx = m0 / nn; s.qy = m1 / nn; s.qz = m2 / nn; s.qw = m3 / nn;
+  s.w0 = w0; s.w1 = w1; s.w2 = w2;
+  return rollout_norm(b0, b1, b2);
+}
+
+// (C) of a row: the state in t[20 .. 32] becomes the output columns 1 .. 16 in t (17 .. 19 move up from 33 .. 35); returns the
+// GIMBAL bit.  The Euler extraction is track_pose's, with comparisons for the clip so that a NaN stays one.
+__device__ inline int rollout_output(double *t) {
+#pragma clang fp contract(off)
+  const double r0 = t[20], r1 = t[21], r2 = t[22], v0 = t[23], v1 = t[24], v2 = t[25];
+  const double x = t[26], y = t[27], z = t[28], w = t[29], w0 = t[30], w1 = t[31], w2 = t[32];
+  const double R0 = 1 - 2 * (y * y + z * z), R1 = 2 * (x * y - z * w), R2 = 2 * (x * z + y * w);
+  const double R3 = 2 * (x * y + z * w), R4 = 1 - 2 * (x * x + z * z), R5 = 2 * (y * z - x * w);
+  const double R6 = 2 * (x * z - y * w), R7 = 2 * (y * z + x * w), R8 = 1 - 2 * (x * x + y * y);
+  double sp = -R6;
+  sp = sp < -1.0 ? -1.0 : (sp > 1.0 ? 1.0 : sp);
+  t[1] = r0; t[2] = r1; t[3] = r2;
+  t[4] = atan2(R7, R8); t[5] = asin(sp); t[6] = atan2(R3, R0);
+  t[7] = v0; t[8] = v1; t[9] = v2;
+  t[10] = (R0 * w0 + R1 * w1) + R2 * w2; t[11] = (R3 * w0 + R4 * w1) + R5 * w2; t[12] = (R6 * w0 + R7 * w1) + R8 * w2;
+  t[13] = x; t[14] = y; t[15] = z; t[16] = w;
+  t[17] = t[33]; t[18] = t[34]; t[19] = t[35];
+  return fabs(R6) >= 1 ? 4 : 0;
+}
+
+template <int TILE>
+__global__ __launch_bounds__(TILE) void k_rollout(const SamplePlan *Sd, RolloutArgs A, const double *nodes, const double *t0,
+                                                  const int *first_row, const int *n_rows, const long long *cursor,
+                                                  const double *joint, const double *mass_scale, const double *push, double *state,
+                                                  long long *count, int *word_io, double *meas, double *rows_out, int *status_out,
+                                                  int B) {
+  __shared__ double roll_tile[TILE * ROLLOUT_PITCH];
+  const int b = blockIdx.x;
+  if (b >= B) return;
+  const SamplePlan &S = *Sd;
+  const long long rows_b = A.capacity > 0 ? A.capacity : (long long)A.n_rows;      // rows of window b's table or ring
+  long long n = n_rows ? n_rows[b] : A.n_rows;
+  n = n < 0 ? 0 : (n > rows_b ? rows_b : n);
+  if (n == 0) return;                                                              // (uniform: a window without rows keeps its state)
+  const bool quat = (A.flags & 2) != 0;
+  const int mcols = quat ? 19 : 18;
+  RolloutState s;                                                                  // (every lane, in front of the first barrier)
+  {
+    const double *sb = state + (size_t)b * 13;
+    s.r0 = sb[0]; s.r1 = sb[1]; s.r2 = sb[2]; s.v0 = sb[3]; s.v1 = sb[4]; s.v2 = sb[5];
+    s.qx = sb[6]; s.qy = sb[7]; s.qz = sb[8]; s.qw = sb[9]; s.w0 = sb[10]; s.w1 = sb[11]; s.w2 = sb[12];
+  }
+  const long long calls = count[b];
+  int word = word_io[b];
+  RolloutBody M;
+  {
+#pragma clang fp contract(off)
+    const double ms = mass_scale ? mass_scale[b] : 1.0;
+    M.m_s = A.mass * ms;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) { M.I[i] = ms * A.Ib[i]; M.J[i] = A.Ii[i] / ms; }
+    const double *pb = push ? push + (size_t)b * 6 : nullptr;
+    M.F0 = pb ? pb[0] : 0.0; M.F1 = pb ? pb[1] : 0.0; M.F2 = pb ? pb[2] : 0.0;
+    M.T0 = pb ? pb[3] : 0.0; M.T1 = pb ? pb[4] : 0.0; M.T2 = pb ? pb[5] : 0.0;
+  }
+  long long pos = 0;                                                               // table or ring row of the segment's first row
+  if (A.capacity > 0) {
+    pos = cursor[b] % A.capacity;
+    if (pos < 0) pos += A.capacity;
+  }
+  const double *x = nodes + (size_t)b * S.n_vars;
+  long long first = first_row ? first_row[b] : A.first_row;
+  first = first < 0 ? 0 : first;
+  const double t0b = t0[b];
+  double *meas_b = meas + (size_t)b * (size_t)rows_b * mcols;
+  double *out_b = rows_out ? rows_out + (size_t)b * (size_t)rows_b * ROLLOUT_COLS : nullptr;
+  const double *joint_b = joint ? joint + (size_t)b * (size_t)rows_b * QTOS_CSV_COLS : nullptr;
+  for (long long j0 = 0; j0 < n; j0 += TILE) {                                     // (n is uniform over the workgroup: so are the barriers)
+    const int m = n - j0 < TILE ? (int)(n - j0) : TILE;
+    long long base = pos + j0;                                                     // (pos < rows_b and j0 < n <= rows_b: one subtraction wraps it)
+    if (base >= rows_b) base -= rows_b;
+    if ((int)threadIdx.x < m) {                                                    // (A) a lane takes a row of the plan
+      const long long k = first + j0 + threadIdx.x;
+      double row[QTOS_CSV_COLS];
+      const double t = sample_row_state_at(S, x, t0b, k > INT_MAX ? INT_MAX : (int)k, A.hz, row);
+      for (int e = 0; e < NEE; ++e) sample_spline(S.eef[e], x, t, 0, row + 25 + 3 * e);
+      rollout_inputs(row, A.ff_scale, roll_tile + threadIdx.x * ROLLOUT_PITCH);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {                                                        // (B) the chain, in program order
+#pragma clang fp contract(off)
+      // QTOS_ROLLOUT_INIT, or QTOS_ROLLOUT_PENDING in the window's own word (spent here, by the first call that gives the window
+      // rows): r_p, v_p, q_p, R(q_p)^T w_p of the first row
+      if (j0 == 0 && ((A.flags & 1) || (word & 32))) {
+        word &= ~32;
+        const double *p = roll_tile;
+        s.r0 = p[1]; s.r1 = p[2]; s.r2 = p[3]; s.v0 = p[4]; s.v1 = p[5]; s.v2 = p[6];
+        s.qx = p[7]; s.qy = p[8]; s.qz = p[9]; s.qw = p[10];
+        const double qx = s.qx, qy = s.qy, qz = s.qz, qw = s.qw;
+        const double R0 = 1 - 2 * (qy * qy + qz * qz), R1 = 2 * (qx * qy - qz * qw), R2 = 2 * (qx * qz + qy * qw);
+        const double R3 = 2 * (qx * qy + qz * qw), R4 = 1 - 2 * (qx * qx + qz * qz), R5 = 2 * (qy * qz - qx * qw);
+        const double R6 = 2 * (qx * qz - qy * qw), R7 = 2 * (qy * qz + qx * qw), R8 = 1 - 2 * (qx * qx + qy * qy);
+        s.w0 = (R0 * p[11] + R3 * p[12]) + R6 * p[13];
+        s.w1 = (R1 * p[11] + R4 * p[12]) + R7 * p[13];
+        s.w2 = (R2 * p[11] + R5 * p[12]) + R8 * p[13];
+      }
+      for (int i = 0; i < m; ++i) {
+        double *p = roll_tile + i * ROLLOUT_PITCH;
+        double ex, ey, ez, ew;
+        rollout_attitude(p, s, ex, ey, ez, ew);
+        const double en = rollout_norm(s.r0 - p[1], s.r1 - p[2], s.r2 - p[3]);
+        const double tilt = 2 * rollout_norm(ex, ey, ez);
+        const bool finite = isfinite(s.r0) && isfinite(s.r1) && isfinite(s.r2) && isfinite(s.v0) && isfinite(s.v1) && isfinite(s.v2) &&
+                            isfinite(s.qx) && isfinite(s.qy) && isfinite(s.qz) && isfinite(s.qw) && isfinite(s.w0) && isfinite(s.w1) &&
+                            isfinite(s.w2);
+        if (!finite) word |= 2;
+        if ((A.dev_max > 0 && en > A.dev_max) || (A.tilt_max > 0 && tilt > A.tilt_max)) word |= 1;
+        int st = word & 3;
+        p[20] = s.r0; p[21] = s.r1; p[22] = s.r2; p[23] = s.v0; p[24] = s.v1; p[25] = s.v2;
+        p[26] = s.qx; p[27] = s.qy; p[28] = s.qz; p[29] = s.qw; p[30] = s.w0; p[31] = s.w1; p[32] = s.w2;
+        p[33] = en; p[34] = tilt;
+        double fbn = 0;
+        if (!st) {
+          const long long c = calls + j0 + i;
+          const bool acts = push != nullptr && c >= A.push_from && c - A.push_from < A.push_ticks;
+          bool clipped = false;
+          for (int u = 0; u < A.substeps; ++u) {
+            const double f = rollout_step(A, M, p, acts, s, clipped);
+            if (u == 0) fbn = f;
+          }
+          st = (clipped ? 8 : 0) | (acts ? 16 : 0);
+        }
+        p[35] = fbn; p[36] = (double)st;
+      }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < m) {                                                    // (C) a lane turns its row's state into the output columns
+      double *p = roll_tile + threadIdx.x * ROLLOUT_PITCH;
+      const int st = (int)p[36] | rollout_output(p);
+      long long o = base + threadIdx.x;
+      if (o >= rows_b) o -= rows_b;
+      status_out[(size_t)b * (size_t)rows_b + o] = st;
+    }
+    __syncthreads();
+    if (out_b) {                                                                   // the tile goes out flat: rows ...
+      const long long all = rows_b * ROLLOUT_COLS, at = base * ROLLOUT_COLS;
+      for (int e = threadIdx.x; e < m * ROLLOUT_COLS; e += TILE) {
+        const int i = e / ROLLOUT_COLS, c = e - i * ROLLOUT_COLS;
+        long long o = at + e;                                                      // (m <= rows_b: o < 2 all)
+        if (o >= all) o -= all;
+        out_b[o] = roll_tile[i * ROLLOUT_PITCH + c];
+      }
+    }
+    {                                                                              // ... and meas
+      const long long all = rows_b * mcols, at = base * mcols;
+      for (int e = threadIdx.x; e < m * mcols; e += TILE) {
+        const int i = e / mcols, c = e - i * mcols;
+        const double *p = roll_tile + i * ROLLOUT_PITCH;
+        long long o = at + e;
+        if (o >= all) o -= all;
+        if (c < 3) meas_b[o] = p[1 + c];
+        else if (c < mcols - 12) meas_b[o] = quat ? p[13 + (c - 3)] : p[4 + (c - 3)];
+        else if (joint_b) {
+          long long ro = base + i;
+          if (ro >= rows_b) ro -= rows_b;
+          meas_b[o] = joint_b[(size_t)ro * QTOS_CSV_COLS + 1 + (c - (mcols - 12))];
+        }
+      }
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    double *sb = state + (size_t)b * 13;
+    sb[0] = s.r0; sb[1] = s.r1; sb[2] = s.r2; sb[3] = s.v0; sb[4] = s.v1; sb[5] = s.v2;
+    sb[6] = s.qx; sb[7] = s.qy; sb[8] = s.qz; sb[9] = s.qw; sb[10] = s.w0; sb[11] = s.w1; sb[12] = s.w2;
+    count[b] = calls + n;
+    word_io[b] = word;
   }
 }
 

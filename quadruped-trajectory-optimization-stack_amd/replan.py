@@ -216,6 +216,21 @@ class ShiftedWindows:
                latency, snap, zero_filter, rom_tol, snap_tol, nominal, max_deviation, cfg; the leg and the quaternion flag are the
                track's).  The order of a replan is then hand-over, joint rows, track (whose ``fill`` writes the measurements of the
                segment), feedback, path goal (so that ``path_base="state"`` sees the corrected start), stitch.
+    rollout    None (the default): nothing is queued and nothing is allocated, and ``meas_traj`` is the caller's to fill.  A dict
+               (needs ``track``, whose ``meas_traj`` it fills): the windows' robots are simulated rigid bodies (k_rollout through
+               qtos_rollout_device, the rule: ``rollout.rollout_rows``), queued behind the joint rows and in front of the track
+               call, and in ``finish()``, over exactly the rows the stitch appends and with its cursor.  A window's first call
+               with rows sets its body on its plan (QTOS_ROLLOUT_PENDING in its word, spent per window, as QTOS_ROLLOUT_INIT sets
+               it); every later one goes on from the carried state, so the body does
+               not jump when the plan under it changes.  ``self.rollout_state`` (B x 13), ``self.rollout_count`` and
+               ``self.rollout_word`` (B) and the rows' status words ``self.rollout_status`` (B x trajectory) live on the device.
+               The dict's entries are ``capi.rollout_params``' keywords (substeps, ff_scale, the gains and limits, dev_max,
+               tilt_max, push_from, push_ticks, mass, gravity, inertia_b, cfg; the quaternion flag is the track's),
+               ``mass_scale`` (a number or one per window), ``push`` (B x 6) and ``rows=True`` to keep ``self.rollout_traj`` (B x
+               trajectory x 20); ``rollout_rows(b)`` reads a window's ring.  With ``joints`` on the measured joint angles are the
+               commanded ones; without, those twelve columns of ``meas_traj`` are not touched.  A ``fill`` callable of ``track``
+               still runs, behind the rollout: the place to add sensor noise.  The planner's reference-compat inertia tensor is
+               indefinite: with gains, give ``inertia_b=config.INERTIA_PHYSICAL``.
     check      None (the default): nothing is queued and nothing is allocated.  A ``capi.check_params(...)`` (needs
                ``trajectory``; its tol is read, its rate and rows are the stitch's): k_plan_check (qtos_plan_check_device, the
                rule: ``plan_check.check_rows`` / ``summarise`` / ``accumulate``) is queued in front of every stitch and in
@@ -225,7 +240,7 @@ class ShiftedWindows:
 
     def __init__(self, planner, start, goal_step, map_id=None, advance=2.5, search=0.4, stream=None, warm="none", x_range=None,
                  handover=None, contact="force", height_set=(0.0,), trajectory=None, stitch="clean", path=None, path_base="spine",
-                 path_hold=True, joints=None, track=None, feedback=None, check=None):
+                 path_hold=True, joints=None, track=None, feedback=None, check=None, rollout=None):
         import torch
         self.torch = torch
         self.P = planner
@@ -313,6 +328,25 @@ class ShiftedWindows:
             self.track_goal_x = None
             if goal_x is not None:
                 self.track_goal_x = torch.as_tensor(np.broadcast_to(np.asarray(goal_x, np.float64), (B,)).copy(), **f64)
+        self._rollout = None
+        if rollout is not None:
+            from . import capi
+            if self.track_traj is None:
+                raise ValueError("rollout needs the measured ring of track (track=dict(...)), which it fills")
+            if not hasattr(planner.lib, "qtos_rollout_device"):
+                raise RuntimeError("this build of the planner library has no rollout kernel (qtos_rollout_device)")
+            kw = dict(rollout)
+            scale, push, keep = kw.pop("mass_scale", None), kw.pop("push", None), kw.pop("rows", False)
+            kw.setdefault("cfg", getattr(planner, "cfg", None))
+            self._rollout = capi.rollout_params(hz=self.hz, first_row=int(self._stitch.first_row), capacity=int(trajectory),
+                                                quaternion=bool(self._track.flags & capi.TRACK_QUAT), **kw)
+            self.rollout_state = torch.zeros((B, capi.ROLLOUT_STATE), **f64)
+            self.rollout_count = torch.zeros((B,), dtype=torch.int64, device=dev)
+            self.rollout_word = torch.full((B,), capi.ROLLOUT_PENDING, dtype=torch.int32, device=dev)
+            self.rollout_status = torch.zeros((B, int(trajectory)), dtype=torch.int32, device=dev)
+            self.rollout_traj = torch.zeros((B, int(trajectory), capi.ROLLOUT_COLS), **f64) if keep else None
+            up = lambda a, shape: None if a is None else torch.as_tensor(np.broadcast_to(np.asarray(a, np.float64), shape).copy(), **f64)
+            self._rollout_scale, self._rollout_push = up(scale, (B,)), up(push, (B, 6))
         self._feedback = None
         if feedback is not None:
             from . import capi
@@ -525,6 +559,31 @@ class ShiftedWindows:
                                                 self.track_count.data_ptr(), self.track_total.data_ptr(), self.track_traj.data_ptr(),
                                                 self.track_status.data_ptr(), sp), "qtos_track_device")
 
+    def _rollout_rows(self, params, n_rows, sp):
+        """Queue k_rollout in front of a stitch, behind the joint rows and in front of the track call: the bodies go on from the
+        state they carry over the rows that stitch appends, under the plan handed over from, and their states fill the measured
+        ring's rows of the segment (the joint columns from the joint ring where ``joints`` is on).  A window's first call with
+        rows sets its state from the plan's row: ``rollout_word`` starts as QTOS_ROLLOUT_PENDING, which the kernel spends per
+        window, so a window whose hand-over row is 0 at the set's first replan is set on its plan by a later one."""
+        import ctypes as C
+        ptr = lambda t: None if t is None else t.data_ptr()
+        self._call(self.P.lib.qtos_rollout_device(self.P.h, self.B, C.byref(params), self.nodes.data_ptr(), self.t0.data_ptr(), None, n_rows,
+                                                  self.cursor.data_ptr(), ptr(self.joint_traj), ptr(self._rollout_scale),
+                                                  ptr(self._rollout_push), self.rollout_state.data_ptr(), self.rollout_count.data_ptr(),
+                                                  self.rollout_word.data_ptr(), self.meas_traj.data_ptr(), ptr(self.rollout_traj),
+                                                  self.rollout_status.data_ptr(), sp), "qtos_rollout_device")
+
+    def rollout_rows(self, b):
+        """Window b's newest min(cursor, trajectory) rollout rows in time order (None without ``rows=True``) and their status
+        words, as numpy (the stream is synchronised): row for row the simulated states of ``trajectory_rows(b)``."""
+        from .stitcher import ring_rows
+        if self._rollout is None:
+            raise RuntimeError("rollout_rows() needs the rollout (rollout=dict(...))")
+        self.stream.synchronize()
+        cur = int(self.cursor[b].item())
+        rows = None if self.rollout_traj is None else ring_rows(self.rollout_traj[b].cpu().numpy(), cur)
+        return rows, ring_rows(self.rollout_status[b].cpu().numpy(), cur)
+
     def _start_feedback(self, sp):
         """Queue k_start_feedback behind the track call and in front of the stitch: self.start (and, without a path, self.goal)
         from the measured ring's row of the hand-over (the kernel reads the cursor and the clock the stitch behind it moves on)."""
@@ -611,6 +670,10 @@ class ShiftedWindows:
                 g = self._joint.copy()
                 g.first_row, g.n_rows = first, n
                 self._joint_rows(g, None, C.c_void_p(self.stream.cuda_stream))
+            if self._rollout is not None:
+                g = self._rollout.copy()
+                g.first_row, g.n_rows = first, n
+                self._rollout_rows(g, None, C.c_void_p(self.stream.cuda_stream))
             if self.track_traj is not None:
                 g = self._track.copy()
                 g.first_row, g.n_rows = first, n
@@ -684,6 +747,8 @@ class ShiftedWindows:
                 # the rows executed of the plan handed over from go to the windows' rings; t0 moves on to the new plan's row 0
                 if self.joint_traj is not None:
                     self._joint_rows(self._joint, self.row.data_ptr(), sp)
+                if self._rollout is not None:
+                    self._rollout_rows(self._rollout, self.row.data_ptr(), sp)
                 if self.track_traj is not None:
                     self._track_rows(self._track, self.row.data_ptr(), sp)
                 if self._feedback is not None:
