@@ -657,6 +657,22 @@ def _i32(a, B):
     return None if a is None else np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.int32), (B,)))
 
 
+def _rows(params):
+    """The rows per window of a window kernel's tables (params.n_rows) or rings (params.capacity)."""
+    return int(params.capacity) if params.capacity > 0 else int(params.n_rows)
+
+
+def _segment(params, B, cursor, *rings):
+    """(rows, cursor) of a window kernel's host form: _rows, and the rings' cursor as B contiguous int64 (table mode: None).
+    `rings`: what ring mode needs besides."""
+    if params.capacity <= 0:
+        return _rows(params), None
+    if cursor is None or any(r is None for r in rings):
+        raise ValueError("ring mode takes the rings as they stand: out, status and cursor" if rings else
+                         "ring mode takes the ring's cursor")
+    return _rows(params), np.ascontiguousarray(np.broadcast_to(np.asarray(cursor, np.int64), (B,)))
+
+
 def params_from_config(cfg):
     p = QtosParams()
     for e in range(NEE):
@@ -1068,12 +1084,7 @@ class Planner:
             params = joint_params(n_rows=int(round(self.dims.duration * 1000.0)) + 1)
         f12 = lambda a: None if a is None else np.ascontiguousarray(a, np.float64).reshape(B, 12)
         first, per, qm, qdm = _i32(first_row, B), _i32(n_rows, B), f12(q_mes), f12(qd_mes)
-        rows = int(params.capacity) if params.capacity > 0 else int(params.n_rows)
-        cur = None
-        if params.capacity > 0:
-            if out is None or status is None or cursor is None:
-                raise ValueError("ring mode takes the rings as they stand: out, status and cursor")
-            cur = np.ascontiguousarray(np.broadcast_to(np.asarray(cursor, np.int64), (B,)))
+        rows, cur = _segment(params, B, cursor, out, status)
         out = np.zeros((B, max(rows, 0), CSV_COLS)) if out is None else np.array(out, np.float64)
         status = np.zeros((B, max(rows, 0)), np.int32) if status is None else np.array(status, np.int32)
         if out.shape != (B, rows, CSV_COLS) or status.shape != (B, rows):
@@ -1101,16 +1112,12 @@ class Planner:
         B = nodes.shape[0]
         t0 = np.ascontiguousarray(np.broadcast_to(np.asarray(t0, np.float64), (B,)))
         first, per = _i32(first_row, B), _i32(n_rows, B)
-        rows = int(params.capacity) if params.capacity > 0 else int(params.n_rows)
+        rows = _rows(params)
         mcols = 19 if params.flags & TRACK_QUAT else 18
         meas = np.ascontiguousarray(meas, np.float64)
         if meas.shape != (B, max(rows, 0), mcols):
             raise ValueError("meas is (B, %d, %d)" % (rows, mcols))
-        cur = None
-        if params.capacity > 0:
-            if out is None or status is None or cursor is None:
-                raise ValueError("ring mode takes the rings as they stand: out, status and cursor")
-            cur = np.ascontiguousarray(np.broadcast_to(np.asarray(cursor, np.int64), (B,)))
+        cur = _segment(params, B, cursor, out, status)[1]
         goal = None if goal_x is None else np.ascontiguousarray(np.broadcast_to(np.asarray(goal_x, np.float64), (B,)))
         count = np.zeros((B, 2), np.int64) if count is None else np.array(count, np.int64).reshape(B, 2)
         total = np.zeros((B, 2)) if total is None else np.array(total, np.float64).reshape(B, 2)
@@ -1142,13 +1149,9 @@ class Planner:
         B = nodes.shape[0]
         t0 = np.ascontiguousarray(np.broadcast_to(np.asarray(t0, np.float64), (B,)))
         first, per = _i32(first_row, B), _i32(n_rows, B)
-        nr = max(int(params.capacity) if params.capacity > 0 else int(params.n_rows), 0)
+        nr, cur = _segment(params, B, cursor)
+        nr = max(nr, 0)                                    # (a negative n_rows: the library refuses it)
         mcols = 19 if params.flags & ROLLOUT_QUAT else 18
-        cur = None
-        if params.capacity > 0:
-            if cursor is None:
-                raise ValueError("ring mode takes the ring's cursor")
-            cur = np.ascontiguousarray(np.broadcast_to(np.asarray(cursor, np.int64), (B,)))
         joint = None if joint is None else np.ascontiguousarray(joint, np.float64)
         if joint is not None and joint.shape != (B, nr, CSV_COLS):
             raise ValueError("joint is (B, %d, %d)" % (nr, CSV_COLS))
@@ -1190,16 +1193,12 @@ class Planner:
         B = nodes.shape[0]
         t0 = np.ascontiguousarray(np.broadcast_to(np.asarray(t0, np.float64), (B,)))
         row, mid = _i32(row, B), _i32(map_id, B)
-        rows = int(params.capacity) if params.capacity > 0 else int(params.n_rows)
+        rows = _rows(params)
         mcols = 19 if params.flags & FEEDBACK_QUAT else 18
         meas = np.ascontiguousarray(meas, np.float64)
         if meas.shape != (B, max(rows, 0), mcols):
             raise ValueError("meas is (B, %d, %d)" % (rows, mcols))
-        cur = None
-        if params.capacity > 0:
-            if cursor is None:
-                raise ValueError("ring mode takes the ring's cursor")
-            cur = np.ascontiguousarray(np.broadcast_to(np.asarray(cursor, np.int64), (B,)))
+        cur = _segment(params, B, cursor)[1]
         if (goal_step is None) != (goal is None):
             raise ValueError("goal_step and goal go together: give both or neither")
         gs = None if goal_step is None else np.ascontiguousarray(goal_step, np.float64).reshape(B, 3)

@@ -175,7 +175,7 @@ int qtos_handover(QtosPlanner *p, int B, const QtosHandover *h, const double *no
 static int stitch_args(const QtosPlanner *p, int B, const QtosStitch *s, const void *nodes, const void *n_rows, const void *t0,
                        const void *traj, const void *cursor, StitchArgs *A) {
   if (!p || B < 1 || !s || !nodes || !t0 || !traj || !cursor) return -1;
-  if (s->capacity < 1 || s->first_row < 0 || s->first_row > 1000000 || (!n_rows && s->n_rows < 0)) return -1;
+  if (s->capacity < 1 || segment_check(s->capacity, s->n_rows, s->first_row, true, !n_rows)) return -1;   // (always a ring)
   A->hz = s->hz > 0 ? s->hz : 1000.0;
   A->capacity = s->capacity;
   A->first_row = s->first_row; A->n_rows = s->n_rows; A->advance_clock = s->advance_clock != 0;
@@ -201,16 +201,11 @@ int qtos_stitch(QtosPlanner *p, int B, const QtosStitch *s, const double *nodes,
   Staging S(p);
   const double *d_nodes = S.in(nodes, (size_t)B * p->M.n_vars);
   const int *d_n = S.in(n_rows, B);
-  double *d_t0 = S.inout(t0, B), *d_traj = S.inout(traj, (size_t)B * (size_t)s->capacity * QTOS_CSV_COLS);
+  double *d_t0 = S.inout(t0, B), *d_traj = S.inout(traj, segment_elems(B, A.capacity, A.n_rows) * QTOS_CSV_COLS);
   long long *d_cur = S.inout(cursor, B);
   if (S.rc) return S.rc;
   const int rc = qtos_stitch_device(p, B, s, d_nodes, d_n, d_t0, d_traj, d_cur, nullptr);
   return rc ? rc : S.download();
-}
-
-// The most rows a window of k_joint_rows or k_track can have: the count where the host knows it, else what the table or ring holds.
-static long long most_rows(int capacity, int n_rows, const int *d_n_rows) {
-  return capacity > 0 ? (d_n_rows ? capacity : std::min<long long>(n_rows, capacity)) : n_rows;
 }
 
 // ---- joint commands of the windows' plans (k_joint_rows, window_kernels.hpp) -----------------------------------
@@ -220,8 +215,7 @@ static int joint_args(const QtosPlanner *p, int B, const QtosJointRows *s, const
                       const void *status, JointArgs *A) {
   (void)first_row; (void)n_rows;
   if (!p || B < 1 || !s || !nodes || !t0 || !out || !status) return -1;
-  if (s->capacity < 0 || (s->capacity > 0 && !cursor) || s->n_rows < 0 || (s->capacity == 0 && s->n_rows < 1)) return -1;
-  if (s->first_row < 0 || s->first_row > 1000000 || (q_mes == nullptr) != (qd_mes == nullptr)) return -1;
+  if (segment_check(s->capacity, s->n_rows, s->first_row, cursor != nullptr) || (q_mes == nullptr) != (qd_mes == nullptr)) return -1;
   if (!(s->l_upper > 0) || !(s->l_lower > 0)) return -1;
   A->hz = s->hz > 0 ? s->hz : 1000.0;
   A->ee_shift = s->ee_shift; A->l_upper = s->l_upper; A->l_lower = s->l_lower; A->tau_max = s->tau_max;
@@ -239,7 +233,7 @@ int qtos_joint_rows_device(QtosPlanner *p, int B, const QtosJointRows *s, const 
                            const double *d_qd_mes, double *d_out, int *d_status, void *stream_) {
   JointArgs A;
   if (joint_args(p, B, s, d_nodes, d_t0, d_first_row, d_n_rows, d_cursor, d_q_mes, d_qd_mes, d_out, d_status, &A)) return -1;
-  const long long most = most_rows(A.capacity, A.n_rows, d_n_rows);
+  const long long most = most_rows(A.capacity, A.n_rows, d_n_rows != nullptr);
   if (most < 1) return 0;
   const int lanes = most > JOINT_TICK ? JOINT_TILE : JOINT_TICK;
   const long long tiles = (most + lanes - 1) / lanes;
@@ -260,7 +254,7 @@ int qtos_joint_rows(QtosPlanner *p, int B, const QtosJointRows *s, const double 
   JointArgs A;
   if (joint_args(p, B, s, nodes, t0, first_row, n_rows, cursor, q_mes, qd_mes, out, status, &A)) return -1;
   HIPCHK(p, hipSetDevice(p->device));
-  const size_t rows = (size_t)B * (size_t)(A.capacity > 0 ? A.capacity : A.n_rows);
+  const size_t rows = segment_elems(B, A.capacity, A.n_rows);
   Staging S(p);
   const double *d_nodes = S.in(nodes, (size_t)B * p->M.n_vars), *d_t0 = S.in(t0, B);
   double *d_out = S.inout(out, rows * QTOS_CSV_COLS);
@@ -278,8 +272,7 @@ int qtos_joint_rows(QtosPlanner *p, int B, const QtosJointRows *s, const double 
 static int track_args(const QtosPlanner *p, int B, const QtosTrack *s, const void *nodes, const void *t0, const void *cursor,
                       const void *meas, const void *count, const void *total, const void *out, const void *status, TrackArgs *A) {
   if (!p || B < 1 || !s || !nodes || !t0 || !meas || !count || !total || !out || !status) return -1;
-  if (s->capacity < 0 || (s->capacity > 0 && !cursor) || s->n_rows < 0 || (s->capacity == 0 && s->n_rows < 1)) return -1;
-  if (s->first_row < 0 || s->first_row > 1000000 || s->delay < 0) return -1;
+  if (segment_check(s->capacity, s->n_rows, s->first_row, cursor != nullptr) || s->delay < 0) return -1;
   if (!(s->l_upper > 0) || !(s->l_lower > 0)) return -1;
   A->hz = s->hz > 0 ? s->hz : 1000.0;
   A->ee_shift = s->ee_shift; A->l_upper = s->l_upper; A->l_lower = s->l_lower;
@@ -296,7 +289,7 @@ int qtos_track_device(QtosPlanner *p, int B, const QtosTrack *s, const double *d
                       double *d_total, double *d_out, int *d_status, void *stream_) {
   TrackArgs A;
   if (track_args(p, B, s, d_nodes, d_t0, d_cursor, d_meas, d_count, d_total, d_out, d_status, &A)) return -1;
-  const long long most = most_rows(A.capacity, A.n_rows, d_n_rows);
+  const long long most = most_rows(A.capacity, A.n_rows, d_n_rows != nullptr);
   if (most < 1) return 0;
   HIPCHK(p, hipSetDevice(p->device));
   if (most > TRACK_TICK)
@@ -315,7 +308,7 @@ int qtos_track(QtosPlanner *p, int B, const QtosTrack *s, const double *nodes, c
   TrackArgs A;
   if (track_args(p, B, s, nodes, t0, cursor, meas, count, total, out, status, &A)) return -1;
   HIPCHK(p, hipSetDevice(p->device));
-  const size_t rows = (size_t)B * (size_t)(A.capacity > 0 ? A.capacity : A.n_rows);
+  const size_t rows = segment_elems(B, A.capacity, A.n_rows);
   const size_t mcols = (A.flags & QTOS_TRACK_QUAT) ? 19 : 18;
   Staging S(p);
   const double *d_nodes = S.in(nodes, (size_t)B * p->M.n_vars), *d_t0 = S.in(t0, B), *d_meas = S.in(meas, rows * mcols);
@@ -337,8 +330,7 @@ static int feedback_args(const QtosPlanner *p, int B, const QtosFeedback *s, con
                          const void *cursor, const void *meas, const void *start, const void *goal_step, const void *goal,
                          const void *status, FeedbackArgs *A) {
   if (!p || B < 1 || !s || !nodes || !t0 || !row || !meas || !start || !status || (goal_step == nullptr) != (goal == nullptr)) return -1;
-  if (s->capacity < 0 || (s->capacity > 0 && !cursor) || (s->capacity == 0 && s->n_rows < 1)) return -1;
-  if (s->first_row < 0 || s->first_row > 1000000 || !(s->latency >= 0)) return -1;
+  if (segment_check(s->capacity, s->n_rows, s->first_row, cursor != nullptr, false) || !(s->latency >= 0)) return -1;   // (one row: no count)
   if (!(s->l_upper > 0) || !(s->l_lower > 0)) return -1;
   for (double g : {s->gain_pos, s->gain_ang, s->gain_foot})
     if (!(g >= 0 && g <= 1)) return -1;
@@ -383,7 +375,7 @@ int qtos_start_feedback(QtosPlanner *p, int B, const QtosFeedback *s, const doub
   FeedbackArgs A;
   if (feedback_args(p, B, s, nodes, t0, row, cursor, meas, start, goal_step, goal, status, &A)) return -1;
   HIPCHK(p, hipSetDevice(p->device));
-  const size_t rows = (size_t)B * (size_t)(A.K.capacity > 0 ? A.K.capacity : A.K.n_rows);
+  const size_t rows = segment_elems(B, A.K.capacity, A.K.n_rows);
   const size_t mcols = A.K.flags ? 19 : 18;
   Staging S(p);
   const double *d_nodes = S.in(nodes, (size_t)B * p->M.n_vars), *d_t0 = S.in(t0, B);
@@ -463,9 +455,7 @@ static int rollout_args(QtosPlanner *p, int B, const QtosRollout *s, const void 
   const char *why = nullptr;
   if (B < 1) why = "B < 1";
   else if (!s || !nodes || !t0 || !state || !count || !word || !meas || !status) why = "a required pointer is null";
-  else if (s->capacity < 0 || (s->capacity > 0 && !cursor)) why = "capacity >= 0, and a ring needs its cursor";
-  else if (s->n_rows < 0 || (s->capacity == 0 && s->n_rows < 1)) why = "n_rows >= 0, and a table has n_rows >= 1";
-  else if (s->first_row < 0 || s->first_row > 1000000) why = "first_row is 0 .. 1000000";
+  else if (const char *seg = segment_check(s->capacity, s->n_rows, s->first_row, cursor != nullptr)) why = seg;
   else if (s->substeps < 1 || s->substeps > 1000) why = "substeps is 1 .. 1000";
   else if (!(s->hz > 0) || !(s->hz <= 1e9)) why = "hz is > 0";
   else if (!(s->mass > 0) || !(s->mass <= 1.7976931348623157e308)) why = "mass is > 0";
@@ -503,7 +493,7 @@ int qtos_rollout_device(QtosPlanner *p, int B, const QtosRollout *s, const doubl
                         int *d_status, void *stream_) {
   RolloutArgs A;
   if (rollout_args(p, B, s, d_nodes, d_t0, d_cursor, d_state, d_count, d_word, d_meas, d_status, &A)) return -1;
-  const long long most = most_rows((int)std::min<long long>(A.capacity, INT_MAX), A.n_rows, d_n_rows);
+  const long long most = most_rows(A.capacity, A.n_rows, d_n_rows != nullptr);
   if (most < 1) return 0;
   HIPCHK(p, hipSetDevice(p->device));
   if (most > ROLLOUT_TICK)
@@ -522,7 +512,7 @@ int qtos_rollout(QtosPlanner *p, int B, const QtosRollout *s, const double *node
   RolloutArgs A;
   if (rollout_args(p, B, s, nodes, t0, cursor, state, count, word, meas, status, &A)) return -1;
   HIPCHK(p, hipSetDevice(p->device));
-  const size_t rows = (size_t)B * (size_t)(A.capacity > 0 ? A.capacity : A.n_rows);
+  const size_t rows = segment_elems(B, A.capacity, A.n_rows);
   const size_t mcols = (A.flags & QTOS_ROLLOUT_QUAT) ? 19 : 18;
   Staging S(p);
   const double *d_nodes = S.in(nodes, (size_t)B * p->M.n_vars), *d_t0 = S.in(t0, B);

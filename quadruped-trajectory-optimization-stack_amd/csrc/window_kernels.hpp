@@ -18,6 +18,7 @@
 // The argument checks and launches are in window_api.hpp.
 #pragma once
 #include "kernels.hpp"
+#include "row_segment.hpp"
 
 namespace qtos {
 
@@ -192,14 +193,23 @@ __global__ __launch_bounds__(512) void k_handover(const SamplePlan *Sd, Handover
 // this kernel is bound by its stores).  The LDS image keeps the rows' pitch of 37 doubles = 74 dwords: the 16 lanes of a
 // ds_write_b64 group land on banks 10 l mod 32 and the bank after each, all 32 distinct, and the flat read-back is
 // consecutive.  Element e of a tile goes to double (base * 37 + e) mod (capacity * 37) of the ring, base the ring row of
-// the tile's first row: a tile that straddles the wrap needs nothing else.  No scratch: the tables come through a pointer
-// and the row array is indexed with constants only (see k_handover).
+// the tile's first row: a tile that straddles the wrap needs nothing else.  That is RowSegment's rule (row_segment.hpp), spelled
+// out here, the ring alone: through RowSegment the 256 x 2500-row launch measured 0.3 - 1.5 % slower than these lines, with the
+// segment formed in front of the first barrier or behind it ("Row segments").  No scratch: the tables come through a
+// pointer and the row array is indexed with constants only (see k_handover).
 constexpr int STITCH_TILE = 512;   // rows per tile = lanes per workgroup: 512 x 37 x 8 = 151 552 bytes of LDS, one workgroup per CU
 struct StitchArgs {                // QtosStitch as the kernel reads it (window_api.hpp stitch_args)
   double hz;
   long long capacity;
   int first_row, n_rows, advance_clock;
 };
+
+// A tile of m rows of COLS doubles, in LDS at that pitch, goes out flat to the window's rows `dst` from row `base` on:
+// consecutive lanes on consecutive doubles, `lanes` of them.
+template <int COLS>
+__device__ inline void segment_tile_out(const RowSegment &G, long long base, int m, const double *tile, double *dst, int lanes) {
+  for (int e = threadIdx.x; e < m * COLS; e += lanes) dst[G.flat(base, COLS, e)] = tile[e];
+}
 
 __global__ __launch_bounds__(STITCH_TILE) void k_stitch(const SamplePlan *Sd, StitchArgs A, const double *nodes, const int *n_rows,
                                                         double *t0, double *traj, long long *cursor, int B) {
@@ -254,10 +264,9 @@ __global__ __launch_bounds__(STITCH_TILE) void k_stitch(const SamplePlan *Sd, St
 // with deriv = 1, then the chain for four legs, written into the row's place in an LDS tile as it is computed; the tile goes
 // out flat, consecutive lanes on consecutive doubles, as k_stitch's (whose pitch of 37 doubles it keeps).  The tile has one
 // row per lane of the workgroup: 512, or one wave where no window has more rows than that (the 1 kHz tick).
-// Two addressing modes: capacity 0, row first_row + j of window b goes to out[b][j] of a B x n_rows x 37 table; capacity > 0, to
-// ring row (cursor[b] + j) mod capacity of a B x capacity x 37 ring -- k_stitch's addressing, but cursor and t0 are only read,
-// so the grid runs over tiles and windows in both modes, and in front of k_stitch on one stream the joint ring is filled row
-// for row with the CSV ring.  The status goes out one int per lane, to the same row of a B x (n_rows | capacity) array.
+// Both addressing modes of RowSegment (row_segment.hpp): a B x n_rows x 37 table or a B x capacity x 37 ring; cursor and t0 are
+// only read, so the grid runs over tiles and windows in both modes, and in front of k_stitch on one stream the joint ring is
+// filled row for row with the CSV ring.  The status goes out one int per lane, to the same row of a B x (n_rows | capacity) array.
 // No atomics and no scratch: the tables come through a pointer (see k_handover), the arrays of the arguments are read with
 // constant indices only (joint_leg is a template over the leg), and the math library's sincos, which returns the cosine
 // through a pointer, is not used.
@@ -360,26 +369,15 @@ __global__ __launch_bounds__(TILE) void k_joint_rows(const SamplePlan *Sd, Joint
   const int b = blockIdx.y;
   if (b >= B) return;
   const SamplePlan &S = *Sd;
-  const long long rows_b = A.capacity > 0 ? A.capacity : (long long)A.n_rows;      // rows of window b's table or ring
-  long long n = n_rows ? n_rows[b] : A.n_rows;
-  n = n < 0 ? 0 : (n > rows_b ? rows_b : n);
-  const long long j0 = (long long)blockIdx.x * blockDim.x;                         // first row of this tile, of the n rows
-  if (j0 >= n) return;                                                             // (uniform over the workgroup)
-  const int m = n - j0 < (long long)blockDim.x ? (int)(n - j0) : (int)blockDim.x;
-  long long pos = 0;                                                               // table or ring row of the segment's first row
-  if (A.capacity > 0) {
-    pos = cursor[b] % A.capacity;
-    if (pos < 0) pos += A.capacity;
-  }
-  long long base = pos + j0;                                                       // (pos < rows_b and j0 < n <= rows_b: one subtraction wraps it)
-  if (base >= rows_b) base -= rows_b;
+  const RowSegment G = RowSegment::of(A.capacity, A.n_rows, A.first_row, n_rows, first_row, cursor, b);
+  const long long j0 = (long long)blockIdx.x * blockDim.x;                        // first row of this tile, of the n rows
+  if (j0 >= G.n) return;                                                           // (uniform over the workgroup)
+  const int m = G.tile_rows(j0, (int)blockDim.x);
+  const long long base = G.row(j0);
   if ((int)threadIdx.x < m) {
     const double *x = nodes + (size_t)b * S.n_vars;
-    long long first = first_row ? first_row[b] : A.first_row;
-    first = first < 0 ? 0 : first;
-    const long long k = first + j0 + threadIdx.x;
     double row[QTOS_CSV_COLS];
-    const double t = sample_row_state_at(S, x, t0[b], k > INT_MAX ? INT_MAX : (int)k, A.hz, row);
+    const double t = sample_row_state_at(S, x, t0[b], G.plan_row(j0, threadIdx.x), A.hz, row);
     for (int e = 0; e < NEE; ++e) sample_spline(S.eef[e], x, t, 0, row + 25 + 3 * e);
     double fv[NEE][3];
     for (int e = 0; e < NEE; ++e) sample_spline(S.eem[e], x, t, 1, fv[e]);
@@ -392,19 +390,10 @@ __global__ __launch_bounds__(TILE) void k_joint_rows(const SamplePlan *Sd, Joint
     st |= joint_leg<1>(A, row, R, wb, fv[1], qm, qdm, dst);
     st |= joint_leg<2>(A, row, R, wb, fv[2], qm, qdm, dst);
     st |= joint_leg<3>(A, row, R, wb, fv[3], qm, qdm, dst);
-    long long o = base + threadIdx.x;
-    if (o >= rows_b) o -= rows_b;
-    status_out[(size_t)b * (size_t)rows_b + o] = st;
+    status_out[(size_t)b * (size_t)G.rows_b + G.tile_row(base, threadIdx.x)] = st;
   }
   __syncthreads();
-  double *dst = out + (size_t)b * (size_t)rows_b * QTOS_CSV_COLS;
-  const long long all = rows_b * QTOS_CSV_COLS;
-  base *= QTOS_CSV_COLS;
-  for (int e = threadIdx.x; e < m * QTOS_CSV_COLS; e += blockDim.x) {
-    long long o = base + e;                                                        // (m <= rows_b: o < 2 all)
-    if (o >= all) o -= all;
-    dst[o] = joint_tile[e];
-  }
+  segment_tile_out<QTOS_CSV_COLS>(G, base, m, joint_tile, out + (size_t)b * (size_t)G.rows_b * QTOS_CSV_COLS, blockDim.x);
 }
 
 // Measured states and tracking errors of the windows (qtos_track*; scripts/run.py:244-273, QTOS/tracking.py Tracking.update /
@@ -417,7 +406,7 @@ __global__ __launch_bounds__(TILE) void k_joint_rows(const SamplePlan *Sd, Joint
 // a template over the leg, and the 24 values and five errors into the row's place of an LDS tile; (B) behind a barrier lane 0
 // runs the CoM chain over the tile's rows and the first lane of the second wave the feet chain (lane 0 again where the
 // workgroup is one wave), each from the total it carries in a register from the previous tile, into columns 24 and 25; (C) the
-// tile goes out flat, consecutive lanes on consecutive doubles, the pitch of 26 doubles kept (k_stitch's addressing: table or
+// tile goes out flat, consecutive lanes on consecutive doubles, the pitch of 26 doubles kept (RowSegment's addressing: table or
 // ring, cursor and t0 only read).  The status is one int per lane.  The owners of the chains write count and total back with
 // plain stores behind the last tile; every lane has read them in front of the first barrier.  No atomics, no scratch (constant
 // indices only, see k_joint_rows), no sincos.
@@ -500,9 +489,8 @@ __global__ __launch_bounds__(TILE) void k_track(const SamplePlan *Sd, TrackArgs 
   const int b = blockIdx.x;
   if (b >= B) return;
   const SamplePlan &S = *Sd;
-  const long long rows_b = A.capacity > 0 ? A.capacity : (long long)A.n_rows;      // rows of window b's table or ring
-  long long n = n_rows ? n_rows[b] : A.n_rows;
-  n = n < 0 ? 0 : (n > rows_b ? rows_b : n);
+  const RowSegment G = RowSegment::of(A.capacity, A.n_rows, A.first_row, n_rows, first_row, cursor, b);
+  const long long rows_b = G.rows_b, n = G.n;
   if (n == 0) return;                                                              // (uniform: a window without rows keeps its accumulators)
   const bool quat = (A.flags & 1) != 0, clean = (A.flags & 2) != 0;
   const int mcols = quat ? 19 : 18;
@@ -510,28 +498,17 @@ __global__ __launch_bounds__(TILE) void k_track(const SamplePlan *Sd, TrackArgs 
   long long rec = count[2 * b + 1];
   double run = total[2 * b + (threadIdx.x == FEET_LANE && FEET_LANE ? 1 : 0)];     // the chain this lane owns, if it owns one
   double run_feet = total[2 * b + 1];                                              // (one wave: lane 0 owns both)
-  long long pos = 0;                                                               // table or ring row of the segment's first row
-  if (A.capacity > 0) {
-    pos = cursor[b] % A.capacity;
-    if (pos < 0) pos += A.capacity;
-  }
   const double *x = nodes + (size_t)b * S.n_vars;
-  long long first = first_row ? first_row[b] : A.first_row;
-  first = first < 0 ? 0 : first;
   const double t0b = t0[b];
   const double *meas_b = meas + (size_t)b * (size_t)rows_b * mcols;
   double *out_b = out + (size_t)b * (size_t)rows_b * TRACK_COLS;
-  const long long all = rows_b * TRACK_COLS;
   for (long long j0 = 0; j0 < n; j0 += TILE) {                                     // (n is uniform over the workgroup: so are the barriers)
-    const int m = n - j0 < TILE ? (int)(n - j0) : TILE;
-    long long base = pos + j0;                                                     // (pos < rows_b and j0 < n <= rows_b: one subtraction wraps it)
-    if (base >= rows_b) base -= rows_b;
+    const int m = G.tile_rows(j0, TILE);
+    const long long base = G.row(j0);
     if ((int)threadIdx.x < m) {                                                    // (A) a lane takes a row
-      const long long k = first + j0 + threadIdx.x;
       double row[25];
-      sample_row_state_at(S, x, t0b, k > INT_MAX ? INT_MAX : (int)k, A.hz, row);
-      long long o = base + threadIdx.x;
-      if (o >= rows_b) o -= rows_b;
+      sample_row_state_at(S, x, t0b, G.plan_row(j0, threadIdx.x), A.hz, row);
+      const long long o = G.tile_row(base, threadIdx.x);
       const double *mr = meas_b + (size_t)o * mcols;
       double *dst = track_tile + threadIdx.x * TRACK_COLS;
       double R[9];
@@ -566,12 +543,7 @@ __global__ __launch_bounds__(TILE) void k_track(const SamplePlan *Sd, TrackArgs 
       if (FEET_LANE) run = f; else run_feet = f;
     }
     __syncthreads();
-    base *= TRACK_COLS;                                                            // (C) the tile goes out flat
-    for (int e = threadIdx.x; e < m * TRACK_COLS; e += TILE) {
-      long long o = base + e;                                                      // (m <= rows_b: o < 2 all)
-      if (o >= all) o -= all;
-      out_b[o] = track_tile[e];
-    }
+    segment_tile_out<TRACK_COLS>(G, base, m, track_tile, out_b, TILE);             // (C) the tile goes out flat
     __syncthreads();
   }
   if (threadIdx.x == 0) {
@@ -656,21 +628,14 @@ __global__ __launch_bounds__(64) void k_start_feedback(const SamplePlan *Sd, Fee
   int *stb = status + b;
   const int map = map_id ? map_id[b] : 0;
   const long long r = row_in[b];
-  const long long rows_b = A.K.capacity > 0 ? A.K.capacity : (long long)A.K.n_rows;   // rows of window b's table or ring
+  const RowSegment G = RowSegment::of(A.K.capacity, A.K.n_rows, A.K.first_row, nullptr, nullptr, cursor, b);
   long long k = r - A.lat;                                                            // the measured plan row
-  if (k > A.K.first_row + r - 1) k = A.K.first_row + r - 1;
-  if (k < A.K.first_row) k = A.K.first_row;
-  const long long j = k - A.K.first_row;                                              // its place in the segment
-  if (r <= 0 || j >= rows_b) { *stb = 32; return; }                              // no measurement: nothing else is touched
-  long long o = j;
-  if (A.K.capacity > 0) {
-    long long pos = cursor[b] % A.K.capacity;
-    if (pos < 0) pos += A.K.capacity;
-    o = pos + j;                                                                      // (pos, j < capacity: one subtraction wraps it)
-    if (o >= A.K.capacity) o -= A.K.capacity;
-  }
+  if (k > G.first + r - 1) k = G.first + r - 1;
+  if (k < G.first) k = G.first;
+  const long long j = k - G.first;                                                    // its place in the segment
+  if (r <= 0 || j >= G.rows_b) { *stb = 32; return; }                            // no measurement: nothing else is touched
   const bool quat = (A.K.flags & 1) != 0;
-  const double *mr = meas + ((size_t)b * (size_t)rows_b + (size_t)o) * (quat ? 19 : 18);
+  const double *mr = meas + ((size_t)b * (size_t)G.rows_b + (size_t)G.row(j)) * (quat ? 19 : 18);
   double row[25] = {0}, dst[TRACK_COLS], R[9];   // (track_leg's error column against `row` is not used here: the row comes behind the legs)
   int st = track_pose(mr, quat, R, dst + 4);                                          // (bit 2: the pitch clip acted)
   dst[1] = mr[0]; dst[2] = mr[1]; dst[3] = mr[2];
@@ -679,7 +644,7 @@ __global__ __launch_bounds__(64) void k_start_feedback(const SamplePlan *Sd, Fee
   track_leg<1>(A.K, row, mr, R, q, dst);
   track_leg<2>(A.K, row, mr, R, q, dst);
   track_leg<3>(A.K, row, mr, R, q, dst);
-  sample_row_state_at(S, nodes + (size_t)b * S.n_vars, t0[b], k > INT_MAX ? INT_MAX : (int)k, A.K.hz, row);
+  sample_row_state_at(S, nodes + (size_t)b * S.n_vars, t0[b], G.plan_row(j, 0), A.K.hz, row);
   double e[18];
 #pragma unroll
   for (int i = 0; i < 18; ++i) e[i] = dst[1 + i] - row[1 + i];
@@ -849,6 +814,9 @@ __global__ __launch_bounds__(CHECK_TILE) void k_plan_check(const SamplePlan *Sd,
   const int b = blockIdx.x;
   if (b >= B) return;
   const SamplePlan &S = *Sd;
+  // A table only, so RowSegment's count and first-row clamps and its plan row are spelled here: through RowSegment the same
+  // lines compiled to 10 more spilled scalar registers, and the launch with per-window arrays measured up to 0.8 % slower
+  // ("Row segments").
   long long n = n_rows ? n_rows[b] : A.n_rows;
   n = n < 0 ? 0 : (n > A.n_rows ? A.n_rows : n);
   long long first = first_row ? first_row[b] : A.first_row;
@@ -940,7 +908,7 @@ __global__ __launch_bounds__(CHECK_TILE) void k_plan_check(const SamplePlan *Sd,
 // reads its e) -- only +, -, x, / and sqrt; (C) behind a barrier a lane turns its row's state into the 20 output columns (R from
 // the quaternion, the Euler extraction of track_pose, R w_b) in the row's own place, and behind one more barrier the tile goes
 // out flat, consecutive lanes on consecutive doubles: `rows` with its pitch of 20, `meas` with its 18 or 19 columns, the joint
-// columns copied from the joint ring's row or left alone (k_stitch's addressing: table or ring, cursor and t0 only read).
+// columns copied from the joint ring's row or left alone (RowSegment's addressing: table or ring, cursor and t0 only read).
 // Carried state, count and word are read in front of the first barrier and written once by lane 0 behind the last tile; a
 // window without rows keeps them (QTOS_ROLLOUT_PENDING in its word with them, until a call gives it rows).  The two chains are NOT split over two lanes or pipelined over tiles: the freeze (a fallen
 // body stops both) couples them row by row, and the one-lane form was not measured against a split one.  No atomics, no
@@ -1083,10 +1051,6 @@ __global__ __launch_bounds__(TILE) void k_rollout(const SamplePlan *Sd, RolloutA
   const int b = blockIdx.x;
   if (b >= B) return;
   const SamplePlan &S = *Sd;
-  const long long rows_b = A.capacity > 0 ? A.capacity : (long long)A.n_rows;      // rows of window b's table or ring
-  long long n = n_rows ? n_rows[b] : A.n_rows;
-  n = n < 0 ? 0 : (n > rows_b ? rows_b : n);
-  if (n == 0) return;                                                              // (uniform: a window without rows keeps its state)
   const bool quat = (A.flags & 2) != 0;
   const int mcols = quat ? 19 : 18;
   RolloutState s;                                                                  // (every lane, in front of the first barrier)
@@ -1108,26 +1072,22 @@ __global__ __launch_bounds__(TILE) void k_rollout(const SamplePlan *Sd, RolloutA
     M.F0 = pb ? pb[0] : 0.0; M.F1 = pb ? pb[1] : 0.0; M.F2 = pb ? pb[2] : 0.0;
     M.T0 = pb ? pb[3] : 0.0; M.T1 = pb ? pb[4] : 0.0; M.T2 = pb ? pb[5] : 0.0;
   }
-  long long pos = 0;                                                               // table or ring row of the segment's first row
-  if (A.capacity > 0) {
-    pos = cursor[b] % A.capacity;
-    if (pos < 0) pos += A.capacity;
-  }
+  // (the segment is formed here, behind the loads of the carried state: formed in front of them its scalars are live across
+  // them, and the tick measured 0.5 - 2 % slower; DESIGN.md, "Row segments")
+  const RowSegment G = RowSegment::of(A.capacity, A.n_rows, A.first_row, n_rows, first_row, cursor, b);
+  const long long rows_b = G.rows_b, n = G.n;
+  if (n == 0) return;                                                              // (uniform: a window without rows keeps its state)
   const double *x = nodes + (size_t)b * S.n_vars;
-  long long first = first_row ? first_row[b] : A.first_row;
-  first = first < 0 ? 0 : first;
   const double t0b = t0[b];
   double *meas_b = meas + (size_t)b * (size_t)rows_b * mcols;
   double *out_b = rows_out ? rows_out + (size_t)b * (size_t)rows_b * ROLLOUT_COLS : nullptr;
   const double *joint_b = joint ? joint + (size_t)b * (size_t)rows_b * QTOS_CSV_COLS : nullptr;
   for (long long j0 = 0; j0 < n; j0 += TILE) {                                     // (n is uniform over the workgroup: so are the barriers)
-    const int m = n - j0 < TILE ? (int)(n - j0) : TILE;
-    long long base = pos + j0;                                                     // (pos < rows_b and j0 < n <= rows_b: one subtraction wraps it)
-    if (base >= rows_b) base -= rows_b;
+    const int m = G.tile_rows(j0, TILE);
+    const long long base = G.row(j0);
     if ((int)threadIdx.x < m) {                                                    // (A) a lane takes a row of the plan
-      const long long k = first + j0 + threadIdx.x;
       double row[QTOS_CSV_COLS];
-      const double t = sample_row_state_at(S, x, t0b, k > INT_MAX ? INT_MAX : (int)k, A.hz, row);
+      const double t = sample_row_state_at(S, x, t0b, G.plan_row(j0, threadIdx.x), A.hz, row);
       for (int e = 0; e < NEE; ++e) sample_spline(S.eef[e], x, t, 0, row + 25 + 3 * e);
       rollout_inputs(row, A.ff_scale, roll_tile + threadIdx.x * ROLLOUT_PITCH);
     }
@@ -1182,35 +1142,22 @@ __global__ __launch_bounds__(TILE) void k_rollout(const SamplePlan *Sd, RolloutA
     if ((int)threadIdx.x < m) {                                                    // (C) a lane turns its row's state into the output columns
       double *p = roll_tile + threadIdx.x * ROLLOUT_PITCH;
       const int st = (int)p[36] | rollout_output(p);
-      long long o = base + threadIdx.x;
-      if (o >= rows_b) o -= rows_b;
-      status_out[(size_t)b * (size_t)rows_b + o] = st;
+      status_out[(size_t)b * (size_t)rows_b + G.tile_row(base, threadIdx.x)] = st;
     }
     __syncthreads();
     if (out_b) {                                                                   // the tile goes out flat: rows ...
-      const long long all = rows_b * ROLLOUT_COLS, at = base * ROLLOUT_COLS;
       for (int e = threadIdx.x; e < m * ROLLOUT_COLS; e += TILE) {
         const int i = e / ROLLOUT_COLS, c = e - i * ROLLOUT_COLS;
-        long long o = at + e;                                                      // (m <= rows_b: o < 2 all)
-        if (o >= all) o -= all;
-        out_b[o] = roll_tile[i * ROLLOUT_PITCH + c];
+        out_b[G.flat(base, ROLLOUT_COLS, e)] = roll_tile[i * ROLLOUT_PITCH + c];
       }
     }
-    {                                                                              // ... and meas
-      const long long all = rows_b * mcols, at = base * mcols;
-      for (int e = threadIdx.x; e < m * mcols; e += TILE) {
-        const int i = e / mcols, c = e - i * mcols;
-        const double *p = roll_tile + i * ROLLOUT_PITCH;
-        long long o = at + e;
-        if (o >= all) o -= all;
-        if (c < 3) meas_b[o] = p[1 + c];
-        else if (c < mcols - 12) meas_b[o] = quat ? p[13 + (c - 3)] : p[4 + (c - 3)];
-        else if (joint_b) {
-          long long ro = base + i;
-          if (ro >= rows_b) ro -= rows_b;
-          meas_b[o] = joint_b[(size_t)ro * QTOS_CSV_COLS + 1 + (c - (mcols - 12))];
-        }
-      }
+    for (int e = threadIdx.x; e < m * mcols; e += TILE) {                          // ... and meas
+      const int i = e / mcols, c = e - i * mcols;
+      const double *p = roll_tile + i * ROLLOUT_PITCH;
+      const long long o = G.flat(base, mcols, e);
+      if (c < 3) meas_b[o] = p[1 + c];
+      else if (c < mcols - 12) meas_b[o] = quat ? p[13 + (c - 3)] : p[4 + (c - 3)];
+      else if (joint_b) meas_b[o] = joint_b[(size_t)G.tile_row(base, i) * QTOS_CSV_COLS + 1 + (c - (mcols - 12))];
     }
     __syncthreads();
   }

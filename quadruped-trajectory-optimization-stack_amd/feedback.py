@@ -14,6 +14,7 @@ import numpy as np
 
 from . import joints, tracking
 from .joints import NEE
+from .stitcher import ring_index
 
 CORRECTED, CLIPPED, GIMBAL, FALLBACK, NO_MEASUREMENT = 1, 2, 4, 8, 32      # status bits of a window
 SNAPPED = 64                                                                 # << f: foot f's z moved by more than snap_tol
@@ -112,7 +113,7 @@ def start_feedback(L, x, t0, row, meas, params, start, height=None, map_id=0, go
         return s_in.copy(), None, err, NO_MEASUREMENT
     k, j = at
     cap = int(params.capacity)
-    m_row = meas[(int(cursor) + j) % cap] if cap > 0 else meas[j]           # (only this row is read)
+    m_row = meas[ring_index(cursor, j + 1, cap)[j]] if cap > 0 else meas[j]        # (only this row is read)
     hz = float(params.hz) if float(params.hz) > 0 else 1000.0
     pose, gimbal = tracking.measured_pose(m_row, params, dtype, with_status=True)
     plan = tracking.plan_positions(L, x, t0, hz, k, 1, dtype)[0, 1:19]

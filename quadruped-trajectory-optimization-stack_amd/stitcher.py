@@ -116,13 +116,19 @@ def stitch_segments(tables, rows, first_row):
     return np.concatenate(segs, axis=0) if segs else np.zeros((0, 37))
 
 
+def ring_index(cursor, n, capacity):
+    """The ring rows of a segment of n rows: (cursor + j) % capacity for j = 0 .. n - 1, the floor modulus, so a negative
+    cursor lands in 0 .. capacity - 1.  The window kernels' form of this line is csrc/row_segment.hpp."""
+    return (int(cursor) + np.arange(int(n))) % int(capacity)
+
+
 def ring_append(ring, cursor, seg):
-    """Append the rows of ``seg`` to a ring of ``len(ring)`` rows in place: row j goes to ring[(cursor + j) % capacity]; a
+    """Append the rows of ``seg`` to a ring of ``len(ring)`` rows in place: row j goes to ring row ring_index(cursor, n, capacity)[j]; a
     segment longer than the ring keeps its first ``capacity`` rows (k_stitch clamps the count).  Returns the new cursor, a
     running total that is never reduced modulo the capacity."""
     cap = len(ring)
     seg = np.asarray(seg)[:cap]
-    ring[(int(cursor) + np.arange(len(seg))) % cap] = seg
+    ring[ring_index(cursor, len(seg), cap)] = seg
     return int(cursor) + len(seg)
 
 

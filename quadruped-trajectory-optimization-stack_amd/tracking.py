@@ -16,6 +16,7 @@ import numpy as np
 
 from . import joints
 from .joints import NEE
+from .stitcher import ring_index
 
 TRACK_COLS = 26
 RECORDED, REACHED, GIMBAL = 1, 2, 4        # status bits of a row
@@ -188,7 +189,7 @@ def track_ring(L, x, t0, hz, first_row, n_rows, meas_ring, cursor, params, out_r
     the cursor is only read.  Returns (count, total)."""
     cap = len(out_ring)
     n = min(max(int(n_rows), 0), cap)
-    at = (int(cursor) + np.arange(n)) % cap
+    at = ring_index(cursor, n, cap)
     rows, status, count, total = track_rows(L, x, t0, hz, first_row, n, np.asarray(meas_ring)[at], params, count, total, goal_x, dtype)
     out_ring[at] = rows
     status_ring[at] = status

@@ -17,6 +17,6 @@ for k in notes.split("- .agpr_count")[1:]:
     if not pat.search(nm):
         continue
     g = lambda f: int(re.search(r"\.%s:\s+(\d+)" % f, k).group(1))
-    print("%-60s vgpr %3d  scratch %4d B  sgpr spills %3d  vgpr spills %3d  code %6d B" %
-          (subprocess.check_output(["c++filt", nm], text=True).strip()[:60], g("vgpr_count"), g("private_segment_fixed_size"),
-           g("sgpr_spill_count"), g("vgpr_spill_count"), size.get(nm, 0)))
+    print("%-60s vgpr %3d  sgpr %3d  scratch %4d B  sgpr spills %3d  vgpr spills %3d  lds %6d B  code %6d B" %
+          (subprocess.check_output(["c++filt", nm], text=True).strip()[:60], g("vgpr_count"), g("sgpr_count"),
+           g("private_segment_fixed_size"), g("sgpr_spill_count"), g("vgpr_spill_count"), g("group_segment_fixed_size"), size.get(nm, 0)))
