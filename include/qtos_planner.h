@@ -140,10 +140,6 @@ int qtos_analyze_order(const QtosParams *params, int *order, int max_positions);
  *   [17] two chains with today's layouts  [18] two chains with a lean layout (two panels + the blanked copy, one dynamic-only
  *   record buffer per chain, gather tables from L2)  [19] the limit (160 KB - 256 B).  DESIGN.md section 5. */
 int qtos_analyze_two_ended(const QtosParams *params, int *out, int n_out);
-/* Host-only: the Kronecker structure of the range-of-motion blocks (experiment QTOS_KRON of round 4): inequality blocks in all,
- * blocks with the structure, the most of them in one stage record, and the largest relative difference between an entry formed
- * through a block's 33 sums and the direct three-term sum on random data. */
-int qtos_analyze_kron(const QtosParams *params, int *n_blocks, int *n_kron, int *max_in_record, double *worst);
 
 /* Terrain side channel.  Replaces `docker cp towr_heightfield.txt <id>:...`
  * (QTOS/utils.py:21-22; scripts/main.py:77-78; QTOS/generateHeightField.py:276-279).
@@ -247,9 +243,6 @@ int qtos_plan_batch(QtosPlanner *p, int B, const double *start, const double *go
  *                            Unset: on a reduced base rules 2 and 1 are analysed and the smaller front is kept (rule 0 loses up to
  *                            six digits of a KKT solve on short trot horizons and is not in the automatic choice there); full-base
  *                            systems keep rule 0
- *   QTOS_KRON=1              experiment builds only (128-slot fronts, k_kkt2): the range-of-motion blocks are assembled through
- *                            their Kronecker structure -- 33 sums per block and one product of static weights per entry instead
- *                            of a three-term sum per entry; plans equal to rounding (1e-8), -0.4 % per launch
  *   QTOS_SWEEP_DS=0          k_step forms the slack steps ds = Ji dx + (g - s) itself (default 1: three waves that idle in the
  *                            backward sweep of the KKT kernels form them, block by block behind the stage that solves the
  *                            block's earliest column; bit-identical plans)
@@ -1025,8 +1018,8 @@ int qtos_debug_trace(QtosPlanner *p, int b, double *trace_out);
  * equality multipliers y of the last KKT solve (zero for dropped rows and rows a reduction eliminated).  Any array may be
  * null. */
 int qtos_debug_duals(QtosPlanner *p, int B, double *s, double *zl, double *zu, double *y);
-/* What this build of the library contains: bit 0 = the Kronecker assembly of k_kkt2<128> (QTOS_KRON; -DQTOS_EXPERIMENTS,
- * scratch/build.sh), bit 1 = per-wave cycle stamps (-DQTOS_STAMPS),
+/* What this build of the library contains: bit 0 is reserved and always 0 (it marked the experiment build of round 4, which
+ * left the library; the other bits keep their numbers), bit 1 = per-wave cycle stamps (-DQTOS_STAMPS),
  * bit 2 = a development build with the benchmark's fronts only (-DQTOS_DEV_F128).  The product library returns 0. */
 int qtos_build_flags(void);
 /* The factor + solve kernel qtos_planner_create selected for this planner, e.g. "k_kkt2<128>", "k_kkt3<112, 1>",

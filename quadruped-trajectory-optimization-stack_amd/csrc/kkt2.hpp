@@ -987,7 +987,7 @@ __device__ __forceinline__ void kkt2_backward(const Kkt2Ctx<F> &cx, const DevPla
   sweep_backward<F>(P, cx.panel, cx.dx, W.sol + (size_t)b * P.n_stages * PIV, cx.xs, cx.red, nxp, wv, lane, cx.lds + ((Kkt2Layout<F>::PB + NS * 6 + 1) & ~1), sd);
 }
 
-template <int F, bool CONT, bool KRON = false>
+template <int F, bool CONT>
 __global__ __launch_bounds__(KT2) void k_kkt2(DevPlan P, DevWork W, int B) {
   const int b = blockIdx.x;
   if (b >= B || W.done[b] || W.chord[b] == 1) return;   // (a problem flagged for a chord step is k_chord's)
@@ -998,7 +998,6 @@ __global__ __launch_bounds__(KT2) void k_kkt2(DevPlan P, DevWork W, int B) {
   const int tid = threadIdx.x, NS = P.n_stages, n = P.n_sol;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, li = lane & 15, lk = lane >> 4;
   const Kkt2Ctx<F> cx(lds, P, W, b, wv, li, lk);
-  double *ksm = (double *)((char *)lds + (KRON ? P.kron_lds_off : 0));   // KRON: the 33 sums of the Kronecker blocks of the record about to be assembled
   constexpr bool DMA = F <= 128;   // records by LDS-DMA into two buffers, else through prefetch registers into one
   double *dbuf = cx.dbuf0;
   int *sbuf = cx.sbuf0;
@@ -1045,9 +1044,7 @@ __global__ __launch_bounds__(KT2) void k_kkt2(DevPlan P, DevWork W, int B) {
   load_records(0);
   __syncthreads();
   header_from_lds(0);
-  if constexpr (KRON) kron_sums(sbuf, dbuf, ksm, wv, 16, lane);
   __syncthreads();
-  if constexpr (KRON) assemble_stage_kron(cx.A, F, sbuf, dbuf, ksm, tid, KT2); else
   assemble_stage(cx.A, F, sbuf, dbuf, tid, KT2);
   assemble_continuations(tid, KT2);
   __syncthreads();
@@ -1074,10 +1071,8 @@ __global__ __launch_bounds__(KT2) void k_kkt2(DevPlan P, DevWork W, int B) {
     load_records(s);
     __syncthreads();
     header_from_lds(s);
-    if constexpr (KRON) { if (s == 1) kron_sums(sbuf, dbuf, ksm, wv, 16, lane); }
     __syncthreads();
     if (s == 1) {
-      if constexpr (KRON) assemble_stage_kron(cx.A, F, sbuf, dbuf, ksm, tid, KT2); else
       assemble_stage(cx.A, F, sbuf, dbuf, tid, KT2);
       assemble_continuations(tid, KT2);
     }
@@ -1127,10 +1122,6 @@ __global__ __launch_bounds__(KT2) void k_kkt2(DevPlan P, DevWork W, int B) {
       const int sv = wv - NT;
       if (sv == 0) {
         kkt2_ab_rhs(cx, k, lane, li, lk, Pk, Xn, has_next, prow_next, rc_cur, true);
-      }
-      else if (KRON && LY::VP) {
-        // the waves that idle in this phase: the 33 sums of the Kronecker blocks of the records of stage k+2 (assembled in C(k))
-        if (k + 2 < NS) kron_sums(sbuf, dbuf, ksm, sv - 1, NSV - 1, lane);
       }
       else if (!LY::VP && sv < NT) {
         // Y = P L^-T of row tile R = sv for its tile wave
@@ -1190,7 +1181,6 @@ __global__ __launch_bounds__(KT2) void k_kkt2(DevPlan P, DevWork W, int B) {
     const int apos = cx.is_upd ? (15 - NU) + cx.uw : cx.uw - NU;
     constexpr int NASM = 15 - (NU >= 12 ? 3 : 0);
     if (wv >= 1 && k + 2 < NS && apos < NASM) {
-      if constexpr (KRON) assemble_stage_kron(cx.A, F, sbuf, dbuf, ksm, apos * 64 + lane, NASM * 64); else
       assemble_stage(cx.A, F, sbuf, dbuf, apos * 64 + lane, NASM * 64);
     }
     if constexpr (CONT) {

@@ -183,10 +183,7 @@ class Staging {
 // k_kkt is compiled once per front size (multiples of 16 up to 128): the LDS layout and every tile
 // loop bound are compile-time constants
 // k_kkt2 (16 waves per problem): fronts up to 208 slots
-static void (*kkt2_kernel(int F, bool cont, bool kron = false))(DevPlan, DevWork, int) {
-#if defined(QTOS_EXPERIMENTS) && !defined(QTOS_DEV_F128)
-  if (kron && !cont && F == 128) return k_kkt2<128, false, true>;
-#endif   // (the Kronecker assembly: the benchmark's front only)
+static void (*kkt2_kernel(int F, bool cont))(DevPlan, DevWork, int) {
 #define QTOS_KKT2(f) case f: return cont ? k_kkt2<f, true> : k_kkt2<f, false>;
   switch (F) {
 #ifdef QTOS_DEV_F128   // (development builds: the benchmark's fronts only, a quarter of the compile time)
@@ -261,11 +258,11 @@ static int upload_spline(QtosPlanner *p, const Spline &S, SampleSpline *out) {
   return 0;
 }
 
-// The analysis of an order rule and variant (pair mode, record cap, Kronecker assembly; the default has none): 0, -1 / 1 failed
-static int build_analysis(Analysis &A, const QtosParams &params, const QtosEnv &env, int order_rule, bool pair = false, int cap = 0, bool kron = false) {
+// The analysis of an order rule and variant (pair mode, record cap; the default has neither): 0, -1 / 1 failed
+static int build_analysis(Analysis &A, const QtosParams &params, const QtosEnv &env, int order_rule, bool pair = false, int cap = 0) {
   A = Analysis();
   A.M.order_rule = order_rule;
-  A.S.env = env; A.S.cell_mode = 2; A.S.pair_mode = pair; A.S.rec_cap_ints = cap; A.S.kron = kron;
+  A.S.env = env; A.S.cell_mode = 2; A.S.pair_mode = pair; A.S.rec_cap_ints = cap;
   if (A.M.build(params)) return -1;
   return A.S.build(A.M) ? 1 : 0;
 }
@@ -302,11 +299,11 @@ static int pick_order_rule(const QtosParams &params, const QtosEnv &env, Analysi
   return best;
 }
 
-// What the qtos_analyze* entry points describe: the default variant (kron: Kronecker assembly), whatever a planner would run
-static int analyze_host(const QtosParams &params, const QtosEnv &env, bool kron, Analysis &A) {
+// What the qtos_analyze* entry points describe: the default variant, whatever a planner would run
+static int analyze_host(const QtosParams &params, const QtosEnv &env, Analysis &A) {
   bool built;
   const int rule = pick_order_rule(params, env, A, built);
-  const int rc = built && !kron ? 0 : build_analysis(A, params, env, rule, false, 0, kron);
+  const int rc = built ? 0 : build_analysis(A, params, env, rule);
   return rc ? print_error(A, rc) : 0;
 }
 static size_t kkt_lds_bytes(Kkt k, const Symbolic &S) {
@@ -355,27 +352,11 @@ static int choose_kernel(const QtosParams &params, const QtosEnv &env, Kkt &kind
     if (ok) { kind = Kkt::kkt3; A = std::move(def); return 0; }
   }
   kind = Kkt::kkt2;
-  bool kron = false;   // (experiment builds: Kronecker assembly of the range-of-motion blocks, k_kkt2<128> only)
-#ifdef QTOS_EXPERIMENTS
-  kron = env.kron != 0;
-#endif
   for (int cap : {0, 4096, 3072, 2048}) {
     int rc;
-    if (kron) {
-      if ((rc = build_analysis(A, params, env, rule, false, cap, true))) return print_error(A, rc);
-      // the Kronecker assembly needs the benchmark's shape: a 128-slot front, no continuation records, its scratch within the LDS
-      const int n_cont = A.S.n_continuation();
-      const size_t need = kkt_lds_bytes(Kkt::kkt2, A.S) + 16 + sizeof(double) * Symbolic::KRON_SM * (size_t)A.S.max_kblocks;
-      if (A.S.front != 128 || n_cont != 0 || A.S.max_kblocks == 0 || need > LDS_LIMIT) {
-        if (env.debug) fprintf(stderr, "qtos: Kronecker assembly not applicable (front %d, %d continuation records, %zu B of LDS)\n", A.S.front, n_cont, need);
-        kron = false;
-      }
-    }
-    if (!kron) {
-      if (cap == 0) { rc = def_rc; A = std::move(def); }
-      else rc = build_analysis(A, params, env, rule, false, cap);
-      if (rc) return print_error(A, rc);
-    }
+    if (cap == 0) { rc = def_rc; A = std::move(def); }
+    else rc = build_analysis(A, params, env, rule, false, cap);
+    if (rc) return print_error(A, rc);
     if (kkt_lds_bytes(Kkt::kkt2, A.S) <= LDS_LIMIT) break;
   }
   return 0;
@@ -670,12 +651,6 @@ static int create_planner(const QtosParams *params, int max_batch, int device, c
   // LDS budget of k_kkt
   const int F = S.front;
   p->kkt_lds = kkt_lds_bytes(p->kkt, S);
-  D.kron_lds_off = 0;
-  if (env.debug) fprintf(stderr, "qtos: Kronecker assembly %s (kkt3 %d, most blocks in a record %d)\n", S.kron ? "on" : "off", (int)(p->kkt == Kkt::kkt3), S.max_kblocks);
-  if (S.kron) {   // (k_kkt2 only: choose_kernel)
-    D.kron_lds_off = (int)((p->kkt_lds + 15) & ~(size_t)15);
-    p->kkt_lds = (size_t)D.kron_lds_off + sizeof(double) * Symbolic::KRON_SM * (size_t)S.max_kblocks;
-  }
   if (p->kkt == Kkt::kkt5 && F > 128) D.sw_on = 0;   // (nine tile waves of twelve: fewer than three helper waves are left)
   if (D.sw_on) {
     // the helper waves' tables of the backward sweep (solution by position, rounds) behind the sweep's own: within the LDS
@@ -703,7 +678,7 @@ static int create_planner(const QtosParams *params, int max_batch, int device, c
     switch (p->kkt) {
       case Kkt::kkt5: p->kkt_fn = kkt5_kernel(F); break;
       case Kkt::kkt3: p->kkt_fn = kkt3_kernel(F); break;
-      case Kkt::kkt2: p->kkt_fn = kkt2_kernel(F, D.n_cont > 0, S.kron); break;
+      case Kkt::kkt2: p->kkt_fn = kkt2_kernel(F, D.n_cont > 0); break;
     }
     p->chord_fn = chord_kernel(F);
     if (!p->kkt_fn) { p->err = "no k_kkt instantiation for this front size"; qtos_planner_destroy(p); return -4; }
@@ -863,15 +838,8 @@ int qtos_analyze(const QtosParams *params, QtosDims *d, int *stage_active, int m
   if (!params || !d) return -1;
   const QtosEnv env = QtosEnv::parse();
   Analysis A;
-  if (analyze_host(*params, env, env.debug_kron != 0, A)) return -1;
+  if (analyze_host(*params, env, A)) return -1;
   const auto &[M, S] = A;
-  if (env.debug_kron) {
-    int nb = 0;
-    const double worst = S.check_kron(&nb);
-    size_t tot = 0;
-    for (const Block &b : M.blocks) tot += b.kind == 1;
-    fprintf(stderr, "qtos: Kronecker blocks %d of %zu inequality blocks, most in a record %d, worst relative difference %.2e, max record %d ints / %d doubles\n", nb, tot, S.max_kblocks, worst, S.max_srec, S.max_drec);
-  }
   fill_dims(M, S, d);
   if (env.debug) { std::vector<SwTask> t; std::vector<int> c, c2; (void)build_sweep_tasks(M, S, t, c, c2); }
   if (stage_active)
@@ -884,7 +852,7 @@ int qtos_analyze(const QtosParams *params, QtosDims *d, int *stage_active, int m
 int qtos_analyze_order(const QtosParams *params, int *order, int max_positions) {
   if (!params || !order) return -1;
   Analysis A;
-  if (analyze_host(*params, QtosEnv::parse(), false, A)) return -1;
+  if (analyze_host(*params, QtosEnv::parse(), A)) return -1;
   const Symbolic &S = A.S;
   const int np = S.n_stages * PIV;
   for (int i = 0; i < np && i < max_positions; ++i) order[i] = i < (int)S.order.size() ? S.order[i] : -1;   // (as qtos_debug_structure)
@@ -903,7 +871,7 @@ int qtos_analyze_order(const QtosParams *params, int *order, int max_positions) 
 int qtos_analyze_two_ended(const QtosParams *params, int *out, int n_out) {
   if (!params || !out || n_out < 20) return -1;
   Analysis A;
-  if (analyze_host(*params, QtosEnv::parse(), false, A)) return -1;
+  if (analyze_host(*params, QtosEnv::parse(), A)) return -1;
   const auto &[M, S] = A;
   const Symbolic::TwoEnded t = S.analyze_two_ended(M);
   const int F = S.front, Fc = std::max(t.front_left, t.front_right);
@@ -922,28 +890,13 @@ int qtos_analyze_two_ended(const QtosParams *params, int *out, int n_out) {
   return 0;
 }
 
-// Host-only: the Kronecker structure of the range-of-motion blocks (Symbolic::kron_meta, QTOS_KRON): how many inequality
-// blocks have it, the most in one stage record, and the largest relative difference between an entry of G' S G / G' w formed
-// through the 33 sums of a block and the direct three-term sum, on random matrices and weights (Symbolic::check_kron).
-int qtos_analyze_kron(const QtosParams *params, int *n_blocks, int *n_kron, int *max_in_record, double *worst) {
-  if (!params || !n_blocks || !n_kron || !max_in_record || !worst) return -1;
-  Analysis A;
-  if (analyze_host(*params, QtosEnv::parse(), true, A)) return -1;
-  const auto &[M, S] = A;
-  *n_blocks = 0;
-  for (const Block &b : M.blocks) *n_blocks += b.kind == 1;
-  *worst = S.check_kron(n_kron);
-  *max_in_record = S.max_kblocks;
-  return 0;
-}
-
 // Host-only: the schedule the helper waves of the backward sweep follow (build_sweep_tasks).  Per place of a round (16 per
 // round, round i runs in step i of the chain, i.e. while it solves stage n_stages - 1 - i): the constraint row (-1: empty),
 // the row's entries, and the smallest and largest position (elimination order) of the row's columns.
 int qtos_analyze_sweep(const QtosParams *params, int *n_rounds, int *rows, int *entries, int *pos_min, int *pos_max, int max_places) {
   if (!params || !n_rounds) return -1;
   Analysis A;
-  if (analyze_host(*params, QtosEnv::parse(), false, A)) return -1;
+  if (analyze_host(*params, QtosEnv::parse(), A)) return -1;
   const auto &[M, S] = A;
   std::vector<SwTask> tasks;
   std::vector<int> cpos, c16;
@@ -1803,10 +1756,7 @@ int qtos_debug_residual(QtosPlanner *p, int B, int refine, double *dx_out, doubl
 }
 
 int qtos_build_flags(void) {
-  int f = 0;
-#ifdef QTOS_EXPERIMENTS
-  f |= 1;
-#endif
+  int f = 0;   // (bit 0 is reserved: always 0)
 #ifdef QTOS_STAMPS
   f |= 2;
 #endif

@@ -173,7 +173,7 @@ def test_kernel_choice_on_the_host(hip_lib, monkeypatch):
     from qtos_amd import capi
     from qtos_amd.config import PlannerConfig
     from test_gpu_kernels import EXPECT
-    for k in ("QTOS_KKT", "QTOS_ORDER", "QTOS_SHORT_STAGES", "QTOS_NO_SHORT_STAGES", "QTOS_KRON"):
+    for k in ("QTOS_KKT", "QTOS_ORDER", "QTOS_SHORT_STAGES", "QTOS_NO_SHORT_STAGES"):
         monkeypatch.delenv(k, raising=False)
     walk = PlannerConfig.knots100()
     cfgs = {"walk": walk, "trot": PlannerConfig.knots100(gait="trot"), "mixed": walk}   # (the terrains do not enter the analysis)
@@ -252,21 +252,6 @@ def test_sweep_schedule_of_the_slack_steps(which):
     assert all((stage_of_first_col[i][live[i]] == st[i]).all() for i in range(rows.shape[0]))
     seq = st[st >= 0]
     assert (np.diff(seq) <= 0).all()
-
-
-def test_kronecker_structure_of_the_range_of_motion_blocks():
-    """Every column of a range-of-motion block's Jacobian is a static multiple of a column of R(theta)^T or of
-    d(R^T (p - r))/d theta (towr range_of_motion_constraint.cc; Symbolic::kron_meta): on the 100-knot walk 252 of the 320
-    inequality blocks (the others are the friction pyramids and terrain rows), at most 8 in a stage record; every entry of
-    G' S G and G' w through the 33 sums of a block equals the direct three-term sum to rounding (random matrices and weights)."""
-    from qtos_amd import capi
-    from qtos_amd.config import PlannerConfig
-    # (the structure as found with every swing row in the system: reduce_swing folds the mid nodes' columns onto the footholds,
-    #  whose weights then differ per dimension -- the experiment's analysis does not cover that)
-    n_blocks, n_kron, most, worst = capi.analyze_kron(PlannerConfig.knots100(reduce_swing=False))
-    assert (n_blocks, n_kron, most) == (320, 252, 8) and worst < 1e-11
-    n_blocks, n_kron, most, worst = capi.analyze_kron(PlannerConfig.knots100(gait="trot", reduce_swing=False))
-    assert 0 < n_kron < n_blocks and worst < 1e-11
 
 
 def test_bad_parameters_are_rejected(hip_lib, cfg):

@@ -95,8 +95,7 @@ def test_k_kkt3_mode_1_gives_the_bits_of_k_kkt2(workload):
 
 def test_default_selection_and_fallback():
     """Unset: k_kkt3 MODE 1 up to 112 slots (the benchmark's transcriptions), k_kkt2 above (`-duration 12` and longer).  A choice that is not applicable (k_kkt5 on a horizon whose pair-mode
-    front has no instantiation, an experiment this build does not contain) falls back to the default instead of failing."""
-    from qtos_amd.capi import build_flags
+    front has no instantiation, an experiment that left the library) falls back to the default instead of failing."""
     from qtos_amd.config import PlannerConfig
     for workload in ("walk", "trot"):
         cfg, _, _ = _workload(workload, 4)
@@ -106,10 +105,9 @@ def test_default_selection_and_fallback():
     P = _planner(PlannerConfig.reference_compat(duration=20.0), 2, "6")
     assert P.kkt_kernel().startswith("k_kkt2")       # (`-duration 20`: a front of 160 slots and more, no k_kkt5 for it)
     P.close()
-    if not build_flags() & 1:
-        P = _planner(PlannerConfig.knots100(), 2, "5")
-        assert P.kkt_kernel() == EXPECT[(None, "walk")]
-        P.close()
+    P = _planner(PlannerConfig.knots100(), 2, "5")
+    assert P.kkt_kernel() == EXPECT[(None, "walk")]
+    P.close()
 
 
 def test_environment_is_read_once_at_creation_and_read_back():
