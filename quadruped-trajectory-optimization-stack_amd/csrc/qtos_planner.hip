@@ -1,9 +1,10 @@
 // qtos_planner.hip -- C ABI (include/qtos_planner.h) over the gfx950 kernels: the handle, the solver's entries (create,
-// submit / poll, report, debug, self-test) over kernels.hpp and kkt*.hpp here, the sampler's and the receding loop's entries over
-// window_kernels.hpp in window_api.hpp.  One translation unit.
+// submit / poll, report, debug, self-test) over kernels.hpp and kkt*.hpp here, the steps that build the handle in
+// planner_create.hpp, the sampler's and the receding loop's entries over window_kernels.hpp in window_api.hpp.  One translation unit.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared qtos_planner.hip -o libqtos_planner.so
 #include <hip/hip_runtime.h>
 
+#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -11,6 +12,7 @@
 #include <chrono>
 #include <cmath>
 #include <string>
+#include <tuple>
 #include <map>
 #include <memory>
 #include <vector>
@@ -113,6 +115,28 @@ struct QtosPlanner : Analysis {   // (the analysis the planner runs: choose_kern
   void (*kkt_fn)(DevPlan, DevWork, int) = nullptr;   // k_kkt / k_kkt2 instantiated for this front size
   int kkt_threads = KT;
   std::string err;
+  bool on_device = false;   // hipSetDevice(device) has succeeded (create_planner): from here on the handle may own device objects
+
+  // The handle owns what it allocates.  One that has made no HIP call yet makes none when it goes.
+  ~QtosPlanner() {
+    if (!on_device) return;
+    (void)hipSetDevice(device);
+    for (void *a : allocs) (void)hipFree(a);
+    for (auto &L : lanes) {
+      for (hipEvent_t e : L.ev)
+        if (e) (void)hipEventDestroy(e);
+      if (L.h_active) (void)hipHostFree(L.h_active);
+      for (hipStream_t s : {L.own, L.side})
+        if (s) (void)hipStreamDestroy(s);
+      for (hipEvent_t e : {L.ev_fork, L.ev_join, L.ev_done})
+        if (e) (void)hipEventDestroy(e);
+    }
+    for (void *q : {(void *)d_table, (void *)d_tab_dx, (void *)d_tab_dy, (void *)d_height, (void *)d_totals})
+      if (q) (void)hipFree(q);
+    for (hipEvent_t e : {ev_in, ev_height})
+      if (e) (void)hipEventDestroy(e);
+    if (own_stream) (void)hipStreamDestroy(own_stream);
+  }
 
   template <class T>
   int upload(const std::vector<T> &v, const T **out) {
@@ -234,30 +258,6 @@ static void (*chord_kernel(int F))(DevPlan, DevWork, int) {
   return nullptr;
 }
 
-static int upload_spline(QtosPlanner *p, const Spline &S, SampleSpline *out) {
-  std::vector<double> tend(2 * S.n_polys), dur(S.dur);
-  double t = 0;
-  double start = 0, start_err = 0;   // the exact start of polynomial i as a sum of two doubles (the additions' rounding errors kept)
-  for (int i = 0; i < S.n_polys; ++i) {
-    t += S.dur[i];
-    tend[i] = t;
-    const double start_f64 = tend[i] - S.dur[i];   // the start as sample_spline forms it
-    tend[S.n_polys + i] = (start - start_f64) + start_err;
-    const double sum = start + S.dur[i], b = sum - start;
-    start_err += (start - (sum - b)) + (S.dur[i] - b);
-    start = sum;
-  }
-  std::vector<int> idx;
-  for (auto &nd : S.idx)
-    for (int i = 0; i < 6; ++i) idx.push_back(nd[i]);
-  out->n_polys = S.n_polys;
-  int rc;
-  if ((rc = p->upload(tend, &out->tend))) return rc;
-  if ((rc = p->upload(dur, &out->dur))) return rc;
-  if ((rc = p->upload(idx, &out->idx))) return rc;
-  return 0;
-}
-
 // The analysis of an order rule and variant (pair mode, record cap; the default has neither): 0, -1 / 1 failed
 static int build_analysis(Analysis &A, const QtosParams &params, const QtosEnv &env, int order_rule, bool pair = false, int cap = 0) {
   A = Analysis();
@@ -268,35 +268,56 @@ static int build_analysis(Analysis &A, const QtosParams &params, const QtosEnv &
 }
 static int print_error(const Analysis &A, int rc) { fprintf(stderr, "qtos: %s\n", (rc < 0 ? A.M.err : A.S.err).c_str()); return -1; }
 
-// Which time keys the elimination order uses (model.hpp HostModel::order_rule).  On a reduced base rules 2 and 1 are analysed:
-// the smaller front wins, then the fewer stages, then the order that needs no continuation records, then rule 2.  Rule 0 -- the
-// order of rounds 1 - 5 -- has the smallest front on some short horizons and is NOT in the automatic choice there: its KKT solve
-// loses up to six digits on short trots (model.hpp).  QTOS_ORDER=0 | 1 | 2 forces one.  `won` keeps the winner, the default
-// variant of its rule (`built`), unless the analysis is to talk (QTOS_DEBUG_SYMBOLIC*, QTOS_DUMP_FIRST): the candidates do not.
-static int pick_order_rule(const QtosParams &params, const QtosEnv &env, Analysis &won, bool &built) {
-  built = false;
-  if (env.order >= 0) return env.order;
+// Which time keys the elimination order uses (model.hpp HostModel::order_rule): the rules in the order of preference, each
+// analysed once.  On a reduced base the rules of the mask are analysed (none given: 2 and 1, the automatic choice): the smaller
+// front comes first, then the fewer stages, then the order that needs no continuation records, then 2 before 1 before 0; a rule
+// whose analysis fails comes last with front 0.  Rule 0 -- the order of rounds 1 - 5 -- has the smallest front on some short
+// horizons and is NOT in the automatic choice there: its KKT solve loses up to six digits on short trots (model.hpp).
+// QTOS_ORDER=0 | 1 | 2 forces one rule, whatever the mask.  The candidates do not talk.
+struct Candidate {
+  int rule, front, stages, cont;
+  bool ok;
+  std::unique_ptr<Analysis> A;   // the default variant of the rule, unless it failed or the analysis is to talk (QTOS_DEBUG_SYMBOLIC*, QTOS_DUMP_FIRST)
+};
+static std::vector<Candidate> order_candidates(const QtosParams &params, const QtosEnv &env, int rules_mask) {
+  QtosEnv quiet = env;
+  quiet.debug = 0; quiet.dump_first.clear();
+  const bool keep = !env.debug && env.dump_first.empty();
+  bool reduced = true;
+  auto analyse = [&](int rule) {
+    Candidate c = {rule, 0, 0, 0, false, std::make_unique<Analysis>()};
+    c.ok = build_analysis(*c.A, params, quiet, rule) == 0;
+    if (c.ok) { c.front = c.A->S.front; c.stages = c.A->S.n_stages; c.cont = c.A->S.n_continuation() > 0; }
+    reduced = c.A->M.reduce_base != 0;
+    if (!c.ok || !keep) c.A.reset();
+    return c;
+  };
+  std::vector<Candidate> out;
+  if (env.order >= 0) { out.push_back(analyse(env.order)); return out; }
   // (rules 1 and 2 move the B-spline coefficients of the reduced base: without it -- every base row in the system, the
   //  configuration the internals' tests pin -- the order of rounds 1 - 5 stays)
-  if (!params.reduce_base) return 0;
-  QtosEnv quiet = env;   // (the candidates do not talk)
-  quiet.debug = 0; quiet.dump_first.clear();
-  Analysis cand;
-  int best = 2, best_front = 1 << 30, best_stages = 1 << 30, best_cont = 1 << 30;
-  for (int rule : {2, 1}) {
-    if (build_analysis(cand, params, quiet, rule)) continue;
-    if (!cand.M.reduce_base) { built = false; return 0; }   // (the model kept the full base: a short horizon or unequal polynomial durations)
-    const Symbolic &S = cand.S;
-    const int cont = S.n_continuation() > 0;
-    if (S.front < best_front || (S.front == best_front && (S.n_stages < best_stages || (S.n_stages == best_stages && cont < best_cont)))) {
-      best = rule; best_front = S.front; best_stages = S.n_stages; best_cont = cont;
-      std::swap(won, cand);
-      built = true;
-    }
+  if (!params.reduce_base) { out.push_back(analyse(0)); return out; }
+  const int mask = (rules_mask & 7) ? (rules_mask & 7) : 6;
+  for (int rule : {2, 1, 0}) {
+    if (!((mask >> rule) & 1)) continue;
+    Candidate c = analyse(rule);
+    // (the model kept the full base, a short horizon or unequal polynomial durations: rule 0 alone)
+    if (c.ok && !reduced) { out.clear(); out.push_back(analyse(0)); return out; }
+    out.push_back(std::move(c));
   }
-  if (env.debug) fprintf(stderr, "qtos: elimination order rule %d (front %d, %d stages)\n", best, best_front, best_stages);
-  built = built && !env.debug && env.dump_first.empty();
-  return best;
+  std::stable_sort(out.begin(), out.end(), [](const Candidate &a, const Candidate &b) {   // (stable: 2 before 1 before 0 among equals)
+    return std::make_tuple(!a.ok, a.front, a.stages, a.cont) < std::make_tuple(!b.ok, b.front, b.stages, b.cont);
+  });
+  return out;
+}
+// The rule a planner runs and qtos_analyze* describes: the first candidate of the automatic mask.  `won` takes its analysis
+// where the candidate kept it (`built`); the caller builds the others, which then talk or say why they fail.
+static int pick_order_rule(const QtosParams &params, const QtosEnv &env, Analysis &won, bool &built) {
+  std::vector<Candidate> c = order_candidates(params, env, 0);
+  if (env.debug && c.size() > 1) fprintf(stderr, "qtos: elimination order rule %d (front %d, %d stages)\n", c[0].rule, c[0].front, c[0].stages);
+  built = c[0].A != nullptr;
+  if (built) won = std::move(*c[0].A);
+  return c[0].rule;
 }
 
 // What the qtos_analyze* entry points describe: the default variant, whatever a planner would run
@@ -367,436 +388,9 @@ __global__ void k_debug_eval(DevPlan P, DevWork W, int B);
 
 const char *qtos_last_error(const QtosPlanner *p) { return p ? p->err.c_str() : "null planner"; }
 
-void qtos_planner_destroy(QtosPlanner *p) {
-  if (!p) return;
-  (void)hipSetDevice(p->device);
-  for (void *a : p->allocs) (void)hipFree(a);
-  for (auto &L : p->lanes) {
-    for (hipEvent_t e : L.ev) (void)hipEventDestroy(e);
-    if (L.h_active) (void)hipHostFree(L.h_active);
-    if (L.own) (void)hipStreamDestroy(L.own);
-    if (L.side) (void)hipStreamDestroy(L.side);
-    for (hipEvent_t e : {L.ev_fork, L.ev_join, L.ev_done})
-      if (e) (void)hipEventDestroy(e);
-  }
-  if (p->ev_in) (void)hipEventDestroy(p->ev_in);
-  for (void *q : {(void *)p->d_table, (void *)p->d_tab_dx, (void *)p->d_tab_dy, (void *)p->d_height})
-    if (q) (void)hipFree(q);
-  if (p->ev_height) (void)hipEventDestroy(p->ev_height);
-  if (p->own_stream) (void)hipStreamDestroy(p->own_stream);
-  if (p->d_totals) (void)hipFree(p->d_totals);
-  delete p;
-}
+void qtos_planner_destroy(QtosPlanner *p) { if (p) delete p; }
 
-// The rows of the inequality blocks for the helper waves of the backward sweep (sweep_backward): a block belongs to the stage
-// of its earliest column; rounds of SW_ROUND rows (one helper wave), round i in step i of the chain (stage NS - 1 - i): a
-// stage's rounds come behind the step that solves it, in the order the chain meets the stages.  Returns the number of
-// rounds (0: the tables cannot be built for this plan).
-static int build_sweep_tasks(const HostModel &M, const Symbolic &S, std::vector<SwTask> &tasks, std::vector<int> &cpos, std::vector<int> &c16) {
-  const int NS = S.n_stages;
-  std::vector<std::vector<SwTask>> by_stage(NS);
-  bool ok = true;
-  for (const Block &b : M.blocks) {
-    if (b.kind != 1) continue;
-    int mn = INT_MAX;
-    const int c0 = (int)cpos.size();
-    for (int a = 0; a < b.n; ++a) {
-      const int pos = S.var_pos[M.block_cols[b.col_off + a]];
-      if (pos < 0) ok = false;
-      cpos.push_back(std::max(pos, 0));
-      mn = std::min(mn, pos);
-    }
-    if (mn < 0 || mn / PIV >= NS) { ok = false; continue; }
-    const int k0 = (int)c16.size(), n4 = b.n & ~3;
-    auto at = [&](int e) { return (unsigned)cpos[c0 + e] & 0xffffu; };
-    for (int q = 0; q < 4; ++q)
-      for (int u = 0; u < SW_RU; u += 2) {
-        const int e0 = std::max(std::min(q + 4 * u, n4 - 4 + q), 0), e1 = std::max(std::min(q + 4 * (u + 1), n4 - 4 + q), 0);
-        c16.push_back((int)(at(std::min(e0, b.n - 1)) | (at(std::min(e1, b.n - 1)) << 16)));
-      }
-    {
-      const int r0 = std::min(n4, b.n - 1), r1 = std::min(n4 + 1, b.n - 1), r2 = std::min(n4 + 2, b.n - 1);
-      c16.push_back((int)(at(r0) | (at(r1) << 16)));
-      c16.push_back((int)at(r2));
-      c16.push_back(0); c16.push_back(0);
-    }
-    for (int r = 0; r < b.m; ++r) by_stage[mn / PIV].push_back({b.goff + r * b.n, b.n, b.row0 + r, k0, c0, {0, 0, 0}});
-  }
-  if ((size_t)NS * PIV > 65535) ok = false;
-  const SwTask none = {0, 4, -1, 0, 0, {0, 0, 0}};
-  int step = 0;
-  auto round_of = [&](const SwTask *t, int cnt) {
-    for (int i = 0; i < SW_ROUND; ++i) tasks.push_back(i < cnt ? t[i] : none);
-    ++step;
-  };
-  for (int u = NS - 1; u >= 0 && ok; --u) {
-    while (step < NS - u) round_of(nullptr, 0);   // (x of stage u is complete behind the barrier of step NS - 1 - u)
-    for (size_t i = 0; i < by_stage[u].size(); i += SW_ROUND) round_of(by_stage[u].data() + i, (int)std::min<size_t>(SW_ROUND, by_stage[u].size() - i));
-  }
-  const int nstep = ((NS + SWD - 1) / SWD) * SWD;
-  while (step < nstep) round_of(nullptr, 0);
-  if (cpos.empty()) cpos.push_back(0);
-  while (c16.size() < 20) c16.push_back(0);
-  if (S.env.debug) {
-    size_t mx = 0, tot = 0;
-    for (auto &v : by_stage) { mx = std::max(mx, v.size()); tot += v.size(); }
-    fprintf(stderr, "qtos: sweep ds: %d rounds for %d stages (chain %d steps), %zu rows, most in a stage %zu; rows by stage:", step, NS, nstep, tot, mx);
-    for (auto &v : by_stage) fprintf(stderr, " %zu", v.size());
-    fprintf(stderr, "\n");
-  }
-  return ok ? step : 0;
-}
-
-// The planner of qtos_planner_create (order_rule < 0: the automatic choice / QTOS_ORDER) and of the candidates of
-// qtos_planner_create_checked (order_rule >= 0), under the environment `env0` as the caller parsed it.
-static int create_planner(const QtosParams *params, int max_batch, int device, const QtosEnv &env0, int order_rule, QtosPlanner **out, Analysis *pre = nullptr) {
-  if (!params || !out || max_batch < 1 || max_batch >= (1 << 24)) return -1;   // (the count words of k_post_counts hold 24 bits per count)
-  *out = nullptr;
-  QtosPlanner *p = new QtosPlanner();
-  p->device = device;
-  p->max_batch = max_batch;
-  p->env = env0;
-  const QtosEnv &env = p->env;
-  p->spec_pattern = env.spec_pattern != 0;
-  if (choose_kernel(*params, env, p->kkt, *p, order_rule, pre)) { delete p; return -1; }
-  const HostModel &M = p->M;
-  const Symbolic &S = p->S;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= device) {
-    fprintf(stderr, "qtos: no HIP device %d (found %d) -- the planner has no CPU fallback\n", device, ndev);
-    delete p;
-    return -2;
-  }
-  int rc = 0;
-#define TRY(x) do { if ((rc = (x))) { fprintf(stderr, "qtos: %s\n", p->err.c_str()); qtos_planner_destroy(p); return rc; } } while (0)
-  {
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) { delete p; return -2; }
-  }
-  DevPlan &D = p->dp;
-  std::memset(&D, 0, sizeof(D));
-  D.n_vars = M.n_vars; D.n_cons = M.n_cons; D.n_stages = S.n_stages; D.front = S.front;
-  D.n_sol = M.n_sol; D.n_rec = (int)M.rec_var.size();
-  {  // k_step writes a recovered node step next to the coefficient steps it is formed from: the two sets must not meet
-    std::vector<char> is_rec(M.n_sol, 0);
-    for (int v : M.rec_var) is_rec[v] = 1;
-    for (int c : M.rec_col)
-      if (c >= 0 && is_rec[c]) { p->err = "reduced base: a recovered node value is the source of another"; fprintf(stderr, "qtos: %s\n", p->err.c_str()); delete p; return -1; }
-  }
-  TRY(p->upload(M.rec_var, &D.rec_var)); TRY(p->upload(M.rec_col, &D.rec_col)); TRY(p->upload(M.rec_w, &D.rec_w));
-  D.n_coef = M.reduce_base ? M.n_coef : 0; D.n_pz = (int)M.pz_var.size();
-  TRY(p->upload(M.pc_var, &D.pc_var)); TRY(p->upload(M.pc_w, &D.pc_w));
-  D.n_psw = (int)M.psw_var.size();
-  TRY(p->upload(M.psw_var, &D.psw_var)); TRY(p->upload(M.psw_src, &D.psw_src)); TRY(p->upload(M.psw_w, &D.psw_w));
-  TRY(p->upload(M.pz_var, &D.pz_var)); TRY(p->upload(M.pz_col, &D.pz_col)); TRY(p->upload(M.pz_w, &D.pz_w));
-  D.n_dyn = (int)M.dyn.size(); D.n_rom = (int)M.rom.size(); D.n_terr = (int)M.terr.size();
-  D.n_force = (int)M.force.size(); D.n_lin = (int)M.linrow.size(); D.n_blocks = (int)M.blocks.size();
-  TRY(p->upload(M.dyn, &D.dyn)); TRY(p->upload(M.rom, &D.rom));
-  {  // flat tables of the spline inputs in pre-pass order (the VecIn records lead the instance structs)
-    auto flat = [&](const void *inst0, size_t inst_bytes, size_t n_inst, int n_vec, const i4_t **var, const d2_t **wa, const d2_t **wb) {
-      std::vector<i4_t> v;
-      std::vector<d2_t> a, b;
-      for (size_t i = 0; i < n_inst; ++i)
-        for (int k = 0; k < n_vec; ++k) {
-          const VecIn &in = ((const VecIn *)((const char *)inst0 + i * inst_bytes))[k];
-          for (int d = 0; d < 3; ++d) {
-            v.push_back(i4_t{in.var[d], in.var[3 + d], in.var[6 + d], in.var[9 + d]});
-            a.push_back(d2_t{in.w[0], in.w[1]});
-            b.push_back(d2_t{in.w[2], in.w[3]});
-          }
-        }
-      int rc2 = p->upload(v, var);
-      if (!rc2) rc2 = p->upload(a, wa);
-      if (!rc2) rc2 = p->upload(b, wb);
-      return rc2;
-    };
-    static_assert(DYN_VIN == 39 && ROM_VIN == 9, "13 / 3 input vectors of three components");
-    TRY(flat(M.dyn.data(), sizeof(DynInst), M.dyn.size(), 13, &D.pre_dyn_var, &D.pre_dyn_wa, &D.pre_dyn_wb));
-    TRY(flat(M.rom.data(), sizeof(RomInst), M.rom.size(), 3, &D.pre_rom_var, &D.pre_rom_wa, &D.pre_rom_wb));
-  }
-  TRY(p->upload(M.force, &D.force)); TRY(p->upload(M.linrow, &D.lin));
-  {  // entry lists of the iterate-dependent Jacobian values, packed (model.hpp: PackedTerm1 / PackedTerm3)
-    std::map<unsigned long long, int> idx_of;
-    std::vector<double> coefs;
-    bool fits = true;
-    auto ci = [&](double a) {
-      unsigned long long bits;
-      std::memcpy(&bits, &a, 8);
-      auto it = idx_of.find(bits);
-      if (it == idx_of.end()) { it = idx_of.emplace(bits, (int)coefs.size()).first; coefs.push_back(a); }
-      return (unsigned short)it->second;
-    };
-    auto off16 = [&](int off) { if (off < 0 || off > 65535) fits = false; return (unsigned short)off; };
-    std::vector<PackedTerm1> d1, r1;
-    std::vector<PackedTerm3> d3;
-    for (const LinTerm1 &t : S.dyn_t1) d1.push_back({(unsigned)t.pos, off16(t.off), ci(t.a)});
-    for (const LinTerm1 &t : S.rom_t1) r1.push_back({(unsigned)t.pos, off16(t.off), ci(t.a)});
-    for (const LinTerm3 &t : S.dyn_t3)
-      d3.push_back({(unsigned)t.pos, {off16(t.off[0]), off16(t.off[1]), off16(t.off[2])}, {ci(t.a[0]), ci(t.a[1]), ci(t.a[2])}});
-    if (!fits || coefs.size() > 65535) {
-      p->err = "Jacobian entry lists exceed the packed format (16-bit offsets / coefficient indices)";
-      fprintf(stderr, "qtos: %s\n", p->err.c_str());
-      qtos_planner_destroy(p);
-      return -4;
-    }
-    D.n_lin_coef = (int)coefs.size();
-    TRY(p->upload(d1, &D.dyn_t1)); TRY(p->upload(d3, &D.dyn_t3)); TRY(p->upload(r1, &D.rom_t1)); TRY(p->upload(coefs, &D.lin_coef));
-  }
-  TRY(p->upload(S.dyn_t1_off, &D.dyn_t1_off)); TRY(p->upload(S.dyn_t3_off, &D.dyn_t3_off));
-  D.n_rom_t1 = (int)S.rom_t1.size();
-  D.dyn_chunk = M.dyn_chunk;
-  D.rom_chunk = S.rom_chunk;
-  TRY(p->upload(S.rom_t1_off, &D.rom_t1_off));
-  TRY(p->upload(S.amask, &D.amask));
-  TRY(p->upload(S.amask2, &D.amask2));
-  TRY(p->upload(S.nxt_pack, &D.nxt_pack));
-  TRY(p->upload(S.ctab, &D.ctab));
-  TRY(p->upload(S.rtab, &D.rtab));
-  TRY(p->upload(S.rhs_ptr, &D.rhs_ptr)); TRY(p->upload(S.rhs_gpos, &D.rhs_gpos)); TRY(p->upload(S.rhs_row, &D.rhs_row));
-  TRY(p->upload(S.kx_ptr, &D.kx_ptr)); TRY(p->upload(S.kx_col, &D.kx_col)); TRY(p->upload(S.kx_pos, &D.kx_pos));
-  D.n_unknowns = S.n_unknowns;
-  D.chord_tol = M.P.chord_tol;
-  D.chord_max = M.P.chord_max > 0 ? M.P.chord_max : 1;
-  D.chord_shrink = M.P.chord_shrink > 0 ? M.P.chord_shrink : 1.0 / 3.0;
-  D.n_cells = S.n_cells;
-  D.n_cont = S.n_continuation();
-  D.table = nullptr; D.tab_dx = D.tab_dy = nullptr; D.tab_ndx = D.tab_ndy = 0;
-  D.off_lin = M.off_lin; D.off_ang = M.off_ang;
-  for (int e = 0; e < NEE; ++e) D.off_eem[e] = M.off_eem[e];
-  TRY(p->upload(S.cont, &D.cont));
-  {  // terrain rows with their stream positions: the row's Jacobian entries, and the pivot diagonals of the foot node's x and
-     // y (two-phase solve: stance rows only)
-    std::vector<int> dpos_of_var(M.n_sol, -1);
-    for (int i = 0; i < (int)S.pack_src.size(); ++i)
-      if ((S.pack_src[i] >> 28) == 5) {
-        const int u = S.piv_unknown[S.pack_src[i] & 0x0fffffff];
-        if (u >= 0 && u < M.n_sol) dpos_of_var[u] = i;
-      }
-    std::vector<TerrDev> td;
-    for (const TerrInst &t : M.terr) {
-      TerrDev d = {t.vx, t.vy, t.vz, t.row, -1, -1, -1, -1, -1, 0, 0.0, 0.0};
-      if (t.in_kkt) {
-        const bool stance = M.row_kind[t.row] == 1;   // equality block: entries at their own stream positions
-        auto pos = [&](int c) { return c < 0 ? -1 : (stance ? S.eq_pos[t.goff + c] : t.goff + c); };
-        d.px = pos(t.cx); d.py = pos(t.cy); d.pz = pos(t.cz);
-        if (M.P.hold_from > 0 && stance) {
-          d.d0 = dpos_of_var[t.vx]; d.d1 = dpos_of_var[t.vy];
-          d.ex = M.sol_diag[t.vx] - M.P.delta_x; d.ey = M.sol_diag[t.vy] - M.P.delta_x;
-        }
-      }
-      td.push_back(d);
-    }
-    TRY(p->upload(td, &D.terr));
-    D.hold_from = M.P.hold_from;
-    D.spec_jac = env.spec_jac;
-    D.hold_weight = M.P.hold_weight > 0 ? M.P.hold_weight : 1e6;
-    D.hold_tol = M.P.hold_tol;
-  }
-  TRY(p->upload(M.blocks, &D.blocks)); TRY(p->upload(M.block_cols, &D.block_cols));
-  {
-    std::vector<IqRow> rows;   // blocks carry their stream offsets once the symbolic analysis has run
-    for (const Block &b : M.blocks)
-      if (b.kind == 1)
-        for (int r = 0; r < b.m; ++r) rows.push_back({b.goff + r * b.n, b.n, b.col_off, b.row0 + r});
-    D.n_iq_rows = (int)rows.size();
-    TRY(p->upload(rows, &D.iq_rows));
-  }
-  {
-    std::vector<SwTask> tasks;
-    std::vector<int> cpos, c16;
-    D.sw_steps = build_sweep_tasks(M, S, tasks, cpos, c16);
-    const bool ok = D.sw_steps > 0;
-    D.sw_on = ok && D.n_iq_rows > 0 && S.front / PIV < SW_W0 && env.sweep_ds != 0;   // (waves 13 .. 15 must be without rows)
-    TRY(p->upload(tasks, &D.sw_tasks)); TRY(p->upload(cpos, &D.sw_cpos)); TRY(p->upload(c16, &D.sw_c16));
-  }
-  {
-    std::vector<int> iq, eq;
-    std::vector<double> lo, hi;
-    for (int r = 0; r < M.n_cons; ++r) {
-      if (M.row_kind[r] == 2) { iq.push_back(r); lo.push_back(M.con_lo[r]); hi.push_back(M.con_hi[r]); }
-      else if (M.row_kind[r] == 1) eq.push_back(r);
-    }
-    D.n_iq = (int)iq.size(); D.n_eqw = (int)eq.size();
-    TRY(p->upload(iq, &D.iq_idx)); TRY(p->upload(eq, &D.eq_idx));
-    TRY(p->upload(lo, &D.iq_lo)); TRY(p->upload(hi, &D.iq_hi));
-  }
-  TRY(p->upload(M.g_static, &D.g_static));
-  TRY(p->upload(S.piv_slot, &D.piv_slot)); TRY(p->upload(S.piv_unknown, &D.piv_unknown));
-  TRY(p->upload(S.piv_diag, &D.piv_diag)); TRY(p->upload(S.stages, &D.stages));
-  TRY(p->upload(S.eq_entries, &D.eq_entries)); TRY(p->upload(S.eq_rhs, &D.eq_rhs));
-  TRY(p->upload(S.iq_blocks, &D.iq_blocks)); TRY(p->upload(S.iq_slots, &D.iq_slots));
-  TRY(p->upload(M.con_lo, &D.con_lo)); TRY(p->upload(M.con_hi, &D.con_hi));
-  TRY(p->upload(M.row_kind, &D.row_kind)); TRY(p->upload(M.init, &D.init));
-  TRY(p->upload(M.node_time, &D.var_time));   // (node times, not the order's keys: model.hpp node_time)
-  D.max_stage_g = S.max_stage_g;
-  TRY(p->upload(S.srec, &D.srec)); TRY(p->upload(S.srec_off, &D.srec_off));
-  TRY(p->upload(S.pack_src, &D.pack_src)); TRY(p->upload(S.drec_off, &D.drec_off));
-  TRY(p->upload(S.diag_pos, &D.diag_pos));
-  TRY(p->upload(S.pair_groups, &D.pair_groups));
-  TRY(p->upload(S.eq_pos, &D.eq_pos)); TRY(p->upload(S.rhs_pos, &D.rhs_pos));
-  TRY(p->upload(S.sig_pos, &D.sig_pos)); TRY(p->upload(S.w_pos, &D.w_pos));
-  D.max_srec = S.max_srec; D.max_drec = S.max_drec; D.stream_len = (int)S.pack_src.size();
-  D.mass = M.P.mass; D.gravity = M.P.gravity; D.mu_fric = M.P.mu; D.f_max = M.P.f_max; D.T = M.T;
-  for (int i = 0; i < 9; ++i) D.Ib[i] = M.P.inertia_b[i];
-  for (int e = 0; e < NEE; ++e)
-    for (int d = 0; d < 3; ++d) D.nominal[e][d] = M.P.nominal_stance[e][d];
-  D.tol = M.P.tol; D.mu_init = M.P.mu_init; D.mu_min = M.P.mu_min; D.delta_x = M.P.delta_x;
-  D.mu_superlinear = M.P.mu_superlinear != 0;
-  D.eps_dual = M.P.eps_dual; D.max_iter = M.P.max_iter; D.stall_iters = M.P.stall_iters; D.stall_alpha = M.P.stall_alpha;
-  D.slack_push = M.P.slack_push > 0 ? M.P.slack_push : 0.01;
-  D.warm_slack_push = M.P.warm_slack_push > 0 ? M.P.warm_slack_push : 0.01;
-  D.terrain_mode = M.P.terrain_mode;
-  D.g_doubles = S.g_doubles;
-  D.panel_stride = (long long)S.n_stages * (S.front + 1) * PIV;
-  // LDS budget of k_kkt
-  const int F = S.front;
-  p->kkt_lds = kkt_lds_bytes(p->kkt, S);
-  if (p->kkt == Kkt::kkt5 && F > 128) D.sw_on = 0;   // (nine tile waves of twelve: fewer than three helper waves are left)
-  if (D.sw_on) {
-    // the helper waves' tables of the backward sweep (solution by position, rounds) behind the sweep's own: within the LDS
-    // the forward pass needs anyway, or the kernel's allocation grows up to the limit; beyond that k_step forms ds itself
-    const size_t need = (p->kkt == Kkt::kkt5 ? kkt5_sweep_base_bytes(F, S.n_stages) : kkt2_sweep_base_bytes(F, S.n_stages)) + sweep_ds_lds_bytes(S.n_stages, D.sw_steps);
-    if (need > LDS_LIMIT || chord_lds_bytes(S.n_stages, D.sw_steps) > 96 * 1024) D.sw_on = 0;
-    else p->kkt_lds = std::max(p->kkt_lds, need);
-  }
-  p->kkt_threads = p->kkt == Kkt::kkt5 ? KT5 : KT2;
-  const int max_front = 208;
-  if (p->kkt != Kkt::kkt5 && (S.max_drec > 2 * 2 * KT || S.max_srec > 3 * 4 * KT || F > max_front || (S.pack_src.size() & 1))) {
-    p->err = "stage record exceeds the prefetch registers";
-    fprintf(stderr, "qtos: stage records too long (%d doubles, %d ints) or front %d > %d\n", S.max_drec, S.max_srec, F, max_front);
-    qtos_planner_destroy(p);
-    return -4;
-  }
-  if (env.debug) fprintf(stderr, "qtos: front %d, k_kkt LDS %zu B\n", F, p->kkt_lds);
-  if (p->kkt_lds > LDS_LIMIT) {
-    p->err = "front too large for LDS";
-    fprintf(stderr, "qtos: front %d needs %zu B of LDS\n", F, p->kkt_lds);
-    qtos_planner_destroy(p);
-    return -4;
-  }
-  {
-    switch (p->kkt) {
-      case Kkt::kkt5: p->kkt_fn = kkt5_kernel(F); break;
-      case Kkt::kkt3: p->kkt_fn = kkt3_kernel(F); break;
-      case Kkt::kkt2: p->kkt_fn = kkt2_kernel(F, D.n_cont > 0); break;
-    }
-    p->chord_fn = chord_kernel(F);
-    if (!p->kkt_fn) { p->err = "no k_kkt instantiation for this front size"; qtos_planner_destroy(p); return -4; }
-    hipError_t e = hipFuncSetAttribute((const void *)p->kkt_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->kkt_lds);
-    if (e != hipSuccess) { p->err = std::string("hipFuncSetAttribute: ") + hipGetErrorString(e); fprintf(stderr, "qtos: %s\n", p->err.c_str()); qtos_planner_destroy(p); return -2; }
-    if (p->chord_fn && D.sw_on) {
-      e = hipFuncSetAttribute((const void *)p->chord_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)chord_lds_bytes(S.n_stages, D.sw_steps));
-      if (e != hipSuccess) { p->err = std::string("hipFuncSetAttribute: ") + hipGetErrorString(e); fprintf(stderr, "qtos: %s\n", p->err.c_str()); qtos_planner_destroy(p); return -2; }
-    }
-  }
-  p->eval_lds = sizeof(double) * (((size_t)M.n_sol + 1) / 2 * 2 + std::max((size_t)DYN_LOC * D.dyn_chunk, (size_t)ROM_LOC * D.rom_chunk) +
-                                  std::max((size_t)DYN_VIN * D.dyn_chunk, (size_t)ROM_VIN * D.rom_chunk));
-  // the coefficient table of the entry lists joins the scratch when it fits (schedules with irregular phase durations have
-  // ten thousand distinct Hermite weights: those read it from memory)
-  D.coef_in_lds = p->eval_lds + sizeof(double) * (size_t)D.n_lin_coef <= 150 * 1024;
-  if (D.coef_in_lds) p->eval_lds += sizeof(double) * (size_t)D.n_lin_coef;
-  {  // k_step's pass over the chord right-hand side: unknown sums and list bounds, then the factors of rhs_chunk entries
-    D.n_rhs_ent = (int)S.rhs_gpos.size();
-    const size_t nuk = (size_t)S.n_unknowns, fixed = ((nuk + 1) & ~(size_t)1) + ((nuk + 4) & ~(size_t)3) / 2;
-    const size_t room = 150 * 1024 / sizeof(double) > fixed ? (150 * 1024 / sizeof(double) - fixed) / (2 * (size_t)ET) : 0;   // passes of ET entries that fit
-    D.rhs_chunk = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>((D.n_rhs_ent + ET - 1) / ET, 12), room)) * ET;
-    p->eval_lds = std::max(p->eval_lds, (fixed + 2 * (size_t)D.rhs_chunk) * sizeof(double));
-  }
-  if (p->eval_lds > 150 * 1024) {
-    p->err = "too many dynamics knots for the LDS scratch";
-    fprintf(stderr, "qtos: evaluation kernels need %zu B of LDS\n", p->eval_lds);
-    qtos_planner_destroy(p);
-    return -4;
-  }
-  for (const void *fn : {(const void *)k_start, (const void *)k_step, (const void *)k_debug_eval})
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->eval_lds) != hipSuccess) { qtos_planner_destroy(p); return -2; }
-  // (k_probe: the widest map the checks of probe_args admit, one row of 16384 columns, needs a little more than 64 KiB)
-  if (hipFuncSetAttribute((const void *)k_probe, hipFuncAttributeMaxDynamicSharedMemorySize, (int)probe_lds_bytes(1, PP_GRID)) != hipSuccess) { qtos_planner_destroy(p); return -2; }
-  // sampling tables
-  SamplePlan &SP = p->sp;
-  std::memset(&SP, 0, sizeof(SP));
-  SP.n_vars = M.n_vars; SP.T = M.T;
-  TRY(upload_spline(p, M.lin, &SP.lin)); TRY(upload_spline(p, M.ang, &SP.ang));
-  for (int e = 0; e < NEE; ++e) { TRY(upload_spline(p, M.eem[e], &SP.eem[e])); TRY(upload_spline(p, M.eef[e], &SP.eef[e])); }
-  TRY(p->alloc(&p->d_sp, 1));
-  HIPCHK(p, hipMemcpy(p->d_sp, &SP, sizeof(SP), hipMemcpyHostToDevice));
-  for (int e = 0; e < NEE; ++e) {   // a stance polynomial of a foot's motion: neither of its nodes has a velocity variable
-    std::vector<int> stance(M.eem[e].n_polys);
-    for (int k = 0; k < M.eem[e].n_polys; ++k) stance[k] = M.eem[e].idx[k][3] < 0 && M.eem[e].idx[k + 1][3] < 0;
-    TRY(p->upload(stance, &p->d_stance[e]));
-  }
-  // workspaces
-  DevWork &W = p->wk;
-  std::memset(&W, 0, sizeof(W));
-  const size_t Bm = (size_t)max_batch, n = M.n_vars, m = M.n_cons;
-  TRY(p->alloc(&W.x, Bm * n)); TRY(p->alloc(&W.dx, Bm * (size_t)M.n_sol));
-  TRY(p->alloc(&W.g, Bm * m)); TRY(p->alloc(&W.gt, Bm * m)); TRY(p->alloc(&W.s, Bm * m));
-  TRY(p->alloc(&W.zl, Bm * m)); TRY(p->alloc(&W.zu, Bm * m)); TRY(p->alloc(&W.ds, Bm * m));
-  TRY(p->alloc(&W.dzl, Bm * m)); TRY(p->alloc(&W.dzu, Bm * m)); TRY(p->alloc(&W.sig, Bm * m));
-  TRY(p->alloc(&W.w, Bm * m));
-  TRY(p->alloc(&W.panel, Bm * (size_t)D.panel_stride));
-  TRY(p->alloc(&W.stream, Bm * (size_t)S.pack_src.size() + 64));   // (+ 64: the helper waves of the sweep read whole groups of a row's entries, sw_load)
-  {  // constants of the stream (static Jacobian values, pivot diagonals): written once per problem
-    std::vector<double> one(S.pack_src.size(), 0.0);
-    for (size_t i = 0; i < S.const_pos.size(); ++i) one[S.const_pos[i]] = S.const_val[i];
-    for (size_t b = 0; b < Bm; ++b)
-      HIPCHK(p, hipMemcpy(W.stream + b * one.size(), one.data(), one.size() * sizeof(double), hipMemcpyHostToDevice));
-  }
-  TRY(p->alloc(&W.mu, Bm)); TRY(p->alloc(&W.viol, Bm));
-  TRY(p->alloc(&W.best_viol, Bm)); TRY(p->alloc(&W.best_it, Bm)); TRY(p->alloc(&W.xbest, Bm * n));
-  TRY(p->alloc(&W.held, Bm));
-#ifdef QTOS_STAMPS
-  if (M.P.max_iter < 79) { p->err = "diagnostic build (QTOS_STAMPS) parks its stamps in trace rows 16..79: create the planner with max_iter >= 79"; fprintf(stderr, "qtos: %s\n", p->err.c_str()); qtos_planner_destroy(p); return -1; }
-#endif
-  TRY(p->alloc(&W.trace, Bm * (size_t)(M.P.max_iter + 1) * 4));
-  TRY(p->alloc(&W.hist, Bm * (size_t)(M.P.max_iter + 1) * HIST_COLS)); TRY(p->alloc(&W.rep, Bm * (size_t)REP_COLS));
-  TRY(p->alloc(&W.status, Bm)); TRY(p->alloc(&W.iters, Bm)); TRY(p->alloc(&W.done, Bm));
-  TRY(p->alloc(&W.n_active, 4 * 4));   // four counters per lane
-  TRY(p->alloc(&W.chord, Bm));
-  TRY(p->alloc(&W.chord_run, Bm));
-  TRY(p->alloc(&W.jam, Bm));
-  TRY(p->alloc(&W.rhs, Bm * (size_t)S.n_unknowns));
-  TRY(p->alloc(&W.minv, Bm * (size_t)S.n_stages * PIV * PIV));
-  TRY(p->alloc(&W.sol, Bm * (size_t)S.n_stages * PIV)); TRY(p->alloc(&W.sol0, Bm * (size_t)S.n_stages * PIV));
-  TRY(p->alloc(&W.dx0, Bm * (size_t)M.n_sol)); TRY(p->alloc(&W.ur, Bm * m));
-  TRY(p->alloc(&p->d_start, Bm * QTOS_START_DOUBLES)); TRY(p->alloc(&p->d_goal, Bm * 3));
-  TRY(p->alloc(&p->d_nodes, Bm * n)); TRY(p->alloc(&p->d_warm, Bm * n)); TRY(p->alloc(&p->d_map, Bm));
-  if (hipStreamCreateWithFlags(&p->own_stream, hipStreamNonBlocking) != hipSuccess) { qtos_planner_destroy(p); return -2; }
-  if (hipMalloc(&p->d_totals, 2 * sizeof(long long)) != hipSuccess || hipMemset(p->d_totals, 0, 2 * sizeof(long long)) != hipSuccess) { qtos_planner_destroy(p); return -3; }
-  p->last_stream = p->own_stream;
-  // launch slots of a call: its iterations plus the launches some problem sat out (at most one per blind slot)
-  p->max_slots = 2 * M.P.max_iter + 2;
-  {  // lanes: one per part of a call that is larger than the GPU -- QTOS_LANES: at most that many; default ONE: measured at 1024
-     // problems per call (round 4, profiles/r04_lanes.txt), parts that start together also reach their stragglers together, and
-     // four lock-step loops of 256 pay four tails where one loop of 1024 pays one (exp_5 75.8 K plans/s on four lanes, 84.0 K
-     // on two, 84.2 K on one)
-    int cus = 256;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus < 1) cus = 256;
-    p->lane_chunk = cus;
-    const int want = env.lanes;
-    const int n_lanes = std::max(1, std::min(want, (max_batch + cus - 1) / cus));
-    p->lanes.resize(n_lanes);
-    if (hipEventCreateWithFlags(&p->ev_in, hipEventDisableTiming) != hipSuccess) { qtos_planner_destroy(p); return -2; }
-    for (int j = 0; j < n_lanes; ++j) {
-      QtosPlanner::Lane &L = p->lanes[j];
-      if (hipHostMalloc((void **)&L.h_active, 4 * sizeof(int) * ((size_t)p->max_slots + 1), hipHostMallocMapped) != hipSuccess) { qtos_planner_destroy(p); return -3; }
-      if (hipHostGetDevicePointer((void **)&L.h_active_dev, L.h_active, 0) != hipSuccess) { qtos_planner_destroy(p); return -2; }
-      L.was_kkt.assign(p->max_slots + 1, 0);
-      L.was_chord.assign(p->max_slots + 1, 0);
-      L.d_n_active = W.n_active + 4 * j;
-      if (j > 0 && hipStreamCreateWithFlags(&L.own, hipStreamNonBlocking) != hipSuccess) { qtos_planner_destroy(p); return -2; }
-      if (hipStreamCreateWithFlags(&L.side, hipStreamNonBlocking) != hipSuccess) { qtos_planner_destroy(p); return -2; }
-      if (hipEventCreateWithFlags(&L.ev_fork, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&L.ev_join, hipEventDisableTiming) != hipSuccess ||
-          hipEventCreateWithFlags(&L.ev_done, hipEventDisableTiming) != hipSuccess) { qtos_planner_destroy(p); return -2; }
-      L.ev.resize(5 * (size_t)p->max_slots + 3);
-      for (auto &e : L.ev)
-        if (hipEventCreate(&e) != hipSuccess) { qtos_planner_destroy(p); return -2; }
-    }
-  }
-#undef TRY
-  *out = p;
-  return 0;
-}
+#include "planner_create.hpp"
 
 int qtos_planner_create(const QtosParams *params, int max_batch, int device, QtosPlanner **out) {
   return create_planner(params, max_batch, device, QtosEnv::parse(), -1, out);   // (a planner reads the environment here, or in qtos_planner_create_checked)
@@ -2030,47 +1624,6 @@ int qtos_planner_selftest(QtosPlanner *p, unsigned long long seed, double tol_re
   return 0;
 }
 
-// The order rules qtos_planner_create_checked would try, in the order it would try them (include/qtos_planner.h).  A rule whose
-// analysis fails comes last with front 0.
-struct Candidate {
-  int rule, front, stages, cont;
-  bool ok;
-  std::unique_ptr<Analysis> A;   // the default variant of the rule (create_planner takes it), unless the analysis is to talk
-};
-static std::vector<Candidate> order_candidates(const QtosParams &params, const QtosEnv &env, int rules_mask) {
-  QtosEnv quiet = env;
-  quiet.debug = 0; quiet.dump_first.clear();
-  const bool keep = !env.debug && env.dump_first.empty();
-  bool reduced = true;
-  auto analyse = [&](int rule) {
-    Candidate c = {rule, 0, 0, 0, false, std::make_unique<Analysis>()};
-    c.ok = build_analysis(*c.A, params, quiet, rule) == 0;
-    if (c.ok) { c.front = c.A->S.front; c.stages = c.A->S.n_stages; c.cont = c.A->S.n_continuation() > 0; }
-    reduced = c.A->M.reduce_base != 0;
-    if (!c.ok || !keep) c.A.reset();
-    return c;
-  };
-  std::vector<Candidate> out;
-  if (env.order >= 0) { out.push_back(analyse(env.order)); return out; }
-  // (rules 1 and 2 move the coefficients of a reduced base: without one rule 0 is the choice, as in pick_order_rule)
-  if (!params.reduce_base) { out.push_back(analyse(0)); return out; }
-  const int mask = (rules_mask & 7) ? (rules_mask & 7) : 6;
-  for (int rule : {2, 1, 0}) {
-    if (!((mask >> rule) & 1)) continue;
-    Candidate c = analyse(rule);
-    if (c.ok && !reduced) { out.clear(); out.push_back(analyse(0)); return out; }    // (the model kept the full base)
-    out.push_back(std::move(c));
-  }
-  // pick_order_rule's preference; the stable sort keeps 2 before 1 before 0 among equals
-  std::stable_sort(out.begin(), out.end(), [](const Candidate &a, const Candidate &b) {
-    if (a.ok != b.ok) return a.ok;
-    if (a.front != b.front) return a.front < b.front;
-    if (a.stages != b.stages) return a.stages < b.stages;
-    return a.cont < b.cont;
-  });
-  return out;
-}
-
 int qtos_analyze_candidates(const QtosParams *params, int rules_mask, int *rules, int *fronts, int *stages, int n) {
   if (!params || n < 0) return -1;
   const std::vector<Candidate> c = order_candidates(*params, QtosEnv::parse(), rules_mask);
@@ -2100,12 +1653,13 @@ int qtos_planner_create_checked(const QtosParams *params, int max_batch, int dev
     QtosSelftest t;
     std::memset(&t, 0, sizeof(t));
     t.order_rule = c.rule; t.residual_refined = -1.0;
-    QtosPlanner *p = nullptr;
-    int rc = c.ok ? create_planner(params, max_batch, device, env, c.rule, &p, c.A.get()) : -1;
+    QtosPlanner *made = nullptr;
+    int rc = c.ok ? create_planner(params, max_batch, device, env, c.rule, &made, c.A.get()) : -1;
+    std::unique_ptr<QtosPlanner> p(made);   // (a candidate that is not handed out goes at the end of its turn)
     c.A.reset();
     if (rc == 0) {
       ++n_built;
-      rc = qtos_planner_selftest(p, 0, tol_residual, &t);
+      rc = qtos_planner_selftest(p.get(), 0, tol_residual, &t);
       if (rc) fprintf(stderr, "qtos: %s\n", p->err.c_str());
     }
     if (rc && !first_rc) first_rc = rc;
@@ -2113,8 +1667,7 @@ int qtos_planner_create_checked(const QtosParams *params, int max_batch, int dev
     log.push_back(t);
     if ((int)log.size() <= max_tried) tried[log.size() - 1] = t;
     if (n_tried) *n_tried = std::min((int)log.size(), max_tried);
-    if (rc == 0 && t.passed) { *out = p; return 0; }
-    if (p) qtos_planner_destroy(p);
+    if (rc == 0 && t.passed) { *out = p.release(); return 0; }
   }
   if (!n_built) return first_rc ? first_rc : -1;
   fprintf(stderr, "qtos: no elimination order passed the KKT self-test:");

@@ -226,7 +226,7 @@ def test_knots200_structure(hip_lib):
 
 @pytest.mark.parametrize("which", ["knots100", "trot", "knots200", "reference_compat", "duration12", "full_system"])
 def test_sweep_schedule_of_the_slack_steps(which):
-    """The schedule by which the idle waves of the backward sweep form ds = Ji dx (qtos_planner.hip build_sweep_tasks; the
+    """The schedule by which the idle waves of the backward sweep form ds = Ji dx (planner_create.hpp build_sweep_tasks; the
     reference has no counterpart: Ipopt forms J d inside its line search).  Host-only invariants: every inequality row of
     the working set exactly once; a row runs no earlier than the step behind the one that solves the stage of its earliest
     column -- every column of the row is then known, positions never decrease along the sweep --; the 16-bit copy of the
