@@ -81,6 +81,10 @@ typedef struct QtosParams {
                           reference's runs: the same 1e-4 as this planner's tol -- keeps the KKT systems of late iterations
                           as well scaled as those of the fourth (with tol / 10 the GPU <-> oracle gaps of the long horizons
                           doubled).  0: mu <- max(mu_min, 0.2 mu) (rounds 1 - 4) */
+  double kappa_sigma;  /* Ipopt's kappa_sigma: behind every step a multiplier is clipped to [mu / (kappa_sigma gap), kappa_sigma mu /
+                          gap], at the new gap and the mu of the step (Ipopt's default 1e10: the clip never acts in the product's
+                          runs).  Must be > 1 -- there is no "0 = default" here: the field is the struct's last, and an image
+                          written for a shorter struct is refused rather than read as a setting */
 } QtosParams;
 
 typedef struct QtosDims {

@@ -13,7 +13,7 @@ where a sum or a quotient is compared at rounding level.  The oracle's constrain
 import numpy as np
 
 NO_BOUND = 1e19
-KAPPA = 1e10                 # z stays within [mu / (KAPPA gap), KAPPA mu / gap] (Ipopt's kappa_sigma)
+KAPPA = 1e10                 # z stays within [mu / (kappa gap), kappa mu / gap]: the default of cfg.kappa_sigma (Ipopt's kappa_sigma)
 ARMIJO = 1e-4
 MAX_TRIALS = 6
 TH_FLOOR = 1e-9              # an l1 infeasibility below this is accepted whatever it was before
@@ -216,21 +216,41 @@ def line_search(constraints, x, dx, s, ds, amax, rows):
     return al, len(log), log
 
 
-def update(s, ds, zl, zu, dzl, dzu, alpha, az, mu, lo, hi):
-    """New (s, zl, zu): s + alpha ds, z + az dz clipped to [mu / (KAPPA gap), KAPPA mu / gap] at the NEW gap and the OLD mu."""
+def kappa_of(cfg):
+    return KAPPA if cfg is None else float(cfg.kappa_sigma)
+
+
+def clip_limits(s_new, mu, lo, hi, cfg=None):
+    """(lowest z_l, highest z_l, lowest z_u, highest z_u) of update(): mu / (kappa gap), kappa mu / gap at the NEW gap and the
+    OLD mu, kappa = cfg.kappa_sigma."""
+    kap = kappa_of(cfg)
+    _, _, dl, du = gaps(s_new, lo, hi)
+    return mu / (kap * dl), kap * mu / dl, mu / (kap * du), kap * mu / du
+
+
+def update(s, ds, zl, zu, dzl, dzu, alpha, az, mu, lo, hi, cfg=None):
+    """New (s, zl, zu): s + alpha ds, z + az dz clipped to [mu / (kappa gap), kappa mu / gap] at the NEW gap and the OLD mu."""
     sn = s + alpha * ds
-    hl, hu, dl, du = gaps(sn, lo, hi)
+    hl, hu = has_bounds(lo, hi)
     a, c = zl + az * dzl, zu + az * dzu
-    a = np.where(hl, np.minimum(np.maximum(a, mu / (KAPPA * dl)), KAPPA * mu / dl), a)
-    c = np.where(hu, np.minimum(np.maximum(c, mu / (KAPPA * du)), KAPPA * mu / du), c)
+    lo_l, hi_l, lo_u, hi_u = clip_limits(sn, mu, lo, hi, cfg)
+    a = np.where(hl, np.minimum(np.maximum(a, lo_l), hi_l), a)
+    c = np.where(hu, np.minimum(np.maximum(c, lo_u), hi_u), c)
     return sn, a, c
 
 
-def clip_active(s_new, zl, zu, dzl, dzu, az, mu, lo, hi):
-    """Rows on which the clip of update() changes z_l or z_u."""
-    hl, hu, dl, du = gaps(s_new, lo, hi)
+def clip_sides(s_new, zl, zu, dzl, dzu, az, mu, lo, hi, cfg=None):
+    """Per row, which limit of update() acts: (z_l at its lowest, z_l at its highest, z_u at its lowest, z_u at its highest)."""
+    hl, hu = has_bounds(lo, hi)
     a, c = zl + az * dzl, zu + az * dzu
-    return (hl & ((a < mu / (KAPPA * dl)) | (a > KAPPA * mu / dl))) | (hu & ((c < mu / (KAPPA * du)) | (c > KAPPA * mu / du)))
+    lo_l, hi_l, lo_u, hi_u = clip_limits(s_new, mu, lo, hi, cfg)
+    return hl & (a < lo_l), hl & (a > hi_l), hu & (c < lo_u), hu & (c > hi_u)
+
+
+def clip_active(s_new, zl, zu, dzl, dzu, az, mu, lo, hi, cfg=None):
+    """Rows on which the clip of update() changes z_l or z_u."""
+    a, b, c, d = clip_sides(s_new, zl, zu, dzl, dzu, az, mu, lo, hi, cfg)
+    return a | b | c | d
 
 
 def next_mu(mu, alpha, cfg):
@@ -336,8 +356,8 @@ def solve(O, q, cfg, x0=None, max_iter=None, eps_rows=None):
             alpha_t, az_t = alpha, az
             x = x + alpha * dx
             g = O.constraints(x)
-        clip = np.nonzero(clip_active(s + alpha_t * ds, zl, zu, dzl, dzu, az_t, mu, lo_i, hi_i))[0]
-        s, zl, zu = update(s, ds, zl, zu, dzl, dzu, alpha_t, az_t, mu, lo_i, hi_i)
+        clip = np.nonzero(clip_active(s + alpha_t * ds, zl, zu, dzl, dzu, az_t, mu, lo_i, hi_i, cfg))[0]
+        s, zl, zu = update(s, ds, zl, zu, dzl, dzu, alpha_t, az_t, mu, lo_i, hi_i, cfg)
         mu_new = next_mu(mu, alpha_t, cfg)
         floor = cfg.mu_superlinear and mu_new == max(cfg.mu_min, cfg.tol) and alpha_t > MU_STEP
         mu = mu_new

@@ -61,6 +61,7 @@ class QoOptions(C.Structure):
         ("stall_alpha", C.c_double), ("chord_max", C.c_int), ("chord_shrink", C.c_double), ("swing_start_on_rule", C.c_int),
         ("eps_dual_swing", C.c_double), ("eps_dual_acc", C.c_double),
         ("mu_superlinear", C.c_int),
+        ("kappa_sigma", C.c_double),
     ]
 
 
@@ -143,6 +144,7 @@ def oracle_options(cfg, O, match_eliminated=False):
     o.chord_tol, o.chord_max, o.chord_shrink = cfg.chord_tol, cfg.chord_max, cfg.chord_shrink
     o.stall_alpha = cfg.stall_alpha
     o.mu_superlinear = int(bool(getattr(cfg, "mu_superlinear", False)))
+    o.kappa_sigma = float(getattr(cfg, "kappa_sigma", 1e10))
     # (the product's reduce_swing applies with nearest-cell terrain only: model.hpp)
     o.swing_start_on_rule = int(bool(getattr(cfg, "reduce_swing", False)) and cfg.terrain_mode == 1)   # (== O.swing_start_on_rule for an Oracle(oracle_dict(cfg)))
     return o

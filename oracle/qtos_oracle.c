@@ -941,6 +941,7 @@ void qo_default_options(qo_options *o) {
   o->eps_dual_swing = -1.0;
   o->eps_dual_acc = -1.0;
   o->mu_superlinear = 1;
+  o->kappa_sigma = 1e10;
 }
 
 /* time stamp of every variable / constraint row: used only to order the KKT unknowns */
@@ -1344,7 +1345,7 @@ int qo_solve(const qo_params *p, const qo_problem *q, const qo_options *o, doubl
       s[i] += al * ds[i];
       zl[i] += az * dzl[i];
       zu[i] += az * dzu[i];
-      const double kap = 1e10;
+      const double kap = o->kappa_sigma;
       if (hl) zl[i] = fmin(fmax(zl[i], mu / (kap * (s[i] - l))), kap * mu / (s[i] - l));
       if (hu) zu[i] = fmin(fmax(zu[i], mu / (kap * (u - s[i]))), kap * mu / (u - s[i]));
     }

@@ -128,6 +128,8 @@ typedef struct {
                           compare the two at rounding level hands this solver a tiny eps for exactly those rows. */
   int mu_superlinear;  /* 1: mu <- max(tol, mu_min, min(0.2 mu, mu sqrt(mu))) behind a step longer than 0.3 (Ipopt's monotone update:
                           mu_linear_decrease_factor 0.2, mu_superlinear_decrease_power 1.5); 0: mu <- max(mu_min, 0.2 mu) */
+  double kappa_sigma;  /* z is clipped to [mu / (kappa_sigma gap), kappa_sigma mu / gap] behind every step, at the new gap and
+                          the old mu (Ipopt's kappa_sigma, default 1e10); > 1 */
 } qo_options;
 
 typedef struct {

@@ -34,6 +34,7 @@ class QtosParams(C.Structure):
         ("chord_max", C.c_int), ("chord_shrink", C.c_double), ("stall_alpha", C.c_double),
         ("reduce_swing", C.c_int),
         ("mu_superlinear", C.c_int),
+        ("kappa_sigma", C.c_double),
     ]
 
 
@@ -705,6 +706,10 @@ def params_from_config(cfg):
     p.stall_alpha = float(cfg.stall_alpha)
     p.reduce_swing = int(getattr(cfg, "reduce_swing", False))
     p.mu_superlinear = int(getattr(cfg, "mu_superlinear", False))
+    if not float(cfg.kappa_sigma) > 1.0:              # (model.hpp refuses it too: a C caller gets -1, bad parameters)
+        raise ValueError("kappa_sigma must be > 1 (Ipopt's default: 1e10), not %r: the clip of z to [mu / (kappa_sigma gap), "
+                         "kappa_sigma mu / gap] needs a band to clip to" % (cfg.kappa_sigma,))
+    p.kappa_sigma = float(cfg.kappa_sigma)
     return p
 
 

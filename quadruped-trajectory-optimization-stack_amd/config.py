@@ -129,6 +129,10 @@ class PlannerConfig:
     # third iterate is better centred: every problem of a trot batch converges in four iterations (it was 4: 58 %, 5: 42 %, i.e.
     # five for the batch: +10 % plans/s), flat walk and terrains unchanged (round 5, profiles/r05_experiments/mu_rule.log).
     mu_superlinear: bool = True
+    # Ipopt's kappa_sigma: behind every step a multiplier z is clipped to [mu / (kappa_sigma gap), kappa_sigma mu / gap], at the
+    # new gap and the mu the step was taken with.  At Ipopt's default 1e10 the clip never acts on the product's workloads (z x gap
+    # stays within a few decades of mu); the tests run small values to put rows on the clip.  Must be > 1.
+    kappa_sigma: float = 1e10
     phase_durations: List[List[float]] = field(default=None)
 
     def __post_init__(self):

@@ -137,6 +137,7 @@ struct DevPlan {
   int mu_superlinear;   // QtosParams.mu_superlinear: Ipopt's monotone update of the barrier parameter
   int max_iter, stall_iters;
   double stall_alpha;          // QtosParams.stall_alpha
+  double kappa_sigma;          // QtosParams.kappa_sigma: the clip of z behind a step (update_row)
   const double *height;
   int n_maps, hnx, hny, terrain_mode;
   double hcell, hx0, hy0;
@@ -1542,7 +1543,7 @@ __global__ __launch_bounds__(ET) void k_step(DevPlan P, DevWork W, int B, int sl
     const double sn = sv + al * d;
     sv = sn;
     const double a = zlv + az * dl_, c = zuv + az * du_;
-    const double kap = 1e10;
+    const double kap = P.kappa_sigma;
     const double gl = hl ? sn - l : 1.0, gu = hu ? u - sn : 1.0;   // (the four quotients side by side, as in ratio_row)
     const double lo_l = mu / (kap * gl), hi_l = kap * mu / gl, lo_u = mu / (kap * gu), hi_u = kap * mu / gu;
     zlv = hl ? fmin(fmax(a, lo_l), hi_l) : a;

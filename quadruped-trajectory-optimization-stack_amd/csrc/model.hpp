@@ -488,6 +488,7 @@ struct HostModel {
       err = "bad durations";
       return -1;
     }
+    if (!(P.kappa_sigma > 1)) { err = "kappa_sigma must be > 1 (Ipopt's default: 1e10)"; return -1; }
     for (int e = 0; e < NEE; ++e) {
       int n = P.n_phases[e];
       if (n < 1 || n > QTOS_MAX_PHASES || n % 2 == 0) { err = "n_phases must be odd, <= QTOS_MAX_PHASES"; return -1; }

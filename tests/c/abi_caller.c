@@ -25,9 +25,9 @@ int main(int argc, char **argv) {
   if (n != sizeof p || extra) { printf("params image %lu bytes (+%d), struct %lu\n", (unsigned long)n, extra, (unsigned long)sizeof p); return 4; }
   memset(&d, 0, sizeof d);
   rc = qtos_analyze(&p, &d, act, 1024);
-  printf("analyze rc=%d sizeof_params=%lu sizeof_dims=%lu n_vars=%d n_cons=%d n_free=%d n_eq=%d n_ineq=%d n_unknowns=%d n_stages=%d pivots=%d front=%d order_rule=%d max_active=%d rows=%d\n",
+  printf("analyze rc=%d sizeof_params=%lu sizeof_dims=%lu n_vars=%d n_cons=%d n_free=%d n_eq=%d n_ineq=%d n_unknowns=%d n_stages=%d pivots=%d front=%d order_rule=%d max_active=%d rows=%d kappa_sigma=%.17g\n",
          rc, (unsigned long)sizeof p, (unsigned long)sizeof d, d.n_vars, d.n_cons, d.n_free, d.n_eq, d.n_ineq, d.n_unknowns, d.n_stages, d.pivots, d.front,
-         d.order_rule, d.max_active, d.n_rows_csv);
+         d.order_rule, d.max_active, d.n_rows_csv, p.kappa_sigma);   /* (the struct's last field: read at the mirror's offset) */
   printf("build_flags=%d\n", qtos_build_flags());
   for (i = 0; i < 3 * QTOS_CSV_COLS; ++i) rows[i] = 0.0;
   rows[0] = 3.756; rows[3] = 0.24; rows[QTOS_CSV_COLS] = 3.757; rows[QTOS_CSV_COLS + 1] = 6.9309e-07; rows[2 * QTOS_CSV_COLS] = 3.758;

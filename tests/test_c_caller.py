@@ -24,7 +24,7 @@ def test_c99_caller_links_and_sees_the_same_structs(tmp_path, name):
            "-Wl,-rpath," + CSRC, "-Wl,--allow-shlib-undefined"]
     r = subprocess.run(cmd, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
-    cfg = PlannerConfig.reference_compat() if name == "reference_compat" else PlannerConfig.knots100(gait="trot")
+    cfg = PlannerConfig.reference_compat() if name == "reference_compat" else PlannerConfig.knots100(gait="trot", kappa_sigma=12.5)
     p = capi.params_from_config(cfg)
     img = tmp_path / "params.bin"
     img.write_bytes(bytes(p))
@@ -37,6 +37,7 @@ def test_c99_caller_links_and_sees_the_same_structs(tmp_path, name):
     for k in ("n_vars", "n_cons", "n_free", "n_eq", "n_ineq", "n_unknowns", "n_stages", "pivots", "front", "order_rule", "max_active"):
         assert int(kv[k]) == getattr(d, k), (k, kv[k], getattr(d, k))
     assert int(kv["rows"]) == d.n_rows_csv
+    assert float(kv["kappa_sigma"]) == cfg.kappa_sigma and C.sizeof(capi.QtosParams) == capi.QtosParams.kappa_sigma.offset + 8
     assert r.stdout.splitlines()[1] == "build_flags=%d" % capi.build_flags()
     assert r.stdout.splitlines()[2] == "write_csv rc=0 bad_path rc=-2 null rc=-1"
     assert open(out).read().splitlines()[:2] == ["3.756,0,0,0.24" + ",0" * 33, "3.757,6.9309e-07" + ",0" * 35]

@@ -22,9 +22,12 @@ Per step and problem, from the GPU's OWN state k (so that no error of an earlier
   5. line search: every trial the GPU made, evaluated through the oracle at the GPU's x_k + alpha dx: the accepted one meets
      the Armijo test, every earlier one fails it; decisions within rows x GATE_VALUE of the right-hand side would be excluded,
      and none may be (test_step_cpu.py holds the reference alone to that)
-  6. update: z of state k + 1 against update(), per row az x the dz bound of 4. + 4 u (|z| + az |dz| + |z_new|); mu against
+  6. update: z of state k + 1 against update(), per row az x the dz bound of 4. + 4 u (|z| + az |dz| + |z_new|); a row the clip
+     of z acts on (the discard_* / clip_* cases: kappa_sigma 10 and 2) against its limit mu_k / (kappa gap) or kappa mu_k / gap
+     at the GPU's own s_{k+1}, 4 u relative + the limit's sensitivity to rb_s, reported as `z_l clip` / `z_u clip`; mu against
      next_mu, 4 u; viol, theta of the history against measures on the oracle's g at x_{k+1}, GATE_VALUE; compl 4 u.  A
-     discarded chord step leaves x, s, z bit for bit
+     discarded chord step leaves x, s, z and mu bit for bit (state k + 1 equals state k), and the step behind it is a fresh
+     factorisation's, held to the dense solve at that same iterate
   7. decisions: the kind of every step, the stop, the factorisation / chord-solve totals against next_kind fed the history's
      own numbers (equalities); the hold latch enters 2. through the diagonal
 
@@ -110,7 +113,7 @@ def _check_case(name, reduced):
     G = _gpu_states(c, cfg)
     K, last = c.steps, G[c.steps]
     W = Worst()
-    excluded = decisions = 0
+    excluded = decisions = clipped_rows = clipped_tail = discarded = 0
     for b in range(c.B):
         R = stc.run(name, b)                        # (the working set and the bounds; the GPU's own states are what is checked)
         free, E, I, lo, hi = R["free"], R["E"], R["I"], R["lo"][R["I"]], R["hi"][R["I"]]
@@ -170,9 +173,14 @@ def _check_case(name, reduced):
                 Kmat = ipm.kkt_matrix(J, free, E, I, sig, np.where(hold_vars & d["held"], cfg.foothold_hold_weight, cfg.delta_x), eps)
                 lu = None
             if kind == 2:
-                # 6. a discarded chord step leaves the iterate bit for bit
-                assert alpha == 0.0 and az == 0.0 and h[2] == mu
-                assert np.array_equal(x1, x0) and np.array_equal(s1, s0) and np.array_equal(zl1, zl0) and np.array_equal(zu1, zu0)
+                # 6. a discarded chord step leaves the iterate bit for bit: state k + 1 IS state k, mu included (al = az = 0
+                # in update_row: s + 0 ds, z + 0 dz, and the clip at the old gap and mu finds z where the last step left it).
+                # The step behind it is then checked like any other: a fresh factorisation (7.) whose direction meets the
+                # dense solve AT THIS ITERATE (2.: the linearisation ran at x, not at the trial point), no chord step after
+                assert alpha == 0.0 and az == 0.0 and h[2] == mu, (name, b, k, alpha, az, h[2], mu)
+                assert np.array_equal(x1, x0) and np.array_equal(s1, s0) and np.array_equal(zl1, zl0) and np.array_equal(zu1, zu0), (name, b, k)
+                assert h[0] == hist[k][0] and h[1] == hist[k][1], (name, b, k, "viol / theta of an iterate that did not move")
+                discarded += k + 1 < steps
             else:
                 xd = x1.astype(np.longdouble) - x0
                 sd = s1.astype(np.longdouble) - s0
@@ -224,10 +232,32 @@ def _check_case(name, reduced):
                         assert not ok, ("an earlier trial meets the Armijo test", name, b, k, t, th, rhs)
                     elif trials < ipm.MAX_TRIALS:
                         assert ok, ("the accepted trial fails the Armijo test", name, b, k, t, th, rhs)
-                # 6. the update of z and mu
-                _, zl_ref, zu_ref = ipm.update(s0, ds, zl0, zu0, dzl, dzu, alpha, az, mu, lo, hi)
-                W.check("zl", np.abs(zl1 - zl_ref), az * e_dzl + 4 * U * (np.abs(zl0) + az * np.abs(dzl) + np.abs(zl_ref)), where(b, k))
-                W.check("zu", np.abs(zu1 - zu_ref), az * e_dzu + 4 * U * (np.abs(zu0) + az * np.abs(dzu) + np.abs(zu_ref)), where(b, k))
+                # 6. the update of z and mu.  The clip's limits are formed from the GPU's OWN new slack and the OLD mu (update_row
+                # clips at sn, which it stores, before mu moves): a row the clip acts on -- z + az dz of the GPU's own state k
+                # outside the band -- is held to its limit at 4 u relative (the gap, one product, one quotient) plus the limit's
+                # sensitivity |limit| / gap to the slack step's recovery bound; a row whose z + az dz is within the dz bound of a
+                # limit may fall either side of it and takes the larger of the two bounds; every other row the dz bound alone
+                lim = ipm.clip_limits(s1, mu, lo, hi, cfg)
+                _, _, dl1, du1 = ipm.gaps(s1, lo, hi)
+                for zn, has, z0, dz, e_dz, z1, gap1, lim_lo, lim_hi in (("l", hl, zl0, dzl, e_dzl, zl1, dl1, lim[0], lim[1]),
+                                                                      ("u", hu, zu0, dzu, e_dzu, zu1, du1, lim[2], lim[3])):
+                    un = z0 + az * dz
+                    ref = np.where(has, np.minimum(np.maximum(un, lim_lo), lim_hi), un)
+                    b_dz = az * e_dz + 4 * U * (np.abs(z0) + az * np.abs(dz) + np.abs(ref))
+                    b_clip = 4 * U * np.abs(ref) + np.abs(ref) / gap1 * alpha * rb_s
+                    clipped = has & ((un < lim_lo) | (un > lim_hi))
+                    near = has & ((np.abs(un - lim_lo) <= b_dz) | (np.abs(un - lim_hi) <= b_dz))
+                    bound = np.where(near, np.maximum(b_dz, b_clip), np.where(clipped, b_clip, b_dz))
+                    err = np.abs(z1 - ref)
+                    rows_c, rows_f = np.nonzero(clipped)[0], np.nonzero(~clipped)[0]
+                    W.check("z" + zn, err[rows_f], bound[rows_f], lambda i, f=where(b, k), r=rows_f: f(r[i]))
+                    # (register rows and tail rows apart: a failure names its worst row on either path)
+                    for r in (rows_c[rows_c < TAIL], rows_c[rows_c >= TAIL]):
+                        if len(r):
+                            W.check("z_%s clip" % zn, err[r], bound[r], lambda i, f=where(b, k), r=r: f(r[i]))
+                    if alpha > ipm.MU_STEP:                    # (mu moves behind this step: the limits at the new mu are others)
+                        clipped_rows += len(rows_c)
+                        clipped_tail += int((rows_c >= TAIL).sum())
                 W.check("mu", abs(h[2] - ipm.next_mu(mu, alpha, cfg)), 4 * U * h[2], (b, k))
             viol, theta, compl = ipm.measures(g1[I], s1, zl1, zu1, lo, hi, g1[E])
             W.check("viol", abs(h[0] - viol), stc.GATE_VALUE, (b, k))
@@ -247,9 +277,17 @@ def _check_case(name, reduced):
             assert rep.status == 1
         assert rep.n_factorizations == kinds.count(0) and rep.n_chord_solves == len(kinds) - kinds.count(0)
     stc.record("gpu_reduced" if reduced else "gpu_full", name,
-               dict(problems=c.B, steps=K, armijo_decisions=decisions, excluded=excluded, achieved_over_bound=W.ratio))
+               dict(problems=c.B, steps=K, armijo_decisions=decisions, excluded=excluded, achieved_over_bound=W.ratio,
+                    clipped_rows_checked_while_mu_moves=clipped_rows, of_them_tail_rows=clipped_tail,
+                    discarded_chord_steps_with_a_step_behind=discarded))
     assert excluded == 0
-    assert not W.fails, W.fails[:8]
+    # the case is on the GPU where the restatement's run put it on the CPU (test_the_case_table_sits_on_the_paths_it_names)
+    if name in stc.CLIP_NAMES:
+        assert clipped_rows > 0 and (c.n_iq <= TAIL or 0 < clipped_tail < clipped_rows), (name, clipped_rows, clipped_tail)
+    else:
+        assert clipped_rows == 0, (name, "the clip acts where kappa_sigma is Ipopt's 1e10")
+    assert (discarded > 0) == (name in stc.DISCARD_NAMES), (name, discarded)
+    assert not W.fails, W.fails[:12]
 
 
 @pytest.mark.parametrize("name", stc.NAMES)
@@ -262,32 +300,48 @@ def test_every_step_of_the_reduced_system_matches_the_restatement(name):
     _check_case(name, True)
 
 
-def test_a_stalled_solve_stops_where_the_restatement_stops_and_hands_back_its_best_iterate():
-    """The cases run with the stall rules off.  Here the bilinear_steps problems run with the product's settings (stall_iters
-    = 5, stall_alpha = 1e-2, max_iter = 24) next to a run without the stall rules: problem 1 (step_cases.STALLED) stalls in its
-    ninth iteration.  In front of its stop every history row is that of the stall-off run bit for bit, and so is the stop row in
-    every column the step writes (its dual infeasibility is k_report's, of the nodes handed back); the stop is where next_kind,
-    fed the history's own numbers, puts it, and for the stalled problem where the restatement's own run and its stall rule put
-    it; the nodes handed back are those of the iterate with the lowest violation, bit for bit what a planner out of iterations
-    at that iterate exports, with that violation."""
+def _groups():
+    """STOPPED by (case, settings): the problems of a case run as one batch."""
+    out = {}
+    for e in stc.STOPPED:
+        out.setdefault((e[0], tuple(sorted(e[2].items()))), []).append(e)
+    return list(out.values())
+
+
+@pytest.mark.parametrize("entries", _groups(), ids=lambda es: "%s-%s" % (es[0][0], "-".join(sorted({str(e[3]) for e in es}))))
+def test_a_stopped_solve_stops_where_the_restatement_stops_and_hands_back_its_best_iterate(entries):
+    """The cases run with the stall rules off.  Here the problems of a step_cases.STOPPED case run with the entry's settings --
+    bilinear_steps with the product's (stall_iters = 5, stall_alpha = 1e-2, max_iter = 24: problem 1 stalls in its ninth
+    iteration), the jam entries with stall_alpha = 0.9 or, far_goal, the product's own 1e-2 -- next to a run without the stall
+    rules.  In front of a stop every history row is that of the rules-off run bit for bit, and so is the stop row in every
+    column the step writes (its dual infeasibility is k_report's, of the nodes handed back); the stop is where next_kind, fed
+    the history's own numbers, puts it, and for the entries' problems where the restatement's own run puts it, of the kind and
+    in the iteration the table names; the nodes handed back are those of the iterate with the lowest violation, bit for bit
+    what a planner out of iterations at that iterate exports, with that violation (a jammed solve may have improved in its
+    last step: then that one); status 1; the last two steps of a jammed solve are shorter than stall_alpha.  The entries
+    that must NOT stop (discard_bilinear under stall_alpha = 0.9: alpha 1, 0 -- the discarded chord step --, 0.25, 1 ...) run
+    to the rules-off result bit for bit: the discarded step does not count."""
     from qtos_amd.capi import Planner
-    name, stalled_b = stc.STALLED
+    name = entries[0][0]
     c = stc.case(name)
-    cfg_on = c.product_full
+    cfg_on = stc.stopped_cfg(entries[0])
     cfg_off = stc.prefix(cfg_on)
-    assert cfg_on.stall_iters > 0 and cfg_on.stall_alpha > 0 and cfg_off.max_iter == cfg_on.max_iter
+    assert cfg_on.stall_alpha > 0 and cfg_off.max_iter == cfg_on.max_iter and cfg_off.stall_alpha == 0 and cfg_off.stall_iters == 0
+    if entries[0][3] == "stalled":
+        assert cfg_on.stall_iters > 0 and cfg_on == c.product_full      # (the product's settings)
 
     def plan(cfg):
         P = Planner(cfg, max_batch=c.B)
         try:
-            P.set_heightfields(c.terrain[0], c.terrain[1])
+            if c.terrain is not None:
+                P.set_heightfields(c.terrain[0], c.terrain[1])
             P.set_report(True)
             nodes, status, iters, viol = P.plan(c.start, c.goal)
             return dict(x=nodes, status=status, iters=iters, viol=viol, reps=[P.report(b) for b in range(c.B)])
         finally:
             P.close()
     on, off = plan(cfg_on), plan(cfg_off)
-    stops = {}
+    stops, best_its = {}, {}
     for b in range(c.B):
         rep, hist = on["reps"][b]
         n = len(hist)
@@ -317,14 +371,29 @@ def test_a_stalled_solve_stops_where_the_restatement_stops_and_hands_back_its_be
             assert np.array_equal(hist[n - 1, INF_DU], ref[n - 1, INF_DU], equal_nan=True), b
         if stops[b] in ("stalled", "jammed"):
             # the best iterate: what a planner out of iterations there exports
-            best = d["best_it"]
+            best = best_its[b] = d["best_it"]
             assert hist[best][0] == d["best_viol"] == min(hist[:, 0]) and on["viol"][b] == d["best_viol"]
             assert n - 1 < len(off["reps"][b][1]) - 1                       # without the rule the solve goes on
             at_best = plan(dataclasses.replace(cfg_off, max_iter=best))
             assert np.array_equal(at_best["reps"][b][1], hist[:best + 1], equal_nan=True)
             assert np.array_equal(on["x"][b], at_best["x"][b]), b
-    assert stops[stalled_b] == "stalled", stops
-    R = ipm.solve(c.O, c.q[stalled_b], cfg_on)
-    assert (R["stop"], R["iters"]) == ("stalled", int(on["iters"][stalled_b]))
-    stc.record("gpu_stalled_solve", name, dict(stops={str(b): v for b, v in stops.items()}, iterations=[int(i) for i in on["iters"]],
-                                               iterations_without_the_stall_rules=[int(i) for i in off["iters"]]))
+        else:
+            # no stop by a rule: the run IS the rules-off run
+            assert n == len(off["reps"][b][1]) and np.array_equal(on["x"][b], off["x"][b]) and on["viol"][b] == off["viol"][b], b
+            assert int(on["status"][b]) == int(off["status"][b])
+        if stops[b] == "jammed":
+            assert n >= 3 and hist[n - 1][4] < cfg_on.stall_alpha and hist[n - 2][4] < cfg_on.stall_alpha, (b, hist[:, 4])
+            assert int(hist[n - 1][7]) != 2 and int(hist[n - 2][7]) != 2
+    for _, b, _, stop, at in entries:
+        assert stops[b] == stop and (at is None or int(on["iters"][b]) == at), (name, b, stops, on["iters"])
+        R = stc.run(name, b, cfg_on)
+        assert (R["stop"], R["iters"]) == (stop, int(on["iters"][b]))
+        if stop == "converged":
+            # the discarded chord step stood between a long step and a short one, and did not count
+            al, kinds = on["reps"][b][1][1:, 4], on["reps"][b][1][1:, 7].astype(int)
+            k = list(kinds).index(2)
+            assert al[k] == 0.0 and 0 < al[k + 1] < cfg_on.stall_alpha <= al[k - 1] and int(on["status"][b]) == 0
+    stc.record("gpu_stopped_solve", "%s %s" % (name, " ".join("%s=%s" % kv for kv in sorted(entries[0][2].items())) or "product settings"),
+               dict(stops={str(b): v for b, v in stops.items()}, iterations=[int(i) for i in on["iters"]], best_iterates={str(b): int(v) for b, v in best_its.items()},
+                    iterations_without_the_stall_rules=[int(i) for i in off["iters"]],
+                    last_alphas={str(b): [float(a) for a in on["reps"][b][1][-2:, 4]] for b in range(c.B)}))

@@ -187,8 +187,10 @@ def test_c99_caller_sees_the_struct_and_the_error_codes(tmp_path, no_order_env):
     assert r.returncode == 0, (r.stdout, r.stderr)
     kv = dict(t.split("=") for ln in r.stdout.splitlines() for t in ln.split())
     assert int(kv["sizeof_selftest"]) == C.sizeof(capi.QtosSelftest) == 72
-    # (the layouts the self-test's result does not travel in stay what they were)
-    assert int(kv["sizeof_params"]) == C.sizeof(capi.QtosParams) == 1440 and int(kv["sizeof_dims"]) == C.sizeof(capi.QtosDims) == 128
+    # (the layouts the self-test's result does not travel in stay what they were; QtosParams: 1440 + the double kappa_sigma,
+    #  appended behind everything that was there)
+    assert capi.QtosParams.kappa_sigma.offset == 1440
+    assert int(kv["sizeof_params"]) == C.sizeof(capi.QtosParams) == 1448 and int(kv["sizeof_dims"]) == C.sizeof(capi.QtosDims) == 128
     assert int(kv["selftest_null"]) == -1 and int(kv["selftest_null_out"]) == -1
     assert int(kv["checked"]) == -2 and int(kv["out_null"]) == 1 and int(kv["n_tried"]) == 0
     assert int(kv["checked_null_params"]) == -1
