@@ -16,6 +16,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "call_schedule.hpp"
 #include "model.hpp"
 #include "symbolic.hpp"
 
@@ -152,8 +153,9 @@ struct DevWork {
   double *best_viol, *xbest;   // stall detection: lowest violation seen and the iterate that had it
   int *held;                   // two-phase solve: 1 once the problem's footholds are held
   int *best_it;
-  int *status, *iters, *done, *n_active;   // n_active[0]: unfinished problems, [1]: of those, flagged for a chord step, [2]: (1 << 20) - the earliest launch slot a
-                                           // problem sat out (k_step; 0 = none), [3]: launch slots of the call in which some problem took a step
+  int *status, *iters, *done, *n_active;   // n_active[0]: unfinished problems, [1]: of those, flagged for a chord step, [2]: the code of the earliest launch slot a
+                                           // problem sat out (k_step; call_schedule.hpp sat_out_code, 0 = none), [3]: launch slots of the call in which some problem
+                                           // took a step -- the four ints k_post_counts sends to a count slot of call_schedule.hpp
   int *chord;                  // per problem: the next KKT solve reuses the stored factorisation (k_chord)
   int *chord_run;              // per problem: chord steps taken with the stored factorisation
   int *jam;                    // per problem: steps in a row shorter than stall_alpha
@@ -1338,7 +1340,7 @@ __global__ __launch_bounds__(ET) void k_step(DevPlan P, DevWork W, int B, int sl
   lds_barrier();
   if (done_flag) return;
   if (missed) {
-    if (tid == 0) atomicMax(W.n_active + 2, (1 << 20) - slot);   // (the EARLIEST slot somebody sat out; 0 = nobody)
+    if (tid == 0) atomicMax(W.n_active + 2, sat_out_code(slot));   // (the EARLIEST slot somebody sat out; 0 = nobody)
     return;
   }
   if (P.n_rec) {

@@ -394,7 +394,9 @@ static int alloc_workspace(QtosPlanner *p) {
 // on two, 84.2 K on one)
 static int create_lanes(QtosPlanner *p) {
   // launch slots of a call: its iterations plus the launches some problem sat out (at most one per blind slot)
-  p->max_slots = 2 * p->M.P.max_iter + 2;
+  SlotLayout &S = p->slots;
+  S.max_slots = 2 * p->M.P.max_iter + 2;
+  if (S.max_slots >= SAT_OUT_BASE) return create_error(p, -1, "max_iter %d: more launch slots than the sat-out code of a slot holds", p->M.P.max_iter);
   int cus = 256;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->device) != hipSuccess || cus < 1) cus = 256;
   p->lane_chunk = cus;
@@ -403,14 +405,15 @@ static int create_lanes(QtosPlanner *p) {
   HIPCHK_AS(p, -2, hipEventCreateWithFlags(&p->ev_in, hipEventDisableTiming));
   for (int j = 0; j < n_lanes; ++j) {
     QtosPlanner::Lane &L = p->lanes[j];
-    HIPCHK_AS(p, -3, hipHostMalloc((void **)&L.h_active, 4 * sizeof(int) * ((size_t)p->max_slots + 1), hipHostMallocMapped));
+    HIPCHK_AS(p, -3, hipHostMalloc((void **)&L.h_active, S.count_ints() * sizeof(int), hipHostMallocMapped));
     HIPCHK_AS(p, -2, hipHostGetDevicePointer((void **)&L.h_active_dev, L.h_active, 0));
-    L.was_kkt.assign(p->max_slots + 1, 0); L.was_chord.assign(p->max_slots + 1, 0);
+    L.ran.assign(S.max_slots + 1, 0);
+    L.kinds_mask = p->chord_fn ? KIND_KKT | KIND_CHORD : KIND_KKT;
     L.d_n_active = p->wk.n_active + 4 * j;
     if (j > 0) HIPCHK_AS(p, -2, hipStreamCreateWithFlags(&L.own, hipStreamNonBlocking));
     HIPCHK_AS(p, -2, hipStreamCreateWithFlags(&L.side, hipStreamNonBlocking));
     for (hipEvent_t *e : {&L.ev_fork, &L.ev_join, &L.ev_done}) HIPCHK_AS(p, -2, hipEventCreateWithFlags(e, hipEventDisableTiming));
-    L.ev.resize(5 * (size_t)p->max_slots + 3);
+    L.ev.resize(S.n_events());
     for (auto &e : L.ev) HIPCHK_AS(p, -2, hipEventCreate(&e));
   }
   return 0;
@@ -419,12 +422,12 @@ static int create_lanes(QtosPlanner *p) {
 // The planner of qtos_planner_create (order_rule < 0: the automatic choice / QTOS_ORDER) and of the candidates of
 // qtos_planner_create_checked (order_rule >= 0), under the environment `env0` as the caller parsed it.
 static int create_planner(const QtosParams *params, int max_batch, int device, const QtosEnv &env0, int order_rule, QtosPlanner **out, Analysis *pre = nullptr) {
-  if (!params || !out || max_batch < 1 || max_batch >= (1 << 24)) return -1;   // (the count words of k_post_counts hold 24 bits per count)
+  if (!params || !out || max_batch < 1 || max_batch >= MAX_BATCH_LIMIT) return -1;   // (call_schedule.hpp: a count of the count word fits its bits)
   *out = nullptr;
   std::unique_ptr<QtosPlanner> owner(new QtosPlanner());   // (whichever way this function is left, the handle goes with it)
   QtosPlanner *p = owner.get();
   p->device = device; p->max_batch = max_batch; p->env = env0;
-  p->spec_pattern = p->env.spec_pattern != 0;
+  p->pattern.on = p->env.spec_pattern != 0;
   if (choose_kernel(*params, p->env, p->kkt, *p, order_rule, pre)) return -1;   // (it has said why)
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= device) {

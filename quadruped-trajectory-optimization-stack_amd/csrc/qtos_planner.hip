@@ -17,7 +17,7 @@
 #include <memory>
 #include <vector>
 
-#include "kernels.hpp"
+#include "kernels.hpp"   // (with call_schedule.hpp: the launch schedule of a plan call)
 #include "window_kernels.hpp"
 #include "kkt2.hpp"
 #include "kkt3.hpp"
@@ -67,23 +67,17 @@ struct QtosPlanner : Analysis {   // (the analysis the planner runs: choose_kern
   // stragglers then run side by side with the other parts' full grids instead of holding the whole call -- the reference's
   // queue of probes (QTOS/generateHeightField.py:375-377) inside ONE call.  The parts never meet: the plans are bit for bit
   // those of a single lane (QTOS_LANES=1).
-  struct Lane {
-    bool open = false;
-    int B = 0, b0 = 0, spec = 0, enq = 0, chk = 0;   // problems, first problem; iterations queued blind / queued in all / whose preceding counts have been read
-    int n_informed = 0;                      // launches of the call that waited for the host to read the counts
-    bool by_pattern = false;                 // the blind slots of this call follow the handle's launch pattern (counts behind the last one only)
+  struct Lane : LaneProgress {               // (call_schedule.hpp: how far the lane is, and what its last call's slots ran)
+    int B = 0, b0 = 0;                       // problems, first problem
     unsigned spins = 0;                      // polls that found no counts yet
     hipStream_t st = nullptr;                // where this lane's kernels go in the call in flight
     hipStream_t own = nullptr, side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_done = nullptr;
     DevWork W;
-    int *h_active = nullptr;      // pinned + mapped, four words per launch slot: {unfinished problems behind it, of those flagged for a chord step, sequence number}
-                                  // packed into the first two, then the code of the earliest slot a problem sat out and the slots that had work
+    int *h_active = nullptr;      // pinned + mapped: the count slots of call_schedule.hpp (SlotLayout::counts_at)
     int *h_active_dev = nullptr;  // the same memory as the device sees it (k_post_counts stores there: no copy engine between two kernels)
     int *d_n_active = nullptr;    // the lane's four device counters (DevWork::n_active)
-    std::vector<hipEvent_t> ev;   // 5 per iteration (kkt begin / end, chord begin / end, counts posted) + 3
-    std::vector<char> was_kkt, was_chord;   // per iteration of the last call: which solve kernels were launched
-    int last_launches = 0, last_iters = 0;
+    std::vector<hipEvent_t> ev;   // SlotLayout::ev, EV_CALL_BEGIN, EV_CALL_END
   };
   std::vector<Lane> lanes;
   int lanes_used = 1, lane_chunk = 256;      // lanes of the call in flight; problems per lane above which a call is cut (the GPU's compute units)
@@ -94,21 +88,18 @@ struct QtosPlanner : Analysis {   // (the analysis the planner runs: choose_kern
   unsigned seq = 0;                          // sequence number of the call in flight, stamped into the count words (k_post_counts)
   hipStream_t call_stream = nullptr;
   hipEvent_t ev_in = nullptr;                // the caller's stream at submit time: the other lanes start behind it
-  unsigned call_seq = 0;             // sequence number of the last call submitted
   Kkt kkt = Kkt::kkt2;               // the factor + solve kernel (choose_kernel)
   QtosEnv env;                       // the environment as qtos_planner_create found it (env.hpp; qtos_env reports it)
-  int spec_next = 1;                 // blind iterations of the next call: the iterations the last one took
+  int last_iters = 1;                // iterations the last call took: the blind iterations of the next (blind_slots)
   int spec_cap = 1;                  // limit of the blind iterations (qtos_set_speculation): 1 = off
-  // Launch pattern (round 6): the solve kernels every launch slot of the handle's last two calls needed (bit 0 the
-  // factorising kernel, bit 1 k_chord), as far as the two agree -- the walk's and the trot's batches take kkt, kkt, kkt, chord
-  // every time.  qtos_plan_submit queues that prefix at once, without a look at the counts; the counts behind its last slot
-  // say whether anything is left (qtos_plan_poll goes on informed) and whether a problem found the wrong kernel (it sat the
-  // launch out, kernels.hpp k_step: the pattern is cut in front of that slot).
+  // Launch pattern (round 6): the solve kernels every launch slot of the handle's last two calls needed, as far as the two
+  // agree -- the walk's and the trot's batches take kkt, kkt, kkt, chord every time.  qtos_plan_submit queues that prefix at
+  // once, without a look at the counts; the counts behind its last slot say whether anything is left (qtos_plan_poll goes on
+  // informed) and whether a problem found the wrong kernel (it sat the launch out, kernels.hpp k_step: the pattern is cut in
+  // front of that slot).
+  LaunchPattern pattern;
   bool per_kernel_events = true;     // HIP events around every solve kernel and behind every slot (qtos_last_timing*); qtos_set_kernel_events(0): only the call's first and last
-  bool spec_pattern = true;
-  std::vector<char> pat, obs_prev;   // the prefix queued blind by the next call; the kinds the last call's slots ran
-  int max_slots = 0;                 // launch slots a call may use (iterations + launches a problem sat out)
-  long long n_pattern_calls = 0, n_pattern_misses = 0;
+  SlotLayout slots;                  // where a lane's count slots and events sit (max_slots: create_lanes)
   std::atomic<int> busy{0};
   size_t kkt_lds = 0, eval_lds = 0;
   void (*chord_fn)(DevPlan, DevWork, int) = nullptr; // k_chord instantiated for this front size (null: chord steps off)
@@ -567,7 +558,7 @@ int qtos_set_heightfields_device(QtosPlanner *p, int n_maps, const double *d_hei
   }
   if (!p->ev_height) HIPCHK(p, hipEventCreateWithFlags(&p->ev_height, hipEventDisableTiming));
   // the last call's kernels, and whatever the host forms queued, are through with the buffer before it is written
-  if (p->seq && p->last_stream != st) HIPCHK(p, hipStreamWaitEvent(st, p->lanes[0].ev[1], 0));
+  if (p->seq && p->last_stream != st) HIPCHK(p, hipStreamWaitEvent(st, p->lanes[0].ev[EV_CALL_END], 0));
   if (p->height_pending && p->height_stream != st) HIPCHK(p, hipStreamWaitEvent(st, p->ev_height, 0));   // (an earlier copy into the same buffer)
   HIPCHK(p, hipMemcpyAsync(p->d_height, d_height, cnt * sizeof(double), hipMemcpyDeviceToDevice, st));
   HIPCHK(p, hipEventRecord(p->ev_height, st));
@@ -588,23 +579,21 @@ int qtos_set_heightfields_device(QtosPlanner *p, int n_maps, const double *d_hei
 // then ran one after the other.)
 // The word carries the sequence number of the call that queued the launch: blind iterations a call queued beyond its end
 // still store into their slots AFTER the next call of the handle has reset them (qtos_plan_submit), and a word of another
-// call must read as "no counts yet", not as "nothing left to do" (24 bits per count: qtos_planner_create limits max_batch).
+// call must read as "no counts yet", not as "nothing left to do" (call_schedule.hpp: pack_counts, read_counts).
 __global__ void k_post_counts(const int *n_active, int *host_slot, unsigned seq) {
   // the two diagnostics first (earliest launch slot a problem sat out, launch slots with work), then both counts in ONE
   // eight-byte store: the host spins on that word (qtos_plan_poll) and must never see half of it
   if (threadIdx.x == 0) {
     const unsigned long long d = (unsigned long long)(unsigned)n_active[2] | ((unsigned long long)(unsigned)n_active[3] << 32);
-    *(volatile unsigned long long *)(host_slot + 2) = d;
+    *(volatile unsigned long long *)(host_slot + SAT_OUT_AT) = d;
     __threadfence_system();
-    const unsigned long long v = (unsigned long long)((unsigned)n_active[0] & 0xffffffu) | ((unsigned long long)((unsigned)n_active[1] & 0xffffffu) << 24) |
-                                 ((unsigned long long)(seq & 0xffffu) << 48);
-    *(volatile unsigned long long *)host_slot = v;
+    *(volatile unsigned long long *)host_slot = pack_counts((unsigned)n_active[0], (unsigned)n_active[1], seq);
   }
   __threadfence_system();
 }
 
-// One launch slot of the call in flight, queued on its stream: the solve kernels named by `kinds` (bit 0 the factorising
-// kernel, bit 1 k_chord), then k_step, then (post) the counts to the host.
+// One launch slot of the call in flight, queued on its stream: the solve kernels the lane's progress names for it (c.ran[it]:
+// KIND_KKT, KIND_CHORD), then k_step, then the counts to the host where it reads them.
 //   informed  the counts of unfinished problems (n) and of problems flagged for a chord step (nc) in front of the slot are
 //             known: kinds = the kernels with work; next to a factorisation of other problems the chord solve runs on the
 //             side stream (the workgroups of the factorising kernel that belong to its problems leave at once and k_chord
@@ -612,37 +601,36 @@ __global__ void k_post_counts(const int *n_active, int *host_slot, unsigned seq)
 //   pattern   kinds = what this slot of the handle's last calls needed (QtosPlanner::pat), queued before any count of this
 //             call has come back; a problem that waits for the other kernel sits the launch out (k_step).
 //   blind     both kernels (qtos_set_speculation; each leaves at once for the problems that are not its own).
-static int queue_iteration(QtosPlanner *p, QtosPlanner::Lane &c, int it, int kinds, bool post) {
+static int queue_iteration(QtosPlanner *p, QtosPlanner::Lane &c, int it) {
   const DevPlan &D = p->dp;
+  const SlotLayout &L = p->slots;
   hipStream_t st = c.st;
-  if (!p->chord_fn) kinds &= 1;
-  const bool do_kkt = kinds & 1, do_chord = (kinds & 2) != 0;
-  c.was_kkt[it] = do_kkt;
-  c.was_chord[it] = do_chord;
+  const int kinds = c.ran[it];
+  const bool do_kkt = kinds & KIND_KKT, do_chord = (kinds & KIND_CHORD) != 0;
   const bool fork = do_kkt && do_chord;
   hipStream_t cs = fork ? c.side : st;
-  if (fork) {
-    HIPCHK(p, hipEventRecord(c.ev_fork, st));            // everything up to the previous k_step
-    HIPCHK(p, hipStreamWaitEvent(cs, c.ev_fork, 0));
-  }
+  if (fork) { HIPCHK(p, hipEventRecord(c.ev_fork, st)); HIPCHK(p, hipStreamWaitEvent(cs, c.ev_fork, 0)); }   // behind everything up to the previous k_step
   if (do_kkt) {
-    if (p->per_kernel_events) HIPCHK(p, hipEventRecord(c.ev[2 + 5 * it], st));
+    if (p->per_kernel_events) HIPCHK(p, hipEventRecord(c.ev[L.ev(it, KKT_BEGIN)], st));
     hipLaunchKernelGGL(p->kkt_fn, dim3(c.B), dim3(p->kkt_threads), p->kkt_lds, st, D, c.W, c.B);
-    if (p->per_kernel_events) HIPCHK(p, hipEventRecord(c.ev[3 + 5 * it], st));
+    if (p->per_kernel_events) HIPCHK(p, hipEventRecord(c.ev[L.ev(it, KKT_END)], st));
   }
   if (do_chord) {
-    if (p->per_kernel_events) HIPCHK(p, hipEventRecord(c.ev[4 + 5 * it], cs));
+    if (p->per_kernel_events) HIPCHK(p, hipEventRecord(c.ev[L.ev(it, CHORD_BEGIN)], cs));
     hipLaunchKernelGGL(p->chord_fn, dim3(c.B), dim3(KTC), chord_lds_bytes(p->S.n_stages, p->dp.sw_on ? p->dp.sw_steps : 0), cs, D, c.W, c.B);
-    if (p->per_kernel_events) HIPCHK(p, hipEventRecord(c.ev[5 + 5 * it], cs));
+    if (p->per_kernel_events) HIPCHK(p, hipEventRecord(c.ev[L.ev(it, CHORD_END)], cs));
   }
-  if (fork) {
-    HIPCHK(p, hipEventRecord(c.ev_join, cs));
-    HIPCHK(p, hipStreamWaitEvent(st, c.ev_join, 0));
-  }
+  if (fork) { HIPCHK(p, hipEventRecord(c.ev_join, cs)); HIPCHK(p, hipStreamWaitEvent(st, c.ev_join, 0)); }
   hipLaunchKernelGGL(k_step, dim3(c.B), dim3(ET), p->eval_lds, st, D, c.W, c.B, it, kinds);
-  if (post) hipLaunchKernelGGL(k_post_counts, dim3(1), dim3(64), 0, st, c.W.n_active, c.h_active_dev + 4 * it, p->seq);
-  if (p->per_kernel_events) HIPCHK(p, hipEventRecord(c.ev[6 + 5 * it], st));
+  if (c.reads(it + 1)) hipLaunchKernelGGL(k_post_counts, dim3(1), dim3(64), 0, st, c.W.n_active, c.h_active_dev + L.counts_at(it + 1), p->seq);
+  if (p->per_kernel_events) HIPCHK(p, hipEventRecord(c.ev[L.ev(it, SLOT_END)], st));
   return 0;
+}
+
+// A call that has ended, or failed on the way: the handle takes the next one (which opens the lanes it uses afresh).
+static int close_call(QtosPlanner *p, int rc) {
+  p->call_open = false; p->busy.store(0);
+  return rc;
 }
 
 // The part [b0, b0 + B) of the planner's workspace and of the caller's buffers, as a workspace of its own (every array is
@@ -664,183 +652,127 @@ static DevWork work_slice(const QtosPlanner *p, const DevWork &w, int b0, int *n
   return s;
 }
 
+// The launches of the call with workspace W on stream st, lane by lane.  The first failure ends it (the caller closes the call).
+static int queue_call(QtosPlanner *p, int B, DevWork W, hipStream_t st) {
+  if (hipSetDevice(p->device) != hipSuccess) return -2;
+  if (p->height_pending) {                                 // a terrain copied in on another stream (qtos_set_heightfields_device)
+    if (hipEventQuery(p->ev_height) == hipSuccess) p->height_pending = false;
+    else if (st != p->height_stream && st != p->own_stream && hipStreamWaitEvent(st, p->ev_height, 0) != hipSuccess) return -2;
+  }
+  p->call_open = true; p->call_stream = st;
+  p->seq = next_seq(p->seq);   // (blind iterations, whose late stores the number tells apart, are off by default: spec_cap 1)
+  // the report is latched here for the whole call: without it the kernels see null pointers (no history, no k_report)
+  if (!p->report) { W.hist = nullptr; W.rep = nullptr; }
+  p->last_report = p->report; p->last_B = B;
+  const DevPlan &D = p->dp;
+  const SlotLayout &L = p->slots;
+  const LaneSplit split(B, p->lane_chunk, (int)p->lanes.size());
+  p->lanes_used = split.n_used;
+  if (split.n_used > 1) HIPCHK(p, hipEventRecord(p->ev_in, st));
+  const LaunchPattern *pattern = p->pattern.serving(split.n_used, p->spec_cap);   // (null: this call does not follow it)
+  for (int j = 0; j < split.n_used; ++j) {
+    QtosPlanner::Lane &c = p->lanes[j];
+    c.b0 = split.first(j); c.B = split.size(j); c.spins = 0;
+    // the slots queued at once: the pattern's prefix, or as many blind iterations as the previous call of this handle needed (its
+    // slowest problem; qtos_set_speculation, 1 by default: the first iteration).  A batch that needs more is continued by
+    // qtos_plan_poll from the counts the iterations send back; blind launches behind the end find every problem done.
+    c.begin(pattern, blind_slots(p->last_iters, p->spec_cap, D.max_iter), L);
+    c.st = j == 0 ? st : c.own;
+    c.W = work_slice(p, W, c.b0, c.d_n_active);
+    if (j > 0) HIPCHK(p, hipStreamWaitEvent(c.st, p->ev_in, 0));
+    std::memset(c.h_active, 0xff, L.count_ints() * sizeof(int));   // no counts yet (late stores of an earlier call carry another sequence number)
+    HIPCHK(p, hipMemsetAsync(c.W.n_active, 0, 4 * sizeof(int), c.st));
+    HIPCHK(p, hipEventRecord(c.ev[EV_CALL_BEGIN], c.st));
+    hipLaunchKernelGGL(k_start, dim3(c.B), dim3(ET), p->eval_lds, c.st, D, c.W, c.B);
+    // (a call that follows the pattern reads no counts in front of the pattern's last slot and posts none)
+    if (c.reads(0)) hipLaunchKernelGGL(k_post_counts, dim3(1), dim3(64), 0, c.st, c.W.n_active, c.h_active_dev + L.counts_at(0), p->seq);
+    if (p->per_kernel_events) HIPCHK(p, hipEventRecord(c.ev[L.ev_start_end()], c.st));
+    for (int it = 0; it < c.spec; ++it)
+      if (int rc = queue_iteration(p, c, it)) return rc;
+  }
+  if (split.n_used == 1 && hipEventRecord(p->lanes[0].ev[EV_CALL_END], st) != hipSuccess) return -2;
+  p->last_stream = st;
+  return 0;
+}
+
 int qtos_plan_submit(QtosPlanner *p, int B, const double *d_start, const double *d_goal,
                      const int *d_map_id, const double *d_warm, double *d_nodes_out,
                      int *d_status_out, int *d_iters_out, double *d_viol_out, void *stream_) {
   if (!p || B < 1 || B > p->max_batch || !d_start || !d_goal || !d_nodes_out) return -1;
   int expected = 0;
   if (!p->busy.compare_exchange_strong(expected, 1)) { p->err = "the planner handle already serves a call (one call per handle at a time)"; return -5; }
-  auto fail = [&](int rc) { p->call_open = false; for (auto &L : p->lanes) L.open = false; p->busy.store(0); return rc; };
-  hipStream_t st = (hipStream_t)stream_;
-  if (hipSetDevice(p->device) != hipSuccess) return fail(-2);
-  if (p->height_pending) {                                 // a terrain copied in on another stream (qtos_set_heightfields_device)
-    if (hipEventQuery(p->ev_height) == hipSuccess) p->height_pending = false;
-    else if (st != p->height_stream && st != p->own_stream && hipStreamWaitEvent(st, p->ev_height, 0) != hipSuccess) return fail(-2);
-  }
-  p->call_open = true;
-  p->call_stream = st;
-  // 16 bits of sequence number in the count word (0xffff = the reset pattern of the slots): the number wraps after 65 534 calls
-  // of the handle.  A stale word can only be taken for this call's if a blind launch of the call 65 534 submits earlier were
-  // still to store -- but a call is submitted only after the previous one was collected (p->busy above) and a call queues at
-  // most max_iter blind launches, each a few microseconds of work once its problems are done: the launches of call n - 65 534
-  // ran tens of thousands of collected calls ago.  Blind iterations are off by default (spec_cap 1).
-  p->seq = p->seq >= 0xfffeu ? 1u : p->seq + 1u;
   DevWork W = p->wk;
   W.start = d_start; W.goal = d_goal; W.map_id = d_map_id; W.warm = d_warm;
   // (the kernel that finishes a problem writes its result: kernels.hpp export_problem)
   W.nodes_out = d_nodes_out; W.status_out = d_status_out; W.iters_out = d_iters_out; W.viol_out = d_viol_out;
   W.totals = (unsigned long long *)p->d_totals;
-  // the report is latched here for the whole call: without it the kernels see null pointers (no history, no k_report)
-  if (!p->report) { W.hist = nullptr; W.rep = nullptr; }
-  p->last_report = p->report;
-  p->last_B = B;
-  const DevPlan &D = p->dp;
-#define SUBCHK(call_) do { hipError_t e_ = (call_); if (e_ != hipSuccess) { p->err = std::string(#call_) + ": " + hipGetErrorString(e_); return fail(e_ == hipErrorOutOfMemory ? -3 : -2); } } while (0)
-  // parts: one lane up to the GPU's compute units, then as many lanes as there are (equal parts)
-  const int n_used = B <= p->lane_chunk ? 1 : std::min((int)p->lanes.size(), (B + p->lane_chunk - 1) / p->lane_chunk);
-  const int per = (B + n_used - 1) / n_used;
-  p->lanes_used = n_used;
-  if (n_used > 1) SUBCHK(hipEventRecord(p->ev_in, st));
-  const int ev_start = 2 + 5 * p->max_slots;
-  // the launch pattern serves calls of one lane (a call cut into lanes keeps the informed loop per lane)
-  const bool by_pattern = p->spec_pattern && n_used == 1 && !p->pat.empty() && p->spec_cap <= 1;
-  if (by_pattern) p->n_pattern_calls++;
-  for (int j = 0; j < n_used; ++j) {
-    QtosPlanner::Lane &c = p->lanes[j];
-    c.open = true; c.b0 = j * per; c.B = std::min(per, B - c.b0); c.spec = c.enq = c.chk = 0; c.spins = 0; c.n_informed = 0;
-    c.by_pattern = by_pattern;
-    c.st = j == 0 ? st : c.own;
-    c.W = work_slice(p, W, c.b0, c.d_n_active);
-    if (j > 0) SUBCHK(hipStreamWaitEvent(c.st, p->ev_in, 0));
-    std::memset(c.h_active, 0xff, 4 * sizeof(int) * ((size_t)p->max_slots + 1));   // no counts yet (late stores of an earlier call carry another sequence number)
-    SUBCHK(hipMemsetAsync(c.W.n_active, 0, 4 * sizeof(int), c.st));
-    SUBCHK(hipEventRecord(c.ev[0], c.st));
-    hipLaunchKernelGGL(k_start, dim3(c.B), dim3(ET), p->eval_lds, c.st, D, c.W, c.B);
-    // counts after k_start (slot max_slots of the pinned array), event ev_start; a call that follows the pattern reads no
-    // counts in front of the pattern's last slot and posts none
-    if (!by_pattern) hipLaunchKernelGGL(k_post_counts, dim3(1), dim3(64), 0, c.st, c.W.n_active, c.h_active_dev + 4 * p->max_slots, p->seq);
-    if (p->per_kernel_events) SUBCHK(hipEventRecord(c.ev[ev_start], c.st));
-    if (by_pattern) {
-      // the prefix of launch slots the handle's last two calls agree on, queued at once
-      c.spec = std::min((int)p->pat.size(), p->max_slots);
-      for (int it = 0; it < c.spec; ++it)
-        if (int rc = queue_iteration(p, c, it, p->pat[it], it + 1 == c.spec)) return fail(rc);
-      c.enq = c.chk = c.spec;     // (the first counts the host reads are those behind slot spec - 1)
-    } else {
-      // Blind iterations: as many as the previous call of this handle needed (its slowest problem), queued without a host
-      // round trip (qtos_set_speculation; 1 by default: the first iteration).  A batch that needs more is continued by
-      // qtos_plan_poll from the counts the iterations send back; blind launches behind the end find every problem done.
-      c.spec = std::max(0, std::min(std::min(p->spec_next, p->spec_cap), D.max_iter));
-      for (int it = 0; it < c.spec; ++it)
-        if (int rc = queue_iteration(p, c, it, it >= 1 ? 3 : 1, true)) return fail(rc);
-      c.enq = c.spec;
-    }
-  }
-#undef SUBCHK
-  if (n_used == 1 && hipEventRecord(p->lanes[0].ev[1], st) != hipSuccess) return fail(-2);
-  p->last_stream = st;
+  const int rc = queue_call(p, B, W, (hipStream_t)stream_);
+  return rc ? close_call(p, rc) : 0;
+}
+
+// hipSetDevice once per poll, and only in front of a launch: in a spin loop of several host threads it is a lock fight.
+static int launch_device(QtosPlanner *p, bool *device_set) {
+  if (!*device_set) HIPCHK(p, hipSetDevice(p->device));
+  *device_set = true;
   return 0;
 }
 
-// One lane as far as the counts that have arrived allow.  *lane_done: every problem of the part has handed its result over.
-static int advance_lane(QtosPlanner *p, QtosPlanner::Lane &c, bool *lane_done, bool *device_set) {
-  *lane_done = false;
-  for (;;) {
-    // counts in front of slot c.chk (behind k_start / slot c.chk - 1): the word itself says when they are there
-    // (k_post_counts stores into mapped host memory; qtos_plan_submit left -1 in every slot) -- an event query on top of
-    // it is a driver call and waits for the end-of-kernel signal of the command processor
-    const int *h = c.h_active + 4 * (c.chk == 0 ? p->max_slots : c.chk - 1);
-    const unsigned long long v = __atomic_load_n((const unsigned long long *)h, __ATOMIC_ACQUIRE);
-    if (v == ~0ull || (unsigned)(v >> 48) != p->seq) {   // nothing yet, or the late store of a blind launch of an earlier call
-      // (a failed launch never fills the slot: look at the stream now and then)
-      if ((++c.spins & 0xfffff) == 0) {
+// One lane as far as the counts that have arrived allow.  It is through (c.open goes) when every problem of the part has handed
+// its result over (export_problem; a problem out of iterations counts as finished).
+static int advance_lane(QtosPlanner *p, QtosPlanner::Lane &c, bool *device_set) {
+  for (int slot = 0;;) {
+    const LaneProgress::Act act = c.next(c.h_active, p->slots, p->seq, &slot);
+    if (act == LaneProgress::QUEUE) {
+      if (int rc = launch_device(p, device_set)) return rc;
+      if (int rc = queue_iteration(p, c, slot)) return rc;
+      if (p->lanes_used == 1) HIPCHK(p, hipEventRecord(c.ev[EV_CALL_END], c.st));   // (the end-of-call event sits behind the last launch)
+    } else if (act != LaneProgress::STEP) {
+      // Waiting: the word itself says when the counts are there (k_post_counts stores into mapped host memory) -- an event query
+      // on top of it is a driver call and waits for the end-of-kernel signal of the command processor.  A failed launch never
+      // fills the slot: look at the stream now and then.
+      if (act == LaneProgress::WAIT && (++c.spins & 0xfffff) == 0) {
         const hipError_t q = hipStreamQuery(c.st);
         if (q != hipSuccess && q != hipErrorNotReady) { p->err = std::string("hipStreamQuery: ") + hipGetErrorString(q); return -2; }
       }
       return 0;
     }
-    const int n = (int)(unsigned)(v & 0xffffffull), nc = (int)(unsigned)((v >> 24) & 0xffffffull);
-    if (n <= 0 || c.chk >= p->max_slots) {
-      // finished in front of slot c.chk (every problem has handed its result over: export_problem; a problem out of
-      // iterations counts as finished)
-      // (a call that followed the pattern learns here how many of its slots had work: h[3], the slots in which some problem
-      //  took a step; the others read every slot's counts and stop at the first without work)
-      const int slots = c.by_pattern ? std::max(0, std::min(h[3], c.chk)) : c.chk;
-      for (int j = slots; j < c.enq; ++j) { c.was_kkt[j] = 0; c.was_chord[j] = 0; }   // blind launches behind the end: no work
-      c.last_launches = slots;
-      c.last_iters = slots;
-      c.open = false;
-      *lane_done = true;
-      return 0;
-    }
-    if (c.chk < c.spec && !c.by_pattern) {
-      // a blind iteration that did run: which of its two solve kernels had work
-      c.was_kkt[c.chk] = n - nc > 0;
-      c.was_chord[c.chk] = nc > 0 && p->chord_fn && c.chk >= 1;
-    }
-    if (c.chk == c.enq) {
-      if (!*device_set) { HIPCHK(p, hipSetDevice(p->device)); *device_set = true; }
-      if (int rc = queue_iteration(p, c, c.chk, (n - nc > 0 ? 1 : 0) | (nc > 0 && c.chk >= 1 ? 2 : 0), true)) return rc;
-      c.enq++;
-      c.n_informed++;
-      if (p->lanes_used == 1) HIPCHK(p, hipEventRecord(c.ev[1], c.st));   // (the end-of-call event sits behind the last launch)
-    }
-    c.chk++;
   }
+}
+
+// The lanes of the open call as far as they get; n_open: those that are not through.
+static int advance_call(QtosPlanner *p, int *n_open) {
+  bool device_set = false;
+  for (int j = 0; j < p->lanes_used; ++j) {
+    QtosPlanner::Lane &c = p->lanes[j];
+    if (!c.open) continue;
+    if (int rc = advance_lane(p, c, &device_set)) return rc;
+    if (c.open) { ++*n_open; continue; }
+    if ((c.W.rep || j > 0) && launch_device(p, &device_set)) return -2;
+    if (c.W.rep) {   // report on: the final measures of the lane's problems, behind the lane's last launch and its end event
+      hipLaunchKernelGGL(k_report, dim3(c.B), dim3(ET), p->eval_lds, c.st, p->dp, c.W, c.B);
+      if (hipGetLastError() != hipSuccess) return -2;
+    }
+    // the caller's stream waits for the part that ran beside it
+    if (j > 0 && (hipEventRecord(c.ev_done, c.st) != hipSuccess || hipStreamWaitEvent(p->call_stream, c.ev_done, 0) != hipSuccess)) return -2;
+  }
+  if (*n_open == 0 && p->lanes_used > 1)   // end of the call: behind every part
+    if (launch_device(p, &device_set) || hipEventRecord(p->lanes[0].ev[EV_CALL_END], p->call_stream) != hipSuccess) return -2;
+  return 0;
 }
 
 int qtos_plan_poll(QtosPlanner *p, int *done) {
   if (!p || !done) return -1;
   *done = 0;
   if (!p->call_open) { *done = 1; return 0; }
-  bool device_set = false;     // (only in front of launches: hipSetDevice in a spin loop of several host threads is a lock fight)
-  auto fail = [&](int rc) { p->call_open = false; for (auto &L : p->lanes) L.open = false; p->busy.store(0); return rc; };
   int n_open = 0;
-  for (int j = 0; j < p->lanes_used; ++j) {
-    QtosPlanner::Lane &c = p->lanes[j];
-    if (!c.open) continue;
-    bool lane_done = false;
-    if (int rc = advance_lane(p, c, &lane_done, &device_set)) return fail(rc);
-    if (!lane_done) { ++n_open; continue; }
-    if (c.W.rep) {   // report on: the final measures of the lane's problems, behind the lane's last launch and its end event
-      if (!device_set) { if (hipSetDevice(p->device) != hipSuccess) return fail(-2); device_set = true; }
-      hipLaunchKernelGGL(k_report, dim3(c.B), dim3(ET), p->eval_lds, c.st, p->dp, c.W, c.B);
-      if (hipGetLastError() != hipSuccess) return fail(-2);
-    }
-    if (j > 0) {   // the caller's stream waits for the part that ran beside it
-      if (!device_set) { if (hipSetDevice(p->device) != hipSuccess) return fail(-2); device_set = true; }
-      if (hipEventRecord(c.ev_done, c.st) != hipSuccess || hipStreamWaitEvent(p->call_stream, c.ev_done, 0) != hipSuccess) return fail(-2);
-    }
-  }
+  if (int rc = advance_call(p, &n_open)) return close_call(p, rc);
   if (n_open) return 0;
-  if (p->lanes_used > 1) {   // end of the call: behind every part
-    if (!device_set && hipSetDevice(p->device) != hipSuccess) return fail(-2);
-    if (hipEventRecord(p->lanes[0].ev[1], p->call_stream) != hipSuccess) return fail(-2);
-  }
-  int iters = 0;
-  for (int j = 0; j < p->lanes_used; ++j) iters = std::max(iters, p->lanes[j].last_iters);
-  p->spec_next = std::max(1, std::min(iters, p->dp.max_iter));
-  if (p->lanes_used == 1) {
-    // The launch pattern of the next call: the kinds this call's slots ran, as far as they agree with the call before it
-    // (the first call of a handle is trusted as it is).  A problem that sat a slot of the pattern out (the code in the last
-    // count words: (1 << 20) - slot) cuts this call's observation in front of that slot -- what the slots behind it ran
-    // was the pattern's choice, not the batch's.
-    const QtosPlanner::Lane &c = p->lanes[0];
-    const int *h = c.h_active + 4 * (c.chk == 0 ? p->max_slots : c.chk - 1);
-    int n_obs = c.last_launches;
-    if (h[2] > 0) { n_obs = std::min(n_obs, (1 << 20) - h[2]); p->n_pattern_misses++; }
-    std::vector<char> obs((size_t)std::max(n_obs, 0));
-    for (int i = 0; i < n_obs; ++i) obs[i] = (char)((c.was_kkt[i] ? 1 : 0) | (c.was_chord[i] ? 2 : 0));
-    size_t k = 0;
-    if (p->obs_prev.empty()) k = obs.size();
-    else while (k < obs.size() && k < p->obs_prev.size() && obs[k] == p->obs_prev[k]) ++k;
-    p->pat.assign(obs.begin(), obs.begin() + k);
-    p->obs_prev.swap(obs);
-  }
-  p->call_open = false;
-  p->busy.store(0);
+  p->last_iters = 0;
+  for (int j = 0; j < p->lanes_used; ++j) p->last_iters = std::max(p->last_iters, p->lanes[j].last_launches);
+  // the launch pattern of the next call, from what this one's slots ran
+  if (p->lanes_used == 1) p->pattern.update(p->lanes[0].ran, p->lanes[0].last_launches, p->lanes[0].sat_out);
   *done = 1;
-  return 0;
+  return close_call(p, 0);
 }
 
 int qtos_plan_wait(QtosPlanner *p) {
@@ -870,7 +802,7 @@ int qtos_plan_totals(QtosPlanner *p, long long *converged, long long *iterations
   long long h[2] = {0, 0};
   // on the planner's own stream, behind the end event of the last call (the caller's stream may be gone by now)
   if (p->call_open) HIPCHK(p, qtos_plan_wait(p) ? hipErrorUnknown : hipSuccess);
-  HIPCHK(p, hipStreamWaitEvent(p->own_stream, p->lanes[0].ev[1], 0));
+  HIPCHK(p, hipStreamWaitEvent(p->own_stream, p->lanes[0].ev[EV_CALL_END], 0));
   HIPCHK(p, hipMemcpyAsync(h, p->d_totals, sizeof(h), hipMemcpyDeviceToHost, p->own_stream));
   if (reset) HIPCHK(p, hipMemsetAsync(p->d_totals, 0, sizeof(h), p->own_stream));
   HIPCHK(p, hipStreamSynchronize(p->own_stream));
@@ -903,33 +835,47 @@ int qtos_plan_batch(QtosPlanner *p, int B, const double *start, const double *go
   return 0;
 }
 
-// Timing of the last call from the HIP events of its lanes: KKT (chord) launches and their seconds summed over the lanes,
+// Timing of the last call from the HIP events of its lanes.  The events are there once the call's end event is.
+static int timing_events(QtosPlanner *p) {
+  if (!p->per_kernel_events) { p->err = "per-kernel events are off (qtos_set_kernel_events)"; return -1; }
+  HIPCHK(p, hipSetDevice(p->device));
+  HIPCHK(p, hipEventSynchronize(p->lanes[0].ev[EV_CALL_END]));
+  return 0;
+}
+// Launches of one solve kernel (kind: KIND_KKT between KKT_BEGIN and KKT_END, KIND_CHORD between CHORD_BEGIN and CHORD_END) and
+// their seconds, summed over the lanes.
+static int kind_timing(QtosPlanner *p, int kind, SlotEvent begin, SlotEvent end, double *seconds, int *launches) {
+  if (int rc = timing_events(p)) return rc;
+  double t = 0;
+  int nl = 0;
+  for (int j = 0; j < p->lanes_used; ++j) {
+    const QtosPlanner::Lane &L = p->lanes[j];
+    for (int i = 0; i < L.last_launches; ++i) {
+      if (!(L.ran[i] & kind)) continue;
+      float ms = 0;
+      HIPCHK(p, hipEventElapsedTime(&ms, L.ev[p->slots.ev(i, begin)], L.ev[p->slots.ev(i, end)]));
+      t += ms * 1e-3;
+      ++nl;
+    }
+  }
+  if (seconds) *seconds = t;
+  if (launches) *launches = nl;
+  return 0;
+}
+
 // total = first kernel of lane 0 to the end of the call, iterations = the slowest lane's.
 int qtos_last_timing(QtosPlanner *p, double *kkt_seconds, int *kkt_launches, double *total_seconds, int *iterations) {
   if (!p) return -1;
-  if (!p->per_kernel_events) { p->err = "per-kernel events are off (qtos_set_kernel_events)"; return -1; }
-  HIPCHK(p, hipSetDevice(p->device));
-  HIPCHK(p, hipEventSynchronize(p->lanes[0].ev[1]));
-  double kkt = 0;
-  int n_kkt = 0, iters = 0;
-  for (int j = 0; j < p->lanes_used; ++j) {
-    const QtosPlanner::Lane &L = p->lanes[j];
-    iters = std::max(iters, L.last_iters);
-    for (int i = 0; i < L.last_launches; ++i) {
-      if (!L.was_kkt[i]) continue;
-      float ms = 0;
-      HIPCHK(p, hipEventElapsedTime(&ms, L.ev[2 + 5 * i], L.ev[3 + 5 * i]));
-      kkt += ms * 1e-3;
-      ++n_kkt;
-    }
-  }
+  if (int rc = kind_timing(p, KIND_KKT, KKT_BEGIN, KKT_END, kkt_seconds, kkt_launches)) return rc;
   float tot = 0;
-  HIPCHK(p, hipEventElapsedTime(&tot, p->lanes[0].ev[0], p->lanes[0].ev[1]));
-  if (kkt_seconds) *kkt_seconds = kkt;
-  if (kkt_launches) *kkt_launches = n_kkt;
+  HIPCHK(p, hipEventElapsedTime(&tot, p->lanes[0].ev[EV_CALL_BEGIN], p->lanes[0].ev[EV_CALL_END]));
   if (total_seconds) *total_seconds = tot * 1e-3;
-  if (iterations) *iterations = iters;
+  if (iterations) *iterations = p->last_iters;
   return 0;
+}
+
+int qtos_last_timing_chord(QtosPlanner *p, double *chord_seconds, int *chord_launches) {
+  return p ? kind_timing(p, KIND_CHORD, CHORD_BEGIN, CHORD_END, chord_seconds, chord_launches) : -1;
 }
 
 // Where the time of the last call went, from the same events (lane 0; one lane per call is what bench.py times):
@@ -944,44 +890,43 @@ int qtos_last_timing(QtosPlanner *p, double *kkt_seconds, int *kkt_launches, dou
 //   qtos_last_timing_chord's numbers: one call instead of three in a timed loop)
 int qtos_last_timing_detail(QtosPlanner *p, double *out, int n_out) {
   if (!p || !out || n_out < 10) return -1;
-  if (!p->per_kernel_events) { p->err = "per-kernel events are off (qtos_set_kernel_events)"; return -1; }
-  HIPCHK(p, hipSetDevice(p->device));
-  HIPCHK(p, hipEventSynchronize(p->lanes[0].ev[1]));
+  if (int rc = timing_events(p)) return rc;
   const QtosPlanner::Lane &L = p->lanes[0];
-  const int ev_start = 2 + 5 * p->max_slots;
   auto ms = [&](hipEvent_t a, hipEvent_t b, double *d) { float t = 0; hipError_t e = hipEventElapsedTime(&t, a, b); *d = t * 1e-3; return e; };
   double tot = 0, start = 0, solve = 0, step = 0, gaps = 0, kkt_s = 0, chord_s = 0;
   int kkt_n = 0, chord_n = 0;
-  HIPCHK(p, ms(L.ev[0], L.ev[1], &tot));
-  HIPCHK(p, ms(L.ev[0], L.ev[ev_start], &start));
-  hipEvent_t prev = L.ev[ev_start];
+  HIPCHK(p, ms(L.ev[EV_CALL_BEGIN], L.ev[EV_CALL_END], &tot));
+  HIPCHK(p, ms(L.ev[EV_CALL_BEGIN], L.ev[p->slots.ev_start_end()], &start));
+  hipEvent_t prev = L.ev[p->slots.ev_start_end()];
   for (int i = 0; i < L.enq; ++i) {
-    if (!L.was_kkt[i] && !L.was_chord[i] && i >= L.last_launches) continue;   // (queued behind the end: nothing ran)
-    hipEvent_t b0 = L.was_kkt[i] ? L.ev[2 + 5 * i] : (L.was_chord[i] ? L.ev[4 + 5 * i] : nullptr);
+    const bool kkt = L.ran[i] & KIND_KKT, chord = (L.ran[i] & KIND_CHORD) != 0;
+    auto ev = [&](SlotEvent e) { return L.ev[p->slots.ev(i, e)]; };
+    if (!kkt && !chord && i >= L.last_launches) continue;   // (queued behind the end: nothing ran)
+    hipEvent_t b0 = kkt ? ev(KKT_BEGIN) : (chord ? ev(CHORD_BEGIN) : nullptr);
     double g = 0, sk = 0, sc = 0, st = 0;
     if (b0) {
       HIPCHK(p, ms(prev, b0, &g));
-      if (L.was_kkt[i]) HIPCHK(p, ms(b0, L.ev[3 + 5 * i], &sk));
-      if (L.was_chord[i]) HIPCHK(p, ms(b0, L.ev[5 + 5 * i], &sc));
+      if (kkt) HIPCHK(p, ms(b0, ev(KKT_END), &sk));
+      if (chord) HIPCHK(p, ms(b0, ev(CHORD_END), &sc));
       if (i < L.last_launches) {
-        if (L.was_kkt[i]) { kkt_s += sk; ++kkt_n; }
-        if (L.was_chord[i]) { double own = sc; if (L.was_kkt[i]) HIPCHK(p, ms(L.ev[4 + 5 * i], L.ev[5 + 5 * i], &own)); chord_s += own; ++chord_n; }
+        if (kkt) { kkt_s += sk; ++kkt_n; }
+        if (chord) { double own = sc; if (kkt) HIPCHK(p, ms(ev(CHORD_BEGIN), ev(CHORD_END), &own)); chord_s += own; ++chord_n; }
       }
       const double sv = std::max(sk, sc);
       double whole = 0;
-      HIPCHK(p, ms(b0, L.ev[6 + 5 * i], &whole));
+      HIPCHK(p, ms(b0, ev(SLOT_END), &whole));
       st = std::max(0.0, whole - sv);
       gaps += std::max(0.0, g); solve += sv; step += st;
     } else {
-      HIPCHK(p, ms(prev, L.ev[6 + 5 * i], &st));
+      HIPCHK(p, ms(prev, ev(SLOT_END), &st));
       step += st;
     }
-    prev = L.ev[6 + 5 * i];
+    prev = ev(SLOT_END);
   }
   gaps += std::max(0.0, tot - start - solve - step - gaps);
   out[0] = tot; out[1] = start; out[2] = solve; out[3] = step; out[4] = gaps;
   out[5] = L.last_launches; out[6] = L.spec; out[7] = L.n_informed;
-  out[8] = (double)p->n_pattern_calls; out[9] = (double)p->n_pattern_misses;
+  out[8] = (double)p->pattern.calls; out[9] = (double)p->pattern.misses;
   if (n_out >= 14) { out[10] = kkt_s; out[11] = kkt_n; out[12] = chord_s; out[13] = chord_n; }
   return 0;
 }
@@ -1050,8 +995,8 @@ int qtos_set_kernel_events(QtosPlanner *p, int on) {
 
 int qtos_set_pattern_speculation(QtosPlanner *p, int on) {
   if (!p) return -1;
-  p->spec_pattern = on != 0;
-  if (!on) { p->pat.clear(); p->obs_prev.clear(); }
+  p->pattern.on = on != 0;
+  if (!on) p->pattern.clear();
   return 0;
 }
 
@@ -1060,28 +1005,6 @@ int qtos_env(const QtosPlanner *p, char *buf, int n) {
   const std::string d = p->env.describe();
   snprintf(buf, (size_t)n, "%s", d.c_str());
   return (int)d.size();
-}
-
-int qtos_last_timing_chord(QtosPlanner *p, double *chord_seconds, int *chord_launches) {
-  if (!p) return -1;
-  if (!p->per_kernel_events) { p->err = "per-kernel events are off (qtos_set_kernel_events)"; return -1; }
-  HIPCHK(p, hipSetDevice(p->device));
-  HIPCHK(p, hipEventSynchronize(p->lanes[0].ev[1]));
-  double t = 0;
-  int nl = 0;
-  for (int j = 0; j < p->lanes_used; ++j) {
-    const QtosPlanner::Lane &L = p->lanes[j];
-    for (int i = 0; i < L.last_launches; ++i) {
-      if (!L.was_chord[i]) continue;
-      float ms = 0;
-      HIPCHK(p, hipEventElapsedTime(&ms, L.ev[4 + 5 * i], L.ev[5 + 5 * i]));
-      t += ms * 1e-3;
-      ++nl;
-    }
-  }
-  if (chord_seconds) *chord_seconds = t;
-  if (chord_launches) *chord_launches = nl;
-  return 0;
 }
 
 #include "window_api.hpp"
@@ -1639,7 +1562,7 @@ int qtos_planner_create_checked(const QtosParams *params, int max_batch, int dev
                                 QtosPlanner **out, QtosSelftest *tried, int max_tried, int *n_tried) {
   if (n_tried) *n_tried = 0;
   if (out) *out = nullptr;
-  if (!params || !out || max_batch < 1 || max_batch >= (1 << 24) || (max_tried > 0 && !tried) || max_tried < 0) return -1;
+  if (!params || !out || max_batch < 1 || max_batch >= MAX_BATCH_LIMIT || (max_tried > 0 && !tried) || max_tried < 0) return -1;
   const QtosEnv env = QtosEnv::parse();
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= device) {   // (before any analysis: nothing can be tested)
