@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 
 #include "call_schedule.hpp"
+#include "kkt_lds.hpp"
 #include "model.hpp"
 #include "symbolic.hpp"
 
@@ -1050,7 +1051,6 @@ __global__ __launch_bounds__(ET) void k_start(DevPlan P, DevWork W, int B) {
 // Building blocks of the KKT kernels (kkt2.hpp: k_kkt2, k_chord): LDS-only barrier, the in-register LDL^T of a 16 x 16 pivot
 // block, the assembly of a stage's records.
 constexpr int KT = 512;    // (record limits of the prefetch path are stated in units of it: qtos_planner_create)
-constexpr int PLD = PIV + 1;
 __device__ __forceinline__ int tri(int r, int c) { return ((r * (r + 1)) >> 1) + c; }  // c <= r
 __device__ __forceinline__ int trs(int a, int b) { return a >= b ? tri(a, b) : tri(b, a); }
 

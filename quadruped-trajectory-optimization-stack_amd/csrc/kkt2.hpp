@@ -40,56 +40,14 @@ struct Kkt2Cfg {
   static constexpr int MAXT = (NTILE + NU - 1) / NU;
   static constexpr int NSV = 16 - NT;            // service waves of the AB phase
   static constexpr int NH = NT <= 8 ? 2 : 1;     // backward pass: waves per row tile
-  static constexpr int FR = (F + 63) & ~63;      // by-slot arrays padded to whole waves
+  static constexpr int FR = Kkt2Lds::of(F).FR;   // by-slot arrays padded to whole waves
 };
 
-// LDS layout (doubles)
+// LDS layout: kkt_lds.hpp states it; the kernels read it by value (a static object of it becomes a device global they load from)
 template <int F>
 struct Kkt2Layout {
-  using CF = Kkt2Cfg<F>;
-  static constexpr int PSZ = (F + 1) * PLD;
-  static constexpr int LIB = 0;                          // 2 x 16 x PLD   L^-1 (current / next)
-  static constexpr int DVB = LIB + 2 * PIV * PLD;        // 2 x 16         1 / d
-  static constexpr int DGB = DVB + 2 * PIV;              // 3 x 16         pivot diagonals (ring)
-  static constexpr int UF = DGB + 3 * PIV;               // FR             accumulated rhs updates
-  static constexpr int XS = UF + CF::FR;                 // FR             solution by slot (backward)
-  static constexpr int RED = XS + CF::FR;                // 2 x 16 x 16 partial sums + 64 dummy slots
-  static constexpr int PSB = RED + 2 * 16 * PIV + 64;    // 3 x 16 ints    pivot slots (ring)
-  static constexpr int HIB = PSB + 3 * PIV / 2;          // 4 ints
-  static constexpr int JM = HIB + 2;                     // 2 x FR ints    slot -> pivot index
-  static constexpr int PM = JM + CF::FR;                 // 2 x 8 ints     pivot-slot bit masks
-  static constexpr int MIV = PM + 8;                     // 16 x PLD       (L D L^T)^-1 of the current pivot block
-  static constexpr int PB = MIV + PIV * PLD;             // 3 panels of (F+1) x PLD: P_k / P_k+1 alternate in 0 and 2, 1 = operand A of the update
-  static constexpr bool VP = F <= 128;                   // update as  U -= V P^T  (operand B in a fourth panel: no room for it on larger fronts)
-  static constexpr int PMB = PB + 3 * PSZ;               // F x PLD: rows of P_k with those of the next pivots blanked
-  static constexpr int VAR = (PMB + (VP ? F * PLD : 0) + 1) & ~1;   // dbuf, then (ints) sbuf, hiall, then the cells A
+  static constexpr Kkt2Lds at() { return Kkt2Lds::of(F); }
 };
-// record buffers: a front of up to 128 slots has two of them, filled by LDS-DMA (1 KB per wave instruction: sizes
-// in 1 KB granules); larger fronts have one, filled through prefetch registers
-__host__ __device__ inline size_t kkt2_dbuf_doubles(int F, int max_drec) {
-  return F <= 128 ? (((size_t)max_drec * 8 + 1023) & ~(size_t)1023) / 8 : (((size_t)max_drec + 1) & ~(size_t)1);
-}
-__host__ __device__ inline size_t kkt2_sbuf_ints(int F, int max_srec) {
-  return F <= 128 ? (((size_t)max_srec * 4 + 1023) & ~(size_t)1023) / 4 : (((size_t)max_srec + 3) & ~(size_t)3);
-}
-// what the backward sweep of k_kkt2 / k_kkt3 keeps in LDS in front of the helper waves' tables (sweep_ds_lds_bytes)
-inline size_t kkt2_sweep_base_bytes(int F, int NS) {
-  const int FR = (F + 63) & ~63;
-  const size_t fixed = 2 * PIV * PLD + 2 * PIV + 3 * PIV + 2 * (size_t)FR + 2 * 16 * PIV + 64 + 3 * PIV / 2 + 2 + FR + 8 + PIV * PLD;
-  return fixed * sizeof(double) + (size_t)NS * 12 * sizeof(int);
-}
-inline size_t kkt2_lds_bytes(int F, int NS, int max_srec, int max_drec, int n_cells) {
-  const int FR = (F + 63) & ~63, PSZ = (F + 1) * PLD;
-  const size_t fixed = 2 * PIV * PLD + 2 * PIV + 3 * PIV + 2 * (size_t)FR + 2 * 16 * PIV + 64 + 3 * PIV / 2 + 2 + FR + 8 + PIV * PLD;
-  size_t o = (fixed + 3 * (size_t)PSZ + (F <= 128 ? (size_t)F * PLD : 0) + 1) & ~(size_t)1;
-  const size_t nbuf = F <= 128 ? 2 : 1;
-  o += nbuf * kkt2_dbuf_doubles(F, max_drec);
-  size_t oi = 2 * o + nbuf * kkt2_sbuf_ints(F, max_srec) + ((((size_t)NS + 1) + 3) & ~(size_t)3);
-  oi += 2 * (((size_t)n_cells + 1) & ~(size_t)1);
-  // (the backward pass keeps NS x 12 ints of sweep tables where the panels were)
-  const size_t sweep = fixed * sizeof(double) + (size_t)NS * 12 * sizeof(int);
-  return oi * sizeof(int) > sweep ? oi * sizeof(int) : sweep;
-}
 
 // pivot-slot mask of up to 256 bits: lane l holds word l & 7
 struct Mask256 {
@@ -181,7 +139,7 @@ struct SweepDs {
   const double *g, *s;
   double *dbg;         // diagnostic build: cycles of the helper waves' turns and of the chain wave's step parts (sweep_backward_early)
 };
-constexpr int SW_W0 = 13, SW_NW = 3, SW_ROUND = 16, SW_RU = 8;
+constexpr int SW_W0 = 13, SW_NW = 3, SW_RU = 8;   // (SW_ROUND: kkt_lds.hpp)
 typedef int swi4_t __attribute__((ext_vector_type(4)));
 typedef int swi2_t __attribute__((ext_vector_type(2)));
 #ifdef QTOS_STAMPS
@@ -194,10 +152,6 @@ struct SwSlot {
   swi4_t c;    // positions of the lane's entries, 16 bits each (sw_c16)
   swi2_t cr;
 };
-// LDS behind the sweep tables: the solution by position (NS x 16 doubles), then the rounds' rows (first four ints of a SwTask)
-__host__ __device__ inline size_t sweep_ds_lds_bytes(int NS, int sw_steps) {
-  return sw_steps > 0 ? 16 + (size_t)NS * PIV * sizeof(double) + (size_t)sw_steps * SW_ROUND * 16 : 0;
-}
 // T = the first four ints of a SwTask: goff, n, row, c16_off
 __device__ __forceinline__ void sw_load(const DevPlan &P, const SweepDs &sd, const swi4_t &T, SwSlot &S, int q) {
   const double *Gr = sd.G + T[0];
@@ -303,7 +257,7 @@ __device__ __forceinline__ void sweep_backward(const DevPlan &P, const double *_
     }
   };
   if (lane < PIV) { red[wv * PIV + lane] = 0.0; red[256 + wv * PIV + lane] = 0.0; }   // (the last stage has no rows besides its pivots)
-  swi4_t *swt = (swi4_t *)(xp + NS * PIV);   // (16-byte aligned: the callers' xp is)
+  swi4_t *swt = (swi4_t *)sweep_rounds(xp, NS);   // (16-byte aligned: the callers' xp is)
   if (HELP && P.sw_on)
     for (int i = wv * 64 + lane; i < P.sw_steps * SW_ROUND; i += NTHR) swt[i] = *(const swi4_t *)(P.sw_tasks + i);
   // waves NT+1 .. 15 have no rows: they only meet the barriers (a SIMD has one vector ALU: what they would execute on
@@ -451,7 +405,7 @@ __device__ __forceinline__ void sweep_backward_early(const DevPlan &P, const dou
     }
   };
   if (lane < PIV) { red[wv * PIV + lane] = 0.0; red[256 + wv * PIV + lane] = 0.0; }   // (the last stage has no rows besides its pivots)
-  swi4_t *swt = (swi4_t *)(xp + NS * PIV);   // (16-byte aligned: the callers' xp is)
+  swi4_t *swt = (swi4_t *)sweep_rounds(xp, NS);   // (16-byte aligned: the callers' xp is)
   if (HELP && P.sw_on)
     for (int i = wv * 64 + lane; i < P.sw_steps * SW_ROUND; i += KT2) swt[i] = *(const swi4_t *)(P.sw_tasks + i);
   // waves NT+1 .. 15 have no rows: they only meet the barriers (a SIMD has one vector ALU: what they would execute on
@@ -640,8 +594,6 @@ template <int F>
 struct Kkt2Ctx {
   using CF = Kkt2Cfg<F>;
   using LY = Kkt2Layout<F>;
-  // record buffers: [dbuf 0][dbuf 1][sbuf 0][sbuf 1] with LDS-DMA (record s lives in buffer s & 1), one of each without
-  static constexpr int NBUF = F <= 128 ? 2 : 1;
   double *lds;
   int li, lk;
   double *Lib, *dvb, *dgb, *UF, *xs, *red, *PB, *Minv;
@@ -667,16 +619,14 @@ struct Kkt2Ctx {
   __device__ __forceinline__ Kkt2Ctx(double *lds_, const DevPlan &P, const DevWork &W, int b, int wv, int li_, int lk_)
       : lds(lds_), li(li_), lk(lk_) {
     const int NS = P.n_stages;
-    Lib = lds + LY::LIB; dvb = lds + LY::DVB; dgb = lds + LY::DGB; UF = lds + LY::UF; xs = lds + LY::XS;
-    red = lds + LY::RED; PB = lds + LY::PB; Minv = lds + LY::MIV;
-    psb = (int *)(lds + LY::PSB); hib = (int *)(lds + LY::HIB);
-    pm = (unsigned *)(lds + LY::PM);
-    jmb = (unsigned char *)(lds + LY::JM);
-    dstride = (int)kkt2_dbuf_doubles(F, P.max_drec); sstride = (int)kkt2_sbuf_ints(F, P.max_srec);
-    dbuf0 = lds + LY::VAR;
-    sbuf0 = (int *)(dbuf0 + NBUF * dstride);
-    hiall = sbuf0 + NBUF * sstride;
-    A = (double *)(hiall + ((NS + 4) & ~3));
+    Lib = lds + LY::at().LIB; dvb = lds + LY::at().DVB; dgb = lds + LY::at().DGB; UF = lds + LY::at().UF; xs = lds + LY::at().XS;
+    red = lds + LY::at().RED; PB = lds + LY::at().PB; Minv = lds + LY::at().MIV;
+    psb = (int *)(lds + LY::at().PSB); hib = (int *)(lds + LY::at().HIB);
+    pm = (unsigned *)(lds + LY::at().PM);
+    jmb = (unsigned char *)(lds + LY::at().JM);
+    const Kkt2Lds::Buffers buf = LY::at().buffers(lds + LY::at().VAR, NS, P.max_srec, P.max_drec);
+    dstride = buf.dstride; sstride = buf.sstride;
+    dbuf0 = buf.dbuf0; sbuf0 = buf.sbuf0; hiall = buf.hiall; A = buf.cells;
     stream = W.stream + (size_t)b * P.stream_len;
     panel = W.panel + (size_t)b * P.panel_stride;
     dx = W.dx + (size_t)b * P.n_sol;
@@ -816,10 +766,10 @@ __device__ __forceinline__ void kkt2_ab_tile(const Kkt2Ctx<F> &cx, int k, int R,
   for (int s4 = 0; s4 < 4; ++s4) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(vt[s4], npp[s4], acc, 0, 0, 0);   // acc -= V P[piv]^T
 #pragma unroll
   for (int g = 0; g < 4; ++g) cx.A[aidx[g]] = 0.0;   // retired (the zero cell stays zero)
-  if constexpr (LY::VP) {
+  if constexpr (LY::at().VP) {
     // operands of the Schur update: -V (accumulator layout -> row-major) and the raw rows, next pivots' rows blanked
     const bool myrowpiv = has_next && ((grp16(m1, R) >> li) & 1u);
-    double *Pm = cx.lds + LY::PMB;
+    double *Pm = cx.lds + LY::at().PMB;
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       Yk[(16 * R + li) * PLD + lk + 4 * g] = myrowpiv ? 0.0 : -vt[g];
@@ -898,12 +848,12 @@ __device__ __forceinline__ void kkt2_update(const Kkt2Ctx<F> &cx, Kkt2Stamps &st
   const unsigned char *jm2 = cx.jmb + (k & 1) * FR;
   double *Xnn = Pk;   // the panel of stage k is dead: it receives the columns of stage k+2
   double dv4[4];
-  if constexpr (!LY::VP) {
+  if constexpr (!LY::at().VP) {
     const double *dik = cx.dvb + (k & 1) * PIV;
 #pragma unroll
     for (int s4 = 0; s4 < 4; ++s4) dv4[s4] = -dik[lk + 4 * s4];
   }
-  const double *Bop = LY::VP ? cx.lds + LY::PMB : Yk;
+  const double *Bop = LY::at().VP ? cx.lds + LY::at().PMB : Yk;
   int rcs[MAXT2];
 #pragma unroll
   for (int t = 0; t < MAXT2; ++t) { rcs[t] = cx.tRC[t]; asm volatile("" : "+s"(rcs[t])); }
@@ -933,7 +883,7 @@ __device__ __forceinline__ void kkt2_update(const Kkt2Ctx<F> &cx, Kkt2Stamps &st
       if (t + 1 < MAXT2) tile_loads(rcs[t + 1], wa[(t + 1) & 1], pbv[(t + 1) & 1]);
 #pragma unroll
       for (int s4 = 0; s4 < 4; ++s4)
-        U[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(LY::VP ? wa[t & 1][s4] : wa[t & 1][s4] * dv4[s4], pbv[t & 1][s4], U[t], 0, 0, 0);
+        U[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(LY::at().VP ? wa[t & 1][s4] : wa[t & 1][s4] * dv4[s4], pbv[t & 1][s4], U[t], 0, 0, 0);
     }
   }
   st.mark(5);
@@ -979,12 +929,12 @@ __device__ __forceinline__ void kkt2_update(const Kkt2Ctx<F> &cx, Kkt2Stamps &st
 template <int F>
 __device__ __forceinline__ void kkt2_backward(const Kkt2Ctx<F> &cx, const DevPlan &P, const DevWork &W, int b, int tid, int wv, int lane) {
   const int NS = P.n_stages;
-  int *nxp = (int *)cx.PB;   // (the panels are dead)
+  int *nxp = (int *)(cx.lds + Kkt2Layout<F>::at().sweep_tables());   // (the panels are dead)
   for (int i = tid; i < NS * 4; i += KT2) nxp[i] = P.nxt_pack[i];
   for (int i = tid; i < NS * 8; i += KT2) nxp[NS * 4 + i] = (int)P.amask2[i];
   __syncthreads();
   const SweepDs sd = {W.stream + (size_t)b * P.stream_len, W.ds + (size_t)b * P.n_cons, W.g + (size_t)b * P.n_cons, W.s + (size_t)b * P.n_cons, W.trace ? W.trace + ((size_t)b * (P.max_iter + 1) + 64) * 4 : nullptr};
-  sweep_backward<F>(P, cx.panel, cx.dx, W.sol + (size_t)b * P.n_stages * PIV, cx.xs, cx.red, nxp, wv, lane, cx.lds + ((Kkt2Layout<F>::PB + NS * 6 + 1) & ~1), sd);
+  sweep_backward<F>(P, cx.panel, cx.dx, W.sol + (size_t)b * P.n_stages * PIV, cx.xs, cx.red, nxp, wv, lane, cx.lds + Kkt2Layout<F>::at().sweep_xp(NS), sd);
 }
 
 template <int F, bool CONT>
@@ -994,11 +944,11 @@ __global__ __launch_bounds__(KT2) void k_kkt2(DevPlan P, DevWork W, int B) {
   extern __shared__ double lds[];
   using CF = Kkt2Cfg<F>;
   using LY = Kkt2Layout<F>;
-  constexpr int NT = CF::NT, NU = CF::NU, MAXT2 = CF::MAXT, NSV = CF::NSV, FR = CF::FR, PSZ = LY::PSZ;
+  constexpr int NT = CF::NT, NU = CF::NU, MAXT2 = CF::MAXT, NSV = CF::NSV, FR = CF::FR, PSZ = LY::at().PSZ;
   const int tid = threadIdx.x, NS = P.n_stages, n = P.n_sol;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, li = lane & 15, lk = lane >> 4;
   const Kkt2Ctx<F> cx(lds, P, W, b, wv, li, lk);
-  constexpr bool DMA = F <= 128;   // records by LDS-DMA into two buffers, else through prefetch registers into one
+  constexpr bool DMA = LY::at().NBUF == 2;   // records by LDS-DMA into two buffers, else through prefetch registers into one
   double *dbuf = cx.dbuf0;
   int *sbuf = cx.sbuf0;
   d4_t U[MAXT2];
@@ -1123,7 +1073,7 @@ __global__ __launch_bounds__(KT2) void k_kkt2(DevPlan P, DevWork W, int B) {
       if (sv == 0) {
         kkt2_ab_rhs(cx, k, lane, li, lk, Pk, Xn, has_next, prow_next, rc_cur, true);
       }
-      else if (!LY::VP && sv < NT) {
+      else if (!LY::at().VP && sv < NT) {
         // Y = P L^-T of row tile R = sv for its tile wave
         const int R = sv;
         const double *Lik = cx.Lib + (k & 1) * PIV * PLD;
@@ -1245,7 +1195,6 @@ __global__ __launch_bounds__(KT2) void k_kkt2(DevPlan P, DevWork W, int B) {
 //   waves 1 .. NT   u -= V_{k-1} p_{k-1} on the other rows of row tile wv - 1, one stage behind
 //   wave NT + 1     w_{k-1} = B_{k-1}^-1 p_{k-1}
 constexpr int KTC = 1024;
-inline size_t chord_lds_bytes(int NS, int sw_steps) { return sizeof(int) * (size_t)NS * 12 + sweep_ds_lds_bytes(NS, sw_steps); }   // sweep tables; solution by position and rounds of the helper waves
 template <int F>
 __global__ __launch_bounds__(KTC) void k_chord(DevPlan P, DevWork W, int B) {
   const int b = blockIdx.x;
@@ -1340,7 +1289,7 @@ __global__ __launch_bounds__(KTC) void k_chord(DevPlan P, DevWork W, int B) {
   }
   __syncthreads();   // the w entries written above are read back below (same workgroup: visible after the barrier)
   const SweepDs sd = {W.stream + (size_t)b * P.stream_len, W.ds + (size_t)b * P.n_cons, W.g + (size_t)b * P.n_cons, W.s + (size_t)b * P.n_cons, W.trace ? W.trace + ((size_t)b * (P.max_iter + 1) + 64) * 4 : nullptr};
-  sweep_backward_early<F, true>(P, panel, dx, W.sol + (size_t)b * P.n_stages * PIV, xs, red, nxp, wv, lane, (double *)(nxp + ((NS * 12 + 3) & ~3)), sd);
+  sweep_backward_early<F, true>(P, panel, dx, W.sol + (size_t)b * P.n_stages * PIV, xs, red, nxp, wv, lane, chord_xp(nxp, NS), sd);
 }
 
 // =================================================================================================

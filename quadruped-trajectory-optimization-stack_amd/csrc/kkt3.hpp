@@ -44,14 +44,15 @@ __device__ __forceinline__ void assemble_targets(double *A, const int *sbuf, con
 }
 template <int F, int MODE>
 __global__ __launch_bounds__(KT2) void k_kkt3(DevPlan P, DevWork W, int B) {
-  static_assert(F <= 128 && F % 16 == 0, "k_kkt3: fronts of up to 128 slots (waves 9 .. 15 must be free in phase AB)");
+  static_assert(Kkt2Cfg<F>::NT <= 8 && F % 16 == 0, "k_kkt3: fronts of up to 128 slots (waves 9 .. 15 must be free in phase AB)");
+  static_assert(Kkt2Layout<F>::at().NBUF == 2, "k_kkt3: the records by LDS-DMA into two buffers");
   static_assert(MODE == 1, "k_kkt3: MODE 0 left the library (scratch/experiments/kkt3_mode0.hpp)");
   const int b = blockIdx.x;
   if (b >= B || W.done[b] || W.chord[b] == 1) return;   // (a problem flagged for a chord step is k_chord's)
   extern __shared__ double lds[];
   using CF = Kkt2Cfg<F>;
   using LY = Kkt2Layout<F>;
-  constexpr int NT = CF::NT, NU = CF::NU, MAXT2 = CF::MAXT, FR = CF::FR, PSZ = LY::PSZ;
+  constexpr int NT = CF::NT, NU = CF::NU, MAXT2 = CF::MAXT, FR = CF::FR, PSZ = LY::at().PSZ;
   // targets of the gather table assembled in phase AB by the waves that idle there.  Fronts of up to 96 slots: none -- with the
   // records of round 5 (reduced swings) and six tile waves the idle waves' assembly lengthens phase AB by more than it takes off
   // phase C: -0.6 % (trot) .. -1.5 % (walk, knots200, reference_compat, exp_5, mixed) per launch without it (round 6,

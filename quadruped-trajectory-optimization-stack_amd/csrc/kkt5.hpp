@@ -42,9 +42,9 @@ struct Kkt5Cfg {
   static constexpr int NT = F / 16;
   static_assert(F % 16 == 0 && NT >= 2 && NT <= 9, "k_kkt5: fronts of 32 .. 144 slots");
   static constexpr int NSVC = KKT5_WAVES - 1 - NT;   // service waves
-  static constexpr int FR = (F + 63) & ~63;
-  static constexpr int PR = F + 2;                   // rows of a panel: the slots, the right-hand side, a row of zeros
-  static constexpr int PSZ = PR * PLD;
+  static constexpr int FR = Kkt5Lds::of(F).FR;
+  static constexpr int PR = Kkt5Lds::of(F).PR;       // rows of a panel: the slots, the right-hand side, a row of zeros
+  static constexpr int PSZ = Kkt5Lds::of(F).PSZ;
   // Row tile of a wave, -1: none.  The factor wave (0) shares its SIMD with waves 4 and 8: a SIMD has one vector ALU and it
   // stands still while an f64 matrix instruction runs, so the tiles go to the other three SIMDs heaviest first (row tile R
   // has R + 1 Schur tiles), serpentine, and the two lightest rows to waves 4 and 8.
@@ -79,43 +79,11 @@ struct Kkt5Cfg {
   }
 };
 
-// LDS layout (doubles)
+// LDS layout: kkt_lds.hpp states it; read by value, as Kkt2Layout
 template <int F>
 struct Kkt5Layout {
-  using CF = Kkt5Cfg<F>;
-  static constexpr int MIV = 0;                         // 2 x 16 x PLD   A11^-1, S22^-1 of the pair being eliminated
-  static constexpr int L21 = MIV + 2 * PIV * PLD;       // 16 x PLD       L21 = A21 A11^-1, row major
-  static constexpr int LIN = L21 + PIV * PLD;           // 16 x PLD       scratch of the factor wave (L^-1; S22)
-  static constexpr int DVN = LIN + PIV * PLD;           // 16             1 / d of the block being factored
-  static constexpr int RSC = DVN + PIV;                 // 4 x 16         scratch of the right-hand-side wave
-  static constexpr int DGB = RSC + 4 * PIV;             // 3 x 32         pivot diagonals (ring by pair % 3)
-  static constexpr int UF = DGB + 3 * 2 * PIV;          // FR             accumulated right-hand-side updates by slot
-  static constexpr int XS = UF + CF::FR;                // FR             solution by slot (backward sweep)
-  static constexpr int RED = XS + CF::FR;               // 2 x 16 x 16 partial sums of the sweep + 64 dummy slots
-  static constexpr int PSB = RED + 2 * 16 * PIV + 64;   // 3 x 32 ints    pivot slots (ring)
-  static constexpr int PM = PSB + 3 * 2 * PIV / 2;      // 3 x 8 words    pivot-slot bit masks (ring)
-  static constexpr int JM = PM + 3 * 8 / 2;             // FR ushorts     slot -> column offset of its pivot in the pair's two panels
-  static constexpr int PAN = (JM + CF::FR / 4 + 1) & ~1;  // 4 panels of PR x PLD: pair q in panels 2 (q & 1), 2 (q & 1) + 1
-  static constexpr int VAR = (PAN + 4 * CF::PSZ + 1) & ~1;   // dbuf, then (ints) sbuf, then the cells A
+  static constexpr Kkt5Lds at() { return Kkt5Lds::of(F); }
 };
-__host__ __device__ inline size_t kkt5_dbuf_doubles(int max_drec) { return (((size_t)max_drec * 8 + 1023) & ~(size_t)1023) / 8; }
-__host__ __device__ inline size_t kkt5_sbuf_ints(int max_srec) { return (((size_t)max_srec * 4 + 1023) & ~(size_t)1023) / 4; }
-inline size_t kkt5_fixed_doubles(int F) {
-  const int FR = (F + 63) & ~63;
-  size_t o = 2 * PIV * PLD + PIV * PLD + PIV * PLD + PIV + 4 * PIV + 3 * 2 * PIV + 2 * (size_t)FR + 2 * 16 * PIV + 64 + 3 * 2 * PIV / 2 + 3 * 8 / 2;
-  o = (o + FR / 4 + 1) & ~(size_t)1;
-  return o;
-}
-// what the backward sweep keeps in LDS in front of the helper waves' tables
-inline size_t kkt5_sweep_base_bytes(int F, int NS) { return kkt5_fixed_doubles(F) * sizeof(double) + (size_t)NS * 12 * sizeof(int); }
-inline size_t kkt5_lds_bytes(int F, int NS, int max_srec, int max_drec, int n_cells) {
-  const size_t PSZ = (size_t)(F + 2) * PLD;
-  size_t o = (kkt5_fixed_doubles(F) + 4 * PSZ + 1) & ~(size_t)1;
-  o += kkt5_dbuf_doubles(max_drec);
-  size_t oi = 2 * o + kkt5_sbuf_ints(max_srec);
-  oi += 2 * (((size_t)n_cells + 1) & ~(size_t)1);
-  return std::max(oi * sizeof(int), kkt5_sweep_base_bytes(F, NS));
-}
 
 // assembly of a pair record (Symbolic::pair_mode: 32 pivot slots / diagonals in front, target words (cell << 13) | first contribution).
 // The waves that assemble do nothing else at that time: a thread's chain of dependent LDS round trips is what a round costs, so
@@ -194,16 +162,16 @@ __global__ __launch_bounds__(KT5) void k_kkt5(DevPlan P, DevWork W, int B) {
   const int R = __builtin_amdgcn_readfirstlane((int)((CF::packed_rows() >> (4 * wv)) & 15) - 1);     // row tile of this wave or -1
   const int sidx = __builtin_amdgcn_readfirstlane((int)((CF::packed_svc() >> (4 * wv)) & 15) - 1);   // rank among the service waves or -1
   const bool is_tile = R >= 0, is_fac = wv == 0, is_svc = sidx >= 0;
-  double *MIVa = lds + LY::MIV, *MIVb = MIVa + PIV * PLD, *L21 = lds + LY::L21, *LIN = lds + LY::LIN, *DVN = lds + LY::DVN;
-  double *RSC = lds + LY::RSC, *dgb = lds + LY::DGB, *UF = lds + LY::UF, *xs = lds + LY::XS, *red = lds + LY::RED;
-  int *psb = (int *)(lds + LY::PSB);
-  unsigned *pm = (unsigned *)(lds + LY::PM);
-  unsigned short *jm = (unsigned short *)(lds + LY::JM);
-  double *PAN = lds + LY::PAN;
-  const int dstride = (int)kkt5_dbuf_doubles(P.max_drec), sstride = (int)kkt5_sbuf_ints(P.max_srec);
-  double *const dbuf = lds + LY::VAR;
-  int *const sbuf = (int *)(dbuf + dstride);
-  double *A = (double *)(sbuf + sstride);   // cells of the assembled entries
+  double *MIVa = lds + LY::at().MIV, *MIVb = MIVa + PIV * PLD, *L21 = lds + LY::at().L21, *LIN = lds + LY::at().LIN, *DVN = lds + LY::at().DVN;
+  double *RSC = lds + LY::at().RSC, *dgb = lds + LY::at().DGB, *UF = lds + LY::at().UF, *xs = lds + LY::at().XS, *red = lds + LY::at().RED;
+  int *psb = (int *)(lds + LY::at().PSB);
+  unsigned *pm = (unsigned *)(lds + LY::at().PM);
+  unsigned short *jm = (unsigned short *)(lds + LY::at().JM);
+  double *PAN = lds + LY::at().PAN;
+  const Kkt5Lds::Buffers buf = LY::at().buffers(lds + LY::at().VAR, P.max_srec, P.max_drec);
+  double *const dbuf = buf.dbuf;
+  int *const sbuf = buf.sbuf;
+  double *A = buf.cells;   // cells of the assembled entries
   const double *stream = W.stream + (size_t)b * P.stream_len;
   double *panel = W.panel + (size_t)b * P.panel_stride;
   double *minv_g = W.minv + (size_t)b * NS * (PIV * PIV);
@@ -213,7 +181,7 @@ __global__ __launch_bounds__(KT5) void k_kkt5(DevPlan P, DevWork W, int B) {
 
   for (int i = tid; i < P.n_cells; i += KT5) A[i] = 0.0;
   for (int i = tid; i < 4 * PSZ; i += KT5) PAN[i] = 0.0;
-  for (int i = tid; i < LY::PAN; i += KT5) lds[i] = 0.0;   // (everything in front of the panels)
+  for (int i = tid; i < LY::at().PAN; i += KT5) lds[i] = 0.0;   // (everything in front of the panels)
   for (int v = tid; v < n; v += KT5) dx[v] = 0.0;
   __syncthreads();
 
@@ -655,13 +623,14 @@ __global__ __launch_bounds__(KT5) void k_kkt5(DevPlan P, DevWork W, int B) {
   // ---- backward substitution (sweep_backward: one barrier per stage, one-stage look-ahead) ---------------------------
   __syncthreads();   // drains the factor-panel stores: they are read back below
   {
-    int *nxp = (int *)PAN;   // (the panels are dead)
+    static_assert(LY::at().sweep_tables() == LY::at().PAN, "the sweep tables go where the panels were");
+    int *nxp = (int *)PAN;   // (the panels are dead; written lds + sweep_tables() the compiler orders two scalar shifts of the sweep differently)
     for (int i = tid; i < NS * 4; i += KT5) nxp[i] = P.nxt_pack[i];
     for (int i = tid; i < NS * 8; i += KT5) nxp[NS * 4 + i] = (int)P.amask2[i];
     for (int i = tid; i < FR; i += KT5) xs[i] = 0.0;
     __syncthreads();
     const SweepDs sd = {W.stream + (size_t)b * P.stream_len, W.ds + (size_t)b * P.n_cons, W.g + (size_t)b * P.n_cons, W.s + (size_t)b * P.n_cons, nullptr};
-    sweep_backward<F, KT5, 9>(P, panel, dx, W.sol + (size_t)b * P.n_stages * PIV, xs, red, nxp, wv, lane, lds + ((LY::PAN + NS * 6 + 1) & ~1), sd);
+    sweep_backward<F, KT5, 9>(P, panel, dx, W.sol + (size_t)b * P.n_stages * PIV, xs, red, nxp, wv, lane, lds + LY::at().sweep_xp(NS), sd);
   }
   K5S(7);
 #undef K5S

@@ -260,7 +260,7 @@ static int configure_kernels(QtosPlanner *p) {
   if (D.sw_on) {
     // the helper waves' tables of the backward sweep (solution by position, rounds) behind the sweep's own: within the LDS
     // the forward pass needs anyway, or the kernel's allocation grows up to the limit; beyond that k_step forms ds itself
-    const size_t need = (p->kkt == Kkt::kkt5 ? kkt5_sweep_base_bytes(F, S.n_stages) : kkt2_sweep_base_bytes(F, S.n_stages)) + sweep_ds_lds_bytes(S.n_stages, D.sw_steps);
+    const size_t need = (p->kkt == Kkt::kkt5 ? Kkt5Lds::of(F).sweep_base_bytes(S.n_stages) : Kkt2Lds::of(F).sweep_base_bytes(S.n_stages)) + sweep_ds_lds_bytes(S.n_stages, D.sw_steps);
     if (need > LDS_LIMIT || chord_lds_bytes(S.n_stages, D.sw_steps) > 96 * 1024) D.sw_on = 0;
     else p->kkt_lds = std::max(p->kkt_lds, need);
   }

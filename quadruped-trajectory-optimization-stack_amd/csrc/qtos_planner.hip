@@ -35,7 +35,6 @@ using namespace qtos;
     }                                                                                         \
   } while (0)
 
-static constexpr size_t LDS_LIMIT = 160 * 1024 - 256;   // LDS one workgroup of the factor + solve kernels may claim
 enum class Kkt { kkt2, kkt3, kkt5 };                      // the factor + solve kernel (choose_kernel)
 // One host analysis.  Symbolic::build writes into its model (goff, g_doubles, dyn_chunk): a model per variant; moving is safe.
 struct Analysis { HostModel M; Symbolic S; };
@@ -320,8 +319,8 @@ static int analyze_host(const QtosParams &params, const QtosEnv &env, Analysis &
 }
 static size_t kkt_lds_bytes(Kkt k, const Symbolic &S) {
   switch (k) {
-    case Kkt::kkt5: return kkt5_lds_bytes(S.front, S.n_stages, S.max_srec, S.max_drec, S.n_cells);
-    default: return kkt2_lds_bytes(S.front, S.n_stages, S.max_srec, S.max_drec, S.n_cells);   // (k_kkt2 and k_kkt3: one layout)
+    case Kkt::kkt5: return Kkt5Lds::of(S.front).bytes(S.n_stages, S.max_srec, S.max_drec, S.n_cells);
+    default: return Kkt2Lds::of(S.front).bytes(S.n_stages, S.max_srec, S.max_drec, S.n_cells);   // (k_kkt2 and k_kkt3: one layout)
   }
 }
 // the kernel's name as rocprofv3 lists it (qtos_kkt_kernel, qtos_analyze_kernel)
@@ -460,17 +459,15 @@ int qtos_analyze_two_ended(const QtosParams *params, int *out, int n_out) {
   const auto &[M, S] = A;
   const Symbolic::TwoEnded t = S.analyze_two_ended(M);
   const int F = S.front, Fc = std::max(t.front_left, t.front_right);
-  auto panel_b = [](int f, int n_pan) { return (size_t)((f + 1) * PLD * n_pan + f * PLD) * sizeof(double); };
-  const size_t rec_b = 2 * (kkt2_dbuf_doubles(F, S.max_drec) * sizeof(double) + kkt2_sbuf_ints(F, S.max_srec) * sizeof(int));
-  const size_t cells_b = (((size_t)S.n_cells + 1) & ~(size_t)1) * sizeof(double);
-  const size_t total = kkt2_lds_bytes(F, S.n_stages, S.max_srec, S.max_drec, S.n_cells);
-  const size_t fixed_b = total > panel_b(F, 3) + rec_b + cells_b ? total - panel_b(F, 3) - rec_b - cells_b : 0;
+  const Kkt2Lds L = Kkt2Lds::of(F), Lc = Kkt2Lds::of(Fc);
+  const size_t rec_b = L.records_bytes(S.max_srec, S.max_drec), cells_b = L.cells_bytes(S.n_cells);
+  const size_t total = L.bytes(S.n_stages, S.max_srec, S.max_drec, S.n_cells), fixed_b = L.fixed_bytes(S.n_stages, S.max_srec, S.max_drec, S.n_cells);
   out[0] = S.n_stages; out[1] = F; out[2] = t.split_stage; out[3] = t.stages_left; out[4] = t.stages_right; out[5] = t.sep_unknowns;
   out[6] = t.stages_sep; out[7] = t.front_left; out[8] = t.front_right; out[9] = t.front_sep; out[10] = t.serial_steps;
   out[11] = t.peak_left; out[12] = t.peak_right;
-  out[13] = (int)total; out[14] = (int)panel_b(F, 3); out[15] = (int)rec_b; out[16] = (int)cells_b;
-  out[17] = (int)(2 * (panel_b(Fc, 3) + rec_b + cells_b + fixed_b));
-  out[18] = (int)(2 * (panel_b(Fc, 2) + kkt2_dbuf_doubles(F, S.max_drec) * sizeof(double) + cells_b + fixed_b));
+  out[13] = (int)total; out[14] = (int)L.panels_bytes(); out[15] = (int)rec_b; out[16] = (int)cells_b;
+  out[17] = (int)(2 * (Lc.panels_bytes(3) + rec_b + cells_b + fixed_b));
+  out[18] = (int)(2 * (Lc.panels_bytes(2) + L.dbuf_doubles(S.max_drec) * sizeof(double) + cells_b + fixed_b));
   out[19] = (int)LDS_LIMIT;
   return 0;
 }
