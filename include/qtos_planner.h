@@ -651,6 +651,78 @@ int qtos_rollout(QtosPlanner *p, int B, const QtosRollout *s, const double *node
                  const int *n_rows, const long long *cursor, const double *joint, const double *mass_scale, const double *push,
                  double *state, long long *count, int *word, double *meas, double *rows, int *status);
 
+/* Force fit: the contact forces of every row made to supply the wrench the planned MOTION needs ("force distribution").  Between
+ * its knots a plan's rows do not obey Newton's law (qtos_plan_check measures by how much); the motion is what the robot tracks, so
+ * the forces give.  For B windows at once (k_force_fit, one workgroup per window; the rule, with the order of every operation of
+ * the solve: force_fit.py), per row k at the plan time min(k / hz, T), with r, p_e, f_e and stance as the check row has them:
+ *   rho_ang, rho_lin  the check row's columns 1 .. 3 and 4 .. 6 of the plan's own forces, formed with m_s = mass mass_scale[b] and
+ *                     the inertia mass_scale[b] inertia_b, as qtos_rollout scales them
+ *   S, n              the feet whose motion polynomial is a stance, and their number
+ *   d_e = (p_e - r) / arm;  rho~ = (rho_ang / arm, rho_lin);  A~_e = [skew(d_e); I3]
+ *   w_e = max(n max(g_e, 0) / sum_S max(g, 0), w_min), g_e = normal . f_e with the terrain basis at the foot (the first of the
+ *         NLP's five force rows); all 1 where the sum is not > 0
+ *   M = sum_S w_e A~_e A~_e^T + damping n I6;  y = M^-1 rho~ by an unpivoted Cholesky;  df_e = w_e A~_e^T y, e in S
+ *   f_fit_e = f_e + df_e for e in S; a swing foot keeps the plan's force; n = 0: nothing is fitted
+ * A fit row has 32 columns:
+ *   0          the time stamp of CSV row k (t0 + k / hz, qtos_sample_csv's to the bit)
+ *   1 .. 12    f_fit, feet FL FR HL HR x xyz, world frame                                                  [N]
+ *  13 .. 15    the angular dynamics rows with f_fit in place of f, signed as check columns 1 .. 3 (rho - A df)  [N m]
+ *  16 .. 18    the linear ones, as check columns 4 .. 6                                                    [N]
+ *  19          sqrt(sum_S |df_e|^2)                                                                        [N]
+ *  20 .. 31    tau_ff = -J^T R^T f_fit per leg, J the leg Jacobian of qtos_joint_rows at the joint angles in columns 1 .. 12 of the
+ *              same row of d_joint (qtos_joint_rows' rows, same addressing); with d_joint NULL these columns are not touched  [N m]
+ * and a status word: bit 0 no stance foot; bit 1 exactly two stance feet (two point feet cannot carry every moment: what remains
+ * is the damped least-squares compromise); bit 2 a non-finite input or result -- then f_fit is the plan's force and columns
+ * 13 .. 19 are NaN; bit 3 + e the fitted force of stance foot e exceeds the NLP's five force rows by more than excess_tol (the
+ * check row's formula of column 23 + e on f_fit).  There are no inequality constraints inside the fit: the excess is measured.
+ * The summary has four QtosCheckRecords per window, the families res_ang (max |13 .. 15|), res_lin (max |16 .. 18|), change
+ * (column 19) and excess (the largest positive excess over the stance feet), with qtos_plan_check's semantics: the largest
+ * violation, the lowest row that attains it, the rows over tol[family]; non-finite counts as +inf; a window without rows has
+ * -inf, -1, 0; no atomics.  Rows count from first (table) or from cursor[b], the window's clock (ring).
+ * Addressing is qtos_joint_rows': capacity 0 a B x n_rows table, capacity > 0 a B x capacity ring at (cursor[b] + j) mod
+ * capacity, cursor and t0 only read -- queued behind qtos_joint_rows_device and in front of qtos_stitch_device with the same
+ * nodes, n_rows, t0 and cursor it fills a fit ring row for row with the CSV and joint rings. */
+#define QTOS_FIT_ACCUMULATE 1        /* flags: merge with the records in d_summary, as QTOS_CHECK_ACCUMULATE */
+#define QTOS_FIT_COLS 32
+#define QTOS_FIT_FAMILIES 4
+typedef struct QtosForceFit {
+  double hz;                    /* rows per second (<= 0: 1000) */
+  int first_row;                /* first row where d_first_row is NULL; 0 .. 1000000 */
+  int n_rows;                   /* table mode: rows per window; both modes: the count where d_n_rows is NULL (>= 0) */
+  long long capacity;           /* 0: table mode; > 0: rows per window in the rings */
+  int flags;                    /* QTOS_FIT_* */
+  double arm;                   /* length the moment rows are divided by (> 0) [m] */
+  double damping;               /* > 0 */
+  double w_min;                 /* floor of the load weights, 0 < w_min <= 1 */
+  double excess_tol;            /* status bit 3 + e: excess > excess_tol [N] */
+  double tol[4];                /* per family: a row counts where its violation is > tol */
+  double hip[4][3];             /* the leg data as QtosJointRows has it; columns 20 .. 31 read lateral, l_upper and l_lower */
+  double lateral[4];
+  double l_upper, l_lower;      /* link lengths (> 0) */
+  double knee_sign[4];
+  double ee_shift;
+} QtosForceFit;
+/* nodes B x n_vars, t0 B; map_id B (NULL: map 0, or flat ground where the handle has no maps), first_row B, n_rows B, joint B x rows
+ * x 37 and mass_scale B (NULL: 1) may be NULL; cursor B, NULL in table mode; rows B x rows x 32 with status B x rows, or summary
+ * B x 4 records, may be NULL, not both (rows and status go together); rows = n_rows or capacity; rows behind a window's count are
+ * not touched.
+ * Device form: all pointers but `s` in device memory, one kernel queued on `stream`; no handle state is read or written but the
+ * sampling tables, the model's constants and the terrain -- it may be queued while a call is open.  Host form: host pointers,
+ * synchronous, through device buffers of its own (no -5); rows, status and summary are copied in and out whole.
+ * Both: -1 on a null planner, and with the reason in qtos_last_error on a null required pointer, B < 1, rows without status or the
+ * reverse, rows and summary both NULL, capacity < 0, a ring without cursor, a table with n_rows < 1, n_rows < 0, first_row outside
+ * 0 .. 1000000, arm or damping not > 0, w_min outside (0, 1], excess_tol not a number, a link length <= 0; -2 on a HIP error; -3
+ * out of memory. */
+int qtos_force_fit_device(QtosPlanner *p, int B, const QtosForceFit *s, const double *d_nodes, const double *d_t0,
+                          const int *d_map_id /* may be NULL */, const int *d_first_row /* may be NULL */,
+                          const int *d_n_rows /* may be NULL */, const long long *d_cursor /* NULL in table mode */,
+                          const double *d_joint /* may be NULL */, const double *d_mass_scale /* may be NULL = 1 */,
+                          double *d_rows /* may be NULL */, int *d_status /* NULL iff d_rows is NULL */,
+                          QtosCheckRecord *d_summary /* may be NULL */, void *stream);
+int qtos_force_fit(QtosPlanner *p, int B, const QtosForceFit *s, const double *nodes, const double *t0, const int *map_id,
+                   const int *first_row, const int *n_rows, const long long *cursor, const double *joint, const double *mass_scale,
+                   double *rows, int *status, QtosCheckRecord *summary);
+
 /* Goals of receding windows from their global paths: where the next plan goes.  Replaces Global_Planner.update / spine_step
  * (QTOS/planner.py:139-161, 195-230) and Combiner.plan_init / spine_step (QTOS/combiner.py:137-212, 223-225) for B windows at
  * once: a window's A* "spine" -- two cubic splines X_p, Y_p over one set of knots -- is read one horizon ahead of the new plan's

@@ -409,6 +409,45 @@ def check_params(hz=1000.0, first_row=0, n_rows=0, tol=CHECK_TOL, accumulate=Fal
     return g
 
 
+class QtosForceFit(C.Structure):
+    """Parameters of a force fit (qtos_force_fit*, include/qtos_planner.h); force_fit.fit_rows reads the same fields."""
+    _fields_ = [
+        ("hz", C.c_double), ("first_row", C.c_int), ("n_rows", C.c_int), ("capacity", C.c_longlong), ("flags", C.c_int),
+        ("arm", C.c_double), ("damping", C.c_double), ("w_min", C.c_double), ("excess_tol", C.c_double), ("tol", C.c_double * 4),
+        ("hip", (C.c_double * 3) * 4), ("lateral", C.c_double * 4), ("l_upper", C.c_double), ("l_lower", C.c_double),
+        ("knee_sign", C.c_double * 4), ("ee_shift", C.c_double),
+    ]
+
+    def copy(self):
+        return QtosForceFit.from_buffer_copy(self)
+
+
+FIT_ACCUMULATE = 1       # QTOS_FIT_ACCUMULATE of include/qtos_planner.h
+FIT_COLS = 32            # QTOS_FIT_COLS
+FIT_FAMILIES = 4         # QTOS_FIT_FAMILIES
+FIT_TOL = (1e-3, 1e-2, 5.0, 1e-2)   # fit_params' default per family (force_fit.FIT_TOL): N m, N, N, N
+
+
+def fit_params(cfg=None, hz=1000.0, first_row=0, n_rows=0, capacity=0, tol=FIT_TOL, accumulate=False, **kw):
+    """A QtosForceFit from force_fit.fit_params(cfg, **kw) -- arm, damping, w_min, excess_tol, robot, ee_shift with its defaults and
+    its checks (ValueError).  tol: one number for the four families (res_ang N m, res_lin N, change N, excess N) or four.
+    capacity 0: table mode."""
+    from . import force_fit
+    r = force_fit.fit_params(cfg, **kw)
+    g = QtosForceFit()
+    g.hz, g.first_row, g.n_rows, g.capacity = float(hz), int(first_row), int(n_rows), int(capacity)
+    g.flags = FIT_ACCUMULATE if accumulate else 0
+    g.arm, g.damping, g.w_min, g.excess_tol = r.arm, r.damping, r.w_min, r.excess_tol
+    for f, v in enumerate(np.broadcast_to(np.asarray(tol, np.float64), (4,))):
+        g.tol[f] = float(v)
+    for e in range(4):
+        for d in range(3):
+            g.hip[e][d] = float(r.hip[e][d])
+        g.lateral[e], g.knee_sign[e] = float(r.lateral[e]), float(r.knee_sign[e])
+    g.l_upper, g.l_lower, g.ee_shift = r.l_upper, r.l_lower, r.ee_shift
+    return g
+
+
 class QtosRollout(C.Structure):
     """Parameters of a rollout (qtos_rollout*, include/qtos_planner.h); rollout.rollout_rows reads the same fields."""
     _fields_ = [
@@ -479,7 +518,7 @@ EXPORTS = [
     "qtos_terrain_env", "qtos_terrain_env_device", "qtos_set_heightfields_device",
     "qtos_joint_rows", "qtos_joint_rows_device", "qtos_track", "qtos_track_device",
     "qtos_start_feedback", "qtos_start_feedback_device", "qtos_plan_check", "qtos_plan_check_device",
-    "qtos_rollout", "qtos_rollout_device",
+    "qtos_rollout", "qtos_rollout_device", "qtos_force_fit", "qtos_force_fit_device",
 ]
 
 _lib = None
@@ -619,6 +658,10 @@ def load():
         llp = C.POINTER(C.c_longlong)
         lib.qtos_rollout.argtypes = [vp, C.c_int, C.POINTER(QtosRollout), dp, dp, ip, ip, llp, dp, dp, dp, dp, llp, ip, dp, dp, ip]
         lib.qtos_rollout_device.argtypes = [vp, C.c_int, C.POINTER(QtosRollout)] + [vp] * 15
+    if hasattr(lib, "qtos_force_fit"):               # (the force fit; older builds loaded through QTOS_LIB lack it)
+        llp = C.POINTER(C.c_longlong)
+        lib.qtos_force_fit.argtypes = [vp, C.c_int, C.POINTER(QtosForceFit), dp, dp, ip, ip, ip, llp, dp, dp, dp, ip, vp]
+        lib.qtos_force_fit_device.argtypes = [vp, C.c_int, C.POINTER(QtosForceFit)] + [vp] * 12
     if hasattr(lib, "qtos_set_heightfields_device"):
         lib.qtos_set_heightfields_device.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, vp]
     _lib = lib
@@ -1250,6 +1293,64 @@ class Planner:
         self._chk(self.lib.qtos_plan_check(self.h, B, C.byref(params), _dp(nodes), _dp(t0), _ip(mid), _ip(first), _ip(per), _llp(cur),
                                            _dp(rows), None if summary is None else summary.ctypes.data_as(C.c_void_p)), "plan_check")
         return rows, summary
+
+    def has_force_fit(self):
+        return hasattr(self.lib, "qtos_force_fit")
+
+    def force_fit(self, nodes, t0, params, map_id=None, first_row=None, n_rows=None, cursor=None, joint=None, mass_scale=None,
+                  rows=True, status=None, summary=None, stream=None):
+        """The contact forces of every row of the plans in `nodes` fitted to the planned motion (qtos_force_fit; the rule:
+        force_fit.py).  params: a QtosForceFit (fit_params()).  Returns (rows, status, summary): rows [B, R, 32] and status [B, R]
+        int32, R = params.n_rows (table mode) or params.capacity (ring mode: `rows`, `status` and `cursor` are the rings as they
+        stand) -- rows=True: new arrays; an array: written into a copy of it, rows behind a window's count stay; False / None: no
+        table -- and summary [B, 4] records of force_fit.SUMMARY (summary=None with a table: computed as well; an array: with
+        params' accumulate flag merged with it; False: none).  joint: [B, R, 37] joint rows in the same addressing (None: columns
+        20 .. 31 are not touched); mass_scale: a number or B; first_row, n_rows: an int or B ints.  numpy arrays go through the host
+        form.  torch tensors on the device (nodes, t0 and whichever of the others are given; rows, status, summary: tensors to
+        write into, summary as B x 4 x 3 float64 words, or None) go through the device form on `stream` (a torch stream; None: the
+        current one) and come back as they are, without a synchronisation."""
+        if not self.has_force_fit():
+            raise RuntimeError("this build of the planner library has no force-fit kernel (qtos_force_fit)")
+        from . import force_fit as ff
+        if hasattr(nodes, "data_ptr"):
+            import torch
+            st = torch.cuda.current_stream(nodes.device) if stream is None else stream
+            B = nodes.reshape(-1, self.n).shape[0]
+            ptr = lambda a: None if a is None or a is False or a is True else C.c_void_p(a.data_ptr())
+            self._chk(self.lib.qtos_force_fit_device(self.h, B, C.byref(params), ptr(nodes), ptr(t0), ptr(map_id), ptr(first_row),
+                                                     ptr(n_rows), ptr(cursor), ptr(joint), ptr(mass_scale), ptr(rows), ptr(status),
+                                                     ptr(summary), C.c_void_p(st.cuda_stream)), "force_fit_device")
+            return (rows if ptr(rows) else None), (status if ptr(status) else None), (summary if ptr(summary) else None)
+        nodes = np.ascontiguousarray(nodes, np.float64).reshape(-1, self.n)
+        B = nodes.shape[0]
+        t0 = np.ascontiguousarray(np.broadcast_to(np.asarray(t0, np.float64), (B,)))
+        mid, first, per = _i32(map_id, B), _i32(first_row, B), _i32(n_rows, B)
+        keep = not (rows is False or rows is None)
+        nr, cur = _segment(params, B, cursor, *((rows, status) if keep and params.capacity > 0 else ()))
+        nr = max(nr, 0)
+        joint = None if joint is None else np.ascontiguousarray(joint, np.float64)
+        if joint is not None and joint.shape != (B, nr, CSV_COLS):
+            raise ValueError("joint is (B, %d, %d)" % (nr, CSV_COLS))
+        ms = None if mass_scale is None else np.ascontiguousarray(np.broadcast_to(np.asarray(mass_scale, np.float64), (B,)))
+        if not keep:
+            rows = status = None
+        else:
+            rows = np.zeros((B, nr, FIT_COLS)) if rows is True else np.array(rows, np.float64)
+            status = np.zeros((B, nr), np.int32) if status is None else np.array(status, np.int32)
+            if rows.shape != (B, nr, FIT_COLS) or status.shape != (B, nr):
+                raise ValueError("rows is (B, %d, %d) and status (B, %d)" % (nr, FIT_COLS, nr))
+        if summary is False:
+            summary = None
+            if rows is None:
+                raise ValueError("rows and summary cannot both be left out")
+        elif summary is None:
+            summary = ff.empty_summary(B)
+        else:
+            summary = np.array(summary, ff.SUMMARY).reshape(B, FIT_FAMILIES)
+        self._chk(self.lib.qtos_force_fit(self.h, B, C.byref(params), _dp(nodes), _dp(t0), _ip(mid), _ip(first), _ip(per), _llp(cur),
+                                          _dp(joint), _dp(ms), _dp(rows), _ip(status),
+                                          None if summary is None else summary.ctypes.data_as(C.c_void_p)), "force_fit")
+        return rows, status, summary
 
     def has_path_goal(self):
         return hasattr(self.lib, "qtos_path_goal")

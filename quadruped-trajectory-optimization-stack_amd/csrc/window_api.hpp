@@ -530,6 +530,78 @@ int qtos_rollout(QtosPlanner *p, int B, const QtosRollout *s, const double *node
   return rc ? rc : S.download();
 }
 
+// ---- the rows' contact forces fitted to the planned motion (k_force_fit, window_kernels.hpp) ---------------------
+// The argument checks of both forms, and QtosForceFit as k_force_fit reads it, with the model's constants and the terrain.  Every
+// -1 but the null planner's leaves its reason in the handle's err.
+static int force_fit_args(QtosPlanner *p, int B, const QtosForceFit *s, const void *nodes, const void *t0, const void *cursor,
+                          const void *rows, const void *status, const void *summary, FitArgs *A) {
+  if (!p) return -1;
+  const char *why = nullptr;
+  if (B < 1) why = "B < 1";
+  else if (!s || !nodes || !t0) why = "a required pointer is null";
+  else if ((rows == nullptr) != (status == nullptr)) why = "rows and status go together";
+  else if (!rows && !summary) why = "rows and summary are both null";
+  else if (const char *seg = segment_check(s->capacity, s->n_rows, s->first_row, cursor != nullptr)) why = seg;
+  else if (!(s->arm > 0) || !(s->arm <= 1.7976931348623157e308)) why = "arm is > 0";
+  else if (!(s->damping > 0) || !(s->damping <= 1.7976931348623157e308)) why = "damping is > 0";
+  else if (!(s->w_min > 0) || !(s->w_min <= 1)) why = "w_min is in (0, 1]";
+  else if (s->excess_tol != s->excess_tol) why = "excess_tol is not a number";
+  else if (!(s->l_upper > 0) || !(s->l_lower > 0)) why = "a link length is <= 0";
+  if (why) {
+    p->err = std::string("qtos_force_fit: ") + why;
+    return -1;
+  }
+  const QtosParams &P = p->M.P;
+  A->hz = s->hz > 0 ? s->hz : 1000.0;
+  A->mass = P.mass; A->gravity = P.gravity; A->mu = P.mu; A->f_max = P.f_max;
+  for (int i = 0; i < 9; ++i) A->Ib[i] = P.inertia_b[i];
+  A->arm = s->arm; A->damping = s->damping; A->w_min = s->w_min; A->excess_tol = s->excess_tol;
+  for (int f = 0; f < FIT_FAMILIES; ++f) A->tol[f] = s->tol[f];
+  for (int e = 0; e < NEE; ++e) {
+    A->lateral[e] = s->lateral[e];
+    A->stance[e] = p->d_stance[e];
+  }
+  A->l_upper = s->l_upper; A->l_lower = s->l_lower;
+  const DevPlan &D = p->dp;
+  A->T.height = D.height; A->T.hcell = D.hcell; A->T.hx0 = D.hx0; A->T.hy0 = D.hy0;
+  A->T.n_maps = D.n_maps; A->T.hnx = D.hnx; A->T.hny = D.hny; A->T.terrain_mode = D.terrain_mode;
+  A->capacity = s->capacity; A->first_row = s->first_row; A->n_rows = s->n_rows;
+  A->accumulate = (s->flags & QTOS_FIT_ACCUMULATE) != 0;
+  return 0;
+}
+
+int qtos_force_fit_device(QtosPlanner *p, int B, const QtosForceFit *s, const double *d_nodes, const double *d_t0, const int *d_map_id,
+                          const int *d_first_row, const int *d_n_rows, const long long *d_cursor, const double *d_joint,
+                          const double *d_mass_scale, double *d_rows, int *d_status, QtosCheckRecord *d_summary, void *stream_) {
+  FitArgs A;
+  if (force_fit_args(p, B, s, d_nodes, d_t0, d_cursor, d_rows, d_status, d_summary, &A)) return -1;
+  HIPCHK(p, hipSetDevice(p->device));
+  hipLaunchKernelGGL(k_force_fit, dim3(B), dim3(FIT_TILE), 0, (hipStream_t)stream_, p->d_sp, A, d_nodes, d_t0, d_map_id, d_first_row,
+                     d_n_rows, d_cursor, d_joint, d_mass_scale, d_rows, d_status, (CheckRecord *)d_summary, B);
+  HIPCHK(p, hipGetLastError());
+  return 0;
+}
+
+int qtos_force_fit(QtosPlanner *p, int B, const QtosForceFit *s, const double *nodes, const double *t0, const int *map_id,
+                   const int *first_row, const int *n_rows, const long long *cursor, const double *joint, const double *mass_scale,
+                   double *rows, int *status, QtosCheckRecord *summary) {
+  FitArgs A;
+  if (force_fit_args(p, B, s, nodes, t0, cursor, rows, status, summary, &A)) return -1;
+  HIPCHK(p, hipSetDevice(p->device));
+  const size_t nr = segment_elems(B, A.capacity, A.n_rows);
+  Staging S(p);
+  const double *d_nodes = S.in(nodes, (size_t)B * p->M.n_vars), *d_t0 = S.in(t0, B);
+  const int *d_map = S.in(map_id, B), *d_first = S.in(first_row, B), *d_n = S.in(n_rows, B);
+  const long long *d_cur = S.in(cursor, B);
+  const double *d_joint = S.in(joint, nr * QTOS_CSV_COLS), *d_ms = S.in(mass_scale, B);
+  double *d_rows = S.inout(rows, nr * FIT_COLS);                                   // (rows behind a window's count come back as they were)
+  int *d_st = S.inout(status, nr);
+  QtosCheckRecord *d_sum = S.inout(summary, (size_t)B * FIT_FAMILIES);             // (the accumulate flag merges with what is there)
+  if (S.rc) return S.rc;
+  const int rc = qtos_force_fit_device(p, B, s, d_nodes, d_t0, d_map, d_first, d_n, d_cur, d_joint, d_ms, d_rows, d_st, d_sum, nullptr);
+  return rc ? rc : S.download();
+}
+
 // ---- goals of receding windows from their global paths (k_path_goal, window_kernels.hpp) ------------------------
 // The argument checks of both forms, and QtosPathGoal as k_path_goal reads it.
 static int path_goal_args(const QtosPlanner *p, int B, const QtosPathGoal *g, const void *knots, const void *coef, const void *n_pieces,

@@ -10,6 +10,7 @@
 //   k_start_feedback: the next plan's start from the measured state
 //   k_plan_check    : what the windows' plans violate between their knots
 //   k_rollout       : the windows' robots as simulated rigid bodies (the measured states k_track reads)
+//   k_force_fit     : the rows' contact forces fitted to the planned motion (k_plan_check's pieces and a 6 x 6 solve per row)
 //   k_path_goal     : goals of the windows from their global paths
 //   k_path_plan     : the global paths (A* and spines)
 //   k_probe*        : the probe and the stamp of the windows' heightfields
@@ -1167,6 +1168,305 @@ __global__ __launch_bounds__(TILE) void k_rollout(const SamplePlan *Sd, RolloutA
     sb[6] = s.qx; sb[7] = s.qy; sb[8] = s.qz; sb[9] = s.qw; sb[10] = s.w0; sb[11] = s.w1; sb[12] = s.w2;
     count[b] = calls + n;
     word_io[b] = word;
+  }
+}
+
+// Force fit (qtos_force_fit*): the contact forces of every row made to supply the wrench the planned motion needs -- what
+// k_plan_check measures as columns 1 .. 6, taken off the stance feet by one damped weighted least-squares solve per row ("force
+// distribution").  The statement of the rule is force_fit.py, with the order of every operation of the solve.  One workgroup per
+// window walks its rows tile by tile, as k_plan_check does: (A) a lane takes a row -- the plan's own dynamics rows with
+// k_plan_check's pieces (sample_spline, sample_spline_acc, dyn_angular, rotation, terrain_at and the stance flag table), the ten
+// sums of the 6 x 6 system over the stance feet, its unpivoted Cholesky in registers (21 entries, constant indices: the loops
+// are unrolled, the feet come through a template as check_foot<E>), the corrections, the residual rows as rho - A df, the excess
+// of the fitted forces and the feed-forward torques at the joint angles of the joint table's row -- and puts its 32 values into
+// the row's place of an LDS tile (pitch 33 doubles: at 32 every lane of a wave would write the same bank); (B) twelve workgroup
+// reductions (wg_reduce) into the four running records, uniform scalars; (C) the tile goes out flat, consecutive lanes on
+// consecutive doubles, RowSegment's addressing: table or ring, cursor and t0 only read.  Without a joint table columns 20 .. 31
+// are not written.  The status is one int per lane.  No atomics: the summary is a function of the rows (force_fit.summarise).
+// fit_excess switches contraction off: it is the one piece numpy forms again from the table's columns, to the bit.
+constexpr int FIT_COLS = 32, FIT_PITCH = 33, FIT_TILE = 256, FIT_FAMILIES = 4;
+struct FitArgs {       // QtosForceFit as the kernel reads it, with the model's constants (window_api.hpp force_fit_args)
+  double hz, mass, gravity, Ib[9], mu, f_max;
+  double arm, damping, w_min, excess_tol, tol[FIT_FAMILIES];
+  double lateral[NEE], l_upper, l_lower;
+  FeedbackTerrain T;
+  const int *stance[NEE];                  // per foot and polynomial of its motion spline: 1 stance, 0 swing
+  long long capacity;
+  int first_row, n_rows, accumulate;
+};
+struct FitFoot {       // one foot of a row, in registers: p = p_e - r, f the plan's force, df the correction
+  double p[3], f[3], df[3], w, hx, hy;
+  bool stance;
+};
+struct FitSums { double W, s0, s1, s2, q00, q01, q02, q11, q12, q22; };
+
+// Foot E of a row: position, force and stance flag as check_foot takes them, its force and lever arm off the dynamics rows ga, gl
+// (check_foot's lines), the terrain's slopes under it and max(normal . f, 0) of a stance foot (0 for a swing foot) into F.w.
+template <int E>
+__device__ inline void fit_foot_load(const SamplePlan &S, const FitArgs &A, const double *x, double t, int map, const double r[3],
+                                     double ga[3], double gl[3], FitFoot &F) {
+  double pe[3];
+  sample_spline(S.eem[E], x, t, 0, pe);
+  sample_spline(S.eef[E], x, t, 0, F.f);
+  F.stance = A.stance[E][sample_segment(S.eem[E], t)] != 0;
+  const double d[3] = {r[0] - pe[0], r[1] - pe[1], r[2] - pe[2]};
+  ga[0] -= F.f[1] * d[2] - F.f[2] * d[1];
+  ga[1] -= F.f[2] * d[0] - F.f[0] * d[2];
+  ga[2] -= F.f[0] * d[1] - F.f[1] * d[0];
+  gl[0] -= F.f[0]; gl[1] -= F.f[1]; gl[2] -= F.f[2];
+  F.p[0] = pe[0] - r[0]; F.p[1] = pe[1] - r[1]; F.p[2] = pe[2] - r[2];
+  Terr tr = terrain_at(A.T, map, pe[0], pe[1]);
+  if (!(isfinite(pe[0]) && isfinite(pe[1]))) { tr.hx = NAN; tr.hy = NAN; }
+  F.hx = tr.hx; F.hy = tr.hy;
+  double b[3], bx[3], by[3];
+  terrain_basis(tr, 0, b, bx, by);
+  const double g = F.f[0] * b[0] + F.f[1] * b[1] + F.f[2] * b[2];
+  F.w = F.stance && g > 0 ? g : 0.0;
+  F.df[0] = 0; F.df[1] = 0; F.df[2] = 0;
+}
+
+// A stance foot's share of the ten sums: d = p / arm, W += w, s_i += w d_i, q_ij += (w d_i) d_j.
+__device__ inline void fit_foot_sums(const FitFoot &F, double arm, FitSums &Q) {
+  if (!F.stance) return;
+  const double d0 = F.p[0] / arm, d1 = F.p[1] / arm, d2 = F.p[2] / arm;
+  const double w0 = F.w * d0, w1 = F.w * d1, w2 = F.w * d2;
+  Q.W += F.w; Q.s0 += w0; Q.s1 += w1; Q.s2 += w2;
+  Q.q00 += w0 * d0; Q.q01 += w0 * d1; Q.q02 += w0 * d2; Q.q11 += w1 * d1; Q.q12 += w1 * d2; Q.q22 += w2 * d2;
+}
+
+__device__ constexpr int fit_ix(int i, int j) { return i * (i + 1) / 2 + j; }   // the lower triangle, row by row
+
+// y = M^-1 rhs by the unpivoted Cholesky of force_fit.py; M: the lower triangle, overwritten with L.
+__device__ inline void fit_solve(double M[21], const double rhs[6], double y[6]) {
+#pragma unroll
+  for (int j = 0; j < 6; ++j) {
+    double acc = M[fit_ix(j, j)];
+#pragma unroll
+    for (int k = 0; k < j; ++k) acc -= M[fit_ix(j, k)] * M[fit_ix(j, k)];
+    const double ljj = sqrt(acc);
+    M[fit_ix(j, j)] = ljj;
+#pragma unroll
+    for (int i = j + 1; i < 6; ++i) {
+      double a = M[fit_ix(i, j)];
+#pragma unroll
+      for (int k = 0; k < j; ++k) a -= M[fit_ix(i, k)] * M[fit_ix(j, k)];
+      M[fit_ix(i, j)] = a / ljj;
+    }
+  }
+  double z[6];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    double acc = rhs[i];
+#pragma unroll
+    for (int k = 0; k < i; ++k) acc -= M[fit_ix(i, k)] * z[k];
+    z[i] = acc / M[fit_ix(i, i)];
+  }
+#pragma unroll
+  for (int i = 5; i >= 0; --i) {
+    double acc = z[i];
+#pragma unroll
+    for (int k = i + 1; k < 6; ++k) acc -= M[fit_ix(k, i)] * y[k];
+    y[i] = acc / M[fit_ix(i, i)];
+  }
+}
+
+// A stance foot's correction df = w (y_ang x d + y_lin), taken off the residual rows and added to the squared change.
+__device__ inline void fit_foot_correct(FitFoot &F, double arm, const double y[6], double ra[3], double rl[3], double &sq) {
+  if (!F.stance) return;
+  const double d0 = F.p[0] / arm, d1 = F.p[1] / arm, d2 = F.p[2] / arm;
+  F.df[0] = (y[1] * d2 - y[2] * d1 + y[3]) * F.w;
+  F.df[1] = (y[2] * d0 - y[0] * d2 + y[4]) * F.w;
+  F.df[2] = (y[0] * d1 - y[1] * d0 + y[5]) * F.w;
+  ra[0] -= F.p[1] * F.df[2] - F.p[2] * F.df[1];
+  ra[1] -= F.p[2] * F.df[0] - F.p[0] * F.df[2];
+  ra[2] -= F.p[0] * F.df[1] - F.p[1] * F.df[0];
+  rl[0] -= F.df[0]; rl[1] -= F.df[1]; rl[2] -= F.df[2];
+  sq += F.df[0] * F.df[0] + F.df[1] * F.df[1] + F.df[2] * F.df[2];
+}
+
+// check_foot's excess of a stance foot on the force f: the NLP's five force rows with the terrain basis of the slopes hx, hy,
+// plan_check.force_rows operation for operation (one rounded operation each); NaN where a row is not finite.
+__device__ inline double fit_excess(const double f[3], double hx, double hy, double mu, double f_max) {
+#pragma clang fp contract(off)
+  const double nn = sqrt((hx * hx + hy * hy) + 1.0), n1 = sqrt((1.0 + 0.0) + hx * hx), n2 = sqrt((0.0 + 1.0) + hy * hy);
+  const double bn[3] = {-hx / nn, -hy / nn, 1.0 / nn};
+  const double b1[3] = {1.0 / n1, 0.0 / n1, hx / n1}, b2[3] = {0.0 / n2, 1.0 / n2, hy / n2};
+  double g[5];
+  g[0] = (f[0] * bn[0] + f[1] * bn[1]) + f[2] * bn[2];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const double s = (q & 1) ? mu : -mu;
+    const double *bt = (q >> 1) ? b2 : b1;
+    g[1 + q] = (f[0] * (s * bn[0] + bt[0]) + f[1] * (s * bn[1] + bt[1])) + f[2] * (s * bn[2] + bt[2]);
+  }
+  double ex = fmax(fmax(fmax(-g[0], g[0] - f_max), fmax(g[1], -g[2])), fmax(g[3], -g[4]));
+  if (!(isfinite(g[0]) && isfinite(g[1]) && isfinite(g[2]) && isfinite(g[3]) && isfinite(g[4]))) ex = NAN;
+  return ex;
+}
+
+// Foot E's fitted force into columns 1 + 3 E .. of dst, its excess into v_ex and the status, its feed-forward torques
+// -J^T R^T f_fit at the joint angles q (joint_leg's lines; q null: the columns are left alone).
+template <int E>
+__device__ inline int fit_foot_out(const FitArgs &A, const FitFoot &F, bool bad, const double R[9], const double *q, double *dst,
+                                   double &v_ex) {
+  double f[3] = {F.f[0], F.f[1], F.f[2]};
+  if (F.stance && !bad) { f[0] = F.f[0] + F.df[0]; f[1] = F.f[1] + F.df[1]; f[2] = F.f[2] + F.df[2]; }
+  dst[1 + 3 * E] = f[0]; dst[2 + 3 * E] = f[1]; dst[3 + 3 * E] = f[2];
+  int st = 0;
+  if (F.stance) {
+    const double ex = fit_excess(f, F.hx, F.hy, A.mu, A.f_max);
+    if (ex > A.excess_tol) st = 8 << E;
+    v_ex = fmax(v_ex, isfinite(ex) ? (ex > 0 ? ex : 0.0) : INFINITY);
+  }
+  if (q) {
+    const double q1 = q[3 * E], q2 = q[3 * E + 1], q3 = q[3 * E + 2];
+    const double d = A.lateral[E], lu = A.l_upper, ll = A.l_lower;
+    const double s1 = sin(q1), c1 = cos(q1), s2 = sin(q2), c2 = cos(q2), s23 = sin(q2 + q3), c23 = cos(q2 + q3);
+    const double x = -lu * s2 - ll * s23, hh = lu * c2 + ll * c23, ls = ll * s23, lc = ll * c23;
+    const double fx = R[0] * f[0] + R[3] * f[1] + R[6] * f[2], fy = R[1] * f[0] + R[4] * f[1] + R[7] * f[2],
+                 fz = R[2] * f[0] + R[5] * f[1] + R[8] * f[2];
+    const double gy = c1 * fy + s1 * fz, gz = c1 * fz - s1 * fy;
+    dst[20 + 3 * E] = -(hh * gy + d * gz); dst[21 + 3 * E] = hh * fx + x * gz; dst[22 + 3 * E] = lc * fx - ls * gz;
+  }
+  return st;
+}
+
+__global__ __launch_bounds__(FIT_TILE) void k_force_fit(const SamplePlan *Sd, FitArgs A, const double *nodes, const double *t0,
+                                                        const int *map_id, const int *first_row, const int *n_rows,
+                                                        const long long *cursor, const double *joint, const double *mass_scale,
+                                                        double *rows_out, int *status_out, CheckRecord *summary, int B) {
+  __shared__ double fit_tile[FIT_TILE * FIT_PITCH];
+  __shared__ double fit_red[FIT_TILE];
+  const int b = blockIdx.x;
+  if (b >= B) return;
+  const SamplePlan &S = *Sd;
+  const RowSegment G = RowSegment::of(A.capacity, A.n_rows, A.first_row, n_rows, first_row, cursor, b);
+  const long long n = G.n, rows_b = G.rows_b;
+  const long long row0 = A.capacity > 0 ? cursor[b] : G.first;                       // what the summary counts its rows from
+  const int map = map_id ? map_id[b] : 0;
+  const double *x = nodes + (size_t)b * S.n_vars;
+  const double t0b = t0[b];
+  const double ms = mass_scale ? mass_scale[b] : 1.0;
+  const double m_s = A.mass * ms;
+  double *out_b = rows_out ? rows_out + (size_t)b * (size_t)rows_b * FIT_COLS : nullptr;
+  const double *joint_b = joint ? joint + (size_t)b * (size_t)rows_b * QTOS_CSV_COLS : nullptr;
+  double run_max[FIT_FAMILIES];
+  long long run_row[FIT_FAMILIES], run_cnt[FIT_FAMILIES];
+#pragma unroll
+  for (int f = 0; f < FIT_FAMILIES; ++f) { run_max[f] = -INFINITY; run_row[f] = -1; run_cnt[f] = 0; }
+  for (long long j0 = 0; j0 < n; j0 += FIT_TILE) {                                   // (n is uniform over the workgroup: so are the barriers)
+    const int m = G.tile_rows(j0, FIT_TILE);
+    const long long base = G.row(j0);
+    double v[FIT_FAMILIES];
+#pragma unroll
+    for (int f = 0; f < FIT_FAMILIES; ++f) v[f] = -INFINITY;                         // a lane without a row: below every violation
+    if ((int)threadIdx.x < m) {                                                      // (A) a lane takes a row
+      const int k = G.plan_row(j0, threadIdx.x);
+      double t = k / A.hz;
+      if (t > S.T) t = S.T;
+      double *dst = fit_tile + threadIdx.x * FIT_PITCH;
+      dst[0] = t0b + k / A.hz;                                                       // sample_row_state_at's time stamp
+      double r[3], a[3], th[3], thd[3], thdd[3], ga[3], gl[3], R[9], Ib[9];
+      sample_spline(S.lin, x, t, 0, r);
+      sample_spline_acc(S.lin, x, t, a);
+      sample_spline(S.ang, x, t, 0, th);
+      sample_spline(S.ang, x, t, 1, thd);
+      sample_spline_acc(S.ang, x, t, thdd);
+      const Trig tg = trig_of(th);
+#pragma unroll
+      for (int i = 0; i < 9; ++i) Ib[i] = ms * A.Ib[i];
+      dyn_angular<double>(Ib, th, thd, thdd, tg, ga);
+      rotation<double>(th, tg, R);
+      gl[0] = m_s * a[0]; gl[1] = m_s * a[1]; gl[2] = m_s * a[2] + m_s * A.gravity;
+      FitFoot F0, F1, F2, F3;
+      fit_foot_load<0>(S, A, x, t, map, r, ga, gl, F0);
+      fit_foot_load<1>(S, A, x, t, map, r, ga, gl, F1);
+      fit_foot_load<2>(S, A, x, t, map, r, ga, gl, F2);
+      fit_foot_load<3>(S, A, x, t, map, r, ga, gl, F3);
+      // the weights: F.w holds max(g, 0) of a stance foot
+      const int cnt = (int)F0.stance + (int)F1.stance + (int)F2.stance + (int)F3.stance;
+      const double nn = (double)cnt, gsum = ((F0.w + F1.w) + F2.w) + F3.w;
+      const bool loaded = gsum > 0;
+      F0.w = loaded ? fmax(nn * F0.w / gsum, A.w_min) : 1.0;
+      F1.w = loaded ? fmax(nn * F1.w / gsum, A.w_min) : 1.0;
+      F2.w = loaded ? fmax(nn * F2.w / gsum, A.w_min) : 1.0;
+      F3.w = loaded ? fmax(nn * F3.w / gsum, A.w_min) : 1.0;
+      double y[6] = {0, 0, 0, 0, 0, 0}, sq = 0;
+      if (cnt > 0) {
+        FitSums Q = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        fit_foot_sums(F0, A.arm, Q);
+        fit_foot_sums(F1, A.arm, Q);
+        fit_foot_sums(F2, A.arm, Q);
+        fit_foot_sums(F3, A.arm, Q);
+        const double lam = A.damping * nn, wl = Q.W + lam;
+        double M[21] = {(Q.q11 + Q.q22) + lam,
+                        -Q.q01, (Q.q00 + Q.q22) + lam,
+                        -Q.q02, -Q.q12, (Q.q00 + Q.q11) + lam,
+                        0.0, Q.s2, -Q.s1, wl,
+                        -Q.s2, 0.0, Q.s0, 0.0, wl,
+                        Q.s1, -Q.s0, 0.0, 0.0, 0.0, wl};
+        const double rhs[6] = {ga[0] / A.arm, ga[1] / A.arm, ga[2] / A.arm, gl[0], gl[1], gl[2]};
+        fit_solve(M, rhs, y);
+      }
+      fit_foot_correct(F0, A.arm, y, ga, gl, sq);
+      fit_foot_correct(F1, A.arm, y, ga, gl, sq);
+      fit_foot_correct(F2, A.arm, y, ga, gl, sq);
+      fit_foot_correct(F3, A.arm, y, ga, gl, sq);
+      const double change = sqrt(sq);
+      bool fin = isfinite(ga[0]) && isfinite(ga[1]) && isfinite(ga[2]) && isfinite(gl[0]) && isfinite(gl[1]) && isfinite(gl[2]) &&
+                 isfinite(change);
+      fin = fin && isfinite(F0.df[0]) && isfinite(F0.df[1]) && isfinite(F0.df[2]) && isfinite(F1.df[0]) && isfinite(F1.df[1]) &&
+            isfinite(F1.df[2]) && isfinite(F2.df[0]) && isfinite(F2.df[1]) && isfinite(F2.df[2]) && isfinite(F3.df[0]) &&
+            isfinite(F3.df[1]) && isfinite(F3.df[2]);
+      const bool bad = !fin;
+      dst[13] = bad ? NAN : ga[0]; dst[14] = bad ? NAN : ga[1]; dst[15] = bad ? NAN : ga[2];
+      dst[16] = bad ? NAN : gl[0]; dst[17] = bad ? NAN : gl[1]; dst[18] = bad ? NAN : gl[2];
+      dst[19] = bad ? NAN : change;
+      const double *q = joint_b ? joint_b + (size_t)G.tile_row(base, threadIdx.x) * QTOS_CSV_COLS + 1 : nullptr;
+      double v_ex = 0;
+      int st = (cnt == 0 ? 1 : 0) | (cnt == 2 ? 2 : 0) | (bad ? 4 : 0);
+      st |= fit_foot_out<0>(A, F0, bad, R, q, dst, v_ex);
+      st |= fit_foot_out<1>(A, F1, bad, R, q, dst, v_ex);
+      st |= fit_foot_out<2>(A, F2, bad, R, q, dst, v_ex);
+      st |= fit_foot_out<3>(A, F3, bad, R, q, dst, v_ex);
+      if (status_out) status_out[(size_t)b * (size_t)rows_b + G.tile_row(base, threadIdx.x)] = st;
+      v[0] = bad ? INFINITY : fmax(fmax(fabs(ga[0]), fabs(ga[1])), fabs(ga[2]));
+      v[1] = bad ? INFINITY : fmax(fmax(fabs(gl[0]), fabs(gl[1])), fabs(gl[2]));
+      v[2] = bad ? INFINITY : change;
+      v[3] = v_ex;
+    }
+    if (summary) {                                                                   // (B) the tile's families into the running records
+#pragma unroll
+      for (int f = 0; f < FIT_FAMILIES; ++f) {
+        const double mx = wg_reduce<1, FIT_TILE>(v[f], fit_red);                     // (m >= 1: a violation, >= 0, is among them)
+        const double at = wg_reduce<2, FIT_TILE>(v[f] == mx ? (double)threadIdx.x : (double)FIT_TILE, fit_red);
+        const double over = wg_reduce<0, FIT_TILE>(v[f] > A.tol[f] ? 1.0 : 0.0, fit_red);
+        if (mx > run_max[f]) { run_max[f] = mx; run_row[f] = row0 + j0 + (long long)at; }
+        run_cnt[f] += (long long)over;
+      }
+    }
+    __syncthreads();
+    if (out_b) {                                                                     // (C) the tile goes out flat
+      for (int e = threadIdx.x; e < m * FIT_COLS; e += FIT_TILE) {
+        const int i = e / FIT_COLS, c = e - i * FIT_COLS;
+        if (c < 20 || joint_b) out_b[G.flat(base, FIT_COLS, e)] = fit_tile[i * FIT_PITCH + c];
+      }
+    }
+    __syncthreads();
+  }
+  if (summary && threadIdx.x == 0) {
+    if (A.accumulate && n == 0) return;                                              // nothing to merge
+#pragma unroll
+    for (int f = 0; f < FIT_FAMILIES; ++f) {
+      CheckRecord rec = {run_max[f], run_row[f], run_cnt[f]};
+      CheckRecord *dst = summary + (size_t)b * FIT_FAMILIES + f;
+      if (A.accumulate) {
+        const CheckRecord old = *dst;
+        if (!(rec.max > old.max)) { rec.max = old.max; rec.row = old.row; }
+        rec.count += old.count;
+      }
+      *dst = rec;
+    }
   }
 }
 

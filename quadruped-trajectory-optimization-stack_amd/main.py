@@ -6,7 +6,8 @@ the per-solve report in the layout of the reference's ``logs/towr_log.out`` (rep
 through the KKT self-test (capi.Planner(checked=True)): a transcription whose elimination orders all fail it is not planned --
 the attempts are printed and the exit status is 2, the reference's "numerical failure" class.  ``--check`` prints, behind the
 solve, what the plan violates between its knots: one line per family of the plan check (plan_check.py); the exit status is
-unchanged.
+unchanged.  ``--fit`` prints, behind those, what fitting the rows' contact forces to the planned motion leaves and changes: one
+line per family of the force fit (force_fit.py); CSV and exit status are unchanged.
 """
 import sys
 
@@ -23,6 +24,9 @@ def main(argv=None):
     check = "--check" in argv
     if check:
         argv.remove("--check")
+    fit = "--fit" in argv
+    if fit:
+        argv.remove("--fit")
     for opt in ("--out", "--heightfield", "--log"):
         if opt in argv:
             i = argv.index(opt)
@@ -44,7 +48,7 @@ def main(argv=None):
         # --log PATH: the per-solve report (report.py) goes to PATH; --log -: to stdout, where it ends with the status line
         # -- the reference's logs/towr_log.out back from `python -m qtos_amd.main ... --log - > logs/towr_log.out`
         try:
-            status = lp.solve(args, out_csv=out, log=sys.stdout if log == "-" else log, check=check)
+            status = lp.solve(args, out_csv=out, log=sys.stdout if log == "-" else log, check=check, fit=fit)
         except capi.SelftestError as e:
             for t in e.attempts:
                 print("KKT self-test: " + t.describe())

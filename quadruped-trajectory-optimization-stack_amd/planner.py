@@ -119,8 +119,13 @@ class LocalPlanner:
                          r=[a.get('-r') for a in args_list])
         return statuses
 
-    def solve(self, args, out_csv=TRAJ_OUT, log=None, check=False):
+    def solve(self, args, out_csv=TRAJ_OUT, log=None, check=False, fit=False):
         """One plan; writes the CSV where the reference's ``docker cp`` would put it.
+
+        fit: True or a writable file object -- behind the solve (and the check's lines) one line per family of the force fit
+        (qtos_force_fit: what is left of the dynamics rows with the fitted forces, the largest change, the largest excess over the
+        friction pyramid, their times, the rows over capi.FIT_TOL) is written there (True: stdout) and the records are kept in
+        ``self.last["fit"]``.  The CSV and the return value are unchanged.
 
         check: True or a writable file object -- behind the solve one line per family of the plan check (qtos_plan_check: the
         largest violation of the CSV's rows, its time, the rows over capi.CHECK_TOL) is written there (True: stdout) and the
@@ -160,6 +165,17 @@ class LocalPlanner:
             self.last["check"] = summary[0]
             text = "\n".join(plan_check.report_lines(summary[0], self.last["t0"][0], self.cfg.hz, list(params.tol))) + "\n"
             out = check if hasattr(check, "write") else sys.stdout
+            out.write(text)
+            out.flush()
+        if fit:
+            # what fitting the rows' contact forces to the planned motion leaves and changes (force_fit.py); the CSV keeps the plan's forces
+            from . import force_fit
+            P = self.planner(args.get('-duration'))
+            params = capi.fit_params(self.cfg, hz=self.cfg.hz, n_rows=len(self.last["rows"][0]))
+            _, _, summary = P.force_fit(self.last["nodes"][:1], self.last["t0"][:1], params, rows=False)
+            self.last["fit"] = summary[0]
+            text = "\n".join(force_fit.report_lines(summary[0], self.last["t0"][0], self.cfg.hz, list(params.tol))) + "\n"
+            out = fit if hasattr(fit, "write") else sys.stdout
             out.write(text)
             out.flush()
         if out_csv:

@@ -236,11 +236,21 @@ class ShiftedWindows:
                rule: ``plan_check.check_rows`` / ``summarise`` / ``accumulate``) is queued in front of every stitch and in
                ``finish()``, over exactly the rows that stitch appends and with its cursor, and merges what they violate into
                ``self.check_summary`` (B x 5 records as B x 5 x 3 words); ``check_worst()`` reads them.  It writes nothing else:
-               plans and trajectory rows are the same bits with and without it."""
+               plans and trajectory rows are the same bits with and without it.
+    fit        None (the default): nothing is queued and nothing is allocated.  A dict of ``capi.fit_params``' keywords (arm, damping,
+               w_min, excess_tol, tol, robot, ee_shift; needs ``trajectory``) and ``mass_scale`` (a number or one per window), or a
+               ``capi.fit_params(...)`` whose rate and rows become the stitch's: k_force_fit (qtos_force_fit_device, the rule:
+               ``force_fit.fit_rows`` / ``summarise`` / ``accumulate``) is queued behind the joint rows and in front of every stitch
+               and in ``finish()``, over exactly the rows that stitch appends and with its cursor.  It fills a ring next to the joint
+               ring (``self.fit_traj``, B x trajectory x 32: time stamp, fitted forces, residual rows, change, feed-forward torques
+               at the joint ring's angles -- without ``joints`` those twelve columns stay zero) with its status words
+               (``self.fit_status``) and merges the four families into ``self.fit_summary`` (B x 4 records as B x 4 x 3 words);
+               ``fit_rows(b)`` and ``fit_worst()`` read them.  Plans, trajectory rows and joint rows are the same bits with and
+               without it."""
 
     def __init__(self, planner, start, goal_step, map_id=None, advance=2.5, search=0.4, stream=None, warm="none", x_range=None,
                  handover=None, contact="force", height_set=(0.0,), trajectory=None, stitch="clean", path=None, path_base="spine",
-                 path_hold=True, joints=None, track=None, feedback=None, check=None, rollout=None):
+                 path_hold=True, joints=None, track=None, feedback=None, check=None, rollout=None, fit=None):
         import torch
         self.torch = torch
         self.P = planner
@@ -373,6 +383,27 @@ class ShiftedWindows:
             self._check.hz, self._check.first_row, self._check.n_rows = self.hz, int(self._stitch.first_row), int(trajectory)
             self._check.flags |= capi.CHECK_ACCUMULATE
             self.check_summary = torch.from_numpy(plan_check.empty_summary(B).view(np.float64).reshape(B, 5, 3).copy()).to(dev)
+        self._fit = None
+        if fit is not None:
+            from . import capi, force_fit
+            if self.traj is None:
+                raise ValueError("fit needs a trajectory ring (trajectory=N)")
+            if not hasattr(planner.lib, "qtos_force_fit_device"):
+                raise RuntimeError("this build of the planner library has no force-fit kernel (qtos_force_fit_device)")
+            scale = None
+            if isinstance(fit, capi.QtosForceFit):
+                self._fit = fit.copy()
+            else:
+                kw = dict(fit)
+                scale = kw.pop("mass_scale", None)
+                self._fit = capi.fit_params(kw.pop("cfg", getattr(planner, "cfg", None)), **kw)
+            # the stitch's rows: its first row, its ring, its clock
+            self._fit.hz, self._fit.first_row, self._fit.n_rows, self._fit.capacity = self.hz, int(self._stitch.first_row), 0, int(trajectory)
+            self._fit.flags |= capi.FIT_ACCUMULATE
+            self.fit_traj = torch.zeros((B, int(trajectory), capi.FIT_COLS), **f64)
+            self.fit_status = torch.zeros((B, int(trajectory)), dtype=torch.int32, device=dev)
+            self.fit_summary = torch.from_numpy(force_fit.empty_summary(B).view(np.float64).reshape(B, 4, 3).copy()).to(dev)
+            self._fit_scale = None if scale is None else torch.as_tensor(np.broadcast_to(np.asarray(scale, np.float64), (B,)).copy(), **f64)
         self.stream = stream if stream is not None else torch.cuda.current_stream(dev)
         self.have_plan = False
         self.x_range = x_range     # (lo, hi): a window that walks past an end of its heightfield turns round (no resets)
@@ -605,6 +636,37 @@ class ShiftedWindows:
                                                      self.cursor.data_ptr(), None, self.check_summary.data_ptr(), sp),
                    "qtos_plan_check_device")
 
+    def _force_fit(self, params, n_rows, sp):
+        """Queue k_force_fit in front of a stitch, behind the joint rows: the fit rows of the segment that stitch appends, to the
+        same ring rows, with the joint ring's angles where ``joints`` is on, merged into the windows' records (the kernel reads the
+        cursor and the clock the stitch behind it moves on)."""
+        import ctypes as C
+        ptr = lambda t: None if t is None else t.data_ptr()
+        self._call(self.P.lib.qtos_force_fit_device(self.P.h, self.B, C.byref(params), self.nodes.data_ptr(), self.t0.data_ptr(),
+                                                    ptr(self.map_id), None, n_rows, self.cursor.data_ptr(), ptr(self.joint_traj),
+                                                    ptr(self._fit_scale), self.fit_traj.data_ptr(), self.fit_status.data_ptr(),
+                                                    self.fit_summary.data_ptr(), sp), "qtos_force_fit_device")
+
+    def fit_rows(self, b):
+        """Window b's newest min(cursor, trajectory) fit rows in time order and their status words, as numpy (the stream is
+        synchronised): row for row the fitted forces of ``trajectory_rows(b)``."""
+        from .stitcher import ring_rows
+        if self._fit is None:
+            raise RuntimeError("fit_rows() needs the force fit (fit=...)")
+        self.stream.synchronize()
+        cur = int(self.cursor[b].item())
+        return ring_rows(self.fit_traj[b].cpu().numpy(), cur), ring_rows(self.fit_status[b].cpu().numpy(), cur)
+
+    def fit_worst(self):
+        """What the fit left and changed over the windows' executed rows so far, [B, 4] records of force_fit.SUMMARY (the families
+        res_ang, res_lin, change, excess: the largest value, the trajectory row -- the window's clock, as ``cursor`` counts it --
+        that attains it, the rows over the tolerance), as numpy (the stream is synchronised)."""
+        from . import force_fit
+        if self._fit is None:
+            raise RuntimeError("fit_worst() needs the force fit (fit=...)")
+        self.stream.synchronize()
+        return self.fit_summary.cpu().numpy().view(force_fit.SUMMARY).reshape(self.B, 4)
+
     def check_worst(self):
         """What the windows' executed rows violated so far, [B, 5] records of plan_check.SUMMARY (the families dyn_ang, dyn_lin,
         rom, terrain, force: the largest violation, the trajectory row -- the window's clock, as ``cursor`` counts it -- that
@@ -679,6 +741,10 @@ class ShiftedWindows:
                 g.first_row, g.n_rows = first, n
                 with self.torch.cuda.stream(self.stream):
                     self._track_rows(g, None, C.c_void_p(self.stream.cuda_stream))
+            if self._fit is not None:
+                g = self._fit.copy()
+                g.first_row, g.n_rows = first, n
+                self._force_fit(g, None, C.c_void_p(self.stream.cuda_stream))
             if self._check is not None:
                 g = self._check.copy()
                 g.first_row, g.n_rows = first, n
@@ -756,6 +822,8 @@ class ShiftedWindows:
                     self._start_feedback(sp)
                     if self.path is not None:
                         self._path_goal(self.path_params, self.offset, sp)
+                if self._fit is not None:
+                    self._force_fit(self._fit, self.row.data_ptr(), sp)
                 if self._check is not None:
                     self._plan_check(self._check, self.row.data_ptr(), sp)
                 self._call(P.lib.qtos_stitch_device(P.h, B, C.byref(self._stitch), self.nodes.data_ptr(), self.row.data_ptr(),
