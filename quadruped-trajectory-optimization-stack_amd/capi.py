@@ -1,5 +1,8 @@
 """ctypes binding of the HIP planner library (csrc/libqtos_planner.so, ABI in include/qtos_planner.h).
 
+The header's mirror -- constants, structures, prototypes -- is abi.py and is re-exported here; this module adds the builders of
+the parameter structures, the host-only analyses and ``Planner``, the owning wrapper of a handle.
+
 There is no CPU fallback: if the library is missing or no MI355X is visible, loading / creating a
 planner raises.  Build with ``python -c "import __graft_entry__ as g; g.build()"`` or
 ``make -C quadruped-trajectory-optimization-stack_amd/csrc``.
@@ -9,94 +12,47 @@ import os
 
 import numpy as np
 
+from .abi import *  # noqa: F401,F403  (the mirror is part of this module's interface: capi.QtosTrack, capi.TRACK_COLS, capi.EXPORTS ...)
+from .abi import (CHECK_ACCUMULATE, CHECK_COLS, CHECK_FAMILIES, CSV_COLS, FEEDBACK_QUAT, FEEDBACK_SNAP, FEEDBACK_ZERO_FILTER,
+                  FIT_ACCUMULATE, FIT_COLS, FIT_FAMILIES, HIST_COLS, JOINT_NO_FF, MAX_PHASES, NEE, PROTOTYPES, ROLLOUT_COLS,
+                  ROLLOUT_INIT, ROLLOUT_QUAT, ROLLOUT_STATE, START_DOUBLES, TRACK_CLEAN_DELAY, TRACK_COLS, TRACK_QUAT, QtosDims,
+                  QtosForceFit, QtosHandover, QtosJointRows, QtosFeedback, QtosParams, QtosPathGoal, QtosPathPlan, QtosPlanCheck,
+                  QtosProbe, QtosReport, QtosRollout, QtosSelftest, QtosStitch, QtosTerrainEnv, QtosTrack)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# (QTOS_LIB names another build of the library in csrc/: A/B timing of kernel variants, scratch/ab.py)
+# (QTOS_LIB names another build of the library in csrc/: A/B timing of kernel variants, scratch/ab2.py)
 LIB_PATH = os.path.join(_HERE, "csrc", os.environ.get("QTOS_LIB", "libqtos_planner.so"))
-NEE, MAX_PHASES, START_DOUBLES, CSV_COLS = 4, 32, 24, 37
 
-
-class QtosParams(C.Structure):
-    _fields_ = [
-        ("n_phases", C.c_int * NEE),
-        ("phase_dur", (C.c_double * MAX_PHASES) * NEE),
-        ("dt_base", C.c_double), ("dt_dyn", C.c_double), ("dt_rom", C.c_double),
-        ("force_polys_per_stance", C.c_int),
-        ("mass", C.c_double), ("gravity", C.c_double), ("inertia_b", C.c_double * 9),
-        ("nominal_stance", (C.c_double * 3) * NEE), ("max_dev", C.c_double * 3),
-        ("mu", C.c_double), ("f_max", C.c_double), ("t_swing_avg", C.c_double),
-        ("honor_start_velocity", C.c_int), ("terrain_mode", C.c_int),
-        ("max_iter", C.c_int),
-        ("tol", C.c_double), ("mu_init", C.c_double), ("mu_min", C.c_double),
-        ("delta_x", C.c_double), ("eps_dual", C.c_double), ("slack_push", C.c_double), ("warm_slack_push", C.c_double),
-        ("stall_iters", C.c_int), ("hold_from", C.c_int), ("hold_weight", C.c_double), ("hold_tol", C.c_double),
-        ("chord_tol", C.c_double),
-        ("reduce_base", C.c_int),
-        ("chord_max", C.c_int), ("chord_shrink", C.c_double), ("stall_alpha", C.c_double),
-        ("reduce_swing", C.c_int),
-        ("mu_superlinear", C.c_int),
-        ("kappa_sigma", C.c_double),
-    ]
-
-
-class QtosDims(C.Structure):
-    _fields_ = [
-        ("n_vars", C.c_int), ("n_cons", C.c_int),
-        ("n_free", C.c_int), ("n_eq", C.c_int), ("n_ineq", C.c_int),
-        ("n_ineq_lower", C.c_int), ("n_ineq_both", C.c_int), ("n_ineq_upper", C.c_int),
-        ("n_eq_work", C.c_int), ("n_unknowns", C.c_int),
-        ("n_stages", C.c_int), ("pivots", C.c_int), ("front", C.c_int),
-        ("n_base_nodes", C.c_int), ("n_dyn_times", C.c_int), ("n_rom_times", C.c_int),
-        ("n_rows_csv", C.c_int),
-        ("panel_doubles", C.c_longlong), ("g_doubles", C.c_longlong),
-        ("kkt_algorithmic_bytes", C.c_longlong), ("kkt_flops", C.c_longlong),
-        ("envelope", C.c_longlong), ("max_active", C.c_int), ("order_rule", C.c_int),
-        ("duration", C.c_double),
-    ]
-
-
-HIST_COLS = 10   # QTOS_HIST_COLS: one record of the iteration history (qtos_plan_report)
 HIST_NAMES = ("inf_pr", "theta", "mu", "dnorm", "alpha_pr", "alpha_du", "ls", "kind", "compl", "inf_du")
-
-
-class QtosReport(C.Structure):
-    _fields_ = [
-        ("status", C.c_int), ("iterations", C.c_int), ("n_rows", C.c_int),
-        ("n_con_evals", C.c_int), ("n_jac_evals", C.c_int), ("n_factorizations", C.c_int), ("n_chord_solves", C.c_int),
-        ("pad", C.c_int),
-        ("constraint_violation", C.c_double), ("dual_infeasibility", C.c_double), ("complementarity", C.c_double),
-        ("nlp_error", C.c_double),
-    ]
-
-
-class QtosSelftest(C.Structure):
-    """One attempt of the create-time KKT self-test (qtos_planner_selftest)."""
-    _fields_ = [
-        ("order_rule", C.c_int), ("front", C.c_int), ("n_stages", C.c_int), ("n_problems", C.c_int),
-        ("worst_stage", C.c_int), ("passed", C.c_int),
-        ("residual", C.c_double), ("residual_refined", C.c_double), ("max_factor", C.c_double),
-        ("growth_limit", C.c_double), ("tol_residual", C.c_double), ("seconds", C.c_double),
-    ]
-
-    def copy(self):
-        return QtosSelftest.from_buffer_copy(self)
-
-    def describe(self):
-        if not self.front:
-            return "rule %d, not built" % self.order_rule
-        return "rule %d, residual %.1e, max |V| %.2e, %s" % (self.order_rule, self.residual, self.max_factor,
-                                                              "passed" if self.passed else "rejected (stage %d)" % self.worst_stage)
-
-
-class QtosHandover(C.Structure):
-    """Parameters of a replan's hand-over (qtos_handover*, include/qtos_planner.h)."""
-    _fields_ = [
-        ("advance", C.c_double), ("search", C.c_double), ("hz", C.c_double),
-        ("rule", C.c_int), ("n_heights", C.c_int), ("heights", C.c_double * 8),
-        ("zero_filter", C.c_int), ("turn", C.c_int), ("x_lo", C.c_double), ("x_hi", C.c_double),
-    ]
-
-
 HANDOVER_RULES = {"force": 0, "heights": 1}
+STITCH_MODES = {"clean": 0, "reference": 1}     # first_row of the two modes of stitcher.Stitcher
+PATH_BASES = {"spine": 0, "state": 1}           # base point of the clipped step: Global_Planner.update / plan_init
+CHECK_TOL = (1e-3, 1e-2, 1e-4, 1e-4, 1e-2)      # check_params' default per family: N m, N, m, m, N
+FIT_TOL = (1e-3, 1e-2, 5.0, 1e-2)               # fit_params' default per family (force_fit.FIT_TOL): N m, N, N, N
+MAX_TRIED = 3                                   # order rules 0, 1, 2
+
+
+# ---- builders of the parameter structures ----
+def _leg(g, robot):
+    """The leg block of a parameter structure from a robot (joints.SOLO12, or a structure that carries the block): hip, lateral
+    and the link lengths, and knee_sign where the structure has it."""
+    for e in range(4):
+        for d in range(3):
+            g.hip[e][d] = float(robot.hip[e][d])
+        g.lateral[e] = float(robot.lateral[e])
+        if hasattr(g, "knee_sign"):
+            g.knee_sign[e] = float(robot.knee_sign[e])
+    g.l_upper, g.l_lower = float(robot.l_upper), float(robot.l_lower)
+
+
+def _map_shape(maps, name="map_yx", first="n_maps"):
+    """(n_maps, rows, cols) of maps given as n_maps x rows x cols or rows x cols (an array, a tensor or nested lists), or as
+    that shape (a tuple or list of 2 or 3 ints)."""
+    is_shape = isinstance(maps, (tuple, list)) and len(maps) in (2, 3) and all(isinstance(v, (int, np.integer)) for v in maps)
+    shape = tuple(int(v) for v in (maps if is_shape else np.shape(maps)))
+    if len(shape) not in (2, 3):
+        raise ValueError("%s is %s x rows x cols or rows x cols, or that shape" % (name, first))
+    return (1,) + shape if len(shape) == 2 else shape
 
 
 def handover_params(advance=2.5, search=0.4, hz=1000.0, rule="force", heights=(0.0,), zero_filter=False, x_range=None):
@@ -117,16 +73,6 @@ def handover_params(advance=2.5, search=0.4, hz=1000.0, rule="force", heights=(0
     return h
 
 
-class QtosStitch(C.Structure):
-    """Parameters of a stitch call (qtos_stitch*, include/qtos_planner.h)."""
-    _fields_ = [
-        ("hz", C.c_double), ("first_row", C.c_int), ("n_rows", C.c_int), ("advance_clock", C.c_int), ("capacity", C.c_longlong),
-    ]
-
-
-STITCH_MODES = {"clean": 0, "reference": 1}     # first_row of the two modes of stitcher.Stitcher
-
-
 def stitch_params(capacity, first_row=0, n_rows=0, hz=1000.0, advance_clock=True):
     """A QtosStitch: rows first_row .. first_row + n - 1 of every window's plan go to its ring of `capacity` rows; first_row 0
     ("clean") or 1 ("reference": pd.read_csv eats row 0, Stitcher(mode="reference"))."""
@@ -135,22 +81,6 @@ def stitch_params(capacity, first_row=0, n_rows=0, hz=1000.0, advance_clock=True
     s.first_row = STITCH_MODES[first_row] if isinstance(first_row, str) else int(first_row)
     s.n_rows, s.advance_clock = int(n_rows), int(bool(advance_clock))
     return s
-
-
-class QtosPathGoal(C.Structure):
-    """Parameters of a path-goal call (qtos_path_goal*, include/qtos_planner.h)."""
-    _fields_ = [
-        ("horizon", C.c_double), ("step_size", C.c_double), ("tol", C.c_double), ("z_offset", C.c_double),
-        ("cell", C.c_double), ("origin_x", C.c_double), ("origin_y", C.c_double), ("t_stop", C.c_double), ("stop_dist", C.c_double),
-        ("base", C.c_int), ("clamp_x", C.c_int), ("advance_clock", C.c_int), ("hold_done", C.c_int),
-        ("n_paths", C.c_int), ("max_pieces", C.c_int), ("n_maps", C.c_int), ("rows", C.c_int), ("cols", C.c_int),
-    ]
-
-    def copy(self):
-        return QtosPathGoal.from_buffer_copy(self)
-
-
-PATH_BASES = {"spine": 0, "state": 1}      # base point of the clipped step: Global_Planner.update / plan_init
 
 
 def path_goal_params(horizon=5.0, step_size=1.0, tol=1e-5, z_offset=0.24, cell=0.1, origin=(1.0, 1.0), t_stop=5.0, stop_dist=0.0,
@@ -166,21 +96,8 @@ def path_goal_params(horizon=5.0, step_size=1.0, tol=1e-5, z_offset=0.24, cell=0
     if table is not None:
         g.n_paths, g.max_pieces = (int(v) for v in np.shape(table["coef"])[0::3])
     if map_yx is not None:
-        shape = np.shape(map_yx)
-        g.n_maps, g.rows, g.cols = (1,) + tuple(shape) if len(shape) == 2 else tuple(shape)
+        g.n_maps, g.rows, g.cols = _map_shape(map_yx)
     return g
-
-
-class QtosPathPlan(C.Structure):
-    """Parameters of a path-plan call (qtos_path_plan*, include/qtos_planner.h)."""
-    _fields_ = [
-        ("rows", C.c_int), ("cols", C.c_int), ("cell", C.c_double), ("origin_x", C.c_double), ("origin_y", C.c_double),
-        ("height_bound", C.c_double), ("step_size", C.c_double), ("max_cells", C.c_int), ("max_open", C.c_int), ("max_pieces", C.c_int),
-        ("n_maps", C.c_int), ("set_done", C.c_int),
-    ]
-
-    def copy(self):
-        return QtosPathPlan.from_buffer_copy(self)
 
 
 def path_plan_params(step_size=1.0, cell=0.1, origin=(1.0, 1.0), height_bound=0.2, max_cells=None, max_open=4096, max_pieces=None,
@@ -192,24 +109,12 @@ def path_plan_params(step_size=1.0, cell=0.1, origin=(1.0, 1.0), height_bound=0.
     g.step_size, g.cell, g.origin_x, g.origin_y = float(step_size), float(cell), float(origin[0]), float(origin[1])
     g.height_bound, g.max_open, g.set_done = float(height_bound), int(max_open), int(bool(set_done))
     if bool_map is not None:
-        shape = np.shape(bool_map)
-        g.n_maps, g.rows, g.cols = (1,) + tuple(shape) if len(shape) == 2 else tuple(shape)
+        g.n_maps, g.rows, g.cols = _map_shape(bool_map, "bool_map")
     if max_cells is None:
         max_cells = min(2 * (g.rows + g.cols), 16384) if max_pieces is None else 2 * int(max_pieces)
     g.max_cells = int(max_cells)
     g.max_pieces = (g.max_cells + 1) // 2 if max_pieces is None else int(max_pieces)
     return g
-
-
-class QtosProbe(C.Structure):
-    """Parameters of a probe / stamp call (qtos_probe*, qtos_probe_stamp*, include/qtos_planner.h)."""
-    _fields_ = [
-        ("rows", C.c_int), ("cols", C.c_int), ("n_maps", C.c_int), ("cell", C.c_double), ("scale", C.c_int), ("multi_map_shift", C.c_int),
-        ("origin_shift", C.c_double), ("z_offset", C.c_double), ("nominal_stance", (C.c_double * 3) * NEE),
-    ]
-
-    def copy(self):
-        return QtosProbe.from_buffer_copy(self)
 
 
 def probe_params(map_yx=None, multi_map_shift=1, scale=1, origin_shift=1.0, cell=0.1, z_offset=0.24,
@@ -223,26 +128,8 @@ def probe_params(map_yx=None, multi_map_shift=1, scale=1, origin_shift=1.0, cell
         for k in range(3):
             g.nominal_stance[e][k] = float(nominal_stance[e][k])
     if map_yx is not None:
-        is_shape = isinstance(map_yx, (tuple, list)) and len(map_yx) in (2, 3) and all(isinstance(v, (int, np.integer)) for v in map_yx)
-        shape = tuple(int(v) for v in (map_yx if is_shape else np.shape(map_yx)))
-        if len(shape) not in (2, 3):
-            raise ValueError("map_yx is n_maps x rows x cols or rows x cols, or that shape")
-        g.n_maps, g.rows, g.cols = (1,) + shape if len(shape) == 2 else shape
+        g.n_maps, g.rows, g.cols = _map_shape(map_yx)
     return g
-
-
-class QtosTerrainEnv(C.Structure):
-    """Parameters of a terrain-env call (qtos_terrain_env*, include/qtos_planner.h)."""
-    _fields_ = [
-        ("n_maps", C.c_int), ("n_base", C.c_int), ("rows", C.c_int), ("cols", C.c_int), ("n_shift", C.c_int), ("n_height", C.c_int),
-        ("climb", C.c_int), ("delta", C.c_double),
-    ]
-
-    def copy(self):
-        return QtosTerrainEnv.from_buffer_copy(self)
-
-
-ENV_MAX_LEVELS, ENV_MAX_DRAWS, ENV_LDS_BYTES = 64, 1 << 24, 3568     # QTOS_ENV_* of include/qtos_planner.h
 
 
 def terrain_env_params(base_yx=None, n_maps=None, n_shift=10, n_height=10, climb=False, delta=0.005):
@@ -251,30 +138,11 @@ def terrain_env_params(base_yx=None, n_maps=None, n_shift=10, n_height=10, climb
     g = QtosTerrainEnv()
     g.n_shift, g.n_height, g.climb, g.delta = int(n_shift), int(n_height), int(bool(climb)), float(delta)
     if base_yx is not None:
-        is_shape = isinstance(base_yx, (tuple, list)) and len(base_yx) in (2, 3) and all(isinstance(v, (int, np.integer)) for v in base_yx)
-        shape = tuple(int(v) for v in (base_yx if is_shape else np.shape(base_yx)))
-        if len(shape) not in (2, 3):
-            raise ValueError("base_yx is n_base x rows x cols or rows x cols, or that shape")
-        g.n_base, g.rows, g.cols = (1,) + shape if len(shape) == 2 else shape
+        g.n_base, g.rows, g.cols = _map_shape(base_yx, "base_yx", "n_base")
         g.n_maps = g.n_base
     if n_maps is not None:
         g.n_maps = int(n_maps)
     return g
-
-
-class QtosJointRows(C.Structure):
-    """Parameters of a joint-rows call (qtos_joint_rows*, include/qtos_planner.h); joints.joint_rows reads the same fields."""
-    _fields_ = [
-        ("hz", C.c_double), ("first_row", C.c_int), ("n_rows", C.c_int), ("capacity", C.c_longlong), ("ee_shift", C.c_double),
-        ("hip", (C.c_double * 3) * 4), ("lateral", C.c_double * 4), ("l_upper", C.c_double), ("l_lower", C.c_double),
-        ("knee_sign", C.c_double * 4), ("kp", C.c_double * 12), ("kd", C.c_double * 12), ("tau_max", C.c_double), ("flags", C.c_int),
-    ]
-
-    def copy(self):
-        return QtosJointRows.from_buffer_copy(self)
-
-
-JOINT_NO_FF = 1     # QTOS_JOINT_NO_FF of include/qtos_planner.h
 
 
 def joint_params(hz=1000.0, first_row=0, n_rows=0, capacity=0, ee_shift=0.015, kp=20.0, kd=0.08, hip_scale=1.0, knee_scale=1.0,
@@ -282,35 +150,14 @@ def joint_params(hz=1000.0, first_row=0, n_rows=0, capacity=0, ee_shift=0.015, k
     """A QtosJointRows with the SOLO12 leg (joints.SOLO12), towr_transform's ee_shift and the gains of the reference's
     data/config/solo12.yml (kp 20, kd 0.08, scales 1, t_max 8) as defaults.  capacity 0: table mode."""
     from . import joints
-    robot = joints.SOLO12 if robot is None else robot
     g = QtosJointRows()
     g.hz, g.first_row, g.n_rows, g.capacity, g.ee_shift = float(hz), int(first_row), int(n_rows), int(capacity), float(ee_shift)
-    for e in range(4):
-        for d in range(3):
-            g.hip[e][d] = float(robot.hip[e][d])
-        g.lateral[e], g.knee_sign[e] = float(robot.lateral[e]), float(robot.knee_sign[e])
-    g.l_upper, g.l_lower = float(robot.l_upper), float(robot.l_lower)
+    _leg(g, joints.SOLO12 if robot is None else robot)
     for j, (a, b) in enumerate(zip(*joints.motor_gains(kp, kd, hip_scale, knee_scale, ankle_scale))):
         g.kp[j], g.kd[j] = float(a), float(b)
     g.tau_max = float(tau_max)
     g.flags = 0 if feed_forward else JOINT_NO_FF
     return g
-
-
-class QtosTrack(C.Structure):
-    """Parameters of a track call (qtos_track*, include/qtos_planner.h); tracking.track_rows reads the same fields."""
-    _fields_ = [
-        ("hz", C.c_double), ("first_row", C.c_int), ("n_rows", C.c_int), ("capacity", C.c_longlong), ("ee_shift", C.c_double),
-        ("hip", (C.c_double * 3) * 4), ("lateral", C.c_double * 4), ("l_upper", C.c_double), ("l_lower", C.c_double),
-        ("delay", C.c_int), ("flags", C.c_int),
-    ]
-
-    def copy(self):
-        return QtosTrack.from_buffer_copy(self)
-
-
-TRACK_QUAT, TRACK_CLEAN_DELAY = 1, 2     # QTOS_TRACK_QUAT, QTOS_TRACK_CLEAN_DELAY of include/qtos_planner.h
-TRACK_COLS = 26                          # QTOS_TRACK_COLS
 
 
 def track_params(hz=1000.0, first_row=0, n_rows=0, capacity=0, ee_shift=0.015, delay=500, rule="reference", quaternion=False, robot=None):
@@ -320,35 +167,12 @@ def track_params(hz=1000.0, first_row=0, n_rows=0, capacity=0, ee_shift=0.015, d
     from . import joints, tracking
     if rule not in tracking.RULES:
         raise ValueError("rule is 'reference' or 'clean'")
-    robot = joints.SOLO12 if robot is None else robot
     g = QtosTrack()
     g.hz, g.first_row, g.n_rows, g.capacity, g.ee_shift = float(hz), int(first_row), int(n_rows), int(capacity), float(ee_shift)
-    for e in range(4):
-        for d in range(3):
-            g.hip[e][d] = float(robot.hip[e][d])
-        g.lateral[e] = float(robot.lateral[e])
-    g.l_upper, g.l_lower = float(robot.l_upper), float(robot.l_lower)
+    _leg(g, joints.SOLO12 if robot is None else robot)
     g.delay = int(delay)
     g.flags = (TRACK_QUAT if quaternion else 0) | (TRACK_CLEAN_DELAY if rule == "clean" else 0)
     return g
-
-
-class QtosFeedback(C.Structure):
-    """Parameters of a feedback hand-over (qtos_start_feedback*, include/qtos_planner.h); feedback.start_feedback reads the same
-    fields."""
-    _fields_ = [
-        ("hz", C.c_double), ("first_row", C.c_int), ("n_rows", C.c_int), ("capacity", C.c_longlong), ("latency", C.c_double),
-        ("ee_shift", C.c_double), ("hip", (C.c_double * 3) * 4), ("lateral", C.c_double * 4), ("l_upper", C.c_double),
-        ("l_lower", C.c_double), ("gain_pos", C.c_double), ("gain_ang", C.c_double), ("gain_foot", C.c_double),
-        ("max_pos", C.c_double), ("max_ang", C.c_double), ("max_foot", C.c_double), ("nominal", (C.c_double * 3) * 4),
-        ("max_deviation", C.c_double * 3), ("rom_tol", C.c_double), ("snap_tol", C.c_double), ("flags", C.c_int),
-    ]
-
-    def copy(self):
-        return QtosFeedback.from_buffer_copy(self)
-
-
-FEEDBACK_QUAT, FEEDBACK_SNAP, FEEDBACK_ZERO_FILTER = 1, 2, 4     # QTOS_FEEDBACK_* of include/qtos_planner.h
 
 
 def feedback_params(cfg=None, hz=1000.0, first_row=0, n_rows=0, capacity=0, latency=0.0, gain_pos=1.0, gain_ang=1.0, gain_foot=1.0,
@@ -359,19 +183,16 @@ def feedback_params(cfg=None, hz=1000.0, first_row=0, n_rows=0, capacity=0, late
     box, nominal and max_deviation, unless those are given.  capacity 0: table mode."""
     from . import joints
     from .config import PlannerConfig
-    robot = joints.SOLO12 if robot is None else robot
     cfg = PlannerConfig() if cfg is None else cfg
     nominal = cfg.nominal_stance if nominal is None else nominal
     max_deviation = cfg.max_deviation if max_deviation is None else max_deviation
     g = QtosFeedback()
     g.hz, g.first_row, g.n_rows, g.capacity, g.latency = float(hz), int(first_row), int(n_rows), int(capacity), float(latency)
     g.ee_shift = float(ee_shift)
+    _leg(g, joints.SOLO12 if robot is None else robot)
     for e in range(4):
         for d in range(3):
-            g.hip[e][d] = float(robot.hip[e][d])
             g.nominal[e][d] = float(nominal[e][d])
-        g.lateral[e] = float(robot.lateral[e])
-    g.l_upper, g.l_lower = float(robot.l_upper), float(robot.l_lower)
     g.gain_pos, g.gain_ang, g.gain_foot = float(gain_pos), float(gain_ang), float(gain_foot)
     g.max_pos, g.max_ang, g.max_foot = float(max_pos), float(max_ang), float(max_foot)
     for d in range(3):
@@ -381,51 +202,14 @@ def feedback_params(cfg=None, hz=1000.0, first_row=0, n_rows=0, capacity=0, late
     return g
 
 
-class QtosPlanCheck(C.Structure):
-    """Parameters of a plan check (qtos_plan_check*, include/qtos_planner.h)."""
-    _fields_ = [("hz", C.c_double), ("first_row", C.c_int), ("n_rows", C.c_int), ("tol", C.c_double * 5), ("flags", C.c_int)]
-
-    def copy(self):
-        return QtosPlanCheck.from_buffer_copy(self)
-
-
-class QtosCheckRecord(C.Structure):
-    """One family of one window in a plan check's summary; plan_check.SUMMARY is its numpy dtype."""
-    _fields_ = [("max", C.c_double), ("row", C.c_longlong), ("count", C.c_longlong)]
-
-
-CHECK_ACCUMULATE = 1     # QTOS_CHECK_ACCUMULATE of include/qtos_planner.h
-CHECK_COLS = 27          # QTOS_CHECK_COLS
-CHECK_TOL = (1e-3, 1e-2, 1e-4, 1e-4, 1e-2)   # check_params' default per family: N m, N, m, m, N
-
-
 def check_params(hz=1000.0, first_row=0, n_rows=0, tol=CHECK_TOL, accumulate=False):
     """A QtosPlanCheck.  tol: one number for the five families (dyn_ang N m, dyn_lin N, rom m, terrain m, force N) or five."""
     g = QtosPlanCheck()
     g.hz, g.first_row, g.n_rows = float(hz), int(first_row), int(n_rows)
-    for f, v in enumerate(np.broadcast_to(np.asarray(tol, np.float64), (5,))):
+    for f, v in enumerate(np.broadcast_to(np.asarray(tol, np.float64), (CHECK_FAMILIES,))):
         g.tol[f] = float(v)
     g.flags = CHECK_ACCUMULATE if accumulate else 0
     return g
-
-
-class QtosForceFit(C.Structure):
-    """Parameters of a force fit (qtos_force_fit*, include/qtos_planner.h); force_fit.fit_rows reads the same fields."""
-    _fields_ = [
-        ("hz", C.c_double), ("first_row", C.c_int), ("n_rows", C.c_int), ("capacity", C.c_longlong), ("flags", C.c_int),
-        ("arm", C.c_double), ("damping", C.c_double), ("w_min", C.c_double), ("excess_tol", C.c_double), ("tol", C.c_double * 4),
-        ("hip", (C.c_double * 3) * 4), ("lateral", C.c_double * 4), ("l_upper", C.c_double), ("l_lower", C.c_double),
-        ("knee_sign", C.c_double * 4), ("ee_shift", C.c_double),
-    ]
-
-    def copy(self):
-        return QtosForceFit.from_buffer_copy(self)
-
-
-FIT_ACCUMULATE = 1       # QTOS_FIT_ACCUMULATE of include/qtos_planner.h
-FIT_COLS = 32            # QTOS_FIT_COLS
-FIT_FAMILIES = 4         # QTOS_FIT_FAMILIES
-FIT_TOL = (1e-3, 1e-2, 5.0, 1e-2)   # fit_params' default per family (force_fit.FIT_TOL): N m, N, N, N
 
 
 def fit_params(cfg=None, hz=1000.0, first_row=0, n_rows=0, capacity=0, tol=FIT_TOL, accumulate=False, **kw):
@@ -438,33 +222,11 @@ def fit_params(cfg=None, hz=1000.0, first_row=0, n_rows=0, capacity=0, tol=FIT_T
     g.hz, g.first_row, g.n_rows, g.capacity = float(hz), int(first_row), int(n_rows), int(capacity)
     g.flags = FIT_ACCUMULATE if accumulate else 0
     g.arm, g.damping, g.w_min, g.excess_tol = r.arm, r.damping, r.w_min, r.excess_tol
-    for f, v in enumerate(np.broadcast_to(np.asarray(tol, np.float64), (4,))):
+    for f, v in enumerate(np.broadcast_to(np.asarray(tol, np.float64), (FIT_FAMILIES,))):
         g.tol[f] = float(v)
-    for e in range(4):
-        for d in range(3):
-            g.hip[e][d] = float(r.hip[e][d])
-        g.lateral[e], g.knee_sign[e] = float(r.lateral[e]), float(r.knee_sign[e])
-    g.l_upper, g.l_lower, g.ee_shift = r.l_upper, r.l_lower, r.ee_shift
+    _leg(g, r)
+    g.ee_shift = r.ee_shift
     return g
-
-
-class QtosRollout(C.Structure):
-    """Parameters of a rollout (qtos_rollout*, include/qtos_planner.h); rollout.rollout_rows reads the same fields."""
-    _fields_ = [
-        ("hz", C.c_double), ("substeps", C.c_int), ("first_row", C.c_int), ("n_rows", C.c_int), ("capacity", C.c_longlong),
-        ("flags", C.c_int), ("mass", C.c_double), ("gravity", C.c_double), ("inertia_b", C.c_double * 9),
-        ("inertia_b_inv", C.c_double * 9), ("ff_scale", C.c_double), ("kp_lin", C.c_double * 3), ("kd_lin", C.c_double * 3),
-        ("kp_ang", C.c_double * 3), ("kd_ang", C.c_double * 3), ("f_fb_max", C.c_double), ("t_fb_max", C.c_double),
-        ("dev_max", C.c_double), ("tilt_max", C.c_double), ("push_from", C.c_longlong), ("push_ticks", C.c_longlong),
-    ]
-
-    def copy(self):
-        return QtosRollout.from_buffer_copy(self)
-
-
-ROLLOUT_INIT, ROLLOUT_QUAT = 1, 2        # QTOS_ROLLOUT_INIT, QTOS_ROLLOUT_QUAT of include/qtos_planner.h
-ROLLOUT_PENDING = 32                     # QTOS_ROLLOUT_PENDING: in a window's carried word, spent by its first call with rows
-ROLLOUT_COLS, ROLLOUT_STATE = 20, 13     # QTOS_ROLLOUT_COLS, QTOS_ROLLOUT_STATE
 
 
 def rollout_params(cfg=None, hz=1000.0, substeps=1, first_row=0, n_rows=0, capacity=0, init=False, quaternion=False, mass=None,
@@ -487,233 +249,6 @@ def rollout_params(cfg=None, hz=1000.0, substeps=1, first_row=0, n_rows=0, capac
     g.f_fb_max, g.t_fb_max, g.dev_max, g.tilt_max = r.f_fb_max, r.t_fb_max, r.dev_max, r.tilt_max
     g.push_from, g.push_ticks = r.push_from, r.push_ticks
     return g
-
-
-class SelftestError(RuntimeError):
-    """No elimination order passed the KKT self-test (qtos_planner_create_checked returned -6); `attempts`: the QtosSelftest
-    records in the order they were tried."""
-
-    def __init__(self, attempts):
-        self.attempts = attempts
-        RuntimeError.__init__(self, "no elimination order passed the KKT self-test: " + "; ".join(a.describe() for a in attempts))
-
-
-MAX_TRIED = 3    # order rules 0, 1, 2
-
-EXPORTS = [
-    "qtos_planner_create", "qtos_planner_destroy", "qtos_planner_dims", "qtos_last_error",
-    "qtos_set_heightfields", "qtos_plan_batch", "qtos_plan_batch_device", "qtos_sample_csv",
-    "qtos_sample_csv_device", "qtos_last_timing", "qtos_debug_eval", "qtos_debug_newton",
-    "qtos_debug_structure", "qtos_debug_trace", "qtos_debug_factor", "qtos_analyze", "qtos_analyze_sweep",
-    "qtos_set_init_table", "qtos_debug_initial_guess", "qtos_shift_warm", "qtos_shift_warm_device",
-    "qtos_last_timing_chord", "qtos_debug_chord", "qtos_plan_totals",
-    "qtos_plan_submit", "qtos_plan_poll", "qtos_plan_wait", "qtos_set_speculation", "qtos_debug_residual", "qtos_project_nodes",
-    "qtos_debug_stream_len", "qtos_debug_read_stream", "qtos_debug_read_rhs", "qtos_build_flags", "qtos_kkt_kernel",
-    "qtos_last_timing_detail", "qtos_set_pattern_speculation", "qtos_env", "qtos_analyze_two_ended", "qtos_analyze_order", "qtos_set_kernel_events",
-    "qtos_write_csv", "qtos_set_report", "qtos_plan_report", "qtos_analyze_counts", "qtos_debug_duals", "qtos_analyze_kernel",
-    "qtos_planner_selftest", "qtos_planner_create_checked", "qtos_analyze_candidates", "qtos_selftest_inputs", "qtos_selftest_bits",
-    "qtos_selftest_problem", "qtos_handover", "qtos_handover_device", "qtos_stitch", "qtos_stitch_device",
-    "qtos_path_goal", "qtos_path_goal_device", "qtos_path_plan", "qtos_path_plan_device",
-    "qtos_probe", "qtos_probe_device", "qtos_probe_stamp", "qtos_probe_stamp_device",
-    "qtos_terrain_env", "qtos_terrain_env_device", "qtos_set_heightfields_device",
-    "qtos_joint_rows", "qtos_joint_rows_device", "qtos_track", "qtos_track_device",
-    "qtos_start_feedback", "qtos_start_feedback_device", "qtos_plan_check", "qtos_plan_check_device",
-    "qtos_rollout", "qtos_rollout_device", "qtos_force_fit", "qtos_force_fit_device",
-]
-
-_lib = None
-
-
-def load():
-    """Load the HIP library; raises OSError with build instructions if it is missing."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise OSError("HIP planner library not built: %s (run __graft_entry__.build()); "
-                      "this package has no CPU fallback" % LIB_PATH)
-    # One HIP runtime per process: PyTorch-ROCm ships its own libamdhip64 / libhsa-runtime64.  If this library
-    # pulled in the system copies first, a later `import torch` would map a second runtime and see no GPU
-    # (torch.cuda.is_available() False, RCCL unusable).  Binding to torch's copy -- when torch is installed --
-    # makes the import order irrelevant; without torch the system runtime is used.
-    try:
-        import importlib.util
-        spec = importlib.util.find_spec("torch")
-        for loc in (spec.submodule_search_locations or []) if spec else []:
-            hip = os.path.join(loc, "lib", "libamdhip64.so")
-            if os.path.exists(hip):
-                C.CDLL(hip, mode=C.RTLD_GLOBAL)
-                break
-    except Exception:
-        pass
-    lib = C.CDLL(LIB_PATH)
-    _warn_if_two_hip_runtimes()
-    dp, ip, vp = C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_void_p
-    lib.qtos_planner_create.argtypes = [C.POINTER(QtosParams), C.c_int, C.c_int, C.POINTER(vp)]
-    lib.qtos_planner_destroy.argtypes = [vp]
-    lib.qtos_planner_destroy.restype = None
-    lib.qtos_planner_dims.argtypes = [vp, C.POINTER(QtosDims)]
-    lib.qtos_last_error.argtypes = [vp]
-    lib.qtos_last_error.restype = C.c_char_p
-    lib.qtos_set_heightfields.argtypes = [vp, C.c_int, dp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double]
-    lib.qtos_plan_batch.argtypes = [vp, C.c_int, dp, dp, ip, dp, dp, ip, ip, dp]
-    lib.qtos_plan_batch_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.qtos_sample_csv.argtypes = [vp, C.c_int, dp, dp, C.c_double, C.c_int, dp]
-    lib.qtos_write_csv.argtypes = [C.c_char_p, dp, C.c_int, C.c_int]
-    lib.qtos_sample_csv_device.argtypes = [vp, C.c_int, vp, vp, C.c_double, C.c_int, vp, vp]
-    lib.qtos_last_timing.argtypes = [vp, dp, ip, dp, ip]
-    lib.qtos_debug_eval.argtypes = [vp, C.c_int, dp, dp, ip, dp, dp, dp]
-    lib.qtos_debug_newton.argtypes = [vp, C.c_int, dp, dp, ip, dp, dp, dp, dp]
-    lib.qtos_debug_structure.argtypes = [vp, ip, ip, ip]
-    lib.qtos_debug_trace.argtypes = [vp, C.c_int, dp]
-    lib.qtos_debug_factor.argtypes = [vp, C.c_int, dp, ip]
-    lib.qtos_analyze.argtypes = [C.POINTER(QtosParams), C.POINTER(QtosDims), ip, C.c_int]
-    lib.qtos_analyze_sweep.argtypes = [C.POINTER(QtosParams), ip, ip, ip, ip, ip, C.c_int]
-    lib.qtos_set_init_table.argtypes = [vp, C.c_int, dp, C.c_int, dp, dp]
-    lib.qtos_debug_initial_guess.argtypes = [vp, C.c_int, dp, dp, ip, dp]
-    if hasattr(lib, "qtos_last_timing_chord"):
-        lib.qtos_last_timing_chord.argtypes = [vp, dp, ip]
-    if hasattr(lib, "qtos_plan_totals"):
-        lib.qtos_plan_totals.argtypes = [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.c_int]
-        lib.qtos_debug_chord.argtypes = [vp, C.c_int, dp]
-    if hasattr(lib, "qtos_project_nodes"):
-        lib.qtos_project_nodes.argtypes = [vp, C.c_int, dp, dp]
-    if hasattr(lib, "qtos_debug_residual"):
-        lib.qtos_debug_residual.argtypes = [vp, C.c_int, C.c_int, dp, dp]
-    if hasattr(lib, "qtos_plan_submit"):
-        lib.qtos_plan_submit.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-        lib.qtos_plan_poll.argtypes = [vp, ip]
-        lib.qtos_plan_wait.argtypes = [vp]
-        lib.qtos_set_speculation.argtypes = [vp, C.c_int]
-    if hasattr(lib, "qtos_last_timing_detail"):   # (round 6)
-        lib.qtos_last_timing_detail.argtypes = [vp, dp, C.c_int]
-        lib.qtos_set_pattern_speculation.argtypes = [vp, C.c_int]
-        if hasattr(lib, "qtos_set_kernel_events"):
-            lib.qtos_set_kernel_events.argtypes = [vp, C.c_int]
-        lib.qtos_env.argtypes = [vp, C.c_char_p, C.c_int]
-    if hasattr(lib, "qtos_analyze_two_ended"):
-        lib.qtos_analyze_two_ended.argtypes = [C.POINTER(QtosParams), ip, C.c_int]
-    if hasattr(lib, "qtos_analyze_order"):
-        lib.qtos_analyze_order.argtypes = [C.POINTER(QtosParams), ip, C.c_int]
-    if hasattr(lib, "qtos_shift_warm"):   # (absent from older builds loaded through QTOS_LIB for A/B timing)
-        lib.qtos_shift_warm.argtypes = [vp, C.c_int, dp, dp, dp, dp, ip, dp]
-        lib.qtos_shift_warm_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]
-    if hasattr(lib, "qtos_set_report"):   # (the per-solve report; older builds loaded through QTOS_LIB lack it)
-        lib.qtos_set_report.argtypes = [vp, C.c_int]
-        lib.qtos_plan_report.argtypes = [vp, C.c_int, C.POINTER(QtosReport), dp, C.c_int]
-        lib.qtos_debug_duals.argtypes = [vp, C.c_int, dp, dp, dp, dp]
-    if hasattr(lib, "qtos_analyze_counts"):
-        lib.qtos_analyze_counts.argtypes = [C.POINTER(QtosParams), C.POINTER(C.c_longlong), C.c_int]
-    if hasattr(lib, "qtos_analyze_kernel"):
-        lib.qtos_analyze_kernel.argtypes = [C.POINTER(QtosParams), C.c_char_p, C.c_int]
-    if hasattr(lib, "qtos_planner_selftest"):   # (the create-time KKT self-test)
-        ull = C.c_ulonglong
-        lib.qtos_planner_selftest.argtypes = [vp, ull, C.c_double, C.POINTER(QtosSelftest)]
-        lib.qtos_planner_create_checked.argtypes = [C.POINTER(QtosParams), C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(vp),
-                                                    C.POINTER(QtosSelftest), C.c_int, ip]
-        lib.qtos_analyze_candidates.argtypes = [C.POINTER(QtosParams), C.c_int, ip, ip, ip, C.c_int]
-        lib.qtos_selftest_inputs.argtypes = [C.POINTER(QtosParams), ull, C.c_int, dp, dp, dp]
-        lib.qtos_selftest_bits.argtypes = [ull, C.c_int, C.c_int, ull]
-        lib.qtos_selftest_bits.restype = ull
-        lib.qtos_selftest_problem.argtypes = [C.POINTER(QtosParams), dp, dp]
-    if hasattr(lib, "qtos_handover"):   # (the hand-over kernel of the receding windows; older builds loaded through QTOS_LIB lack it)
-        lib.qtos_handover.argtypes = [vp, C.c_int, C.POINTER(QtosHandover), dp, dp, dp, dp, dp, ip]
-        lib.qtos_handover_device.argtypes = [vp, C.c_int, C.POINTER(QtosHandover), vp, vp, vp, vp, vp, vp, vp]
-    if hasattr(lib, "qtos_stitch"):     # (the stitch kernel of the receding windows; older builds lack it)
-        llp = C.POINTER(C.c_longlong)
-        lib.qtos_stitch.argtypes = [vp, C.c_int, C.POINTER(QtosStitch), dp, ip, dp, dp, llp]
-        lib.qtos_stitch_device.argtypes = [vp, C.c_int, C.POINTER(QtosStitch), vp, vp, vp, vp, vp, vp]
-    if hasattr(lib, "qtos_path_goal"):  # (the path-goal kernel of the receding windows; older builds lack it)
-        lib.qtos_path_goal.argtypes = [vp, C.c_int, C.POINTER(QtosPathGoal), dp, dp, ip, dp, ip, dp, ip, dp, dp, dp, dp, ip]
-        lib.qtos_path_goal_device.argtypes = [vp, C.c_int, C.POINTER(QtosPathGoal)] + [vp] * 13
-    if hasattr(lib, "qtos_path_plan"):  # (the path-plan kernel of the receding windows; older builds lack it)
-        lib.qtos_path_plan.argtypes = [vp, C.c_int, C.POINTER(QtosPathPlan), dp, ip, dp, dp, dp, dp, ip, ip, ip, ip, ip]
-        lib.qtos_path_plan_device.argtypes = [vp, C.c_int, C.POINTER(QtosPathPlan)] + [vp] * 12
-    if hasattr(lib, "qtos_probe"):      # (the probe and stamp kernels of the windows' boolean maps; older builds lack them)
-        lib.qtos_probe.argtypes = [vp, C.POINTER(QtosProbe), dp, C.c_int, ip, ip, ip, dp, dp, ip]
-        lib.qtos_probe_device.argtypes = [vp, C.POINTER(QtosProbe), vp, C.c_int] + [vp] * 7
-        lib.qtos_probe_stamp.argtypes = [vp, C.POINTER(QtosProbe), ip, ip, ip, ip, dp]
-        lib.qtos_probe_stamp_device.argtypes = [vp, C.POINTER(QtosProbe)] + [vp] * 6
-    if hasattr(lib, "qtos_terrain_env"):    # (the terrain-env kernel; older builds loaded through QTOS_LIB lack it)
-        u64p = C.POINTER(C.c_uint64)
-        lib.qtos_terrain_env.argtypes = [vp, C.POINTER(QtosTerrainEnv), dp, ip, u64p, ip, dp, dp, ip]
-        lib.qtos_terrain_env_device.argtypes = [vp, C.POINTER(QtosTerrainEnv)] + [vp] * 8
-    if hasattr(lib, "qtos_joint_rows"):     # (the joint-rows kernel; older builds loaded through QTOS_LIB lack it)
-        llp = C.POINTER(C.c_longlong)
-        lib.qtos_joint_rows.argtypes = [vp, C.c_int, C.POINTER(QtosJointRows), dp, dp, ip, ip, llp, dp, dp, dp, ip]
-        lib.qtos_joint_rows_device.argtypes = [vp, C.c_int, C.POINTER(QtosJointRows)] + [vp] * 10
-    if hasattr(lib, "qtos_track"):          # (the track kernel; older builds loaded through QTOS_LIB lack it)
-        llp = C.POINTER(C.c_longlong)
-        lib.qtos_track.argtypes = [vp, C.c_int, C.POINTER(QtosTrack), dp, dp, ip, ip, llp, dp, dp, llp, dp, dp, ip]
-        lib.qtos_track_device.argtypes = [vp, C.c_int, C.POINTER(QtosTrack)] + [vp] * 12
-    if hasattr(lib, "qtos_start_feedback"):          # (the feedback hand-over; older builds loaded through QTOS_LIB lack it)
-        llp = C.POINTER(C.c_longlong)
-        lib.qtos_start_feedback.argtypes = [vp, C.c_int, C.POINTER(QtosFeedback), dp, dp, ip, llp, dp, ip, dp, dp, dp, dp, ip]
-        lib.qtos_start_feedback_device.argtypes = [vp, C.c_int, C.POINTER(QtosFeedback)] + [vp] * 12
-    if hasattr(lib, "qtos_plan_check"):              # (the plan check; older builds loaded through QTOS_LIB lack it)
-        llp = C.POINTER(C.c_longlong)
-        lib.qtos_plan_check.argtypes = [vp, C.c_int, C.POINTER(QtosPlanCheck), dp, dp, ip, ip, ip, llp, dp, vp]
-        lib.qtos_plan_check_device.argtypes = [vp, C.c_int, C.POINTER(QtosPlanCheck)] + [vp] * 9
-    if hasattr(lib, "qtos_rollout"):                 # (the rollout kernel; older builds loaded through QTOS_LIB lack it)
-        llp = C.POINTER(C.c_longlong)
-        lib.qtos_rollout.argtypes = [vp, C.c_int, C.POINTER(QtosRollout), dp, dp, ip, ip, llp, dp, dp, dp, dp, llp, ip, dp, dp, ip]
-        lib.qtos_rollout_device.argtypes = [vp, C.c_int, C.POINTER(QtosRollout)] + [vp] * 15
-    if hasattr(lib, "qtos_force_fit"):               # (the force fit; older builds loaded through QTOS_LIB lack it)
-        llp = C.POINTER(C.c_longlong)
-        lib.qtos_force_fit.argtypes = [vp, C.c_int, C.POINTER(QtosForceFit), dp, dp, ip, ip, ip, llp, dp, dp, dp, ip, vp]
-        lib.qtos_force_fit_device.argtypes = [vp, C.c_int, C.POINTER(QtosForceFit)] + [vp] * 12
-    if hasattr(lib, "qtos_set_heightfields_device"):
-        lib.qtos_set_heightfields_device.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, vp]
-    _lib = lib
-    return lib
-
-
-def _warn_if_two_hip_runtimes():
-    """The pre-load above gives ONE HIP runtime only if torch's libamdhip64 has the SONAME this library was linked against:
-    with a torch wheel built for another ROCm major both copies get mapped and the kernels register with whichever wins
-    symbol lookup.  Said loudly instead of failing obscurely later."""
-    try:
-        paths = {ln.split()[-1] for ln in open("/proc/self/maps") if "libamdhip64" in ln}
-        real = {os.path.realpath(q) for q in paths}
-        if len(real) > 1:
-            import warnings
-            warnings.warn("two HIP runtimes are mapped into this process (%s): the planner library and PyTorch do not share "
-                          "one libamdhip64; GPU work may fail or see no device" % ", ".join(sorted(real)))
-    except OSError:
-        pass
-
-
-def _dp(a):
-    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
-
-
-def _ip(a):
-    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_int))
-
-
-def _llp(a):
-    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_longlong))
-
-
-def _i32(a, B):
-    """An int or an array of B ints as a contiguous int32 array of B (None stays None)."""
-    return None if a is None else np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.int32), (B,)))
-
-
-def _rows(params):
-    """The rows per window of a window kernel's tables (params.n_rows) or rings (params.capacity)."""
-    return int(params.capacity) if params.capacity > 0 else int(params.n_rows)
-
-
-def _segment(params, B, cursor, *rings):
-    """(rows, cursor) of a window kernel's host form: _rows, and the rings' cursor as B contiguous int64 (table mode: None).
-    `rings`: what ring mode needs besides."""
-    if params.capacity <= 0:
-        return _rows(params), None
-    if cursor is None or any(r is None for r in rings):
-        raise ValueError("ring mode takes the rings as they stand: out, status and cursor" if rings else
-                         "ring mode takes the ring's cursor")
-    return _rows(params), np.ascontiguousarray(np.broadcast_to(np.asarray(cursor, np.int64), (B,)))
 
 
 def params_from_config(cfg):
@@ -756,6 +291,192 @@ def params_from_config(cfg):
     return p
 
 
+class SelftestError(RuntimeError):
+    """No elimination order passed the KKT self-test (qtos_planner_create_checked returned -6); `attempts`: the QtosSelftest
+    records in the order they were tried."""
+
+    def __init__(self, attempts):
+        self.attempts = attempts
+        RuntimeError.__init__(self, "no elimination order passed the KKT self-test: " + "; ".join(a.describe() for a in attempts))
+
+
+# ---- the library ----
+_lib = None
+
+
+def load():
+    """Load the HIP library; raises OSError with build instructions if it is missing."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    if not os.path.exists(LIB_PATH):
+        raise OSError("HIP planner library not built: %s (run __graft_entry__.build()); "
+                      "this package has no CPU fallback" % LIB_PATH)
+    # One HIP runtime per process: PyTorch-ROCm ships its own libamdhip64 / libhsa-runtime64.  If this library
+    # pulled in the system copies first, a later `import torch` would map a second runtime and see no GPU
+    # (torch.cuda.is_available() False, RCCL unusable).  Binding to torch's copy -- when torch is installed --
+    # makes the import order irrelevant; without torch the system runtime is used.
+    try:
+        import importlib.util
+        spec = importlib.util.find_spec("torch")
+        for loc in (spec.submodule_search_locations or []) if spec else []:
+            hip = os.path.join(loc, "lib", "libamdhip64.so")
+            if os.path.exists(hip):
+                C.CDLL(hip, mode=C.RTLD_GLOBAL)
+                break
+    except Exception:
+        pass
+    lib = C.CDLL(LIB_PATH)
+    _warn_if_two_hip_runtimes()
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(lib, name, None)       # (an older build loaded through QTOS_LIB for A/B timing lacks the newer entry points: has())
+        if fn is not None:
+            fn.restype, fn.argtypes = restype, argtypes
+    _lib = lib
+    return lib
+
+
+def _warn_if_two_hip_runtimes():
+    """The pre-load above gives ONE HIP runtime only if torch's libamdhip64 has the SONAME this library was linked against:
+    with a torch wheel built for another ROCm major both copies get mapped and the kernels register with whichever wins
+    symbol lookup.  Said loudly instead of failing obscurely later."""
+    try:
+        paths = {ln.split()[-1] for ln in open("/proc/self/maps") if "libamdhip64" in ln}
+        real = {os.path.realpath(q) for q in paths}
+        if len(real) > 1:
+            import warnings
+            warnings.warn("two HIP runtimes are mapped into this process (%s): the planner library and PyTorch do not share "
+                          "one libamdhip64; GPU work may fail or see no device" % ", ".join(sorted(real)))
+    except OSError:
+        pass
+
+
+def has(symbol):
+    """Whether the loaded library exports `symbol`."""
+    lib = load()
+    return hasattr(lib, symbol)
+
+
+def _need(symbol, what):
+    if not has(symbol):
+        raise RuntimeError("this build of the planner library has no %s (%s)" % (what, symbol))
+
+
+# ---- pointers ----
+def ptr(t):
+    """The device pointer of a tensor for a device form (None stays None)."""
+    return None if t is None else t.data_ptr()
+
+
+def ptr_given(t):
+    """ptr() where an argument may also be True or False, which name no tensor."""
+    return None if t is None or t is True or t is False else t.data_ptr()
+
+
+def _dp(a):
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _ip(a):
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_int))
+
+
+def _llp(a):
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_longlong))
+
+
+def _vp(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+# ---- staging of the host forms' arguments (None stays None throughout) ----
+def _bcast(a, B, dtype=np.float64, copy=False):
+    """A number or an array of B as a contiguous array of B of that dtype; copy: one the call may write to."""
+    if a is None:
+        return None
+    a = np.broadcast_to(np.asarray(a, dtype), (B,))
+    return np.array(a) if copy else np.ascontiguousarray(a)
+
+
+def _vec(a, B, dtype=np.int32):
+    """An array of B entries (B -1: of however many it has) as a contiguous one of that dtype."""
+    return None if a is None else np.ascontiguousarray(a, dtype).reshape(B)
+
+
+def _mat(a, shape, copy=False):
+    """An array as contiguous float64 of that shape; copy: one the call may write to."""
+    return None if a is None else (np.array if copy else np.ascontiguousarray)(a, np.float64).reshape(shape)
+
+
+def _maps(a):
+    """Maps n_maps x rows x cols, or rows x cols for one, as a contiguous float64 array n_maps x rows x cols."""
+    a = np.ascontiguousarray(a, np.float64)
+    return a[None] if a.ndim == 2 else a
+
+
+def _rows(params):
+    """The rows per window of a window kernel's tables (params.n_rows) or rings (params.capacity)."""
+    return int(params.capacity) if params.capacity > 0 else int(params.n_rows)
+
+
+def _segment(params, B, cursor, *rings):
+    """(rows, cursor) of a window kernel's host form: _rows, and the rings' cursor as B contiguous int64 (table mode: None).
+    `rings`: what ring mode needs besides."""
+    if params.capacity <= 0:
+        return _rows(params), None
+    if cursor is None or any(r is None for r in rings):
+        raise ValueError("ring mode takes the rings as they stand: out, status and cursor" if rings else
+                         "ring mode takes the ring's cursor")
+    return _rows(params), _bcast(cursor, B, np.int64)
+
+
+def _table(rows, shape, reshape=False):
+    """The `rows` argument of a host form: True: a new table of zeros; False / None: no table; an array: a float64 copy of it
+    (reshape: brought to `shape`; otherwise its shape is the caller's to check)."""
+    if rows is True:
+        return np.zeros(shape)
+    if rows is False or rows is None:
+        return None
+    rows = np.array(rows, np.float64)
+    return rows.reshape(shape) if reshape else rows
+
+
+def _summary(summary, rows, records, B, families):
+    """The `summary` argument of a host form: False: none, which needs a table (`rows`); None: empty records; an array: a
+    copy of it as B x families records.  records: plan_check or force_fit, which define the dtype SUMMARY."""
+    if summary is False:
+        if rows is None:
+            raise ValueError("rows and summary cannot both be left out")
+        return None
+    if summary is None:
+        return records.empty_summary(B)
+    return np.array(summary, records.SUMMARY).reshape(B, families)
+
+
+def _meas(meas, B, rows, quaternion):
+    """The measured rows of a host form as contiguous float64: (B, rows, 18), or 19 columns with the quaternion."""
+    mcols = 19 if quaternion else 18
+    meas = np.ascontiguousarray(meas, np.float64)
+    if meas.shape != (B, max(rows, 0), mcols):
+        raise ValueError("meas is (B, %d, %d)" % (rows, mcols))
+    return meas
+
+
+def _out_status(out, status, B, rows, cols):
+    """The row table and the status words a host form writes: copies of the arrays as they stand, or (None) zeros."""
+    out = np.zeros((B, max(rows, 0), cols)) if out is None else np.array(out, np.float64)
+    status = np.zeros((B, max(rows, 0)), np.int32) if status is None else np.array(status, np.int32)
+    if out.shape != (B, rows, cols) or status.shape != (B, rows):
+        raise ValueError("out is (B, %d, %d) and status (B, %d)" % (rows, cols, rows))
+    return out, status
+
+
+def _goal_pair(goal_step, goal):
+    if (goal_step is None) != (goal is None):
+        raise ValueError("goal_step and goal go together: give both or neither")
+
+
+# ---- host-only entry points ----
 def build_flags():
     """Bit 0: reserved, always 0; bit 1: stamps; bit 2: development build."""
     return int(load().qtos_build_flags())
@@ -776,12 +497,11 @@ def analyze(cfg):
 def analyze_counts(cfg):
     """Host-only: (nonzeros of the equality, of the inequality constraint Jacobian) of the full system, the counts the
     Ipopt header prints (qtos_analyze_counts).  None with a library that lacks the entry point."""
-    lib = load()
-    if not hasattr(lib, "qtos_analyze_counts"):
+    if not has("qtos_analyze_counts"):
         return None
     p = params_from_config(cfg)
     c = (C.c_longlong * 2)()
-    if lib.qtos_analyze_counts(C.byref(p), c, 2) != 2:
+    if load().qtos_analyze_counts(C.byref(p), c, 2) != 2:
         raise ValueError("qtos_analyze_counts failed")
     return int(c[0]), int(c[1])
 
@@ -799,10 +519,8 @@ def analyze_kernel(cfg):
 
 
 def _selftest_lib():
-    lib = load()
-    if not hasattr(lib, "qtos_planner_selftest"):
-        raise RuntimeError("this build of the planner library has no KKT self-test (qtos_planner_selftest)")
-    return lib
+    _need("qtos_planner_selftest", "KKT self-test")
+    return load()
 
 
 def analyze_candidates(cfg, rules_mask=0):
@@ -931,27 +649,71 @@ class Planner:
         if rc != 0:
             raise RuntimeError("%s failed (%d): %s" % (what, rc, self.lib.qtos_last_error(self.h).decode()))
 
+    # ---- what this build of the library has (a build loaded through QTOS_LIB for A/B timing may be an older one) ----
+    has, _need = staticmethod(has), staticmethod(_need)      # (the module's: a handle's library is the loaded one)
+
+    def has_report(self):
+        return self.has("qtos_set_report")
+
+    def has_handover(self):
+        return self.has("qtos_handover")
+
+    def has_stitch(self):
+        return self.has("qtos_stitch")
+
+    def has_joint_rows(self):
+        return self.has("qtos_joint_rows")
+
+    def has_track(self):
+        return self.has("qtos_track")
+
+    def has_rollout(self):
+        return self.has("qtos_rollout")
+
+    def has_start_feedback(self):
+        return self.has("qtos_start_feedback")
+
+    def has_plan_check(self):
+        return self.has("qtos_plan_check")
+
+    def has_force_fit(self):
+        return self.has("qtos_force_fit")
+
+    def has_path_goal(self):
+        return self.has("qtos_path_goal")
+
+    def has_path_plan(self):
+        return self.has("qtos_path_plan")
+
+    def has_probe(self):
+        return self.has("qtos_probe")
+
+    def has_terrain_env(self):
+        return self.has("qtos_terrain_env")
+
+    def _nodes(self, nodes):
+        """(nodes as contiguous float64 B x n, B): how every host form takes its plans."""
+        nodes = np.ascontiguousarray(nodes, np.float64).reshape(-1, self.n)
+        return nodes, nodes.shape[0]
+
     def set_heightfields(self, maps, cell, x0=-1.0, y0=-1.0):
         """maps: (n_maps, nx, ny) heights, maps[k][ix][iy] at x = x0 + ix*cell, y = y0 + iy*cell."""
         if maps is None:
             self._chk(self.lib.qtos_set_heightfields(self.h, 0, None, 0, 0, 1.0, 0.0, 0.0), "set_heightfields")
             return
-        a = np.ascontiguousarray(maps, dtype=np.float64)
-        if a.ndim == 2:
-            a = a[None]
+        a = _maps(maps)
         self._chk(self.lib.qtos_set_heightfields(self.h, a.shape[0], _dp(a), a.shape[1], a.shape[2],
                                                  cell, x0, y0), "set_heightfields")
 
     def plan(self, start, goal, map_id=None, warm=None):
-        start = np.ascontiguousarray(start, np.float64).reshape(-1, START_DOUBLES)
-        goal = np.ascontiguousarray(goal, np.float64).reshape(-1, 3)
+        start = _mat(start, (-1, START_DOUBLES))
+        goal = _mat(goal, (-1, 3))
         B = start.shape[0]
         nodes = np.empty((B, self.n))
         status = np.empty(B, np.int32)
         iters = np.empty(B, np.int32)
         viol = np.empty(B)
-        mid = None if map_id is None else np.ascontiguousarray(map_id, np.int32)
-        wm = None if warm is None else np.ascontiguousarray(warm, np.float64).reshape(B, self.n)
+        mid, wm = _vec(map_id, -1), _mat(warm, (B, self.n))
         self._chk(self.lib.qtos_plan_batch(self.h, B, _dp(start), _dp(goal), _ip(mid), _dp(wm),
                                            _dp(nodes), _ip(status), _ip(iters), _dp(viol)), "plan_batch")
         return nodes, status, iters, viol
@@ -984,19 +746,15 @@ class Planner:
 
     def selftest(self, seed=0, tol_residual=0.0):
         """One run of the KKT self-test on this handle (qtos_planner_selftest): a QtosSelftest; raises while a call is open."""
-        _selftest_lib()
+        self._need("qtos_planner_selftest", "KKT self-test")
         t = QtosSelftest()
         self._chk(self.lib.qtos_planner_selftest(self.h, int(seed), float(tol_residual), C.byref(t)), "planner_selftest")
         return t
 
-    def has_report(self):
-        return hasattr(self.lib, "qtos_set_report")
-
     def set_report(self, on):
         """Per-solve report (iteration history + final measures) for the calls submitted from now on; raises while a call is
         open (the flag is latched per call)."""
-        if not self.has_report():
-            raise RuntimeError("this build of the planner library has no per-solve report (qtos_set_report)")
+        self._need("qtos_set_report", "per-solve report")
         self._chk(self.lib.qtos_set_report(self.h, int(bool(on))), "set_report")
 
     def report(self, b):
@@ -1030,9 +788,8 @@ class Planner:
         return {k: (a[i] if i < 5 or i in (10, 12) else int(a[i])) for i, k in enumerate(keys)}
 
     def sample(self, nodes, t0, hz=1000.0, n_rows=None):
-        nodes = np.ascontiguousarray(nodes, np.float64).reshape(-1, self.n)
-        B = nodes.shape[0]
-        t0 = np.ascontiguousarray(np.broadcast_to(np.asarray(t0, np.float64), (B,)))
+        nodes, B = self._nodes(nodes)
+        t0 = _bcast(t0, B)
         if n_rows is None:
             n_rows = int(round(self.dims.duration * hz)) + 1
         rows = np.empty((B, n_rows, CSV_COLS))
@@ -1041,18 +798,12 @@ class Planner:
 
     def shift_warm(self, nodes_prev, offset, start, goal, map_id=None):
         """Time-shifted warm start of a replan (qtos_shift_warm): previous plan read `offset` seconds later."""
-        nodes_prev = np.ascontiguousarray(nodes_prev, np.float64).reshape(-1, self.n)
-        B = nodes_prev.shape[0]
-        off = np.ascontiguousarray(np.broadcast_to(np.asarray(offset, np.float64), (B,)))
-        start = np.ascontiguousarray(start, np.float64).reshape(B, START_DOUBLES)
-        goal = np.ascontiguousarray(goal, np.float64).reshape(B, 3)
-        mid = None if map_id is None else np.ascontiguousarray(map_id, np.int32)
+        nodes_prev, B = self._nodes(nodes_prev)
+        off, mid = _bcast(offset, B), _vec(map_id, -1)
+        start, goal = _mat(start, (B, START_DOUBLES)), _mat(goal, (B, 3))
         out = np.empty((B, self.n))
         self._chk(self.lib.qtos_shift_warm(self.h, B, _dp(nodes_prev), _dp(off), _dp(start), _dp(goal), _ip(mid), _dp(out)), "shift_warm")
         return out
-
-    def has_handover(self):
-        return hasattr(self.lib, "qtos_handover")
 
     def handover(self, nodes, advance=2.5, search=0.4, hz=1000.0, rule="force", heights=(0.0,), zero_filter=False,
                  goal_step=None, goal=None, x_range=None):
@@ -1060,46 +811,31 @@ class Planner:
         of every plan in `nodes` that passes the contact rule.  Returns (start [B, 24], offset [B], row [B]); with goal_step
         (B x 3; turned round outside x_range if that is given) and goal (B x 3; its z is kept) also their new values:
         (start, offset, row, goal_step, goal)."""
-        if not self.has_handover():
-            raise RuntimeError("this build of the planner library has no hand-over kernel (qtos_handover)")
-        nodes = np.ascontiguousarray(nodes, np.float64).reshape(-1, self.n)
-        B = nodes.shape[0]
+        self._need("qtos_handover", "hand-over kernel")
+        nodes, B = self._nodes(nodes)
         h = handover_params(advance, search, hz, rule, heights, zero_filter, x_range)
         start, offset, row = np.empty((B, START_DOUBLES)), np.empty(B), np.empty(B, np.int32)
-        gs = gl = None
-        if (goal_step is None) != (goal is None):
-            raise ValueError("goal_step and goal go together: give both or neither")
-        if goal_step is not None:
-            gs = np.array(goal_step, np.float64).reshape(B, 3)
-            gl = np.array(goal, np.float64).reshape(B, 3)
+        _goal_pair(goal_step, goal)
+        gs, gl = _mat(goal_step, (B, 3), copy=True), _mat(goal, (B, 3), copy=True)
         self._chk(self.lib.qtos_handover(self.h, B, C.byref(h), _dp(nodes), _dp(gs), _dp(start), _dp(gl), _dp(offset), _ip(row)), "handover")
         return (start, offset, row) if gs is None else (start, offset, row, gs, gl)
-
-    def has_stitch(self):
-        return hasattr(self.lib, "qtos_stitch")
 
     def stitch(self, nodes, n_rows, t0, traj, cursor, first_row=0, hz=1000.0, advance_clock=True):
         """Append an executed segment of every plan in `nodes` to its window's ring (qtos_stitch, host form): rows first_row ..
         first_row + n - 1 with n = n_rows[b] (an array: in a loop, the hand-over rows) or n_rows (an int, for every window),
         clamped to 0 .. capacity, go to traj[b][(cursor[b] + j) % capacity]; traj is (B, capacity, 37).  Returns new arrays
         (traj, cursor, t0): cursor + n and, with advance_clock, t0 + n / hz."""
-        if not self.has_stitch():
-            raise RuntimeError("this build of the planner library has no stitch kernel (qtos_stitch)")
-        nodes = np.ascontiguousarray(nodes, np.float64).reshape(-1, self.n)
-        B = nodes.shape[0]
+        self._need("qtos_stitch", "stitch kernel")
+        nodes, B = self._nodes(nodes)
         traj = np.array(traj, np.float64)
         if traj.ndim != 3 or traj.shape[0] != B or traj.shape[2] != CSV_COLS:
             raise ValueError("traj is (B, capacity, %d)" % CSV_COLS)
-        t0 = np.array(np.broadcast_to(np.asarray(t0, np.float64), (B,)))
-        cursor = np.array(np.broadcast_to(np.asarray(cursor, np.int64), (B,)))
-        per = None if np.ndim(n_rows) == 0 else np.ascontiguousarray(n_rows, np.int32).reshape(B)
+        t0, cursor = _bcast(t0, B, copy=True), _bcast(cursor, B, np.int64, copy=True)
+        per = None if np.ndim(n_rows) == 0 else _vec(n_rows, B)
         s = stitch_params(traj.shape[1], first_row, 0 if per is not None else n_rows, hz, advance_clock)
         self._chk(self.lib.qtos_stitch(self.h, B, C.byref(s), _dp(nodes), _ip(per), _dp(t0), _dp(traj), _llp(cursor)),
                   "stitch")
         return traj, cursor, t0
-
-    def has_joint_rows(self):
-        return hasattr(self.lib, "qtos_joint_rows")
 
     def joint_rows(self, nodes, t0, params=None, first_row=None, n_rows=None, q_mes=None, qd_mes=None, out=None, status=None,
                    cursor=None):
@@ -1110,26 +846,18 @@ class Planner:
         (an array) or params.first_row.  n_rows (an array) gives every window its own count.  With params.n_rows = 1, first_row
         and the measured q_mes, qd_mes (B x 12) that is one tick of B robots.  Ring mode (params.capacity > 0): `out`
         (B x capacity x 37), `status` (B x capacity) and `cursor` (B) are the rings as they stand; returns new arrays."""
-        if not self.has_joint_rows():
-            raise RuntimeError("this build of the planner library has no joint-rows kernel (qtos_joint_rows)")
-        nodes = np.ascontiguousarray(nodes, np.float64).reshape(-1, self.n)
-        B = nodes.shape[0]
-        t0 = np.ascontiguousarray(np.broadcast_to(np.asarray(t0, np.float64), (B,)))
+        self._need("qtos_joint_rows", "joint-rows kernel")
+        nodes, B = self._nodes(nodes)
+        t0 = _bcast(t0, B)
         if params is None:
             params = joint_params(n_rows=int(round(self.dims.duration * 1000.0)) + 1)
-        f12 = lambda a: None if a is None else np.ascontiguousarray(a, np.float64).reshape(B, 12)
-        first, per, qm, qdm = _i32(first_row, B), _i32(n_rows, B), f12(q_mes), f12(qd_mes)
+        first, per = _bcast(first_row, B, np.int32), _bcast(n_rows, B, np.int32)
+        qm, qdm = _mat(q_mes, (B, 12)), _mat(qd_mes, (B, 12))
         rows, cur = _segment(params, B, cursor, out, status)
-        out = np.zeros((B, max(rows, 0), CSV_COLS)) if out is None else np.array(out, np.float64)
-        status = np.zeros((B, max(rows, 0)), np.int32) if status is None else np.array(status, np.int32)
-        if out.shape != (B, rows, CSV_COLS) or status.shape != (B, rows):
-            raise ValueError("out is (B, %d, %d) and status (B, %d)" % (rows, CSV_COLS, rows))
+        out, status = _out_status(out, status, B, rows, CSV_COLS)
         self._chk(self.lib.qtos_joint_rows(self.h, B, C.byref(params), _dp(nodes), _dp(t0), _ip(first), _ip(per),
                                            _llp(cur), _dp(qm), _dp(qdm), _dp(out), _ip(status)), "joint_rows")
         return out, status
-
-    def has_track(self):
-        return hasattr(self.lib, "qtos_track")
 
     def track(self, nodes, t0, meas, params, first_row=None, n_rows=None, cursor=None, goal_x=None, count=None, total=None, out=None,
               status=None):
@@ -1141,31 +869,20 @@ class Planner:
         the rings as they stand, meas is a ring with the same addressing).  count (B, 2) int64 = (calls, recorded) and total (B, 2)
         = (total_com, total_feet) are the accumulators as they stand (None: zeros).  With params.n_rows = 1 and first_row that is
         one tick of B robots.  Returns new arrays (rows, status, count, total)."""
-        if not self.has_track():
-            raise RuntimeError("this build of the planner library has no track kernel (qtos_track)")
-        nodes = np.ascontiguousarray(nodes, np.float64).reshape(-1, self.n)
-        B = nodes.shape[0]
-        t0 = np.ascontiguousarray(np.broadcast_to(np.asarray(t0, np.float64), (B,)))
-        first, per = _i32(first_row, B), _i32(n_rows, B)
+        self._need("qtos_track", "track kernel")
+        nodes, B = self._nodes(nodes)
+        t0 = _bcast(t0, B)
+        first, per = _bcast(first_row, B, np.int32), _bcast(n_rows, B, np.int32)
         rows = _rows(params)
-        mcols = 19 if params.flags & TRACK_QUAT else 18
-        meas = np.ascontiguousarray(meas, np.float64)
-        if meas.shape != (B, max(rows, 0), mcols):
-            raise ValueError("meas is (B, %d, %d)" % (rows, mcols))
+        meas = _meas(meas, B, rows, params.flags & TRACK_QUAT)
         cur = _segment(params, B, cursor, out, status)[1]
-        goal = None if goal_x is None else np.ascontiguousarray(np.broadcast_to(np.asarray(goal_x, np.float64), (B,)))
+        goal = _bcast(goal_x, B)
         count = np.zeros((B, 2), np.int64) if count is None else np.array(count, np.int64).reshape(B, 2)
-        total = np.zeros((B, 2)) if total is None else np.array(total, np.float64).reshape(B, 2)
-        out = np.zeros((B, max(rows, 0), TRACK_COLS)) if out is None else np.array(out, np.float64)
-        status = np.zeros((B, max(rows, 0)), np.int32) if status is None else np.array(status, np.int32)
-        if out.shape != (B, rows, TRACK_COLS) or status.shape != (B, rows):
-            raise ValueError("out is (B, %d, %d) and status (B, %d)" % (rows, TRACK_COLS, rows))
+        total = np.zeros((B, 2)) if total is None else _mat(total, (B, 2), copy=True)
+        out, status = _out_status(out, status, B, rows, TRACK_COLS)
         self._chk(self.lib.qtos_track(self.h, B, C.byref(params), _dp(nodes), _dp(t0), _ip(first), _ip(per),
                                       _llp(cur), _dp(meas), _dp(goal), _llp(count), _dp(total), _dp(out), _ip(status)), "track")
         return out, status, count, total
-
-    def has_rollout(self):
-        return hasattr(self.lib, "qtos_rollout")
 
     def rollout(self, nodes, t0, params, first_row=None, n_rows=None, cursor=None, joint=None, mass_scale=None, push=None, state=None,
                 count=None, word=None, meas=None, rows=True, status=None):
@@ -1178,30 +895,22 @@ class Planner:
         `cursor` are the rings as they stand, joint a ring with the same addressing).  meas: (B, rows, 18), or 19 with params'
         quaternion flag (None: zeros); rows: True, an array (B, rows, 20) or False / None for no table.  Returns new arrays
         (meas, rows or None, status, state, count, word)."""
-        if not self.has_rollout():
-            raise RuntimeError("this build of the planner library has no rollout kernel (qtos_rollout)")
-        nodes = np.ascontiguousarray(nodes, np.float64).reshape(-1, self.n)
-        B = nodes.shape[0]
-        t0 = np.ascontiguousarray(np.broadcast_to(np.asarray(t0, np.float64), (B,)))
-        first, per = _i32(first_row, B), _i32(n_rows, B)
+        self._need("qtos_rollout", "rollout kernel")
+        nodes, B = self._nodes(nodes)
+        t0 = _bcast(t0, B)
+        first, per = _bcast(first_row, B, np.int32), _bcast(n_rows, B, np.int32)
         nr, cur = _segment(params, B, cursor)
         nr = max(nr, 0)                                    # (a negative n_rows: the library refuses it)
         mcols = 19 if params.flags & ROLLOUT_QUAT else 18
         joint = None if joint is None else np.ascontiguousarray(joint, np.float64)
         if joint is not None and joint.shape != (B, nr, CSV_COLS):
             raise ValueError("joint is (B, %d, %d)" % (nr, CSV_COLS))
-        ms = None if mass_scale is None else np.ascontiguousarray(np.broadcast_to(np.asarray(mass_scale, np.float64), (B,)))
-        push = None if push is None else np.ascontiguousarray(push, np.float64).reshape(B, 6)
-        state = np.zeros((B, ROLLOUT_STATE)) if state is None else np.array(state, np.float64).reshape(B, ROLLOUT_STATE)
-        count = np.zeros(B, np.int64) if count is None else np.array(np.broadcast_to(np.asarray(count, np.int64), (B,)))
-        word = np.zeros(B, np.int32) if word is None else np.array(np.broadcast_to(np.asarray(word, np.int32), (B,)))
+        ms, push = _bcast(mass_scale, B), _mat(push, (B, 6))
+        state = np.zeros((B, ROLLOUT_STATE)) if state is None else _mat(state, (B, ROLLOUT_STATE), copy=True)
+        count = np.zeros(B, np.int64) if count is None else _bcast(count, B, np.int64, copy=True)
+        word = np.zeros(B, np.int32) if word is None else _bcast(word, B, np.int32, copy=True)
         meas = np.zeros((B, nr, mcols)) if meas is None else np.array(meas, np.float64)
-        if rows is True:
-            rows = np.zeros((B, nr, ROLLOUT_COLS))
-        elif rows is False or rows is None:
-            rows = None
-        else:
-            rows = np.array(rows, np.float64)
+        rows = _table(rows, (B, nr, ROLLOUT_COLS))
         status = np.zeros((B, nr), np.int32) if status is None else np.array(status, np.int32)
         if meas.shape != (B, nr, mcols) or status.shape != (B, nr) or (rows is not None and rows.shape != (B, nr, ROLLOUT_COLS)):
             raise ValueError("meas is (B, %d, %d), rows (B, %d, %d) and status (B, %d)" % (nr, mcols, nr, ROLLOUT_COLS, nr))
@@ -1209,9 +918,6 @@ class Planner:
                                         _dp(ms), _dp(push), _dp(state), _llp(count), _ip(word), _dp(meas), _dp(rows), _ip(status)),
                   "rollout")
         return meas, rows, status, state, count, word
-
-    def has_start_feedback(self):
-        return hasattr(self.lib, "qtos_start_feedback")
 
     def start_feedback(self, nodes, t0, row, meas, params, start, cursor=None, map_id=None, goal_step=None, goal=None, err=None,
                        status=None):
@@ -1222,32 +928,21 @@ class Planner:
         map_id (B): the handle's heightfield of every window (None: map 0).  goal_step and goal (B x 3) go together: goal[:, 0:2]
         = start[:, 0:2] + goal_step[:, 0:2] of the corrected start.  err (B x 18) and status (B) are the arrays as they stand
         (None: zeros): a window without a measurement keeps its entries.  Returns new arrays (start, goal or None, err, status)."""
-        if not self.has_start_feedback():
-            raise RuntimeError("this build of the planner library has no feedback hand-over (qtos_start_feedback)")
-        nodes = np.ascontiguousarray(nodes, np.float64).reshape(-1, self.n)
-        B = nodes.shape[0]
-        t0 = np.ascontiguousarray(np.broadcast_to(np.asarray(t0, np.float64), (B,)))
-        row, mid = _i32(row, B), _i32(map_id, B)
-        rows = _rows(params)
-        mcols = 19 if params.flags & FEEDBACK_QUAT else 18
-        meas = np.ascontiguousarray(meas, np.float64)
-        if meas.shape != (B, max(rows, 0), mcols):
-            raise ValueError("meas is (B, %d, %d)" % (rows, mcols))
+        self._need("qtos_start_feedback", "feedback hand-over")
+        nodes, B = self._nodes(nodes)
+        t0 = _bcast(t0, B)
+        row, mid = _bcast(row, B, np.int32), _bcast(map_id, B, np.int32)
+        meas = _meas(meas, B, _rows(params), params.flags & FEEDBACK_QUAT)
         cur = _segment(params, B, cursor)[1]
-        if (goal_step is None) != (goal is None):
-            raise ValueError("goal_step and goal go together: give both or neither")
-        gs = None if goal_step is None else np.ascontiguousarray(goal_step, np.float64).reshape(B, 3)
-        gl = None if goal is None else np.array(goal, np.float64).reshape(B, 3)
-        start = np.array(start, np.float64).reshape(B, START_DOUBLES)
-        err = np.zeros((B, 18)) if err is None else np.array(err, np.float64).reshape(B, 18)
+        _goal_pair(goal_step, goal)
+        gs, gl = _mat(goal_step, (B, 3)), _mat(goal, (B, 3), copy=True)
+        start = _mat(start, (B, START_DOUBLES), copy=True)
+        err = np.zeros((B, 18)) if err is None else _mat(err, (B, 18), copy=True)
         status = np.zeros(B, np.int32) if status is None else np.array(status, np.int32).reshape(B)
         self._chk(self.lib.qtos_start_feedback(self.h, B, C.byref(params), _dp(nodes), _dp(t0), _ip(row),
                                                _llp(cur), _dp(meas), _ip(mid), _dp(start), _dp(gs), _dp(gl), _dp(err), _ip(status)),
                   "start_feedback")
         return start, gl, err, status
-
-    def has_plan_check(self):
-        return hasattr(self.lib, "qtos_plan_check")
 
     def plan_check(self, nodes, t0, params, map_id=None, first_row=None, n_rows=None, cursor=None, rows=True, summary=None,
                    stream=None):
@@ -1259,43 +954,26 @@ class Planner:
         form.  torch tensors on the device (nodes, t0 and whichever of the others are given; rows / summary: tensors to write
         into, summary as B x 5 x 3 float64 words or None) go through the device form on `stream` (a torch stream; None: the
         current one) and come back as they are, without a synchronisation."""
-        if not self.has_plan_check():
-            raise RuntimeError("this build of the planner library has no plan-check kernel (qtos_plan_check)")
+        self._need("qtos_plan_check", "plan-check kernel")
         from . import plan_check as pc
         if hasattr(nodes, "data_ptr"):
             import torch
             st = torch.cuda.current_stream(nodes.device) if stream is None else stream
             B = nodes.reshape(-1, self.n).shape[0]
-            ptr = lambda a: None if a is None or a is False or a is True else C.c_void_p(a.data_ptr())
-            self._chk(self.lib.qtos_plan_check_device(self.h, B, C.byref(params), ptr(nodes), ptr(t0), ptr(map_id), ptr(first_row),
-                                                      ptr(n_rows), ptr(cursor), ptr(rows), ptr(summary), C.c_void_p(st.cuda_stream)),
+            p = ptr_given
+            self._chk(self.lib.qtos_plan_check_device(self.h, B, C.byref(params), p(nodes), p(t0), p(map_id), p(first_row),
+                                                      p(n_rows), p(cursor), p(rows), p(summary), C.c_void_p(st.cuda_stream)),
                       "plan_check_device")
-            return (rows if ptr(rows) else None), (summary if ptr(summary) else None)
-        nodes = np.ascontiguousarray(nodes, np.float64).reshape(-1, self.n)
-        B = nodes.shape[0]
-        t0 = np.ascontiguousarray(np.broadcast_to(np.asarray(t0, np.float64), (B,)))
-        mid, first, per = _i32(map_id, B), _i32(first_row, B), _i32(n_rows, B)
-        cur = None if cursor is None else np.ascontiguousarray(np.broadcast_to(np.asarray(cursor, np.int64), (B,)))
-        if rows is True:
-            rows = np.zeros((B, int(params.n_rows), CHECK_COLS))
-        elif rows is False or rows is None:
-            rows = None
-        else:
-            rows = np.array(rows, np.float64).reshape(B, int(params.n_rows), CHECK_COLS)
-        if summary is False:
-            summary = None
-            if rows is None:
-                raise ValueError("rows and summary cannot both be left out")
-        elif summary is None:
-            summary = pc.empty_summary(B)
-        else:
-            summary = np.array(summary, pc.SUMMARY).reshape(B, 5)
+            return (rows if p(rows) else None), (summary if p(summary) else None)
+        nodes, B = self._nodes(nodes)
+        t0 = _bcast(t0, B)
+        mid, first, per = _bcast(map_id, B, np.int32), _bcast(first_row, B, np.int32), _bcast(n_rows, B, np.int32)
+        cur = _bcast(cursor, B, np.int64)
+        rows = _table(rows, (B, int(params.n_rows), CHECK_COLS), reshape=True)
+        summary = _summary(summary, rows, pc, B, CHECK_FAMILIES)
         self._chk(self.lib.qtos_plan_check(self.h, B, C.byref(params), _dp(nodes), _dp(t0), _ip(mid), _ip(first), _ip(per), _llp(cur),
-                                           _dp(rows), None if summary is None else summary.ctypes.data_as(C.c_void_p)), "plan_check")
+                                           _dp(rows), _vp(summary)), "plan_check")
         return rows, summary
-
-    def has_force_fit(self):
-        return hasattr(self.lib, "qtos_force_fit")
 
     def force_fit(self, nodes, t0, params, map_id=None, first_row=None, n_rows=None, cursor=None, joint=None, mass_scale=None,
                   rows=True, status=None, summary=None, stream=None):
@@ -1309,51 +987,38 @@ class Planner:
         form.  torch tensors on the device (nodes, t0 and whichever of the others are given; rows, status, summary: tensors to
         write into, summary as B x 4 x 3 float64 words, or None) go through the device form on `stream` (a torch stream; None: the
         current one) and come back as they are, without a synchronisation."""
-        if not self.has_force_fit():
-            raise RuntimeError("this build of the planner library has no force-fit kernel (qtos_force_fit)")
+        self._need("qtos_force_fit", "force-fit kernel")
         from . import force_fit as ff
         if hasattr(nodes, "data_ptr"):
             import torch
             st = torch.cuda.current_stream(nodes.device) if stream is None else stream
             B = nodes.reshape(-1, self.n).shape[0]
-            ptr = lambda a: None if a is None or a is False or a is True else C.c_void_p(a.data_ptr())
-            self._chk(self.lib.qtos_force_fit_device(self.h, B, C.byref(params), ptr(nodes), ptr(t0), ptr(map_id), ptr(first_row),
-                                                     ptr(n_rows), ptr(cursor), ptr(joint), ptr(mass_scale), ptr(rows), ptr(status),
-                                                     ptr(summary), C.c_void_p(st.cuda_stream)), "force_fit_device")
-            return (rows if ptr(rows) else None), (status if ptr(status) else None), (summary if ptr(summary) else None)
-        nodes = np.ascontiguousarray(nodes, np.float64).reshape(-1, self.n)
-        B = nodes.shape[0]
-        t0 = np.ascontiguousarray(np.broadcast_to(np.asarray(t0, np.float64), (B,)))
-        mid, first, per = _i32(map_id, B), _i32(first_row, B), _i32(n_rows, B)
+            p = ptr_given
+            self._chk(self.lib.qtos_force_fit_device(self.h, B, C.byref(params), p(nodes), p(t0), p(map_id), p(first_row),
+                                                     p(n_rows), p(cursor), p(joint), p(mass_scale), p(rows), p(status),
+                                                     p(summary), C.c_void_p(st.cuda_stream)), "force_fit_device")
+            return (rows if p(rows) else None), (status if p(status) else None), (summary if p(summary) else None)
+        nodes, B = self._nodes(nodes)
+        t0 = _bcast(t0, B)
+        mid, first, per = _bcast(map_id, B, np.int32), _bcast(first_row, B, np.int32), _bcast(n_rows, B, np.int32)
         keep = not (rows is False or rows is None)
         nr, cur = _segment(params, B, cursor, *((rows, status) if keep and params.capacity > 0 else ()))
         nr = max(nr, 0)
         joint = None if joint is None else np.ascontiguousarray(joint, np.float64)
         if joint is not None and joint.shape != (B, nr, CSV_COLS):
             raise ValueError("joint is (B, %d, %d)" % (nr, CSV_COLS))
-        ms = None if mass_scale is None else np.ascontiguousarray(np.broadcast_to(np.asarray(mass_scale, np.float64), (B,)))
-        if not keep:
-            rows = status = None
+        ms = _bcast(mass_scale, B)
+        rows = _table(rows, (B, nr, FIT_COLS))
+        if rows is None:
+            status = None
         else:
-            rows = np.zeros((B, nr, FIT_COLS)) if rows is True else np.array(rows, np.float64)
             status = np.zeros((B, nr), np.int32) if status is None else np.array(status, np.int32)
             if rows.shape != (B, nr, FIT_COLS) or status.shape != (B, nr):
                 raise ValueError("rows is (B, %d, %d) and status (B, %d)" % (nr, FIT_COLS, nr))
-        if summary is False:
-            summary = None
-            if rows is None:
-                raise ValueError("rows and summary cannot both be left out")
-        elif summary is None:
-            summary = ff.empty_summary(B)
-        else:
-            summary = np.array(summary, ff.SUMMARY).reshape(B, FIT_FAMILIES)
+        summary = _summary(summary, rows, ff, B, FIT_FAMILIES)
         self._chk(self.lib.qtos_force_fit(self.h, B, C.byref(params), _dp(nodes), _dp(t0), _ip(mid), _ip(first), _ip(per), _llp(cur),
-                                          _dp(joint), _dp(ms), _dp(rows), _ip(status),
-                                          None if summary is None else summary.ctypes.data_as(C.c_void_p)), "force_fit")
+                                          _dp(joint), _dp(ms), _dp(rows), _ip(status), _vp(summary)), "force_fit")
         return rows, status, summary
-
-    def has_path_goal(self):
-        return hasattr(self.lib, "qtos_path_goal")
 
     def path_goal(self, table, clock, params, path_id=None, map_yx=None, map_id=None, offset=None, start=None, done=None):
         """Goals of the windows' next plans from their global paths (qtos_path_goal, host form; the rule:
@@ -1362,8 +1027,7 @@ class Planner:
         cols or rows x cols (None: every height 0) with map_id [B] (None: map 0); offset [B] (None: 0); start [B, 24] (None where
         nothing reads it); done [B] (None: no done bits are kept).  Returns new arrays (goal [B, 3], done [B] int32 or None,
         clock [B])."""
-        if not self.has_path_goal():
-            raise RuntimeError("this build of the planner library has no path-goal kernel (qtos_path_goal)")
+        self._need("qtos_path_goal", "path-goal kernel")
         clock = np.array(clock, np.float64).reshape(-1)
         B = len(clock)
         g = params.copy()
@@ -1376,21 +1040,15 @@ class Planner:
             raise ValueError("not a path table: knots [n_paths, max_pieces + 1], coef [n_paths, 2, 4, max_pieces], n_pieces [n_paths]")
         grids = None
         if map_yx is not None:
-            grids = np.ascontiguousarray(map_yx, np.float64)
-            grids = grids[None] if grids.ndim == 2 else grids
+            grids = _maps(map_yx)
             g.n_maps, g.rows, g.cols = grids.shape
-        pid = None if path_id is None else np.ascontiguousarray(path_id, np.int32).reshape(B)
-        mid = None if map_id is None else np.ascontiguousarray(map_id, np.int32).reshape(B)
-        off = None if offset is None else np.ascontiguousarray(np.broadcast_to(np.asarray(offset, np.float64), (B,)))
-        st = None if start is None else np.ascontiguousarray(start, np.float64).reshape(B, START_DOUBLES)
+        pid, mid, off = _vec(path_id, B), _vec(map_id, B), _bcast(offset, B)
+        st = _mat(start, (B, START_DOUBLES))
         dn = None if done is None else np.array(done, np.int32).reshape(B)
         goal = np.empty((B, 3))
         self._chk(self.lib.qtos_path_goal(self.h, B, C.byref(g), _dp(knots), _dp(coef), _ip(npc), _dp(rg), _ip(pid), _dp(grids), _ip(mid),
                                           _dp(clock), _dp(off), _dp(st), _dp(goal), _ip(dn)), "path_goal")
         return goal, dn, clock
-
-    def has_path_plan(self):
-        return hasattr(self.lib, "qtos_path_plan")
 
     def path_plan(self, bool_map, start, robot_goal, params, map_id=None, done=None, cells=True):
         """The windows' global paths, planned on the device (qtos_path_plan, host form; the rule: global_planner.path_plan).
@@ -1398,11 +1056,9 @@ class Planner:
         [B, 3]; params: a QtosPathPlan (path_plan_params; the maps' sizes are filled in here); done [B] (None: no done bits);
         cells False: the paths' cells are not kept.  Returns the dict of global_planner.path_plan: the path table (knots, coef,
         n_pieces, robot_goal) plus cells (or None), n_cells, status, and done where it was given."""
-        if not self.has_path_plan():
-            raise RuntimeError("this build of the planner library has no path-plan kernel (qtos_path_plan)")
+        self._need("qtos_path_plan", "path-plan kernel")
         g = params.copy()
-        maps = np.ascontiguousarray(bool_map, np.float64)
-        maps = maps[None] if maps.ndim == 2 else maps
+        maps = _maps(bool_map)
         g.n_maps, g.rows, g.cols = maps.shape
         rg = np.ascontiguousarray(robot_goal, np.float64)
         B = rg.shape[0]
@@ -1411,7 +1067,7 @@ class Planner:
         if st.shape[1] != START_DOUBLES:
             st = np.concatenate([st[:, 0:2], np.zeros((B, START_DOUBLES - 2))], axis=1)
         st = np.ascontiguousarray(st)
-        mid = None if map_id is None else np.ascontiguousarray(map_id, np.int32).reshape(B)
+        mid = _vec(map_id, B)
         dn = None if done is None else np.array(done, np.int32).reshape(B)
         mp, mc = max(g.max_pieces, 1), max(g.max_cells, 1)     # (sizes of the arrays only: the library checks the values)
         knots, coef, npc = np.zeros((B, mp + 1)), np.zeros((B, 2, 4, mp)), np.zeros(B, np.int32)
@@ -1424,19 +1080,14 @@ class Planner:
             out["done"] = dn
         return out
 
-    def has_probe(self):
-        return hasattr(self.lib, "qtos_probe")
-
     def probe(self, map_yx, params=None, capacity=None):
         """The probe patches of the maps as solver problems (qtos_probe, host form; the rule: feasibility.probe_table).  map_yx
         n_maps x rows x cols or rows x cols; params: a QtosProbe (probe_params; the maps' sizes are filled in here); capacity: room
         for that many problems (None: a first call with capacity 0 reads their number, a second one fills arrays of that size).
         Returns the dict of feasibility.probe_table -- offsets, slot, patch, start, goal, map_id, the last four with
         min(N, capacity) rows."""
-        if not self.has_probe():
-            raise RuntimeError("this build of the planner library has no probe kernels (qtos_probe)")
-        maps = np.ascontiguousarray(map_yx, np.float64)
-        maps = maps[None] if maps.ndim == 2 else maps
+        self._need("qtos_probe", "probe kernels")
+        maps = _maps(map_yx)
         g = (params or probe_params()).copy()
         g.n_maps, g.rows, g.cols = maps.shape
         offsets = np.zeros(g.n_maps + 1, np.int32)
@@ -1458,14 +1109,13 @@ class Planner:
         """Exit statuses -> boolean maps (qtos_probe_stamp, host form; the rule: feasibility.stamp_table).  shape (rows, cols) or
         (n_maps, rows, cols); offsets, slot, patch as probe() returned them; status [offsets[-1]].  Returns n_maps x rows x cols
         doubles of 0.0 / 1.0."""
-        if not self.has_probe():
-            raise RuntimeError("this build of the planner library has no probe kernels (qtos_probe_stamp)")
+        self._need("qtos_probe_stamp", "probe kernels")
         offsets = np.ascontiguousarray(offsets, np.int32)
         g = (params or probe_params()).copy()
         g.n_maps, (g.rows, g.cols) = len(offsets) - 1, tuple(shape)[-2:]
         slot = np.ascontiguousarray(slot, np.int32)
         patch = None if patch is None else np.ascontiguousarray(patch, np.int32).reshape(-1, 3)     # (not read by the library)
-        status = np.ascontiguousarray(status, np.int32).reshape(-1)
+        status = _vec(status, -1)
         N = int(offsets[-1])
         if slot.size != g.n_maps * g.rows * max(g.cols // 2 - 1, 0) or len(status) < N or (patch is not None and len(patch) < N):
             raise ValueError("slot is n_maps x rows x (cols // 2 - 1); patch (or None) and status hold offsets[-1] entries")
@@ -1473,24 +1123,19 @@ class Planner:
         self._chk(self.lib.qtos_probe_stamp(self.h, C.byref(g), _ip(offsets), _ip(slot), _ip(patch), _ip(status), _dp(out)), "probe_stamp")
         return out
 
-    def has_terrain_env(self):
-        return hasattr(self.lib, "qtos_terrain_env")
-
     def terrain_env(self, base_yx, seed, draws=None, base_id=None, params=None, map_yx=None, height_xy=None):
         """The randomised terrains of the maps (qtos_terrain_env, host form; the rule: heightfield.random_env_table).  base_yx
         n_base x rows x cols or rows x cols; seed [n_maps] (0 .. 2**64 - 1); draws [n_maps] outputs already consumed (None: 0);
         base_id [n_maps] or None (map m reads base m); params: a QtosTerrainEnv (terrain_env_params; the sizes are filled in
         here); map_yx, height_xy: arrays the call writes into (None: zeros) -- a map with a non-zero status keeps what they
         hold.  Returns the dict of random_env_table: map_yx, height_xy, draws, status."""
-        if not self.has_terrain_env():
-            raise RuntimeError("this build of the planner library has no terrain-env kernel (qtos_terrain_env)")
-        base = np.ascontiguousarray(base_yx, np.float64)
-        base = base[None] if base.ndim == 2 else base
+        self._need("qtos_terrain_env", "terrain-env kernel")
+        base = _maps(base_yx)
         seed = np.ascontiguousarray([int(v) for v in np.ravel(seed)], np.uint64)
         g = (params or terrain_env_params()).copy()
         g.n_maps, (g.n_base, g.rows, g.cols) = len(seed), base.shape
         draws = np.zeros(g.n_maps, np.int32) if draws is None else np.array(draws, np.int32).reshape(g.n_maps)
-        bid = None if base_id is None else np.ascontiguousarray(base_id, np.int32).reshape(g.n_maps)
+        bid = _vec(base_id, g.n_maps)
         out_m = np.zeros((g.n_maps, g.rows, g.cols)) if map_yx is None else map_yx
         out_h = np.zeros((g.n_maps, g.cols, g.rows)) if height_xy is None else height_xy
         for a in (out_m, out_h):
@@ -1509,7 +1154,7 @@ class Planner:
         runs next -- `plan`, `probe`, ... on its own stream, a device-form solve on any stream --, so no synchronisation is
         needed round this call; RuntimeError (-5) while a call is open."""
         import torch
-        if not hasattr(self.lib, "qtos_set_heightfields_device"):
+        if not self.has("qtos_set_heightfields_device"):
             raise RuntimeError("this build of the planner library has no qtos_set_heightfields_device")
         t = height_xy[None] if height_xy.dim() == 2 else height_xy
         if not t.is_cuda or t.device.index != self.device or t.dtype != torch.float64 or t.dim() != 3:
@@ -1530,7 +1175,7 @@ class Planner:
             return
         dx = np.ascontiguousarray(dx, np.float64)
         dy = np.ascontiguousarray(dy, np.float64)
-        nodes = np.ascontiguousarray(nodes, np.float64).reshape(len(dy), len(dx), self.n)
+        nodes = _mat(nodes, (len(dy), len(dx), self.n))
         self._chk(self.lib.qtos_set_init_table(self.h, len(dx), _dp(dx), len(dy), _dp(dy), _dp(nodes)), "set_init_table")
         self.init_table = (dx, dy, nodes)
 
@@ -1557,17 +1202,14 @@ class Planner:
     def initial_guess(self, start, goal, map_id=None):
         """The starting point a solve without `warm` uses for these problems (tests: the oracle is started
         from the same point)."""
-        start = np.ascontiguousarray(start, np.float64).reshape(-1, START_DOUBLES)
-        goal = np.ascontiguousarray(goal, np.float64).reshape(-1, 3)
+        start, goal, mid = _mat(start, (-1, START_DOUBLES)), _mat(goal, (-1, 3)), _vec(map_id, -1)
         out = np.empty((start.shape[0], self.n))
-        mid = None if map_id is None else np.ascontiguousarray(map_id, np.int32)
         self._chk(self.lib.qtos_debug_initial_guess(self.h, start.shape[0], _dp(start), _dp(goal), _ip(mid), _dp(out)), "initial_guess")
         return out
 
     def kkt_kernel(self):
-        """Name of the factor + solve kernel the planner selected (the one rocprofv3 lists), e.g. 'k_kkt5<128>'."""
+        """Name of the factor + solve kernel the planner selected (the one rocprofv3 lists), e.g. 'k_kkt3<96, 1>'."""
         buf = C.create_string_buffer(64)
-        self.lib.qtos_kkt_kernel.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
         self._chk(min(self.lib.qtos_kkt_kernel(self.h, buf, 64), 0), "kkt_kernel")
         return buf.value.decode()
 
@@ -1576,7 +1218,7 @@ class Planner:
         nl, it = C.c_int(), C.c_int()
         self._chk(self.lib.qtos_last_timing(self.h, C.byref(k), C.byref(nl), C.byref(t), C.byref(it)), "last_timing")
         out = dict(kkt_seconds=k.value, kkt_launches=nl.value, total_seconds=t.value, iterations=it.value)
-        if hasattr(self.lib, "qtos_last_timing_chord"):
+        if self.has("qtos_last_timing_chord"):
             c, nc = C.c_double(), C.c_int()
             self._chk(self.lib.qtos_last_timing_chord(self.h, C.byref(c), C.byref(nc)), "last_timing_chord")
             out.update(chord_seconds=c.value, chord_launches=nc.value)
@@ -1590,25 +1232,20 @@ class Planner:
 
     # ---- introspection (parity tests) ----
     def debug_eval(self, start, goal, nodes, map_id=None, jac=True):
-        start = np.ascontiguousarray(start, np.float64).reshape(-1, START_DOUBLES)
-        goal = np.ascontiguousarray(goal, np.float64).reshape(-1, 3)
-        nodes = np.ascontiguousarray(nodes, np.float64).reshape(-1, self.n)
+        start, goal, mid = _mat(start, (-1, START_DOUBLES)), _mat(goal, (-1, 3)), _vec(map_id, -1)
+        nodes = self._nodes(nodes)[0]
         B = start.shape[0]
         g = np.empty((B, self.m))
         J = np.empty((B, self.m, self.n)) if jac else None
-        mid = None if map_id is None else np.ascontiguousarray(map_id, np.int32)
         self._chk(self.lib.qtos_debug_eval(self.h, B, _dp(start), _dp(goal), _ip(mid), _dp(nodes), _dp(g), _dp(J)), "debug_eval")
         return g, J
 
     def debug_newton(self, start, goal, nodes, sig, w, map_id=None):
-        start = np.ascontiguousarray(start, np.float64).reshape(-1, START_DOUBLES)
-        goal = np.ascontiguousarray(goal, np.float64).reshape(-1, 3)
-        nodes = np.ascontiguousarray(nodes, np.float64).reshape(-1, self.n)
+        start, goal, mid = _mat(start, (-1, START_DOUBLES)), _mat(goal, (-1, 3)), _vec(map_id, -1)
+        nodes = self._nodes(nodes)[0]
         B = start.shape[0]
-        sig = np.ascontiguousarray(sig, np.float64).reshape(B, self.m)
-        w = np.ascontiguousarray(w, np.float64).reshape(B, self.m)
+        sig, w = _mat(sig, (B, self.m)), _mat(w, (B, self.m))
         dx = np.empty((B, self.n))
-        mid = None if map_id is None else np.ascontiguousarray(map_id, np.int32)
         self._chk(self.lib.qtos_debug_newton(self.h, B, _dp(start), _dp(goal), _ip(mid), _dp(nodes), _dp(sig), _dp(w), _dp(dx)), "debug_newton")
         return dx
 
@@ -1621,9 +1258,9 @@ class Planner:
     def project(self, nodes):
         """What given nodes become when a solve starts from them (reduce_base: their projection onto the space of the base's
         B-spline coefficients; otherwise a copy)."""
-        nodes = np.ascontiguousarray(nodes, np.float64).reshape(-1, self.n)
+        nodes, B = self._nodes(nodes)
         out = np.empty_like(nodes)
-        self._chk(self.lib.qtos_project_nodes(self.h, nodes.shape[0], _dp(nodes), _dp(out)), "project_nodes")
+        self._chk(self.lib.qtos_project_nodes(self.h, B, _dp(nodes), _dp(out)), "project_nodes")
         return out
 
     def debug_residual(self, B, refine=False):

@@ -240,18 +240,12 @@ def feasibility_maps_device(planner, maps_yx, multi_map_shift=1, scale=1, stream
     import torch
 
     from . import capi
-    P = planner
-    if not P.has_probe():
-        raise RuntimeError("this build of the planner library has no probe kernels (qtos_probe_device)")
+    P, ptr, chk = planner, capi.ptr, planner._chk
+    P._need("qtos_probe_device", "probe kernels")
     dev = torch.device("cuda", P.device)
     stream = torch.cuda.current_stream(dev) if stream is None else stream
     sp = C.c_void_p(stream.cuda_stream)
     f64, i32 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.int32, device=dev)
-    ptr = lambda t: t.data_ptr()
-
-    def chk(rc, what):
-        if rc != 0:
-            raise RuntimeError("%s failed (%d): %s" % (what, rc, P.lib.qtos_last_error(P.h).decode()))
     with torch.cuda.stream(stream):
         maps = torch.as_tensor(maps_yx, **f64)
         maps = (maps[None] if maps.dim() == 2 else maps).contiguous()
@@ -300,9 +294,8 @@ def random_env_device(planner, base_yx, seeds, base_id=None, draws=None, n_shift
     import torch
 
     from . import capi
-    P = planner
-    if not P.has_terrain_env():
-        raise RuntimeError("this build of the planner library has no terrain-env kernel (qtos_terrain_env_device)")
+    P, ptr = planner, capi.ptr
+    P._need("qtos_terrain_env_device", "terrain-env kernel")
     dev = torch.device("cuda", P.device)
     stream = torch.cuda.current_stream(dev) if stream is None else stream
     sp = C.c_void_p(stream.cuda_stream)
@@ -322,10 +315,7 @@ def random_env_device(planner, base_yx, seeds, base_id=None, draws=None, n_shift
         g = capi.terrain_env_params((n_base, rows, cols), n_maps, n_shift, n_height, climb, delta)
         map_yx, height_xy = torch.zeros((n_maps, rows, cols), **f64), torch.zeros((n_maps, cols, rows), **f64)
         status = torch.zeros((n_maps,), **i32)
-        rc = P.lib.qtos_terrain_env_device(P.h, C.byref(g), base.data_ptr(), None if bid is None else bid.data_ptr(), seed.data_ptr(),
-                                           None if draws is None else draws.data_ptr(), map_yx.data_ptr(), height_xy.data_ptr(),
-                                           status.data_ptr(), sp)
-        if rc != 0:
-            raise RuntimeError("qtos_terrain_env_device failed (%d): %s" % (rc, P.lib.qtos_last_error(P.h).decode()))
+        P._chk(P.lib.qtos_terrain_env_device(P.h, C.byref(g), ptr(base), ptr(bid), ptr(seed), ptr(draws), ptr(map_yx), ptr(height_xy),
+                                             ptr(status), sp), "qtos_terrain_env_device")
         P.set_heightfields_device(height_xy, 2.0 / rows if cell is None else cell, stream=stream)
     return map_yx, status

@@ -27,9 +27,12 @@ than the new schedule, and measured on the randomized heightfields (scratch/shif
 from towr's straight-line guess, whatever the slack push and whichever variable sets are shifted.  A batch waits
 for its slowest window, so the loops start cold, like the reference's solver.
 """
+import ctypes as C
+
 import numpy as np
 
-from . import flags
+from . import capi, flags
+from .capi import ptr
 from .stitcher import Stitcher, row_state
 
 
@@ -280,19 +283,18 @@ class ShiftedWindows:
         self.advance, self.hz = float(advance), 1000.0
         self.n_search = int(round(search * self.hz))
         if handover is None:
-            handover = "kernel" if hasattr(planner.lib, "qtos_handover_device") else "rows"
+            handover = "kernel" if planner.has("qtos_handover_device") else "rows"
         if handover not in ("kernel", "rows") or contact not in ("force", "heights"):
             raise ValueError("handover is 'kernel' or 'rows', contact 'force' or 'heights'")
         if contact == "heights" and handover != "kernel":
             raise ValueError("contact='heights' needs handover='kernel'")
-        if handover == "kernel" and not hasattr(planner.lib, "qtos_handover_device"):
-            raise RuntimeError("this build of the planner library has no hand-over kernel (qtos_handover_device)")
+        if handover == "kernel":
+            planner._need("qtos_handover_device", "hand-over kernel")
         self.handover, self.contact = handover, contact
         k0 = int(round(advance * self.hz))
         if handover == "rows":
             self.rows = torch.empty((B, k0 + self.n_search + 1, 37), **f64)
         else:
-            from . import capi
             # (the row counts are rounded here, once: the kernel gets times that round to exactly these rows)
             self._hand = capi.handover_params(k0 / self.hz, self.n_search / self.hz, self.hz, contact, height_set, False, x_range)
             self.row = torch.zeros((B,), dtype=torch.int32, device=dev)      # hand-over row of the last replan
@@ -300,11 +302,9 @@ class ShiftedWindows:
         self.offset = torch.zeros((B,), **f64)
         self.traj = None
         if trajectory is not None:
-            from . import capi
             if stitch not in capi.STITCH_MODES:
                 raise ValueError("stitch is 'clean' or 'reference'")
-            if not hasattr(planner.lib, "qtos_stitch_device"):
-                raise RuntimeError("this build of the planner library has no stitch kernel (qtos_stitch_device)")
+            planner._need("qtos_stitch_device", "stitch kernel")
             self._stitch = capi.stitch_params(int(trajectory), stitch, 0, self.hz, True)
             self.traj = torch.zeros((B, int(trajectory), 37), **f64)
             self.cursor = torch.zeros((B,), dtype=torch.int64, device=dev)
@@ -312,21 +312,17 @@ class ShiftedWindows:
                 self.row = torch.zeros((B,), dtype=torch.int32, device=dev)
         self.joint_traj = None
         if joints is not None:
-            from . import capi
             if self.traj is None:
                 raise ValueError("joints needs a trajectory ring (trajectory=N)")
-            if not hasattr(planner.lib, "qtos_joint_rows_device"):
-                raise RuntimeError("this build of the planner library has no joint-rows kernel (qtos_joint_rows_device)")
+            planner._need("qtos_joint_rows_device", "joint-rows kernel")
             self._joint = capi.joint_params(hz=self.hz, first_row=int(self._stitch.first_row), capacity=int(trajectory), **dict(joints))
             self.joint_traj = torch.zeros((B, int(trajectory), 37), **f64)
             self.joint_status = torch.zeros((B, int(trajectory)), dtype=torch.int32, device=dev)
         self.track_traj = None
         if track is not None:
-            from . import capi
             if self.traj is None:
                 raise ValueError("track needs a trajectory ring (trajectory=N)")
-            if not hasattr(planner.lib, "qtos_track_device"):
-                raise RuntimeError("this build of the planner library has no track kernel (qtos_track_device)")
+            planner._need("qtos_track_device", "track kernel")
             track = dict(track)
             goal_x, self._track_fill = track.pop("goal_x", None), track.pop("fill", None)
             self._track = capi.track_params(hz=self.hz, first_row=int(self._stitch.first_row), capacity=int(trajectory), **track)
@@ -340,11 +336,9 @@ class ShiftedWindows:
                 self.track_goal_x = torch.as_tensor(np.broadcast_to(np.asarray(goal_x, np.float64), (B,)).copy(), **f64)
         self._rollout = None
         if rollout is not None:
-            from . import capi
             if self.track_traj is None:
                 raise ValueError("rollout needs the measured ring of track (track=dict(...)), which it fills")
-            if not hasattr(planner.lib, "qtos_rollout_device"):
-                raise RuntimeError("this build of the planner library has no rollout kernel (qtos_rollout_device)")
+            planner._need("qtos_rollout_device", "rollout kernel")
             kw = dict(rollout)
             scale, push, keep = kw.pop("mass_scale", None), kw.pop("push", None), kw.pop("rows", False)
             kw.setdefault("cfg", getattr(planner, "cfg", None))
@@ -359,11 +353,9 @@ class ShiftedWindows:
             self._rollout_scale, self._rollout_push = up(scale, (B,)), up(push, (B, 6))
         self._feedback = None
         if feedback is not None:
-            from . import capi
             if self.track_traj is None:
                 raise ValueError("feedback needs the measured ring of track (track=dict(...))")
-            if not hasattr(planner.lib, "qtos_start_feedback_device"):
-                raise RuntimeError("this build of the planner library has no feedback hand-over (qtos_start_feedback_device)")
+            planner._need("qtos_start_feedback_device", "feedback hand-over")
             kw = dict(feedback)
             kw.setdefault("cfg", getattr(planner, "cfg", None))
             t = self._track
@@ -373,11 +365,10 @@ class ShiftedWindows:
             self.feedback_err = torch.zeros((B, 18), **f64)
         self._check = None
         if check is not None:
-            from . import capi, plan_check
+            from . import plan_check
             if self.traj is None:
                 raise ValueError("check needs a trajectory ring (trajectory=N)")
-            if not hasattr(planner.lib, "qtos_plan_check_device"):
-                raise RuntimeError("this build of the planner library has no plan-check kernel (qtos_plan_check_device)")
+            planner._need("qtos_plan_check_device", "plan-check kernel")
             # the stitch's rows: its first row, its clamp of the count (the ring's capacity), its clock
             self._check = check.copy()
             self._check.hz, self._check.first_row, self._check.n_rows = self.hz, int(self._stitch.first_row), int(trajectory)
@@ -385,11 +376,10 @@ class ShiftedWindows:
             self.check_summary = torch.from_numpy(plan_check.empty_summary(B).view(np.float64).reshape(B, 5, 3).copy()).to(dev)
         self._fit = None
         if fit is not None:
-            from . import capi, force_fit
+            from . import force_fit
             if self.traj is None:
                 raise ValueError("fit needs a trajectory ring (trajectory=N)")
-            if not hasattr(planner.lib, "qtos_force_fit_device"):
-                raise RuntimeError("this build of the planner library has no force-fit kernel (qtos_force_fit_device)")
+            planner._need("qtos_force_fit_device", "force-fit kernel")
             scale = None
             if isinstance(fit, capi.QtosForceFit):
                 self._fit = fit.copy()
@@ -416,16 +406,10 @@ class ShiftedWindows:
         # other sets' streams on this runtime -- four sets took 28 ms per replan instead of 17.)
         torch.cuda.current_stream(dev).synchronize()
 
-    def _call(self, rc, what):
-        if rc != 0:
-            raise RuntimeError("%s failed: %d %s" % (what, rc, self.P.lib.qtos_last_error(self.P.h)))
-
     def _init_path(self, path, path_base, path_hold, advance):
         """Upload the path table and the height grids (once) and fix the parameters of the path-goal calls."""
-        from . import capi
         torch, dev, B = self.torch, self.dev, self.B
-        if not hasattr(self.P.lib, "qtos_path_goal_device"):
-            raise RuntimeError("this build of the planner library has no path-goal kernel (qtos_path_goal_device)")
+        self.P._need("qtos_path_goal_device", "path-goal kernel")
         if path_base not in capi.PATH_BASES:
             raise ValueError("path_base is 'spine' or 'state'")
         f64 = dict(dtype=torch.float64, device=dev)
@@ -461,17 +445,14 @@ class ShiftedWindows:
         self.clock = torch.zeros((B,), **f64)
         self.done = torch.zeros((B,), **i32)
         if plan is not None:
-            import ctypes as C
             # (on the caller's current stream, as the uploads above: __init__ ends with a wait for it)
             self._path_plan(C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
 
     def _init_path_plan(self, path, plan):
         """The buffers and parameters of the device path planner (k_path_plan): the table k_path_goal reads is written on the
         device, one path per window.  Returns what stands for the table where only its sizes are read."""
-        from . import capi
         torch, dev, B = self.torch, self.dev, self.B
-        if not hasattr(self.P.lib, "qtos_path_plan_device"):
-            raise RuntimeError("this build of the planner library has no path-plan kernel (qtos_path_plan_device)")
+        self.P._need("qtos_path_plan_device", "path-plan kernel")
         f64 = dict(dtype=torch.float64, device=dev)
         i32 = dict(dtype=torch.int32, device=dev)
         maps = np.asarray(plan["bool_map"], np.float64)
@@ -498,12 +479,10 @@ class ShiftedWindows:
 
     def _path_plan(self, sp):
         """Queue k_path_plan: every window's path from self.start[:, 0:2] to its robot goal, into the table k_path_goal reads."""
-        import ctypes as C
-        ptr = lambda t: None if t is None else t.data_ptr()
-        self._call(self.P.lib.qtos_path_plan_device(self.P.h, self.B, C.byref(self._path_plan_params), ptr(self._plan_maps),
-                                                    ptr(self._plan_map_id), ptr(self.start), ptr(self._path_rg), ptr(self._path_knots),
-                                                    ptr(self._path_coef), ptr(self._path_n), ptr(self.path_cells), ptr(self.path_n_cells),
-                                                    ptr(self.path_status), ptr(self.done), sp), "qtos_path_plan_device")
+        self.P._chk(self.P.lib.qtos_path_plan_device(self.P.h, self.B, C.byref(self._path_plan_params), ptr(self._plan_maps),
+                                                     ptr(self._plan_map_id), ptr(self.start), ptr(self._path_rg), ptr(self._path_knots),
+                                                     ptr(self._path_coef), ptr(self._path_n), ptr(self.path_cells), ptr(self.path_n_cells),
+                                                     ptr(self.path_status), ptr(self.done), sp), "qtos_path_plan_device")
 
     def repath(self, robot_goal=None, bool_map=None):
         """Plan every window's path anew from where it stands, self.start[:, 0:2], on the set's stream (PATH_Solver.solve,
@@ -513,7 +492,6 @@ class ShiftedWindows:
         result, say): where that is not the set's stream, the host waits for it once, and the caller may drop the tensor as soon
         as repath() returns.  The windows' clock starts again at 0 and their done bits are cleared (a window without a path gets
         bit 2 back).  Refused while a replan is pending."""
-        import ctypes as C
         torch = self.torch
         if self.path is None or self._path_plan_params is None:
             raise RuntimeError("repath() needs the device path planner (path=dict(plan=...))")
@@ -553,20 +531,17 @@ class ShiftedWindows:
 
     def _path_goal(self, params, offset, sp):
         """Queue k_path_goal: the goals of the plans about to be asked for, from self.start (and the hand-over's offset)."""
-        import ctypes as C
-        ptr = lambda t: None if t is None else t.data_ptr()
-        self._call(self.P.lib.qtos_path_goal_device(self.P.h, self.B, C.byref(params), ptr(self._path_knots), ptr(self._path_coef),
-                                                    ptr(self._path_n), ptr(self._path_rg), ptr(self.path_id), ptr(self._path_grids),
-                                                    ptr(self.path_map_id), ptr(self.clock), ptr(offset), ptr(self.start), ptr(self.goal),
-                                                    ptr(self.done), sp), "qtos_path_goal_device")
+        self.P._chk(self.P.lib.qtos_path_goal_device(self.P.h, self.B, C.byref(params), ptr(self._path_knots), ptr(self._path_coef),
+                                                     ptr(self._path_n), ptr(self._path_rg), ptr(self.path_id), ptr(self._path_grids),
+                                                     ptr(self.path_map_id), ptr(self.clock), ptr(offset), ptr(self.start), ptr(self.goal),
+                                                     ptr(self.done), sp), "qtos_path_goal_device")
 
     def _joint_rows(self, params, n_rows, sp):
         """Queue k_joint_rows in front of a stitch: the joint rows of the segment that stitch appends, to the same ring rows (the
         kernel reads the cursor and the clock the stitch behind it moves on)."""
-        import ctypes as C
-        self._call(self.P.lib.qtos_joint_rows_device(self.P.h, self.B, C.byref(params), self.nodes.data_ptr(), self.t0.data_ptr(), None,
-                                                     n_rows, self.cursor.data_ptr(), None, None, self.joint_traj.data_ptr(),
-                                                     self.joint_status.data_ptr(), sp), "qtos_joint_rows_device")
+        self.P._chk(self.P.lib.qtos_joint_rows_device(self.P.h, self.B, C.byref(params), self.nodes.data_ptr(), self.t0.data_ptr(), None,
+                                                      n_rows, self.cursor.data_ptr(), None, None, self.joint_traj.data_ptr(),
+                                                      self.joint_status.data_ptr(), sp), "qtos_joint_rows_device")
 
     def joint_rows(self, b):
         """Window b's newest min(cursor, trajectory) joint rows in time order and their status words, as numpy (the stream is
@@ -581,14 +556,13 @@ class ShiftedWindows:
     def _track_rows(self, params, n_rows, sp):
         """Queue k_track in front of a stitch (behind the joint rows): the track rows of the segment that stitch appends, from the
         measured ring's rows of that segment, to the same ring rows."""
-        import ctypes as C
         if self._track_fill is not None:
             self._track_fill(self)
-        self._call(self.P.lib.qtos_track_device(self.P.h, self.B, C.byref(params), self.nodes.data_ptr(), self.t0.data_ptr(), None, n_rows,
-                                                self.cursor.data_ptr(), self.meas_traj.data_ptr(),
-                                                None if self.track_goal_x is None else self.track_goal_x.data_ptr(),
-                                                self.track_count.data_ptr(), self.track_total.data_ptr(), self.track_traj.data_ptr(),
-                                                self.track_status.data_ptr(), sp), "qtos_track_device")
+        self.P._chk(self.P.lib.qtos_track_device(self.P.h, self.B, C.byref(params), self.nodes.data_ptr(), self.t0.data_ptr(), None, n_rows,
+                                                 self.cursor.data_ptr(), self.meas_traj.data_ptr(),
+                                                 ptr(self.track_goal_x),
+                                                 self.track_count.data_ptr(), self.track_total.data_ptr(), self.track_traj.data_ptr(),
+                                                 self.track_status.data_ptr(), sp), "qtos_track_device")
 
     def _rollout_rows(self, params, n_rows, sp):
         """Queue k_rollout in front of a stitch, behind the joint rows and in front of the track call: the bodies go on from the
@@ -596,13 +570,11 @@ class ShiftedWindows:
         ring's rows of the segment (the joint columns from the joint ring where ``joints`` is on).  A window's first call with
         rows sets its state from the plan's row: ``rollout_word`` starts as QTOS_ROLLOUT_PENDING, which the kernel spends per
         window, so a window whose hand-over row is 0 at the set's first replan is set on its plan by a later one."""
-        import ctypes as C
-        ptr = lambda t: None if t is None else t.data_ptr()
-        self._call(self.P.lib.qtos_rollout_device(self.P.h, self.B, C.byref(params), self.nodes.data_ptr(), self.t0.data_ptr(), None, n_rows,
-                                                  self.cursor.data_ptr(), ptr(self.joint_traj), ptr(self._rollout_scale),
-                                                  ptr(self._rollout_push), self.rollout_state.data_ptr(), self.rollout_count.data_ptr(),
-                                                  self.rollout_word.data_ptr(), self.meas_traj.data_ptr(), ptr(self.rollout_traj),
-                                                  self.rollout_status.data_ptr(), sp), "qtos_rollout_device")
+        self.P._chk(self.P.lib.qtos_rollout_device(self.P.h, self.B, C.byref(params), self.nodes.data_ptr(), self.t0.data_ptr(), None, n_rows,
+                                                   self.cursor.data_ptr(), ptr(self.joint_traj), ptr(self._rollout_scale),
+                                                   ptr(self._rollout_push), self.rollout_state.data_ptr(), self.rollout_count.data_ptr(),
+                                                   self.rollout_word.data_ptr(), self.meas_traj.data_ptr(), ptr(self.rollout_traj),
+                                                   self.rollout_status.data_ptr(), sp), "qtos_rollout_device")
 
     def rollout_rows(self, b):
         """Window b's newest min(cursor, trajectory) rollout rows in time order (None without ``rows=True``) and their status
@@ -618,34 +590,30 @@ class ShiftedWindows:
     def _start_feedback(self, sp):
         """Queue k_start_feedback behind the track call and in front of the stitch: self.start (and, without a path, self.goal)
         from the measured ring's row of the hand-over (the kernel reads the cursor and the clock the stitch behind it moves on)."""
-        import ctypes as C
         moves = self.path is None
-        self._call(self.P.lib.qtos_start_feedback_device(self.P.h, self.B, C.byref(self._feedback), self.nodes.data_ptr(), self.t0.data_ptr(),
-                                                         self.row.data_ptr(), self.cursor.data_ptr(), self.meas_traj.data_ptr(),
-                                                         None if self.map_id is None else self.map_id.data_ptr(), self.start.data_ptr(),
-                                                         self.goal_step.data_ptr() if moves else None,
-                                                         self.goal.data_ptr() if moves else None, self.feedback_err.data_ptr(),
-                                                         self.feedback_status.data_ptr(), sp), "qtos_start_feedback_device")
+        self.P._chk(self.P.lib.qtos_start_feedback_device(self.P.h, self.B, C.byref(self._feedback), self.nodes.data_ptr(), self.t0.data_ptr(),
+                                                          self.row.data_ptr(), self.cursor.data_ptr(), self.meas_traj.data_ptr(),
+                                                          ptr(self.map_id), self.start.data_ptr(),
+                                                          self.goal_step.data_ptr() if moves else None,
+                                                          self.goal.data_ptr() if moves else None, self.feedback_err.data_ptr(),
+                                                          self.feedback_status.data_ptr(), sp), "qtos_start_feedback_device")
 
     def _plan_check(self, params, n_rows, sp):
         """Queue k_plan_check in front of a stitch: the rows that stitch appends, merged into the windows' records (the kernel
         reads the cursor and the clock the stitch behind it moves on; no table is written)."""
-        import ctypes as C
-        self._call(self.P.lib.qtos_plan_check_device(self.P.h, self.B, C.byref(params), self.nodes.data_ptr(), self.t0.data_ptr(),
-                                                     None if self.map_id is None else self.map_id.data_ptr(), None, n_rows,
-                                                     self.cursor.data_ptr(), None, self.check_summary.data_ptr(), sp),
-                   "qtos_plan_check_device")
+        self.P._chk(self.P.lib.qtos_plan_check_device(self.P.h, self.B, C.byref(params), self.nodes.data_ptr(), self.t0.data_ptr(),
+                                                      ptr(self.map_id), None, n_rows,
+                                                      self.cursor.data_ptr(), None, self.check_summary.data_ptr(), sp),
+                    "qtos_plan_check_device")
 
     def _force_fit(self, params, n_rows, sp):
         """Queue k_force_fit in front of a stitch, behind the joint rows: the fit rows of the segment that stitch appends, to the
         same ring rows, with the joint ring's angles where ``joints`` is on, merged into the windows' records (the kernel reads the
         cursor and the clock the stitch behind it moves on)."""
-        import ctypes as C
-        ptr = lambda t: None if t is None else t.data_ptr()
-        self._call(self.P.lib.qtos_force_fit_device(self.P.h, self.B, C.byref(params), self.nodes.data_ptr(), self.t0.data_ptr(),
-                                                    ptr(self.map_id), None, n_rows, self.cursor.data_ptr(), ptr(self.joint_traj),
-                                                    ptr(self._fit_scale), self.fit_traj.data_ptr(), self.fit_status.data_ptr(),
-                                                    self.fit_summary.data_ptr(), sp), "qtos_force_fit_device")
+        self.P._chk(self.P.lib.qtos_force_fit_device(self.P.h, self.B, C.byref(params), self.nodes.data_ptr(), self.t0.data_ptr(),
+                                                     ptr(self.map_id), None, n_rows, self.cursor.data_ptr(), ptr(self.joint_traj),
+                                                     ptr(self._fit_scale), self.fit_traj.data_ptr(), self.fit_status.data_ptr(),
+                                                     self.fit_summary.data_ptr(), sp), "qtos_force_fit_device")
 
     def fit_rows(self, b):
         """Window b's newest min(cursor, trajectory) fit rows in time order and their status words, as numpy (the stream is
@@ -717,8 +685,6 @@ class ShiftedWindows:
     def finish(self):
         """The end of the loop (with ``trajectory``): append the rest of the newest plan, its rows first_row .. the last, to
         every window's ring.  The clock stays: ``t0`` is still the time stamp of that plan's row 0."""
-        import ctypes as C
-        from . import capi
         if self.traj is None:
             raise RuntimeError("finish() needs a trajectory ring (trajectory=...)")
         if getattr(self, "_pending", False) or not self.have_plan:
@@ -749,9 +715,9 @@ class ShiftedWindows:
                 g = self._check.copy()
                 g.first_row, g.n_rows = first, n
                 self._plan_check(g, None, C.c_void_p(self.stream.cuda_stream))
-            self._call(self.P.lib.qtos_stitch_device(self.P.h, self.B, C.byref(s), self.nodes.data_ptr(), None, self.t0.data_ptr(),
-                                                     self.traj.data_ptr(), self.cursor.data_ptr(), C.c_void_p(self.stream.cuda_stream)),
-                       "qtos_stitch_device")
+            self.P._chk(self.P.lib.qtos_stitch_device(self.P.h, self.B, C.byref(s), self.nodes.data_ptr(), None, self.t0.data_ptr(),
+                                                      self.traj.data_ptr(), self.cursor.data_ptr(), C.c_void_p(self.stream.cuda_stream)),
+                        "qtos_stitch_device")
             first += n
 
     def trajectory_rows(self, b):
@@ -764,14 +730,13 @@ class ShiftedWindows:
 
     def _handover_rows(self, sp):
         """The hand-over through the sampled row table (handover="rows"): what _begin did before k_handover."""
-        import ctypes as C
         torch, P, B = self.torch, self.P, self.B
         # hand-over rows: sample the newest plan from `advance` on, take the first row with all feet in contact
         # (force columns 25.. of a foot are non-zero exactly in stance: the reference tests foot heights against
         # the terrain's height set, QTOS/combiner.py:78-92 -- the same rows on these maps)
         n_rows = self.rows.shape[1]
-        self._call(P.lib.qtos_sample_csv_device(P.h, B, self.nodes.data_ptr(), self.t0.data_ptr(), C.c_double(self.hz), n_rows,
-                                                self.rows.data_ptr(), sp), "qtos_sample_csv_device")
+        self.P._chk(P.lib.qtos_sample_csv_device(P.h, B, self.nodes.data_ptr(), self.t0.data_ptr(), C.c_double(self.hz), n_rows,
+                                                 self.rows.data_ptr(), sp), "qtos_sample_csv_device")
         k0 = n_rows - self.n_search - 1
         cand = self.rows[:, k0:, :]
         contact = (cand[:, :, 25:37].reshape(B, -1, 4, 3)[..., 2] > 0).all(dim=2)
@@ -792,7 +757,6 @@ class ShiftedWindows:
         self.goal[:, 0:2] = self.start[:, 0:2] + self.goal_step[:, 0:2]
 
     def _begin(self):
-        import ctypes as C
         torch, P, B = self.torch, self.P, self.B
         sp = C.c_void_p(self.stream.cuda_stream)
         warm_ptr = None
@@ -800,10 +764,10 @@ class ShiftedWindows:
             if self.handover == "kernel":
                 # hand-over: k_handover picks every window's row of its newest plan, evaluates it into start and moves the goal
                 # (with a path: without goal_step, the goal is k_path_goal's)
-                self._call(P.lib.qtos_handover_device(P.h, B, C.byref(self._hand), self.nodes.data_ptr(),
-                                                      None if self.path is not None else self.goal_step.data_ptr(),
-                                                      self.start.data_ptr(), None if self.path is not None else self.goal.data_ptr(),
-                                                      self.offset.data_ptr(), self.row.data_ptr(), sp), "qtos_handover_device")
+                self.P._chk(P.lib.qtos_handover_device(P.h, B, C.byref(self._hand), self.nodes.data_ptr(),
+                                                       None if self.path is not None else self.goal_step.data_ptr(),
+                                                       self.start.data_ptr(), None if self.path is not None else self.goal.data_ptr(),
+                                                       self.offset.data_ptr(), self.row.data_ptr(), sp), "qtos_handover_device")
             else:
                 self._handover_rows(sp)
             if self.path is not None and self._feedback is None:
@@ -826,21 +790,21 @@ class ShiftedWindows:
                     self._force_fit(self._fit, self.row.data_ptr(), sp)
                 if self._check is not None:
                     self._plan_check(self._check, self.row.data_ptr(), sp)
-                self._call(P.lib.qtos_stitch_device(P.h, B, C.byref(self._stitch), self.nodes.data_ptr(), self.row.data_ptr(),
-                                                    self.t0.data_ptr(), self.traj.data_ptr(), self.cursor.data_ptr(), sp),
-                           "qtos_stitch_device")
+                self.P._chk(P.lib.qtos_stitch_device(P.h, B, C.byref(self._stitch), self.nodes.data_ptr(), self.row.data_ptr(),
+                                                     self.t0.data_ptr(), self.traj.data_ptr(), self.cursor.data_ptr(), sp),
+                            "qtos_stitch_device")
             self.nodes, self.prev = self.prev, self.nodes
             if self.warm_mode == "shifted":
-                self._call(P.lib.qtos_shift_warm_device(P.h, B, self.prev.data_ptr(), self.offset.data_ptr(), self.start.data_ptr(),
-                                                        self.goal.data_ptr(), None if self.map_id is None else self.map_id.data_ptr(),
-                                                        self.warm.data_ptr(), sp), "qtos_shift_warm_device")
+                self.P._chk(P.lib.qtos_shift_warm_device(P.h, B, self.prev.data_ptr(), self.offset.data_ptr(), self.start.data_ptr(),
+                                                         self.goal.data_ptr(), ptr(self.map_id),
+                                                         self.warm.data_ptr(), sp), "qtos_shift_warm_device")
                 mix = getattr(self, "_mix", "all")
                 if mix != "all":     # (scratch/shift_exp.py: only part of the shifted plan, the rest from the straight-line guess)
                     guess = torch.empty_like(self.warm)
                     big = torch.full_like(self.offset, 1e9)
-                    self._call(P.lib.qtos_shift_warm_device(P.h, B, self.prev.data_ptr(), big.data_ptr(), self.start.data_ptr(),
-                                                            self.goal.data_ptr(), None if self.map_id is None else self.map_id.data_ptr(),
-                                                            guess.data_ptr(), sp), "qtos_shift_warm_device")
+                    self.P._chk(P.lib.qtos_shift_warm_device(P.h, B, self.prev.data_ptr(), big.data_ptr(), self.start.data_ptr(),
+                                                             self.goal.data_ptr(), ptr(self.map_id),
+                                                             guess.data_ptr(), sp), "qtos_shift_warm_device")
                     nbn = P.dims.n_base_nodes
                     if mix == "cold":
                         self.warm.copy_(guess)
@@ -851,7 +815,7 @@ class ShiftedWindows:
                 warm_ptr = self.warm.data_ptr()
         elif self.path is not None:
             self._path_goal(self.path_params_init, None, sp)
-        self._call(P.lib.qtos_plan_submit(P.h, B, self.start.data_ptr(), self.goal.data_ptr(),
-                                          None if self.map_id is None else self.map_id.data_ptr(), warm_ptr,
-                                          self.nodes.data_ptr(), self.status.data_ptr(), self.iters.data_ptr(),
-                                          self.viol.data_ptr(), sp), "qtos_plan_submit")
+        self.P._chk(P.lib.qtos_plan_submit(P.h, B, self.start.data_ptr(), self.goal.data_ptr(),
+                                           ptr(self.map_id), warm_ptr,
+                                           self.nodes.data_ptr(), self.status.data_ptr(), self.iters.data_ptr(),
+                                           self.viol.data_ptr(), sp), "qtos_plan_submit")
