@@ -304,8 +304,8 @@ def next_kind(cfg, d, it, alpha, viol_before, viol_after, theta_after):
 # ---- the whole iteration ---------------------------------------------------------------------------------------------
 def solve(O, q, cfg, x0=None, max_iter=None, eps_rows=None):
     """The solve of problem q of oracle O with the settings of cfg, from towr's straight-line guess or from given nodes x0
-    (then a warm start).  Returns a dict: states (one per iterate: x, g, s, zl, zu by inequality row, mu, viol, theta, compl,
-    held), events (one per step: kind, rejected, alpha, az, amax, trials, margins, clip rows, mu floor reached), status (0
+    (then a warm start).  Returns a dict: states (one per iterate: x, g, s, zl, zu by inequality row, y by equality row -- of the
+    KKT solve behind the step that led there --, mu, viol, theta, compl, held), events (one per step: kind, rejected, alpha, az, amax, trials, margins, clip rows, mu floor reached), status (0
     converged, 1 otherwise), iters, x (the result: the best iterate of a stalled or jammed solve) and the working set."""
     max_iter = cfg.max_iter if max_iter is None else max_iter
     free, E, I, lo, hi, kind = working_set(O, q)
@@ -324,10 +324,11 @@ def solve(O, q, cfg, x0=None, max_iter=None, eps_rows=None):
     d["best_viol"] = viol if not (viol <= cfg.tol and theta <= cfg.tol) else np.inf
     xbest = x.copy()
     states, events = [], []
+    y = np.zeros(len(E))                          # the equality rows' multipliers of the last KKT solve (none yet: 0)
 
     def snap(held):
         states.append(dict(x=x.copy(), g=g.copy(), s=s.copy(), zl=zl.copy(), zu=zu.copy(), mu=mu, viol=viol, theta=theta,
-                           compl=measures(g[I], s, zl, zu, lo_i, hi_i, g[E])[2], held=held))
+                           compl=measures(g[I], s, zl, zu, lo_i, hi_i, g[E])[2], held=held, y=y.copy()))
     snap(False)
     status, it = 1, 0
     if viol <= cfg.tol and theta <= cfg.tol:
@@ -346,6 +347,7 @@ def solve(O, q, cfg, x0=None, max_iter=None, eps_rows=None):
         hp, _, lu = solve_refined(K, rhs, lu)
         dx = np.zeros(O.n)
         dx[free] = hp[:len(free)].astype(np.float64)
+        y = hp[len(free):].astype(np.float64)     # (a discarded chord step's too: the solve was made)
         ds, dzl, dzu = slack_and_dual_steps(J[I], dx, g[I], s, zl, zu, mu, lo_i, hi_i)
         amax, az = step_lengths(s, ds, zl, zu, dzl, dzu, mu, lo_i, hi_i)
         alpha, trials, log = line_search(O.constraints, x, dx, s, ds, amax, (E, I))

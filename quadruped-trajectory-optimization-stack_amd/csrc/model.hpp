@@ -874,6 +874,14 @@ struct HostModel {
         ColBuilder cb{{}, this};
         ti.cx = cb.add(ti.vx); ti.cy = cb.add(ti.vy); ti.cz = cb.add(ti.vz);
         ti.ncol = (int)cb.cols.size();
+        // Bilinear heightfield: a stance row carries the terrain's slopes on the foothold's x, y.  Keyed at the stance's first
+        // node its multiplier is eliminated in front of the foothold (whose key is the stance's last node) with the pivot
+        // -eps_dual, and comes out of the back substitution as -(g + J dx) / eps_dual: with a slope in J, an error of 1e-8 in the
+        // foothold's step is an error of order 1 in y (the step itself is unharmed, the report's dual infeasibility is not).
+        // The row is keyed behind its foothold there, as the dynamics rows are behind their variables.  Nearest-cell maps and
+        // flat ground keep the node's time: the row's one entry 1 gives y to rounding, and the order of the default system stays.
+        if (P.terrain_mode == 0 && !swing)
+          for (int c : cb.cols) con_time[row] = std::max(con_time[row], var_time[c]);
         bool dup = !swing && node >= 1 && S.idx[node - 1][0] == ti.vx;  // second node of a stance
         if (swing) { con_hi[row] = BIG; row_kind[row] = 2; }
         if (ti.ncol == 0 || dup) row_kind[row] = 0;

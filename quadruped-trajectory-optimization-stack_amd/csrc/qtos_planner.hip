@@ -1349,7 +1349,10 @@ int qtos_debug_duals(QtosPlanner *p, int B, double *s, double *zl, double *zu, d
     HIPCHK(p, hipMemcpy(sol.data(), p->wk.sol, sol.size() * sizeof(double), hipMemcpyDeviceToHost));
     HIPCHK(p, hipMemcpy(it.data(), p->wk.iters, B * sizeof(int), hipMemcpyDeviceToHost));
     std::memset(y, 0, (size_t)B * m * sizeof(double));
-    const int n = p->M.n_vars;
+    // (a multiplier's id in the order is n_sol + row: behind ALL solver variables, the reduced base's coefficients included --
+    //  counted from n_vars a coefficient would be read as a multiplier and the multipliers land n_coef rows too far, the last
+    //  problem's behind the caller's array)
+    const int n = p->M.n_sol;
     for (int b = 0; b < B; ++b)
       if (it[b] > 0)   // (a problem that took no step has no KKT solve of its own)
         for (int q = 0; q < p->S.n_unknowns; ++q)

@@ -17,7 +17,7 @@ from conftest import ROOT, load_gv, start_vector  # noqa: F401  (path set-up)
 
 import linearisation_cases as lc
 import spline_cases as sc
-from oracle import ipm
+from oracle import duals, ipm
 from oracle.oracle import Oracle, oracle_dict
 from qtos_amd import workloads
 from qtos_amd.config import PlannerConfig
@@ -68,6 +68,42 @@ def _far(pairs, mode, dx):
         goal[:, 0] += dx
         return start, goal, t, None
     return f
+
+
+WIDE = 2.5                                  # `groups`: the nominal stance's x and y scaled by this
+
+
+def _wide_stance():
+    return tuple((WIDE * x, WIDE * y, z) for x, y, z in PlannerConfig().nominal_stance)
+
+
+def _groups(cfg):
+    """Three warm starts, one per group of unknowns that attains the dual infeasibility in no other case (searched on the CPU,
+    test_duals_cpu.py holds the outcome): a robot standing still -- the goal 2 cm from the start, the feet on the nominal stance,
+    so that towr's straight-line guess leaves every range-of-motion row its whole band and z_u - z_l all but cancels -- with ONE
+    node moved far enough to violate a few rows, whose z = mu / warm_slack_push then stand alone.  Problem 0: the yaw of base
+    node 8 by 0.2 rad -- both horizontal range-of-motion rows of all four feet at t = 0.8 s, with levers of 0.425 and 0.5 m (the
+    stance 2.5 times as wide as the default: with its levers of 0.17 and 0.2 m a foothold, whose entries are 1, wins); problem
+    1: the height of base node 12 by 0.1 m -- the vertical rows of all four feet; problem 2: the normal force of one stance
+    node of foot 0 to -50 N -- its unilateral row and its four friction rows.  The nodes are put into the reduced system's space
+    (the base spline projected, the swings on their rule), so that both systems start from the same point."""
+    from oracle import projection
+    start, goal = workloads.flat_goals(4, seed=3)
+    start, goal = np.repeat(start[:1], 3, axis=0), np.repeat(goal[:1], 3, axis=0)
+    for e in range(4):
+        start[:, 6 + 3 * e:8 + 3 * e] = start[:, :2] + np.array(cfg.nominal_stance[e][:2])
+    goal[:] = start[:, :3] + np.array([0.02, 0.01, 0.0])
+    O = Oracle(oracle_dict(lc.full(cfg)))
+    warm = []
+    for b in range(3):
+        q = sc.oracle_problem(O, cfg, start[b], goal[b])
+        xl, xh = O.var_bounds(q)
+        x = O.initial_guess(q)
+        v, dv = ((O.L.off_ang + 6 * 8 + 2, 0.2), (O.L.off_lin + 6 * 12 + 2, 0.1), (O.L.off_eef[0] + 52, -50.0))[b]
+        assert xl[v] != xh[v]
+        x[v] += dv
+        warm.append(O.project_swings(projection.project_nodes(x, O.L, (xl != xh).astype(np.int32))))
+    return start, goal, None, np.stack(warm)
 
 
 def _gv1(cfg):
@@ -152,6 +188,14 @@ EXTRA_CASES = {
     # bilinear_1s' problem 0 with its goal 5 m further out: jams under the product's own stall_alpha = 1e-2
     "far_goal": (lambda: PlannerConfig(duration=1.0, dt_base=0.5, dt_dynamic=0.5, dt_range_of_motion=0.5, terrain_mode=0),
                  _far(((1, 0),), 0, 5.0), 8, False, 304, "a jam under the product's settings"),
+    # max_iter = 0 warm starts whose dual infeasibility is attained by a base coefficient or a force node (see _groups): every
+    # other case's is a foothold's or a base-linear unknown's.  Not on the smallest transcription (two_base_polys, 1 s), for two
+    # reasons: the reduced base takes effect from 20 base polynomials on (model.hpp), and the coverage has to hold on the
+    # reduced system too -- hence the reference transcription, 50 polynomials --; and with the default stance's levers (0.17
+    # and 0.2 m) a base-angular unknown collects at most 4 x 0.37 x its B-spline weight (<= 2/3) of the rows' z where a
+    # foothold's entry is 1, so a foothold wins the maximum whatever node is moved -- hence the stance 2.5 times as wide
+    "groups": (lambda: PlannerConfig.reference_compat(nominal_stance=_wide_stance()), _groups, 0, True, 1024,
+               "the dual infeasibility attained by a base-angular, a base-linear and a force unknown"),
 }
 # The cases on which qo_solve is no reference (its Jacobian pattern comes from one evaluation at a perturbed starting point, see
 # bilinear_steps above): on the bilinear trot it parts from the restatement in the FIRST step, by 0.15 to 0.17 in the nodes
@@ -161,9 +205,11 @@ EXTRA_CASES = {
 # events only
 NO_QO = ("bilinear_no_qo", "discard_trot", "bilinear_trot")
 QO_NAMES = [n for n in NAMES if n not in NO_QO]             # the cases on which qo_solve is a reference
+DUAL_NAMES = NAMES + ["groups"]                             # the cases of the dual-infeasibility checks (oracle/duals.py)
 DISCARD_NAMES = [n for n in NAMES if n.startswith("discard_")]
 CLIP_NAMES = [n for n in NAMES if n.startswith("clip_")]
 REDUCED_NAMES = [n for n in NAMES if CASES[n][3]]
+DUAL_REDUCED_NAMES = REDUCED_NAMES + ["groups"]
 # (max_iter: as far as the CPU has run these solves WITHOUT the rules and seen them stay finite -- the GPU test runs them so)
 _JAM = dict(stall_iters=0, stall_alpha=0.9, chord_tol=0.0, max_iter=6)
 # Solves that the stall or the jam rule stops, and one it must not stop: (case, problem, settings on top of the case's product
@@ -239,6 +285,65 @@ def run(name, b, cfg=None):
 def stopped_cfg(entry):
     """The configuration of a STOPPED entry: the case's product configuration on the full system with the entry's settings."""
     return dataclasses.replace(case(entry[0]).product_full, **entry[2])
+
+
+REDUCED_SETTINGS = ((True, False), (False, True), (True, True))      # (reduce_base, reduce_swing), as test_gpu_linearisation.REDUCED
+_bases = {}
+
+
+def setting(c, key):
+    """The case's configuration with (reduce_base, reduce_swing) = key."""
+    return dataclasses.replace(c.cfg, reduce_base=key[0], reduce_swing=key[1])
+
+
+def basis(name, key):
+    """(Z, group per column) of oracle/duals.solver_basis for a case under (reduce_base, reduce_swing) = key, cached.  The free
+    variables are those of the case's first problem: the same for all of them (asserted by the tests through structure())."""
+    if (name, key) not in _bases:
+        c = case(name)
+        free = ipm.working_set(c.O, c.q[0])[0]
+        _bases[(name, key)] = duals.solver_basis(c.O, c.O.L, setting(c, key), free)
+    return _bases[(name, key)]
+
+
+def entry_gate(c):
+    """The gate on a Jacobian entry: the bilinear map's slopes of 2.7 enter its entries."""
+    return lc.GATE_ENTRY_BILINEAR if c.cfg.terrain_mode == 0 else GATE_ENTRY
+
+
+def dual_measure(c, Z, x, y, zl, zu, J=None):
+    """The restatement's dual infeasibility at nodes x with y, z_l, z_u by constraint row, on the case's terrain: (value, attaining
+    column, gate).  The gate, derived like item 3 of test_gpu_steps.py's header and from no measured number: the product forms
+    per unknown p the sum over its Jacobian entries of G_rp v_r, G the entries of J Z as its linearisation wrote them, each off
+    by at most the gate on an entry times the weight |Z| of the node variables behind it -- GATE_ENTRY sum |Z| |v| --, and
+    summed in float64 in another order than here: (terms + 4) u sum |Z| |J| |v| (the four: forming v = y + z_u - z_l and
+    the products' own roundings).  The largest over the columns: the maximum of two lists whose entries differ by at most their
+    bounds differs by at most the largest bound."""
+    val, col, info = duals.dual_infeasibility(c.O.jacobian(x) if J is None else J, Z, y, zl, zu)
+    return val, col, dual_gate(info, entry_gate(c))
+
+
+def dual_gate(info, gate_entry):
+    """The gate of dual_measure from the per-column figures of duals.dual_infeasibility."""
+    return float((gate_entry * info["weight"] + (info["terms"] + 4) * U * info["abs_terms"]).max())
+
+
+def y_gate_of(spread):
+    """The gate on the multipliers y, relative to the dense y's largest entry: GATE_DIRECTION -- dx and y are one solve vector --
+    unless ipm.solve_refined and an unrefined LAPACK solve of the same matrix differ by `spread` > GATE_DIRECTION / GATE_FACTOR;
+    then GATE_FACTOR times that (the rule kkt_cases uses for GATE_CPU_SPREAD)."""
+    return GATE_DIRECTION if spread <= GATE_DIRECTION / lc.GATE_FACTOR else lc.GATE_FACTOR * spread
+
+
+def record_dual(section, name, entry):
+    """Print the figures of a dual-infeasibility check; where the environment variable QTOS_DUAL_ACCURACY names a file, keep them
+    in it as JSON (profiles/dual_accuracy.json is such a file from an MI355X run)."""
+    print("dual accuracy [%s, %s]: %s" % (section, name, json.dumps(entry)))
+    path = os.environ.get("QTOS_DUAL_ACCURACY")
+    if path:
+        data = json.load(open(path)) if os.path.exists(path) else {}
+        data.setdefault(section, {})[name] = entry
+        json.dump(data, open(path, "w"), indent=1, sort_keys=True)
 
 
 def exclusion_margin(n_rows):

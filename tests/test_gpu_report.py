@@ -69,8 +69,54 @@ def test_report_changes_no_plan_and_its_history_is_the_trace(name):
         # times what DESIGN.md section 4 records (max 1.4e-2 / 3.6e-2 / 0.89, medians 1.4e-2 / 2.2e-2 / 2.2e-2)
         bound_max, bound_median = {"trot": (2.2e-2, 2.2e-2), "walk": (5.5e-2, 3.3e-2), "mixed": (1.35, 3.3e-2)}[name]
         assert max(errs) < bound_max and float(np.median(errs)) < bound_median
+        _recompute_inf_du(name, P, c, ter, mid, on)
     finally:
         P.close()
+
+
+def _recompute_inf_du(name, P, c, ter, mid, on):
+    """The report's dual infeasibility of a few problems of a product workload -- the reduced default system: B-spline
+    coefficients and footholds are the unknowns -- against oracle/duals.py: the oracle's Jacobian at the returned nodes on the
+    problem's own map, the basis Z of the unknowns, y, z_l, z_u of Planner.duals, under the gate of test_gpu_steps.py item 8.
+    The problems: the converged one with the largest overall NLP error (the figure DESIGN.md section 4 quotes per workload), and
+    three seeded others, one of them not converged where there is one."""
+    import step_cases as stc
+    from oracle import duals
+    from oracle.oracle import Oracle, oracle_dict
+    nodes, status, iters, viol = on
+    B = nodes.shape[0]
+    reps = [P.report(b)[0] for b in range(B)]
+    s, zl, zu, y = P.duals(B)
+    rk, vf, _ = P.structure()
+    free = np.nonzero(vf != 0)[0]
+    conv = np.nonzero(status == 0)[0]
+    worst = int(conv[np.argmax([reps[b].nlp_error for b in conv])])
+    rng = np.random.default_rng(5)
+    rest = np.setdiff1d(np.arange(B), [worst])
+    bad = np.setdiff1d(np.nonzero(status != 0)[0], [worst])
+    picks = [worst] + ([int(rng.choice(bad))] if len(bad) else [])
+    picks += [int(b) for b in rng.choice(np.setdiff1d(rest, picks), 4 - len(picks), replace=False)]
+    assert c.reduce_base and c.reduce_swing and c.terrain_mode == 1
+    entry, basis = {}, {}
+    for b in picks:
+        m = 0 if mid is None else int(mid[b])
+        if ter is None:
+            O = Oracle(oracle_dict(stc.lc.full(c)))
+        else:
+            O = Oracle(oracle_dict(stc.lc.full(c)), height=ter[0] if np.ndim(ter[0]) == 2 else ter[0][m], hcell=ter[1])
+        if not basis:
+            basis["Z"], basis["groups"] = duals.solver_basis(O, O.L, c, free)      # (the same on every map)
+        assert not y[b][rk != 1].any() and not zl[b][rk != 2].any() and not zu[b][rk != 2].any()
+        val, col, info = duals.dual_infeasibility(O.jacobian(nodes[b]), basis["Z"], y[b], zl[b], zu[b])
+        gate = stc.dual_gate(info, stc.GATE_ENTRY)
+        r = reps[b]
+        entry[str(b)] = dict(status=int(status[b]), iterations=int(iters[b]), map=m, report_inf_du=r.dual_infeasibility, restated_inf_du=val, gate=gate,
+                             achieved_over_bound=abs(r.dual_infeasibility - val) / gate, group=duals.GROUPS[basis["groups"][col]],
+                             constraint_violation=r.constraint_violation, complementarity=r.complementarity, nlp_error=r.nlp_error,
+                             largest_nlp_error_of_the_converged=b == worst)
+    stc.record_dual("workloads", name, entry)
+    for b, e in entry.items():
+        assert abs(e["report_inf_du"] - e["restated_inf_du"]) <= e["gate"], (name, b, e)
 
 
 def test_cold_start_of_the_logged_solve_prints_the_reference_first_row(cfg):

@@ -30,6 +30,29 @@ Per step and problem, from the GPU's OWN state k (so that no error of an earlier
      factorisation's, held to the dense solve at that same iterate
   7. decisions: the kind of every step, the stop, the factorisation / chord-solve totals against next_kind fed the history's
      own numbers (equalities); the hold latch enters 2. through the diagonal
+  8. dual infeasibility: history row k (bit for bit the report's figure of prefix planner k) against oracle/duals.py at the
+     GPU's own state k -- the oracle's Jacobian at the exported nodes, the basis Z of the system's unknowns (B-spline
+     coefficients and footholds on the reduced system; step_cases.basis), y, z_l, z_u of Planner.duals.  Gate: the largest
+     over the unknowns of GATE_ENTRY (bilinear cases: GATE_ENTRY_BILINEAR) x sum |Z| |v| + (terms + 4) u sum |Z| |J| |v|,
+     derived like 3. (step_cases.dual_measure).  Row 0 is k_start's (no solve yet: y = 0, asserted).  A discarded chord step
+     leaves x, s, z where they were, but its row does NOT repeat the preceding row's figure: k_step forms the measure behind
+     every step with the multipliers of the solve it has just made, so row k + 1 carries the discarded chord solve's y at the
+     iterate that stayed.  Held as every other row: Planner.duals of prefix planner k + 1 hands out that y.  The `hold` case
+     runs with the hold weight in the stream's diagonal entries: a diagonal read as a Jacobian entry would show as 1e6
+  9. y: exactly 0 on the rows structure() does not mark as equalities; on the others against the multipliers of the dense
+     solve of 2. at state k - 1 (a discarded chord step: the chord solve's), GATE_DIRECTION of the dense y's largest entry --
+     dx and y are one solve vector -- unless solve_refined and the unrefined LAPACK solve of the same matrices differ by more
+     than GATE_DIRECTION / GATE_FACTOR of it somewhere in the case: then GATE_FACTOR x that spread (step_cases.y_gate_of).
+     The multipliers are the report's only -- no plan depends on them, the dual infeasibility does.  On the bilinear map this
+     check found the multiplier of a stance's terrain row off by 2.7 where the dense solve has 7e-5 and the largest multiplier
+     is 2.3 (bilinear_1s problem 3, row 34: 2.4e5 times the gate; bilinear_steps 53 times, bilinear_no_qo 1.008 times), with dx
+     and every other multiplier at the dense solve's values and the library's own k_residual at 0.60: the row was keyed at the
+     stance's first node and so eliminated in front of its foothold with the pivot -eps_dual, y = -(g + J dx) / eps_dual, where
+     an error of 7e-9 in the foothold's step (the terrain's slope of 2.75 in J) is 2.7.  model.hpp keys such a row behind its
+     foothold on a bilinear map since (test_duals_cpu.py holds the order)
+ 10. ||d||: history column 3 of an accepted step against max |(x_{k+1} - x_k) / alpha| over the free variables, within rb; a
+     discarded step (alpha = 0) leaves nothing to recover it from: counted and reported
+Figures of 8. to 10.: profiles/dual_accuracy.json, with the groups of unknowns that attained the maximum per case.
 
 What state k is: the export of a solve at its LAST iteration.  k_step takes its speculative first trial (spec: the trial
 point evaluated with its Jacobian, lin_done, no gt -> g copy, the hold weight patched into the stream) only where another
@@ -45,9 +68,10 @@ import dataclasses
 
 import numpy as np
 import pytest
+from scipy.linalg import lu_solve
 
 import step_cases as stc
-from oracle import ipm
+from oracle import duals, ipm
 
 pytestmark = pytest.mark.gpu
 U = stc.U
@@ -66,12 +90,12 @@ def _gpu_states(c, cfg):
                 P.set_heightfields(c.terrain[0], c.terrain[1])
             P.set_report(True)
             nodes, status, iters, _ = P.plan(c.start, c.goal, warm=c.warm)
-            s, zl, zu, _ = P.duals(c.B)             # (before any debug_* call: those reuse the workspace)
+            s, zl, zu, y = P.duals(c.B)             # (before any debug_* call: those reuse the workspace)
             reps = [P.report(b) for b in range(c.B)]
             rk, vf, _ = P.structure()
         finally:
             P.close()
-        out.append(dict(x=nodes, status=status, iters=iters, s=s, zl=zl, zu=zu, reps=reps, rk=rk, vf=vf))
+        out.append(dict(x=nodes, status=status, iters=iters, s=s, zl=zl, zu=zu, y=y, reps=reps, rk=rk, vf=vf))
     return out
 
 
@@ -113,7 +137,9 @@ def _check_case(name, reduced):
     G = _gpu_states(c, cfg)
     K, last = c.steps, G[c.steps]
     W = Worst()
-    excluded = decisions = clipped_rows = clipped_tail = discarded = 0
+    excluded = decisions = clipped_rows = clipped_tail = discarded = no_dnorm = 0
+    Z, col_group = stc.basis(name, (True, True) if reduced else (False, False))
+    attained, y_spread, y_checks = set(), 0.0, []
     for b in range(c.B):
         R = stc.run(name, b)                        # (the working set and the bounds; the GPU's own states are what is checked)
         free, E, I, lo, hi = R["free"], R["E"], R["I"], R["lo"][R["I"]], R["hi"][R["I"]]
@@ -140,6 +166,16 @@ def _check_case(name, reduced):
             g = G[min(k, steps)]
             assert not g["s"][b][off_rows].any() and not g["zl"][b][off_rows].any() and not g["zu"][b][off_rows].any()
             return g["x"][b], g["s"][b][I], g["zl"][b][I], g["zu"][b][I]
+
+        def dual_state(k):
+            # 8. the dual infeasibility of history row k against the restatement at the GPU's own state k; 9. y off the equality rows
+            g = G[min(k, steps)]
+            assert g["reps"][b][0].dual_infeasibility == hist[min(k, steps)][INF_DU], (name, b, k)
+            assert not g["y"][b][last["rk"] != 1].any(), (name, b, k, "y off the rows structure() marks as equalities")
+            val, col, gate = stc.dual_measure(c, Z, g["x"][b], g["y"][b], g["zl"][b], g["zu"][b])
+            grp = duals.GROUPS[col_group[col]]
+            attained.add(grp)
+            W.check("inf_du", abs(hist[min(k, steps)][INF_DU] - val), gate, dict(problem=b, step=k, group=grp, restatement=val))
         # 1. the starting state
         x0, s0, zl0, zu0 = state(0)
         g0 = c.O.constraints(x0)
@@ -154,6 +190,8 @@ def _check_case(name, reduced):
         W.check("start_zl", np.abs(zl0 - np.where(hl, mu0 / dl, 0.0)), 4 * U * np.abs(zl0), where(b, 0))
         W.check("start_zu", np.abs(zu0 - np.where(hu, mu0 / du, 0.0)), 4 * U * np.abs(zu0), where(b, 0))
         W.check("start_compl", abs(hist[0][8] - compl), 4 * U * compl, (b, 0))
+        assert not G[0]["y"][b].any()                       # (k_start's row 0: no KKT solve yet)
+        dual_state(0)
         d = ipm.new_decisions()
         d["best_viol"] = hist[0][0]
         Kmat = lu = None
@@ -169,6 +207,7 @@ def _check_case(name, reduced):
             J = c.O.jacobian(x0)
             sig, w = np.zeros(c.O.m), np.zeros(c.O.m)
             sig[I], w[I] = ipm.barrier_terms(g0[I], s0, zl0, zu0, mu, lo, hi)
+            rhs_k = ipm.kkt_rhs(J, g0, free, E, I, w)
             if kind == 0:
                 Kmat = ipm.kkt_matrix(J, free, E, I, sig, np.where(hold_vars & d["held"], cfg.foothold_hold_weight, cfg.delta_x), eps)
                 lu = None
@@ -181,6 +220,9 @@ def _check_case(name, reduced):
                 assert np.array_equal(x1, x0) and np.array_equal(s1, s0) and np.array_equal(zl1, zl0) and np.array_equal(zu1, zu0), (name, b, k)
                 assert h[0] == hist[k][0] and h[1] == hist[k][1], (name, b, k, "viol / theta of an iterate that did not move")
                 discarded += k + 1 < steps
+                # 10. the direction of a discarded step is not applied: nothing to recover its largest entry from
+                no_dnorm += 1
+                hp, _, lu = ipm.solve_refined(Kmat, rhs_k, lu)          # (9.: the chord solve was made, and its y is in the next row)
             else:
                 xd = x1.astype(np.longdouble) - x0
                 sd = s1.astype(np.longdouble) - s0
@@ -188,12 +230,14 @@ def _check_case(name, reduced):
                 rb_x = U * (np.abs(x1) + np.abs(xd).astype(np.float64)) / alpha + U * np.abs(dx)
                 rb_s = U * (np.abs(s1) + np.abs(sd).astype(np.float64)) / alpha + U * np.abs(ds)
                 # 2. the direction
-                hp, _, lu = ipm.solve_refined(Kmat, ipm.kkt_rhs(J, g0, free, E, I, w), lu)
+                hp, _, lu = ipm.solve_refined(Kmat, rhs_k, lu)
                 ref = hp[:len(free)].astype(np.float64)
                 scale = np.abs(ref).max()
                 assert not dx[np.setdiff1d(np.arange(c.O.n), free)].any()
                 W.check("dx_chord" if kind == 1 else "dx", np.abs(dx[free] - ref), stc.GATE_DIRECTION * scale + rb_x[free],
                         lambda i, b=b, k=k: dict(problem=b, step=k, variable=int(free[i])))
+                # 10. the history's ||d||: the largest entry of the direction
+                W.check("dnorm", abs(h[3] - np.abs(dx[free]).max()), rb_x[free].max(), (b, k))
                 # 3. ds
                 JI = J[I]
                 aJ, adx = np.abs(JI), np.abs(dx)
@@ -263,6 +307,13 @@ def _check_case(name, reduced):
             W.check("viol", abs(h[0] - viol), stc.GATE_VALUE, (b, k))
             W.check("theta", abs(h[1] - theta), stc.GATE_VALUE, (b, k))
             W.check("compl", abs(h[8] - compl), 4 * U * compl, (b, k))
+            # 9. y of this step's solve (state k + 1 hands it out) against the dense solve's, on the rows the system keeps as
+            # equalities; the two dense solves' own spread decides the gate once the case is through
+            on = last["rk"][E] == 1
+            y_ref = hp[len(free):].astype(np.float64)[on]
+            y_spread = max(y_spread, float(np.abs(lu_solve(lu, rhs_k)[len(free):][on] - y_ref).max() / np.abs(y_ref).max()))
+            y_checks.append((np.abs(G[k + 1]["y"][b][E[on]] - y_ref), np.abs(y_ref).max(), b, k, E[on]))
+            dual_state(k + 1)
             # 7. the decisions behind this step, from the history's own numbers
             d = ipm.next_kind(cfg, d, k, alpha, hist[k][0], h[0], h[1])
             assert d["stop"] in (None, "converged")           # (the stall rules are off)
@@ -276,10 +327,16 @@ def _check_case(name, reduced):
         else:
             assert rep.status == 1
         assert rep.n_factorizations == kinds.count(0) and rep.n_chord_solves == len(kinds) - kinds.count(0)
+    y_gate = stc.y_gate_of(y_spread)
+    for err, scale, b, k, rows in y_checks:
+        W.check("y", err, y_gate * scale, lambda i, b=b, k=k, rows=rows: dict(problem=b, step=k, row=int(rows[i])))
+    stc.record_dual("gpu_reduced" if reduced else "gpu_full", name,
+                    dict(achieved_over_bound={q: W.ratio.get(q, 0.0) for q in ("inf_du", "y", "dnorm")}, y_cpu_spread=y_spread, y_gate=y_gate,
+                         attaining_groups=sorted(attained), rows_of_discarded_steps_without_dnorm=no_dnorm, problems=c.B, steps=K))
     stc.record("gpu_reduced" if reduced else "gpu_full", name,
                dict(problems=c.B, steps=K, armijo_decisions=decisions, excluded=excluded, achieved_over_bound=W.ratio,
                     clipped_rows_checked_while_mu_moves=clipped_rows, of_them_tail_rows=clipped_tail,
-                    discarded_chord_steps_with_a_step_behind=discarded))
+                    discarded_chord_steps_with_a_step_behind=discarded, dual_infeasibility_attained_by=sorted(attained)))
     assert excluded == 0
     # the case is on the GPU where the restatement's run put it on the CPU (test_the_case_table_sits_on_the_paths_it_names)
     if name in stc.CLIP_NAMES:
@@ -290,12 +347,12 @@ def _check_case(name, reduced):
     assert not W.fails, W.fails[:12]
 
 
-@pytest.mark.parametrize("name", stc.NAMES)
+@pytest.mark.parametrize("name", stc.DUAL_NAMES)
 def test_every_step_of_the_full_system_matches_the_restatement(name):
     _check_case(name, False)
 
 
-@pytest.mark.parametrize("name", stc.REDUCED_NAMES)
+@pytest.mark.parametrize("name", stc.DUAL_REDUCED_NAMES)
 def test_every_step_of_the_reduced_system_matches_the_restatement(name):
     _check_case(name, True)
 
