@@ -301,11 +301,14 @@ static terr terrain_at(const qo_params *p, double x, double y) {
   double fx = (x - p->hx0) / p->hcell, fy = (y - p->hy0) / p->hcell;
   double mx = p->hnx - 1, my = p->hny - 1;
   if (p->terrain_mode == 1) { /* nearest cell: ledges stay flat, steps are jumps */
-    int jx = (int)floor(fx + 0.5), jy = (int)floor(fy + 0.5);
-    if (jx < 0) jx = 0;
-    if (jy < 0) jy = 0;
-    if (jx > p->hnx - 1) jx = p->hnx - 1;
-    if (jy > p->hny - 1) jy = p->hny - 1;
+    /* clamped as doubles, then converted: (int) of a double beyond int is undefined (x86-64 gives INT_MIN: cell 0 for a point
+     * far beyond the LAST border).  In range not a bit changes. */
+    double gx = floor(fx + 0.5), gy = floor(fy + 0.5);
+    if (!(gx > 0)) gx = 0;
+    if (!(gy > 0)) gy = 0;
+    if (gx > mx) gx = mx;
+    if (gy > my) gy = my;
+    int jx = (int)gx, jy = (int)gy;
     t.h = p->height[jx * p->hny + jy];
     return t;
   }

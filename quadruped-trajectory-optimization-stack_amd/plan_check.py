@@ -144,8 +144,9 @@ def terrain_at(terrain, mode, x, y, dtype):
     fx, fy = np.where(bad, dtype(0), fx), np.where(bad, dtype(0), fy)
     nan = np.where(bad, dtype(np.nan), dtype(0))
     if mode == 1:
-        jx = np.clip(np.floor(fx + dtype(0.5)).astype(np.int64), 0, nx - 1)
-        jy = np.clip(np.floor(fy + dtype(0.5)).astype(np.int64), 0, ny - 1)
+        # clipped in floating point, then converted: beyond 2^63 the conversion is not defined (numpy gives the FIRST cell)
+        jx = np.clip(np.floor(fx + dtype(0.5)), 0, nx - 1).astype(np.int64)
+        jy = np.clip(np.floor(fy + dtype(0.5)), 0, ny - 1).astype(np.int64)
         return Hd[jx, jy] + nan, zero + nan, zero + nan
     cx, cy = (fx <= 0) | (fx >= nx - 1), (fy <= 0) | (fy >= ny - 1)
     fx, fy = np.clip(fx, 0, nx - 1), np.clip(fy, 0, ny - 1)
