@@ -651,6 +651,73 @@ int qtos_rollout(QtosPlanner *p, int B, const QtosRollout *s, const double *node
                  const int *n_rows, const long long *cursor, const double *joint, const double *mass_scale, const double *push,
                  double *state, long long *count, int *word, double *meas, double *rows, int *status);
 
+/* Rollout through the feet: qtos_rollout with its feedback wrench delivered by the feet that stand (k_rollout_feet, one workgroup
+ * per window; the rule, with the order of every operation: rollout_feet.py).  qtos_rollout applies F_fb and tau_fb to the body as a
+ * free wrench; a quadruped pushes only through its stance feet, and two point feet supply no moment about the line through them.
+ * Per row, beside qtos_rollout's quantities: p_e and f_e the plan's foot positions and forces (CSV columns 7 .. 18 and 25 .. 36),
+ * the stance flags as qtos_force_fit takes them, n their number, and the fit's load weights with g_e = f_e,z, the VERTICAL
+ * component: w_e = max(n max(g_e, 0) / sum_S max(g, 0), w_min), all 1 where the sum is not > 0 (qtos_force_fit takes g_e along the
+ * terrain normal; the rollout reads no terrain, and the two are equal on flat ground and on nearest-cell terrain).
+ * Per step the lines of qtos_rollout hold but for a and tau:
+ *   rho~ = (tau_fb / arm, F_fb), the clipped PD terms;  l_e = p_e - r with r the STATE's position;  d_e = l_e / arm
+ *   M = sum_S w_e A~_e A~_e^T + damping n I6, A~_e = [skew(d_e); I3];  y = M^-1 rho~ by qtos_force_fit's unpivoted Cholesky (n = 0:
+ *   y = 0);  df_e = w_e (y_ang x d_e + y_lin) for a stance foot, 0 for a swing foot;  f_a,e = ff_scale f_e + df_e
+ *   QTOS_FEET_LIMIT: every STANCE foot's f_a is then limited by comparisons (a NaN stays a NaN): z = max(f_z, 0); f_max > 0: z =
+ *   min(z, f_max); f_x and f_y clipped to +-mu z.  Against the vertical: the terrain normal only on flat and nearest-cell terrain
+ *   F_a = ((f_a,0 + f_a,1) + f_a,2) + f_a,3;  tau_a = sum_e l_e x f_a,e in the same order
+ *   a = (F_a + F_push) / m_s - g e_z;  tau = tau_a + tau_push (the levers are taken from the actual centre of mass)
+ * With all gains 0, ff_scale 1 and no limit df = 0 exactly, and r, v are qtos_rollout's to the bit.
+ * meas, rows, state, count and word are qtos_rollout's (column 19 of rows stays |F_fb|, the DESIRED force of the tick's first
+ * step).  frows has 16 columns, with g_e = f_a,e - ff_scale f_e of the tick's first step:
+ *   0 the time stamp;  1 .. 12 f_a [N];  13 |sum_S g_e - F_fb| [N];  14 |sum_S l_e x g_e - tau_fb| [N m];  15 sqrt(sum_S |g_e|^2) [N]
+ * 13 and 14 are what the feet did not deliver.  A frozen row has 0 in 13 .. 15 and the plan's forces f_e in 1 .. 12.
+ * status: qtos_rollout's bits, and bit 6 no stance foot in this row, bit 7 exactly two stance feet, bit 8 a comparison of the limit
+ * acted in a step of this tick. */
+#define QTOS_FEET_LIMIT 1            /* feet_flags: limit every stance force (no pulling, friction pyramid, force cap) */
+#define QTOS_ROLLOUT_FEET_COLS 16
+#define QTOS_ROLLOUT_NO_STANCE 64    /* status of a row; QTOS_ROLLOUT_PENDING (32) stays the carried word's alone */
+#define QTOS_ROLLOUT_TWO_STANCE 128
+#define QTOS_ROLLOUT_LIMITED 256
+typedef struct QtosRolloutFeet {
+  /* the body: QtosRollout's fields under their names, in its order and at its offsets -- the first sizeof(QtosRollout) bytes ARE a
+   * QtosRollout, and a caller may fill them through a QtosRollout pointer */
+  double hz;
+  int substeps;
+  int first_row;
+  int n_rows;
+  long long capacity;
+  int flags;                    /* QTOS_ROLLOUT_* */
+  double mass, gravity;
+  double inertia_b[9];
+  double inertia_b_inv[9];
+  double ff_scale;
+  double kp_lin[3], kd_lin[3];
+  double kp_ang[3], kd_ang[3];
+  double f_fb_max, t_fb_max;
+  double dev_max, tilt_max;
+  long long push_from, push_ticks;
+  /* the feet */
+  double arm;                   /* length the moment rows are divided by (> 0) [m] */
+  double damping;               /* > 0 */
+  double w_min;                 /* floor of the load weights, 0 < w_min <= 1 */
+  double mu;                    /* friction coefficient of the limit (>= 0) */
+  double f_max;                 /* cap of the vertical force of the limit [N] (<= 0: none) */
+  int feet_flags;               /* QTOS_FEET_* */
+} QtosRolloutFeet;
+/* The arguments are qtos_rollout's, with frows B x rows x 16 (may be NULL) in front of status; both forms behave as
+ * qtos_rollout's do (one kernel on `stream`; the host form synchronous through device buffers of its own).
+ * Both: qtos_rollout's errors, and -1 with the reason in qtos_last_error on arm or damping not > 0, w_min outside (0, 1], mu < 0 or
+ * not a number. */
+int qtos_rollout_feet_device(QtosPlanner *p, int B, const QtosRolloutFeet *s, const double *d_nodes, const double *d_t0,
+                             const int *d_first_row /* may be NULL */, const int *d_n_rows /* may be NULL */,
+                             const long long *d_cursor /* NULL in table mode */, const double *d_joint /* may be NULL */,
+                             const double *d_mass_scale /* may be NULL = 1 */, const double *d_push /* may be NULL */,
+                             double *d_state /* in/out */, long long *d_count /* in/out */, int *d_word /* in/out */, double *d_meas,
+                             double *d_rows /* may be NULL */, double *d_frows /* may be NULL */, int *d_status, void *stream);
+int qtos_rollout_feet(QtosPlanner *p, int B, const QtosRolloutFeet *s, const double *nodes, const double *t0, const int *first_row,
+                      const int *n_rows, const long long *cursor, const double *joint, const double *mass_scale, const double *push,
+                      double *state, long long *count, int *word, double *meas, double *rows, double *frows, int *status);
+
 /* Force fit: the contact forces of every row made to supply the wrench the planned MOTION needs ("force distribution").  Between
  * its knots a plan's rows do not obey Newton's law (qtos_plan_check measures by how much); the motion is what the robot tracks, so
  * the forces give.  For B windows at once (k_force_fit, one workgroup per window; the rule, with the order of every operation of

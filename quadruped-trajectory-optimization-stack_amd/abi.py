@@ -14,6 +14,8 @@ CONSTANTS = {
     "QTOS_ROLLOUT_INIT": 1, "QTOS_ROLLOUT_QUAT": 2,
     "QTOS_ROLLOUT_PENDING": 32,           # in a window's carried word, spent by its first call with rows
     "QTOS_ROLLOUT_COLS": 20, "QTOS_ROLLOUT_STATE": 13,
+    "QTOS_FEET_LIMIT": 1, "QTOS_ROLLOUT_FEET_COLS": 16,
+    "QTOS_ROLLOUT_NO_STANCE": 64, "QTOS_ROLLOUT_TWO_STANCE": 128, "QTOS_ROLLOUT_LIMITED": 256,      # status bits of a feet rollout's row
     "QTOS_FIT_ACCUMULATE": 1, "QTOS_FIT_COLS": 32, "QTOS_FIT_FAMILIES": 4,
     "QTOS_ENV_MAX_LEVELS": 64, "QTOS_ENV_MAX_DRAWS": 1 << 24, "QTOS_ENV_LDS_BYTES": 3568,
 }
@@ -192,6 +194,21 @@ class QtosRollout(_Struct):
     ]
 
 
+class QtosRolloutFeet(_Struct):
+    """Parameters of a rollout through the feet (qtos_rollout_feet*): QtosRollout's fields, then the feet's.
+    rollout_feet.rollout_feet_rows takes it as its RolloutParams and as its FeetParams."""
+    _fields_ = QtosRollout._fields_ + [
+        ("arm", C.c_double), ("damping", C.c_double), ("w_min", C.c_double), ("mu", C.c_double), ("f_max", C.c_double),
+        ("feet_flags", C.c_int),
+    ]
+
+    def with_body(self, body):
+        """A copy whose QtosRollout part is `body` (a QtosRollout)."""
+        g = self.copy()
+        C.memmove(C.byref(g), C.byref(body), C.sizeof(QtosRollout))
+        return g
+
+
 class QtosForceFit(_Struct):
     """Parameters of a force fit (qtos_force_fit*); force_fit.fit_rows reads the same fields."""
     _fields_ = [
@@ -248,6 +265,8 @@ def _prototypes():
         "qtos_plan_check_device": f(h, i, P(QtosPlanCheck), vp, vp, vp, vp, vp, vp, vp, vp, vp),
         "qtos_rollout":        f(h, i, P(QtosRollout), dp, dp, ip, ip, qp, dp, dp, dp, dp, qp, ip, dp, dp, ip),
         "qtos_rollout_device": f(h, i, P(QtosRollout), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp),
+        "qtos_rollout_feet":        f(h, i, P(QtosRolloutFeet), dp, dp, ip, ip, qp, dp, dp, dp, dp, qp, ip, dp, dp, dp, ip),
+        "qtos_rollout_feet_device": f(h, i, P(QtosRolloutFeet), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp),
         "qtos_force_fit":        f(h, i, P(QtosForceFit), dp, dp, ip, ip, ip, qp, dp, dp, dp, ip, vp),   # (summary, as above)
         "qtos_force_fit_device": f(h, i, P(QtosForceFit), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp),
         "qtos_path_goal":        f(h, i, P(QtosPathGoal), dp, dp, ip, dp, ip, dp, ip, dp, dp, dp, dp, ip),

@@ -15,9 +15,9 @@ import numpy as np
 from .abi import *  # noqa: F401,F403  (the mirror is part of this module's interface: capi.QtosTrack, capi.TRACK_COLS, capi.EXPORTS ...)
 from .abi import (CHECK_ACCUMULATE, CHECK_COLS, CHECK_FAMILIES, CSV_COLS, FEEDBACK_QUAT, FEEDBACK_SNAP, FEEDBACK_ZERO_FILTER,
                   FIT_ACCUMULATE, FIT_COLS, FIT_FAMILIES, HIST_COLS, JOINT_NO_FF, MAX_PHASES, NEE, PROTOTYPES, ROLLOUT_COLS,
-                  ROLLOUT_INIT, ROLLOUT_QUAT, ROLLOUT_STATE, START_DOUBLES, TRACK_CLEAN_DELAY, TRACK_COLS, TRACK_QUAT, QtosDims,
+                  ROLLOUT_FEET_COLS, ROLLOUT_INIT, ROLLOUT_QUAT, ROLLOUT_STATE, START_DOUBLES, TRACK_CLEAN_DELAY, TRACK_COLS, TRACK_QUAT, QtosDims,
                   QtosForceFit, QtosHandover, QtosJointRows, QtosFeedback, QtosParams, QtosPathGoal, QtosPathPlan, QtosPlanCheck,
-                  QtosProbe, QtosReport, QtosRollout, QtosSelftest, QtosStitch, QtosTerrainEnv, QtosTrack)
+                  QtosProbe, QtosReport, QtosRollout, QtosRolloutFeet, QtosSelftest, QtosStitch, QtosTerrainEnv, QtosTrack)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (QTOS_LIB names another build of the library in csrc/: A/B timing of kernel variants, scratch/ab2.py)
@@ -248,6 +248,17 @@ def rollout_params(cfg=None, hz=1000.0, substeps=1, first_row=0, n_rows=0, capac
         g.kp_lin[i], g.kd_lin[i], g.kp_ang[i], g.kd_ang[i] = float(r.kp_lin[i]), float(r.kd_lin[i]), float(r.kp_ang[i]), float(r.kd_ang[i])
     g.f_fb_max, g.t_fb_max, g.dev_max, g.tilt_max = r.f_fb_max, r.t_fb_max, r.dev_max, r.tilt_max
     g.push_from, g.push_ticks = r.push_from, r.push_ticks
+    return g
+
+
+def rollout_feet_params(cfg=None, arm=0.2, damping=1e-6, w_min=0.01, mu=None, f_max=None, limit=False, **body):
+    """A QtosRolloutFeet: `body` are rollout_params' keywords (cfg is passed on to it).  arm, damping and w_min default to the fit's,
+    mu and f_max to the planner configuration's friction and force limit (cfg None: the defaults'); limit: QTOS_FEET_LIMIT.  A
+    value outside its range raises ValueError, as rollout_feet.FeetParams does."""
+    from . import rollout_feet
+    f = rollout_feet.FeetParams(cfg, arm, damping, w_min, mu, f_max, limit)
+    g = QtosRolloutFeet().with_body(rollout_params(cfg=cfg, **body))
+    g.arm, g.damping, g.w_min, g.mu, g.f_max, g.feet_flags = f.arm, f.damping, f.w_min, f.mu, f.f_max, f.feet_flags
     return g
 
 
@@ -670,6 +681,9 @@ class Planner:
     def has_rollout(self):
         return self.has("qtos_rollout")
 
+    def has_rollout_feet(self):
+        return self.has("qtos_rollout_feet")
+
     def has_start_feedback(self):
         return self.has("qtos_start_feedback")
 
@@ -918,6 +932,39 @@ class Planner:
                                         _dp(ms), _dp(push), _dp(state), _llp(count), _ip(word), _dp(meas), _dp(rows), _ip(status)),
                   "rollout")
         return meas, rows, status, state, count, word
+
+    def rollout_feet(self, nodes, t0, params, first_row=None, n_rows=None, cursor=None, joint=None, mass_scale=None, push=None, state=None,
+                     count=None, word=None, meas=None, rows=True, frows=True, status=None):
+        """Roll the windows' bodies out with their feedback delivered through the stance feet (qtos_rollout_feet, host form; the
+        rule: rollout_feet.rollout_feet_rows).  params: a QtosRolloutFeet (rollout_feet_params()).  Every other argument is
+        rollout()'s; frows: True, an array (B, rows, 16) or False / None for no feet table.  Returns new arrays (meas, rows or None,
+        frows or None, status, state, count, word)."""
+        self._need("qtos_rollout_feet", "feet rollout kernel")
+        body = params
+        nodes, B = self._nodes(nodes)
+        t0 = _bcast(t0, B)
+        first, per = _bcast(first_row, B, np.int32), _bcast(n_rows, B, np.int32)
+        nr, cur = _segment(body, B, cursor)
+        nr = max(nr, 0)                                    # (a negative n_rows: the library refuses it)
+        mcols = 19 if body.flags & ROLLOUT_QUAT else 18
+        joint = None if joint is None else np.ascontiguousarray(joint, np.float64)
+        if joint is not None and joint.shape != (B, nr, CSV_COLS):
+            raise ValueError("joint is (B, %d, %d)" % (nr, CSV_COLS))
+        ms, push = _bcast(mass_scale, B), _mat(push, (B, 6))
+        state = np.zeros((B, ROLLOUT_STATE)) if state is None else _mat(state, (B, ROLLOUT_STATE), copy=True)
+        count = np.zeros(B, np.int64) if count is None else _bcast(count, B, np.int64, copy=True)
+        word = np.zeros(B, np.int32) if word is None else _bcast(word, B, np.int32, copy=True)
+        meas = np.zeros((B, nr, mcols)) if meas is None else np.array(meas, np.float64)
+        rows, frows = _table(rows, (B, nr, ROLLOUT_COLS)), _table(frows, (B, nr, ROLLOUT_FEET_COLS))
+        status = np.zeros((B, nr), np.int32) if status is None else np.array(status, np.int32)
+        if meas.shape != (B, nr, mcols) or status.shape != (B, nr) or (rows is not None and rows.shape != (B, nr, ROLLOUT_COLS)) or \
+                (frows is not None and frows.shape != (B, nr, ROLLOUT_FEET_COLS)):
+            raise ValueError("meas is (B, %d, %d), rows (B, %d, %d), frows (B, %d, %d) and status (B, %d)"
+                             % (nr, mcols, nr, ROLLOUT_COLS, nr, ROLLOUT_FEET_COLS, nr))
+        self._chk(self.lib.qtos_rollout_feet(self.h, B, C.byref(params), _dp(nodes), _dp(t0), _ip(first), _ip(per), _llp(cur), _dp(joint),
+                                             _dp(ms), _dp(push), _dp(state), _llp(count), _ip(word), _dp(meas), _dp(rows), _dp(frows),
+                                             _ip(status)), "rollout_feet")
+        return meas, rows, frows, status, state, count, word
 
     def start_feedback(self, nodes, t0, row, meas, params, start, cursor=None, map_id=None, goal_step=None, goal=None, err=None,
                        status=None):

@@ -530,6 +530,87 @@ int qtos_rollout(QtosPlanner *p, int B, const QtosRollout *s, const double *node
   return rc ? rc : S.download();
 }
 
+// ---- the rollout with its feedback through the stance feet (k_rollout_feet, window_kernels.hpp) ------------------
+// The argument checks of both forms: qtos_rollout's on the body (the structure's first sizeof(QtosRollout) bytes), then the feet's own; QtosRolloutFeet as k_rollout_feet reads it.
+static int rollout_feet_args(QtosPlanner *p, int B, const QtosRolloutFeet *s, const void *nodes, const void *t0, const void *cursor,
+                             const void *state, const void *count, const void *word, const void *meas, const void *status, RolloutArgs *A,
+                             FeetArgs *F) {
+  if (!p) return -1;
+  if (!s) {
+    p->err = "qtos_rollout_feet: a required pointer is null";
+    return -1;
+  }
+  static_assert(offsetof(QtosRolloutFeet, arm) == sizeof(QtosRollout) && offsetof(QtosRolloutFeet, push_ticks) == offsetof(QtosRollout, push_ticks) &&
+                    offsetof(QtosRolloutFeet, flags) == offsetof(QtosRollout, flags) && offsetof(QtosRolloutFeet, ff_scale) == offsetof(QtosRollout, ff_scale),
+                "QtosRolloutFeet begins with QtosRollout's fields");
+  QtosRollout body;
+  std::memcpy(&body, s, sizeof(body));
+  if (rollout_args(p, B, &body, nodes, t0, cursor, state, count, word, meas, status, A)) {
+    p->err = "qtos_rollout_feet: " + p->err.substr(p->err.find(": ") + 2);
+    return -1;
+  }
+  const char *why = nullptr;
+  if (!(s->arm > 0) || !(s->arm <= 1.7976931348623157e308)) why = "arm is > 0";
+  else if (!(s->damping > 0) || !(s->damping <= 1.7976931348623157e308)) why = "damping is > 0";
+  else if (!(s->w_min > 0) || !(s->w_min <= 1)) why = "w_min is in (0, 1]";
+  else if (!(s->mu >= 0)) why = "mu is >= 0";
+  if (why) {
+    p->err = std::string("qtos_rollout_feet: ") + why;
+    return -1;
+  }
+  F->arm = s->arm; F->damping = s->damping; F->w_min = s->w_min; F->mu = s->mu; F->f_max = s->f_max;
+  for (int e = 0; e < NEE; ++e) F->stance[e] = p->d_stance[e];
+  F->limit = (s->feet_flags & QTOS_FEET_LIMIT) != 0;
+  return 0;
+}
+
+int qtos_rollout_feet_device(QtosPlanner *p, int B, const QtosRolloutFeet *s, const double *d_nodes, const double *d_t0,
+                             const int *d_first_row, const int *d_n_rows, const long long *d_cursor, const double *d_joint,
+                             const double *d_mass_scale, const double *d_push, double *d_state, long long *d_count, int *d_word,
+                             double *d_meas, double *d_rows, double *d_frows, int *d_status, void *stream_) {
+  RolloutArgs A;
+  FeetArgs F;
+  if (rollout_feet_args(p, B, s, d_nodes, d_t0, d_cursor, d_state, d_count, d_word, d_meas, d_status, &A, &F)) return -1;
+  const long long most = most_rows(A.capacity, A.n_rows, d_n_rows != nullptr);
+  if (most < 1) return 0;
+  HIPCHK(p, hipSetDevice(p->device));
+  if (most > ROLLOUT_TICK)
+    hipLaunchKernelGGL(k_rollout_feet<ROLLOUT_TILE>, dim3(B), dim3(ROLLOUT_TILE), 0, (hipStream_t)stream_, p->d_sp, A, F, d_nodes, d_t0,
+                       d_first_row, d_n_rows, d_cursor, d_joint, d_mass_scale, d_push, d_state, d_count, d_word, d_meas, d_rows, d_frows,
+                       d_status, B);
+  else
+    hipLaunchKernelGGL(k_rollout_feet<ROLLOUT_TICK>, dim3(B), dim3(ROLLOUT_TICK), 0, (hipStream_t)stream_, p->d_sp, A, F, d_nodes, d_t0,
+                       d_first_row, d_n_rows, d_cursor, d_joint, d_mass_scale, d_push, d_state, d_count, d_word, d_meas, d_rows, d_frows,
+                       d_status, B);
+  HIPCHK(p, hipGetLastError());
+  return 0;
+}
+
+int qtos_rollout_feet(QtosPlanner *p, int B, const QtosRolloutFeet *s, const double *nodes, const double *t0, const int *first_row,
+                      const int *n_rows, const long long *cursor, const double *joint, const double *mass_scale, const double *push,
+                      double *state, long long *count, int *word, double *meas, double *rows_out, double *frows, int *status) {
+  RolloutArgs A;
+  FeetArgs F;
+  if (rollout_feet_args(p, B, s, nodes, t0, cursor, state, count, word, meas, status, &A, &F)) return -1;
+  HIPCHK(p, hipSetDevice(p->device));
+  const size_t rows = segment_elems(B, A.capacity, A.n_rows);
+  const size_t mcols = (A.flags & QTOS_ROLLOUT_QUAT) ? 19 : 18;
+  Staging S(p);
+  const double *d_nodes = S.in(nodes, (size_t)B * p->M.n_vars), *d_t0 = S.in(t0, B);
+  const int *d_first = S.in(first_row, B), *d_n = S.in(n_rows, B);
+  const long long *d_cur = S.in(cursor, B);
+  const double *d_joint = S.in(joint, rows * QTOS_CSV_COLS), *d_ms = S.in(mass_scale, B), *d_push = S.in(push, (size_t)B * 6);
+  double *d_state = S.inout(state, (size_t)B * 13);
+  long long *d_count = S.inout(count, B);
+  int *d_word = S.inout(word, B);
+  double *d_meas = S.inout(meas, rows * mcols), *d_rows = S.inout(rows_out, rows * ROLLOUT_COLS), *d_frows = S.inout(frows, rows * FEET_COLS);
+  int *d_st = S.inout(status, rows);
+  if (S.rc) return S.rc;
+  const int rc = qtos_rollout_feet_device(p, B, s, d_nodes, d_t0, d_first, d_n, d_cur, d_joint, d_ms, d_push, d_state, d_count, d_word,
+                                          d_meas, d_rows, d_frows, d_st, nullptr);
+  return rc ? rc : S.download();
+}
+
 // ---- the rows' contact forces fitted to the planned motion (k_force_fit, window_kernels.hpp) ---------------------
 // The argument checks of both forms, and QtosForceFit as k_force_fit reads it, with the model's constants and the terrain.  Every
 // -1 but the null planner's leaves its reason in the handle's err.

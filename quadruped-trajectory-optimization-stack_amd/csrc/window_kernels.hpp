@@ -975,6 +975,56 @@ __device__ inline double rollout_clip(double v, double lim, bool &acted) {   // 
   return v;
 }
 
+// rollout_step's lines 1, 2 and 4 .. 7 and, below, 9 .. 11 as two functions of their own, for k_rollout_feet's step, which replaces
+// the lines between them.  rollout_step itself keeps its one body: split into these calls k_rollout compiled to other code.
+// Lines 1, 2 and 4 .. 7 of rollout.step under the row p: e, the clipped F_fb (b), R(q) and the clipped tau_fb (c).
+__device__ inline void rollout_feedback(const RolloutArgs &A, const double *p, const RolloutState &s, double e[3], double b[3], double R[9],
+                                        double c[3], bool &clipped) {
+#pragma clang fp contract(off)
+  e[0] = s.r0 - p[1]; e[1] = s.r1 - p[2]; e[2] = s.r2 - p[3];
+  b[0] = rollout_clip(-(A.kp_lin[0] * e[0]) - A.kd_lin[0] * (s.v0 - p[4]), A.f_fb_max, clipped);
+  b[1] = rollout_clip(-(A.kp_lin[1] * e[1]) - A.kd_lin[1] * (s.v1 - p[5]), A.f_fb_max, clipped);
+  b[2] = rollout_clip(-(A.kp_lin[2] * e[2]) - A.kd_lin[2] * (s.v2 - p[6]), A.f_fb_max, clipped);
+  const double x = s.qx, y = s.qy, z = s.qz, w = s.qw;
+  R[0] = 1 - 2 * (y * y + z * z); R[1] = 2 * (x * y - z * w); R[2] = 2 * (x * z + y * w);
+  R[3] = 2 * (x * y + z * w); R[4] = 1 - 2 * (x * x + z * z); R[5] = 2 * (y * z - x * w);
+  R[6] = 2 * (x * z - y * w); R[7] = 2 * (y * z + x * w); R[8] = 1 - 2 * (x * x + y * y);
+  double qx, qy, qz, qw;
+  rollout_attitude(p, s, qx, qy, qz, qw);
+  const double g0 = 2 * qx, g1 = 2 * qy, g2 = 2 * qz;
+  const double u0 = (R[0] * s.w0 + R[1] * s.w1) + R[2] * s.w2, u1 = (R[3] * s.w0 + R[4] * s.w1) + R[5] * s.w2,
+               u2 = (R[6] * s.w0 + R[7] * s.w1) + R[8] * s.w2;
+  c[0] = rollout_clip(A.kp_ang[0] * g0 + A.kd_ang[0] * (p[11] - u0), A.t_fb_max, clipped);
+  c[1] = rollout_clip(A.kp_ang[1] * g1 + A.kd_ang[1] * (p[12] - u1), A.t_fb_max, clipped);
+  c[2] = rollout_clip(A.kp_ang[2] * g2 + A.kd_ang[2] * (p[13] - u2), A.t_fb_max, clipped);
+}
+
+// Lines 9 .. 11 of rollout.step: the state moved on by h under the acceleration a and the world torque t, R = R(q) of the old state.
+__device__ inline void rollout_advance(const RolloutArgs &A, const RolloutBody &M, const double R[9], const double a[3], const double t[3],
+                                       RolloutState &s) {
+#pragma clang fp contract(off)
+  const double h = A.h;
+  const double x = s.qx, y = s.qy, z = s.qz, w = s.qw;
+  s.v0 = s.v0 + h * a[0]; s.r0 = s.r0 + h * s.v0;
+  s.v1 = s.v1 + h * a[1]; s.r1 = s.r1 + h * s.v1;
+  s.v2 = s.v2 + h * a[2]; s.r2 = s.r2 + h * s.v2;
+  const double tb0 = (R[0] * t[0] + R[3] * t[1]) + R[6] * t[2], tb1 = (R[1] * t[0] + R[4] * t[1]) + R[7] * t[2],
+               tb2 = (R[2] * t[0] + R[5] * t[1]) + R[8] * t[2];
+  const double i0 = (M.I[0] * s.w0 + M.I[1] * s.w1) + M.I[2] * s.w2, i1 = (M.I[3] * s.w0 + M.I[4] * s.w1) + M.I[5] * s.w2,
+               i2 = (M.I[6] * s.w0 + M.I[7] * s.w1) + M.I[8] * s.w2;
+  const double n0 = tb0 - (s.w1 * i2 - s.w2 * i1), n1 = tb1 - (s.w2 * i0 - s.w0 * i2), n2 = tb2 - (s.w0 * i1 - s.w1 * i0);
+  const double w0 = s.w0 + h * ((M.J[0] * n0 + M.J[1] * n1) + M.J[2] * n2);
+  const double w1 = s.w1 + h * ((M.J[3] * n0 + M.J[4] * n1) + M.J[5] * n2);
+  const double w2 = s.w2 + h * ((M.J[6] * n0 + M.J[7] * n1) + M.J[8] * n2);
+  const double hh = h * 0.5;
+  const double d0 = (w * w0 + y * w2) - z * w1, d1 = (w * w1 - x * w2) + z * w0, d2 = (w * w2 + x * w1) - y * w0,
+               d3 = (-(x * w0) - y * w1) - z * w2;
+  const double m0 = x + hh * d0, m1 = y + hh * d1, m2 = z + hh * d2, m3 = w + hh * d3;
+  const double nn = sqrt(((m0 * m0 + m1 * m1) + m2 * m2) + m3 * m3);
+  s.qx = m0 / nn; s.qy = m1 / nn; s.qz = m2 / nn; s.qw = m3 / nn;
+  s.w0 = w0; s.w1 = w1; s.w2 = w2;
+}
+
 // One step of length A.h under the row p (rollout.step, its lines 1 .. 11); returns |F_fb|.
 __device__ inline double rollout_step(const RolloutArgs &A, const RolloutBody &M, const double *p, bool push, RolloutState &s,
                                       bool &clipped) {
@@ -1022,12 +1072,14 @@ __device__ inline double rollout_step(const RolloutArgs &A, const RolloutBody &M
   return rollout_norm(b0, b1, b2);
 }
 
-// (C) of a row: the state in t[20 .. 32] becomes the output columns 1 .. 16 in t (17 .. 19 move up from 33 .. 35); returns the
-// GIMBAL bit.  The Euler extraction is track_pose's, with comparisons for the clip so that a NaN stays one.
+// (C) of a row: the state in t[S .. S + 12] (k_rollout: 20 .. 32) becomes the output columns 1 .. 16 in t (17 .. 19 move up from
+// S + 13 .. S + 15); returns the GIMBAL bit.  The Euler extraction is track_pose's, with comparisons for the clip so that a NaN
+// stays one.
+template <int S = 20>
 __device__ inline int rollout_output(double *t) {
 #pragma clang fp contract(off)
-  const double r0 = t[20], r1 = t[21], r2 = t[22], v0 = t[23], v1 = t[24], v2 = t[25];
-  const double x = t[26], y = t[27], z = t[28], w = t[29], w0 = t[30], w1 = t[31], w2 = t[32];
+  const double r0 = t[S], r1 = t[S + 1], r2 = t[S + 2], v0 = t[S + 3], v1 = t[S + 4], v2 = t[S + 5];
+  const double x = t[S + 6], y = t[S + 7], z = t[S + 8], w = t[S + 9], w0 = t[S + 10], w1 = t[S + 11], w2 = t[S + 12];
   const double R0 = 1 - 2 * (y * y + z * z), R1 = 2 * (x * y - z * w), R2 = 2 * (x * z + y * w);
   const double R3 = 2 * (x * y + z * w), R4 = 1 - 2 * (x * x + z * z), R5 = 2 * (y * z - x * w);
   const double R6 = 2 * (x * z - y * w), R7 = 2 * (y * z + x * w), R8 = 1 - 2 * (x * x + y * y);
@@ -1038,7 +1090,7 @@ __device__ inline int rollout_output(double *t) {
   t[7] = v0; t[8] = v1; t[9] = v2;
   t[10] = (R0 * w0 + R1 * w1) + R2 * w2; t[11] = (R3 * w0 + R4 * w1) + R5 * w2; t[12] = (R6 * w0 + R7 * w1) + R8 * w2;
   t[13] = x; t[14] = y; t[15] = z; t[16] = w;
-  t[17] = t[33]; t[18] = t[34]; t[19] = t[35];
+  t[17] = t[S + 13]; t[18] = t[S + 14]; t[19] = t[S + 15];
   return fabs(R6) >= 1 ? 4 : 0;
 }
 
@@ -1236,20 +1288,33 @@ __device__ inline void fit_foot_sums(const FitFoot &F, double arm, FitSums &Q) {
 
 __device__ constexpr int fit_ix(int i, int j) { return i * (i + 1) / 2 + j; }   // the lower triangle, row by row
 
+// acc - a b of the solve below.  FitFused: under the compiler's default, which may fuse it (k_force_fit); FitExact: two rounded
+// operations (k_rollout_feet, whose chain switches contraction off).
+struct FitFused {
+  static __device__ inline double nms(double acc, double a, double b) { return acc - a * b; }
+};
+struct FitExact {
+  static __device__ inline double nms(double acc, double a, double b) {
+#pragma clang fp contract(off)
+    return acc - a * b;
+  }
+};
+
 // y = M^-1 rhs by the unpivoted Cholesky of force_fit.py; M: the lower triangle, overwritten with L.
+template <class Op = FitFused>
 __device__ inline void fit_solve(double M[21], const double rhs[6], double y[6]) {
 #pragma unroll
   for (int j = 0; j < 6; ++j) {
     double acc = M[fit_ix(j, j)];
 #pragma unroll
-    for (int k = 0; k < j; ++k) acc -= M[fit_ix(j, k)] * M[fit_ix(j, k)];
+    for (int k = 0; k < j; ++k) acc = Op::nms(acc, M[fit_ix(j, k)], M[fit_ix(j, k)]);
     const double ljj = sqrt(acc);
     M[fit_ix(j, j)] = ljj;
 #pragma unroll
     for (int i = j + 1; i < 6; ++i) {
       double a = M[fit_ix(i, j)];
 #pragma unroll
-      for (int k = 0; k < j; ++k) a -= M[fit_ix(i, k)] * M[fit_ix(j, k)];
+      for (int k = 0; k < j; ++k) a = Op::nms(a, M[fit_ix(i, k)], M[fit_ix(j, k)]);
       M[fit_ix(i, j)] = a / ljj;
     }
   }
@@ -1258,14 +1323,14 @@ __device__ inline void fit_solve(double M[21], const double rhs[6], double y[6])
   for (int i = 0; i < 6; ++i) {
     double acc = rhs[i];
 #pragma unroll
-    for (int k = 0; k < i; ++k) acc -= M[fit_ix(i, k)] * z[k];
+    for (int k = 0; k < i; ++k) acc = Op::nms(acc, M[fit_ix(i, k)], z[k]);
     z[i] = acc / M[fit_ix(i, i)];
   }
 #pragma unroll
   for (int i = 5; i >= 0; --i) {
     double acc = z[i];
 #pragma unroll
-    for (int k = i + 1; k < 6; ++k) acc -= M[fit_ix(k, i)] * y[k];
+    for (int k = i + 1; k < 6; ++k) acc = Op::nms(acc, M[fit_ix(k, i)], y[k]);
     y[i] = acc / M[fit_ix(i, i)];
   }
 }
@@ -1467,6 +1532,286 @@ __global__ __launch_bounds__(FIT_TILE) void k_force_fit(const SamplePlan *Sd, Fi
       }
       *dst = rec;
     }
+  }
+}
+
+// Rollout through the feet (qtos_rollout_feet*): k_rollout with its feedback wrench delivered by the feet that stand.  The
+// statement of the rule is rollout_feet.py: lines 1, 2, 4 .. 7 and 9 .. 11 of the step are k_rollout's (rollout_feedback,
+// rollout_advance), lines 3 and 8 are replaced -- the clipped PD wrench is distributed over the stance feet by k_force_fit's damped
+// load-weighted 6 x 6 solve (its ten sums, its matrix and fit_solve, here with one rounded operation per operation), the forces
+// act at the plan's footholds about the ACTUAL centre of mass and, with QTOS_FEET_LIMIT, are limited by comparisons to what a
+// foot can do.  The kernel has k_rollout's shape: one workgroup per window; per tile (A) a lane takes a row -- the plan row, the
+// 20 inputs, the feet's positions and forces, the load weights from the forces' vertical components and the stance mask into the
+// row's place of an LDS tile; (B) lane 0 walks the chain, only +, -, x, / and sqrt, the 21 entries of M and of L in registers with
+// constant indices (the feet come through unrolled loops); the applied forces and the missing wrench of a tick's FIRST step stay
+// in registers until the tick's last step has read the plan's forces, then take their place; (C) a lane turns its row's state into
+// the output columns, and the tile goes out flat: rows, meas and the 16-column feet rows (RowSegment's addressing).
+// A row of the tile, FEET_PITCH = 67 doubles (odd: consecutive lanes on different banks): 0 .. 19 the inputs / outputs, 20 .. 31
+// p_e, 32 .. 43 f_e (behind the tick: f_a), 44 .. 47 w_e (behind the tick: columns 13 .. 15), 48 the stance mask, 49 .. 61 the
+// state, 62 |e|, 63 tilt, 64 |F_fb|, 65 the status, 66 unused.  256 x 67 x 8 = 137 216 bytes of LDS, 64 x 67 x 8 = 34 304 for
+// the tick.  No atomics, no scratch, every barrier uniform.
+constexpr int FEET_COLS = 16;
+constexpr int FEET_PITCH = 67;
+constexpr int FEET_P = 20, FEET_F = 32, FEET_W = 44, FEET_MASK = 48, FEET_STATE = 49, FEET_STATUS = 65;   // places in a row of the tile
+struct FeetArgs {   // QtosRolloutFeet's own fields as the kernel reads them (window_api.hpp rollout_feet_args)
+  double arm, damping, w_min, mu, f_max;
+  const int *stance[NEE];                  // per foot and polynomial of its motion spline: 1 stance, 0 swing
+  int limit;
+};
+struct FeetOut { double fa[12], miss_f, miss_t, change; };   // columns 1 .. 15 of a feet row
+
+// The feet of a plan row c (37 columns) into the row's place d of the tile: p_e, f_e, the load weights w_e from the vertical
+// components of the stance feet's forces and the stance mask (rollout_feet.plan_feet).
+__device__ inline void feet_inputs(const double *c, int mask, double w_min, double *d) {
+#pragma clang fp contract(off)
+  double g[NEE];
+  int cnt = 0;
+#pragma unroll
+  for (int e = 0; e < NEE; ++e) {
+    const bool on = (mask >> e) & 1;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { d[FEET_P + 3 * e + i] = c[7 + 3 * e + i]; d[FEET_F + 3 * e + i] = c[25 + 3 * e + i]; }
+    const double fz = c[27 + 3 * e];
+    g[e] = on && fz > 0 ? fz : 0.0;
+    cnt += on ? 1 : 0;
+  }
+  const double gsum = ((g[0] + g[1]) + g[2]) + g[3], nn = (double)cnt;
+  const bool loaded = gsum > 0;
+#pragma unroll
+  for (int e = 0; e < NEE; ++e) {
+    const double x = (nn * g[e]) / gsum;
+    d[FEET_W + e] = loaded ? (x < w_min ? w_min : x) : 1.0;
+  }
+  d[FEET_MASK] = (double)mask;
+}
+
+// One step of length A.h under the row p of the tile (rollout_feet.step); returns |F_fb|.  o: the applied forces and what the
+// feet did not deliver, of this step.
+__device__ inline double rollout_feet_step(const RolloutArgs &A, const FeetArgs &Ft, const RolloutBody &M, const double *p, bool push,
+                                           RolloutState &s, bool &clipped, bool &limited, FeetOut &o) {
+#pragma clang fp contract(off)
+  double e[3], b[3], R[9], c[3];
+  rollout_feedback(A, p, s, e, b, R, c, clipped);
+  const double arm = Ft.arm, ff = A.ff_scale;
+  const double rhs[6] = {c[0] / arm, c[1] / arm, c[2] / arm, b[0], b[1], b[2]};
+  const int mask = (int)p[FEET_MASK];
+  double l[12], d[12];
+  FitSums Q = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  int cnt = 0;
+#pragma unroll
+  for (int k = 0; k < NEE; ++k) {
+    l[3 * k] = p[FEET_P + 3 * k] - s.r0; l[3 * k + 1] = p[FEET_P + 3 * k + 1] - s.r1; l[3 * k + 2] = p[FEET_P + 3 * k + 2] - s.r2;
+    d[3 * k] = l[3 * k] / arm; d[3 * k + 1] = l[3 * k + 1] / arm; d[3 * k + 2] = l[3 * k + 2] / arm;
+    if ((mask >> k) & 1) {                                     // fit_foot_sums' lines, one rounded operation each
+      const double w = p[FEET_W + k];
+      const double w0 = w * d[3 * k], w1 = w * d[3 * k + 1], w2 = w * d[3 * k + 2];
+      Q.W = Q.W + w; Q.s0 = Q.s0 + w0; Q.s1 = Q.s1 + w1; Q.s2 = Q.s2 + w2;
+      Q.q00 = Q.q00 + w0 * d[3 * k]; Q.q01 = Q.q01 + w0 * d[3 * k + 1]; Q.q02 = Q.q02 + w0 * d[3 * k + 2];
+      Q.q11 = Q.q11 + w1 * d[3 * k + 1]; Q.q12 = Q.q12 + w1 * d[3 * k + 2]; Q.q22 = Q.q22 + w2 * d[3 * k + 2];
+      ++cnt;
+    }
+  }
+  double y[6] = {0, 0, 0, 0, 0, 0};
+  if (cnt > 0) {
+    const double lam = Ft.damping * (double)cnt, wl = Q.W + lam;
+    double K[21] = {(Q.q11 + Q.q22) + lam,
+                    -Q.q01, (Q.q00 + Q.q22) + lam,
+                    -Q.q02, -Q.q12, (Q.q00 + Q.q11) + lam,
+                    0.0, Q.s2, -Q.s1, wl,
+                    -Q.s2, 0.0, Q.s0, 0.0, wl,
+                    Q.s1, -Q.s0, 0.0, 0.0, 0.0, wl};
+    fit_solve<FitExact>(K, rhs, y);
+  }
+  double Fa[3] = {0, 0, 0}, ta[3] = {0, 0, 0}, gF[3] = {0, 0, 0}, gT[3] = {0, 0, 0}, sq = 0;
+#pragma unroll
+  for (int k = 0; k < NEE; ++k) {
+    const bool on = (mask >> k) & 1;
+    const double *dk = d + 3 * k, *lk = l + 3 * k;
+    const double f0 = ff * p[FEET_F + 3 * k], f1 = ff * p[FEET_F + 3 * k + 1], f2 = ff * p[FEET_F + 3 * k + 2];
+    double a0 = f0 + 0.0, a1 = f1 + 0.0, a2 = f2 + 0.0;
+    if (on) {
+      const double w = p[FEET_W + k];
+      a0 = f0 + ((y[1] * dk[2] - y[2] * dk[1]) + y[3]) * w;
+      a1 = f1 + ((y[2] * dk[0] - y[0] * dk[2]) + y[4]) * w;
+      a2 = f2 + ((y[0] * dk[1] - y[1] * dk[0]) + y[5]) * w;
+      if (Ft.limit) {                                          // by comparisons only: a NaN stays a NaN
+        if (a2 < 0) { a2 = 0.0; limited = true; }
+        if (Ft.f_max > 0 && a2 > Ft.f_max) { a2 = Ft.f_max; limited = true; }
+        const double lim = Ft.mu * a2;
+        if (a0 < -lim) { a0 = -lim; limited = true; } else if (a0 > lim) { a0 = lim; limited = true; }
+        if (a1 < -lim) { a1 = -lim; limited = true; } else if (a1 > lim) { a1 = lim; limited = true; }
+      }
+    }
+    o.fa[3 * k] = a0; o.fa[3 * k + 1] = a1; o.fa[3 * k + 2] = a2;
+    const double x0 = lk[1] * a2 - lk[2] * a1, x1 = lk[2] * a0 - lk[0] * a2, x2 = lk[0] * a1 - lk[1] * a0;
+    if (k == 0) { Fa[0] = a0; Fa[1] = a1; Fa[2] = a2; ta[0] = x0; ta[1] = x1; ta[2] = x2; }
+    else { Fa[0] = Fa[0] + a0; Fa[1] = Fa[1] + a1; Fa[2] = Fa[2] + a2; ta[0] = ta[0] + x0; ta[1] = ta[1] + x1; ta[2] = ta[2] + x2; }
+    if (on) {                                                  // what this foot adds to the plan's force, and its moment
+      const double g0 = a0 - f0, g1 = a1 - f1, g2 = a2 - f2;
+      gF[0] = gF[0] + g0; gF[1] = gF[1] + g1; gF[2] = gF[2] + g2;
+      gT[0] = gT[0] + (lk[1] * g2 - lk[2] * g1); gT[1] = gT[1] + (lk[2] * g0 - lk[0] * g2); gT[2] = gT[2] + (lk[0] * g1 - lk[1] * g0);
+      sq = sq + ((g0 * g0 + g1 * g1) + g2 * g2);
+    }
+  }
+  o.miss_f = rollout_norm(gF[0] - b[0], gF[1] - b[1], gF[2] - b[2]);
+  o.miss_t = rollout_norm(gT[0] - c[0], gT[1] - c[1], gT[2] - c[2]);
+  o.change = sqrt(sq);
+  const double P0 = push ? M.F0 : 0.0, P1 = push ? M.F1 : 0.0, P2 = push ? M.F2 : 0.0;
+  const double Q0 = push ? M.T0 : 0.0, Q1 = push ? M.T1 : 0.0, Q2 = push ? M.T2 : 0.0;
+  const double a[3] = {(Fa[0] + P0) / M.m_s, (Fa[1] + P1) / M.m_s, (Fa[2] + P2) / M.m_s - A.gravity};
+  const double t[3] = {ta[0] + Q0, ta[1] + Q1, ta[2] + Q2};
+  rollout_advance(A, M, R, a, t, s);
+  return rollout_norm(b[0], b[1], b[2]);
+}
+
+template <int TILE>
+__global__ __launch_bounds__(TILE) void k_rollout_feet(const SamplePlan *Sd, RolloutArgs A, FeetArgs Ft, const double *nodes, const double *t0,
+                                                       const int *first_row, const int *n_rows, const long long *cursor,
+                                                       const double *joint, const double *mass_scale, const double *push, double *state,
+                                                       long long *count, int *word_io, double *meas, double *rows_out, double *frows_out,
+                                                       int *status_out, int B) {
+  __shared__ double feet_tile[TILE * FEET_PITCH];
+  const int b = blockIdx.x;
+  if (b >= B) return;
+  const SamplePlan &S = *Sd;
+  const bool quat = (A.flags & 2) != 0;
+  const int mcols = quat ? 19 : 18;
+  RolloutState s;                                                                  // (every lane, in front of the first barrier)
+  {
+    const double *sb = state + (size_t)b * 13;
+    s.r0 = sb[0]; s.r1 = sb[1]; s.r2 = sb[2]; s.v0 = sb[3]; s.v1 = sb[4]; s.v2 = sb[5];
+    s.qx = sb[6]; s.qy = sb[7]; s.qz = sb[8]; s.qw = sb[9]; s.w0 = sb[10]; s.w1 = sb[11]; s.w2 = sb[12];
+  }
+  const long long calls = count[b];
+  int word = word_io[b];
+  RolloutBody M;
+  {
+#pragma clang fp contract(off)
+    const double ms = mass_scale ? mass_scale[b] : 1.0;
+    M.m_s = A.mass * ms;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) { M.I[i] = ms * A.Ib[i]; M.J[i] = A.Ii[i] / ms; }
+    const double *pb = push ? push + (size_t)b * 6 : nullptr;
+    M.F0 = pb ? pb[0] : 0.0; M.F1 = pb ? pb[1] : 0.0; M.F2 = pb ? pb[2] : 0.0;
+    M.T0 = pb ? pb[3] : 0.0; M.T1 = pb ? pb[4] : 0.0; M.T2 = pb ? pb[5] : 0.0;
+  }
+  const RowSegment G = RowSegment::of(A.capacity, A.n_rows, A.first_row, n_rows, first_row, cursor, b);
+  const long long rows_b = G.rows_b, n = G.n;
+  if (n == 0) return;                                                              // (uniform: a window without rows keeps its state)
+  const double *x = nodes + (size_t)b * S.n_vars;
+  const double t0b = t0[b];
+  double *meas_b = meas + (size_t)b * (size_t)rows_b * mcols;
+  double *out_b = rows_out ? rows_out + (size_t)b * (size_t)rows_b * ROLLOUT_COLS : nullptr;
+  double *feet_b = frows_out ? frows_out + (size_t)b * (size_t)rows_b * FEET_COLS : nullptr;
+  const double *joint_b = joint ? joint + (size_t)b * (size_t)rows_b * QTOS_CSV_COLS : nullptr;
+  for (long long j0 = 0; j0 < n; j0 += TILE) {                                     // (n is uniform over the workgroup: so are the barriers)
+    const int m = G.tile_rows(j0, TILE);
+    const long long base = G.row(j0);
+    if ((int)threadIdx.x < m) {                                                    // (A) a lane takes a row of the plan
+      double row[QTOS_CSV_COLS];
+      const double t = sample_row_state_at(S, x, t0b, G.plan_row(j0, threadIdx.x), A.hz, row);
+      int mask = 0;
+#pragma unroll
+      for (int e = 0; e < NEE; ++e) {
+        sample_spline(S.eef[e], x, t, 0, row + 25 + 3 * e);
+        mask |= (Ft.stance[e][sample_segment(S.eem[e], t)] != 0 ? 1 : 0) << e;
+      }
+      double *dst = feet_tile + threadIdx.x * FEET_PITCH;
+      rollout_inputs(row, A.ff_scale, dst);
+      feet_inputs(row, mask, Ft.w_min, dst);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {                                                        // (B) the chain, in program order
+#pragma clang fp contract(off)
+      if (j0 == 0 && ((A.flags & 1) || (word & 32))) {                             // QTOS_ROLLOUT_INIT / _PENDING, as in k_rollout
+        word &= ~32;
+        const double *p = feet_tile;
+        s.r0 = p[1]; s.r1 = p[2]; s.r2 = p[3]; s.v0 = p[4]; s.v1 = p[5]; s.v2 = p[6];
+        s.qx = p[7]; s.qy = p[8]; s.qz = p[9]; s.qw = p[10];
+        const double qx = s.qx, qy = s.qy, qz = s.qz, qw = s.qw;
+        const double R0 = 1 - 2 * (qy * qy + qz * qz), R1 = 2 * (qx * qy - qz * qw), R2 = 2 * (qx * qz + qy * qw);
+        const double R3 = 2 * (qx * qy + qz * qw), R4 = 1 - 2 * (qx * qx + qz * qz), R5 = 2 * (qy * qz - qx * qw);
+        const double R6 = 2 * (qx * qz - qy * qw), R7 = 2 * (qy * qz + qx * qw), R8 = 1 - 2 * (qx * qx + qy * qy);
+        s.w0 = (R0 * p[11] + R3 * p[12]) + R6 * p[13];
+        s.w1 = (R1 * p[11] + R4 * p[12]) + R7 * p[13];
+        s.w2 = (R2 * p[11] + R5 * p[12]) + R8 * p[13];
+      }
+      for (int i = 0; i < m; ++i) {
+        double *p = feet_tile + i * FEET_PITCH;
+        double ex, ey, ez, ew;
+        rollout_attitude(p, s, ex, ey, ez, ew);
+        const double en = rollout_norm(s.r0 - p[1], s.r1 - p[2], s.r2 - p[3]);
+        const double tilt = 2 * rollout_norm(ex, ey, ez);
+        const bool finite = isfinite(s.r0) && isfinite(s.r1) && isfinite(s.r2) && isfinite(s.v0) && isfinite(s.v1) && isfinite(s.v2) &&
+                            isfinite(s.qx) && isfinite(s.qy) && isfinite(s.qz) && isfinite(s.qw) && isfinite(s.w0) && isfinite(s.w1) &&
+                            isfinite(s.w2);
+        if (!finite) word |= 2;
+        if ((A.dev_max > 0 && en > A.dev_max) || (A.tilt_max > 0 && tilt > A.tilt_max)) word |= 1;
+        int st = word & 3;
+        double *q = p + FEET_STATE;
+        q[0] = s.r0; q[1] = s.r1; q[2] = s.r2; q[3] = s.v0; q[4] = s.v1; q[5] = s.v2;
+        q[6] = s.qx; q[7] = s.qy; q[8] = s.qz; q[9] = s.qw; q[10] = s.w0; q[11] = s.w1; q[12] = s.w2;
+        q[13] = en; q[14] = tilt;
+        const int mask = (int)p[FEET_MASK];
+        const int cnt = (mask & 1) + ((mask >> 1) & 1) + ((mask >> 2) & 1) + ((mask >> 3) & 1);
+        const int feet_bits = (cnt == 0 ? 64 : 0) | (cnt == 2 ? 128 : 0);
+        double fbn = 0;
+        if (!st) {
+          const long long c = calls + j0 + i;
+          const bool acts = push != nullptr && c >= A.push_from && c - A.push_from < A.push_ticks;
+          bool clipped = false, limited = false;
+          FeetOut first;
+          fbn = rollout_feet_step(A, Ft, M, p, acts, s, clipped, limited, first);
+          for (int u = 1; u < A.substeps; ++u) {
+            FeetOut later;
+            rollout_feet_step(A, Ft, M, p, acts, s, clipped, limited, later);
+          }
+#pragma unroll
+          for (int k = 0; k < 12; ++k) p[FEET_F + k] = first.fa[k];               // (behind the tick's last step: it read f_e and w_e)
+          p[FEET_W] = first.miss_f; p[FEET_W + 1] = first.miss_t; p[FEET_W + 2] = first.change;
+          st = (clipped ? 8 : 0) | (acts ? 16 : 0) | (limited ? 256 : 0);
+        } else {
+          p[FEET_W] = 0.0; p[FEET_W + 1] = 0.0; p[FEET_W + 2] = 0.0;             // a frozen row: the plan's forces stay in their place
+        }
+        q[15] = fbn; p[FEET_STATUS] = (double)(st | feet_bits);
+      }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < m) {                                                    // (C) a lane turns its row's state into the output columns
+      double *p = feet_tile + threadIdx.x * FEET_PITCH;
+      const int st = (int)p[FEET_STATUS] | rollout_output<FEET_STATE>(p);
+      status_out[(size_t)b * (size_t)rows_b + G.tile_row(base, threadIdx.x)] = st;
+    }
+    __syncthreads();
+    if (out_b) {                                                                   // the tile goes out flat: rows ...
+      for (int e = threadIdx.x; e < m * ROLLOUT_COLS; e += TILE) {
+        const int i = e / ROLLOUT_COLS, c = e - i * ROLLOUT_COLS;
+        out_b[G.flat(base, ROLLOUT_COLS, e)] = feet_tile[i * FEET_PITCH + c];
+      }
+    }
+    if (feet_b) {                                                                  // ... the feet rows ...
+      for (int e = threadIdx.x; e < m * FEET_COLS; e += TILE) {
+        const int i = e / FEET_COLS, c = e - i * FEET_COLS;
+        const double *p = feet_tile + i * FEET_PITCH;
+        feet_b[G.flat(base, FEET_COLS, e)] = c == 0 ? p[0] : (c < 13 ? p[FEET_F + (c - 1)] : p[FEET_W + (c - 13)]);
+      }
+    }
+    for (int e = threadIdx.x; e < m * mcols; e += TILE) {                          // ... and meas
+      const int i = e / mcols, c = e - i * mcols;
+      const double *p = feet_tile + i * FEET_PITCH;
+      const long long o = G.flat(base, mcols, e);
+      if (c < 3) meas_b[o] = p[1 + c];
+      else if (c < mcols - 12) meas_b[o] = quat ? p[13 + (c - 3)] : p[4 + (c - 3)];
+      else if (joint_b) meas_b[o] = joint_b[(size_t)G.tile_row(base, i) * QTOS_CSV_COLS + 1 + (c - (mcols - 12))];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    double *sb = state + (size_t)b * 13;
+    sb[0] = s.r0; sb[1] = s.r1; sb[2] = s.r2; sb[3] = s.v0; sb[4] = s.v1; sb[5] = s.v2;
+    sb[6] = s.qx; sb[7] = s.qy; sb[8] = s.qz; sb[9] = s.qw; sb[10] = s.w0; sb[11] = s.w1; sb[12] = s.w2;
+    count[b] = calls + n;
+    word_io[b] = word;
   }
 }
 

@@ -233,7 +233,13 @@ class ShiftedWindows:
                trajectory x 20); ``rollout_rows(b)`` reads a window's ring.  With ``joints`` on the measured joint angles are the
                commanded ones; without, those twelve columns of ``meas_traj`` are not touched.  A ``fill`` callable of ``track``
                still runs, behind the rollout: the place to add sensor noise.  The planner's reference-compat inertia tensor is
-               indefinite: with gains, give ``inertia_b=config.INERTIA_PHYSICAL``.
+               indefinite: with gains, give ``inertia_b=config.INERTIA_PHYSICAL``.  An entry ``feet=dict(arm=, damping=, w_min=,
+               mu=, f_max=, limit=)`` (``capi.rollout_feet_params``' keywords; arm, damping and w_min default to the fit's, mu and
+               f_max to the configuration's friction and force limit) queues k_rollout_feet (qtos_rollout_feet_device, the rule:
+               ``rollout_feet.rollout_feet_rows``) IN PLACE of k_rollout, at the same point and with the same carried arrays: the
+               feedback wrench is delivered through the stance feet, optionally limited to what a foot can do, and
+               ``self.rollout_feet_traj`` (B x trajectory x 16: applied forces, what the feet did not deliver) is filled beside the
+               other rings; ``rollout_feet_rows(b)`` reads a window's.  Without ``feet`` nothing of it is allocated or queued.
     check      None (the default): nothing is queued and nothing is allocated.  A ``capi.check_params(...)`` (needs
                ``trajectory``; its tol is read, its rate and rows are the stitch's): k_plan_check (qtos_plan_check_device, the
                rule: ``plan_check.check_rows`` / ``summarise`` / ``accumulate``) is queued in front of every stitch and in
@@ -341,6 +347,7 @@ class ShiftedWindows:
             planner._need("qtos_rollout_device", "rollout kernel")
             kw = dict(rollout)
             scale, push, keep = kw.pop("mass_scale", None), kw.pop("push", None), kw.pop("rows", False)
+            feet = kw.pop("feet", None)
             kw.setdefault("cfg", getattr(planner, "cfg", None))
             self._rollout = capi.rollout_params(hz=self.hz, first_row=int(self._stitch.first_row), capacity=int(trajectory),
                                                 quaternion=bool(self._track.flags & capi.TRACK_QUAT), **kw)
@@ -351,6 +358,13 @@ class ShiftedWindows:
             self.rollout_traj = torch.zeros((B, int(trajectory), capi.ROLLOUT_COLS), **f64) if keep else None
             up = lambda a, shape: None if a is None else torch.as_tensor(np.broadcast_to(np.asarray(a, np.float64), shape).copy(), **f64)
             self._rollout_scale, self._rollout_push = up(scale, (B,)), up(push, (B, 6))
+            self._feet = None
+            if feet is not None:
+                planner._need("qtos_rollout_feet_device", "feet rollout kernel")
+                fk = dict(feet)
+                fk.setdefault("cfg", kw["cfg"])
+                self._feet = capi.rollout_feet_params(**fk)                  # (its body is the call's QtosRollout, put in by _rollout_rows)
+                self.rollout_feet_traj = torch.zeros((B, int(trajectory), capi.ROLLOUT_FEET_COLS), **f64)
         self._feedback = None
         if feedback is not None:
             if self.track_traj is None:
@@ -569,7 +583,18 @@ class ShiftedWindows:
         state they carry over the rows that stitch appends, under the plan handed over from, and their states fill the measured
         ring's rows of the segment (the joint columns from the joint ring where ``joints`` is on).  A window's first call with
         rows sets its state from the plan's row: ``rollout_word`` starts as QTOS_ROLLOUT_PENDING, which the kernel spends per
-        window, so a window whose hand-over row is 0 at the set's first replan is set on its plan by a later one."""
+        window, so a window whose hand-over row is 0 at the set's first replan is set on its plan by a later one.  With ``feet``
+        k_rollout_feet is queued in its place, with the same carried arrays, and fills ``rollout_feet_traj`` as well."""
+        if self._feet is not None:
+            f = self._feet.with_body(params)
+            self.P._chk(self.P.lib.qtos_rollout_feet_device(self.P.h, self.B, C.byref(f), self.nodes.data_ptr(), self.t0.data_ptr(), None, n_rows,
+                                                            self.cursor.data_ptr(), ptr(self.joint_traj), ptr(self._rollout_scale),
+                                                            ptr(self._rollout_push), self.rollout_state.data_ptr(),
+                                                            self.rollout_count.data_ptr(), self.rollout_word.data_ptr(),
+                                                            self.meas_traj.data_ptr(), ptr(self.rollout_traj),
+                                                            self.rollout_feet_traj.data_ptr(), self.rollout_status.data_ptr(), sp),
+                        "qtos_rollout_feet_device")
+            return
         self.P._chk(self.P.lib.qtos_rollout_device(self.P.h, self.B, C.byref(params), self.nodes.data_ptr(), self.t0.data_ptr(), None, n_rows,
                                                    self.cursor.data_ptr(), ptr(self.joint_traj), ptr(self._rollout_scale),
                                                    ptr(self._rollout_push), self.rollout_state.data_ptr(), self.rollout_count.data_ptr(),
@@ -586,6 +611,15 @@ class ShiftedWindows:
         cur = int(self.cursor[b].item())
         rows = None if self.rollout_traj is None else ring_rows(self.rollout_traj[b].cpu().numpy(), cur)
         return rows, ring_rows(self.rollout_status[b].cpu().numpy(), cur)
+
+    def rollout_feet_rows(self, b):
+        """Window b's newest min(cursor, trajectory) feet rows (16 columns: time stamp, applied forces, what the feet did not
+        deliver) in time order, as numpy (the stream is synchronised): row for row with ``rollout_rows(b)``."""
+        from .stitcher import ring_rows
+        if self._rollout is None or self._feet is None:
+            raise RuntimeError("rollout_feet_rows() needs the rollout through the feet (rollout=dict(..., feet=dict(...)))")
+        self.stream.synchronize()
+        return ring_rows(self.rollout_feet_traj[b].cpu().numpy(), int(self.cursor[b].item()))
 
     def _start_feedback(self, sp):
         """Queue k_start_feedback behind the track call and in front of the stitch: self.start (and, without a path, self.goal)
