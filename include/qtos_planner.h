@@ -741,7 +741,8 @@ int qtos_rollout_feet(QtosPlanner *p, int B, const QtosRolloutFeet *s, const dou
  * and a status word: bit 0 no stance foot; bit 1 exactly two stance feet (two point feet cannot carry every moment: what remains
  * is the damped least-squares compromise); bit 2 a non-finite input or result -- then f_fit is the plan's force and columns
  * 13 .. 19 are NaN; bit 3 + e the fitted force of stance foot e exceeds the NLP's five force rows by more than excess_tol (the
- * check row's formula of column 23 + e on f_fit).  There are no inequality constraints inside the fit: the excess is measured.
+ * check row's formula of column 23 + e on f_fit).  There are no inequality constraints inside the fit: the excess is measured
+ * (qtos_force_qp below is the fit under those limits).
  * The summary has four QtosCheckRecords per window, the families res_ang (max |13 .. 15|), res_lin (max |16 .. 18|), change
  * (column 19) and excess (the largest positive excess over the stance feet), with qtos_plan_check's semantics: the largest
  * violation, the lowest row that attains it, the rows over tol[family]; non-finite counts as +inf; a window without rows has
@@ -789,6 +790,70 @@ int qtos_force_fit_device(QtosPlanner *p, int B, const QtosForceFit *s, const do
 int qtos_force_fit(QtosPlanner *p, int B, const QtosForceFit *s, const double *nodes, const double *t0, const int *map_id,
                    const int *first_row, const int *n_rows, const long long *cursor, const double *joint, const double *mass_scale,
                    double *rows, int *status, QtosCheckRecord *summary);
+
+/* Force QP: the force fit inside the friction pyramid -- the best wrench the stance feet can deliver without pulling, without
+ * sliding and below the force cap.  For B windows at once (k_force_qp, one workgroup of 128 lanes per window, one lane per row;
+ * the rule, with the order of every operation: force_qp.py).  Per row, with everything up to the fit's M, y and df_fit as
+ * qtos_force_fit forms it, and the NLP's five force rows written as six rows per stance foot with the terrain basis at the foot,
+ *   -n.f <= 0, n.f <= f_max, (t1 - mu n).f <= 0, -(t1 + mu n).f <= 0, (t2 - mu n).f <= 0, -(t2 + mu n).f <= 0    (G_e f_e <= h_e),
+ * the problem in x = (df_e), e in S, c = damping n:
+ *   minimise 1/2 |rho~ - sum_S A~_e df_e|^2 + 1/2 c sum_S |df_e|^2 / w_e   subject to   G_e (f_e + df_e) <= h_e, e in S
+ * whose unconstrained minimiser is the fit.  Where the fit's forces obey every limit row the row is the fit's row (fit path).
+ * Otherwise (limited path) the result is DEFINED as the central point of the barrier problem at the fixed weight mu_end, the
+ * minimiser of the objective - mu_end sum log(h - G f): strictly feasible, a smooth function of the data, suboptimal by at most
+ * 6 n mu_end; it is computed by a feasible-start primal-dual interior-point iteration (Mehrotra steps down to 10 mu_end, then
+ * centering steps; one unpivoted 12 x 12 Cholesky per step) that stops at max |s z - mu_end| <= 1e-10 mu_end and |r_d|inf <=
+ * 1e-9 (1 + |q|inf), or after max_iter steps -- then the row keeps its last iterate, which is feasible, and says so.
+ * A row without a stance foot, a swing foot and a non-finite row behave as in qtos_force_fit.
+ * Outputs per row: qtos_force_fit's 32 columns with f_qp in place of f_fit (13 .. 18 the dynamics rows with f_qp, 19 the size of
+ * f_qp - f, 20 .. 31 tau_ff from f_qp), so a consumer of fit rows takes them as they are; 8 columns of the solve (qrows):
+ *   0 steps taken (0 on the fit path)   1 max |s z - mu_end| / mu_end   2 |r_d|inf [N]   3 the smallest slack over the stance feet [N]
+ *   4 the largest multiplier   5 sqrt(sum |f_qp - f_fit|^2) [N]   6 objective(f_qp) - objective(f_fit) >= 0 [N^2]
+ *   7 the number of limit rows with slack <= act_tol
+ * and a status word: bits 0 .. 2 as qtos_force_fit's; bit 3 + e foot e has a limit row with slack <= act_tol; bit 7 the cap of
+ * max_iter steps was reached; bit 8 the row took the limited path.  The summary has four QtosCheckRecords per window: res_ang,
+ * res_lin and change as qtos_force_fit's, and limited (column 5 of qrows), with qtos_plan_check's semantics and merge; no atomics.
+ * Addressing, the device and host forms and the return codes are qtos_force_fit's; also -1 with the reason in qtos_last_error for
+ * mu, f_max or mu_end not > 0, act_tol not a number, max_iter outside 1 .. 25. */
+#define QTOS_QP_COLS 8
+#define QTOS_QP_MAX_ITER 25
+#define QTOS_QP_NO_STANCE 1          /* status bits of a force-QP row */
+#define QTOS_QP_TWO_STANCE 2
+#define QTOS_QP_NONFINITE 4
+#define QTOS_QP_ACTIVE 8             /* << e: foot e has a limit row with slack <= act_tol */
+#define QTOS_QP_CAP 128
+#define QTOS_QP_LIMITED 256
+typedef struct QtosForceQp {
+  double hz;                    /* QtosForceFit's fields, in its order */
+  int first_row;
+  int n_rows;
+  long long capacity;
+  int flags;                    /* QTOS_FIT_* */
+  double arm;
+  double damping;
+  double w_min;
+  double excess_tol;            /* not read */
+  double tol[4];                /* per family: res_ang, res_lin, change, limited */
+  double hip[4][3];
+  double lateral[4];
+  double l_upper, l_lower;
+  double knee_sign[4];
+  double ee_shift;
+  double mu;                    /* friction coefficient of the pyramid (> 0) */
+  double f_max;                 /* cap of the normal force (> 0) [N] */
+  double mu_end;                /* the barrier weight of the central point (> 0) [N^2] */
+  double act_tol;               /* a limit row counts as active where its slack is <= act_tol [N] */
+  int max_iter;                 /* 1 .. 25 */
+} QtosForceQp;
+int qtos_force_qp_device(QtosPlanner *p, int B, const QtosForceQp *s, const double *d_nodes, const double *d_t0,
+                         const int *d_map_id /* may be NULL */, const int *d_first_row /* may be NULL */,
+                         const int *d_n_rows /* may be NULL */, const long long *d_cursor /* NULL in table mode */,
+                         const double *d_joint /* may be NULL */, const double *d_mass_scale /* may be NULL = 1 */,
+                         double *d_rows /* may be NULL */, double *d_qrows /* may be NULL */, int *d_status /* NULL iff d_rows is NULL */,
+                         QtosCheckRecord *d_summary /* may be NULL */, void *stream);
+int qtos_force_qp(QtosPlanner *p, int B, const QtosForceQp *s, const double *nodes, const double *t0, const int *map_id,
+                  const int *first_row, const int *n_rows, const long long *cursor, const double *joint, const double *mass_scale,
+                  double *rows, double *qrows, int *status, QtosCheckRecord *summary);
 
 /* Goals of receding windows from their global paths: where the next plan goes.  Replaces Global_Planner.update / spine_step
  * (QTOS/planner.py:139-161, 195-230) and Combiner.plan_init / spine_step (QTOS/combiner.py:137-212, 223-225) for B windows at

@@ -17,6 +17,9 @@ CONSTANTS = {
     "QTOS_FEET_LIMIT": 1, "QTOS_ROLLOUT_FEET_COLS": 16,
     "QTOS_ROLLOUT_NO_STANCE": 64, "QTOS_ROLLOUT_TWO_STANCE": 128, "QTOS_ROLLOUT_LIMITED": 256,      # status bits of a feet rollout's row
     "QTOS_FIT_ACCUMULATE": 1, "QTOS_FIT_COLS": 32, "QTOS_FIT_FAMILIES": 4,
+    "QTOS_QP_COLS": 8, "QTOS_QP_MAX_ITER": 25,
+    "QTOS_QP_NO_STANCE": 1, "QTOS_QP_TWO_STANCE": 2, "QTOS_QP_NONFINITE": 4, "QTOS_QP_ACTIVE": 8, "QTOS_QP_CAP": 128,
+    "QTOS_QP_LIMITED": 256,               # status bits of a force-QP row
     "QTOS_ENV_MAX_LEVELS": 64, "QTOS_ENV_MAX_DRAWS": 1 << 24, "QTOS_ENV_LDS_BYTES": 3568,
 }
 globals().update({name[len("QTOS_"):]: value for name, value in CONSTANTS.items()})
@@ -219,6 +222,13 @@ class QtosForceFit(_Struct):
     ]
 
 
+class QtosForceQp(_Struct):
+    """Parameters of a force QP (qtos_force_qp*): QtosForceFit's fields, then the limits'.  force_qp.qp_rows reads the same fields."""
+    _fields_ = QtosForceFit._fields_ + [
+        ("mu", C.c_double), ("f_max", C.c_double), ("mu_end", C.c_double), ("act_tol", C.c_double), ("max_iter", C.c_int),
+    ]
+
+
 def _prototypes():
     """name -> (restype, argtypes) of every entry point, in the header's order.  Host forms take typed pointers, so that a
     numpy array of the wrong dtype is refused here; device forms (and qtos_plan_submit) take c_void_p for every device
@@ -269,6 +279,8 @@ def _prototypes():
         "qtos_rollout_feet_device": f(h, i, P(QtosRolloutFeet), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp),
         "qtos_force_fit":        f(h, i, P(QtosForceFit), dp, dp, ip, ip, ip, qp, dp, dp, dp, ip, vp),   # (summary, as above)
         "qtos_force_fit_device": f(h, i, P(QtosForceFit), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp),
+        "qtos_force_qp":        f(h, i, P(QtosForceQp), dp, dp, ip, ip, ip, qp, dp, dp, dp, dp, ip, vp),
+        "qtos_force_qp_device": f(h, i, P(QtosForceQp), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp),
         "qtos_path_goal":        f(h, i, P(QtosPathGoal), dp, dp, ip, dp, ip, dp, ip, dp, dp, dp, dp, ip),
         "qtos_path_goal_device": f(h, i, P(QtosPathGoal), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp),
         "qtos_path_plan":        f(h, i, P(QtosPathPlan), dp, ip, dp, dp, dp, dp, ip, ip, ip, ip, ip),

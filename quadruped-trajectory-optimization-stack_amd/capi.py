@@ -14,9 +14,9 @@ import numpy as np
 
 from .abi import *  # noqa: F401,F403  (the mirror is part of this module's interface: capi.QtosTrack, capi.TRACK_COLS, capi.EXPORTS ...)
 from .abi import (CHECK_ACCUMULATE, CHECK_COLS, CHECK_FAMILIES, CSV_COLS, FEEDBACK_QUAT, FEEDBACK_SNAP, FEEDBACK_ZERO_FILTER,
-                  FIT_ACCUMULATE, FIT_COLS, FIT_FAMILIES, HIST_COLS, JOINT_NO_FF, MAX_PHASES, NEE, PROTOTYPES, ROLLOUT_COLS,
+                  FIT_ACCUMULATE, FIT_COLS, FIT_FAMILIES, QP_COLS, HIST_COLS, JOINT_NO_FF, MAX_PHASES, NEE, PROTOTYPES, ROLLOUT_COLS,
                   ROLLOUT_FEET_COLS, ROLLOUT_INIT, ROLLOUT_QUAT, ROLLOUT_STATE, START_DOUBLES, TRACK_CLEAN_DELAY, TRACK_COLS, TRACK_QUAT, QtosDims,
-                  QtosForceFit, QtosHandover, QtosJointRows, QtosFeedback, QtosParams, QtosPathGoal, QtosPathPlan, QtosPlanCheck,
+                  QtosForceFit, QtosForceQp, QtosHandover, QtosJointRows, QtosFeedback, QtosParams, QtosPathGoal, QtosPathPlan, QtosPlanCheck,
                   QtosProbe, QtosReport, QtosRollout, QtosRolloutFeet, QtosSelftest, QtosStitch, QtosTerrainEnv, QtosTrack)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -226,6 +226,24 @@ def fit_params(cfg=None, hz=1000.0, first_row=0, n_rows=0, capacity=0, tol=FIT_T
         g.tol[f] = float(v)
     _leg(g, r)
     g.ee_shift = r.ee_shift
+    return g
+
+
+def qp_params(cfg=None, hz=1000.0, first_row=0, n_rows=0, capacity=0, tol=FIT_TOL, accumulate=False, **kw):
+    """A QtosForceQp from force_qp.qp_params(cfg, **kw) -- mu, f_max (None: cfg's friction and force_limit), mu_end, act_tol,
+    max_iter and the fit's arm, damping, w_min, robot, ee_shift, with their defaults and checks (ValueError).  tol: one number for
+    the four families (res_ang N m, res_lin N, change N, limited N) or four.  capacity 0: table mode."""
+    from . import force_qp
+    r = force_qp.qp_params(cfg, **kw)
+    g = QtosForceQp()
+    g.hz, g.first_row, g.n_rows, g.capacity = float(hz), int(first_row), int(n_rows), int(capacity)
+    g.flags = FIT_ACCUMULATE if accumulate else 0
+    g.arm, g.damping, g.w_min, g.excess_tol = r.arm, r.damping, r.w_min, r.excess_tol
+    for f, v in enumerate(np.broadcast_to(np.asarray(tol, np.float64), (FIT_FAMILIES,))):
+        g.tol[f] = float(v)
+    _leg(g, r)
+    g.ee_shift = r.ee_shift
+    g.mu, g.f_max, g.mu_end, g.act_tol, g.max_iter = r.mu, r.f_max, r.mu_end, r.act_tol, r.max_iter
     return g
 
 
@@ -1066,6 +1084,46 @@ class Planner:
         self._chk(self.lib.qtos_force_fit(self.h, B, C.byref(params), _dp(nodes), _dp(t0), _ip(mid), _ip(first), _ip(per), _llp(cur),
                                           _dp(joint), _dp(ms), _dp(rows), _ip(status), _vp(summary)), "force_fit")
         return rows, status, summary
+
+    def force_qp(self, nodes, t0, params, map_id=None, first_row=None, n_rows=None, cursor=None, joint=None, mass_scale=None,
+                 rows=True, qrows=True, status=None, summary=None, stream=None):
+        """The force fit inside the friction pyramid (qtos_force_qp; the rule: force_qp.py).  params: a QtosForceQp (qp_params()).
+        The arguments are force_fit's; returns (rows, qrows, status, summary): rows [B, R, 32], qrows [B, R, 8] the solve's table
+        (True: a new array with rows; an array: written into a copy; False / None: none) and summary [B, 4] records of the families
+        res_ang, res_lin, change, limited.  torch tensors on the device go through the device form on `stream`."""
+        self._need("qtos_force_qp", "force-QP kernel")
+        from . import force_qp as fq
+        if hasattr(nodes, "data_ptr"):
+            import torch
+            st = torch.cuda.current_stream(nodes.device) if stream is None else stream
+            B = nodes.reshape(-1, self.n).shape[0]
+            p = ptr_given
+            self._chk(self.lib.qtos_force_qp_device(self.h, B, C.byref(params), p(nodes), p(t0), p(map_id), p(first_row), p(n_rows),
+                                                    p(cursor), p(joint), p(mass_scale), p(rows), p(qrows), p(status), p(summary),
+                                                    C.c_void_p(st.cuda_stream)), "force_qp_device")
+            return (rows if p(rows) else None), (qrows if p(qrows) else None), (status if p(status) else None), (summary if p(summary) else None)
+        nodes, B = self._nodes(nodes)
+        t0 = _bcast(t0, B)
+        mid, first, per = _bcast(map_id, B, np.int32), _bcast(first_row, B, np.int32), _bcast(n_rows, B, np.int32)
+        keep = not (rows is False or rows is None)
+        nr, cur = _segment(params, B, cursor, *((rows, status) if keep and params.capacity > 0 else ()))
+        nr = max(nr, 0)
+        joint = None if joint is None else np.ascontiguousarray(joint, np.float64)
+        if joint is not None and joint.shape != (B, nr, CSV_COLS):
+            raise ValueError("joint is (B, %d, %d)" % (nr, CSV_COLS))
+        ms = _bcast(mass_scale, B)
+        rows = _table(rows, (B, nr, FIT_COLS))
+        if rows is None:
+            status = qrows = None
+        else:
+            status = np.zeros((B, nr), np.int32) if status is None else np.array(status, np.int32)
+            qrows = _table(qrows, (B, nr, QP_COLS))
+            if rows.shape != (B, nr, FIT_COLS) or status.shape != (B, nr) or (qrows is not None and qrows.shape != (B, nr, QP_COLS)):
+                raise ValueError("rows is (B, %d, %d), qrows (B, %d, %d) and status (B, %d)" % (nr, FIT_COLS, nr, QP_COLS, nr))
+        summary = _summary(summary, rows, fq, B, FIT_FAMILIES)
+        self._chk(self.lib.qtos_force_qp(self.h, B, C.byref(params), _dp(nodes), _dp(t0), _ip(mid), _ip(first), _ip(per), _llp(cur),
+                                         _dp(joint), _dp(ms), _dp(rows), _dp(qrows), _ip(status), _vp(summary)), "force_qp")
+        return rows, qrows, status, summary
 
     def path_goal(self, table, clock, params, path_id=None, map_yx=None, map_id=None, offset=None, start=None, done=None):
         """Goals of the windows' next plans from their global paths (qtos_path_goal, host form; the rule:

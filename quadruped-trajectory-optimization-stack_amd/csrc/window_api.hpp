@@ -683,6 +683,69 @@ int qtos_force_fit(QtosPlanner *p, int B, const QtosForceFit *s, const double *n
   return rc ? rc : S.download();
 }
 
+// ---- the force fit inside the friction pyramid (k_force_qp, window_kernels.hpp) -----------------------------------
+// QtosForceQp begins with QtosForceFit's fields in its order, so the fit's checks and FitArgs are force_fit_args' on that part.
+static int force_qp_args(QtosPlanner *p, int B, const QtosForceQp *s, const void *nodes, const void *t0, const void *cursor,
+                         const void *rows, const void *qrows, const void *status, const void *summary, FitArgs *A, QpArgs *Q) {
+  if (!p) return -1;
+  static_assert(offsetof(QtosForceQp, mu) == sizeof(QtosForceFit), "QtosForceQp repeats QtosForceFit's layout");
+  QtosForceFit fit;
+  if (s) memcpy(&fit, s, sizeof fit);
+  const char *why = nullptr;
+  if (force_fit_args(p, B, s ? &fit : nullptr, nodes, t0, cursor, rows, status, summary, A)) {
+    p->err.replace(0, strlen("qtos_force_fit"), "qtos_force_qp");
+    return -1;
+  }
+  if (qrows && !rows) why = "qrows go with rows";
+  else if (!(s->mu > 0) || !(s->mu <= 1.7976931348623157e308)) why = "mu is > 0";
+  else if (!(s->f_max > 0) || !(s->f_max <= 1.7976931348623157e308)) why = "f_max is > 0";
+  else if (!(s->mu_end > 0) || !(s->mu_end <= 1.7976931348623157e308)) why = "mu_end is > 0";
+  else if (s->act_tol != s->act_tol) why = "act_tol is not a number";
+  else if (s->max_iter < 1 || s->max_iter > QP_MAX_ITER) why = "max_iter is 1 .. 25";
+  if (why) {
+    p->err = std::string("qtos_force_qp: ") + why;
+    return -1;
+  }
+  A->mu = s->mu; A->f_max = s->f_max;
+  Q->mu = s->mu; Q->f_max = s->f_max; Q->mu_end = s->mu_end; Q->act_tol = s->act_tol; Q->max_iter = s->max_iter;
+  return 0;
+}
+
+int qtos_force_qp_device(QtosPlanner *p, int B, const QtosForceQp *s, const double *d_nodes, const double *d_t0, const int *d_map_id,
+                         const int *d_first_row, const int *d_n_rows, const long long *d_cursor, const double *d_joint,
+                         const double *d_mass_scale, double *d_rows, double *d_qrows, int *d_status, QtosCheckRecord *d_summary,
+                         void *stream_) {
+  FitArgs A;
+  QpArgs Q;
+  if (force_qp_args(p, B, s, d_nodes, d_t0, d_cursor, d_rows, d_qrows, d_status, d_summary, &A, &Q)) return -1;
+  HIPCHK(p, hipSetDevice(p->device));
+  hipLaunchKernelGGL(k_force_qp, dim3(B), dim3(QP_TILE), 0, (hipStream_t)stream_, p->d_sp, A, Q, d_nodes, d_t0, d_map_id, d_first_row,
+                     d_n_rows, d_cursor, d_joint, d_mass_scale, d_rows, d_qrows, d_status, (CheckRecord *)d_summary, B);
+  HIPCHK(p, hipGetLastError());
+  return 0;
+}
+
+int qtos_force_qp(QtosPlanner *p, int B, const QtosForceQp *s, const double *nodes, const double *t0, const int *map_id,
+                  const int *first_row, const int *n_rows, const long long *cursor, const double *joint, const double *mass_scale,
+                  double *rows, double *qrows, int *status, QtosCheckRecord *summary) {
+  FitArgs A;
+  QpArgs Q;
+  if (force_qp_args(p, B, s, nodes, t0, cursor, rows, qrows, status, summary, &A, &Q)) return -1;
+  HIPCHK(p, hipSetDevice(p->device));
+  const size_t nr = segment_elems(B, A.capacity, A.n_rows);
+  Staging S(p);
+  const double *d_nodes = S.in(nodes, (size_t)B * p->M.n_vars), *d_t0 = S.in(t0, B);
+  const int *d_map = S.in(map_id, B), *d_first = S.in(first_row, B), *d_n = S.in(n_rows, B);
+  const long long *d_cur = S.in(cursor, B);
+  const double *d_joint = S.in(joint, nr * QTOS_CSV_COLS), *d_ms = S.in(mass_scale, B);
+  double *d_rows = S.inout(rows, nr * FIT_COLS), *d_qrows = S.inout(qrows, nr * QP_COLS);
+  int *d_st = S.inout(status, nr);
+  QtosCheckRecord *d_sum = S.inout(summary, (size_t)B * FIT_FAMILIES);
+  if (S.rc) return S.rc;
+  const int rc = qtos_force_qp_device(p, B, s, d_nodes, d_t0, d_map, d_first, d_n, d_cur, d_joint, d_ms, d_rows, d_qrows, d_st, d_sum, nullptr);
+  return rc ? rc : S.download();
+}
+
 // ---- goals of receding windows from their global paths (k_path_goal, window_kernels.hpp) ------------------------
 // The argument checks of both forms, and QtosPathGoal as k_path_goal reads it.
 static int path_goal_args(const QtosPlanner *p, int B, const QtosPathGoal *g, const void *knots, const void *coef, const void *n_pieces,

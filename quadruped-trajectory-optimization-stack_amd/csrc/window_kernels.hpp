@@ -11,6 +11,7 @@
 //   k_plan_check    : what the windows' plans violate between their knots
 //   k_rollout       : the windows' robots as simulated rigid bodies (the measured states k_track reads)
 //   k_force_fit     : the rows' contact forces fitted to the planned motion (k_plan_check's pieces and a 6 x 6 solve per row)
+//   k_force_qp      : that fit inside the friction pyramid (k_force_fit's pieces and an interior-point solve per limited row)
 //   k_path_goal     : goals of the windows from their global paths
 //   k_path_plan     : the global paths (A* and spines)
 //   k_probe*        : the probe and the stamp of the windows' heightfields
@@ -1521,6 +1522,615 @@ __global__ __launch_bounds__(FIT_TILE) void k_force_fit(const SamplePlan *Sd, Fi
   }
   if (summary && threadIdx.x == 0) {
     if (A.accumulate && n == 0) return;                                              // nothing to merge
+#pragma unroll
+    for (int f = 0; f < FIT_FAMILIES; ++f) {
+      CheckRecord rec = {run_max[f], run_row[f], run_cnt[f]};
+      CheckRecord *dst = summary + (size_t)b * FIT_FAMILIES + f;
+      if (A.accumulate) {
+        const CheckRecord old = *dst;
+        if (!(rec.max > old.max)) { rec.max = old.max; rec.row = old.row; }
+        rec.count += old.count;
+      }
+      *dst = rec;
+    }
+  }
+}
+
+// Force QP (qtos_force_qp*): the force fit inside the friction pyramid.  The statement of the rule is force_qp.py, with the order
+// of every operation; this kernel runs that order with contraction off (qp_* below; the row's plan side is k_force_fit's device
+// functions, one copy of each, with fit_solve<FitExact>).  A row whose fitted forces obey the six limit rows of every stance foot
+// is the fit's row; any other is the central point of the barrier problem at mu_end, by a feasible-start primal-dual iteration
+// of at most 25 steps, each with one unpivoted 12 x 12 Cholesky.  One workgroup of QP_TILE = 128 lanes per window, one lane per
+// row, k_force_fit's three phases.  What a lane carries through the iteration -- x, s, z, the feet's bases, lever arms, forces
+// and weights, about 200 doubles -- stays in registers (constant indices: the loops over feet and limit rows are unrolled); the
+// 78 entries of K and the 12 of the solves' vector live in a per-lane LDS slab, entry k of lane l at k * QP_TILE + l: consecutive
+// lanes on consecutive doubles, so a wave's access to one entry is conflict-free, and the factorisation's loops stay rolled with
+// run-time indices, which registers cannot take.  Every loop has a fixed bound; a NaN fails every comparison and runs into the
+// cap; nothing spins on memory.  The lanes of a wave whose rows took the fit path wait for those that did not.
+constexpr int QP_COLS = 8, QP_PITCH = 9, QP_TILE = 128, QP_SLAB = 90, QP_MAX_ITER = 25;
+constexpr double QP_CTOL = 1e-10, QP_RTOL = 1e-9;                                     // force_qp.CTOL, RTOL
+struct QpArgs { double mu, f_max, mu_end, act_tol; int max_iter; };
+struct QpFoot {        // one foot of a row as the iteration reads it
+  double d[3], w, f[3], B[3][3];
+  bool on;
+};
+__device__ constexpr int qp_ix(int i, int j) { return i * (i + 1) / 2 + j; }
+
+__device__ inline double qp_dot(const double u[3], const double v[3]) {
+#pragma clang fp contract(off)
+  return (u[0] * v[0] + u[1] * v[1]) + u[2] * v[2];
+}
+__device__ inline void qp_basis(double hx, double hy, double B[3][3]) {
+#pragma clang fp contract(off)
+  const double v[3][3] = {{-hx, -hy, 1.0}, {1.0, 0.0, hx}, {0.0, 1.0, hy}};
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const double nn = sqrt((v[a][0] * v[a][0] + v[a][1] * v[a][1]) + v[a][2] * v[a][2]);
+    B[a][0] = v[a][0] / nn; B[a][1] = v[a][1] / nn; B[a][2] = v[a][2] / nn;
+  }
+}
+__device__ inline void qp_gmul(const double B[3][3], double mu, const double v[3], double out[6]) {
+#pragma clang fp contract(off)
+  const double a = qp_dot(B[0], v), b = qp_dot(B[1], v), c2 = qp_dot(B[2], v), ma = mu * a;
+  out[0] = -a; out[1] = a; out[2] = b - ma; out[3] = -(b + ma); out[4] = c2 - ma; out[5] = -(c2 + ma);
+}
+__device__ inline void qp_gtmul(const double B[3][3], double mu, const double y[6], double out[3]) {
+#pragma clang fp contract(off)
+  const double al = (y[1] - y[0]) - mu * (((y[2] + y[3]) + y[4]) + y[5]), be = y[2] - y[3], ga = y[4] - y[5];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) out[i] = (B[0][i] * al + B[1][i] * be) + B[2][i] * ga;
+}
+// grad_e = (c / w_e) x_e - ((r~_ang x d_e) + r~_lin), r~ = rho~ - sum_S (d_e x x_e, x_e); 0 for a swing foot.
+__device__ inline void qp_grad(const QpFoot Ft[NEE], const double rho[6], double c, const double x[NEE][3], double g[NEE][3]) {
+#pragma clang fp contract(off)
+  double r[6] = {rho[0], rho[1], rho[2], rho[3], rho[4], rho[5]};
+#pragma unroll
+  for (int e = 0; e < NEE; ++e)
+    if (Ft[e].on) {
+      const double *d = Ft[e].d, *v = x[e];
+      r[0] = r[0] - (d[1] * v[2] - d[2] * v[1]);
+      r[1] = r[1] - (d[2] * v[0] - d[0] * v[2]);
+      r[2] = r[2] - (d[0] * v[1] - d[1] * v[0]);
+      r[3] = r[3] - v[0]; r[4] = r[4] - v[1]; r[5] = r[5] - v[2];
+    }
+#pragma unroll
+  for (int e = 0; e < NEE; ++e) {
+    g[e][0] = 0; g[e][1] = 0; g[e][2] = 0;
+    if (Ft[e].on) {
+      const double *d = Ft[e].d;
+      const double cw = c / Ft[e].w;
+      g[e][0] = cw * x[e][0] - ((r[1] * d[2] - r[2] * d[1]) + r[3]);
+      g[e][1] = cw * x[e][1] - ((r[2] * d[0] - r[0] * d[2]) + r[4]);
+      g[e][2] = cw * x[e][2] - ((r[0] * d[1] - r[1] * d[0]) + r[5]);
+    }
+  }
+}
+// K = H + G^T diag(z / s) G into the lane's slab (the lower triangle, row by row), then its unpivoted Cholesky in place.
+__device__ inline void qp_factor(const QpFoot Ft[NEE], double c, double mu, const double s[NEE][6], const double z[NEE][6], double *K) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int e = 0; e < NEE; ++e) {
+    double blk[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+    if (Ft[e].on) {
+      double D[6];
+#pragma unroll
+      for (int r = 0; r < 6; ++r) D[r] = z[e][r] / s[e][r];
+      const double S = ((D[2] + D[3]) + D[4]) + D[5];
+      const double cnn = (D[0] + D[1]) + (mu * mu) * S, cn1 = mu * (D[3] - D[2]), cn2 = mu * (D[5] - D[4]), c11 = D[2] + D[3], c22 = D[4] + D[5];
+      const double(*B)[3] = Ft[e].B;
+      double Tn[3], T1[3], T2[3];
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        Tn[j] = (cnn * B[0][j] + cn1 * B[1][j]) + cn2 * B[2][j];
+        T1[j] = cn1 * B[0][j] + c11 * B[1][j];
+        T2[j] = cn2 * B[0][j] + c22 * B[2][j];
+      }
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j <= i; ++j) blk[i][j] = (B[0][i] * Tn[j] + B[1][i] * T1[j]) + B[2][i] * T2[j];
+    }
+#pragma unroll
+    for (int e2 = 0; e2 <= e; ++e2) {
+      const bool both = Ft[e].on && Ft[e2].on;
+      const double dd = qp_dot(Ft[e].d, Ft[e2].d);
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+          if (e == e2 && j > i) continue;
+          double v = -(Ft[e2].d[i] * Ft[e].d[j]);
+          if (i == j) {
+            v = (dd + 1.0) - Ft[e2].d[i] * Ft[e].d[j];
+            if (e == e2) v = v + c / Ft[e].w;
+          }
+          double k = both ? v : (e == e2 && i == j ? 1.0 : 0.0);
+          if (e == e2 && Ft[e].on) k = k + blk[i][j];
+          K[qp_ix(3 * e + i, 3 * e2 + j) * QP_TILE] = k;
+        }
+    }
+  }
+  for (int j = 0; j < 12; ++j) {
+    double acc = K[qp_ix(j, j) * QP_TILE];
+    for (int k = 0; k < j; ++k) {
+      const double l = K[qp_ix(j, k) * QP_TILE];
+      acc = acc - l * l;
+    }
+    const double ljj = sqrt(acc);
+    K[qp_ix(j, j) * QP_TILE] = ljj;
+    for (int i = j + 1; i < 12; ++i) {
+      double a = K[qp_ix(i, j) * QP_TILE];
+      for (int k = 0; k < j; ++k) a = a - K[qp_ix(i, k) * QP_TILE] * K[qp_ix(j, k) * QP_TILE];
+      K[qp_ix(i, j) * QP_TILE] = a / ljj;
+    }
+  }
+}
+// v = K^-1 v with the factor in the slab: v is the slab's entries 78 .. 89, in place.
+__device__ inline void qp_backsolve(double *K, double v[NEE][3]) {
+#pragma clang fp contract(off)
+  double *V = K + 78 * QP_TILE;
+#pragma unroll
+  for (int e = 0; e < NEE; ++e)
+#pragma unroll
+    for (int i = 0; i < 3; ++i) V[(3 * e + i) * QP_TILE] = v[e][i];
+  for (int i = 0; i < 12; ++i) {
+    double acc = V[i * QP_TILE];
+    for (int k = 0; k < i; ++k) acc = acc - K[qp_ix(i, k) * QP_TILE] * V[k * QP_TILE];
+    V[i * QP_TILE] = acc / K[qp_ix(i, i) * QP_TILE];
+  }
+  for (int i = 11; i >= 0; --i) {
+    double acc = V[i * QP_TILE];
+    for (int k = i + 1; k < 12; ++k) acc = acc - K[qp_ix(k, i) * QP_TILE] * V[k * QP_TILE];
+    V[i * QP_TILE] = acc / K[qp_ix(i, i) * QP_TILE];
+  }
+#pragma unroll
+  for (int e = 0; e < NEE; ++e)
+#pragma unroll
+    for (int i = 0; i < 3; ++i) v[e][i] = V[(3 * e + i) * QP_TILE];
+}
+// Foot e's six rows of a step dx: ds = -G dx, dz = t - (z / s) ds (t = -z for the predictor, rc / s for the combined step).
+__device__ inline void qp_foot_step(const QpFoot &F, double mu, const double dx[3], const double s[6], const double z[6], const double t[6],
+                                    double ds[6], double dz[6]) {
+#pragma clang fp contract(off)
+  double gd[6];
+  qp_gmul(F.B, mu, dx, gd);
+#pragma unroll
+  for (int r = 0; r < 6; ++r) {
+    ds[r] = -gd[r];
+    dz[r] = t[r] - (z[r] / s[r]) * ds[r];
+  }
+}
+// The limited path of a row (force_qp.solve_rows): x, s, z of the last iterate, the residuals it stopped at; returns the steps.
+__device__ inline int qp_solve(const QpFoot Ft[NEE], const double rho[6], double c, double m, const QpArgs &Q, const double xfit[NEE][3],
+                               double *K, double x[NEE][3], double s[NEE][6], double z[NEE][6], double &comp, double &rdn, bool &cap) {
+#pragma clang fp contract(off)
+  const double mu = Q.mu, mu_end = Q.mu_end, inf = INFINITY;
+  const double gam_lo = fmin(1.0, Q.f_max / 4.0), gam_hi = Q.f_max / 2.0;
+  {                                                                                   // the start
+    double xi[NEE][3], si[NEE][6], ratio = inf;
+#pragma unroll
+    for (int e = 0; e < NEE; ++e) {
+      xi[e][0] = 0; xi[e][1] = 0; xi[e][2] = 0;
+      if (Ft[e].on) {
+        const double gam = fmin(fmax(qp_dot(Ft[e].B[0], Ft[e].f), gam_lo), gam_hi);
+        double tmp[3], dir[3], gv[6], gd[6];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          xi[e][i] = Ft[e].B[0][i] * gam - Ft[e].f[i];
+          tmp[i] = Ft[e].f[i] + xi[e][i];
+          dir[i] = xfit[e][i] - xi[e][i];
+        }
+        qp_gmul(Ft[e].B, mu, tmp, gv);
+        qp_gmul(Ft[e].B, mu, dir, gd);
+#pragma unroll
+        for (int r = 0; r < 6; ++r) {
+          si[e][r] = (r == 1 ? Q.f_max : 0.0) - gv[r];
+          if (-gd[r] < 0) ratio = fmin(ratio, si[e][r] / gd[r]);
+        }
+      }
+    }
+    const double theta = fmin(1.0, 0.9 * ratio);
+#pragma unroll
+    for (int e = 0; e < NEE; ++e) {
+#pragma unroll
+      for (int r = 0; r < 6; ++r) { s[e][r] = 1.0; z[e][r] = 1.0; }
+      x[e][0] = 0; x[e][1] = 0; x[e][2] = 0;
+      if (Ft[e].on) {
+        double tmp[3], gv[6];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          x[e][i] = xi[e][i] + theta * (xfit[e][i] - xi[e][i]);
+          tmp[i] = Ft[e].f[i] + x[e][i];
+        }
+        qp_gmul(Ft[e].B, mu, tmp, gv);
+#pragma unroll
+        for (int r = 0; r < 6; ++r) {
+          s[e][r] = (r == 1 ? Q.f_max : 0.0) - gv[r];
+          z[e][r] = 1.0 / s[e][r];
+        }
+      }
+    }
+  }
+  double qinf = 0;
+  {
+    const double x0[NEE][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+    double q[NEE][3];
+    qp_grad(Ft, rho, c, x0, q);
+#pragma unroll
+    for (int e = 0; e < NEE; ++e) qinf = fmax(qinf, fmax(fmax(fabs(q[e][0]), fabs(q[e][1])), fabs(q[e][2])));
+  }
+  const int max_iter = Q.max_iter < QP_MAX_ITER ? Q.max_iter : QP_MAX_ITER;
+  int steps = 0;
+  cap = false;
+  for (int it = 0; it <= QP_MAX_ITER; ++it) {
+    double grad[NEE][3], rd[NEE][3], acc = 0, comp_now = 0, rd_now = 0;
+    qp_grad(Ft, rho, c, x, grad);
+#pragma unroll
+    for (int e = 0; e < NEE; ++e) {
+      rd[e][0] = 0; rd[e][1] = 0; rd[e][2] = 0;
+      if (Ft[e].on) {
+        double gt[3];
+        qp_gtmul(Ft[e].B, mu, z[e], gt);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          rd[e][i] = grad[e][i] + gt[i];
+          rd_now = fmax(rd_now, fabs(rd[e][i]));
+        }
+#pragma unroll
+        for (int r = 0; r < 6; ++r) {
+          const double sz = s[e][r] * z[e][r];
+          acc = acc + sz;
+          comp_now = fmax(comp_now, fabs(sz - mu_end));
+        }
+      }
+    }
+    comp_now = comp_now / mu_end;
+    const double muk = acc / m;
+    comp = comp_now; rdn = rd_now;
+    if (comp_now <= QP_CTOL && rd_now <= QP_RTOL * (1.0 + qinf)) break;
+    if (it >= max_iter) { cap = true; break; }
+    qp_factor(Ft, c, mu, s, z, K);
+    double t[NEE][6], dx[NEE][3];
+    double target = mu_end;
+    const bool pred = muk > 10.0 * mu_end;
+    if (pred) {                                                                       // the predictor and the corrector's target
+#pragma unroll
+      for (int e = 0; e < NEE; ++e)
+#pragma unroll
+        for (int i = 0; i < 3; ++i) dx[e][i] = -grad[e][i];
+      qp_backsolve(K, dx);
+      double rs = inf, rz = inf;
+#pragma unroll
+      for (int e = 0; e < NEE; ++e)
+        if (Ft[e].on) {
+          double ta[6], ds[6], dz[6];
+#pragma unroll
+          for (int r = 0; r < 6; ++r) ta[r] = -z[e][r];
+          qp_foot_step(Ft[e], mu, dx[e], s[e], z[e], ta, ds, dz);
+#pragma unroll
+          for (int r = 0; r < 6; ++r) {
+            if (ds[r] < 0) rs = fmin(rs, s[e][r] / -ds[r]);
+            if (dz[r] < 0) rz = fmin(rz, z[e][r] / -dz[r]);
+            t[e][r] = ds[r] * dz[r];                                                  // (the corrector's term, kept for rc below)
+          }
+        }
+      const double ala = fmin(1.0, fmin(rs, rz));
+      double acc_a = 0;
+#pragma unroll
+      for (int e = 0; e < NEE; ++e)
+        if (Ft[e].on) {
+          double ta[6], ds[6], dz[6];
+#pragma unroll
+          for (int r = 0; r < 6; ++r) ta[r] = -z[e][r];
+          qp_foot_step(Ft[e], mu, dx[e], s[e], z[e], ta, ds, dz);
+#pragma unroll
+          for (int r = 0; r < 6; ++r) acc_a = acc_a + (s[e][r] + ala * ds[r]) * (z[e][r] + ala * dz[r]);
+        }
+      const double ratio = (acc_a / m) / muk;
+      target = fmax(((ratio * ratio) * ratio) * muk, mu_end);
+    }
+#pragma unroll
+    for (int e = 0; e < NEE; ++e) {
+      dx[e][0] = -0.0; dx[e][1] = -0.0; dx[e][2] = -0.0;
+      if (Ft[e].on) {
+        double gt[3];
+#pragma unroll
+        for (int r = 0; r < 6; ++r) {
+          double rc = target - s[e][r] * z[e][r];
+          if (pred) rc = rc - t[e][r];
+          t[e][r] = rc / s[e][r];
+        }
+        qp_gtmul(Ft[e].B, mu, t[e], gt);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) dx[e][i] = -(rd[e][i] + gt[i]);
+      }
+    }
+    qp_backsolve(K, dx);
+    double rs = inf, rz = inf;
+#pragma unroll
+    for (int e = 0; e < NEE; ++e)
+      if (Ft[e].on) {
+        double ds[6], dz[6];
+        qp_foot_step(Ft[e], mu, dx[e], s[e], z[e], t[e], ds, dz);
+#pragma unroll
+        for (int r = 0; r < 6; ++r) {
+          if (ds[r] < 0) rs = fmin(rs, s[e][r] / -ds[r]);
+          if (dz[r] < 0) rz = fmin(rz, z[e][r] / -dz[r]);
+        }
+      }
+    const double al = fmin(1.0, 0.99 * fmin(rs, rz));
+#pragma unroll
+    for (int e = 0; e < NEE; ++e)
+      if (Ft[e].on) {
+        double ds[6], dz[6];
+        qp_foot_step(Ft[e], mu, dx[e], s[e], z[e], t[e], ds, dz);
+#pragma unroll
+        for (int r = 0; r < 6; ++r) {
+          s[e][r] = s[e][r] + al * ds[r];
+          z[e][r] = z[e][r] + al * dz[r];
+        }
+#pragma unroll
+        for (int i = 0; i < 3; ++i) x[e][i] = x[e][i] + al * dx[e][i];
+      }
+    ++steps;
+  }
+  return steps;
+}
+// objective(x) - objective(x_fit) as force_qp.objective_gap forms it, and |x - x_fit|^2 into dsq.
+__device__ inline double qp_gap(const QpFoot Ft[NEE], const double rho[6], double c, const double xfit[NEE][3], const double x[NEE][3], double &dsq) {
+#pragma clang fp contract(off)
+  double g[NEE][3], AD[6] = {0, 0, 0, 0, 0, 0}, lin = 0, quad = 0;
+  qp_grad(Ft, rho, c, xfit, g);
+  dsq = 0;
+#pragma unroll
+  for (int e = 0; e < NEE; ++e)
+    if (Ft[e].on) {
+      const double D[3] = {x[e][0] - xfit[e][0], x[e][1] - xfit[e][1], x[e][2] - xfit[e][2]};
+      const double *d = Ft[e].d;
+      AD[0] = AD[0] + (d[1] * D[2] - d[2] * D[1]);
+      AD[1] = AD[1] + (d[2] * D[0] - d[0] * D[2]);
+      AD[2] = AD[2] + (d[0] * D[1] - d[1] * D[0]);
+      AD[3] = AD[3] + D[0]; AD[4] = AD[4] + D[1]; AD[5] = AD[5] + D[2];
+      lin = lin + qp_dot(g[e], D);
+      const double dd = qp_dot(D, D);
+      quad = quad + (c / Ft[e].w) * dd;
+      dsq = dsq + dd;
+    }
+  const double sq = ((((AD[0] * AD[0] + AD[1] * AD[1]) + AD[2] * AD[2]) + AD[3] * AD[3]) + AD[4] * AD[4]) + AD[5] * AD[5];
+  return lin + 0.5 * (sq + quad);
+}
+// A stance foot's df = x_e taken off the residual rows and added to the squared change (fit_foot_correct's lines, one rounded
+// operation each, as force_qp.py forms them).
+__device__ inline void qp_foot_residual(FitFoot &F, const double xe[3], double ra[3], double rl[3], double &sq) {
+#pragma clang fp contract(off)
+  if (!F.stance) return;
+  F.df[0] = xe[0]; F.df[1] = xe[1]; F.df[2] = xe[2];
+  ra[0] = ra[0] - (F.p[1] * xe[2] - F.p[2] * xe[1]);
+  ra[1] = ra[1] - (F.p[2] * xe[0] - F.p[0] * xe[2]);
+  ra[2] = ra[2] - (F.p[0] * xe[1] - F.p[1] * xe[0]);
+  rl[0] = rl[0] - xe[0]; rl[1] = rl[1] - xe[1]; rl[2] = rl[2] - xe[2];
+  sq = sq + ((xe[0] * xe[0] + xe[1] * xe[1]) + xe[2] * xe[2]);
+}
+__device__ inline void qp_foot_of(const FitFoot &F, double arm, QpFoot &Q, double xfit[3]) {
+#pragma clang fp contract(off)
+  Q.on = F.stance;
+  Q.w = F.w;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) { Q.d[i] = F.p[i] / arm; Q.f[i] = F.f[i]; xfit[i] = F.stance ? F.df[i] : 0.0; }
+  qp_basis(F.hx, F.hy, Q.B);
+}
+
+__global__ __launch_bounds__(QP_TILE) void k_force_qp(const SamplePlan *Sd, FitArgs A, QpArgs Q, const double *nodes, const double *t0,
+                                                      const int *map_id, const int *first_row, const int *n_rows, const long long *cursor,
+                                                      const double *joint, const double *mass_scale, double *rows_out, double *qrows_out,
+                                                      int *status_out, CheckRecord *summary, int B) {
+  __shared__ double qp_slab[QP_SLAB * QP_TILE];
+  __shared__ double qp_tile[QP_TILE * FIT_PITCH];
+  __shared__ double qp_qtile[QP_TILE * QP_PITCH];
+  __shared__ double qp_red[QP_TILE];
+  const int b = blockIdx.x;
+  if (b >= B) return;
+  const SamplePlan &S = *Sd;
+  const RowSegment G = RowSegment::of(A.capacity, A.n_rows, A.first_row, n_rows, first_row, cursor, b);
+  const long long n = G.n, rows_b = G.rows_b;
+  const long long row0 = A.capacity > 0 ? cursor[b] : G.first;                       // what the summary counts its rows from
+  const int map = map_id ? map_id[b] : 0;
+  const double *x = nodes + (size_t)b * S.n_vars;
+  const double t0b = t0[b];
+  const double ms = mass_scale ? mass_scale[b] : 1.0;
+  const double m_s = A.mass * ms;
+  double *out_b = rows_out ? rows_out + (size_t)b * (size_t)rows_b * FIT_COLS : nullptr;
+  double *qout_b = qrows_out ? qrows_out + (size_t)b * (size_t)rows_b * QP_COLS : nullptr;
+  const double *joint_b = joint ? joint + (size_t)b * (size_t)rows_b * QTOS_CSV_COLS : nullptr;
+  double run_max[FIT_FAMILIES];
+  long long run_row[FIT_FAMILIES], run_cnt[FIT_FAMILIES];
+#pragma unroll
+  for (int f = 0; f < FIT_FAMILIES; ++f) { run_max[f] = -INFINITY; run_row[f] = -1; run_cnt[f] = 0; }
+  for (long long j0 = 0; j0 < n; j0 += QP_TILE) {                                    // (n is uniform over the workgroup: so are the barriers)
+    const int m = G.tile_rows(j0, QP_TILE);
+    const long long base = G.row(j0);
+    double v[FIT_FAMILIES];
+#pragma unroll
+    for (int f = 0; f < FIT_FAMILIES; ++f) v[f] = -INFINITY;
+    if ((int)threadIdx.x < m) {                                                      // (A) a lane takes a row: k_force_fit's lines up to the fit
+      const int k = G.plan_row(j0, threadIdx.x);
+      double t = k / A.hz;
+      if (t > S.T) t = S.T;
+      double *dst = qp_tile + threadIdx.x * FIT_PITCH;
+      double *qdst = qp_qtile + threadIdx.x * QP_PITCH;
+      dst[0] = t0b + k / A.hz;
+      double r[3], a[3], th[3], thd[3], thdd[3], ga[3], gl[3], R[9], Ib[9];
+      sample_spline(S.lin, x, t, 0, r);
+      sample_spline_acc(S.lin, x, t, a);
+      sample_spline(S.ang, x, t, 0, th);
+      sample_spline(S.ang, x, t, 1, thd);
+      sample_spline_acc(S.ang, x, t, thdd);
+      const Trig tg = trig_of(th);
+#pragma unroll
+      for (int i = 0; i < 9; ++i) Ib[i] = ms * A.Ib[i];
+      dyn_angular<double>(Ib, th, thd, thdd, tg, ga);
+      rotation<double>(th, tg, R);
+      gl[0] = m_s * a[0]; gl[1] = m_s * a[1]; gl[2] = m_s * a[2] + m_s * A.gravity;
+      FitFoot F0, F1, F2, F3;
+      fit_foot_load<0>(S, A, x, t, map, r, ga, gl, F0);
+      fit_foot_load<1>(S, A, x, t, map, r, ga, gl, F1);
+      fit_foot_load<2>(S, A, x, t, map, r, ga, gl, F2);
+      fit_foot_load<3>(S, A, x, t, map, r, ga, gl, F3);
+      const int cnt = (int)F0.stance + (int)F1.stance + (int)F2.stance + (int)F3.stance;
+      const double nn = (double)cnt, gsum = ((F0.w + F1.w) + F2.w) + F3.w;
+      const bool loaded = gsum > 0;
+      F0.w = loaded ? fmax(nn * F0.w / gsum, A.w_min) : 1.0;
+      F1.w = loaded ? fmax(nn * F1.w / gsum, A.w_min) : 1.0;
+      F2.w = loaded ? fmax(nn * F2.w / gsum, A.w_min) : 1.0;
+      F3.w = loaded ? fmax(nn * F3.w / gsum, A.w_min) : 1.0;
+      const double rho_w[6] = {ga[0], ga[1], ga[2], gl[0], gl[1], gl[2]};            // the plan's own dynamics rows
+      const double rho[6] = {ga[0] / A.arm, ga[1] / A.arm, ga[2] / A.arm, gl[0], gl[1], gl[2]};
+      double y[6] = {0, 0, 0, 0, 0, 0}, sq = 0;
+      if (cnt > 0) {
+        FitSums Qs = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        fit_foot_sums(F0, A.arm, Qs);
+        fit_foot_sums(F1, A.arm, Qs);
+        fit_foot_sums(F2, A.arm, Qs);
+        fit_foot_sums(F3, A.arm, Qs);
+        const double lam = A.damping * nn, wl = Qs.W + lam;
+        double M[21] = {(Qs.q11 + Qs.q22) + lam,
+                        -Qs.q01, (Qs.q00 + Qs.q22) + lam,
+                        -Qs.q02, -Qs.q12, (Qs.q00 + Qs.q11) + lam,
+                        0.0, Qs.s2, -Qs.s1, wl,
+                        -Qs.s2, 0.0, Qs.s0, 0.0, wl,
+                        Qs.s1, -Qs.s0, 0.0, 0.0, 0.0, wl};
+        fit_solve<FitExact>(M, rho, y);
+      }
+      fit_foot_correct(F0, A.arm, y, ga, gl, sq);
+      fit_foot_correct(F1, A.arm, y, ga, gl, sq);
+      fit_foot_correct(F2, A.arm, y, ga, gl, sq);
+      fit_foot_correct(F3, A.arm, y, ga, gl, sq);
+      double change = sqrt(sq);
+      bool fin = isfinite(ga[0]) && isfinite(ga[1]) && isfinite(ga[2]) && isfinite(gl[0]) && isfinite(gl[1]) && isfinite(gl[2]) &&
+                 isfinite(change);
+      fin = fin && isfinite(F0.df[0]) && isfinite(F0.df[1]) && isfinite(F0.df[2]) && isfinite(F1.df[0]) && isfinite(F1.df[1]) &&
+            isfinite(F1.df[2]) && isfinite(F2.df[0]) && isfinite(F2.df[1]) && isfinite(F2.df[2]) && isfinite(F3.df[0]) &&
+            isfinite(F3.df[1]) && isfinite(F3.df[2]);
+      bool bad = !fin;
+      // the limits on the fit's forces: the slacks h - G (f + df_fit) of the stance feet
+      QpFoot Ft[NEE];
+      double xfit[NEE][3], sl[NEE][6], zl[NEE][6], xq[NEE][3];
+      qp_foot_of(F0, A.arm, Ft[0], xfit[0]);
+      qp_foot_of(F1, A.arm, Ft[1], xfit[1]);
+      qp_foot_of(F2, A.arm, Ft[2], xfit[2]);
+      qp_foot_of(F3, A.arm, Ft[3], xfit[3]);
+      bool inside = true;
+#pragma unroll
+      for (int e = 0; e < NEE; ++e) {
+#pragma unroll
+        for (int q6 = 0; q6 < 6; ++q6) { sl[e][q6] = NAN; zl[e][q6] = 0.0; }
+        if (Ft[e].on) {
+          const double ff[3] = {Ft[e].f[0] + xfit[e][0], Ft[e].f[1] + xfit[e][1], Ft[e].f[2] + xfit[e][2]};
+          double gv[6];
+          qp_gmul(Ft[e].B, Q.mu, ff, gv);
+#pragma unroll
+          for (int q6 = 0; q6 < 6; ++q6) {
+            const double val = gv[q6] - (q6 == 1 ? Q.f_max : 0.0);
+            if (!(val <= 0)) inside = false;
+            sl[e][q6] = -val;
+          }
+        }
+      }
+      const bool limited = cnt > 0 && !bad && !inside;
+      double qcol[QP_COLS] = {0, 0, 0, 0, 0, 0, 0, 0};
+      bool cap = false;
+      if (limited) {
+        double comp, rdn, dsq;
+        const int steps = qp_solve(Ft, rho, A.damping * nn, 6.0 * nn, Q, xfit, qp_slab + threadIdx.x, xq, sl, zl, comp, rdn, cap);
+        ga[0] = rho_w[0]; ga[1] = rho_w[1]; ga[2] = rho_w[2]; gl[0] = rho_w[3]; gl[1] = rho_w[4]; gl[2] = rho_w[5];
+        sq = 0;
+        qp_foot_residual(F0, xq[0], ga, gl, sq);
+        qp_foot_residual(F1, xq[1], ga, gl, sq);
+        qp_foot_residual(F2, xq[2], ga, gl, sq);
+        qp_foot_residual(F3, xq[3], ga, gl, sq);
+        change = sqrt(sq);
+        const double gap = qp_gap(Ft, rho, A.damping * nn, xfit, xq, dsq);
+        bool f2 = isfinite(ga[0]) && isfinite(ga[1]) && isfinite(ga[2]) && isfinite(gl[0]) && isfinite(gl[1]) && isfinite(gl[2]) && isfinite(change);
+#pragma unroll
+        for (int e = 0; e < NEE; ++e) f2 = f2 && isfinite(xq[e][0]) && isfinite(xq[e][1]) && isfinite(xq[e][2]);
+        bad = !f2;
+        double smin = INFINITY, zmax = 0;
+#pragma unroll
+        for (int e = 0; e < NEE; ++e)
+          if (Ft[e].on) {
+#pragma unroll
+            for (int q6 = 0; q6 < 6; ++q6) { smin = fmin(smin, sl[e][q6]); zmax = fmax(zmax, zl[e][q6]); }
+          }
+        qcol[0] = (double)steps;
+        qcol[1] = bad ? NAN : comp; qcol[2] = bad ? NAN : rdn; qcol[3] = bad ? NAN : smin; qcol[4] = bad ? NAN : zmax;
+        qcol[5] = bad ? NAN : sqrt(dsq); qcol[6] = bad ? NAN : gap;
+      } else if (cnt > 0 && !bad) {
+        double smin = INFINITY;
+#pragma unroll
+        for (int e = 0; e < NEE; ++e)
+          if (Ft[e].on) {
+#pragma unroll
+            for (int q6 = 0; q6 < 6; ++q6) smin = fmin(smin, sl[e][q6]);
+          }
+        qcol[3] = smin;
+      } else if (bad) {
+#pragma unroll
+        for (int c6 = 1; c6 < 7; ++c6) qcol[c6] = NAN;
+      }
+      dst[13] = bad ? NAN : ga[0]; dst[14] = bad ? NAN : ga[1]; dst[15] = bad ? NAN : ga[2];
+      dst[16] = bad ? NAN : gl[0]; dst[17] = bad ? NAN : gl[1]; dst[18] = bad ? NAN : gl[2];
+      dst[19] = bad ? NAN : change;
+      const double *q = joint_b ? joint_b + (size_t)G.tile_row(base, threadIdx.x) * QTOS_CSV_COLS + 1 : nullptr;
+      double v_ex = 0;
+      fit_foot_out<0>(A, F0, bad, R, q, dst, v_ex);                                  // (the forces and the torques; its excess bits are not this kernel's)
+      fit_foot_out<1>(A, F1, bad, R, q, dst, v_ex);
+      fit_foot_out<2>(A, F2, bad, R, q, dst, v_ex);
+      fit_foot_out<3>(A, F3, bad, R, q, dst, v_ex);
+      int st = (cnt == 0 ? 1 : 0) | (cnt == 2 ? 2 : 0) | (bad ? 4 : 0) | (limited ? 256 : 0) | (cap ? 128 : 0);
+      int n_act = 0;
+#pragma unroll
+      for (int e = 0; e < NEE; ++e)
+        if (Ft[e].on && !bad) {
+#pragma unroll
+          for (int q6 = 0; q6 < 6; ++q6)
+            if (sl[e][q6] <= Q.act_tol) { ++n_act; st |= 8 << e; }
+        }
+      qcol[7] = (double)n_act;
+#pragma unroll
+      for (int c6 = 0; c6 < QP_COLS; ++c6) qdst[c6] = qcol[c6];
+      if (status_out) status_out[(size_t)b * (size_t)rows_b + G.tile_row(base, threadIdx.x)] = st;
+      v[0] = bad ? INFINITY : fmax(fmax(fabs(ga[0]), fabs(ga[1])), fabs(ga[2]));
+      v[1] = bad ? INFINITY : fmax(fmax(fabs(gl[0]), fabs(gl[1])), fabs(gl[2]));
+      v[2] = bad ? INFINITY : change;
+      v[3] = isfinite(qcol[5]) ? fabs(qcol[5]) : INFINITY;
+    }
+    if (summary) {                                                                   // (B) the tile's families into the running records
+#pragma unroll
+      for (int f = 0; f < FIT_FAMILIES; ++f) {
+        const double mx = wg_reduce<1, QP_TILE>(v[f], qp_red);
+        const double at = wg_reduce<2, QP_TILE>(v[f] == mx ? (double)threadIdx.x : (double)QP_TILE, qp_red);
+        const double over = wg_reduce<0, QP_TILE>(v[f] > A.tol[f] ? 1.0 : 0.0, qp_red);
+        if (mx > run_max[f]) { run_max[f] = mx; run_row[f] = row0 + j0 + (long long)at; }
+        run_cnt[f] += (long long)over;
+      }
+    }
+    __syncthreads();
+    if (out_b) {                                                                     // (C) the tiles go out flat
+      for (int e = threadIdx.x; e < m * FIT_COLS; e += QP_TILE) {
+        const int i = e / FIT_COLS, c = e - i * FIT_COLS;
+        if (c < 20 || joint_b) out_b[G.flat(base, FIT_COLS, e)] = qp_tile[i * FIT_PITCH + c];
+      }
+    }
+    if (qout_b) {
+      for (int e = threadIdx.x; e < m * QP_COLS; e += QP_TILE) {
+        const int i = e / QP_COLS, c = e - i * QP_COLS;
+        qout_b[G.flat(base, QP_COLS, e)] = qp_qtile[i * QP_PITCH + c];
+      }
+    }
+    __syncthreads();
+  }
+  if (summary && threadIdx.x == 0) {
+    if (A.accumulate && n == 0) return;
 #pragma unroll
     for (int f = 0; f < FIT_FAMILIES; ++f) {
       CheckRecord rec = {run_max[f], run_row[f], run_cnt[f]};

@@ -7,7 +7,9 @@ through the KKT self-test (capi.Planner(checked=True)): a transcription whose el
 the attempts are printed and the exit status is 2, the reference's "numerical failure" class.  ``--check`` prints, behind the
 solve, what the plan violates between its knots: one line per family of the plan check (plan_check.py); the exit status is
 unchanged.  ``--fit`` prints, behind those, what fitting the rows' contact forces to the planned motion leaves and changes: one
-line per family of the force fit (force_fit.py); CSV and exit status are unchanged.
+line per family of the force fit (force_fit.py); CSV and exit status are unchanged.  ``--fit-limits MU,FMAX`` prints the lines of
+the fit inside the friction pyramid instead (force_qp.py: friction coefficient MU, force cap FMAX in newtons; ``-`` for either
+keeps the planner's); CSV and exit status are unchanged.
 """
 import sys
 
@@ -27,7 +29,8 @@ def main(argv=None):
     fit = "--fit" in argv
     if fit:
         argv.remove("--fit")
-    for opt in ("--out", "--heightfield", "--log"):
+    limits = None
+    for opt in ("--out", "--heightfield", "--log", "--fit-limits"):
         if opt in argv:
             i = argv.index(opt)
             val = argv[i + 1]
@@ -36,6 +39,10 @@ def main(argv=None):
                 out = val
             elif opt == "--log":
                 log = val
+            elif opt == "--fit-limits":
+                mu, f_max = val.split(",")
+                limits = {k: float(v) for k, v in (("mu", mu), ("f_max", f_max)) if v != "-"}
+                fit = "limits"
             else:
                 hf = val
     args = flags.parse_flags(argv)
@@ -48,7 +55,7 @@ def main(argv=None):
         # --log PATH: the per-solve report (report.py) goes to PATH; --log -: to stdout, where it ends with the status line
         # -- the reference's logs/towr_log.out back from `python -m qtos_amd.main ... --log - > logs/towr_log.out`
         try:
-            status = lp.solve(args, out_csv=out, log=sys.stdout if log == "-" else log, check=check, fit=fit)
+            status = lp.solve(args, out_csv=out, log=sys.stdout if log == "-" else log, check=check, fit=fit, limits=limits)
         except capi.SelftestError as e:
             for t in e.attempts:
                 print("KKT self-test: " + t.describe())

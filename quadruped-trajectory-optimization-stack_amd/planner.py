@@ -119,13 +119,15 @@ class LocalPlanner:
                          r=[a.get('-r') for a in args_list])
         return statuses
 
-    def solve(self, args, out_csv=TRAJ_OUT, log=None, check=False, fit=False):
+    def solve(self, args, out_csv=TRAJ_OUT, log=None, check=False, fit=False, limits=None):
         """One plan; writes the CSV where the reference's ``docker cp`` would put it.
 
         fit: True or a writable file object -- behind the solve (and the check's lines) one line per family of the force fit
         (qtos_force_fit: what is left of the dynamics rows with the fitted forces, the largest change, the largest excess over the
         friction pyramid, their times, the rows over capi.FIT_TOL) is written there (True: stdout) and the records are kept in
-        ``self.last["fit"]``.  The CSV and the return value are unchanged.
+        ``self.last["fit"]``.  The CSV and the return value are unchanged.  fit="limits": the fit inside the friction pyramid instead
+        (qtos_force_qp; the rule: force_qp.py) with limits = dict(mu=, f_max=, mu_end=, ...) (None: the planner's friction and force
+        limit): one line per family of the force QP on stdout, the records in ``self.last["fit_limits"]``.
 
         check: True or a writable file object -- behind the solve one line per family of the plan check (qtos_plan_check: the
         largest violation of the CSV's rows, its time, the rows over capi.CHECK_TOL) is written there (True: stdout) and the
@@ -167,7 +169,17 @@ class LocalPlanner:
             out = check if hasattr(check, "write") else sys.stdout
             out.write(text)
             out.flush()
-        if fit:
+        if isinstance(fit, str):
+            if fit != "limits":
+                raise ValueError('fit is True, a file object or "limits"')
+            from . import force_qp
+            P = self.planner(args.get('-duration'))
+            params = capi.qp_params(self.cfg, hz=self.cfg.hz, n_rows=len(self.last["rows"][0]), **(limits or {}))
+            _, _, _, summary = P.force_qp(self.last["nodes"][:1], self.last["t0"][:1], params, rows=False)
+            self.last["fit_limits"] = summary[0]
+            sys.stdout.write("\n".join(force_qp.report_lines(summary[0], self.last["t0"][0], self.cfg.hz, list(params.tol))) + "\n")
+            sys.stdout.flush()
+        elif fit:
             # what fitting the rows' contact forces to the planned motion leaves and changes (force_fit.py); the CSV keeps the plan's forces
             from . import force_fit
             P = self.planner(args.get('-duration'))

@@ -254,7 +254,10 @@ class ShiftedWindows:
                ring (``self.fit_traj``, B x trajectory x 32: time stamp, fitted forces, residual rows, change, feed-forward torques
                at the joint ring's angles -- without ``joints`` those twelve columns stay zero) with its status words
                (``self.fit_status``) and merges the four families into ``self.fit_summary`` (B x 4 records as B x 4 x 3 words);
-               ``fit_rows(b)`` and ``fit_worst()`` read them.  Plans, trajectory rows and joint rows are the same bits with and
+               ``fit_rows(b)`` and ``fit_worst()`` read them.  With ``limits=dict(mu=, f_max=, mu_end=, act_tol=, max_iter=)`` among
+               the keywords (or a ``capi.qp_params(...)``) k_force_qp (qtos_force_qp_device, the rule: ``force_qp.qp_rows``) is
+               queued in that place instead: the fit inside the friction pyramid, into the same fit ring and a ring of the solve's
+               eight columns (``self.qp_traj``, read by ``qp_rows(b)``); the fourth family is then ``limited``.  Plans, trajectory rows and joint rows are the same bits with and
                without it."""
 
     def __init__(self, planner, start, goal_step, map_id=None, advance=2.5, search=0.4, stream=None, warm="none", x_range=None,
@@ -394,13 +397,20 @@ class ShiftedWindows:
             if self.traj is None:
                 raise ValueError("fit needs a trajectory ring (trajectory=N)")
             planner._need("qtos_force_fit_device", "force-fit kernel")
-            scale = None
-            if isinstance(fit, capi.QtosForceFit):
+            scale, limits = None, None
+            if isinstance(fit, (capi.QtosForceFit, capi.QtosForceQp)):
                 self._fit = fit.copy()
+                limits = isinstance(fit, capi.QtosForceQp) or None
             else:
                 kw = dict(fit)
-                scale = kw.pop("mass_scale", None)
-                self._fit = capi.fit_params(kw.pop("cfg", getattr(planner, "cfg", None)), **kw)
+                scale, limits = kw.pop("mass_scale", None), kw.pop("limits", None)
+                if limits is None:
+                    self._fit = capi.fit_params(kw.pop("cfg", getattr(planner, "cfg", None)), **kw)
+                else:
+                    self._fit = capi.qp_params(kw.pop("cfg", getattr(planner, "cfg", None)), **kw, **dict(limits))
+            if limits is not None:                    # the fit inside the friction pyramid: k_force_qp in k_force_fit's place
+                planner._need("qtos_force_qp_device", "force-QP kernel")
+                self.qp_traj = torch.zeros((B, int(trajectory), capi.QP_COLS), **f64)
             # the stitch's rows: its first row, its ring, its clock
             self._fit.hz, self._fit.first_row, self._fit.n_rows, self._fit.capacity = self.hz, int(self._stitch.first_row), 0, int(trajectory)
             self._fit.flags |= capi.FIT_ACCUMULATE
@@ -644,6 +654,12 @@ class ShiftedWindows:
         """Queue k_force_fit in front of a stitch, behind the joint rows: the fit rows of the segment that stitch appends, to the
         same ring rows, with the joint ring's angles where ``joints`` is on, merged into the windows' records (the kernel reads the
         cursor and the clock the stitch behind it moves on)."""
+        if isinstance(params, capi.QtosForceQp):
+            self.P._chk(self.P.lib.qtos_force_qp_device(self.P.h, self.B, C.byref(params), self.nodes.data_ptr(), self.t0.data_ptr(),
+                                                        ptr(self.map_id), None, n_rows, self.cursor.data_ptr(), ptr(self.joint_traj),
+                                                        ptr(self._fit_scale), self.fit_traj.data_ptr(), self.qp_traj.data_ptr(),
+                                                        self.fit_status.data_ptr(), self.fit_summary.data_ptr(), sp), "qtos_force_qp_device")
+            return
         self.P._chk(self.P.lib.qtos_force_fit_device(self.P.h, self.B, C.byref(params), self.nodes.data_ptr(), self.t0.data_ptr(),
                                                      ptr(self.map_id), None, n_rows, self.cursor.data_ptr(), ptr(self.joint_traj),
                                                      ptr(self._fit_scale), self.fit_traj.data_ptr(), self.fit_status.data_ptr(),
@@ -658,6 +674,15 @@ class ShiftedWindows:
         self.stream.synchronize()
         cur = int(self.cursor[b].item())
         return ring_rows(self.fit_traj[b].cpu().numpy(), cur), ring_rows(self.fit_status[b].cpu().numpy(), cur)
+
+    def qp_rows(self, b):
+        """Window b's newest min(cursor, trajectory) rows of the force QP's solve table (8 columns, force_qp.py) in time order, as
+        numpy (the stream is synchronised): row for row with ``fit_rows(b)``."""
+        from .stitcher import ring_rows
+        if not isinstance(self._fit, capi.QtosForceQp):
+            raise RuntimeError("qp_rows() needs the force fit with limits (fit=dict(limits=...))")
+        self.stream.synchronize()
+        return ring_rows(self.qp_traj[b].cpu().numpy(), int(self.cursor[b].item()))
 
     def fit_worst(self):
         """What the fit left and changed over the windows' executed rows so far, [B, 4] records of force_fit.SUMMARY (the families
