@@ -363,12 +363,24 @@ int qtos_stitch(QtosPlanner *p, int B, const QtosStitch *s, const double *nodes,
  *   r = p_b - hip, h^2 = r_y^2 + r_z^2 - lateral^2, c3 = (r_x^2 + h^2 - l_u^2 - l_l^2) / (2 l_u l_l)
  *   q1 = atan2(r_y h + r_z lateral, r_y lateral - r_z h), q3 = knee_sign acos(clip(c3, -1, 1)),
  *   q2 = atan2(-r_x, h) - atan2(l_l sin q3, l_u + l_l cos q3)
+ *   on the fold side, c3 < -1/2, where c3 + 1 and h^2 are small differences: h^2 = (r_y - lateral)(r_y + lateral) + r_z^2 (h = 0
+ *         where the h^2 above is < 0) and q3 = knee_sign 2 atan2(sqrt(max(a, 0)), sqrt(max(b, 0))) with rho^2 = r_x^2 + h^2,
+ *         a = ((l_u + l_l)^2 - rho^2) / (2 l_u l_l) and b = (rho^2 - (l_u - l_l)^2) / (2 l_u l_l), b = 0 where c3 < -1; q1 and q2 as
+ *         above with this h and q3.  The status bits are the comparisons of the c3 and h^2 above on both sides
  *   qdot = J^-1 v_b (closed 3 x 3 solve), tau_ff = -J^T R^T f with f the plan's foot force (0 with flags bit 0)
  *   tau = clip(kp (q - q_mes) + kd (qdot - qd_mes) + tau_ff, -tau_max, tau_max); without q_mes the PD terms are left out,
  *         tau_max <= 0: no clip
  * and a status word: bit e the target of foot e is beyond the leg's reach (c3 > 1: the leg is straight and points at it), bit
  * 4 + e inside its folded length (c3 < -1), bit 8 + e nearer to the hip axis than the lateral offset (h^2 < 0, h taken as 0).  A
- * leg with a status bit has qdot = 0.
+ * leg with one of these bits has qdot = 0.  Bit 12 + e (QTOS_JOINT_NONFINITE << e): one of leg e's nine numbers q, qdot, tau_ff
+ * (tau_ff as the motor law takes it: 0 with QTOS_JOINT_NO_FF) is not finite -- a non-finite node, or a division by a
+ * determinant that is exactly zero.  Non-finite input: the two clips are comparisons that keep a NaN, and a leg whose target p_b
+ * has a non-finite component has q = qdot = (NaN, NaN, NaN) (with them tau_ff, and tau where it is formed from them) and
+ * bit 12 + e; no finite angle or rate comes out of such a target.  Its bits e, 4 + e and 8 + e are what the three comparisons
+ * give (none on a NaN).  A non-finite force alone leaves q and qdot as they are, tau_ff non-finite, and sets bit 12 + e.  The
+ * other legs of the row are not touched by it unless they read the same number (the CoM, the Euler angles).
+ * One unit in the last place inside full stretch (c3 just below 1) the rule has no bit and qdot = J^-1 v_b is unbounded:
+ * |qdot| grows as 1 / sin q3.  That is the rule as it stands; see DESIGN.md section 6.
  * Two addressing modes.  capacity 0 (table): out is B x n_rows x 37, status B x n_rows, and out[b][j] is joint row first + j,
  * j = 0 .. n - 1, with first = d_first_row ? d_first_row[b] : first_row and n = d_n_rows ? d_n_rows[b] : n_rows clamped to
  * 0 .. n_rows; rows behind n are not touched.  With n_rows = 1, d_first_row and the measured state that is the 1 kHz tick of B
@@ -377,6 +389,7 @@ int qtos_stitch(QtosPlanner *p, int B, const QtosStitch *s, const double *nodes,
  * in front of qtos_stitch_device on the same stream with the same nodes, n_rows, t0 and cursor, it fills a joint ring row for
  * row with the CSV ring. */
 #define QTOS_JOINT_NO_FF 1      /* flags: leave the feed-forward torque out (MotorModel.convert_to_torque) */
+#define QTOS_JOINT_NONFINITE 4096 /* status: leg 0's bit "a number of this leg is not finite"; leg e: << e (bits 12 .. 15) */
 typedef struct QtosJointRows {
   double hz;                    /* rows per second (<= 0: 1000) */
   int first_row;                /* first row where d_first_row is NULL; 0 .. 1000000 */
@@ -428,6 +441,10 @@ int qtos_joint_rows(QtosPlanner *p, int B, const QtosJointRows *s, const double 
  * in `recorded`; then calls += n.  Unrecorded rows carry their pose and errors and repeat the standing totals.
  * Status word of a row: bit 0 recorded, bit 1 measured CoM x >= goal_x[b] (never without goal_x), bit 2 the pitch clip acted
  * (|R20| >= 1, quaternion mode).
+ * Non-finite input: nothing is replaced.  A measured row with a non-finite number has non-finite columns wherever that number
+ * enters -- the pitch clip is a comparison that keeps a NaN, so a quaternion that is zero, NaN or infinite gives NaN Euler
+ * columns and feet, without bit 2 -- and, if the row is recorded, total_com and / or total_feet are non-finite from that row on,
+ * in this call and in every later call that takes them in.  Bit 1 is a comparison (false on a NaN).
  * Addressing: qtos_joint_rows' exactly, for `out`, `status` and `meas` alike -- capacity 0: tables of n_rows rows per window,
  * row first + j at [b][j], n = d_n_rows ? d_n_rows[b] : n_rows clamped to 0 .. n_rows, rows behind n untouched, a window with
  * n = 0 keeps its count and total; capacity > 0: rings, row first + j at ring row (cursor[b] + j) mod capacity; cursor and t0 are

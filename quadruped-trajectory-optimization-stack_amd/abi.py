@@ -8,6 +8,7 @@ CONSTANTS = {
     "QTOS_NEE": 4, "QTOS_MAX_PHASES": 32, "QTOS_START_DOUBLES": 24, "QTOS_CSV_COLS": 37,
     "QTOS_HIST_COLS": 10,                 # one record of the iteration history (qtos_plan_report)
     "QTOS_JOINT_NO_FF": 1,
+    "QTOS_JOINT_NONFINITE": 4096,         # leg 0's bit in the status word of a joint row; leg e: << e
     "QTOS_TRACK_QUAT": 1, "QTOS_TRACK_CLEAN_DELAY": 2, "QTOS_TRACK_COLS": 26,
     "QTOS_FEEDBACK_QUAT": 1, "QTOS_FEEDBACK_SNAP": 2, "QTOS_FEEDBACK_ZERO_FILTER": 4,
     "QTOS_CHECK_ACCUMULATE": 1, "QTOS_CHECK_COLS": 27, "QTOS_CHECK_FAMILIES": 5,

@@ -324,19 +324,32 @@ __device__ inline int joint_leg(const JointArgs &A, const double *row, const dou
   const double vz = R[2] * ux + R[5] * uy + R[8] * uz - (wb[0] * by - wb[1] * bx);
   const double rx = bx - A.hip[E][0], ry = by - A.hip[E][1], rz = bz + A.ee_shift - A.hip[E][2];
   // inverse kinematics (joints.leg_ik)
+  // (the two clips are comparisons, as feedback_clip: a NaN stays a NaN where fmax and fmin would drop it; a target with a
+  // non-finite component gives NaN angles and rates, never a finite number)
+  const bool finite = isfinite(rx) && isfinite(ry) && isfinite(rz);
   const double h2 = ry * ry + rz * rz - d * d;
-  const double h = sqrt(fmax(h2, 0.0));
-  const double c3 = (rx * rx + fmax(h2, 0.0) - lu * lu - ll * ll) / (2 * lu * ll);
+  const double h2c = h2 < 0 ? 0.0 : h2;
+  double h = sqrt(h2c);
+  const double c3 = (rx * rx + h2c - lu * lu - ll * ll) / (2 * lu * ll);
   const int status = (c3 > 1 ? 1 : 0) | (c3 < -1 ? 1 << 4 : 0) | (h2 < 0 ? 1 << 8 : 0);
-  const double q1 = atan2(ry * h + rz * d, ry * d - rz * h);
-  const double q3 = A.knee_sign[E] * acos(fmin(fmax(c3, -1.0), 1.0));
+  double q3 = finite ? A.knee_sign[E] * acos(c3 < -1 ? -1.0 : (c3 > 1 ? 1.0 : c3)) : NAN;
+  if (finite && c3 < -0.5) {
+    // the fold side (joints.leg_ik): c3 + 1 and h^2 are small differences there, so h^2 is formed as (r_y - d)(r_y + d) + r_z^2
+    // and the knee from the half angle, both numerators from rho^2 directly; the status bits stay the comparisons above
+    const double hf2 = (ry - d) * (ry + d) + rz * rz;
+    h = h2 < 0 ? 0.0 : sqrt(hf2 < 0 ? 0.0 : hf2);
+    const double rho2 = rx * rx + h * h;
+    const double a = ((lu + ll) * (lu + ll) - rho2) / (2 * lu * ll), b = (rho2 - (lu - ll) * (lu - ll)) / (2 * lu * ll);
+    q3 = A.knee_sign[E] * (2 * atan2(sqrt(a < 0 ? 0.0 : a), sqrt(c3 < -1 || b < 0 ? 0.0 : b)));
+  }
+  const double q1 = finite ? atan2(ry * h + rz * d, ry * d - rz * h) : NAN;
   const double s3 = sin(q3), c3c = cos(q3);
-  const double q2 = atan2(-rx, h) - atan2(ll * s3, lu + ll * c3c);
+  const double q2 = finite ? atan2(-rx, h) - atan2(ll * s3, lu + ll * c3c) : NAN;
   // the chain at q (joints._hip_frame): the foot at (x, d, -hh) in the hip frame
   const double s1 = sin(q1), c1 = cos(q1), s2 = sin(q2), c2 = cos(q2), s23 = sin(q2 + q3), c23 = cos(q2 + q3);
   const double x = -lu * s2 - ll * s23, hh = lu * c2 + ll * c23, ls = ll * s23, lc = ll * c23;
   // joint rates (joints.joint_rates): zero for a leg with a status bit
-  double qd1 = 0, qd2 = 0, qd3 = 0;
+  double qd1 = finite ? 0 : NAN, qd2 = qd1, qd3 = qd1;
   if (!status) {
     const double wy = c1 * vy + s1 * vz, wz = c1 * vz - s1 * vy, det = -(lu * ll * s3);
     qd1 = wy / hh;
@@ -360,7 +373,11 @@ __device__ inline int joint_leg(const JointArgs &A, const double *row, const dou
   dst[25 + 3 * E] = joint_motor(A.kp[3 * E], A.kd[3 * E], q1, qd1, t1, A.tau_max, pd, m1, n1);
   dst[26 + 3 * E] = joint_motor(A.kp[3 * E + 1], A.kd[3 * E + 1], q2, qd2, t2, A.tau_max, pd, m2, n2);
   dst[27 + 3 * E] = joint_motor(A.kp[3 * E + 2], A.kd[3 * E + 2], q3, qd3, t3, A.tau_max, pd, m3, n3);
-  return status << E;
+  // NONFINITE: one of the leg's nine numbers q, qdot, tau_ff is not finite (a non-finite input; a division by a determinant
+  // that is exactly zero)
+  const bool all_finite = isfinite(q1) && isfinite(q2) && isfinite(q3) && isfinite(qd1) && isfinite(qd2) && isfinite(qd3) &&
+                          isfinite(t1) && isfinite(t2) && isfinite(t3);
+  return (status | (all_finite ? 0 : 1 << 12)) << E;
 }
 
 template <int TILE>
@@ -443,7 +460,8 @@ __device__ inline int track_pose(const double *m, bool quat, double R[9], double
   R[3] = 2 * (x * y + z * w); R[4] = 1 - 2 * (x * x + z * z); R[5] = 2 * (y * z - x * w);
   R[6] = 2 * (x * z - y * w); R[7] = 2 * (y * z + x * w); R[8] = 1 - 2 * (x * x + y * y);
   euler[0] = atan2(R[7], R[8]);
-  euler[1] = asin(fmin(fmax(-R[6], -1.0), 1.0));
+  const double sp = -R[6];
+  euler[1] = asin(sp < -1 ? -1.0 : (sp > 1 ? 1.0 : sp));                             // (comparisons: a NaN stays a NaN, without the bit)
   euler[2] = atan2(R[3], R[0]);
   return fabs(R[6]) >= 1 ? 4 : 0;
 }

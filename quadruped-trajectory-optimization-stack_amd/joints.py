@@ -18,6 +18,8 @@ HAA rotation, the foot stands at u = (x, d, -h) in it,
 and at p = hip + Rx(q1) u in the base frame: r = p - hip has r_y = d cos q1 + h sin q1, r_z = d sin q1 - h cos q1, hence
 h^2 = r_y^2 + r_z^2 - d^2, r_y h + r_z d = (h^2 + d^2) sin q1 and r_y d - r_z h = (h^2 + d^2) cos q1; x^2 + h^2 =
 l_u^2 + l_l^2 + 2 l_u l_l cos q3, and the direction of (h, -x) is q2 plus the angle of (l_u + l_l cos q3, l_l sin q3).
+With rho^2 = x^2 + h^2: 1 - cos q3 = ((l_u + l_l)^2 - rho^2) / (2 l_u l_l) and 1 + cos q3 = (rho^2 - (l_u - l_l)^2) / (2 l_u l_l), whose
+square roots are in the ratio tan(q3 / 2): what leg_ik forms the knee from on the fold side.
 """
 import numpy as np
 
@@ -26,6 +28,8 @@ LEGS = ("FL", "FR", "HL", "HR")            # the order of SOLO12.csv_entry
 JOINTS = ("HAA", "HFE", "KFE")
 JOINT_COLS = 37
 REACH, FOLD, INSIDE = 1, 2, 4              # status bits of one leg (leg_ik)
+NONFINITE = 8                              # of one leg: the target, or one of the leg's numbers, is not finite (bit 12 + e of a row)
+STATUS_NONFINITE = 1 << 12                 # QTOS_JOINT_NONFINITE: leg 0's bit in the status word of a row
 FLAG_NO_FF = 1                             # QtosJointRows.flags bit 0: the feed-forward torque is left out (convert_to_torque)
 
 
@@ -129,18 +133,35 @@ def leg_ik(leg, p_b, robot=SOLO12, dtype=np.longdouble):
     """Closed-form inverse kinematics of leg `leg` (0 FL, 1 FR, 2 HL, 3 HR) for the foot at p_b [..., 3] in the base frame:
     (q [..., 3] = HAA, HFE, KFE, status [...] int32).  Status bits: REACH (c3 > 1: the target is beyond the leg's length; the
     leg is straight and points at it, the nearest reachable point in the leg's plane), FOLD (c3 < -1) and INSIDE (h^2 < 0: the
-    target is nearer to the hip axis than the lateral offset; h is taken as 0)."""
+    target is nearer to the hip axis than the lateral offset; h is taken as 0).  The two clips keep a NaN (np.maximum, np.clip),
+    and a target with a non-finite component has q = (NaN, NaN, NaN) and the bit NONFINITE: no finite angle comes out of a
+    target that is not a point (the formulas alone would give a NaN in r_x the q1 of the other two components, and an
+    infinite r_z the angles of a leg that points at it).  The three comparisons are what they are on such a target."""
     hip, d = _field(robot, "hip", (NEE, 3))[leg].astype(dtype), dtype(_field(robot, "lateral")[leg])
     lu, ll, knee = dtype(robot.l_upper), dtype(robot.l_lower), dtype(_field(robot, "knee_sign")[leg])
     r = np.asarray(p_b).astype(dtype) - hip
     rx, ry, rz = r[..., 0], r[..., 1], r[..., 2]
     c3, h2 = ik_margins(leg, p_b, robot, dtype)
     h = np.sqrt(np.maximum(h2, dtype(0)))
-    q1 = np.arctan2(ry * h + rz * d, ry * d - rz * h)
     q3 = knee * np.arccos(np.clip(c3, dtype(-1), dtype(1)))
+    # The fold side, c3 < -1/2.  There c3 + 1 = (rho^2 - (l_u - l_l)^2) / (2 l_u l_l), rho^2 = r_x^2 + h^2, is a small number next
+    # to 1 and h^2 a small difference of squares, so c3 and the h above resolve a foot next to the folded length only to
+    # nanometres.  h^2 is formed as (r_y - d)(r_y + d) + r_z^2 and the knee from the half angle, tan(q3 / 2) =
+    # sqrt((1 - c3) / (1 + c3)), with both numerators formed from rho^2 directly.  The status bits stay the comparisons of
+    # c3 and h^2 as ik_margins forms them: a leg with INSIDE keeps h = 0, one with FOLD q3 = +-pi.
+    with np.errstate(invalid="ignore"):
+        fold = c3 < -0.5
+        hf = np.where(h2 < 0, dtype(0), np.sqrt(np.maximum((ry - d) * (ry + d) + rz * rz, dtype(0))))
+        rho2 = rx * rx + hf * hf
+        a = np.maximum(((lu + ll) * (lu + ll) - rho2) / (2 * lu * ll), dtype(0))
+        b = np.where(c3 < -1, dtype(0), np.maximum((rho2 - (lu - ll) * (lu - ll)) / (2 * lu * ll), dtype(0)))
+        h = np.where(fold, hf, h)
+        q3 = np.where(fold, knee * (2 * np.arctan2(np.sqrt(a), np.sqrt(b))), q3)
+    q1 = np.arctan2(ry * h + rz * d, ry * d - rz * h)
     q2 = np.arctan2(-rx, h) - np.arctan2(ll * np.sin(q3), lu + ll * np.cos(q3))
-    status = (REACH * (c3 > 1) + FOLD * (c3 < -1) + INSIDE * (h2 < 0)).astype(np.int32)
-    return np.stack([q1, q2, q3], -1), status
+    bad = ~np.isfinite(r).all(-1)
+    status = (REACH * (c3 > 1) + FOLD * (c3 < -1) + INSIDE * (h2 < 0) + NONFINITE * bad).astype(np.int32)
+    return np.where(bad[..., None], dtype(np.nan), np.stack([q1, q2, q3], -1)), status
 
 
 def _hip_frame(leg, q, robot, dtype):
@@ -176,17 +197,19 @@ def leg_jacobian(leg, q, robot=SOLO12, dtype=np.longdouble):
 def joint_rates(leg, q, v_b, status=None, robot=SOLO12, dtype=np.longdouble):
     """qdot = J^-1 v_b by a closed solve in the hip frame: with w = Rx(q1)^T v_b, w_y = h qdot1, and the 2 x 2 system of
     (w_x, w_z - d qdot1) in (qdot2, qdot3) has the determinant -l_u l_l sin q3.  A leg with a status bit gets qdot = 0 (J is
-    singular at a straight or folded knee and at h = 0)."""
+    singular at a straight or folded knee and at h = 0); a leg with leg_ik's NONFINITE bit gets qdot = NaN."""
     s1, c1, x, h, ls, lc, d, det = _hip_frame(leg, q, robot, dtype)
     v = np.asarray(v_b).astype(dtype)
     wx, wy, wz = v[..., 0], c1 * v[..., 1] + s1 * v[..., 2], c1 * v[..., 2] - s1 * v[..., 1]
-    ok = np.ones(np.shape(x), bool) if status is None else np.asarray(status) == 0
+    st = np.zeros(np.shape(x), np.int32) if status is None else np.asarray(status)
+    ok = (st & (REACH | FOLD | INSIDE)) == 0
     hs, dets = np.where(ok, h, dtype(1)), np.where(ok, -det, dtype(1))
     qd1 = wy / hs
     rz = wz - d * qd1
     qd2 = (wx * ls + lc * rz) / dets
     qd3 = (x * wx - h * rz) / dets
-    return np.where(ok[..., None], np.stack([qd1, qd2, qd3], -1), dtype(0))
+    qd = np.where(ok[..., None], np.stack([qd1, qd2, qd3], -1), dtype(0))
+    return np.where(((st & NONFINITE) != 0)[..., None], dtype(np.nan), qd)
 
 
 def feed_forward(leg, q, euler, force, robot=SOLO12, dtype=np.longdouble):
@@ -226,8 +249,10 @@ def motor_torque(q, qd, tau_ff, kp, kd, tau_max, q_mes=None, qd_mes=None):
 
 def joint_state(rows, foot_vel, params, dtype=np.longdouble):
     """Cartesian rows [n, 37] (in dtype) and the feet's velocities [n, 4, 3] -> (q [n, 12], qd [n, 12], tau_ff [n, 12],
-    status [n] int32: bit e reach, bit 4 + e fold, bit 8 + e inside of foot e)."""
+    status [n] int32: bit e reach, bit 4 + e fold, bit 8 + e inside of foot e, bit 12 + e nonfinite: one of the leg's nine
+    numbers q, qdot, tau_ff -- tau_ff as the motor law takes it, 0 with FLAG_NO_FF -- is not finite)."""
     n = rows.shape[0]
+    no_ff = bool(int(getattr(params, "flags", 0)) & FLAG_NO_FF)
     q, qd, tff = np.zeros((n, 12), dtype), np.zeros((n, 12), dtype), np.zeros((n, 12), dtype)
     status = np.zeros(n, np.int32)
     for e in range(NEE):
@@ -238,6 +263,9 @@ def joint_state(rows, foot_vel, params, dtype=np.longdouble):
         qd[:, 3 * e:3 * e + 3] = joint_rates(e, qe, v_b, st, params, dtype)
         tff[:, 3 * e:3 * e + 3] = feed_forward(e, qe, rows[:, 4:7], rows[:, 25 + 3 * e:28 + 3 * e], params, dtype)
         status |= ((st & REACH) << e) | (((st & FOLD) >> 1) << (4 + e)) | (((st & INSIDE) >> 2) << (8 + e))
+        nine = [q[:, 3 * e:3 * e + 3], qd[:, 3 * e:3 * e + 3]] + ([] if no_ff else [tff[:, 3 * e:3 * e + 3]])
+        bad = ~np.isfinite(np.concatenate(nine, 1)).all(1)
+        status |= np.where(bad, STATUS_NONFINITE << e, 0).astype(np.int32)
     return q, qd, tff, status
 
 
