@@ -872,6 +872,63 @@ int qtos_force_qp(QtosPlanner *p, int B, const QtosForceQp *s, const double *nod
                   const int *first_row, const int *n_rows, const long long *cursor, const double *joint, const double *mass_scale,
                   double *rows, double *qrows, int *status, QtosCheckRecord *summary);
 
+/* Rollout with the force QP: qtos_rollout_feet with qtos_force_qp's limited path in place of the comparisons of QTOS_FEET_LIMIT, in
+ * every step of the simulated closed loop (k_rollout_qp, one workgroup per window; the rule, with the order of every operation:
+ * rollout_qp.py).  Everything is qtos_rollout_feet's -- the inputs, the weights, the step's lines, the freeze, PENDING / INIT, the
+ * columns of meas, rows and frows -- except the line that forms f_a.  Per step, with f0_e = ff_scale f_e, df_e, d_e, rho~ and n as
+ * qtos_rollout_feet forms them and the six limit rows of qtos_force_qp in the basis of flat ground (the rollout reads no terrain):
+ *   fit path      every stance foot's six values G (f0 + df) - h are <= 0:  f_a = f0 + df, qtos_rollout_feet's unlimited step to the
+ *                 bit.  A NaN fails the comparison, takes the limited path and runs into the cap; the next row's freeze catches it
+ *   limited path  f_a = f0 + x, x the central point at weight mu_end of qtos_force_qp's problem with d = d_e, w, rho~, c = damping n,
+ *                 f = f0 and the fit df: strictly feasible, by that function's iteration and stopping rule
+ * A per-step optimum is not a balance controller: the call reports what the limits cost the feedback, it cures nothing.
+ * qrows has qtos_force_qp's 8 columns for the tick's FIRST step (on the fit path 0 but for columns 3 and 7, which come from the
+ * fit's slacks; 0 on a row without a stance foot and on a frozen row).  status: qtos_rollout_feet's bits, with bit 8 (LIMITED) a step
+ * of this tick took the limited path, and bit 9 (CAP) a step reached max_iter. */
+#define QTOS_ROLLOUT_QP_COLS 8
+#define QTOS_ROLLOUT_CAP 512
+typedef struct QtosRolloutQp {
+  /* QtosRolloutFeet's fields under their names, in its order and at its offsets */
+  double hz;
+  int substeps;
+  int first_row;
+  int n_rows;
+  long long capacity;
+  int flags;                    /* QTOS_ROLLOUT_* */
+  double mass, gravity;
+  double inertia_b[9];
+  double inertia_b_inv[9];
+  double ff_scale;
+  double kp_lin[3], kd_lin[3];
+  double kp_ang[3], kd_ang[3];
+  double f_fb_max, t_fb_max;
+  double dev_max, tilt_max;
+  long long push_from, push_ticks;
+  double arm;
+  double damping;
+  double w_min;
+  double mu;                    /* friction coefficient of the pyramid (> 0) */
+  double f_max;                 /* cap of the normal force (> 0) [N] */
+  int feet_flags;               /* not read */
+  /* the QP */
+  double mu_end;                /* the barrier weight of the central point (> 0) [N^2] */
+  double act_tol;               /* a limit row counts as active where its slack is <= act_tol [N] */
+  int max_iter;                 /* 1 .. 25 */
+} QtosRolloutQp;
+/* The arguments are qtos_rollout_feet's, with qrows B x rows x 8 (may be NULL) behind frows; both forms behave as qtos_rollout_feet's
+ * do.  Both: qtos_rollout_feet's errors, and -1 with the reason in qtos_last_error on mu, f_max or mu_end not > 0, max_iter outside
+ * 1 .. 25, act_tol not a number. */
+int qtos_rollout_qp_device(QtosPlanner *p, int B, const QtosRolloutQp *s, const double *d_nodes, const double *d_t0,
+                           const int *d_first_row /* may be NULL */, const int *d_n_rows /* may be NULL */,
+                           const long long *d_cursor /* NULL in table mode */, const double *d_joint /* may be NULL */,
+                           const double *d_mass_scale /* may be NULL = 1 */, const double *d_push /* may be NULL */,
+                           double *d_state /* in/out */, long long *d_count /* in/out */, int *d_word /* in/out */, double *d_meas,
+                           double *d_rows /* may be NULL */, double *d_frows /* may be NULL */, double *d_qrows /* may be NULL */,
+                           int *d_status, void *stream);
+int qtos_rollout_qp(QtosPlanner *p, int B, const QtosRolloutQp *s, const double *nodes, const double *t0, const int *first_row,
+                    const int *n_rows, const long long *cursor, const double *joint, const double *mass_scale, const double *push,
+                    double *state, long long *count, int *word, double *meas, double *rows, double *frows, double *qrows, int *status);
+
 /* Goals of receding windows from their global paths: where the next plan goes.  Replaces Global_Planner.update / spine_step
  * (QTOS/planner.py:139-161, 195-230) and Combiner.plan_init / spine_step (QTOS/combiner.py:137-212, 223-225) for B windows at
  * once: a window's A* "spine" -- two cubic splines X_p, Y_p over one set of knots -- is read one horizon ahead of the new plan's

@@ -21,6 +21,7 @@ CONSTANTS = {
     "QTOS_QP_COLS": 8, "QTOS_QP_MAX_ITER": 25,
     "QTOS_QP_NO_STANCE": 1, "QTOS_QP_TWO_STANCE": 2, "QTOS_QP_NONFINITE": 4, "QTOS_QP_ACTIVE": 8, "QTOS_QP_CAP": 128,
     "QTOS_QP_LIMITED": 256,               # status bits of a force-QP row
+    "QTOS_ROLLOUT_QP_COLS": 8, "QTOS_ROLLOUT_CAP": 512,       # a rollout with the force QP: its solve table, its status bit
     "QTOS_ENV_MAX_LEVELS": 64, "QTOS_ENV_MAX_DRAWS": 1 << 24, "QTOS_ENV_LDS_BYTES": 3568,
 }
 globals().update({name[len("QTOS_"):]: value for name, value in CONSTANTS.items()})
@@ -213,6 +214,13 @@ class QtosRolloutFeet(_Struct):
         return g
 
 
+class QtosRolloutQp(_Struct):
+    """Parameters of a rollout with the force QP (qtos_rollout_qp*): QtosRolloutFeet's fields, then the QP's.
+    rollout_qp.rollout_qp_rows takes it as its RolloutParams and as its QpFeetParams."""
+    _fields_ = QtosRolloutFeet._fields_ + [("mu_end", C.c_double), ("act_tol", C.c_double), ("max_iter", C.c_int)]
+    with_body = QtosRolloutFeet.with_body
+
+
 class QtosForceFit(_Struct):
     """Parameters of a force fit (qtos_force_fit*); force_fit.fit_rows reads the same fields."""
     _fields_ = [
@@ -282,6 +290,8 @@ def _prototypes():
         "qtos_force_fit_device": f(h, i, P(QtosForceFit), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp),
         "qtos_force_qp":        f(h, i, P(QtosForceQp), dp, dp, ip, ip, ip, qp, dp, dp, dp, dp, ip, vp),
         "qtos_force_qp_device": f(h, i, P(QtosForceQp), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp),
+        "qtos_rollout_qp":        f(h, i, P(QtosRolloutQp), dp, dp, ip, ip, qp, dp, dp, dp, dp, qp, ip, dp, dp, dp, dp, ip),
+        "qtos_rollout_qp_device": f(h, i, P(QtosRolloutQp), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp),
         "qtos_path_goal":        f(h, i, P(QtosPathGoal), dp, dp, ip, dp, ip, dp, ip, dp, dp, dp, dp, ip),
         "qtos_path_goal_device": f(h, i, P(QtosPathGoal), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp),
         "qtos_path_plan":        f(h, i, P(QtosPathPlan), dp, ip, dp, dp, dp, dp, ip, ip, ip, ip, ip),

@@ -15,9 +15,9 @@ import numpy as np
 from .abi import *  # noqa: F401,F403  (the mirror is part of this module's interface: capi.QtosTrack, capi.TRACK_COLS, capi.EXPORTS ...)
 from .abi import (CHECK_ACCUMULATE, CHECK_COLS, CHECK_FAMILIES, CSV_COLS, FEEDBACK_QUAT, FEEDBACK_SNAP, FEEDBACK_ZERO_FILTER,
                   FIT_ACCUMULATE, FIT_COLS, FIT_FAMILIES, QP_COLS, HIST_COLS, JOINT_NO_FF, MAX_PHASES, NEE, PROTOTYPES, ROLLOUT_COLS,
-                  ROLLOUT_FEET_COLS, ROLLOUT_INIT, ROLLOUT_QUAT, ROLLOUT_STATE, START_DOUBLES, TRACK_CLEAN_DELAY, TRACK_COLS, TRACK_QUAT, QtosDims,
+                  ROLLOUT_FEET_COLS, ROLLOUT_INIT, ROLLOUT_QP_COLS, ROLLOUT_QUAT, ROLLOUT_STATE, START_DOUBLES, TRACK_CLEAN_DELAY, TRACK_COLS, TRACK_QUAT, QtosDims,
                   QtosForceFit, QtosForceQp, QtosHandover, QtosJointRows, QtosFeedback, QtosParams, QtosPathGoal, QtosPathPlan, QtosPlanCheck,
-                  QtosProbe, QtosReport, QtosRollout, QtosRolloutFeet, QtosSelftest, QtosStitch, QtosTerrainEnv, QtosTrack)
+                  QtosProbe, QtosReport, QtosRollout, QtosRolloutFeet, QtosRolloutQp, QtosSelftest, QtosStitch, QtosTerrainEnv, QtosTrack)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (QTOS_LIB names another build of the library in csrc/: A/B timing of kernel variants, scratch/ab2.py)
@@ -277,6 +277,17 @@ def rollout_feet_params(cfg=None, arm=0.2, damping=1e-6, w_min=0.01, mu=None, f_
     f = rollout_feet.FeetParams(cfg, arm, damping, w_min, mu, f_max, limit)
     g = QtosRolloutFeet().with_body(rollout_params(cfg=cfg, **body))
     g.arm, g.damping, g.w_min, g.mu, g.f_max, g.feet_flags = f.arm, f.damping, f.w_min, f.mu, f.f_max, f.feet_flags
+    return g
+
+
+def rollout_qp_params(cfg=None, arm=0.2, damping=1e-6, w_min=0.01, mu=None, f_max=None, mu_end=1e-6, act_tol=1e-3, max_iter=25, **body):
+    """A QtosRolloutQp: rollout_feet_params' keywords without `limit`, and the QP's mu_end, act_tol and max_iter.  A value outside
+    its range raises ValueError, as rollout_qp.QpFeetParams does (mu > 0 and f_max > 0 among them)."""
+    from . import rollout_qp
+    f = rollout_qp.QpFeetParams(cfg, arm, damping, w_min, mu, f_max, mu_end, act_tol, max_iter)
+    g = QtosRolloutQp().with_body(rollout_params(cfg=cfg, **body))
+    g.arm, g.damping, g.w_min, g.mu, g.f_max, g.feet_flags = f.arm, f.damping, f.w_min, f.mu, f.f_max, 0
+    g.mu_end, g.act_tol, g.max_iter = f.mu_end, f.act_tol, f.max_iter
     return g
 
 
@@ -702,6 +713,9 @@ class Planner:
     def has_rollout_feet(self):
         return self.has("qtos_rollout_feet")
 
+    def has_rollout_qp(self):
+        return self.has("qtos_rollout_qp")
+
     def has_start_feedback(self):
         return self.has("qtos_start_feedback")
 
@@ -983,6 +997,38 @@ class Planner:
                                              _dp(ms), _dp(push), _dp(state), _llp(count), _ip(word), _dp(meas), _dp(rows), _dp(frows),
                                              _ip(status)), "rollout_feet")
         return meas, rows, frows, status, state, count, word
+
+    def rollout_qp(self, nodes, t0, params, first_row=None, n_rows=None, cursor=None, joint=None, mass_scale=None, push=None, state=None,
+                   count=None, word=None, meas=None, rows=True, frows=True, qrows=True, status=None):
+        """Roll the windows' bodies out with their stance forces from the pyramid QP (qtos_rollout_qp, host form; the rule:
+        rollout_qp.rollout_qp_rows).  params: a QtosRolloutQp (rollout_qp_params()).  Every other argument is rollout_feet()'s;
+        qrows: True, an array (B, rows, 8) or False / None for no solve table.  Returns new arrays (meas, rows or None, frows or
+        None, qrows or None, status, state, count, word)."""
+        self._need("qtos_rollout_qp", "QP rollout kernel")
+        nodes, B = self._nodes(nodes)
+        t0 = _bcast(t0, B)
+        first, per = _bcast(first_row, B, np.int32), _bcast(n_rows, B, np.int32)
+        nr, cur = _segment(params, B, cursor)
+        nr = max(nr, 0)                                    # (a negative n_rows: the library refuses it)
+        mcols = 19 if params.flags & ROLLOUT_QUAT else 18
+        joint = None if joint is None else np.ascontiguousarray(joint, np.float64)
+        if joint is not None and joint.shape != (B, nr, CSV_COLS):
+            raise ValueError("joint is (B, %d, %d)" % (nr, CSV_COLS))
+        ms, push = _bcast(mass_scale, B), _mat(push, (B, 6))
+        state = np.zeros((B, ROLLOUT_STATE)) if state is None else _mat(state, (B, ROLLOUT_STATE), copy=True)
+        count = np.zeros(B, np.int64) if count is None else _bcast(count, B, np.int64, copy=True)
+        word = np.zeros(B, np.int32) if word is None else _bcast(word, B, np.int32, copy=True)
+        meas = np.zeros((B, nr, mcols)) if meas is None else np.array(meas, np.float64)
+        rows, frows, qrows = _table(rows, (B, nr, ROLLOUT_COLS)), _table(frows, (B, nr, ROLLOUT_FEET_COLS)), _table(qrows, (B, nr, ROLLOUT_QP_COLS))
+        status = np.zeros((B, nr), np.int32) if status is None else np.array(status, np.int32)
+        if meas.shape != (B, nr, mcols) or status.shape != (B, nr) or (rows is not None and rows.shape != (B, nr, ROLLOUT_COLS)) or \
+                (frows is not None and frows.shape != (B, nr, ROLLOUT_FEET_COLS)) or (qrows is not None and qrows.shape != (B, nr, ROLLOUT_QP_COLS)):
+            raise ValueError("meas is (B, %d, %d), rows (B, %d, %d), frows (B, %d, %d), qrows (B, %d, %d) and status (B, %d)"
+                             % (nr, mcols, nr, ROLLOUT_COLS, nr, ROLLOUT_FEET_COLS, nr, ROLLOUT_QP_COLS, nr))
+        self._chk(self.lib.qtos_rollout_qp(self.h, B, C.byref(params), _dp(nodes), _dp(t0), _ip(first), _ip(per), _llp(cur), _dp(joint),
+                                           _dp(ms), _dp(push), _dp(state), _llp(count), _ip(word), _dp(meas), _dp(rows), _dp(frows),
+                                           _dp(qrows), _ip(status)), "rollout_qp")
+        return meas, rows, frows, qrows, status, state, count, word
 
     def start_feedback(self, nodes, t0, row, meas, params, start, cursor=None, map_id=None, goal_step=None, goal=None, err=None,
                        status=None):

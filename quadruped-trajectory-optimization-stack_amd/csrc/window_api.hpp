@@ -746,6 +746,89 @@ int qtos_force_qp(QtosPlanner *p, int B, const QtosForceQp *s, const double *nod
   return rc ? rc : S.download();
 }
 
+// ---- the rollout with the force QP in every step (k_rollout_qp, window_kernels.hpp) ------------------------------
+// QtosRolloutQp begins with QtosRolloutFeet's fields at its offsets, so the body's and the feet's checks are rollout_feet_args' on
+// that part; then the QP's own.
+static int rollout_qp_args(QtosPlanner *p, int B, const QtosRolloutQp *s, const void *nodes, const void *t0, const void *cursor,
+                           const void *state, const void *count, const void *word, const void *meas, const void *status, RolloutArgs *A,
+                           FeetArgs *F, QpArgs *Q) {
+  if (!p) return -1;
+  static_assert(offsetof(QtosRolloutQp, feet_flags) == offsetof(QtosRolloutFeet, feet_flags) && offsetof(QtosRolloutQp, arm) == offsetof(QtosRolloutFeet, arm) &&
+                    offsetof(QtosRolloutQp, f_max) == offsetof(QtosRolloutFeet, f_max) && offsetof(QtosRolloutQp, push_ticks) == offsetof(QtosRolloutFeet, push_ticks),
+                "QtosRolloutQp begins with QtosRolloutFeet's fields");
+  QtosRolloutFeet feet;
+  if (s) {
+    std::memcpy(&feet, s, offsetof(QtosRolloutFeet, feet_flags));
+    feet.feet_flags = 0;
+  }
+  if (rollout_feet_args(p, B, s ? &feet : nullptr, nodes, t0, cursor, state, count, word, meas, status, A, F)) {
+    p->err = "qtos_rollout_qp: " + p->err.substr(p->err.find(": ") + 2);
+    return -1;
+  }
+  const char *why = nullptr;
+  if (!(s->mu > 0) || !(s->mu <= 1.7976931348623157e308)) why = "mu is > 0";
+  else if (!(s->f_max > 0) || !(s->f_max <= 1.7976931348623157e308)) why = "f_max is > 0";
+  else if (!(s->mu_end > 0) || !(s->mu_end <= 1.7976931348623157e308)) why = "mu_end is > 0";
+  else if (s->act_tol != s->act_tol) why = "act_tol is not a number";
+  else if (s->max_iter < 1 || s->max_iter > QP_MAX_ITER) why = "max_iter is 1 .. 25";
+  if (why) {
+    p->err = std::string("qtos_rollout_qp: ") + why;
+    return -1;
+  }
+  Q->mu = s->mu; Q->f_max = s->f_max; Q->mu_end = s->mu_end; Q->act_tol = s->act_tol; Q->max_iter = s->max_iter;
+  return 0;
+}
+
+int qtos_rollout_qp_device(QtosPlanner *p, int B, const QtosRolloutQp *s, const double *d_nodes, const double *d_t0, const int *d_first_row,
+                           const int *d_n_rows, const long long *d_cursor, const double *d_joint, const double *d_mass_scale,
+                           const double *d_push, double *d_state, long long *d_count, int *d_word, double *d_meas, double *d_rows,
+                           double *d_frows, double *d_qrows, int *d_status, void *stream_) {
+  RolloutArgs A;
+  FeetArgs F;
+  QpArgs Q;
+  if (rollout_qp_args(p, B, s, d_nodes, d_t0, d_cursor, d_state, d_count, d_word, d_meas, d_status, &A, &F, &Q)) return -1;
+  const long long most = most_rows(A.capacity, A.n_rows, d_n_rows != nullptr);
+  if (most < 1) return 0;
+  HIPCHK(p, hipSetDevice(p->device));
+  if (most > ROLLOUT_TICK)
+    hipLaunchKernelGGL(k_rollout_qp<ROLLOUT_TILE>, dim3(B), dim3(ROLLOUT_TILE), 0, (hipStream_t)stream_, p->d_sp, A, F, Q, d_nodes, d_t0,
+                       d_first_row, d_n_rows, d_cursor, d_joint, d_mass_scale, d_push, d_state, d_count, d_word, d_meas, d_rows, d_frows,
+                       d_qrows, d_status, B);
+  else
+    hipLaunchKernelGGL(k_rollout_qp<ROLLOUT_TICK>, dim3(B), dim3(ROLLOUT_TICK), 0, (hipStream_t)stream_, p->d_sp, A, F, Q, d_nodes, d_t0,
+                       d_first_row, d_n_rows, d_cursor, d_joint, d_mass_scale, d_push, d_state, d_count, d_word, d_meas, d_rows, d_frows,
+                       d_qrows, d_status, B);
+  HIPCHK(p, hipGetLastError());
+  return 0;
+}
+
+int qtos_rollout_qp(QtosPlanner *p, int B, const QtosRolloutQp *s, const double *nodes, const double *t0, const int *first_row,
+                    const int *n_rows, const long long *cursor, const double *joint, const double *mass_scale, const double *push,
+                    double *state, long long *count, int *word, double *meas, double *rows_out, double *frows, double *qrows, int *status) {
+  RolloutArgs A;
+  FeetArgs F;
+  QpArgs Q;
+  if (rollout_qp_args(p, B, s, nodes, t0, cursor, state, count, word, meas, status, &A, &F, &Q)) return -1;
+  HIPCHK(p, hipSetDevice(p->device));
+  const size_t rows = segment_elems(B, A.capacity, A.n_rows);
+  const size_t mcols = (A.flags & QTOS_ROLLOUT_QUAT) ? 19 : 18;
+  Staging S(p);
+  const double *d_nodes = S.in(nodes, (size_t)B * p->M.n_vars), *d_t0 = S.in(t0, B);
+  const int *d_first = S.in(first_row, B), *d_n = S.in(n_rows, B);
+  const long long *d_cur = S.in(cursor, B);
+  const double *d_joint = S.in(joint, rows * QTOS_CSV_COLS), *d_ms = S.in(mass_scale, B), *d_push = S.in(push, (size_t)B * 6);
+  double *d_state = S.inout(state, (size_t)B * 13);
+  long long *d_count = S.inout(count, B);
+  int *d_word = S.inout(word, B);
+  double *d_meas = S.inout(meas, rows * mcols), *d_rows = S.inout(rows_out, rows * ROLLOUT_COLS), *d_frows = S.inout(frows, rows * FEET_COLS);
+  double *d_qrows = S.inout(qrows, rows * QP_COLS);
+  int *d_st = S.inout(status, rows);
+  if (S.rc) return S.rc;
+  const int rc = qtos_rollout_qp_device(p, B, s, d_nodes, d_t0, d_first, d_n, d_cur, d_joint, d_ms, d_push, d_state, d_count, d_word, d_meas,
+                                        d_rows, d_frows, d_qrows, d_st, nullptr);
+  return rc ? rc : S.download();
+}
+
 // ---- goals of receding windows from their global paths (k_path_goal, window_kernels.hpp) ------------------------
 // The argument checks of both forms, and QtosPathGoal as k_path_goal reads it.
 static int path_goal_args(const QtosPlanner *p, int B, const QtosPathGoal *g, const void *knots, const void *coef, const void *n_pieces,

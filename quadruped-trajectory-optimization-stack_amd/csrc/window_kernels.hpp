@@ -1624,6 +1624,7 @@ __device__ inline void qp_grad(const QpFoot Ft[NEE], const double rho[6], double
   }
 }
 // K = H + G^T diag(z / s) G into the lane's slab (the lower triangle, row by row), then its unpivoted Cholesky in place.
+template <int STRIDE = QP_TILE>
 __device__ inline void qp_factor(const QpFoot Ft[NEE], double c, double mu, const double s[NEE][6], const double z[NEE][6], double *K) {
 #pragma clang fp contract(off)
 #pragma unroll
@@ -1664,47 +1665,48 @@ __device__ inline void qp_factor(const QpFoot Ft[NEE], double c, double mu, cons
           }
           double k = both ? v : (e == e2 && i == j ? 1.0 : 0.0);
           if (e == e2 && Ft[e].on) k = k + blk[i][j];
-          K[qp_ix(3 * e + i, 3 * e2 + j) * QP_TILE] = k;
+          K[qp_ix(3 * e + i, 3 * e2 + j) * STRIDE] = k;
         }
     }
   }
   for (int j = 0; j < 12; ++j) {
-    double acc = K[qp_ix(j, j) * QP_TILE];
+    double acc = K[qp_ix(j, j) * STRIDE];
     for (int k = 0; k < j; ++k) {
-      const double l = K[qp_ix(j, k) * QP_TILE];
+      const double l = K[qp_ix(j, k) * STRIDE];
       acc = acc - l * l;
     }
     const double ljj = sqrt(acc);
-    K[qp_ix(j, j) * QP_TILE] = ljj;
+    K[qp_ix(j, j) * STRIDE] = ljj;
     for (int i = j + 1; i < 12; ++i) {
-      double a = K[qp_ix(i, j) * QP_TILE];
-      for (int k = 0; k < j; ++k) a = a - K[qp_ix(i, k) * QP_TILE] * K[qp_ix(j, k) * QP_TILE];
-      K[qp_ix(i, j) * QP_TILE] = a / ljj;
+      double a = K[qp_ix(i, j) * STRIDE];
+      for (int k = 0; k < j; ++k) a = a - K[qp_ix(i, k) * STRIDE] * K[qp_ix(j, k) * STRIDE];
+      K[qp_ix(i, j) * STRIDE] = a / ljj;
     }
   }
 }
 // v = K^-1 v with the factor in the slab: v is the slab's entries 78 .. 89, in place.
+template <int STRIDE = QP_TILE>
 __device__ inline void qp_backsolve(double *K, double v[NEE][3]) {
 #pragma clang fp contract(off)
-  double *V = K + 78 * QP_TILE;
+  double *V = K + 78 * STRIDE;
 #pragma unroll
   for (int e = 0; e < NEE; ++e)
 #pragma unroll
-    for (int i = 0; i < 3; ++i) V[(3 * e + i) * QP_TILE] = v[e][i];
+    for (int i = 0; i < 3; ++i) V[(3 * e + i) * STRIDE] = v[e][i];
   for (int i = 0; i < 12; ++i) {
-    double acc = V[i * QP_TILE];
-    for (int k = 0; k < i; ++k) acc = acc - K[qp_ix(i, k) * QP_TILE] * V[k * QP_TILE];
-    V[i * QP_TILE] = acc / K[qp_ix(i, i) * QP_TILE];
+    double acc = V[i * STRIDE];
+    for (int k = 0; k < i; ++k) acc = acc - K[qp_ix(i, k) * STRIDE] * V[k * STRIDE];
+    V[i * STRIDE] = acc / K[qp_ix(i, i) * STRIDE];
   }
   for (int i = 11; i >= 0; --i) {
-    double acc = V[i * QP_TILE];
-    for (int k = i + 1; k < 12; ++k) acc = acc - K[qp_ix(k, i) * QP_TILE] * V[k * QP_TILE];
-    V[i * QP_TILE] = acc / K[qp_ix(i, i) * QP_TILE];
+    double acc = V[i * STRIDE];
+    for (int k = i + 1; k < 12; ++k) acc = acc - K[qp_ix(k, i) * STRIDE] * V[k * STRIDE];
+    V[i * STRIDE] = acc / K[qp_ix(i, i) * STRIDE];
   }
 #pragma unroll
   for (int e = 0; e < NEE; ++e)
 #pragma unroll
-    for (int i = 0; i < 3; ++i) v[e][i] = V[(3 * e + i) * QP_TILE];
+    for (int i = 0; i < 3; ++i) v[e][i] = V[(3 * e + i) * STRIDE];
 }
 // Foot e's six rows of a step dx: ds = -G dx, dz = t - (z / s) ds (t = -z for the predictor, rc / s for the combined step).
 __device__ inline void qp_foot_step(const QpFoot &F, double mu, const double dx[3], const double s[6], const double z[6], const double t[6],
@@ -1719,6 +1721,8 @@ __device__ inline void qp_foot_step(const QpFoot &F, double mu, const double dx[
   }
 }
 // The limited path of a row (force_qp.solve_rows): x, s, z of the last iterate, the residuals it stopped at; returns the steps.
+// STRIDE: the distance between two entries of the lane's slab K (QP_TILE: k_force_qp's lanes side by side; 1: a slab of one lane's own).
+template <int STRIDE = QP_TILE>
 __device__ inline int qp_solve(const QpFoot Ft[NEE], const double rho[6], double c, double m, const QpArgs &Q, const double xfit[NEE][3],
                                double *K, double x[NEE][3], double s[NEE][6], double z[NEE][6], double &comp, double &rdn, bool &cap) {
 #pragma clang fp contract(off)
@@ -1807,7 +1811,7 @@ __device__ inline int qp_solve(const QpFoot Ft[NEE], const double rho[6], double
     comp = comp_now; rdn = rd_now;
     if (comp_now <= QP_CTOL && rd_now <= QP_RTOL * (1.0 + qinf)) break;
     if (it >= max_iter) { cap = true; break; }
-    qp_factor(Ft, c, mu, s, z, K);
+    qp_factor<STRIDE>(Ft, c, mu, s, z, K);
     double t[NEE][6], dx[NEE][3];
     double target = mu_end;
     const bool pred = muk > 10.0 * mu_end;
@@ -1816,7 +1820,7 @@ __device__ inline int qp_solve(const QpFoot Ft[NEE], const double rho[6], double
       for (int e = 0; e < NEE; ++e)
 #pragma unroll
         for (int i = 0; i < 3; ++i) dx[e][i] = -grad[e][i];
-      qp_backsolve(K, dx);
+      qp_backsolve<STRIDE>(K, dx);
       double rs = inf, rz = inf;
 #pragma unroll
       for (int e = 0; e < NEE; ++e)
@@ -1863,7 +1867,7 @@ __device__ inline int qp_solve(const QpFoot Ft[NEE], const double rho[6], double
         for (int i = 0; i < 3; ++i) dx[e][i] = -(rd[e][i] + gt[i]);
       }
     }
-    qp_backsolve(K, dx);
+    qp_backsolve<STRIDE>(K, dx);
     double rs = inf, rz = inf;
 #pragma unroll
     for (int e = 0; e < NEE; ++e)
@@ -2180,6 +2184,7 @@ __global__ __launch_bounds__(QP_TILE) void k_force_qp(const SamplePlan *Sd, FitA
 // the tick.  No atomics, no scratch, every barrier uniform.
 constexpr int FEET_COLS = 16;
 constexpr int FEET_PITCH = 67;
+constexpr int ROLLQP_PITCH = 75, ROLLQP_Q = 67;              // k_rollout_qp's row (below): the solve's 8 columns behind the feet's places
 constexpr int FEET_P = 20, FEET_F = 32, FEET_W = 44, FEET_MASK = 48, FEET_STATE = 49, FEET_STATUS = 65;   // places in a row of the tile
 struct FeetArgs {   // QtosRolloutFeet's own fields as the kernel reads them (window_api.hpp rollout_feet_args)
   double arm, damping, w_min, mu, f_max;
@@ -2187,6 +2192,14 @@ struct FeetArgs {   // QtosRolloutFeet's own fields as the kernel reads them (wi
   int limit;
 };
 struct FeetOut { double fa[12], miss_f, miss_t, change; };   // columns 1 .. 15 of a feet row
+// What a step of the rollout with the force QP (k_rollout_qp, below) adds: the solve's eight columns, its two bits, and where the
+// chain lane keeps K and the solves' vector -- 90 doubles of LDS at stride 1.
+struct FeetQp {
+  const QpArgs *Q;
+  double *slab;
+  double col[QP_COLS];
+  bool limited, cap;
+};
 
 // The feet of a plan row c (37 columns) into the row's place d of the tile: p_e, f_e, the load weights w_e from the vertical
 // components of the stance feet's forces and the stance mask (rollout_feet.plan_feet).
@@ -2214,9 +2227,12 @@ __device__ inline void feet_inputs(const double *c, int mask, double w_min, doub
 }
 
 // One step of length A.h under the row p of the tile (rollout_feet.step); returns |F_fb|.  o: the applied forces and what the
-// feet did not deliver, of this step.
+// feet did not deliver, of this step.  QP (rollout_qp.step, k_rollout_qp): the stance forces are the fit's where those lie inside
+// the limits and the central point of force_qp.py's barrier problem where they do not, in place of the comparisons; qp: the
+// solve's columns and bits of this step.
+template <bool QP = false>
 __device__ inline double rollout_feet_step(const RolloutArgs &A, const FeetArgs &Ft, const RolloutBody &M, const double *p, bool push,
-                                           RolloutState &s, bool &clipped, bool &limited, FeetOut &o) {
+                                           RolloutState &s, bool &clipped, bool &limited, FeetOut &o, FeetQp *qp = nullptr) {
 #pragma clang fp contract(off)
   double e[3], b[3], R[9], c[3];
   rollout_feedback(A, p, s, e, b, R, c, clipped);
@@ -2251,6 +2267,69 @@ __device__ inline double rollout_feet_step(const RolloutArgs &A, const FeetArgs 
     fit_solve<FitExact>(K, rhs, y);
   }
   double Fa[3] = {0, 0, 0}, ta[3] = {0, 0, 0}, gF[3] = {0, 0, 0}, gT[3] = {0, 0, 0}, sq = 0;
+  [[maybe_unused]] double xq[NEE][3];
+  [[maybe_unused]] bool qp_path = false;
+  if constexpr (QP) {                                          // the path and, on the limited one, the QP's x in place of df
+    const QpArgs &Qa = *qp->Q;
+    QpFoot Fq[NEE];
+    double xfit[NEE][3], sl[NEE][6], zl[NEE][6];
+    bool inside = true;
+#pragma unroll
+    for (int k = 0; k < NEE; ++k) {
+      const double *dk = d + 3 * k;
+      QpFoot &F = Fq[k];
+      F.on = (mask >> k) & 1;
+      F.w = p[FEET_W + k];
+      F.d[0] = dk[0]; F.d[1] = dk[1]; F.d[2] = dk[2];
+      F.f[0] = ff * p[FEET_F + 3 * k]; F.f[1] = ff * p[FEET_F + 3 * k + 1]; F.f[2] = ff * p[FEET_F + 3 * k + 2];
+      qp_basis(0.0, 0.0, F.B);                                 // (the rollout reads no terrain)
+      xfit[k][0] = 0; xfit[k][1] = 0; xfit[k][2] = 0;
+#pragma unroll
+      for (int r = 0; r < 6; ++r) { sl[k][r] = NAN; zl[k][r] = 0.0; }
+      if (F.on) {
+        xfit[k][0] = ((y[1] * dk[2] - y[2] * dk[1]) + y[3]) * F.w;
+        xfit[k][1] = ((y[2] * dk[0] - y[0] * dk[2]) + y[4]) * F.w;
+        xfit[k][2] = ((y[0] * dk[1] - y[1] * dk[0]) + y[5]) * F.w;
+        const double fit[3] = {F.f[0] + xfit[k][0], F.f[1] + xfit[k][1], F.f[2] + xfit[k][2]};
+        double gv[6];
+        qp_gmul(F.B, Qa.mu, fit, gv);
+#pragma unroll
+        for (int r = 0; r < 6; ++r) {
+          const double val = gv[r] - (r == 1 ? Qa.f_max : 0.0);
+          if (!(val <= 0)) inside = false;                     // (a NaN takes the limited path and runs into the cap)
+          sl[k][r] = -val;
+        }
+      }
+    }
+    qp_path = cnt > 0 && !inside;
+#pragma unroll
+    for (int c = 0; c < QP_COLS; ++c) qp->col[c] = 0.0;
+    qp->limited = qp_path; qp->cap = false;
+    if (qp_path) {
+      double comp, rdn, dsq;
+      const double cq = Ft.damping * (double)cnt;
+      const int steps = qp_solve<1>(Fq, rhs, cq, 6.0 * (double)cnt, Qa, xfit, qp->slab, xq, sl, zl, comp, rdn, qp->cap);
+      const double gap = qp_gap(Fq, rhs, cq, xfit, xq, dsq);
+      qp->col[0] = (double)steps; qp->col[1] = comp; qp->col[2] = rdn; qp->col[5] = sqrt(dsq); qp->col[6] = gap;
+    }
+    if (cnt > 0) {
+      double smin = INFINITY, zmax = 0;
+      int n_act = 0;
+#pragma unroll
+      for (int k = 0; k < NEE; ++k)
+        if (Fq[k].on) {
+#pragma unroll
+          for (int r = 0; r < 6; ++r) {
+            smin = sl[k][r] < smin ? sl[k][r] : smin;          // (by comparisons: numpy's min; a NaN is not taken here, the
+            zmax = zl[k][r] > zmax ? zl[k][r] : zmax;          //  row it belongs to ends at the cap and is frozen behind it)
+            if (sl[k][r] <= Qa.act_tol) ++n_act;
+          }
+        }
+      qp->col[3] = smin; qp->col[7] = (double)n_act;
+      if (qp_path) qp->col[4] = zmax;
+    }
+    limited = limited || qp_path;
+  }
 #pragma unroll
   for (int k = 0; k < NEE; ++k) {
     const bool on = (mask >> k) & 1;
@@ -2262,7 +2341,9 @@ __device__ inline double rollout_feet_step(const RolloutArgs &A, const FeetArgs 
       a0 = f0 + ((y[1] * dk[2] - y[2] * dk[1]) + y[3]) * w;
       a1 = f1 + ((y[2] * dk[0] - y[0] * dk[2]) + y[4]) * w;
       a2 = f2 + ((y[0] * dk[1] - y[1] * dk[0]) + y[5]) * w;
-      if (Ft.limit) {                                          // by comparisons only: a NaN stays a NaN
+      if constexpr (QP) {
+        if (qp_path) { a0 = f0 + xq[k][0]; a1 = f1 + xq[k][1]; a2 = f2 + xq[k][2]; }
+      } else if (Ft.limit) {                                   // by comparisons only: a NaN stays a NaN
         if (a2 < 0) { a2 = 0.0; limited = true; }
         if (Ft.f_max > 0 && a2 > Ft.f_max) { a2 = Ft.f_max; limited = true; }
         const double lim = Ft.mu * a2;
@@ -2292,6 +2373,8 @@ __device__ inline double rollout_feet_step(const RolloutArgs &A, const FeetArgs 
   return rollout_norm(b[0], b[1], b[2]);
 }
 
+// (k_rollout_qp, below, carries a twin of this kernel's text -- INIT / PENDING, the freeze, phases (A) and (C), the write-out --
+// with its own pitch, step and solve table: a change here belongs there too.)
 template <int TILE>
 __global__ __launch_bounds__(TILE) void k_rollout_feet(const SamplePlan *Sd, RolloutArgs A, FeetArgs Ft, const double *nodes, const double *t0,
                                                        const int *first_row, const int *n_rows, const long long *cursor,
@@ -2427,6 +2510,185 @@ __global__ __launch_bounds__(TILE) void k_rollout_feet(const SamplePlan *Sd, Rol
     for (int e = threadIdx.x; e < m * mcols; e += TILE) {                          // ... and meas
       const int i = e / mcols, c = e - i * mcols;
       const double *p = feet_tile + i * FEET_PITCH;
+      const long long o = G.flat(base, mcols, e);
+      if (c < 3) meas_b[o] = p[1 + c];
+      else if (c < mcols - 12) meas_b[o] = quat ? p[13 + (c - 3)] : p[4 + (c - 3)];
+      else if (joint_b) meas_b[o] = joint_b[(size_t)G.tile_row(base, i) * QTOS_CSV_COLS + 1 + (c - (mcols - 12))];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    double *sb = state + (size_t)b * 13;
+    sb[0] = s.r0; sb[1] = s.r1; sb[2] = s.r2; sb[3] = s.v0; sb[4] = s.v1; sb[5] = s.v2;
+    sb[6] = s.qx; sb[7] = s.qy; sb[8] = s.qz; sb[9] = s.qw; sb[10] = s.w0; sb[11] = s.w1; sb[12] = s.w2;
+    count[b] = calls + n;
+    word_io[b] = word;
+  }
+}
+
+// Rollout with the force QP (qtos_rollout_qp*; the rule: rollout_qp.py): k_rollout_feet with k_force_qp's limited path in place of
+// its comparisons, in every step of the chain.  The phases (A), (B), (C) and the flat write-out are k_rollout_feet's; the chain on
+// lane 0 reuses rollout_feedback, rollout_advance, fit_solve<FitExact> and the qp_* functions (one copy of each: the iteration is
+// k_force_qp's, instantiated at stride 1 on a slab of the chain lane's own, QP_SLAB = 90 doubles).  A row of the tile grows by the
+// solve's 8 columns of the tick's first step, places 67 .. 74: ROLLQP_PITCH = 75 doubles (odd, as FEET_PITCH is), so 256 x 75 x 8 +
+// 720 = 154 320 bytes of LDS for the table's instantiation, under the 160 KB of a gfx950 workgroup, and 64 x 75 x 8 + 720 = 39 120
+// for the tick's.  Contraction is off in every function of the chain; every loop has a fixed bound (at most QP_MAX_ITER steps of
+// 12 columns); no atomics; every barrier uniform.  The lanes beside the chain wait at the barrier: a tick costs the chain's latency
+// on one lane, one f64 operation after the other.  The text below is k_rollout_feet's but for the pitch, the step and the solve's
+// table (a body shared by both kernels changed k_rollout_feet's register allocation): a change to one belongs
+// in the other.
+template <int TILE>
+__global__ __launch_bounds__(TILE) void k_rollout_qp(const SamplePlan *Sd, RolloutArgs A, FeetArgs Ft, QpArgs Q, const double *nodes,
+                                                     const double *t0, const int *first_row, const int *n_rows, const long long *cursor,
+                                                     const double *joint, const double *mass_scale, const double *push, double *state,
+                                                     long long *count, int *word_io, double *meas, double *rows_out, double *frows_out,
+                                                     double *qrows_out, int *status_out, int B) {
+  __shared__ double rollqp_tile[TILE * ROLLQP_PITCH];
+  __shared__ double rollqp_slab[QP_SLAB];                                           // (K and the solves' vector of the chain lane, at stride 1)
+  const int b = blockIdx.x;
+  if (b >= B) return;
+  const SamplePlan &S = *Sd;
+  const bool quat = (A.flags & 2) != 0;
+  const int mcols = quat ? 19 : 18;
+  RolloutState s;                                                                  // (every lane, in front of the first barrier)
+  {
+    const double *sb = state + (size_t)b * 13;
+    s.r0 = sb[0]; s.r1 = sb[1]; s.r2 = sb[2]; s.v0 = sb[3]; s.v1 = sb[4]; s.v2 = sb[5];
+    s.qx = sb[6]; s.qy = sb[7]; s.qz = sb[8]; s.qw = sb[9]; s.w0 = sb[10]; s.w1 = sb[11]; s.w2 = sb[12];
+  }
+  const long long calls = count[b];
+  int word = word_io[b];
+  RolloutBody M;
+  {
+#pragma clang fp contract(off)
+    const double ms = mass_scale ? mass_scale[b] : 1.0;
+    M.m_s = A.mass * ms;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) { M.I[i] = ms * A.Ib[i]; M.J[i] = A.Ii[i] / ms; }
+    const double *pb = push ? push + (size_t)b * 6 : nullptr;
+    M.F0 = pb ? pb[0] : 0.0; M.F1 = pb ? pb[1] : 0.0; M.F2 = pb ? pb[2] : 0.0;
+    M.T0 = pb ? pb[3] : 0.0; M.T1 = pb ? pb[4] : 0.0; M.T2 = pb ? pb[5] : 0.0;
+  }
+  const RowSegment G = RowSegment::of(A.capacity, A.n_rows, A.first_row, n_rows, first_row, cursor, b);
+  const long long rows_b = G.rows_b, n = G.n;
+  if (n == 0) return;                                                              // (uniform: a window without rows keeps its state)
+  const double *x = nodes + (size_t)b * S.n_vars;
+  const double t0b = t0[b];
+  double *meas_b = meas + (size_t)b * (size_t)rows_b * mcols;
+  double *out_b = rows_out ? rows_out + (size_t)b * (size_t)rows_b * ROLLOUT_COLS : nullptr;
+  double *feet_b = frows_out ? frows_out + (size_t)b * (size_t)rows_b * FEET_COLS : nullptr;
+  double *qp_b = qrows_out ? qrows_out + (size_t)b * (size_t)rows_b * QP_COLS : nullptr;
+  const double *joint_b = joint ? joint + (size_t)b * (size_t)rows_b * QTOS_CSV_COLS : nullptr;
+  for (long long j0 = 0; j0 < n; j0 += TILE) {                                     // (n is uniform over the workgroup: so are the barriers)
+    const int m = G.tile_rows(j0, TILE);
+    const long long base = G.row(j0);
+    if ((int)threadIdx.x < m) {                                                    // (A) a lane takes a row of the plan
+      double row[QTOS_CSV_COLS];
+      const double t = sample_row_state_at(S, x, t0b, G.plan_row(j0, threadIdx.x), A.hz, row);
+      int mask = 0;
+#pragma unroll
+      for (int e = 0; e < NEE; ++e) {
+        sample_spline(S.eef[e], x, t, 0, row + 25 + 3 * e);
+        mask |= (Ft.stance[e][sample_segment(S.eem[e], t)] != 0 ? 1 : 0) << e;
+      }
+      double *dst = rollqp_tile + threadIdx.x * ROLLQP_PITCH;
+      rollout_inputs(row, A.ff_scale, dst);
+      feet_inputs(row, mask, Ft.w_min, dst);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {                                                        // (B) the chain, in program order
+#pragma clang fp contract(off)
+      if (j0 == 0 && ((A.flags & 1) || (word & 32))) {                             // QTOS_ROLLOUT_INIT / _PENDING, as in k_rollout
+        word &= ~32;
+        const double *p = rollqp_tile;
+        s.r0 = p[1]; s.r1 = p[2]; s.r2 = p[3]; s.v0 = p[4]; s.v1 = p[5]; s.v2 = p[6];
+        s.qx = p[7]; s.qy = p[8]; s.qz = p[9]; s.qw = p[10];
+        const double qx = s.qx, qy = s.qy, qz = s.qz, qw = s.qw;
+        const double R0 = 1 - 2 * (qy * qy + qz * qz), R1 = 2 * (qx * qy - qz * qw), R2 = 2 * (qx * qz + qy * qw);
+        const double R3 = 2 * (qx * qy + qz * qw), R4 = 1 - 2 * (qx * qx + qz * qz), R5 = 2 * (qy * qz - qx * qw);
+        const double R6 = 2 * (qx * qz - qy * qw), R7 = 2 * (qy * qz + qx * qw), R8 = 1 - 2 * (qx * qx + qy * qy);
+        s.w0 = (R0 * p[11] + R3 * p[12]) + R6 * p[13];
+        s.w1 = (R1 * p[11] + R4 * p[12]) + R7 * p[13];
+        s.w2 = (R2 * p[11] + R5 * p[12]) + R8 * p[13];
+      }
+      for (int i = 0; i < m; ++i) {
+        double *p = rollqp_tile + i * ROLLQP_PITCH;
+        double ex, ey, ez, ew;
+        rollout_attitude(p, s, ex, ey, ez, ew);
+        const double en = rollout_norm(s.r0 - p[1], s.r1 - p[2], s.r2 - p[3]);
+        const double tilt = 2 * rollout_norm(ex, ey, ez);
+        const bool finite = isfinite(s.r0) && isfinite(s.r1) && isfinite(s.r2) && isfinite(s.v0) && isfinite(s.v1) && isfinite(s.v2) &&
+                            isfinite(s.qx) && isfinite(s.qy) && isfinite(s.qz) && isfinite(s.qw) && isfinite(s.w0) && isfinite(s.w1) &&
+                            isfinite(s.w2);
+        if (!finite) word |= 2;
+        if ((A.dev_max > 0 && en > A.dev_max) || (A.tilt_max > 0 && tilt > A.tilt_max)) word |= 1;
+        int st = word & 3;
+        double *q = p + FEET_STATE;
+        q[0] = s.r0; q[1] = s.r1; q[2] = s.r2; q[3] = s.v0; q[4] = s.v1; q[5] = s.v2;
+        q[6] = s.qx; q[7] = s.qy; q[8] = s.qz; q[9] = s.qw; q[10] = s.w0; q[11] = s.w1; q[12] = s.w2;
+        q[13] = en; q[14] = tilt;
+        const int mask = (int)p[FEET_MASK];
+        const int cnt = (mask & 1) + ((mask >> 1) & 1) + ((mask >> 2) & 1) + ((mask >> 3) & 1);
+        int feet_bits = (cnt == 0 ? 64 : 0) | (cnt == 2 ? 128 : 0);
+        double fbn = 0;
+        if (!st) {
+          const long long c = calls + j0 + i;
+          const bool acts = push != nullptr && c >= A.push_from && c - A.push_from < A.push_ticks;
+          bool clipped = false, limited = false;
+          FeetOut first;
+          FeetQp q1, q2;
+          q1.Q = &Q; q1.slab = rollqp_slab; q2.Q = &Q; q2.slab = rollqp_slab;
+          fbn = rollout_feet_step<true>(A, Ft, M, p, acts, s, clipped, limited, first, &q1);
+          bool cap = q1.cap;
+          for (int u = 1; u < A.substeps; ++u) {
+            FeetOut later;
+            rollout_feet_step<true>(A, Ft, M, p, acts, s, clipped, limited, later, &q2);
+            cap = cap || q2.cap;
+          }
+#pragma unroll
+          for (int k = 0; k < QP_COLS; ++k) p[ROLLQP_Q + k] = q1.col[k];           // (the solve's columns of the tick's first step)
+          feet_bits |= cap ? 512 : 0;
+#pragma unroll
+          for (int k = 0; k < 12; ++k) p[FEET_F + k] = first.fa[k];               // (behind the tick's last step: it read f_e and w_e)
+          p[FEET_W] = first.miss_f; p[FEET_W + 1] = first.miss_t; p[FEET_W + 2] = first.change;
+          st = (clipped ? 8 : 0) | (acts ? 16 : 0) | (limited ? 256 : 0);
+        } else {
+          p[FEET_W] = 0.0; p[FEET_W + 1] = 0.0; p[FEET_W + 2] = 0.0;             // a frozen row: the plan's forces stay in their place
+#pragma unroll
+          for (int k = 0; k < QP_COLS; ++k) p[ROLLQP_Q + k] = 0.0;
+        }
+        q[15] = fbn; p[FEET_STATUS] = (double)(st | feet_bits);
+      }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < m) {                                                    // (C) a lane turns its row's state into the output columns
+      double *p = rollqp_tile + threadIdx.x * ROLLQP_PITCH;
+      const int st = (int)p[FEET_STATUS] | rollout_output<FEET_STATE>(p);
+      status_out[(size_t)b * (size_t)rows_b + G.tile_row(base, threadIdx.x)] = st;
+    }
+    __syncthreads();
+    if (out_b) {                                                                   // the tile goes out flat: rows ...
+      for (int e = threadIdx.x; e < m * ROLLOUT_COLS; e += TILE) {
+        const int i = e / ROLLOUT_COLS, c = e - i * ROLLOUT_COLS;
+        out_b[G.flat(base, ROLLOUT_COLS, e)] = rollqp_tile[i * ROLLQP_PITCH + c];
+      }
+    }
+    if (feet_b) {                                                                  // ... the feet rows ...
+      for (int e = threadIdx.x; e < m * FEET_COLS; e += TILE) {
+        const int i = e / FEET_COLS, c = e - i * FEET_COLS;
+        const double *p = rollqp_tile + i * ROLLQP_PITCH;
+        feet_b[G.flat(base, FEET_COLS, e)] = c == 0 ? p[0] : (c < 13 ? p[FEET_F + (c - 1)] : p[FEET_W + (c - 13)]);
+      }
+    }
+    if (qp_b) {                                                                    // ... the solve's columns ...
+      for (int e = threadIdx.x; e < m * QP_COLS; e += TILE) {
+        const int i = e / QP_COLS, c = e - i * QP_COLS;
+        qp_b[G.flat(base, QP_COLS, e)] = rollqp_tile[i * ROLLQP_PITCH + ROLLQP_Q + c];
+      }
+    }
+    for (int e = threadIdx.x; e < m * mcols; e += TILE) {                          // ... and meas
+      const int i = e / mcols, c = e - i * mcols;
+      const double *p = rollqp_tile + i * ROLLQP_PITCH;
       const long long o = G.flat(base, mcols, e);
       if (c < 3) meas_b[o] = p[1 + c];
       else if (c < mcols - 12) meas_b[o] = quat ? p[13 + (c - 3)] : p[4 + (c - 3)];

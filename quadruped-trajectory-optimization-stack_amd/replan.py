@@ -240,6 +240,12 @@ class ShiftedWindows:
                feedback wrench is delivered through the stance feet, optionally limited to what a foot can do, and
                ``self.rollout_feet_traj`` (B x trajectory x 16: applied forces, what the feet did not deliver) is filled beside the
                other rings; ``rollout_feet_rows(b)`` reads a window's.  Without ``feet`` nothing of it is allocated or queued.
+               ``feet=dict(..., limit="qp", mu_end=, act_tol=, max_iter=)`` (``capi.rollout_qp_params``' keywords) queues
+               k_rollout_qp (qtos_rollout_qp_device, the rule: ``rollout_qp.rollout_qp_rows``) in place of k_rollout_feet, with the
+               same carried arrays: every step's stance forces are the fit's where those obey the limits and the pyramid QP's
+               where they do not; ``self.rollout_qp_traj`` (B x trajectory x 8, the solve's columns of every tick's first step) is
+               filled as well, and ``rollout_qp_rows(b)`` reads a window's.  ``limit=True / False`` queue and allocate what they
+               did without it.
     check      None (the default): nothing is queued and nothing is allocated.  A ``capi.check_params(...)`` (needs
                ``trajectory``; its tol is read, its rate and rows are the stitch's): k_plan_check (qtos_plan_check_device, the
                rule: ``plan_check.check_rows`` / ``summarise`` / ``accumulate``) is queued in front of every stitch and in
@@ -361,12 +367,19 @@ class ShiftedWindows:
             self.rollout_traj = torch.zeros((B, int(trajectory), capi.ROLLOUT_COLS), **f64) if keep else None
             up = lambda a, shape: None if a is None else torch.as_tensor(np.broadcast_to(np.asarray(a, np.float64), shape).copy(), **f64)
             self._rollout_scale, self._rollout_push = up(scale, (B,)), up(push, (B, 6))
-            self._feet = None
+            self._feet, self._feet_qp = None, False
             if feet is not None:
                 planner._need("qtos_rollout_feet_device", "feet rollout kernel")
                 fk = dict(feet)
                 fk.setdefault("cfg", kw["cfg"])
-                self._feet = capi.rollout_feet_params(**fk)                  # (its body is the call's QtosRollout, put in by _rollout_rows)
+                self._feet_qp = fk.get("limit") == "qp"
+                if self._feet_qp:                                            # (k_rollout_qp in place of k_rollout_feet)
+                    planner._need("qtos_rollout_qp_device", "QP rollout kernel")
+                    del fk["limit"]
+                    self._feet = capi.rollout_qp_params(**fk)
+                    self.rollout_qp_traj = torch.zeros((B, int(trajectory), capi.ROLLOUT_QP_COLS), **f64)
+                else:
+                    self._feet = capi.rollout_feet_params(**fk)              # (its body is the call's QtosRollout, put in by _rollout_rows)
                 self.rollout_feet_traj = torch.zeros((B, int(trajectory), capi.ROLLOUT_FEET_COLS), **f64)
         self._feedback = None
         if feedback is not None:
@@ -594,7 +607,18 @@ class ShiftedWindows:
         ring's rows of the segment (the joint columns from the joint ring where ``joints`` is on).  A window's first call with
         rows sets its state from the plan's row: ``rollout_word`` starts as QTOS_ROLLOUT_PENDING, which the kernel spends per
         window, so a window whose hand-over row is 0 at the set's first replan is set on its plan by a later one.  With ``feet``
-        k_rollout_feet is queued in its place, with the same carried arrays, and fills ``rollout_feet_traj`` as well."""
+        k_rollout_feet is queued in its place, with the same carried arrays, and fills ``rollout_feet_traj`` as well; with
+        ``limit="qp"`` k_rollout_qp, which fills ``rollout_qp_traj`` too."""
+        if self._feet is not None and self._feet_qp:
+            f = self._feet.with_body(params)
+            self.P._chk(self.P.lib.qtos_rollout_qp_device(self.P.h, self.B, C.byref(f), self.nodes.data_ptr(), self.t0.data_ptr(), None, n_rows,
+                                                          self.cursor.data_ptr(), ptr(self.joint_traj), ptr(self._rollout_scale),
+                                                          ptr(self._rollout_push), self.rollout_state.data_ptr(),
+                                                          self.rollout_count.data_ptr(), self.rollout_word.data_ptr(),
+                                                          self.meas_traj.data_ptr(), ptr(self.rollout_traj),
+                                                          self.rollout_feet_traj.data_ptr(), self.rollout_qp_traj.data_ptr(),
+                                                          self.rollout_status.data_ptr(), sp), "qtos_rollout_qp_device")
+            return
         if self._feet is not None:
             f = self._feet.with_body(params)
             self.P._chk(self.P.lib.qtos_rollout_feet_device(self.P.h, self.B, C.byref(f), self.nodes.data_ptr(), self.t0.data_ptr(), None, n_rows,
@@ -630,6 +654,15 @@ class ShiftedWindows:
             raise RuntimeError("rollout_feet_rows() needs the rollout through the feet (rollout=dict(..., feet=dict(...)))")
         self.stream.synchronize()
         return ring_rows(self.rollout_feet_traj[b].cpu().numpy(), int(self.cursor[b].item()))
+
+    def rollout_qp_rows(self, b):
+        """Window b's newest min(cursor, trajectory) solve rows (8 columns, force_qp.py's QP_COLS, of every tick's first step) in
+        time order, as numpy (the stream is synchronised): row for row with ``rollout_feet_rows(b)``."""
+        from .stitcher import ring_rows
+        if self._rollout is None or self._feet is None or not self._feet_qp:
+            raise RuntimeError("rollout_qp_rows() needs the rollout with the force QP (rollout=dict(..., feet=dict(limit=\"qp\", ...)))")
+        self.stream.synchronize()
+        return ring_rows(self.rollout_qp_traj[b].cpu().numpy(), int(self.cursor[b].item()))
 
     def _start_feedback(self, sp):
         """Queue k_start_feedback behind the track call and in front of the stitch: self.start (and, without a path, self.goal)
